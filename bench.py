@@ -28,6 +28,15 @@ which backend / world size / devices the ranks saw.
 `--seam` selects which side of the drop-in boundary drives the loop: `philox` (default; in-kernel counter-based noise),
 `torch` (the reference caller's own kwargs -- torch's generator, progress=True -- which also run inside libgdx) or
 `stepwise` (the model(x, t, **kw) callable protocol: one Python call + one update launch per step).
+
+A plain run only sets up, warms up, times the K steps and prints the record.  `--full` adds what the headline does not
+need: the in-situ HIP-event timing of the FFN-1 GEMM launches inside the timed region (the record's `roofline` object) and
+the torch-CPU baseline (`cpu_baseline`, `gpu_over_cpu`; `--no-cpu-baseline` drops it again).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed loop returned in its last step: rank 0's gathered
+samples as DIR/samples.npy (float32, [batch, J, 1, T]).  Above 64 MB a fixed subset of whole samples is written instead
+(rows drawn by numpy's default_rng(0), in ascending order).  Weights, conditioning and noise are seeded, so the same
+arguments give the same inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -159,6 +168,22 @@ def cpu_baseline(p, cfg, sd, B, seedp, mfcc, loop_steps, budget_s, full_loops):
             "ms_per_step": sec * 1e3}
 
 
+def dump_outputs(path, arrays, limit=64 << 20):
+    """Write each tensor as path/<name>.npy in float32.  Above `limit` bytes in all, every array keeps the same share of
+    its leading-dimension rows (whole samples), drawn by numpy's default_rng(0) and kept in ascending order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = a.detach().float().cpu()
+        if total > limit:
+            keep = max(1, a.shape[0] * limit // total)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            log(f"dump-outputs: {name} is {a.numel() * 4 / 2**20:.0f} MB; writing {keep} of its {a.shape[0]} rows")
+            a = a[torch.from_numpy(rows)]
+        np.save(os.path.join(path, f"{name}.npy"), a.numpy())
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh children (one per GPU) with the rendezvous environment of
     torch.distributed.run and wait for them.  The parent never initialises the GPU and never re-execs; a child that fails
@@ -211,6 +236,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU work the cpu_baseline leg may spend")
     ap.add_argument("--save-samples", default=None, help="rank 0 writes the gathered samples of the timed run here (torch.save)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the timed run's samples as DIR/samples.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the in-situ FFN-1 GEMM roofline figures and the CPU baseline (off: headline only)")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))       # before anything touches the GPU
@@ -304,9 +333,9 @@ def main():
         run(min(args.warmup, loop_steps))
     barrier()
     log(f"timing {steps} steps ...")
-    eng0 = inner._get_engine(device)
-    if rank == 0:
-        eng0.profile_begin(512)      # HIP events around the first 512 FFN-1 GEMM launches of the timed region
+    if rank == 0 and args.full:
+        # HIP events around the first 512 FFN-1 GEMM launches of the timed region
+        inner._get_engine(device).profile_begin(512)
     t0 = time.perf_counter()
     out = run(steps)
     barrier()
@@ -325,6 +354,8 @@ def main():
         dist.all_gather_object(seen, mine)
     if rank == 0 and args.save_samples:
         torch.save(out.cpu(), args.save_samples)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"samples": out})
 
     nsub = (B + sub - 1) // sub
     ms_per_step = elapsed * 1e3 / steps                  # one step over the rank's whole batch (all its sub-batches)
@@ -337,19 +368,7 @@ def main():
         flops_step = eng.forward_flops(GDX_CFG if p["cfg"] else GDX_COND) * nsub      # prepared shape = one sub-batch
         if B % sub:
             flops_step *= B / (nsub * sub)
-        # dominant kernel = the MFMA GEMM; its north-star instance is FFN linear1 (+bias+GELU):
-        # algorithmic FLOPs per launch = 2 * rows * d * ff, timed with HIP events on the launch stream
-        rows, d, ff = (2 if p["cfg"] else 1) * min(sub, B) * (T + 1), p["d"], 1024
-        gemm_us, gemm_launches = eng.profile_end()
-        gemm_flops = 2.0 * rows * d * ff
         f16 = p["dtype"] in ("fp16", "bf16")
-        traffic, traffic_src = None, None
-        # the PMC passes were taken at the preset's one-GPU shape: a global batch split over several ranks is another GEMM
-        if os.path.exists(TRAFFIC_FILE) and not custom and not (p["global_batch"] and world > 1):
-            ent = json.load(open(TRAFFIC_FILE)).get(args.config)     # PMC passes cannot run inside this process
-            if ent:
-                traffic, traffic_src = ent["hbm_bytes_per_launch"], ent["source"]
-        achieved = gemm_flops / (gemm_us * 1e-6) / 1e12 if gemm_us else 0.0
         peak = F16_MFMA_PEAK_TFLOPS if f16 else F32_MFMA_PEAK_TFLOPS
         loop_name = f"{loop_steps}-step {'p_sample_loop' if p['sampler'] == 'p' else 'ddim_sample_loop'}"
         topo = "MDM_Old (V1 encoder-only topology)" if p["arch"] == "mdm_old" else "MDM (V2: local attention + RoPE)"
@@ -381,16 +400,29 @@ def main():
             "step_tflops": round(world * flops_step / (ms_per_step * 1e-3) / 1e12, 2),
             ("step_frac_of_f16_mfma_peak" if f16 else "step_frac_of_f32_mfma_peak"):
                 round(flops_step / (ms_per_step * 1e-3) / 1e12 / peak, 4),
-            "roofline": {"bound": "mfma", "kernel": ("gemmh kernel (gemmh.hip)" if f16 else "gemm4_kernel (gemm2.hip)") +
-                                                    ", FFN linear1 + bias + GELU, "
-                                                    f"M={rows} N={ff} K={d}; HIP events on the launch stream around "
-                                                    f"{gemm_launches} launches inside the timed loop",
-                         "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "avg_launch_us": round(gemm_us, 2), "flops_per_launch": gemm_flops},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            # dominant kernel = the MFMA GEMM; its north-star instance is FFN linear1 (+bias+GELU):
+            # algorithmic FLOPs per launch = 2 * rows * d * ff, timed with HIP events on the launch stream
+            rows, d, ff = (2 if p["cfg"] else 1) * min(sub, B) * (T + 1), p["d"], 1024
+            gemm_us, gemm_launches = eng.profile_end()
+            gemm_flops = 2.0 * rows * d * ff
+            traffic, traffic_src = None, None
+            # the PMC passes were taken at the preset's one-GPU shape: a global batch split over several ranks is another GEMM
+            if os.path.exists(TRAFFIC_FILE) and not custom and not (p["global_batch"] and world > 1):
+                ent = json.load(open(TRAFFIC_FILE)).get(args.config)     # PMC passes cannot run inside this process
+                if ent:
+                    traffic, traffic_src = ent["hbm_bytes_per_launch"], ent["source"]
+            achieved = gemm_flops / (gemm_us * 1e-6) / 1e12 if gemm_us else 0.0
+            rec["roofline"] = {"bound": "mfma", "kernel": ("gemmh kernel (gemmh.hip)" if f16 else "gemm4_kernel (gemm2.hip)") +
+                                                          ", FFN linear1 + bias + GELU, "
+                                                          f"M={rows} N={ff} K={d}; HIP events on the launch stream around "
+                                                          f"{gemm_launches} launches inside the timed loop",
+                               "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                               "frac": round(achieved / peak, 4), "traffic": traffic,
+                               "traffic_source": traffic_src,
+                               "avg_launch_us": round(gemm_us, 2), "flops_per_launch": gemm_flops}
+        if args.full and not args.no_cpu_baseline and world == 1:
             nb = min(sub, B)
             rec["cpu_baseline"] = cpu_baseline(p, cfg, sd, nb, seedp[:nb], mfcc[:nb], loop_steps, args.cpu_seconds,
                                                full_loops=args.config == "1" and not custom)

@@ -116,6 +116,21 @@ def test_bench_gpus_2_starts_its_own_ranks_and_gathers_the_one_rank_samples(tmp_
     assert a.shape == b.shape == (6, 37, 1, 20) and torch.equal(a, b)
 
 
+def test_bench_plain_run_dumps_its_samples_and_full_adds_the_extras(tmp_path):
+    """A plain run prints the headline record without the roofline / CPU legs and --dump-outputs writes the timed loop's
+    samples; --full adds the roofline object and computes the same samples (the inputs are seeded)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    plain = _bench(["--gpus", "1", "--save-samples", str(tmp_path / "one.pt"), "--dump-outputs", str(tmp_path / "plain")],
+                   env=env)
+    full = _bench(["--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "full")], env=env)
+    assert plain["steps"] == full["steps"] == 3 and plain["ms_per_step"] > 0 and full["ms_per_step"] > 0
+    assert "roofline" not in plain and "cpu_baseline" not in plain
+    assert full["roofline"]["unit"] == "TFLOP/s" and "cpu_baseline" not in full          # SMALL has --no-cpu-baseline
+    a, b = np.load(tmp_path / "plain" / "samples.npy"), np.load(tmp_path / "full" / "samples.npy")
+    assert a.dtype == np.float32 and a.shape == (6, 37, 1, 20)
+    assert np.array_equal(a, torch.load(tmp_path / "one.pt").float().numpy()) and np.array_equal(a, b)
+
+
 def test_bench_refuses_more_ranks_than_samples():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     args = [a if a != "6" else "1" for a in SMALL]

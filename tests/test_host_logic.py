@@ -339,6 +339,26 @@ def test_bench_presets_are_the_baseline_configs():
     assert bench.SCHEDULE_STEPS == 1000 and bench.F32_MFMA_PEAK_TFLOPS == 157.3 and bench.F16_MFMA_PEAK_TFLOPS == 2500.0
 
 
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array as float32 .npy; above the byte cap a seeded subset of whole rows, in ascending
+    order and the same on every call."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x = torch.arange(40 * 3 * 5, dtype=torch.float64).view(40, 3, 1, 5)
+    bench.dump_outputs(str(tmp_path / "all"), {"samples": x})
+    got = np.load(tmp_path / "all" / "samples.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    row = 3 * 5 * 4
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"samples": x}, limit=10 * row + row // 2)
+    a, b = np.load(tmp_path / "a" / "samples.npy"), np.load(tmp_path / "b" / "samples.npy")
+    assert a.shape == (10, 3, 1, 5) and np.array_equal(a, b)
+    rows = a[:, 0, 0, 0].astype(np.int64) // 15
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, x.float().numpy()[rows])
+
+
 
 def test_bench_gpus_n_spawns_its_own_ranks_and_reports_their_failure():
     """`python bench.py --gpus 2` started plainly (no RANK in the environment) must start two ranks itself; on a box without

@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() {   # name, bench arguments
   n=$1; shift
-  rocprofv3 --kernel-trace --stats -d $O/kt_$n -o k -- python3 $R/bench.py "$@" --no-cpu-baseline > $O/kt_$n.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats -d $O/kt_$n -o k -- python3 $R/bench.py --full "$@" --no-cpu-baseline > $O/kt_$n.log 2>&1 || exit 1
   python3 $R/tools/kstats_db.py $O/kt_$n/k_results.db 20 > $O/kernel_stats_$n.txt || exit 1
   tail -1 $O/kt_$n.log | cut -c1-300 >> $O/bench_lines.txt
   echo "$n done" >> $O/progress.txt

@@ -18,13 +18,13 @@ for c in $CONFIGS; do
     genea) B="--config genea"; S="--config genea --steps 100 --warmup 10"; P="--config genea --steps 10 --warmup 2";;
     5b16) B="--config 5 --batch 16 --steps 200 --warmup 20"; S="--config 5 --batch 16 --steps 60 --warmup 10"; P="--config 5 --batch 16 --steps 10 --warmup 2";;
   esac
-  timeout -k 10 400 python3 $R/bench.py $B --no-cpu-baseline > $O/bench_c$c.json 2> $O/bench_c$c.log || exit 1
-  rocprofv3 --kernel-trace --stats -d $O/kt_c$c -o k -- python3 $R/bench.py $S --no-cpu-baseline > $O/kt_c$c.log 2>&1 || exit 1
+  timeout -k 10 400 python3 $R/bench.py --full $B --no-cpu-baseline > $O/bench_c$c.json 2> $O/bench_c$c.log || exit 1
+  rocprofv3 --kernel-trace --stats -d $O/kt_c$c -o k -- python3 $R/bench.py --full $S --no-cpu-baseline > $O/kt_c$c.log 2>&1 || exit 1
   python3 $R/tools/kstats_db.py $O/kt_c$c/k_results.db 24 > $O/kernel_stats_c$c.txt || exit 1
   cat $O/bench_c$c.json >> $O/kernel_stats_c$c.txt
   for ctr in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
     t=$(echo $ctr | cut -d' ' -f1)
-    rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_${t}_c$c -o p -- python3 $R/bench.py $P --no-cpu-baseline > $O/pmc_${t}_c$c.log 2>&1 || exit 1
+    rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_${t}_c$c -o p -- python3 $R/bench.py --full $P --no-cpu-baseline > $O/pmc_${t}_c$c.log 2>&1 || exit 1
   done
   rm -rf $O/kt_c$c
   echo "config $c done" >> $O/progress.txt
