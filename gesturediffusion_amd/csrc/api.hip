@@ -743,6 +743,22 @@ static int gemm(int am, int bm, int om, int ep, const GemmParams& p, hipStream_t
     return 0;
 }
 
+// V2 front end (RoPE -> causal local attention -> RoPE at t+1) for compute dtype `dtype`: the one dispatch of the forwards and
+// of the test entry point gdx_local_attention.  The 16-bit kernel (local_attention_half) reads xseq16 and writes enc16 plus the
+// optional fp32 copy enc; otherwise the fp32 kernel (MFMA, or the scalar one for other head widths / windows) reads xseq and
+// writes enc plus the optional 16-bit copy enc16.
+static bool local_attention_half(int dtype, int d, int heads, int window) {
+    return dtype != GDX_DTYPE_F32 && HFN(dtype == GDX_DTYPE_BF16, local_attention_f16_supported, d, heads, window);
+}
+static hipError_t launch_local_attention_any(int dtype, const float* xseq, const _Float16* xseq16, const float* cosT,
+                                             const float* sinT, float* enc, _Float16* enc16, int B, int T, int d, int heads,
+                                             int window, hipStream_t s) {
+    const bool bf = dtype == GDX_DTYPE_BF16;
+    if (local_attention_half(dtype, d, heads, window))
+        return HFN(bf, launch_local_attention_f16, xseq16, cosT, sinT, enc16, enc, B, T, d, heads, window, s);
+    return HFN(bf, launch_local_attention, xseq, cosT, sinT, enc, enc16, B, T, d, heads, window, s);
+}
+
 // The per-step kernel sequence.  temb: [*, d] rows (row stride tstride, 0 = shared by the batch).
 // Writes x0 for Beff samples into x0_out ([Beff, J, T]).
 static int forward_core_f16(gdx_model* h, const float* x, const float* temb, int tstride, const float* c2t, int mode,
@@ -780,8 +796,8 @@ static int forward_core(gdx_model* h, const float* x, const float* temb, int tst
         if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_BIAS, p, s)) return -1;
         p = GemmParams{h->emb_pose, d, h->proj_pose.w, h->proj_pose.kpad, nullptr, h->addend, d, h->c2, d, h->xseq, d, Beff * T, d, d, T, B};
         if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_RES_VEC, p, s)) return -1;
-        HIPCHK(launch_local_attention(h->xseq, h->rope_cos, h->rope_sin, h->xa, nullptr, Beff, T, d, h->cfg.cl_head,
-                                      h->cfg.window, s));
+        HIPCHK(launch_local_attention_any(GDX_DTYPE_F32, h->xseq, nullptr, h->rope_cos, h->rope_sin, h->xa, nullptr, Beff, T, d,
+                                          h->cfg.cl_head, h->cfg.window, s));
     }
     if (h->keep_taps)
         HIPCHK(hipMemcpyAsync(h->taps[0], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
@@ -860,17 +876,14 @@ static int forward_core_f16(gdx_model* h, const float* x, const float* temb, int
         HIPCHK(HFN(h->bf16, launch_token0, temb, tstride, seed_emb, nullptr, h->xa, h->xa16, c2t, c2s, h->c2, state, Beff, B, S, d, s));
         if (gemm_f16(h->bf16, h->xt16, Jp, h->in_x, h->in_x.bias, nullptr, 0, nullptr, 0, nullptr, 0, h->emb16, d, Beff * T, d, T, 0, 0, s))
             return -1;
-        if (HFN(h->bf16, local_attention_f16_supported, d, h->cfg.cl_head, h->cfg.window)) {
-            if (gemm_f16(h->bf16, h->emb16, d, h->proj_pose, nullptr, h->addend, d, h->c2, d, nullptr, 0, h->xseq16, d, Beff * T, d, T, 0, 0, s))
-                return -1;
-            HIPCHK(HFN(h->bf16, launch_local_attention_f16, h->xseq16, h->rope_cos, h->rope_sin, h->xa16, tap32, Beff, T, d,
-                                              h->cfg.cl_head, h->cfg.window, s));
-        } else {
-            if (gemm_f16(h->bf16, h->emb16, d, h->proj_pose, nullptr, h->addend, d, h->c2, d, h->xseq, d, nullptr, 0, Beff * T, d, T, 0, 0, s))
-                return -1;
-            HIPCHK(HFN(h->bf16, launch_local_attention, h->xseq, h->rope_cos, h->rope_sin, h->xa, h->xa16, Beff, T, d, h->cfg.cl_head,
-                                          h->cfg.window, s));
-        }
+        // proj_pose writes the operand the front end's kernel reads: 16-bit xseq16, or fp32 xseq for the fp32 kernel
+        const int dt = h->bf16 ? GDX_DTYPE_BF16 : GDX_DTYPE_F16;
+        const bool la16 = local_attention_half(dt, d, h->cfg.cl_head, h->cfg.window);
+        if (gemm_f16(h->bf16, h->emb16, d, h->proj_pose, nullptr, h->addend, d, h->c2, d, la16 ? nullptr : h->xseq, d,
+                     la16 ? h->xseq16 : nullptr, d, Beff * T, d, T, 0, 0, s))
+            return -1;
+        HIPCHK(launch_local_attention_any(dt, h->xseq, h->xseq16, h->rope_cos, h->rope_sin, la16 ? tap32 : h->xa, h->xa16, Beff, T,
+                                          d, h->cfg.cl_head, h->cfg.window, s));
     }
     if (h->keep_taps)
         HIPCHK(hipMemcpyAsync(h->taps[0], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
@@ -1345,7 +1358,10 @@ extern "C" int gdx_set_test_half_dtype(int32_t dtype) {
     return 0;
 }
 
-namespace gdx { int g_gemmh_force_mb = -1, g_gemmh_force_nbw = -1; }
+namespace gdx {
+int g_gemmh_force_mb = -1, g_gemmh_force_nbw = -1;
+GemmHLaunched g_gemmh_launched = {0, 0, 0, 0, 0};
+}
 
 extern "C" int gdx_set_test_gemmh_tile(int32_t mb, int32_t nbw) {
     if (mb < 0 || nbw < 0 || (mb == 0) != (nbw == 0)) return fail("gdx_set_test_gemmh_tile: (mb, nbw) both positive, or (0, 0)");
@@ -1354,29 +1370,123 @@ extern "C" int gdx_set_test_gemmh_tile(int32_t mb, int32_t nbw) {
     return 0;
 }
 
-extern "C" int gdx_linear_f16(const float* A, const float* W, const float* bias, float* C32, float* C16, int32_t M,
-                              int32_t N, int32_t K, int32_t gelu, void* stream) {
-    if (!A || !W || (!C32 && !C16) || M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 64)
-        return fail("gdx_linear_f16: bad argument");
-    hipStream_t s = (hipStream_t)stream;
+// gdx_linear_half / gdx_linear_f16.  force_mb < 0: the process-wide tile setting (gdx_set_test_gemmh_tile) stays in force.
+static int linear_half(const char* who, const float* A, const float* W, const float* bias, const float* R, int32_t ldr,
+                       const float* V, int32_t ldv, float* C32, float* C16, int32_t c_rows, int32_t M, int32_t N, int32_t K,
+                       int32_t T, int32_t rowmap, int32_t gelu, bool bf, int32_t force_mb, int32_t force_nbw,
+                       int32_t* launched, hipStream_t s) {
+    const std::string w(who);
+    const long out_rows = rowmap ? (long)M + (M - 1) / T + 1 : M;    // rows the epilogue stores (rowmap: m + m/T + 1)
+    if (!A || !W || (!C32 && !C16) || M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 64 || T <= 0 || c_rows < out_rows ||
+        (R && (ldr < N || ldr % 4)) || (V && (ldv < N || ldv % 4)))
+        return fail(w + ": bad argument");
     const int npad = round_up(N, 256);
-    if (2 * (size_t)M * K >= (1ull << 31) || 2 * (size_t)npad * K >= (1ull << 31))
-        return fail("gdx_linear_f16: an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
+    if (2 * (size_t)M * K >= (1ull << 31) || 2 * (size_t)npad * K >= (1ull << 31) || 2 * (size_t)c_rows * N >= (1ull << 31))
+        return fail(w + ": an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
     _Float16 *a16 = nullptr, *w16 = nullptr, *c16 = nullptr;
     std::vector<void*> pool;
     int rc = 0;
     if (dev_alloc(pool, (void**)&a16, 2 * (size_t)M * K) || dev_alloc(pool, (void**)&w16, 2 * (size_t)npad * K) ||
-        dev_alloc(pool, (void**)&c16, 2 * (size_t)M * N))
+        (C16 && dev_alloc(pool, (void**)&c16, 2 * (size_t)c_rows * N)))
         rc = -1;
-    if (!rc && HFN(g_test_bf16, launch_convert_f16, A, a16, (int64_t)M * K, s) != hipSuccess) rc = fail("gdx_linear_f16: convert failed");
-    if (!rc) rc = pack_f16_into(w16, W, N, K, 0, K, npad, K, s, g_test_bf16);
+    if (!rc && HFN(bf, launch_convert_f16, A, a16, (int64_t)M * K, s) != hipSuccess) rc = fail(w + ": convert failed");
+    // the 16-bit output is staged from the caller's C16, so rows the kernel does not store come back unchanged (NaN stays NaN)
+    if (!rc && C16 && HFN(bf, launch_convert_f16, C16, c16, (int64_t)c_rows * N, s) != hipSuccess) rc = fail(w + ": convert failed");
+    if (!rc) rc = pack_f16_into(w16, W, N, K, 0, K, npad, K, s, bf);
     if (!rc) {
-        GemmHParams p{a16, K, w16, K, (int)((size_t)M * K * 2), (int)((size_t)npad * K * 2), bias, nullptr, 0, nullptr, 0,
-                      C32, N, C16 ? c16 : nullptr, N, M, N, K, 1, 0, gelu};
-        hipError_t e = HFN(g_test_bf16, launch_gemmh, p, s);
+        GemmHParams p{a16, K, w16, K, (int)((size_t)M * K * 2), (int)((size_t)npad * K * 2), bias, R, ldr, V, ldv,
+                      C32, N, c16, N, M, N, K, T, rowmap, gelu};
+        const int keep_mb = g_gemmh_force_mb, keep_nbw = g_gemmh_force_nbw;
+        if (force_mb >= 0) { g_gemmh_force_mb = force_mb; g_gemmh_force_nbw = force_nbw; }
+        g_gemmh_launched = GemmHLaunched{0, 0, 0, 0, 0};
+        hipError_t e = HFN(bf, launch_gemmh, p, s);
+        if (force_mb >= 0) { g_gemmh_force_mb = keep_mb; g_gemmh_force_nbw = keep_nbw; }
         if (e != hipSuccess) rc = fail(std::string("launch_gemmh: ") + hipGetErrorString(e));
+        if (launched) {
+            const GemmHLaunched& l = g_gemmh_launched;
+            launched[0] = l.mb; launched[1] = l.nbw; launched[2] = l.main_rows; launched[3] = l.tail_mb; launched[4] = l.tail_nbw;
+        }
     }
-    if (!rc && C16 && HFN(g_test_bf16, launch_convert_f32, c16, C16, (int64_t)M * N, s) != hipSuccess) rc = fail("gdx_linear_f16: convert failed");
+    if (!rc && C16 && HFN(bf, launch_convert_f32, c16, C16, (int64_t)c_rows * N, s) != hipSuccess) rc = fail(w + ": convert failed");
+    (void)hipStreamSynchronize(s);
+    free_pool(pool);
+    return rc;
+}
+
+extern "C" int gdx_linear_half(const float* A, const float* W, const float* bias, const float* R, int32_t ldr, const float* V,
+                               int32_t ldv, float* C32, float* C16, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T,
+                               int32_t rowmap, int32_t gelu, int32_t dtype, int32_t tile_mb, int32_t tile_nbw,
+                               int32_t* launched, void* stream) {
+    if ((dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) || tile_mb < 0 || tile_nbw < 0 || (tile_mb == 0) != (tile_nbw == 0))
+        return fail("gdx_linear_half: bad argument");
+    return linear_half("gdx_linear_half", A, W, bias, R, ldr, V, ldv, C32, C16, c_rows, M, N, K, T, rowmap, gelu,
+                       dtype == GDX_DTYPE_BF16, tile_mb, tile_nbw, launched, (hipStream_t)stream);
+}
+
+extern "C" int gdx_linear_f16(const float* A, const float* W, const float* bias, float* C32, float* C16, int32_t M,
+                              int32_t N, int32_t K, int32_t gelu, void* stream) {
+    return linear_half("gdx_linear_f16", A, W, bias, nullptr, 0, nullptr, 0, C32, C16, M, M, N, K, 1, 0, gelu, g_test_bf16, -1,
+                       -1, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int gdx_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float* out32,
+                             float* out16, int32_t out_rows, int32_t rows, int32_t d, int32_t compact_S, int32_t half_input,
+                             int32_t dtype, void* stream) {
+    const long need = compact_S > 0 ? (long)rows - (rows + compact_S - 1) / compact_S : rows;
+    if (!x || !gamma || !beta || (!out32 && !out16) || rows <= 0 || d <= 0 || d % 32 || d > 2048 || compact_S < 0 ||
+        out_rows < need || (dtype != GDX_DTYPE_F32 && dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) ||
+        (dtype == GDX_DTYPE_F32 && (half_input || out16)) || (half_input && !out16))
+        return fail("gdx_layernorm: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const bool bf = dtype == GDX_DTYPE_BF16;
+    const int64_t n_in = (int64_t)rows * d, n_out = (int64_t)out_rows * d;
+    _Float16 *x16 = nullptr, *r16 = nullptr, *o16 = nullptr;
+    std::vector<void*> pool;
+    int rc = 0;
+    if ((half_input && (dev_alloc(pool, (void**)&x16, 2 * (size_t)n_in) || (res && dev_alloc(pool, (void**)&r16, 2 * (size_t)n_in)))) ||
+        (out16 && dev_alloc(pool, (void**)&o16, 2 * (size_t)n_out)))
+        rc = -1;
+    if (!rc && half_input && (HFN(bf, launch_convert_f16, x, x16, n_in, s) != hipSuccess ||
+                              (res && HFN(bf, launch_convert_f16, res, r16, n_in, s) != hipSuccess)))
+        rc = fail("gdx_layernorm: convert failed");
+    if (!rc && out16 && HFN(bf, launch_convert_f16, out16, o16, n_out, s) != hipSuccess) rc = fail("gdx_layernorm: convert failed");
+    if (!rc) {
+        const hipError_t e = half_input ? HFN(bf, launch_layernorm_f16, x16, r16, gamma, beta, o16, out32, rows, d, compact_S, s)
+                                        : HFN(bf, launch_layernorm, x, res, gamma, beta, out32, o16, rows, d, compact_S, s);
+        if (e != hipSuccess) rc = fail(std::string("launch_layernorm: ") + hipGetErrorString(e));
+    }
+    if (!rc && out16 && HFN(bf, launch_convert_f32, o16, out16, n_out, s) != hipSuccess) rc = fail("gdx_layernorm: convert failed");
+    (void)hipStreamSynchronize(s);
+    free_pool(pool);
+    return rc;
+}
+
+extern "C" int gdx_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc, float* enc16,
+                                   int32_t enc_rows, int32_t B, int32_t T, int32_t d, int32_t heads, int32_t window,
+                                   int32_t dtype, int32_t* kernel, void* stream) {
+    const bool dt_ok = dtype == GDX_DTYPE_F32 || dtype == GDX_DTYPE_F16 || dtype == GDX_DTYPE_BF16;
+    if (!xseq || !cosT || !sinT || !dt_ok || B <= 0 || T <= 0 || heads <= 0 || d <= 0 || d % heads || (d / heads) % 2 ||
+        window <= 0 || T % window || enc_rows < (long)B * (T + 1) || (dtype == GDX_DTYPE_F32 && enc16))
+        return fail("gdx_local_attention: bad argument");
+    const bool half = local_attention_half(dtype, d, heads, window);
+    if (!half && !enc) return fail("gdx_local_attention: the fp32 kernel needs enc");
+    if (half && !enc16) return fail("gdx_local_attention: the 16-bit kernel needs enc16");
+    hipStream_t s = (hipStream_t)stream;
+    const bool bf = dtype == GDX_DTYPE_BF16;
+    const int64_t n_in = (int64_t)B * T * d, n_out = (int64_t)enc_rows * d;
+    _Float16 *x16 = nullptr, *e16 = nullptr;
+    std::vector<void*> pool;
+    int rc = 0;
+    if ((half && dev_alloc(pool, (void**)&x16, 2 * (size_t)n_in)) || (enc16 && dev_alloc(pool, (void**)&e16, 2 * (size_t)n_out)))
+        rc = -1;
+    if (!rc && half && HFN(bf, launch_convert_f16, xseq, x16, n_in, s) != hipSuccess) rc = fail("gdx_local_attention: convert failed");
+    if (!rc && enc16 && HFN(bf, launch_convert_f16, enc16, e16, n_out, s) != hipSuccess) rc = fail("gdx_local_attention: convert failed");
+    if (!rc) {
+        const hipError_t e = launch_local_attention_any(dtype, xseq, x16, cosT, sinT, enc, e16, B, T, d, heads, window, s);
+        if (e != hipSuccess) rc = fail(std::string("launch_local_attention: ") + hipGetErrorString(e));
+    }
+    if (!rc && enc16 && HFN(bf, launch_convert_f32, e16, enc16, n_out, s) != hipSuccess) rc = fail("gdx_local_attention: convert failed");
+    if (kernel) *kernel = half ? 2 : local_attention_mfma_supported(d, heads, window) ? 1 : 0;
     (void)hipStreamSynchronize(s);
     free_pool(pool);
     return rc;

@@ -69,6 +69,10 @@ hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s);
 //   C[row_out][n] = act( sum_k A[m][k] W[n][k] + bias[n] + R[row_out][n] + V[m / T][n] ),  row_out = rowmap ? m + m/T + 1 : m
 // forced tile of launch_gemmh (both half-type builds): -1 = not read yet (GDX_GEMMH_TILE), 0 = the cost model's choice
 extern int g_gemmh_force_mb, g_gemmh_force_nbw;
+// what the last launch_gemmh ran (both half-type builds; read by the test entry point gdx_linear_half): the tile of the first
+// launch (mb == 16: the eight-wave kernel), the rows of the row cut's main part (0: no cut) and the tile of the tail launch
+struct GemmHLaunched { int mb, nbw, main_rows, tail_mb, tail_nbw; };
+extern GemmHLaunched g_gemmh_launched;
 
 struct GemmHParams {
     const _Float16* A; int lda;      // [M][K] halves, K % 64 == 0
@@ -131,6 +135,8 @@ hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, 
        enc[b][t+1][:].   xseq [B*T][d];  cos/sin tables [>=T+1][e/2], e = d/heads. */                                       \
     hipError_t launch_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc, _Float16* enc16, \
                                       int B, int T, int d, int heads, int window, hipStream_t s);                           \
+    /* true when launch_local_attention takes the fp32 MFMA kernel (else the scalar one) */                                 \
+    bool local_attention_mfma_supported(int d, int heads, int window);                                                      \
     /* dst[i] = (half) src[i] and back */                                                                                   \
     hipError_t launch_convert_f16(const float* src, _Float16* dst, int64_t n, hipStream_t s);                               \
     hipError_t launch_convert_f32(const _Float16* src, float* dst, int64_t n, hipStream_t s);                               \

@@ -885,6 +885,7 @@ hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s) {
                 if (debug)
                     fprintf(stderr, "[gemmh] M=%d N=%d K=%d -> rows 0..%d as 256x256 tiles (%ld rounds), %d rows as %dx%d tiles\n",
                             p.M, p.N, p.K, m_main, full, pt.M, tail.tmb * 16, tail.tnbw * 64);
+                g_gemmh_launched = GemmHLaunched{16, 4, m_main, tail.tmb, tail.tnbw};
                 hipError_t e = launch_gh_choice(pm, GhChoice{c_main, 16, 4}, num_cus, s);
                 if (e != hipSuccess) return e;
                 return launch_gh_choice(pt, tail, num_cus, s);
@@ -892,6 +893,7 @@ hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s) {
         }
     }
     if (debug) fprintf(stderr, "[gemmh] M=%d N=%d K=%d -> tile %dx%d\n", p.M, p.N, p.K, whole.tmb * 16, whole.tnbw * 64);
+    g_gemmh_launched = GemmHLaunched{whole.tmb, whole.tnbw, 0, 0, 0};
     return launch_gh_choice(p, whole, num_cus, s);
 }
 

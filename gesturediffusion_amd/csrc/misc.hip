@@ -216,7 +216,10 @@ __global__ __launch_bounds__(256) void layernorm_h_gen_kernel(const half_t* __re
     }
     const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + 1e-5f);
     for (int e = lane; e < d; e += 64) {
-        const float r = (at(e) - mean) * rstd * g[e] + bta[e];
+        float r = (at(e) - mean) * rstd * g[e] + bta[e];
+        // out16 is r rounded: without the barrier the compiler fuses the last multiply-add into the 16-bit conversion
+        // (v_fma_mixlo_f16, one rounding from the exact value), which disagrees with out32 rounded on ~1e-4 of the elements
+        asm volatile("" : "+v"(r));
         out16[orow * d + e] = (half_t)r;
         if (out32) out32[orow * d + e] = r;
     }
@@ -634,11 +637,16 @@ __global__ __launch_bounds__(256) void local_attention_mfma_kernel(const float* 
     }
 }
 
+bool local_attention_mfma_supported(int d, int heads, int window) {
+    const int e = d / heads;
+    return (e == 32 || e == 64 || e == 128) && window >= 1 && window <= 16 && d % 4 == 0;
+}
+
 hipError_t launch_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc,
                                   _Float16* enc16_, int B, int T, int d, int heads, int window, hipStream_t s) {
     half_t* enc16 = reinterpret_cast<half_t*>(enc16_);
     const int e = d / heads;
-    if ((e == 32 || e == 64 || e == 128) && window >= 1 && window <= 16 && d % 4 == 0) {
+    if (GDX_HNS_NAME::local_attention_mfma_supported(d, heads, window)) {
         const int nwork = B * heads * (T / window);
         const dim3 grid((nwork + 3) / 4), block(256);
         if (e == 128)

@@ -312,6 +312,37 @@ int gdx_bench_attention(int32_t B, int32_t S, int32_t H, int32_t d, int32_t vers
  * may be NULL).  K % 64 == 0, N % 64 == 0.  Synchronises the stream (scratch is freed on return). */
 int gdx_linear_f16(const float* A, const float* W, const float* bias, float* C32, float* C16,
                    int32_t M, int32_t N, int32_t K, int32_t gelu, void* stream);
+/* The same GEMM with the whole epilogue the forwards use, element type `dtype` (GDX_DTYPE_F16 / _BF16, not the process-wide
+ * setting):  C[row_out][n] = act(A W^T + bias[n] + R[row_out * ldr + n] + V[(m / T) * ldv + n]),  act = GELU if gelu,
+ * row_out = rowmap ? m + m/T + 1 : m  (token 0 of every sample of a [B, T+1] layout skipped).  bias, R, V may each be NULL.
+ * C32 (fp32, written in place) and / or C16 (the 16-bit output widened to fp32) hold c_rows >= the stored rows
+ * (rowmap ? M + (M-1)/T + 1 : M) rows of N; the 16-bit output is staged from C16's own values, so rows the kernel does not
+ * store come back unchanged.  (tile_mb, tile_nbw) forces a tile shape as gdx_set_test_gemmh_tile does, for this call only
+ * ((0, 0) = the cost model, with its row cut).  launched (optional, 5 entries) receives what ran: the (mb, nbw) of the
+ * first launch (mb = 16: the eight-wave kernel), the rows of the row cut's main part (0: no cut) and the (mb, nbw) of the
+ * tail launch.  K % 64 == 0, N % 64 == 0.  Synchronises the stream. */
+int gdx_linear_half(const float* A, const float* W, const float* bias, const float* R, int32_t ldr, const float* V,
+                    int32_t ldv, float* C32, float* C16, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T,
+                    int32_t rowmap, int32_t gelu, int32_t dtype, int32_t tile_mb, int32_t tile_nbw, int32_t* launched,
+                    void* stream);
+/* out = LayerNorm(x + res) over rows of d (eps 1e-5, biased variance; csrc/misc.hip) as the forwards launch it.
+ * half_input = 0: fp32 x / res (the fp32 kernels, with a 16-bit copy out16 in element type dtype when out16 is given);
+ * half_input = 1: x / res rounded to dtype (GDX_DTYPE_F16 / _BF16) by the call, the 16-bit kernels (out16 required, out32
+ * optional).  res may be NULL.  compact_S > 0: rows are [B, S] tokens and token 0 of every sample is dropped from the output.
+ * out32 / out16 are fp32 device arrays of out_rows >= the stored rows; out16 receives the 16-bit output widened, staged
+ * from its own values like gdx_linear_half's C16.  d % 32 == 0, d <= 2048.  Synchronises the stream. */
+int gdx_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float* out32, float* out16,
+                  int32_t out_rows, int32_t rows, int32_t d, int32_t compact_S, int32_t half_input, int32_t dtype,
+                  void* stream);
+/* V2 front end (RoPE -> causal local attention, window `window`, look back one window -> RoPE at t+1) through the same
+ * dispatch as the forward of compute dtype `dtype`: xseq [B, T, d] fp32 (rounded to dtype by the call when the 16-bit kernel
+ * runs), cos / sin [>= T+1][d / heads / 2], enc [B, T+1, d] fp32 (rows b*(T+1) stay untouched) and / or enc16 (the 16-bit
+ * output widened, staged from its own values), each of enc_rows >= B*(T+1) rows.  The fp32 kernels need enc, the 16-bit one
+ * enc16; GDX_DTYPE_F32 takes no enc16.  kernel (optional) receives what ran: 0 the scalar fp32 kernel, 1 the fp32 MFMA
+ * kernel, 2 the 16-bit kernel.  T % window == 0.  Synchronises the stream. */
+int gdx_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc, float* enc16, int32_t enc_rows,
+                        int32_t B, int32_t T, int32_t d, int32_t heads, int32_t window, int32_t dtype, int32_t* kernel,
+                        void* stream);
 /* ctx = softmax(Q K^T / sqrt(hd)) V per (sample, head) through the fp16 attention kernel
  * (csrc/attentionh.hip): qkv [B*S][3d] and ctx [B*S][d] are fp32 device arrays converted to / from
  * fp16 by the call.  head_dim = d / H in {32, 64, 128, 256}.  Synchronises the stream. */
