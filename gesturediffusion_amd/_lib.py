@@ -22,7 +22,7 @@ EXPORTS = [
     "gdx_randn", "gdx_sample_loop", "gdx_bench_ffn_gemm", "gdx_bench_gemm", "gdx_forward_flops", "gdx_profile_begin", "gdx_profile_end", "gdx_bench_attention",
     "gdx_linear_f16", "gdx_linear_f32", "gdx_bench_gemm_f16", "gdx_attention_f16", "gdx_attention_f32", "gdx_plms_update", "gdx_postprocess", "gdx_q_sample_t", "gdx_masked_l2", "gdx_set_graph_replay", "gdx_mfcc",
     "gdx_set_guards", "gdx_check_guards", "gdx_packed_bytes", "gdx_export_packed", "gdx_import_packed", "gdx_set_test_half_dtype",
-    "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention",
+    "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
 ]
 
 
@@ -117,6 +117,7 @@ def load():
         "gdx_postprocess": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
         "gdx_plms_update": [C.POINTER(PlmsArgs), vp],
         "gdx_attention_f16": [vp, vp, i32, i32, i32, i32, vp],
+        "gdx_attention_half": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
         "gdx_attention_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
         "gdx_bench_gemm_f16": [i32, i32, i32, i32, i32, C.POINTER(C.c_float), vp],
         "gdx_set_guards": [vp, i32],

@@ -1512,6 +1512,39 @@ extern "C" int gdx_attention_f16(const float* qkv, float* ctx, int32_t B, int32_
     return rc;
 }
 
+extern "C" int gdx_attention_half(const float* qkv, int32_t qkv_rows, float* ctx, int32_t ctx_rows, int32_t B, int32_t S,
+                                  int32_t H, int32_t d, int32_t dtype, int32_t kernel, int32_t grid, int32_t* launched,
+                                  void* stream) {
+    // every refusal comes before the first HIP call (tests/test_host_logic.py checks them without a GPU)
+    if (dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) return fail("gdx_attention_half: dtype must be GDX_DTYPE_F16 or _BF16");
+    if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H || !HFN(dtype == GDX_DTYPE_BF16, attentionh_supported, S, H, d))
+        return fail("gdx_attention_half: bad argument / unsupported shape (head_dim 32, 64, 128 or 256)");
+    if (kernel < 0 || kernel > 3) return fail("gdx_attention_half: unknown kernel (0 = dispatch, 1 = h8, 2 = h8q, 3 = h8p)");
+    if (kernel >= 2 && d / H < 64) return fail("gdx_attention_half: h8q / h8p have no head_dim 32 instantiation");
+    if (grid < 0 || (grid > 0 && kernel != 3)) return fail("gdx_attention_half: grid is for the persistent kernel (kernel 3) only");
+    if ((long)qkv_rows < (long)B * S || (long)ctx_rows < (long)B * S) return fail("gdx_attention_half: qkv_rows / ctx_rows below B*S");
+    if (2 * (size_t)qkv_rows * 3 * d >= (1ull << 31) || 2 * (size_t)ctx_rows * d >= (1ull << 31))
+        return fail("gdx_attention_half: a buffer exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
+    hipStream_t s = (hipStream_t)stream;
+    const bool bf = dtype == GDX_DTYPE_BF16;
+    const int64_t n_in = (int64_t)qkv_rows * 3 * d, n_out = (int64_t)ctx_rows * d;
+    _Float16 *q16 = nullptr, *c16 = nullptr;
+    std::vector<void*> pool;
+    int rc = 0;
+    if (dev_alloc(pool, (void**)&q16, 2 * (size_t)n_in) || dev_alloc(pool, (void**)&c16, 2 * (size_t)n_out)) rc = -1;
+    if (!rc && HFN(bf, launch_convert_f16, qkv, q16, n_in, s) != hipSuccess) rc = fail("gdx_attention_half: convert failed");
+    // the 16-bit output is staged from the caller's ctx, so rows the kernel does not store come back unchanged (NaN stays NaN)
+    if (!rc && HFN(bf, launch_convert_f16, ctx, c16, n_out, s) != hipSuccess) rc = fail("gdx_attention_half: convert failed");
+    if (!rc) {
+        const hipError_t e = HFN(bf, launch_attentionh_kernel, q16, c16, B, S, H, d, (long)qkv_rows, kernel, grid, launched, s);
+        if (e != hipSuccess) rc = fail(std::string("launch_attentionh_kernel: ") + hipGetErrorString(e));
+    }
+    if (!rc && HFN(bf, launch_convert_f32, c16, ctx, n_out, s) != hipSuccess) rc = fail("gdx_attention_half: convert failed");
+    (void)hipStreamSynchronize(s);
+    free_pool(pool);
+    return rc;
+}
+
 // fp32 SDPA core on a caller's [B*S][3d] buffer (test entry point).  The kernels read whole K/V tiles past the last
 // sample, so the call works on a scratch copy with GDX_ROW_PAD zero rows behind it, like the workspace of gdx_prepare.
 extern "C" int gdx_attention_f32(const float* qkv, float* ctx, int32_t B, int32_t S, int32_t H, int32_t d, int32_t version,

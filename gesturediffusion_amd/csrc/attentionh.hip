@@ -295,12 +295,14 @@ __global__ __launch_bounds__(512, 1) void attentionh8q_kernel(const _Float16* __
     char* sl = smem + NST * STAGE_BYTES + wave * (16 * ROWB);
     const int kbase = l15 * ROWB + ((lq ^ fswz(l15)) << 4);
     const auto rsrcQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), (short)0, ah_records(qkv_bytes - base_off * 2), 0x00020000);
-    auto dma_q = [&](int qi) {                                          // rows past S: the next sample's / zeros, their columns are never stored
+    // rows past S repeat row S - 1 (as in attentionh8_kernel): a query that is never stored still takes part in the block's
+    // rescale vote, so it must not come from the next sample or the pad -- or a sample's bits would depend on its neighbours
+    auto dma_q = [&](int qi) {
         const int q0 = 16 * (qb_lo + wave + 8 * qi);
 #pragma unroll
         for (int j = 0; j < NPQ; ++j) {
             const int row = j * RPP + lane / CPR;
-            const int vo = (int)((q0 + row) * ld * 2) + (((lane % CPR) ^ fswz(row)) * 16);
+            const int vo = (int)(min(q0 + row, S - 1) * ld * 2) + (((lane % CPR) ^ fswz(row)) * 16);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcQ, (lds_ptr_t)(sl + j * 1024), 16, vo, 0, 0, 0);
         }
     };
@@ -602,8 +604,8 @@ __global__ __launch_bounds__(512, 1) void attentionh8p_kernel(const _Float16* __
             asm volatile("" ::: "memory");
 #pragma unroll
             for (int j = 0; j < NPQ; ++j) {
-                const int row = j * RPP + ln / CPR;
-                const int vo = (int)((q0 + row) * ld * 2) + (((ln % CPR) ^ fswz(row)) * 16);
+                const int row = j * RPP + ln / CPR;                      // rows past S repeat row S - 1 (see attentionh8q_kernel)
+                const int vo = (int)(min(q0 + row, S - 1) * ld * 2) + (((ln % CPR) ^ fswz(row)) * 16);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcQ, (lds_ptr_t)(sl + j * 1024), 16, vo, 0, 0, 0);
             }
             ah_wait_vm<0>();
@@ -785,7 +787,7 @@ __global__ __launch_bounds__(512, 1) void attentionh8p_kernel(const _Float16* __
 }
 
 template <int HD>
-static hipError_t launch_ah8p(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_bytes, int num_cus,
+static hipError_t launch_ah8p(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_bytes, int grid,
                               hipStream_t s) {
     const size_t lds = (size_t)3 * 2 * 32 * HD * 2 + (size_t)8 * 16 * HD * 2;   // three K/V stages + a 16-row slice per wave
     static bool attr_done = false;
@@ -801,7 +803,6 @@ static hipError_t launch_ah8p(const _Float16* qkv, _Float16* ctx, int B, int S, 
     const int nqb = (S + 15) / 16;
     const int nchunk = (nqb + 15) / 16;
     const int nitems = B * H * nchunk;
-    const int grid = nitems < num_cus ? nitems : num_cus;
     const float c_log2 = 1.4426950408889634f / sqrtf((float)HD);
     if (g2_dbg_buf)                                               // the stamped build of the kernel (diagnostic launches only)
         hipLaunchKernelGGL((attentionh8p_kernel<HD, 2, true>), dim3(grid), dim3(512), lds, s, qkv, ctx, S, H, d, nchunk, nitems,
@@ -853,8 +854,13 @@ bool attentionh_supported(int S, int H, int d) {
     return (hd == 32 || hd == 64 || hd == 128 || hd == 256) && d % 8 == 0 && S >= 1;
 }
 
-// qkv_rows: rows of the qkv buffer that are readable (>= B*S); reads past them return zeros
-hipError_t launch_attentionh(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, hipStream_t s) {
+// The one dispatch of the forward and of the test entry point gdx_attention_half.  kernel: 0 = the forward's choice, 1 = the
+// 8-wave x 1-block kernel, 2 = 8 x 2 blocks, 3 = the persistent form (the callers refuse 2 / 3 at head_dim 32, which has no
+// instantiation of them); grid > 0: workgroups of the persistent form (0 = one per CU, at most one per item).  launched
+// (optional, 3 entries): the kernel that ran (1-3), its grid and its work-item count.  qkv_rows: rows of the qkv buffer that are
+// readable (>= B*S); reads past them return zeros.
+hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, int kernel,
+                                    int grid, int* launched, hipStream_t s) {
     const int hd = d / H;
     const long bytes = qkv_rows * 3L * d * 2;
     // measured (tools/attnh_one.py, us): B=128 S=521 hd=256: 8 waves x 1 block 373, 8 waves x 2 blocks 292, persistent 273-285;
@@ -864,22 +870,40 @@ hipError_t launch_attentionh(const _Float16* qkv, _Float16* ctx, int B, int S, i
     const int nqb = (S + 15) / 16;
     const long nitems = (long)B * H * ((nqb + 15) / 16);
     const int num_cus = gemm2_num_cus();
-    // persistent form once every CU has at least two items to chain (profiles/r02h_*)
-    if (hd >= 64 && nitems >= 2L * num_cus) {
-        if (hd == 256) return launch_ah8p<256>(qkv, ctx, B, S, H, d, bytes, num_cus, s);
-        if (hd == 128) return launch_ah8p<128>(qkv, ctx, B, S, H, d, bytes, num_cus, s);
-        return launch_ah8p<64>(qkv, ctx, B, S, H, d, bytes, num_cus, s);
+    if (kernel == 0) {
+        // persistent form once every CU has at least two items to chain (profiles/r02h_*)
+        if (hd >= 64 && nitems >= 2L * num_cus) kernel = 3;
+        else if (hd >= 64 && nitems >= 128) kernel = 2;
+        else kernel = 1;
     }
-    if (hd >= 64 && nitems >= 128) {
+    if ((kernel != 1 && (hd < 64 || kernel > 3)) || kernel < 1 || (grid != 0 && kernel != 3) || grid < 0) return hipErrorInvalidValue;
+    if (kernel == 3 && grid == 0) grid = nitems < num_cus ? (int)nitems : num_cus;
+    if (launched) {
+        launched[0] = kernel;
+        launched[1] = kernel == 3 ? grid : kernel == 2 ? (int)nitems : B * H * ((nqb + 7) / 8);
+        launched[2] = kernel == 1 ? B * H * ((nqb + 7) / 8) : (int)nitems;
+    }
+    if (kernel == 3) {
+        if (hd == 256) return launch_ah8p<256>(qkv, ctx, B, S, H, d, bytes, grid, s);
+        if (hd == 128) return launch_ah8p<128>(qkv, ctx, B, S, H, d, bytes, grid, s);
+        if (hd == 64) return launch_ah8p<64>(qkv, ctx, B, S, H, d, bytes, grid, s);
+        return hipErrorInvalidValue;
+    }
+    if (kernel == 2) {
         if (hd == 256) return launch_ah8q<256>(qkv, ctx, B, S, H, d, bytes, s);
         if (hd == 128) return launch_ah8q<128>(qkv, ctx, B, S, H, d, bytes, s);
-        return launch_ah8q<64>(qkv, ctx, B, S, H, d, bytes, s);
+        if (hd == 64) return launch_ah8q<64>(qkv, ctx, B, S, H, d, bytes, s);
+        return hipErrorInvalidValue;
     }
     if (hd == 256) return launch_ah8<256>(qkv, ctx, B, S, H, d, bytes, s);
     if (hd == 128) return launch_ah8<128>(qkv, ctx, B, S, H, d, bytes, s);
     if (hd == 64) return launch_ah8<64>(qkv, ctx, B, S, H, d, bytes, s);
     if (hd == 32) return launch_ah8<32>(qkv, ctx, B, S, H, d, bytes, s);
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_attentionh(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, hipStream_t s) {
+    return launch_attentionh_kernel(qkv, ctx, B, S, H, d, qkv_rows, 0, 0, nullptr, s);
 }
 
 GDX_HNS_END

@@ -106,6 +106,10 @@ hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, 
     /* reduced-precision attention (attentionh.hip): qkv / ctx in halves, head_dim 32/64/128/256, any S; qkv_rows = readable rows */ \
     bool attentionh_supported(int S, int H, int d);                                                                         \
     hipError_t launch_attentionh(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, hipStream_t s); \
+    /* the same dispatch with a forced kernel (0 = the forward's choice, 1 = h8, 2 = h8q, 3 = h8p), the persistent grid      \
+       (0 = its default) and a report of what ran (launched: kernel, grid, work items); used by gdx_attention_half */        \
+    hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows,     \
+                                        int kernel, int grid, int* launched, hipStream_t s);                               \
     /* out = LayerNorm(x + res) (res may be nullptr); compact_S > 0: rows are [B, S] tokens and token 0 of every sample is  \
        dropped from the output ([B, S-1, d]); out (fp32) and out16 (half copy) are each optional */                         \
     hipError_t launch_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float* out,        \

@@ -135,6 +135,41 @@ def test_c_abi_rejects_bad_config_without_gpu():
     assert lib.gdx_sampler_update(None, None) != 0
 
 
+def test_attention_half_refuses_what_has_no_kernel_without_gpu():
+    """gdx_attention_half validates before its first HIP call: every combination without an instantiation is refused with a
+    message (the pointers are never dereferenced)."""
+    import ctypes as C
+    from gesturediffusion_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgdx.so not built")
+    lib = _lib.load()
+    p = C.c_void_p(0x1000)
+    rep = (C.c_int32 * 3)(-1, -1, -1)
+    ok = dict(qkv_rows=2 * 61, ctx_rows=2 * 61, B=2, S=61, H=4, d=512, dtype=1, kernel=0, grid=0)
+    cases = [
+        (dict(d=128, kernel=2), b"no head_dim 32"),                # h8q at head_dim 32
+        (dict(d=128, kernel=3), b"no head_dim 32"),                # h8p at head_dim 32
+        (dict(d=128, kernel=3, dtype=2), b"no head_dim 32"),
+        (dict(kernel=4), b"unknown kernel"),
+        (dict(kernel=-1), b"unknown kernel"),
+        (dict(kernel=1, grid=8), b"persistent kernel"),            # grid for a non-persistent kernel
+        (dict(kernel=2, grid=8), b"persistent kernel"),
+        (dict(kernel=0, grid=8), b"persistent kernel"),
+        (dict(kernel=3, grid=-1), b"persistent kernel"),
+        (dict(qkv_rows=2 * 61 - 1), b"below B*S"),
+        (dict(ctx_rows=2 * 61 - 1), b"below B*S"),
+        (dict(dtype=0), b"dtype"),
+        (dict(d=4 * 48), b"unsupported shape"),                    # head_dim 48
+        (dict(S=0), b"unsupported shape"),
+    ]
+    for change, msg in cases:
+        a = dict(ok, **change)
+        rc = lib.gdx_attention_half(p, a["qkv_rows"], p, a["ctx_rows"], a["B"], a["S"], a["H"], a["d"], a["dtype"], a["kernel"],
+                                    a["grid"], rep, None)
+        assert rc != 0 and msg in lib.gdx_last_error(), (change, lib.gdx_last_error())
+        assert list(rep) == [-1, -1, -1], change              # refused before anything ran
+
+
 # ------------------------------------------------------------------------------- schedule / coefficients
 @pytest.mark.parametrize("sched", ["cosine", "linear"])
 @pytest.mark.parametrize("tag,resp", [("1000", ""), ("ddim10", "ddim10"), ("ddim100", "ddim100"), ("s20", [20])])
