@@ -23,7 +23,9 @@ EXPORTS = [
     "gdx_linear_f16", "gdx_linear_f32", "gdx_bench_gemm_f16", "gdx_attention_f16", "gdx_attention_f32", "gdx_plms_update", "gdx_postprocess", "gdx_q_sample_t", "gdx_masked_l2", "gdx_set_graph_replay", "gdx_mfcc",
     "gdx_set_guards", "gdx_check_guards", "gdx_packed_bytes", "gdx_export_packed", "gdx_import_packed", "gdx_set_test_half_dtype",
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
+    "gdx_bpd_terms", "gdx_bpd_loop",
 ]
+GDX_BPD_CHUNK = 4096   # include/gdx.h
 
 
 class GdxError(RuntimeError):
@@ -63,6 +65,27 @@ class LoopArgs(C.Structure):
         ("const_noise", C.c_int32), ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64),
         ("dump", C.c_void_p), ("dump_steps", C.c_void_p), ("n_dump", C.c_int32),
         ("run_steps", C.c_int32), ("k_base", C.c_int32), ("clip_denoised", C.c_int32),
+    ]
+
+
+class BpdArgs(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32), ("step_index", C.c_int32),
+        ("coef", C.c_void_p), ("t", C.c_void_p), ("x_start", C.c_void_p), ("x_t", C.c_void_p), ("noise", C.c_void_p),
+        ("x0_cond", C.c_void_p), ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p),
+        ("inpaint_motion", C.c_void_p), ("model_mean", C.c_void_p), ("clip_denoised", C.c_int32), ("prior", C.c_int32),
+        ("prior_log_variance", C.c_float), ("vb", C.c_void_p), ("xstart_mse", C.c_void_p), ("mse", C.c_void_p),
+        ("ld", C.c_int32), ("col", C.c_int32), ("pred_xstart", C.c_void_p), ("workspace", C.c_void_p),
+    ]
+
+
+class BpdLoopArgs(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("num_steps", C.c_int32), ("coef", C.c_void_p), ("timestep_map", C.c_void_p),
+        ("x_start", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p),
+        ("noise_tape", C.c_void_p), ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64),
+        ("clip_denoised", C.c_int32), ("run_steps", C.c_int32), ("k_base", C.c_int32), ("prior_log_variance", C.c_float),
+        ("vb", C.c_void_p), ("xstart_mse", C.c_void_p), ("mse", C.c_void_p), ("prior_bpd", C.c_void_p),
     ]
 
 
@@ -127,6 +150,8 @@ def load():
         "gdx_packed_bytes": [vp, C.POINTER(i64)],
         "gdx_export_packed": [vp, vp, i64, vp],
         "gdx_import_packed": [vp, vp, i64, vp],
+        "gdx_bpd_terms": [C.POINTER(BpdArgs), vp],
+        "gdx_bpd_loop": [vp, C.POINTER(BpdLoopArgs), vp],
         "gdx_profile_begin": [vp, i32],
         "gdx_profile_end": [vp, C.POINTER(C.c_float), C.POINTER(i32)],
     }

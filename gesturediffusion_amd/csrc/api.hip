@@ -115,6 +115,7 @@ struct gdx_model {
     bool c2t_valid = false;
     bool tables_valid = false;        // temb_table (and c2t_table) hold the rows of tmap_host under the current weights
     std::vector<int64_t> tmap_host;
+    float *bpd_xt = nullptr, *bpd_z = nullptr, *bpd_part = nullptr;   // gdx_bpd_loop: x_t, Philox noise [B, J, T], chunk sums
     // graph replay of launch-bound loops (gdx_sample_loop)
     bool graph_replay = false;        // gdx_set_graph_replay
     int* gstate = nullptr;            // device {schedule index, executed-step number}
@@ -587,6 +588,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     h->taps.clear();
     h->temb_table = nullptr; h->temb_table_rows = 0; h->tmap_dev = nullptr; h->c2t_table = nullptr; h->c2t_valid = false;
     h->tables_valid = false;
+    h->bpd_xt = h->bpd_z = h->bpd_part = nullptr;
     // the shape is recorded only once every allocation has succeeded: after a failed hipMalloc a retry with the same
     // shape must allocate again instead of returning early on partial buffers
     h->B = 0; h->T = 0; h->S = frames + 1; h->cond_set = false;
@@ -969,6 +971,104 @@ extern "C" int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timest
     return 0;
 }
 
+// timestep-embedding table (and, V2, its W_coa image) for every kept step of a loop, shared by gdx_sample_loop and gdx_bpd_loop
+static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timestep_map, hipStream_t s) {
+    const int d = h->d;
+    // timestep-embedding table for every kept step, once per loop (same t for the whole batch:
+    // gaussian_diffusion.py:712), through the respacing map (respace.py:124-129)
+    if (h->temb_table_rows < num_steps) {
+        float* t3 = nullptr;
+        // + GDX_ROW_PAD rows behind the last of the three tables: the table linears run on the persistent GEMM, which
+        // reads / stores whole tiles
+        if (dev_alloc(h->ws_allocs, (void**)&t3, sizeof(float) * (3 * (size_t)num_steps + GDX_ROW_PAD) * d)) return -1;
+        HIPCHK(hipMemsetAsync(t3, 0, sizeof(float) * (3 * (size_t)num_steps + GDX_ROW_PAD) * d, s));
+        if (h->cfg.arch == GDX_ARCH_MDM && dev_alloc(h->ws_allocs, (void**)&h->c2t_table, sizeof(float) * ((size_t)num_steps + GDX_ROW_PAD) * d))
+            return -1;
+        if (dev_alloc(h->ws_allocs, (void**)&h->tmap_dev, sizeof(int64_t) * num_steps)) return -1;
+        h->temb_table = t3;
+        h->temb_table_rows = num_steps;
+        h->tables_valid = false; h->c2t_valid = false;
+    }
+    float* table = h->temb_table;
+    // the tables depend on the weights and the timestep map only: a loop run in blocks (run_steps) builds them once
+    const bool tables_live = h->tables_valid && (int)h->tmap_host.size() == num_steps &&
+                             !memcmp(h->tmap_host.data(), timestep_map, sizeof(int64_t) * num_steps) &&
+                             (h->cfg.arch != GDX_ARCH_MDM || h->c2t_valid);
+    if (tables_live) return 0;
+    h->tmap_host.assign(timestep_map, timestep_map + num_steps);
+    HIPCHK(hipMemcpyAsync(h->tmap_dev, h->tmap_host.data(), sizeof(int64_t) * num_steps, hipMemcpyHostToDevice, s));
+    float* scratch0 = table + (size_t)h->temb_table_rows * d;
+    float* scratch1 = scratch0 + (size_t)h->temb_table_rows * d;
+    if (time_embed(h, h->tmap_dev, num_steps, scratch0, scratch1, table, s)) return -1;
+    if (h->cfg.arch == GDX_ARCH_MDM) {
+        // timestep half of the coarse slice of project_to_lat for every kept step, once per loop (same kernel as
+        // gdx_forward's per-sample rows)
+        HIPCHK(launch_small_linear(table, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2t_table, d, num_steps, d, d, 0, s));
+        h->c2t_valid = true;
+    }
+    h->tables_valid = true;
+    return 0;
+}
+
+int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
+                uint32_t step, float* z_out, float* xt_out, void* stream);                                      // sampler.hip
+
+// calc_bpd_loop (gaussian_diffusion.py:1537-1592): per step q_sample -> denoiser -> fused bound terms, through the SAME forward
+// entry (pose-layout x_t, forward_core) the step-wise protocol reaches via gdx_forward, so both give the same bits.
+extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* stream) {
+    if (!h) return fail("gdx_bpd_loop: null handle");
+    if (!a) return fail("gdx_bpd_loop: null argument");
+    if (check_ready(h, "gdx_bpd_loop")) return -1;
+    if (!a->coef || !a->timestep_map || !a->x_start || !a->vb || !a->xstart_mse || !a->mse)
+        return fail("gdx_bpd_loop: null argument");
+    if (a->mode < GDX_COND || a->mode > GDX_CFG) return fail("gdx_bpd_loop: bad mode");
+    if (a->mode == GDX_CFG && !a->scale) return fail("gdx_bpd_loop: GDX_CFG needs scale");
+    if (a->num_steps <= 0 || a->k_base < 0 || a->k_base >= a->num_steps || a->run_steps < 0 || a->k_base + a->run_steps > a->num_steps)
+        return fail("gdx_bpd_loop: bad step range");
+    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_bpd_loop: mask without motion");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B, d = h->d;
+    const size_t per = (size_t)h->J * h->T;
+    const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
+    if (!h->bpd_xt && dev_alloc(h->ws_allocs, (void**)&h->bpd_xt, sizeof(float) * B * per)) return -1;
+    if (!h->bpd_part && dev_alloc(h->ws_allocs, (void**)&h->bpd_part, sizeof(float) * 4 * B * chunks)) return -1;
+    if (!a->noise_tape && !h->bpd_z && dev_alloc(h->ws_allocs, (void**)&h->bpd_z, sizeof(float) * B * per)) return -1;
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    const float* table = h->temb_table;
+    gdx_bpd_args_t u;
+    memset(&u, 0, sizeof(u));
+    u.batch = B; u.njoints = h->J; u.frames = h->T;
+    u.coef = a->coef; u.x_start = a->x_start; u.x_t = h->bpd_xt;
+    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
+    u.clip_denoised = a->clip_denoised;
+    u.vb = a->vb; u.xstart_mse = a->xstart_mse; u.mse = a->mse; u.ld = a->num_steps;
+    u.workspace = h->bpd_part;
+    const int k_end = a->run_steps > 0 ? a->k_base + a->run_steps : a->num_steps;
+    for (int k = a->k_base; k < k_end; ++k) {
+        const int idx = a->num_steps - 1 - k;
+        if (a->noise_tape) {
+            u.noise = a->noise_tape + (size_t)(k - a->k_base) * B * per;
+            if (gdx_q_sample(a->x_start, u.noise, a->coef, idx, (int64_t)(B * per), h->bpd_xt, stream)) return -1;
+        } else {
+            u.noise = h->bpd_z;
+            if (gdx_bpd_xt_(a->x_start, a->coef, idx, B, (long)per, a->philox_seed, a->sample_offset, (uint32_t)k, h->bpd_z, h->bpd_xt,
+                            stream))
+                return -1;
+        }
+        if (forward_core(h, h->bpd_xt, table + (size_t)idx * d, 0, h->c2t_table ? h->c2t_table + (size_t)idx * d : nullptr, a->mode, h->x0, s))
+            return -1;
+        u.step_index = idx; u.col = k;
+        if (gdx_bpd_terms(&u, stream)) return -1;
+    }
+    if (a->prior_bpd) {
+        u.prior = 1; u.prior_log_variance = a->prior_log_variance; u.step_index = a->num_steps - 1;
+        u.vb = a->prior_bpd; u.ld = 1; u.col = 0;
+        if (gdx_bpd_terms(&u, stream)) return -1;
+    }
+    return 0;
+}
+
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
     if (check_ready(h, "gdx_sample_loop")) return -1;
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");
@@ -980,40 +1080,8 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         return fail("gdx_sample_loop: ddim_sample_loop supports neither const_noise nor dump_steps");  // :903-906
     hipStream_t s = (hipStream_t)stream;
     const int B = h->B, d = h->d;
-    // timestep-embedding table for every kept step, once per loop (same t for the whole batch:
-    // gaussian_diffusion.py:712), through the respacing map (respace.py:124-129)
-    if (h->temb_table_rows < a->num_steps) {
-        float* t3 = nullptr;
-        // + GDX_ROW_PAD rows behind the last of the three tables: the table linears run on the persistent GEMM, which
-        // reads / stores whole tiles
-        if (dev_alloc(h->ws_allocs, (void**)&t3, sizeof(float) * (3 * (size_t)a->num_steps + GDX_ROW_PAD) * d)) return -1;
-        HIPCHK(hipMemsetAsync(t3, 0, sizeof(float) * (3 * (size_t)a->num_steps + GDX_ROW_PAD) * d, s));
-        if (h->cfg.arch == GDX_ARCH_MDM && dev_alloc(h->ws_allocs, (void**)&h->c2t_table, sizeof(float) * ((size_t)a->num_steps + GDX_ROW_PAD) * d))
-            return -1;
-        if (dev_alloc(h->ws_allocs, (void**)&h->tmap_dev, sizeof(int64_t) * a->num_steps)) return -1;
-        h->temb_table = t3;
-        h->temb_table_rows = a->num_steps;
-        h->tables_valid = false; h->c2t_valid = false;
-    }
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
     float* table = h->temb_table;
-    // the tables depend on the weights and the timestep map only: a loop run in blocks (run_steps) builds them once
-    const bool tables_live = h->tables_valid && (int)h->tmap_host.size() == a->num_steps &&
-                             !memcmp(h->tmap_host.data(), a->timestep_map, sizeof(int64_t) * a->num_steps) &&
-                             (h->cfg.arch != GDX_ARCH_MDM || h->c2t_valid);
-    if (!tables_live) {
-    h->tmap_host.assign(a->timestep_map, a->timestep_map + a->num_steps);
-    HIPCHK(hipMemcpyAsync(h->tmap_dev, h->tmap_host.data(), sizeof(int64_t) * a->num_steps, hipMemcpyHostToDevice, s));
-    float* scratch0 = table + (size_t)h->temb_table_rows * d;
-    float* scratch1 = scratch0 + (size_t)h->temb_table_rows * d;
-    if (time_embed(h, h->tmap_dev, a->num_steps, scratch0, scratch1, table, s)) return -1;
-    if (h->cfg.arch == GDX_ARCH_MDM) {
-        // timestep half of the coarse slice of project_to_lat for every kept step, once per loop (same kernel as
-        // gdx_forward's per-sample rows)
-        HIPCHK(launch_small_linear(table, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2t_table, d, a->num_steps, d, d, 0, s));
-        h->c2t_valid = true;
-    }
-    h->tables_valid = true;
-    }
 
     const int64_t per = (int64_t)h->J * h->T;
     int dump_i = 0;

@@ -393,6 +393,192 @@ __global__ void cfg_blend_kernel(const float* __restrict__ c, const float* __res
     out[i] = __fadd_rn(u[i], __fmul_rn(sc, diff));
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Variational bound (reference gaussian_diffusion.py:1192-1225, 1519-1592, diffusion/losses.py:12-77; gdx.h gdx_bpd_terms).
+// bpd_xt_kernel forms x_t = sa*x0 + s1m*z with in-kernel Philox noise and STORES z next to it: the terms kernel reads the
+// same z back (4 B/element written and read once) instead of running Philox + Box-Muller a second time per element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bpd_xt_kernel(const float* __restrict__ x0, const float* __restrict__ coef, int idx,
+                                                     int batch, long per_sample, long groups, uint64_t seed,
+                                                     uint64_t sample_offset, uint32_t step, float* __restrict__ z_out,
+                                                     float* __restrict__ xt_out) {
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= groups * batch) return;
+    const int b = gid / groups;
+    const uint32_t grp = gid - (long)b * groups;
+    const float sa = coef[(long)idx * 8 + 5], s1m = coef[(long)idx * 8 + 6];
+    const f32x4 z = philox_normal4(seed, sample_offset + (uint64_t)b, step, grp);
+    const long e0 = (long)b * per_sample + 4L * grp;
+    if (VEC) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(x0 + e0);
+        f32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = __fadd_rn(__fmul_rn(sa, x[i]), __fmul_rn(s1m, z[i]));
+        *reinterpret_cast<f32x4*>(z_out + e0) = z;
+        *reinterpret_cast<f32x4*>(xt_out + e0) = r;
+    } else {
+        for (int i = 0; i < 4 && 4L * grp + i < per_sample; ++i) {
+            z_out[e0 + i] = z[i];
+            xt_out[e0 + i] = __fadd_rn(__fmul_rn(sa, x0[e0 + i]), __fmul_rn(s1m, z[i]));
+        }
+    }
+}
+
+struct BpdDev {
+    long per_sample, groups;
+    int chunks;
+    const float* coef;
+    const int64_t* t;
+    int step_index;
+    const float *x0, *xt, *z, *oc, *ou, *scale;
+    const uint8_t* mask;
+    const float *motion, *mean;
+    int clip, prior;
+    float prior_lv;
+    float *pred, *part;
+};
+
+// approx_standard_normal_cdf (losses.py:42-47); th.pow(x, 3) is x*x*x
+__device__ __forceinline__ float bpd_cdf(float x) {
+    const float x3 = __fmul_rn(__fmul_rn(x, x), x);
+    const float u = __fmul_rn(0.7978845608028654f, __fadd_rn(x, __fmul_rn(0.044715f, x3)));
+    return __fmul_rn(0.5f, __fadd_rn(1.0f, tanhf(u)));
+}
+
+constexpr int BPD_GROUPS = GDX_BPD_CHUNK / 4;      // float4 groups per block: 256 threads x 4 groups
+
+// One block = one GDX_BPD_CHUNK-element slice of one sample (grid (chunks, B)): per-thread partial sums of the three
+// quantities in element order, wave64 shuffle reduction, the four waves through LDS, then ONE ordinary store of the
+// block's three sums to part[(b*chunks + chunk)*4 ..]; bpd_finish_kernel adds a sample's chunks in sequence.  The
+// summation order is a function of J*T alone, so a sample's numbers do not depend on the batch around it.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
+    __shared__ float red[4][3];
+    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const long idx = a.t ? a.t[b] : a.step_index;
+    const float* c = a.coef + idx * 8;
+    const float pm1 = c[0], pm2 = c[1], lv1 = c[2], lv2 = c[3], sra = c[4], sa = c[5], srm1 = c[7];
+    // the per-step scalars of normal_kl / the decoder term, in torch's op order on the expanded fp32 tables
+    const float klc = a.prior ? __fadd_rn(__fsub_rn(-1.0f, a.prior_lv), expf(a.prior_lv))
+                              : __fadd_rn(__fsub_rn(__fadd_rn(-1.0f, lv2), lv1), expf(__fsub_rn(lv1, lv2)));
+    const float e2 = expf(-lv2);
+    const float inv_std = expf(-__fmul_rn(0.5f, lv2));
+    const float bin = (float)(1.0 / 255.0);
+    const bool first = idx == 0;
+    const float sc = a.ou ? a.scale[b] : 0.0f;
+    const long base = (long)b * a.per_sample;
+    float s_vb = 0.0f, s_x = 0.0f, s_e = 0.0f;
+    for (int it = 0; it < BPD_GROUPS / 256; ++it) {
+        const long grp = (long)chunk * BPD_GROUPS + it * 256 + tid;
+        if (grp >= a.groups) break;
+        const long e0 = base + 4L * grp;
+        const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
+        f32x4 x0;
+        if (VEC) x0 = *reinterpret_cast<const f32x4*>(a.x0 + e0);
+        else for (int i = 0; i < 4; ++i) x0[i] = i < nval ? a.x0[e0 + i] : 0.f;
+        if (a.prior) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float m = __fmul_rn(sa, x0[i]);
+                if (i < nval) s_vb = __fadd_rn(s_vb, __fmul_rn(0.5f, __fadd_rn(klc, __fmul_rn(m, m))));
+            }
+            continue;
+        }
+        f32x4 xt, p, z, mm;
+        if (VEC) {
+            xt = *reinterpret_cast<const f32x4*>(a.xt + e0);
+            p = *reinterpret_cast<const f32x4*>(a.oc + e0);
+        } else {
+            for (int i = 0; i < 4; ++i) { xt[i] = i < nval ? a.xt[e0 + i] : 0.f; p[i] = i < nval ? a.oc[e0 + i] : 0.f; }
+        }
+        if (a.ou) {
+            f32x4 u;
+            if (VEC) u = *reinterpret_cast<const f32x4*>(a.ou + e0);
+            else for (int i = 0; i < 4; ++i) u[i] = i < nval ? a.ou[e0 + i] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) p[i] = __fadd_rn(u[i], __fmul_rn(sc, __fsub_rn(p[i], u[i])));
+        }
+        if (a.mask) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < nval && a.mask[e0 + i]) p[i] = a.motion[e0 + i];
+        }
+        if (a.clip) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) p[i] = p[i] < -1.0f ? -1.0f : (p[i] > 1.0f ? 1.0f : p[i]);
+        }
+        if (a.z) {
+            if (VEC) z = *reinterpret_cast<const f32x4*>(a.z + e0);
+            else for (int i = 0; i < 4; ++i) z[i] = i < nval ? a.z[e0 + i] : 0.f;
+        } else {
+            z = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if (a.mean) {
+            if (VEC) mm = *reinterpret_cast<const f32x4*>(a.mean + e0);
+            else for (int i = 0; i < 4; ++i) mm[i] = i < nval ? a.mean[e0 + i] : 0.f;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mm[i] = __fadd_rn(__fmul_rn(pm1, p[i]), __fmul_rn(pm2, xt[i]));
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float v;
+            if (first) {            // discretized_gaussian_log_likelihood (losses.py:50-77), block-uniform branch
+                const float cx = __fsub_rn(x0[i], mm[i]);
+                const float cp = bpd_cdf(__fmul_rn(inv_std, __fadd_rn(cx, bin)));
+                const float cm = bpd_cdf(__fmul_rn(inv_std, __fsub_rn(cx, bin)));
+                const float lp = x0[i] < -0.999f ? logf(fmaxf(cp, 1e-12f))
+                               : (x0[i] > 0.999f ? logf(fmaxf(__fsub_rn(1.0f, cm), 1e-12f))
+                                                 : logf(fmaxf(__fsub_rn(cp, cm), 1e-12f)));
+                v = -lp;
+            } else {                // normal_kl (losses.py:33-39)
+                const float mt = __fadd_rn(__fmul_rn(pm1, x0[i]), __fmul_rn(pm2, xt[i]));
+                const float dm = __fsub_rn(mt, mm[i]);
+                v = __fmul_rn(0.5f, __fadd_rn(klc, __fmul_rn(__fmul_rn(dm, dm), e2)));
+            }
+            const float dx = __fsub_rn(p[i], x0[i]);
+            const float eps = __fdiv_rn(__fsub_rn(__fmul_rn(sra, xt[i]), p[i]), srm1);
+            const float de = __fsub_rn(eps, z[i]);
+            if (i < nval) {
+                s_vb = __fadd_rn(s_vb, v);
+                s_x = __fadd_rn(s_x, __fmul_rn(dx, dx));
+                s_e = __fadd_rn(s_e, __fmul_rn(de, de));
+            }
+        }
+        if (a.pred) {
+            if (VEC) *reinterpret_cast<f32x4*>(a.pred + e0) = p;
+            else for (int i = 0; i < nval; ++i) a.pred[e0 + i] = p[i];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s_vb = __fadd_rn(s_vb, __shfl_down(s_vb, off, 64));
+        s_x = __fadd_rn(s_x, __shfl_down(s_x, off, 64));
+        s_e = __fadd_rn(s_e, __shfl_down(s_e, off, 64));
+    }
+    if ((tid & 63) == 0) { red[tid >> 6][0] = s_vb; red[tid >> 6][1] = s_x; red[tid >> 6][2] = s_e; }
+    __syncthreads();
+    if (tid < 3) {
+        const float s = __fadd_rn(__fadd_rn(__fadd_rn(red[0][tid], red[1][tid]), red[2][tid]), red[3][tid]);
+        a.part[((long)b * a.chunks + chunk) * 4 + tid] = s;
+    }
+}
+
+// out[b*ld + col] = (sum of the sample's chunk sums, in chunk order) / (J*T)  [ / ln 2 for the bound ]: mean_flat(.) / np.log(2.0)
+__global__ void bpd_finish_kernel(const float* __restrict__ part, int chunks, long per_sample, int batch, float* vb,
+                                  float* xs, float* mse, int ld, int col) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * 3) return;
+    const int b = i / 3, q = i % 3;
+    float* out = q == 0 ? vb : (q == 1 ? xs : mse);
+    if (!out) return;
+    float s = 0.0f;
+    for (int ch = 0; ch < chunks; ++ch) s = __fadd_rn(s, part[((long)b * chunks + ch) * 4 + q]);
+    float m = __fdiv_rn(s, (float)per_sample);
+    if (q == 0) m = __fdiv_rn(m, 0.6931471805599453f);
+    out[(long)b * ld + col] = m;
+}
+
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, float* out, int B, int64_t per_sample,
                             hipStream_t s) {
     const long total = (long)B * per_sample;
@@ -539,4 +725,58 @@ extern "C" int gdx_randn(float* out, int32_t batch, int64_t per_sample, uint64_t
     hipLaunchKernelGGL(gdx::randn_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, batch,
                        (long)per_sample, groups, philox_seed, sample_offset, rng_step);
     return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_randn: launch failed");
+}
+
+static inline bool aligned16(const void* p) { return !((uintptr_t)p & 15); }
+
+extern "C" int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream) {
+    using namespace gdx;
+    if (!a) return gdx_set_error_("gdx_bpd_terms: null argument");
+    if (!a->coef || !a->x_start || !a->workspace) return gdx_set_error_("gdx_bpd_terms: null argument");
+    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return gdx_set_error_("gdx_bpd_terms: bad shape");
+    if (a->prior) {
+        if (!a->vb) return gdx_set_error_("gdx_bpd_terms: the prior term needs vb");
+    } else {
+        if (!a->x_t || !a->x0_cond) return gdx_set_error_("gdx_bpd_terms: null argument");
+        if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_bpd_terms: CFG needs scale");
+        if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_bpd_terms: mask without motion");
+        if (a->mse && !a->noise) return gdx_set_error_("gdx_bpd_terms: mse needs noise");
+    }
+    if (a->ld <= 0 || a->col < 0 || a->col >= a->ld) return gdx_set_error_("gdx_bpd_terms: bad output column");
+    BpdDev d;
+    d.per_sample = (long)a->njoints * a->frames;
+    d.groups = (d.per_sample + 3) / 4;
+    d.chunks = (int)((d.per_sample + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK);
+    if (a->batch == 0 || d.per_sample == 0) return 0;
+    d.coef = a->coef; d.t = a->t; d.step_index = a->step_index;
+    d.x0 = a->x_start; d.xt = a->x_t; d.z = a->noise; d.oc = a->x0_cond; d.ou = a->x0_uncond; d.scale = a->scale;
+    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion; d.mean = a->model_mean;
+    d.clip = a->clip_denoised; d.prior = a->prior; d.prior_lv = a->prior_log_variance;
+    d.pred = a->prior ? nullptr : a->pred_xstart; d.part = a->workspace;
+    const bool vec = d.per_sample % 4 == 0 && aligned16(d.x0) && aligned16(d.xt) && aligned16(d.z) && aligned16(d.oc) &&
+                     aligned16(d.ou) && aligned16(d.mean) && aligned16(d.pred);
+    const dim3 grid(d.chunks, a->batch), block(256);
+    if (vec) hipLaunchKernelGGL(bpd_terms_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
+    else hipLaunchKernelGGL(bpd_terms_kernel<false>, grid, block, 0, (hipStream_t)stream, d);
+    if (hipGetLastError() != hipSuccess) return gdx_set_error_("gdx_bpd_terms: launch failed");
+    hipLaunchKernelGGL(bpd_finish_kernel, dim3((a->batch * 3 + 63) / 64), dim3(64), 0, (hipStream_t)stream, d.part, d.chunks,
+                       d.per_sample, a->batch, a->vb, a->prior ? nullptr : a->xstart_mse, a->prior ? nullptr : a->mse, a->ld,
+                       a->col);
+    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_bpd_terms: launch failed");
+}
+
+// internal (api.hip, gdx_bpd_loop): x_t and the stored Philox noise of one step (bpd_xt_kernel)
+int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
+                uint32_t step, float* z_out, float* xt_out, void* stream) {
+    using namespace gdx;
+    const long groups = (per_sample + 3) / 4, total = groups * batch;
+    if (total == 0) return 0;
+    const dim3 grid((total + 255) / 256), block(256);
+    if (per_sample % 4 == 0 && aligned16(x0) && aligned16(z_out) && aligned16(xt_out))
+        hipLaunchKernelGGL(bpd_xt_kernel<true>, grid, block, 0, (hipStream_t)stream, x0, coef, idx, batch, per_sample, groups, seed,
+                           sample_offset, step, z_out, xt_out);
+    else
+        hipLaunchKernelGGL(bpd_xt_kernel<false>, grid, block, 0, (hipStream_t)stream, x0, coef, idx, batch, per_sample, groups,
+                           seed, sample_offset, step, z_out, xt_out);
+    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_bpd_loop: x_t launch failed");
 }

@@ -9,6 +9,8 @@ coefficient rows; every per-element operation runs in libgdx.so:
   * `gdx_forward`         the denoiser (through the model callable protocol `model(x, ts, **kw)`)
   * `gdx_sampler_update`  CFG blend + inpainting + posterior mean / DDIM step + noise, one pass
   * `gdx_sample_loop`     the whole loop enqueued from C++ with in-kernel Philox noise
+  * `gdx_bpd_terms` / `gdx_bpd_loop`   the variational bound in bits/dim (`_vb_terms_bpd` :1192-1225, `_prior_bpd`
+                          :1519-1535, `calc_bpd_loop` :1537-1592, and `training_losses` under LossType.KL / RESCALED_KL)
 
 Configured mode = the one the reference hard-codes (`utils/model_util.py:37-72`): START_X mean, FIXED_SMALL / FIXED_LARGE
 variance; this is what `gdx_sample_loop` runs.  The other two readings of the denoiser output, EPSILON and PREVIOUS_X
@@ -595,25 +597,194 @@ class GaussianDiffusion:
     def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, dataset=None):
         """FORWARD half of the reference's training_losses (:1227-1352) in its configured mode (LossType.MSE, START_X,
         fixed variance, lambda_vel = lambda_rcxyz = lambda_fc = 0): x_t = q_sample(x_start, t, noise), the model's x0
-        prediction, terms['rot_mse'] = masked_l2(x_start, prediction, y['mask']), terms['loss'] = rot_mse.  The values are
-        those the reference would log; there is no autograd graph behind them (training is out of scope)."""
+        prediction, terms['rot_mse'] = masked_l2(x_start, prediction, y['mask']), terms['loss'] = rot_mse.  Under LossType.KL /
+        RESCALED_KL (:1258-1268) terms['loss'] is the bound's term at t from _vb_terms_bpd (times num_timesteps when rescaled).
+        The values are those the reference would log; there is no autograd graph behind them (training is out of scope,
+        SURVEY 2.1)."""
         from . import gaussian_diffusion as _gd
-        if self.loss_type not in (_gd.LossType.MSE, _gd.LossType.RESCALED_MSE):
+        vb_loss = self.loss_type in (_gd.LossType.KL, _gd.LossType.RESCALED_KL)
+        if not vb_loss and self.loss_type not in (_gd.LossType.MSE, _gd.LossType.RESCALED_MSE):
             raise NotImplementedError(self.loss_type)
         self._check_supported()
         for lam in ("lambda_vel", "lambda_rcxyz", "lambda_fc"):
-            if getattr(self, lam, 0.0):
+            if getattr(self, lam, 0.0) and not vb_loss:
                 raise NotImplementedError(f"{lam} > 0 needs the xyz / velocity terms, which are not on the path")
         mask = model_kwargs["y"]["mask"]                       # KeyError / TypeError like the reference (:1243)
         if noise is None:
             noise = th.randn_like(x_start)
         x_t = self.q_sample(x_start, t, noise=noise)
+        if vb_loss:
+            # LossType.KL / RESCALED_KL (reference :1258-1268): the bound's term at t, times num_timesteps when rescaled
+            loss = self._vb_terms_bpd(model=model, x_start=x_start, x_t=x_t, t=t, clip_denoised=False,
+                                      model_kwargs=model_kwargs)["output"]
+            if self.loss_type == _gd.LossType.RESCALED_KL:
+                loss = loss * self.num_timesteps
+            return {"loss": loss}
         with th.no_grad():
             model_output = self._call_model(model, x_t, t, model_kwargs)
         assert model_output.shape == x_start.shape
         terms = {"rot_mse": self.masked_l2(x_start, model_output, mask)}
         terms["loss"] = terms["rot_mse"]
         return terms
+
+    # ------------------------------------------------------------------ variational bound (reference :1192-1225, :1519-1592)
+    def bpd_table(self, device):
+        """[num_timesteps, 8] fp32 rows consumed by gdx_bpd_terms / gdx_bpd_loop (include/gdx.h), each the fp64 table rounded
+        once (.float(), reference :1595-1608): posterior_mean_coef1, posterior_mean_coef2, posterior_log_variance_clipped,
+        the model log-variance of _model_variance_tables(), sqrt_recip_alphas_cumprod, sqrt_alphas_cumprod,
+        sqrt_one_minus_alphas_cumprod, sqrt_recipm1_alphas_cumprod."""
+        key = ("bpd", self.model_var_type, str(device))
+        if key not in self._coef_cache:
+            f32 = lambda a: th.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).float()   # noqa: E731
+            c = th.zeros(self.num_timesteps, 8, dtype=th.float32)
+            for col, tab in enumerate((self.posterior_mean_coef1, self.posterior_mean_coef2,
+                                       self.posterior_log_variance_clipped, self._model_variance_tables()[1],
+                                       self.sqrt_recip_alphas_cumprod, self.sqrt_alphas_cumprod,
+                                       self.sqrt_one_minus_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod)):
+                c[:, col] = f32(tab)
+            self._coef_cache[key] = c.to(device)
+        return self._coef_cache[key]
+
+    def _prior_log_variance(self):
+        """log_one_minus_alphas_cumprod at the last step, rounded to fp32 as _extract_into_tensor would."""
+        return float(np.float32(self.log_one_minus_alphas_cumprod[self.num_timesteps - 1]))
+
+    def _bpd_step(self, model, x_start, x_t, t, clip_denoised, model_kwargs, noise=None):
+        """One denoiser call + gdx_bpd_terms -> (vb [B], xstart_mse [B], mse [B] or None, pred_xstart)."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        self._check_supported()
+        E.require_device(x_t, "x_t")
+        xs, xt = E.f32c(x_start, "x_start"), E.f32c(x_t, "x_t")
+        assert xs.shape == xt.shape and t.shape == (xs.shape[0],)
+        tt = E.require_device(t, "t").to(th.int64).contiguous()
+        with th.no_grad():
+            raw = E.f32c(self._call_model(model, xt, t, model_kwargs), "model output")
+        assert raw.shape == xt.shape
+        y = model_kwargs["y"]                                             # KeyError like the reference (:307)
+        mask = motion = None
+        if "inpainting_mask" in y.keys() and "inpainted_motion" in y.keys():
+            mask = E.require_device(y["inpainting_mask"], "inpainting_mask").to(th.bool).contiguous()
+            motion = E.f32c(y["inpainted_motion"], "inpainted_motion")
+            assert raw.shape == mask.shape == motion.shape
+        x0, mean = raw, None
+        if self.model_mean_type != ModelMeanType.START_X:
+            # EPSILON / PREVIOUS_X (reference :357-372): the x0 prediction comes from gdx_plms_update kind 8; PREVIOUS_X also
+            # hands the raw output over as the model's posterior mean (:361)
+            assert mask is None, 'This feature supports only X_start pred for mow!'
+            if self.model_mean_type == ModelMeanType.EPSILON:
+                x0 = E.plms_update(8, self._xstart_table(xt.device), tt, xt, raw)
+            else:
+                x0, mean = E.plms_update(8, self._xstart_table(xt.device), tt, raw, xt), raw
+        return E.bpd_terms(self.bpd_table(xt.device), xs, xt, x0, noise=E.f32c(noise, "noise") if noise is not None else None,
+                           t=tt, inpaint_mask=mask, inpaint_motion=motion, model_mean=mean, clip_denoised=clip_denoised)
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """A term of the variational bound in bits/dim (reference :1192-1225): the decoder NLL where t == 0, else
+        KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t)); {'output': [B], 'pred_xstart'}.  One fused kernel pass (gdx_bpd_terms)."""
+        vb, _, _, pred = self._bpd_step(model, x_start, x_t, t, clip_denoised, model_kwargs)
+        return {"output": vb, "pred_xstart": pred}
+
+    def _prior_bpd(self, x_start):
+        """The prior term KL(q(x_T | x_0) || N(0, 1)) in bits/dim (reference :1519-1535) -> [B]."""
+        xs = E.f32c(x_start, "x_start")
+        return E.bpd_prior(self.bpd_table(xs.device), xs, self.num_timesteps - 1, self._prior_log_variance())
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, *, rng="torch", philox_seed=0,
+                      sample_offset=0, noise_tape=None, progress=False, fused=True):
+        """The whole variational bound in bits/dim with the per-timestep x0 / eps error curves (reference :1537-1592):
+        {'total_bpd' [B], 'prior_bpd' [B], 'vb' / 'xstart_mse' / 'mse' [B, num_timesteps]}, columns in descending t.
+        A native denoiser (or its ClassifierFreeSampleModel) read as START_X runs the loop inside libgdx (gdx_bpd_loop);
+        any other callable, EPSILON / PREVIOUS_X, or fused=False go step by step through _vb_terms_bpd's kernel.  Noise:
+        rng="torch" draws one normal_() per step in the reference's order (:1563), rng="philox" is counter-based (draw number
+        = executed step k, keyed by sample_offset + b), noise_tape [num_timesteps, B, J, 1, T] replays recorded draws."""
+        if rng not in ("torch", "philox"):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        if model_kwargs is None:
+            model_kwargs = {}
+        self._check_supported()
+        xs = E.f32c(x_start, "x_start")
+        B, n, dev_ = xs.shape[0], self.num_timesteps, xs.device
+        tape = E.f32c(noise_tape, "noise_tape") if noise_tape is not None else None
+        if tape is not None:
+            assert tuple(tape.shape) == (n, *xs.shape), "noise_tape must be [num_timesteps, B, J, 1, T]"
+        if fused and _is_native(model) and self.model_mean_type == ModelMeanType.START_X:
+            vb, xm, em, prior = self._fused_bpd_loop(model, xs, clip_denoised, model_kwargs, rng, philox_seed, sample_offset,
+                                                     tape, progress)
+        else:
+            vb, xm, em = (th.empty(B, n, device=dev_, dtype=th.float32) for _ in range(3))
+            steps = range(n)
+            if progress:
+                from tqdm.auto import tqdm
+                steps = tqdm(steps)
+            for k in steps:
+                t = th.full((B,), n - 1 - k, device=dev_, dtype=th.long)
+                if tape is not None:
+                    z = tape[k]
+                elif rng == "philox":
+                    z = E.randn(tuple(xs.shape), dev_, philox_seed, sample_offset, k)
+                else:
+                    z = th.randn_like(xs)
+                x_t = self.q_sample(xs, t, noise=z)
+                vb[:, k], xm[:, k], em[:, k], _ = self._bpd_step(model, xs, x_t, t, clip_denoised, model_kwargs, noise=z)
+            prior = self._prior_bpd(xs)
+        return {"total_bpd": vb.sum(dim=1) + prior, "prior_bpd": prior, "vb": vb, "xstart_mse": xm, "mse": em}
+
+    def _fused_bpd_loop(self, model, xs, clip_denoised, model_kwargs, rng, philox_seed, sample_offset, tape, progress):
+        """gdx_bpd_loop, issued block by block like _fused_loop (torch-generator noise is drawn NOISE_BLOCK steps ahead)."""
+        from ..model.cfg_sampler import ClassifierFreeSampleModel
+        y = model_kwargs["y"]
+        inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
+        B, J, F, T = xs.shape
+        inner._check_inputs(xs, y)
+        if hasattr(inner, "cl_head") and T % 10 != 0:
+            from ..model.mdm import _window_error
+            raise _window_error(T, 10)
+        if self.rescale_timesteps:
+            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
+        eng = inner._get_engine(xs.device)
+        eng.prepare(B, T)
+        eng.set_condition(y["seed"], y["mfcc"], cache=False)
+        if isinstance(model, ClassifierFreeSampleModel):
+            mode, scale = GDX_CFG, E.f32c(y["scale"].reshape(-1), "y['scale']")
+        else:
+            mode, scale = (GDX_UNCOND if y.get("uncond", False) else GDX_COND), None
+        mask = motion = None
+        if "inpainting_mask" in y and "inpainted_motion" in y:
+            mask = E.require_device(y["inpainting_mask"], "inpainting_mask").to(th.bool).contiguous()
+            motion = E.f32c(y["inpainted_motion"], "inpainted_motion")
+            assert mask.shape == motion.shape == xs.shape
+        n = self.num_timesteps
+        vb, xm, em = (th.empty(B, n, device=xs.device, dtype=th.float32) for _ in range(3))
+        prior = th.empty(B, device=xs.device, dtype=th.float32)
+        draw = tape is None and rng == "torch"
+        block = noise_block_steps(n, B * J * F * T) if draw else (min(n, NOISE_BLOCK) if progress else n)
+        buf = th.empty((block, B, J, F, T), device=xs.device, dtype=th.float32) if draw else None
+        bar = None
+        if progress:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=n)
+        coef, tmap = self.bpd_table(xs.device), self._timestep_map()
+        k = 0
+        while k < n:
+            nb = min(block, n - k)
+            if draw:
+                for j in range(nb):
+                    buf[j].normal_()
+                blk = buf
+            else:
+                blk = tape[k:] if tape is not None else None
+            eng.bpd_loop(xs, mode, coef, tmap, vb, xm, em, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+                         noise_tape=blk, philox_seed=philox_seed, sample_offset=sample_offset, clip_denoised=clip_denoised,
+                         run_steps=nb, k_base=k, prior_bpd=prior if k + nb == n else None,
+                         prior_log_variance=self._prior_log_variance())
+            k += nb
+            if bar is not None:
+                th.cuda.current_stream(xs.device).synchronize()
+                bar.update(nb)
+        if bar is not None:
+            bar.close()
+        return vb, xm, em, prior
 
     # ------------------------------------------------------------------ PLMS (reference :995-1190)
     def _pred_xstart(self, model, x, t, clip_denoised, denoised_fn, model_kwargs):

@@ -175,6 +175,21 @@ class Engine:
         _lib.check(self.lib.gdx_sample_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
         self._keep_loop = (tmap, ds)
 
+    def bpd_loop(self, x_start, mode, coef, timestep_map, vb, xstart_mse, mse, scale=None, inpaint_mask=None,
+                 inpaint_motion=None, noise_tape=None, philox_seed=0, sample_offset=0, clip_denoised=True, run_steps=0,
+                 k_base=0, prior_bpd=None, prior_log_variance=0.0):
+        """gdx_bpd_loop: steps k_base .. of the variational bound into column k of vb / xstart_mse / mse [B, num_steps]."""
+        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
+        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        a = _lib.BpdLoopArgs(mode=mode, num_steps=len(tmap), coef=coef.data_ptr(), timestep_map=tmap.ctypes.data,
+                             x_start=x_start.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
+                             inpaint_motion=p(inpaint_motion), noise_tape=p(noise_tape), philox_seed=philox_seed,
+                             sample_offset=sample_offset, clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
+                             k_base=k_base, prior_log_variance=prior_log_variance, vb=vb.data_ptr(),
+                             xstart_mse=xstart_mse.data_ptr(), mse=mse.data_ptr(), prior_bpd=p(prior_bpd))
+        _lib.check(self.lib.gdx_bpd_loop(self.handle, C.byref(a), _stream(x_start.device)), self.lib)
+        self._keep_loop = (tmap,)
+
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
         _lib.check(self.lib.gdx_forward_flops(self.handle, mode, C.byref(f)), self.lib)
@@ -213,6 +228,46 @@ def sampler_update(kind, coef, x, x0_cond, out, t=None, step_index=0, x0_uncond=
                         cond_coef=cond_coef.data_ptr() if cond_coef is not None else None,
                         clip_denoised=int(bool(clip_denoised)))
     _lib.check(lib.gdx_sampler_update(C.byref(a), _stream(x.device)), lib)
+    return out
+
+
+def bpd_workspace(batch, per_sample, device):
+    """Chunk-sum scratch of gdx_bpd_terms (include/gdx.h): 4 floats per (sample, GDX_BPD_CHUNK-element chunk)."""
+    chunks = (per_sample + _lib.GDX_BPD_CHUNK - 1) // _lib.GDX_BPD_CHUNK
+    return torch.empty(max(1, 4 * batch * chunks), device=device, dtype=torch.float32)
+
+
+def bpd_terms(coef, x_start, x_t, x0_cond, noise=None, t=None, step_index=0, x0_uncond=None, scale=None, inpaint_mask=None,
+              inpaint_motion=None, model_mean=None, clip_denoised=True, want_pred=True, want_mse=True):
+    """gdx_bpd_terms on [B,J,1,T] tensors -> (vb [B], xstart_mse [B], mse [B] or None, pred_xstart or None)."""
+    lib = _lib.load()
+    B, J, F, T = x_start.shape
+    dev = x_start.device
+    out = torch.empty(3, B, device=dev, dtype=torch.float32)
+    pred = torch.empty_like(x_start) if want_pred else None
+    ws = bpd_workspace(B, J * F * T, dev)
+    want_mse = want_mse and noise is not None
+    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
+    a = _lib.BpdArgs(batch=B, njoints=J * F, frames=T, step_index=step_index, coef=coef.data_ptr(), t=p(t),
+                     x_start=x_start.data_ptr(), x_t=x_t.data_ptr(), noise=p(noise), x0_cond=x0_cond.data_ptr(),
+                     x0_uncond=p(x0_uncond), scale=p(scale), inpaint_mask=p(inpaint_mask), inpaint_motion=p(inpaint_motion),
+                     model_mean=p(model_mean), clip_denoised=int(bool(clip_denoised)), prior=0, prior_log_variance=0.0,
+                     vb=out[0].data_ptr(), xstart_mse=out[1].data_ptr(), mse=out[2].data_ptr() if want_mse else None,
+                     ld=1, col=0, pred_xstart=p(pred), workspace=ws.data_ptr())
+    _lib.check(lib.gdx_bpd_terms(C.byref(a), _stream(dev)), lib)
+    return out[0], out[1], (out[2] if want_mse else None), pred
+
+
+def bpd_prior(coef, x_start, step_index, prior_log_variance):
+    """The prior term of the bound (gdx_bpd_terms, prior mode) -> [B]."""
+    lib = _lib.load()
+    B, J, F, T = x_start.shape
+    out = torch.empty(B, device=x_start.device, dtype=torch.float32)
+    ws = bpd_workspace(B, J * F * T, x_start.device)
+    a = _lib.BpdArgs(batch=B, njoints=J * F, frames=T, step_index=step_index, coef=coef.data_ptr(),
+                     x_start=x_start.data_ptr(), prior=1, prior_log_variance=prior_log_variance, vb=out.data_ptr(), ld=1,
+                     col=0, workspace=ws.data_ptr())
+    _lib.check(lib.gdx_bpd_terms(C.byref(a), _stream(x_start.device)), lib)
     return out
 
 

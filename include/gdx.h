@@ -282,6 +282,84 @@ typedef struct {
 } gdx_loop_args_t;
 int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream);
 
+/* ---- variational bound (evaluation) ----------------------------------------------------- */
+/* One term of the variational bound in bits/dim plus the two per-step error curves, fused over [B,J,1,T]: replaces
+ * _vb_terms_bpd (gaussian_diffusion.py:1192-1225) with its helpers normal_kl / discretized_gaussian_log_likelihood
+ * (diffusion/losses.py:12-77), the body of calc_bpd_loop's step (:1576-1578) and _prior_bpd (:1519-1535).
+ * Per element, coefficient row c = coef[idx] = (posterior_mean_coef1, posterior_mean_coef2, posterior_log_variance_clipped,
+ * model log-variance, sqrt_recip_alphas_cumprod, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod,
+ * sqrt_recipm1_alphas_cumprod), idx = t[b] if t != NULL else step_index:
+ *   pred    = x0_cond -> CFG blend -> inpainting blend -> clamp, exactly as in the sampler update
+ *   m_true  = c0*x_start + c1*x_t;   m_model = model_mean if given else c0*pred + c1*x_t
+ *   kl      = 0.5*(-1 + c3 - c2 + exp(c2 - c3) + (m_true - m_model)^2 * exp(-c3))
+ *   nll     = -log of the discretised Gaussian(m_model, exp(0.5*c3)) at x_start (tanh cdf, +-1/255 bin, 1e-12 clamps)
+ *   vb[b]         = mean(idx == 0 ? nll : kl) / ln 2
+ *   xstart_mse[b] = mean((pred - x_start)^2);   mse[b] = mean(((c4*x_t - pred)/c7 - noise)^2)
+ * each written at [b*ld + col] (an output may be NULL).  prior != 0 selects the prior term instead:
+ *   vb[b] = mean(0.5*(-1 - prior_log_variance + exp(prior_log_variance) + (c5*x_start)^2)) / ln 2
+ * and needs only coef, x_start, vb and workspace.  All arithmetic is fp32 with separately rounded products / sums and
+ * accurate exp / log / tanh.  A sample's numbers are sums in a fixed order (thread, wave, block, then the
+ * ceil(J*T / GDX_BPD_CHUNK) blocks of the sample in sequence through `workspace`): no atomics, so they do not depend on the
+ * batch the sample sits in.  workspace: device, 4 * batch * ceil(J*T / GDX_BPD_CHUNK) floats, the caller's. */
+#define GDX_BPD_CHUNK 4096
+typedef struct {
+    int32_t batch, njoints, frames;
+    int32_t step_index;        /* used when t == NULL */
+    const float* coef;         /* [num_steps][8], rows as above */
+    const int64_t* t;          /* [B] or NULL */
+    const float* x_start;
+    const float* x_t;
+    const float* noise;        /* the z of x_t = c5*x_start + c6*z; NULL only when mse == NULL */
+    const float* x0_cond;      /* START_X model output (cond pass), or an already formed pred_xstart */
+    const float* x0_uncond;    /* NULL or uncond pass */
+    const float* scale;        /* [B] when x0_uncond != NULL */
+    const uint8_t* inpaint_mask;   /* NULL or bool bytes [B,J,1,T] */
+    const float* inpaint_motion;
+    const float* model_mean;   /* NULL, or the model's posterior mean when it is not c0*pred + c1*x_t (PREVIOUS_X: the raw
+                                  output, with x0_cond = the x0 prediction formed by gdx_plms_update kind 8) */
+    int32_t clip_denoised;
+    int32_t prior;
+    float prior_log_variance;  /* log_one_minus_alphas_cumprod[num_steps - 1] rounded to fp32 */
+    float* vb;
+    float* xstart_mse;
+    float* mse;
+    int32_t ld, col;
+    float* pred_xstart;        /* NULL or [B,J,1,T]: pred */
+    float* workspace;
+} gdx_bpd_args_t;
+int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream);
+
+/* replaces calc_bpd_loop (gaussian_diffusion.py:1537-1592) for a START_X denoiser with fixed variance: for executed step
+ * k = k_base .. (index i = num_steps - 1 - k) it forms x_t = sqrt_alphas_cumprod[i]*x_start + sqrt_one_minus_alphas_cumprod[i]*z_k
+ * (q_sample, :233-251), runs the denoiser at timestep_map[i] and the fused terms above, all enqueued on `stream` with no
+ * host synchronisation.  z_k is slice k - k_base of noise_tape ([steps of this call][B,J,1,T]) or, when noise_tape == NULL,
+ * Philox N(0,1) keyed by (philox_seed; sample_offset + b; draw k; element).  vb / xstart_mse / mse: device [B][num_steps],
+ * column k holds timestep num_steps - 1 - k (the reference appends in descending t).  run_steps > 0 executes only that many
+ * steps (block-wise issue); 0 = down to index 0.  prior_bpd (NULL or device [B]) receives the prior term.  Graph replay does
+ * not apply to this loop.  Refusals come before the first HIP call. */
+typedef struct {
+    int32_t mode;              /* GDX_COND / GDX_UNCOND / GDX_CFG */
+    int32_t num_steps;
+    const float* coef;         /* device [num_steps][8], rows of the terms above */
+    const int64_t* timestep_map;   /* HOST [num_steps] */
+    const float* x_start;
+    const float* scale;        /* [B] for GDX_CFG */
+    const uint8_t* inpaint_mask;
+    const float* inpaint_motion;
+    const float* noise_tape;   /* NULL -> Philox */
+    uint64_t philox_seed;
+    uint64_t sample_offset;
+    int32_t clip_denoised;
+    int32_t run_steps;
+    int32_t k_base;
+    float prior_log_variance;
+    float* vb;
+    float* xstart_mse;
+    float* mse;
+    float* prior_bpd;
+} gdx_bpd_loop_args_t;
+int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* stream);
+
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  Off by
  * default: on ROCm 7.2 the replay measured ~10 % slower than eager launches even for launch-dominated small batches

@@ -1,0 +1,258 @@
+"""calc_bpd_loop / _vb_terms_bpd / _prior_bpd / training_losses(KL) on the GPU: gdx_bpd_terms, gdx_bpd_loop (include/gdx.h).
+
+Allowances (tests/bpd_restatement.py::worst_ratios): xstart_mse / mse FWD_TOL and total_bpd LOOP_TOL relative to the
+reference's fp32 fixture; every vb / prior_bpd entry 10 x the reference's own fp32-vs-fp64 deviation at that entry, floored
+at FWD_TOL * max|fixture|.  Each case prints its worst error / allowance ratios (`bpd-ratio ...`, run with -s)."""
+import numpy as np
+import pytest
+import torch
+
+import bpd_restatement as R
+from conftest import load_golden, rel_err, weights_from
+from test_bpd_host import CASES
+from test_gpu_parity import TINY, build_model, dev
+
+pytestmark = pytest.mark.gpu
+ARCHS = ["mdm", "mdm_old"]
+
+
+def _diffusion(case="small_clip", loss="MSE", resp=(20,), steps=1000, schedule="cosine"):
+    from gesturediffusion_amd.diffusion import gaussian_diffusion as gd
+    from gesturediffusion_amd.diffusion.respace import SpacedDiffusion, space_timesteps
+    var, mean = CASES[case][:2]
+    if case == "lin100":
+        resp, steps, schedule = (100,), 100, "linear"
+    return SpacedDiffusion(use_timesteps=space_timesteps(steps, list(resp)), betas=gd.get_named_beta_schedule(schedule, steps),
+                           model_mean_type=getattr(gd.ModelMeanType, mean), model_var_type=getattr(gd.ModelVarType, var),
+                           loss_type=getattr(gd.LossType, loss))
+
+
+def _setup(arch, case, compute_dtype="fp32"):
+    from gesturediffusion_amd.model.cfg_sampler import ClassifierFreeSampleModel
+    g = load_golden(f"bpd_{arch}_tiny.npz")
+    d = dev()
+    m = build_model(arch, TINY, weights_from(load_golden(f"loops_{arch}_tiny.npz")))
+    m.compute_dtype = compute_dtype
+    _, _, clip, wrap, inp = CASES[case]
+    n1 = 1 if case == "lin100" else None
+    T = lambda k: torch.from_numpy(g[k][:n1]).to(d)   # noqa: E731
+    y = {"seed": T("seed"), "mfcc": T("mfcc")}
+    if wrap:
+        y["scale"] = T("scale")
+    if inp:
+        y["inpainting_mask"], y["inpainted_motion"] = T("inpainting_mask"), T("inpainted_motion")
+    tape = torch.from_numpy(g["tape100" if case == "lin100" else "tape"]).to(d)
+    return g, (ClassifierFreeSampleModel(m) if wrap else m), _diffusion(case), T("x_start"), tape, y, clip
+
+
+def _np(r):
+    return {k: v.cpu().numpy() for k, v in r.items()}
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("fused", [True, False])
+def test_calc_bpd_loop_vs_reference_fixture(arch, case, fused):
+    """1. The reference's calc_bpd_loop on the recorded noise tape: library loop (gdx_bpd_loop) and step-wise path."""
+    g, model, df, xs, tape, y, clip = _setup(arch, case)
+    r = df.calc_bpd_loop(model, xs, clip_denoised=clip, model_kwargs={"y": y}, noise_tape=tape, fused=fused)
+    assert r["vb"].shape == (xs.shape[0], df.num_timesteps) and r["total_bpd"].shape == (xs.shape[0],)
+    R.assert_case(_np(r), g, case, f"{arch}-{'fused' if fused else 'stepwise'}")
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+@pytest.mark.parametrize("case", ["small_clip", "cfg", "inpaint", "large"])
+def test_fused_equals_stepwise_and_blockwise_bit_for_bit(arch, case, monkeypatch):
+    """2. One gdx_bpd_loop call == the step-wise protocol == the loop issued in blocks of 7 steps (run_steps / k_base)."""
+    from gesturediffusion_amd.diffusion import gaussian_diffusion as gd
+    g, model, df, xs, tape, y, clip = _setup(arch, case)
+    kw = dict(clip_denoised=clip, model_kwargs={"y": y}, noise_tape=tape)
+    one = df.calc_bpd_loop(model, xs, **kw)
+    step = df.calc_bpd_loop(model, xs, fused=False, **kw)
+    monkeypatch.setattr(gd, "NOISE_BLOCK", 7)
+    blocks = df.calc_bpd_loop(model, xs, progress=True, **kw)
+    for k in R.OUTS:
+        assert torch.equal(one[k], step[k]), k
+        assert torch.equal(one[k], blocks[k]), k
+    assert torch.equal(one["total_bpd"], one["vb"].sum(dim=1) + one["prior_bpd"])
+
+
+@pytest.mark.parametrize("J,T", [(37, 23), (263, 196)])
+def test_bpd_terms_kernel_batch_independent_and_vs_restatement(J, T):
+    """3. gdx_bpd_terms alone (no forward): sample b in a B=1 call == row b of the B=5 call, bit for bit, at a per-sample
+    count that is not a multiple of 4 (scalar tail) and at one that spans 13 chunks; values against the fp64 restatement."""
+    from gesturediffusion_amd import engine as E
+    from gesturediffusion_amd.diffusion import gaussian_diffusion as gd
+    d = dev()
+    df = gd.GaussianDiffusion(betas=gd.get_named_beta_schedule("cosine", 1000), model_mean_type=gd.ModelMeanType.START_X,
+                              model_var_type=gd.ModelVarType.FIXED_LARGE, loss_type=gd.LossType.MSE)
+    coef = df.bpd_table(d)
+    gen = torch.Generator().manual_seed(J * T)
+    B = 5
+    x0, z, oc, ou, motion = (torch.randn(B, J, 1, T, generator=gen) * s for s in (0.6, 1.0, 0.7, 0.7, 0.5))
+    mask = torch.rand(B, J, 1, T, generator=gen) < 0.2
+    t = torch.tensor([0, 1, 17, 500, 999])
+    scale = torch.tensor([2.5, 1.0, 0.0, -1.0, 3.0])
+    xt = df.q_sample(x0.to(d), t.to(d), noise=z.to(d))
+    dv = [v.to(d) for v in (x0, z, oc, ou, motion, mask, scale, t)]
+    full = E.bpd_terms(coef, dv[0], xt, dv[2], noise=dv[1], t=dv[7], x0_uncond=dv[3], scale=dv[6], inpaint_mask=dv[5],
+                       inpaint_motion=dv[4], clip_denoised=True)
+    for b in range(B):
+        s = slice(b, b + 1)
+        one = E.bpd_terms(coef, dv[0][s].clone(), xt[s].clone(), dv[2][s].clone(), noise=dv[1][s].clone(), t=dv[7][s].clone(),
+                          x0_uncond=dv[3][s].clone(), scale=dv[6][s].clone(), inpaint_mask=dv[5][s].clone(),
+                          inpaint_motion=dv[4][s].clone(), clip_denoised=True)
+        for a, w in zip(one, full):
+            assert torch.equal(a, w[s]), b
+    tab = R.tables(df.betas, "FIXED_LARGE")
+    pred = R.blend(oc.numpy(), ou.numpy(), scale.numpy(), mask.numpy(), motion.numpy(), clip=True)
+    vb, xm, em = R.step_terms(tab, t.numpy(), x0.numpy(), xt.cpu().numpy(), z.numpy(), pred)
+    assert rel_err(full[3].cpu(), pred) < 1e-6
+    print("bpd-terms", J, T, rel_err(full[0].cpu(), vb), rel_err(full[1].cpu(), xm), rel_err(full[2].cpu(), em))
+    assert rel_err(full[1].cpu(), xm) < R.FWD_TOL and rel_err(full[2].cpu(), em) < R.FWD_TOL
+    assert rel_err(full[0].cpu(), vb) < R.FWD_TOL
+    prior = E.bpd_prior(coef, dv[0], 999, df._prior_log_variance())
+    assert torch.equal(prior[2:3], E.bpd_prior(coef, dv[0][2:3].clone(), 999, df._prior_log_variance()))
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_philox_loop_batch_independent_and_shard_invariant(arch):
+    """3 / 5. In-kernel Philox noise of the loop: sample b as a B=1 run with sample_offset=b == row b of the whole batch; a
+    shard with sample_offset equals its rows; the step-wise path (gdx_randn noise) gives the same bits."""
+    g, model, df, xs, tape, y, clip = _setup(arch, "small_clip")
+    kw = dict(clip_denoised=clip, rng="philox", philox_seed=11)
+    whole = df.calc_bpd_loop(model, xs, model_kwargs={"y": y}, **kw)
+    step = df.calc_bpd_loop(model, xs, model_kwargs={"y": y}, fused=False, **kw)
+    for b in range(xs.shape[0]):
+        yb = {k: v[b:b + 1].contiguous() for k, v in y.items()}
+        one = df.calc_bpd_loop(model, xs[b:b + 1].contiguous(), model_kwargs={"y": yb}, sample_offset=b, **kw)
+        for k in R.OUTS[1:]:                     # the kernels' own outputs (total_bpd is their torch sum)
+            assert torch.equal(one[k], whole[k][b:b + 1]), (k, b)
+    ys = {k: v[1:].contiguous() for k, v in y.items()}
+    shard = df.calc_bpd_loop(model, xs[1:].contiguous(), model_kwargs={"y": ys}, sample_offset=1, **kw)
+    for k in R.OUTS[1:]:
+        assert torch.equal(shard[k], whole[k][1:]), k
+        assert torch.equal(step[k], whole[k]), k
+    other = df.calc_bpd_loop(model, xs, model_kwargs={"y": y}, clip_denoised=clip, rng="philox", philox_seed=12)
+    assert not torch.equal(other["mse"], whole["mse"])
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_torch_rng_reproduces_with_the_generator_seed(arch):
+    """5. rng="torch" (the reference's own call shape): one normal_() per step from torch's generator, the same on the fused
+    and the step-wise path, reproducible from the seed."""
+    g, model, df, xs, tape, y, clip = _setup(arch, "small_noclip")
+    d = dev()
+    runs = []
+    for fused in (True, True, False):
+        torch.manual_seed(5)
+        torch.cuda.manual_seed_all(5)
+        runs.append(df.calc_bpd_loop(model, xs, clip_denoised=False, model_kwargs={"y": y}, fused=fused))
+    torch.manual_seed(6)
+    torch.cuda.manual_seed_all(6)
+    other = df.calc_bpd_loop(model, xs, False, {"y": y})
+    for k in R.OUTS:
+        assert torch.equal(runs[0][k], runs[1][k]) and torch.equal(runs[0][k], runs[2][k]), k
+    assert not torch.equal(other["mse"], runs[0]["mse"])
+    assert runs[0]["vb"].device == d and torch.isfinite(runs[0]["total_bpd"]).all()
+
+
+@pytest.mark.parametrize("arch,T", [("mdm_old", 196), ("mdm", 200)])
+def test_full_1000_step_bound_at_config2_shape(arch, T):
+    """4. 1000 steps at J=263, d=512, L=8, B=4: every step's three numbers from the step-wise path against the fp64 restatement
+    fed with that step's own pred_xstart (isolates the bound kernels from forward error); the fused loop equals the step-wise
+    numbers bit for bit; total_bpd == vb.sum(1) + prior_bpd."""
+    from gesturediffusion_amd.diffusion import gaussian_diffusion as gd
+    from gesturediffusion_amd.utils.init import init_state_dict, synthetic_inputs
+    cfg = dict(arch=arch, njoints=263, nfeats=1, latent_dim=512, ff_size=1024, num_layers=8, num_heads=4, seed_poses=10)
+    m = build_model(arch, cfg, init_state_dict(cfg, seed=0))
+    d = dev()
+    B, n = 4, 1000
+    x, seedp, mfcc = synthetic_inputs(cfg, B, T, seed=10)
+    xs = (x * 0.6).to(d)
+    y = {"seed": seedp.to(d), "mfcc": mfcc.to(d)}
+    df = gd.GaussianDiffusion(betas=gd.get_named_beta_schedule("cosine", n), model_mean_type=gd.ModelMeanType.START_X,
+                              model_var_type=gd.ModelVarType.FIXED_SMALL, loss_type=gd.LossType.MSE)
+    fused = df.calc_bpd_loop(m, xs, clip_denoised=True, model_kwargs={"y": y}, rng="philox", philox_seed=3)
+    tab = R.tables(df.betas, "FIXED_SMALL")
+    from gesturediffusion_amd import engine as E
+    x0n = xs.cpu().numpy()
+    got, want = np.empty((3, B, n)), np.empty((3, B, n))
+    for k in range(n):
+        t = torch.full((B,), n - 1 - k, device=d, dtype=torch.long)
+        z = E.randn(tuple(xs.shape), d, 3, 0, k)
+        x_t = df.q_sample(xs, t, noise=z)
+        vb, xm, em, pred = df._bpd_step(m, xs, x_t, t, True, {"y": y}, noise=z)
+        got[:, :, k] = torch.stack((vb, xm, em)).cpu().numpy()
+        want[:, :, k] = R.step_terms(tab, t.cpu().numpy(), x0n, x_t.cpu().numpy(), z.cpu().numpy(), pred.cpu().numpy())
+    for i, name in enumerate(("vb", "xstart_mse", "mse")):
+        err = np.abs(got[i] - want[i]).max() / np.abs(want[i]).max()
+        print(f"bpd-real {arch} T={T} {name}: max|err| / max|ref| = {err:.3g} (allowed {R.FWD_TOL})")
+        assert err < R.FWD_TOL, name
+        assert np.array_equal(fused[name].cpu().numpy().astype(np.float64), got[i]), name
+    assert torch.equal(fused["total_bpd"], fused["vb"].sum(dim=1) + fused["prior_bpd"])
+    assert rel_err(fused["prior_bpd"].cpu(), R.prior_term(tab, x0n)) < R.FWD_TOL
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_half_models_xstart_mse_within_stated_tolerance(arch, dtype):
+    """6. 16-bit denoisers: the bound's arithmetic stays fp32.  numerics.py states |out16 - out32| <= e = tol * max|out32| per
+    element, hence |mse16 - mse32| = |mean((d16)^2 - (d32)^2)| <= 2 e sqrt(mse32) + e^2 (Cauchy-Schwarz), per step."""
+    from gesturediffusion_amd import numerics
+    g, model, df, xs, tape, y, clip = _setup(arch, "small_noclip")
+    kw = dict(clip_denoised=False, model_kwargs={"y": y}, noise_tape=tape)
+    r32 = df.calc_bpd_loop(model, xs, **kw)
+    top = torch.empty(df.num_timesteps, dtype=torch.float64, device=xs.device)
+    for k in range(df.num_timesteps):           # max|out32| of each step's forward, from the step-wise path's pred_xstart
+        t = torch.full((xs.shape[0],), df.num_timesteps - 1 - k, device=xs.device, dtype=torch.long)
+        top[k] = df._bpd_step(model, xs, df.q_sample(xs, t, noise=tape[k]), t, False, {"y": y})[3].abs().max()
+    g2, model16, df, xs, tape, y, clip = _setup(arch, "small_noclip", dtype)
+    r16 = df.calc_bpd_loop(model16, xs, **kw)
+    e = numerics.stated_tolerance(dtype, None, loop=False) * top          # [num_timesteps], broadcast over the batch
+    m32 = r32["xstart_mse"].double()
+    bound = 2 * e * m32.sqrt() + e * e
+    diff = (r16["xstart_mse"].double() - m32).abs()
+    print(f"bpd-half {arch} {dtype}: worst |mse16 - mse32| / bound = {float((diff / bound).max()):.3g}")
+    assert torch.isfinite(r16["total_bpd"]).all() and bool((diff <= bound).all())
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+@pytest.mark.parametrize("loss", ["KL", "RESCALED_KL"])
+def test_training_losses_kl_vs_reference_fixture(arch, loss):
+    """7. training_losses under LossType.KL / RESCALED_KL at t = [19, 3, 0] (reference :1258-1268)."""
+    g, model, _, xs, tape, y, clip = _setup(arch, "small_noclip")
+    d = dev()
+    df = _diffusion("small_noclip", loss=loss)
+    y = dict(y, mask=torch.from_numpy(g["mask"]).to(d))
+    terms = df.training_losses(model, xs, torch.from_numpy(g["t_kl"]).to(d), model_kwargs={"y": y}, noise=tape[0])
+    tag = "kl" if loss == "KL" else "rkl"
+    ref32, ref64 = g[tag + ".loss"].astype(np.float64), g[tag + ".loss_fp64"]
+    allow = np.maximum(10 * np.abs(ref32 - ref64), R.FWD_TOL * np.abs(ref32).max())
+    err = np.abs(terms["loss"].cpu().numpy().astype(np.float64) - ref32)
+    print(f"bpd-ratio {arch} training_losses {loss}: {float((err / allow).max()):.3g}")
+    assert list(terms) == ["loss"] and bool((err <= allow).all())
+
+
+def test_bpd_loop_refusals():
+    """The refusals of gdx_bpd_loop that need a handle: call before gdx_prepare, bad step range, CFG without scale."""
+    import ctypes as C
+    from gesturediffusion_amd import _lib
+    from gesturediffusion_amd.engine import GDX_CFG, GDX_COND, GdxError
+    g, model, df, xs, tape, y, clip = _setup("mdm_old", "small_clip")
+    d = dev()
+    eng = model._get_engine(d)
+    lib = eng.lib
+    fresh = type(eng)(1, 16, 128, 256, 2, 4, 10)
+    assert lib.gdx_bpd_loop(fresh.handle, C.byref(_lib.BpdLoopArgs()), None) < 0 and b"gdx_prepare" in lib.gdx_last_error()
+    df.calc_bpd_loop(model, xs, clip_denoised=clip, model_kwargs={"y": y}, noise_tape=tape)       # prepares + conditions
+    out = [torch.empty(3, 20, device=d) for _ in range(3)]
+    coef, tmap = df.bpd_table(d), df._timestep_map()
+    with pytest.raises(GdxError, match="bad step range"):
+        eng.bpd_loop(xs, GDX_COND, coef, tmap, *out, noise_tape=tape, k_base=20)
+    with pytest.raises(GdxError, match="bad step range"):
+        eng.bpd_loop(xs, GDX_COND, coef, tmap, *out, noise_tape=tape, k_base=15, run_steps=6)
+    with pytest.raises(GdxError, match="needs scale"):
+        eng.bpd_loop(xs, GDX_CFG, coef, tmap, *out, noise_tape=tape)
+    with pytest.raises(ValueError):
+        df.calc_bpd_loop(model, xs, model_kwargs={"y": y}, rng="numpy")
