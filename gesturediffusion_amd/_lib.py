@@ -23,7 +23,7 @@ EXPORTS = [
     "gdx_linear_f16", "gdx_linear_f32", "gdx_bench_gemm_f16", "gdx_attention_f16", "gdx_attention_f32", "gdx_plms_update", "gdx_postprocess", "gdx_q_sample_t", "gdx_masked_l2", "gdx_set_graph_replay", "gdx_mfcc",
     "gdx_set_guards", "gdx_check_guards", "gdx_packed_bytes", "gdx_export_packed", "gdx_import_packed", "gdx_set_test_half_dtype",
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
-    "gdx_bpd_terms", "gdx_bpd_loop",
+    "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full",
 ]
 GDX_BPD_CHUNK = 4096   # include/gdx.h
 
@@ -130,6 +130,8 @@ def load():
         "gdx_linear_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
         "gdx_linear_f32": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
         "gdx_linear_half": [vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                            C.POINTER(i32), vp],
+        "gdx_linear_full": [vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                             C.POINTER(i32), vp],
         "gdx_layernorm": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
         "gdx_local_attention": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],

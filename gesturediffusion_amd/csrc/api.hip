@@ -719,6 +719,9 @@ extern "C" int gdx_set_condition(gdx_handle_t h, const float* seed, const float*
     return 0;
 }
 
+// gdx_linear_full (tests): 0 = the dispatch below, 1 = gemm2.hip or an error, 2 = gemm.hip; for the duration of one call
+static int g_gemm_test_kernel = 0;
+
 static int gemm(int am, int bm, int om, int ep, const GemmParams& p, hipStream_t s) {
     hipError_t e;
     // Operands beyond the 2 GiB range of a buffer descriptor: the persistent kernel cannot address them and the 128 x 128 kernel
@@ -733,12 +736,13 @@ static int gemm(int am, int bm, int om, int ep, const GemmParams& p, hipStream_t
         if (ep == EPI_BIAS || ep == EPI_GELU) { q.R = nullptr; q.V = nullptr; }
         if (ep == EPI_RES) { q.V = nullptr; ep2 = EPI_BIAS; }
         if (ep == EPI_RES_VEC) { q.bias = nullptr; ep2 = EPI_BIAS; }
-        if (gemm2_supported(om, ep2, q)) {
+        if (g_gemm_test_kernel != 2 && gemm2_supported(om, ep2, q)) {
             e = launch_gemm2(om, ep2, q, s);
             if (e == hipSuccess) return 0;
             if (e != hipErrorNotSupported) return fail(std::string("launch_gemm2: ") + hipGetErrorString(e));
         }
     }
+    if (g_gemm_test_kernel == 1) return fail("gemm: the persistent kernel (gemm2.hip) does not take this problem");
     // shapes the persistent kernel does not take (N not a multiple of 64, K not a multiple of 32, unaligned rows)
     e = launch_gemm(am, bm, om, ep, p, s);
     if (e != hipSuccess) return fail(std::string("launch_gemm: ") + hipGetErrorString(e));
@@ -1381,43 +1385,96 @@ extern "C" int gdx_bench_gemm(int32_t M, int32_t N, int32_t K, int32_t epi, int3
 
 namespace gdx { extern int g2_test_tile[3]; }
 
-// out = epilogue(A W^T) through the fp32 GEMM path of the encoder (csrc/gemm2.hip, fallback gemm.hip) on padded scratch
-// copies of the caller's arrays (test entry point: the kernels read / store whole tiles past M, like the workspace).
-extern "C" int gdx_linear_f32(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M,
-                              int32_t N, int32_t K, int32_t epi, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk,
-                              void* stream) {
-    if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || K % 32 || epi < EPI_BIAS || epi > EPI_RES || (epi == EPI_RES && !R))
-        return fail("gdx_linear_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
+// gdx_linear_full / gdx_linear_f32: one launch through gemm() on scratch copies laid out like the workspace.  A and R carry
+// GDX_ROW_PAD rows of NaN bit patterns behind the caller's rows (in the forwards those rows hold whatever the last whole-tile
+// store left there; the kernels read whole tiles of A); C is staged from the caller's own values and copied back whole.
+static int linear_full(const char* who, const float* A, const float* W, const float* bias, const float* R, int32_t ldr,
+                       const float* V, int32_t ldv, float* C, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T,
+                       int32_t rowmap, int32_t gelu, int32_t kernel, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk,
+                       int32_t* launched, hipStream_t s) {
+    // every refusal comes before the first HIP call (tests/test_host_logic.py checks them without a GPU)
+    const std::string w(who);
+    if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || K % 32 || T <= 0) return fail(w + ": bad argument");
+    const long out_rows = rowmap ? (long)M + (M - 1) / T + 1 : M;    // rows the epilogue stores (rowmap: m + m/T + 1)
+    if (c_rows < out_rows) return fail(w + ": c_rows below the stored rows");
+    if ((R && ldr < N) || (V && ldv < N)) return fail(w + ": ldr / ldv below N");
+    if (kernel < 0 || kernel > 2) return fail(w + ": unknown kernel (0 = dispatch, 1 = gemm2.hip, 2 = gemm.hip)");
+    if (tile_mb < 0 || tile_nbw < 0 || tile_bk < 0 || ((tile_mb == 0) != (tile_nbw == 0)) || ((tile_mb == 0) != (tile_bk == 0)))
+        return fail(w + ": (tile_mb, tile_nbw, tile_bk) all positive, or (0, 0, 0)");
+    if (tile_mb && kernel == 2) return fail(w + ": a forced tile is for the persistent kernel (kernel 0 or 1) only");
+    // the mode / epilogue pair of the forward that has this operand set (forward_core); anything else has no launch
+    int om = OUT_ROWS, ep = EPI_BIAS;
+    if (gelu) {
+        if (R || V || rowmap) return fail(w + ": no launch in the forwards: GELU goes with the bias epilogue only (FFN-1)");
+        ep = EPI_GELU;
+    } else if (V) {
+        if (!R || bias || rowmap)
+            return fail(w + ": no launch in the forwards: V goes with R, without bias and without a row map (V2 proj_pose)");
+        ep = EPI_RES_VEC;
+    } else if (R) {
+        ep = EPI_RES;
+        if (rowmap) om = OUT_TOKROWS;
+    } else if (rowmap) {
+        return fail(w + ": no launch in the forwards: the row map goes with R (V1 input linear)");
+    }
+    const size_t arow = (size_t)M + GDX_ROW_PAD, crow = (size_t)c_rows + GDX_ROW_PAD;
+    const size_t r_rows = R ? (size_t)out_rows : 0, rrow = r_rows + GDX_ROW_PAD;
+    if (4 * arow * K >= (1ull << 31) || 4 * crow * N >= (1ull << 31) || (R && 4 * rrow * ldr >= (1ull << 31)))
+        return fail(w + ": an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
     hipError_t e = gemm_init();
     if (e != hipSuccess) return fail(std::string("gemm_init: ") + hipGetErrorString(e));
     const int npad = round_up(N, 128);
-    float *a = nullptr, *w = nullptr, *b = nullptr, *r = nullptr, *c = nullptr;
+    float *a = nullptr, *wp = nullptr, *r = nullptr, *c = nullptr;
     std::vector<void*> pool;
-    const size_t prow = (size_t)M + GDX_ROW_PAD;
     int rc = 0;
-    if (dev_alloc(pool, (void**)&a, sizeof(float) * prow * K) || dev_alloc(pool, (void**)&w, sizeof(float) * (size_t)npad * K) ||
-        dev_alloc(pool, (void**)&b, sizeof(float) * npad) || dev_alloc(pool, (void**)&r, sizeof(float) * prow * N) ||
-        dev_alloc(pool, (void**)&c, sizeof(float) * prow * N))
+    if (dev_alloc(pool, (void**)&a, sizeof(float) * arow * K) || dev_alloc(pool, (void**)&wp, sizeof(float) * (size_t)npad * K) ||
+        (R && dev_alloc(pool, (void**)&r, sizeof(float) * rrow * ldr)) || dev_alloc(pool, (void**)&c, sizeof(float) * crow * N))
         rc = -1;
-    if (!rc && (hipMemsetAsync(a, 0, sizeof(float) * prow * K, s) != hipSuccess || hipMemsetAsync(w, 0, sizeof(float) * (size_t)npad * K, s) != hipSuccess ||
-                hipMemsetAsync(b, 0, sizeof(float) * npad, s) != hipSuccess || hipMemsetAsync(r, 0, sizeof(float) * prow * N, s) != hipSuccess ||
+    // 0xff bytes: every padding float is a NaN; the packed weight's padding rows are zero, as gdx_set_weight leaves them
+    if (!rc && (hipMemsetAsync(a + (size_t)M * K, 0xff, sizeof(float) * GDX_ROW_PAD * K, s) != hipSuccess ||
+                hipMemsetAsync(wp, 0, sizeof(float) * (size_t)npad * K, s) != hipSuccess ||
+                (R && hipMemsetAsync(r + r_rows * ldr, 0xff, sizeof(float) * GDX_ROW_PAD * ldr, s) != hipSuccess) ||
+                hipMemsetAsync(c + (size_t)c_rows * N, 0xff, sizeof(float) * GDX_ROW_PAD * N, s) != hipSuccess ||
                 hipMemcpyAsync(a, A, sizeof(float) * (size_t)M * K, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(w, W, sizeof(float) * (size_t)N * K, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                (bias && hipMemcpyAsync(b, bias, sizeof(float) * N, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-                (R && hipMemcpyAsync(r, R, sizeof(float) * (size_t)M * N, hipMemcpyDeviceToDevice, s) != hipSuccess)))
-        rc = fail("gdx_linear_f32: staging failed");
+                hipMemcpyAsync(wp, W, sizeof(float) * (size_t)N * K, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                (R && hipMemcpyAsync(r, R, sizeof(float) * r_rows * ldr, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+                hipMemcpyAsync(c, C, sizeof(float) * (size_t)c_rows * N, hipMemcpyDeviceToDevice, s) != hipSuccess))
+        rc = fail(w + ": staging failed");
     if (!rc) {
-        GemmParams p{a, K, w, K, b, epi == EPI_RES ? r : nullptr, N, nullptr, 0, c, N, M, N, K, 1, 1};
+        GemmParams p{a, K, wp, K, bias, r, ldr, V, ldv, c, N, M, N, K, T, 1};
         g2_test_tile[0] = tile_mb; g2_test_tile[1] = tile_nbw; g2_test_tile[2] = tile_bk;
-        rc = gemm(A_ROWS, B_WEIGHT, OUT_ROWS, epi, p, s);
+        g_gemm_test_kernel = kernel;
+        g_gemm_launched = GemmLaunched{0, 0, 0, 0, 0, 0};
+        rc = gemm(A_ROWS, B_WEIGHT, om, ep, p, s);
+        g_gemm_test_kernel = 0;
         g2_test_tile[0] = g2_test_tile[1] = g2_test_tile[2] = 0;
+        if (launched) {
+            const GemmLaunched& l = g_gemm_launched;
+            launched[0] = l.file; launched[1] = l.mb; launched[2] = l.nbw; launched[3] = l.bk; launched[4] = l.nst; launched[5] = l.resp;
+        }
     }
-    if (!rc && hipMemcpyAsync(C, c, sizeof(float) * (size_t)M * N, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        rc = fail("gdx_linear_f32: copy-out failed");
+    if (!rc && hipMemcpyAsync(C, c, sizeof(float) * (size_t)c_rows * N, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        rc = fail(w + ": copy-out failed");
     (void)hipStreamSynchronize(s);
     free_pool(pool);
     return rc;
+}
+
+extern "C" int gdx_linear_full(const float* A, const float* W, const float* bias, const float* R, int32_t ldr, const float* V,
+                               int32_t ldv, float* C, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T, int32_t rowmap,
+                               int32_t gelu, int32_t kernel, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk,
+                               int32_t* launched, void* stream) {
+    return linear_full("gdx_linear_full", A, W, bias, R, ldr, V, ldv, C, c_rows, M, N, K, T, rowmap, gelu, kernel, tile_mb,
+                       tile_nbw, tile_bk, launched, (hipStream_t)stream);
+}
+
+// the plain / GELU / residual epilogues of the same call, R and C [M][N], through the dispatcher
+extern "C" int gdx_linear_f32(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M,
+                              int32_t N, int32_t K, int32_t epi, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk,
+                              void* stream) {
+    if (epi < EPI_BIAS || epi > EPI_RES || (epi == EPI_RES && !R)) return fail("gdx_linear_f32: bad argument");
+    return linear_full("gdx_linear_f32", A, W, bias, epi == EPI_RES ? R : nullptr, N, nullptr, 0, C, M, M, N, K, 1, 0,
+                       epi == EPI_GELU, 0, tile_mb, tile_nbw, tile_bk, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int gdx_set_test_half_dtype(int32_t dtype) {

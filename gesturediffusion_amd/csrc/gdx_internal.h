@@ -34,13 +34,15 @@ constexpr int ROW_PAD = GDX_ROW_PAD;
 // ---- GEMM (gemm.hip) ---------------------------------------------------------------------
 // C = A * W^T (+ epilogue).  W is a packed weight [Npad][ldw], K-contiguous, zero padded to
 // multiples of 128 rows / 32 columns, so the weight operand never needs a bounds check.
+// Instantiated (gemm.hip GDX_GEMM_INSTANCES): A_ROWS x B_WEIGHT with OUT_ROWS under each Epi and OUT_TOKROWS under EPI_RES.
+// A_POSE, B_TOKENS and OUT_POSE are branches of the kernel template that no instantiation uses: launch_gemm refuses them.
 enum AMode { A_ROWS = 0,      // A[m][k] = A[m*lda + k]
-             A_POSE = 1 };    // A[m][k] = x[(b*K + k)*T + t],  m = b*T + t   (pose tensor, k-major)
+             A_POSE = 1 };    // (not instantiated) A[m][k] = x[(b*K + k)*T + t],  m = b*T + t   (pose tensor, k-major)
 enum BMode { B_WEIGHT = 0,    // second operand is the padded weight
-             B_TOKENS = 1 };  // second operand rows are tokens: row(n) = n + n/T + 1 (skip token 0), n < N
+             B_TOKENS = 1 };  // (not instantiated) second operand rows are tokens: row(n) = n + n/T + 1 (skip token 0), n < N
 enum OutMode { OUT_ROWS = 0,     // C[m*ldc + n]
                OUT_TOKROWS = 1,  // C[(m + m/T + 1)*ldc + n]   (frames into [B, T+1, d], token 0 skipped)
-               OUT_POSE = 2 };   // C[((n/T)*M + m)*T + n%T]    (swapped GEMM -> pose tensor [B, M=J, 1, T])
+               OUT_POSE = 2 };   // (not instantiated) C[((n/T)*M + m)*T + n%T]    (swapped GEMM -> pose tensor [B, M=J, 1, T])
 enum Epi { EPI_BIAS = 0,      // + bias[n]      (bias[m] for OUT_POSE)
            EPI_GELU = 1,      // gelu_erf(. + bias[n])
            EPI_RES = 2,       // + bias[n] + R[row_out*ldr + n]
@@ -53,9 +55,9 @@ struct GemmParams {
     const float* R; int ldr;
     const float* V; int ldv;
     float* C; int ldc;
-    int M, N, K;   // K: multiple of 32 for A_ROWS; true K for A_POSE (guarded)
+    int M, N, K;   // K: multiple of 32 (A_ROWS)
     int T;         // frames per sample, for the row maps
-    int Bmod;      // A_POSE: source sample = (m / T) % Bmod (CFG runs the same x through both passes)
+    int Bmod;      // read by the A_POSE branch only (not instantiated): source sample = (m / T) % Bmod
 };
 
 hipError_t gemm_init();   // raises the dynamic-LDS limit of every instantiation
@@ -64,6 +66,11 @@ hipError_t launch_gemm(int amode, int bmode, int omode, int epi, const GemmParam
 // persistent wave-specialised variant for A_ROWS x B_WEIGHT -> OUT_ROWS (gemm2.hip)
 bool gemm2_supported(int omode, int epi, const GemmParams& p);
 hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s);
+// what the last fp32 GEMM launch ran, recorded where the launch is decided (launch_gemm / launch_cfg; read by the test entry
+// point gdx_linear_full): file 1 = gemm2.hip, 2 = gemm.hip; for gemm2.hip the tile shape (mb, nbw, bk), its LDS ring depth and
+// whether it was the RESP instantiation
+struct GemmLaunched { int file, mb, nbw, bk, nst, resp; };
+extern GemmLaunched g_gemm_launched;
 
 // fp16-input / fp32-accumulate persistent GEMM of the reduced-precision mode (gemmh.hip):
 //   C[row_out][n] = act( sum_k A[m][k] W[n][k] + bias[n] + R[row_out][n] + V[m / T][n] ),  row_out = rowmap ? m + m/T + 1 : m

@@ -40,7 +40,9 @@
 // (its surplus rows are garbage that nothing consumes; ROW_PAD >= the tallest tile is a static_assert in launch_cfg).
 // The general epilogue (boundary linears: token-row map, R, V) moves rows, so it guards every access with m < M.
 // Summation order per output element is k-slab by k-slab and does not depend on the tile shape, so results are
-// independent of batch size / tile choice (tests/test_gpu_parity.py::test_full_size_properties_config2).
+// independent of batch size / tile choice (tests/test_gpu_parity.py::test_full_size_properties_config2 through whole forwards;
+// tests/test_gpu_gemm_f32.py::test_tile_and_batch_independence_bitwise at kernel level: all 21 shapes, both slab depths, every
+// epilogue, GELU included, give identical bits).
 #include "gdx_internal.h"
 
 #include <cstdio>
@@ -375,7 +377,8 @@ __global__ __launch_bounds__(512, 1) void gemm4_kernel(const GemmParams p, const
 }
 
 unsigned long long* g2_dbg_buf = nullptr;   // set by gdx_bench_gemm when GDX_GEMM_DEBUG is set
-int g2_test_tile[3] = {0, 0, 0};            // (MB, NBW, BK) forced by gdx_linear_f32 for the duration of one call (tests)
+int g2_test_tile[3] = {0, 0, 0};            // (MB, NBW, BK) forced by gdx_linear_full for the duration of one call (tests)
+GemmLaunched g_gemm_launched = {0, 0, 0, 0, 0, 0};
 
 template <int MB, int NBW, int BK, int NST>
 constexpr size_t g4_lds_bytes(int N) {
@@ -403,6 +406,7 @@ static hipError_t launch_cfg(const GemmParams& p, int epi, int omode, int num_cu
     const int ntm = (p.M + BM - 1) / BM, ntn = p.N / BN;
     const int ntiles = ntm * ntn;
     const int grid = ntiles < num_cus ? ntiles : num_cus;
+    g_gemm_launched = GemmLaunched{1, MB, NBW, BK, NST, RESP ? 1 : 0};
     hipLaunchKernelGGL((gemm4_kernel<MB, NBW, BK, NST, RESP>), dim3(grid), dim3(512), lds, s, p, epi, omode, ntn, ntiles,
                        g2_dbg_buf);
     return hipGetLastError();

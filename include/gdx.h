@@ -456,6 +456,24 @@ int gdx_attention_f32(const float* qkv, float* ctx, int32_t B, int32_t S, int32_
  * point: works on padded scratch copies and synchronises the stream. */
 int gdx_linear_f32(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
                    int32_t K, int32_t epi, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk, void* stream);
+/* The same GEMM path with the whole epilogue the fp32 forwards use, through the forwards' own dispatcher:
+ *   C[row_out][n] = act(A W^T + bias[n] + R[row_out * ldr + n] + V[(m / T) * ldv + n]),  act = GELU if gelu,
+ *   row_out = rowmap ? m + m/T + 1 : m  (token 0 of every sample of a [B, T+1] layout skipped).
+ * bias [N], R [rowmap ? M + (M-1)/T + 1 : M][ldr] and V [ceil(M / T)][ldv] may each be NULL, but only the operand sets the
+ * forwards launch are taken: bias (gelu or not); R (+ bias); R with the row map (+ bias); R + V.  Any other combination is
+ * refused.  C [c_rows][N], c_rows >= the stored rows, is staged from the caller's own values into a scratch with GDX_ROW_PAD
+ * further rows and all c_rows rows are copied back: rows the kernel does not store come back unchanged, and whole-tile stores
+ * past M (plain and residual epilogues of gemm2.hip) show up in the caller's rows past M.  The scratch copies of A and R carry
+ * GDX_ROW_PAD rows of NaN behind the caller's rows.  kernel: 0 = the dispatcher's choice, 1 = csrc/gemm2.hip only (an error
+ * where it does not take the problem, instead of the fallback), 2 = csrc/gemm.hip only.  (tile_mb, tile_nbw, tile_bk) as in
+ * gdx_linear_f32 (kernel 0 or 1); a forced shape that is not valid for the problem is not an error: the cost model's choice
+ * runs and `launched` says so.  launched (optional, 6 entries) receives what ran: the file (1 = gemm2.hip, 2 = gemm.hip) and,
+ * for gemm2.hip, the tile's (mb, nbw, bk), its LDS ring depth and 1 if it was the residual-prefetch (RESP) instantiation.
+ * K % 32 == 0.  Every refusal comes before the first HIP call.  Synchronises the stream. */
+int gdx_linear_full(const float* A, const float* W, const float* bias, const float* R, int32_t ldr, const float* V,
+                    int32_t ldv, float* C, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T, int32_t rowmap,
+                    int32_t gelu, int32_t kernel, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk, int32_t* launched,
+                    void* stream);
 /* Time `iters` launches of the fp16 GEMM on scratch operands filled with N(0,1). */
 int gdx_bench_gemm_f16(int32_t M, int32_t N, int32_t K, int32_t gelu, int32_t iters, float* avg_us,
                        void* stream);

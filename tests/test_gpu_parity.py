@@ -276,15 +276,20 @@ def test_real_shapes_vs_reference_golden(name, arch, J, dm):
 
 @pytest.mark.parametrize("arch,dm,H,T,B", [("mdm_old", 256, 4, 37, 3), ("mdm", 256, 4, 40, 2), ("mdm_old", 512, 4, 15, 5),
                                             ("mdm_old", 128, 2, 250, 1), ("mdm", 512, 8, 30, 2), ("mdm", 1024, 4, 20, 2),
-                                            ("mdm", 512, 4, 10, 3), ("mdm", 256, 4, 70, 5)])
+                                            ("mdm", 512, 4, 10, 3), ("mdm", 256, 4, 70, 5),
+                                            ("mdm_old", 96, 3, 37, 3), ("mdm", 96, 3, 40, 2)])
 def test_forward_vs_oracle_odd_shapes(arch, dm, H, T, B):
     """Shapes outside the fixtures: head_dim 64 (attention3's second instantiation), sequences that are
     not multiples of the 16/32-token blocks, a single sample, 8 heads, K = 263+ tails -- against the CPU oracle.  The V2
     rows run the fp32-MFMA local-attention front end at its three head widths (d / 8 = 32, 64, 128), with one window
-    only (T = 10), and with a work count that is not a multiple of the four waves of a block (5 x 8 x 7 windows)."""
+    only (T = 10), and with a work count that is not a multiple of the four waves of a block (5 x 8 x 7 windows).
+    The d = 96 rows (3 heads, ff_size 160) are the widths that are multiples of 32 but not of 64: every encoder GEMM
+    (N = 96, 288, 160) is refused by the persistent kernel and runs on csrc/gemm.hip (tests/test_gpu_gemm_f32.py tests that
+    kernel alone at these widths)."""
     from gesturediffusion_amd.utils.init import init_state_dict, synthetic_inputs
     from oracle import mdm_forward as omf
-    cfg = dict(arch=arch, njoints=37, nfeats=1, latent_dim=dm, ff_size=192, num_layers=2, num_heads=H, seed_poses=10)
+    cfg = dict(arch=arch, njoints=37, nfeats=1, latent_dim=dm, ff_size=160 if dm == 96 else 192, num_layers=2, num_heads=H,
+               seed_poses=10)
     sd = init_state_dict(cfg, seed=5, perturb=True)
     m = build_model(arch, cfg, sd)
     d = dev()

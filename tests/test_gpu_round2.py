@@ -673,9 +673,12 @@ G4_TILES = [(4, 2, 32), (5, 2, 32), (6, 2, 32), (8, 2, 32), (9, 2, 32), (5, 3, 3
 @pytest.mark.parametrize("tile", G4_TILES + [(0, 0, 0)])
 def test_fp32_gemm_every_tile_shape_vs_torch(tile):
     """The persistent fp32 GEMM (csrc/gemm2.hip) alone, every tile shape of G4_CONFIGS forced in turn (and the cost model's
-    own choice): plain, GELU and residual epilogues (the residual one is the RESP instantiation where the shape has one; the
-    two-stage shapes are not offered to it and the call falls back to the cost model's choice),
-    row counts of one row, less than a tile, a ragged last tile and several rounds of tiles, against fp64 torch."""
+    own choice): plain, GELU and residual epilogues, row counts of one row, less than a tile, a ragged last tile and several
+    rounds of tiles, against fp64 torch.  This entry point does not report what ran: under the residual epilogue the six
+    two-stage shapes are not offered and another shape (the cost model's choice) runs in their place, the shapes with
+    mb * nbw <= 10 run as the RESP instantiation and the others through the general epilogue.  tests/test_gpu_gemm_f32.py
+    asserts all of that through gdx_linear_full's `launched` report, and covers the general epilogue, the edges and
+    csrc/gemm.hip."""
     import ctypes as C
     from gesturediffusion_amd import _lib
     lib = _lib.load()

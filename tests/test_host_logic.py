@@ -170,6 +170,52 @@ def test_attention_half_refuses_what_has_no_kernel_without_gpu():
         assert list(rep) == [-1, -1, -1], change              # refused before anything ran
 
 
+def test_linear_full_refuses_what_the_forwards_do_not_launch_without_gpu():
+    """gdx_linear_full validates before its first HIP call: operand sets the fp32 forwards have no launch for, unknown
+    kernels, a tile forced on gemm.hip, short buffers and operands past 2 GiB are refused with a message (the pointers are
+    never dereferenced, `launched` is not touched).  gdx_linear_f32, now a wrapper of the same call, keeps its refusals."""
+    import ctypes as C
+    from gesturediffusion_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgdx.so not built")
+    lib = _lib.load()
+    p = C.c_void_p(0x1000)
+    rep = (C.c_int32 * 6)(-1, -1, -1, -1, -1, -1)
+    ok = dict(bias=p, R=None, ldr=0, V=None, ldv=0, c_rows=80, M=77, N=128, K=64, T=7, rowmap=0, gelu=0, kernel=0,
+              tile=(0, 0, 0))
+    cases = [
+        (dict(V=p, ldv=128), b"V goes with R"),                                  # V without R
+        (dict(V=p, ldv=128, R=p, ldr=128), b"V goes with R"),                    # R + V + bias
+        (dict(V=p, ldv=128, R=p, ldr=128, bias=None, rowmap=1, c_rows=100), b"V goes with R"),
+        (dict(gelu=1, R=p, ldr=128), b"GELU goes with the bias epilogue"),
+        (dict(gelu=1, R=p, ldr=128, V=p, ldv=128, bias=None), b"GELU goes with the bias epilogue"),
+        (dict(rowmap=1, c_rows=100), b"row map goes with R"),
+        (dict(rowmap=1, R=p, ldr=128, c_rows=87), b"c_rows below"),              # 77 + 10 + 1 rows are stored
+        (dict(c_rows=76), b"c_rows below"),
+        (dict(R=p, ldr=124), b"ldr / ldv below N"),
+        (dict(R=p, ldr=128, V=p, ldv=64, bias=None), b"ldr / ldv below N"),
+        (dict(kernel=3), b"unknown kernel"),
+        (dict(kernel=-1), b"unknown kernel"),
+        (dict(kernel=2, tile=(4, 2, 32)), b"forced tile is for the persistent kernel"),
+        (dict(tile=(4, 0, 32)), b"all positive"),
+        (dict(tile=(4, 2, -32)), b"all positive"),
+        (dict(K=48), b"bad argument"),
+        (dict(T=0), b"bad argument"),
+        (dict(M=0), b"bad argument"),
+        (dict(M=(1 << 31) // (64 * 4), c_rows=(1 << 31) // (64 * 4)), b"2 GiB"),
+    ]
+    for change, msg in cases:
+        a = dict(ok, **change)
+        rc = lib.gdx_linear_full(p, p, a["bias"], a["R"], a["ldr"], a["V"], a["ldv"], p, a["c_rows"], a["M"], a["N"], a["K"],
+                                 a["T"], a["rowmap"], a["gelu"], a["kernel"], *a["tile"], rep, None)
+        assert rc != 0 and msg in lib.gdx_last_error(), (change, lib.gdx_last_error())
+        assert list(rep) == [-1] * 6, change                   # refused before anything ran
+    for epi, R in ((3, p), (-1, p), (2, None)):
+        assert lib.gdx_linear_f32(p, p, p, R, p, 77, 128, 64, epi, 0, 0, 0, None) != 0
+        assert b"gdx_linear_f32: bad argument" in lib.gdx_last_error()
+    assert lib.gdx_linear_f32(p, p, p, None, p, 77, 128, 48, 0, 0, 0, 0, None) != 0 and b"gdx_linear_f32" in lib.gdx_last_error()
+
+
 # ------------------------------------------------------------------------------- schedule / coefficients
 @pytest.mark.parametrize("sched", ["cosine", "linear"])
 @pytest.mark.parametrize("tag,resp", [("1000", ""), ("ddim10", "ddim10"), ("ddim100", "ddim100"), ("s20", [20])])
