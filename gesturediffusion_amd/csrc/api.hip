@@ -1,8 +1,7 @@
 // libgdx.so host side: handle, packed weights, workspace, the per-step kernel sequence of the
 // denoiser (V1 = reference model/mdm_old.py:84-122, V2 = model/mdm.py:105-224) and the sampling
 // loops (diffusion/gaussian_diffusion.py:598-730, 879-993).  C ABI in include/gdx.h.
-#include "gdx_internal.h"
-#include "../../include/gdx.h"
+#include "gdx_host.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -16,17 +15,10 @@ namespace gdx {
 
 static thread_local std::string g_err;
 
-static int fail(const std::string& m) {
+int fail(const std::string& m) {
     g_err = m;
     return -1;
 }
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // dst[r][c] = (r < n && c < k) ? src[r*src_ld + col0 + c] : 0      (dst is [npad][kpad])
 __global__ void pack_weight_kernel(const float* __restrict__ src, int src_ld, int col0, int n, int k,
@@ -56,10 +48,6 @@ __global__ void pack_weight_bf16_kernel(const float* __restrict__ src, int src_l
     dst[i] = (r < n && c < k) ? (__bf16)src[(long)r * src_ld + col0 + c] : (__bf16)0.0f;
 }
 
-// half-type dispatch: the reduced-precision kernels exist as gdx:: (fp16) and gdx::b16:: (bf16) builds of one source
-#define HFN(bf, fn, ...) ((bf) ? gdx::b16::fn(__VA_ARGS__) : gdx::h16::fn(__VA_ARGS__))
-static bool g_test_bf16 = false;    // gdx_set_test_half_dtype: element type of the stand-alone test / bench entry points
-
 struct Packed {          // a Linear weight [n][k] packed to [npad][kpad] (+ bias [npad])
     float* w = nullptr;
     float* bias = nullptr;
@@ -76,7 +64,6 @@ struct Layer {
 }  // namespace gdx
 
 using namespace gdx;
-namespace gdx { extern unsigned long long* g2_dbg_buf; }
 int gdx_sampler_update_state_(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);   // sampler.hip
 int gdx_sampler_update_tm_(int kind, int B, int J, int T, int ldx, int ldo, const float* coef, int step_index, float* xt,
                            const float* x0t, const float* scale, int const_noise, uint64_t seed, uint64_t sample_offset,
@@ -136,15 +123,15 @@ struct gdx_model {
 static constexpr size_t GUARD_BYTES = 64 * 1024;
 static constexpr int GUARD_BYTE = 0xA5;
 
-static int dev_alloc(std::vector<void*>& pool, void** p, size_t bytes) {
+int gdx::dev_alloc(std::vector<void*>& pool, void** p, size_t bytes) {
     hipError_t e = hipMalloc(p, bytes ? bytes : 16);
     if (e != hipSuccess) return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
     pool.push_back(*p);
     return 0;
 }
 
-static int pack_f16_into(_Float16* dst, const float* src, int n, int src_ld, int col0, int k, int npad, int kpad,
-                         hipStream_t s, bool bf = false) {
+int gdx::pack_f16_into(_Float16* dst, const float* src, int n, int src_ld, int col0, int k, int npad, int kpad, hipStream_t s,
+                       bool bf) {
     const long total = (long)npad * kpad;
     hipLaunchKernelGGL(bf ? pack_weight_bf16_kernel : pack_weight_f16_kernel, dim3((total + 255) / 256), dim3(256), 0, s, src,
                        src_ld, col0, n, k, dst, npad, kpad);
@@ -228,7 +215,7 @@ extern "C" int gdx_create(const gdx_config_t* cfg, gdx_handle_t* out) {
     return 0;
 }
 
-static void free_pool(std::vector<void*>& pool) {
+void gdx::free_pool(std::vector<void*>& pool) {
     for (void* p : pool) (void)hipFree(p);
     pool.clear();
 }
@@ -719,46 +706,39 @@ extern "C" int gdx_set_condition(gdx_handle_t h, const float* seed, const float*
     return 0;
 }
 
-// gdx_linear_full (tests): 0 = the dispatch below, 1 = gemm2.hip or an error, 2 = gemm.hip; for the duration of one call
-static int g_gemm_test_kernel = 0;
-
-static int gemm(int am, int bm, int om, int ep, const GemmParams& p, hipStream_t s) {
+// ctl (test / bench entry points only): a forced file or tile, the stamp buffer and the report of what ran (gdx_internal.h)
+int gdx::gemm(int om, int ep, const GemmParams& p, hipStream_t s, GemmCtl* ctl) {
     hipError_t e;
+    const int file = ctl ? ctl->file : 0;
     // Operands beyond the 2 GiB range of a buffer descriptor: the persistent kernel cannot address them and the 128 x 128 kernel
     // of gemm.hip would silently produce other bits for the same rows (another summation order).  Refuse instead: the caller
     // splits the batch (bench.py's config 4 runs sub-batches of 256 for this reason).
     if ((long)(p.M + ROW_PAD) * p.lda * 4 >= (1L << 31) || (long)(p.M + ROW_PAD) * p.ldc * 4 >= (1L << 31))
         return fail("gemm: an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
-    if (am == A_ROWS && bm == B_WEIGHT) {
-        // persistent kernel: residual / per-sample-vector terms are selected by the pointers, not by the mode
-        GemmParams q = p;
-        int ep2 = ep;
-        if (ep == EPI_BIAS || ep == EPI_GELU) { q.R = nullptr; q.V = nullptr; }
-        if (ep == EPI_RES) { q.V = nullptr; ep2 = EPI_BIAS; }
-        if (ep == EPI_RES_VEC) { q.bias = nullptr; ep2 = EPI_BIAS; }
-        if (g_gemm_test_kernel != 2 && gemm2_supported(om, ep2, q)) {
-            e = launch_gemm2(om, ep2, q, s);
-            if (e == hipSuccess) return 0;
-            if (e != hipErrorNotSupported) return fail(std::string("launch_gemm2: ") + hipGetErrorString(e));
-        }
+    // persistent kernel: residual / per-sample-vector terms are selected by the pointers, not by the mode
+    GemmParams q = p;
+    int ep2 = ep;
+    if (ep == EPI_BIAS || ep == EPI_GELU) { q.R = nullptr; q.V = nullptr; }
+    if (ep == EPI_RES) { q.V = nullptr; ep2 = EPI_BIAS; }
+    if (ep == EPI_RES_VEC) { q.bias = nullptr; ep2 = EPI_BIAS; }
+    if (file != 2 && gemm2_supported(om, ep2, q)) {
+        e = launch_gemm2(om, ep2, q, s, ctl);
+        if (e == hipSuccess) return 0;
+        if (e != hipErrorNotSupported) return fail(std::string("launch_gemm2: ") + hipGetErrorString(e));
     }
-    if (g_gemm_test_kernel == 1) return fail("gemm: the persistent kernel (gemm2.hip) does not take this problem");
+    if (file == 1) return fail("gemm: the persistent kernel (gemm2.hip) does not take this problem");
     // shapes the persistent kernel does not take (N not a multiple of 64, K not a multiple of 32, unaligned rows)
-    e = launch_gemm(am, bm, om, ep, p, s);
+    e = launch_gemm(om, ep, p, s, ctl);
     if (e != hipSuccess) return fail(std::string("launch_gemm: ") + hipGetErrorString(e));
     return 0;
 }
 
-// V2 front end (RoPE -> causal local attention -> RoPE at t+1) for compute dtype `dtype`: the one dispatch of the forwards and
-// of the test entry point gdx_local_attention.  The 16-bit kernel (local_attention_half) reads xseq16 and writes enc16 plus the
-// optional fp32 copy enc; otherwise the fp32 kernel (MFMA, or the scalar one for other head widths / windows) reads xseq and
-// writes enc plus the optional 16-bit copy enc16.
-static bool local_attention_half(int dtype, int d, int heads, int window) {
+bool gdx::local_attention_half(int dtype, int d, int heads, int window) {
     return dtype != GDX_DTYPE_F32 && HFN(dtype == GDX_DTYPE_BF16, local_attention_f16_supported, d, heads, window);
 }
-static hipError_t launch_local_attention_any(int dtype, const float* xseq, const _Float16* xseq16, const float* cosT,
-                                             const float* sinT, float* enc, _Float16* enc16, int B, int T, int d, int heads,
-                                             int window, hipStream_t s) {
+hipError_t gdx::launch_local_attention_any(int dtype, const float* xseq, const _Float16* xseq16, const float* cosT,
+                                           const float* sinT, float* enc, _Float16* enc16, int B, int T, int d, int heads,
+                                           int window, hipStream_t s) {
     const bool bf = dtype == GDX_DTYPE_BF16;
     if (local_attention_half(dtype, d, heads, window))
         return HFN(bf, launch_local_attention_f16, xseq16, cosT, sinT, enc16, enc, B, T, d, heads, window, s);
@@ -791,17 +771,17 @@ static int forward_core(gdx_model* h, const float* x, const float* temb, int tst
     if (h->cfg.arch == GDX_ARCH_MDM_OLD) {
         HIPCHK(launch_token0(temb, tstride, seed_emb, h->pe, h->xa, nullptr, nullptr, nullptr, nullptr, state, Beff, B, S, d, s));
         // frames -> rows (b, t+1) of the encoder input, + hoisted MFCC/bias/PE term      (model/mdm_old.py:104-112)
-        p = GemmParams{h->xt, Jp, h->in_x.w, h->in_x.kpad, nullptr, h->addend, d, nullptr, 0, h->xa, d, Beff * T, d, Jp, T, B};
-        if (gemm(A_ROWS, B_WEIGHT, OUT_TOKROWS, EPI_RES, p, s)) return -1;
+        p = GemmParams{h->xt, Jp, h->in_x.w, h->in_x.kpad, nullptr, h->addend, d, nullptr, 0, h->xa, d, Beff * T, d, Jp, T};
+        if (gemm(OUT_TOKROWS, EPI_RES, p, s)) return -1;
     } else {
         // coarse slice of project_to_lat = W_coa temb (c2t, from the caller) + W_coa seed_emb (c2_seed, per conditioning)
         if (!c2t) return fail("forward_core: V2 needs the W_coa * temb rows");
         const float* c2s = mode == GDX_UNCOND ? h->c2_seed + (size_t)B * d : h->c2_seed;
         HIPCHK(launch_token0(temb, tstride, seed_emb, nullptr, h->xa, nullptr, c2t, c2s, h->c2, state, Beff, B, S, d, s));
-        p = GemmParams{h->xt, Jp, h->in_x.w, h->in_x.kpad, h->in_x.bias, nullptr, 0, nullptr, 0, h->emb_pose, d, Beff * T, d, Jp, T, B};
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_BIAS, p, s)) return -1;
-        p = GemmParams{h->emb_pose, d, h->proj_pose.w, h->proj_pose.kpad, nullptr, h->addend, d, h->c2, d, h->xseq, d, Beff * T, d, d, T, B};
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_RES_VEC, p, s)) return -1;
+        p = GemmParams{h->xt, Jp, h->in_x.w, h->in_x.kpad, h->in_x.bias, nullptr, 0, nullptr, 0, h->emb_pose, d, Beff * T, d, Jp, T};
+        if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;
+        p = GemmParams{h->emb_pose, d, h->proj_pose.w, h->proj_pose.kpad, nullptr, h->addend, d, h->c2, d, h->xseq, d, Beff * T, d, d, T};
+        if (gemm(OUT_ROWS, EPI_RES_VEC, p, s)) return -1;
         HIPCHK(launch_local_attention_any(GDX_DTYPE_F32, h->xseq, nullptr, h->rope_cos, h->rope_sin, h->xa, nullptr, Beff, T, d,
                                           h->cfg.cl_head, h->cfg.window, s));
     }
@@ -809,26 +789,26 @@ static int forward_core(gdx_model* h, const float* x, const float* temb, int tst
         HIPCHK(hipMemcpyAsync(h->taps[0], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
     for (int l = 0; l < h->L; ++l) {
         const Layer& ly = h->layers[l];
-        p = GemmParams{h->xa, d, ly.qkv.w, ly.qkv.kpad, ly.qkv.bias, nullptr, 0, nullptr, 0, h->qkv, 3 * d, N, 3 * d, d, T, B};
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_BIAS, p, s)) return -1;
+        p = GemmParams{h->xa, d, ly.qkv.w, ly.qkv.kpad, ly.qkv.bias, nullptr, 0, nullptr, 0, h->qkv, 3 * d, N, 3 * d, d, T};
+        if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;
         if (attention3_supported(S, h->H, d))
             HIPCHK(launch_attention3(h->qkv, h->ctx, Beff, S, h->H, d, s));
         else                                              // other head dims / more than 256 tokens: the general 32 x 32-block kernel
             HIPCHK(launch_attention(h->qkv, h->ctx, Beff, S, h->H, d, s));
         // x = LN1(x + out_proj(ctx)): the residual add rides in the GEMM epilogue (prefetched one tile ahead, gemm2.hip)
-        p = GemmParams{h->ctx, d, ly.out.w, ly.out.kpad, ly.out.bias, h->xa, d, nullptr, 0, h->tmp, d, N, d, d, T, B};
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_RES, p, s)) return -1;
+        p = GemmParams{h->ctx, d, ly.out.w, ly.out.kpad, ly.out.bias, h->xa, d, nullptr, 0, h->tmp, d, N, d, d, T};
+        if (gemm(OUT_ROWS, EPI_RES, p, s)) return -1;
         HIPCHK(launch_layernorm(h->tmp, nullptr, ly.g1, ly.b1, h->xb, nullptr, N, d, 0, s));
-        p = GemmParams{h->xb, d, ly.ff1.w, ly.ff1.kpad, ly.ff1.bias, nullptr, 0, nullptr, 0, h->ffb, h->ff, N, h->ff, d, T, B};
+        p = GemmParams{h->xb, d, ly.ff1.w, ly.ff1.kpad, ly.ff1.bias, nullptr, 0, nullptr, 0, h->ffb, h->ff, N, h->ff, d, T};
         const bool stamp = h->prof && h->prof_used + 2 <= h->prof_ev.size();
         if (stamp) HIPCHK(hipEventRecord(h->prof_ev[h->prof_used], s));
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_GELU, p, s)) return -1;
+        if (gemm(OUT_ROWS, EPI_GELU, p, s)) return -1;
         if (stamp) {
             HIPCHK(hipEventRecord(h->prof_ev[h->prof_used + 1], s));
             h->prof_used += 2;
         }
-        p = GemmParams{h->ffb, h->ff, ly.ff2.w, ly.ff2.kpad, ly.ff2.bias, h->xb, d, nullptr, 0, h->tmp, d, N, d, h->ff, T, B};
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_RES, p, s)) return -1;
+        p = GemmParams{h->ffb, h->ff, ly.ff2.w, ly.ff2.kpad, ly.ff2.bias, h->xb, d, nullptr, 0, h->tmp, d, N, d, h->ff, T};
+        if (gemm(OUT_ROWS, EPI_RES, p, s)) return -1;
         const bool last = l + 1 == h->L;
         const float* res2 = nullptr;
         // the last layer's output is only needed without token 0 (model/mdm.py:219): write it compacted [Beff*T, d]
@@ -838,8 +818,8 @@ static int forward_core(gdx_model* h, const float* x, const float* temb, int tst
             HIPCHK(hipMemcpyAsync(h->taps[l + 1], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
     }
     // OutputProcess (model/mdm.py:372-380): token-major GEMM, then the permute back to [B, J, 1, T]
-    p = GemmParams{h->xc, d, h->outp.w, h->outp.kpad, h->outp.bias, nullptr, 0, nullptr, 0, h->x0t, h->ldo, Beff * T, h->ldo, d, T, B};
-    if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_BIAS, p, s)) return -1;
+    p = GemmParams{h->xc, d, h->outp.w, h->outp.kpad, h->outp.bias, nullptr, 0, nullptr, 0, h->x0t, h->ldo, Beff * T, h->ldo, d, T};
+    if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;
     if (!tm) HIPCHK(launch_transpose_out(h->x0t, x0_out, Beff, J, T, h->ldo, s));
     return 0;
 }
@@ -1237,11 +1217,11 @@ extern "C" int gdx_mfcc(const float* signal, int64_t n, int32_t frame_len, int32
     float* melv = pw + (size_t)rows * nbp;
     float* energy = melv + (size_t)rows * 64;
     HIPCHK(launch_mfcc_frames(signal, (long)n, frames, numframes, frame_len, frame_step, Lp, preemph, s));
-    GemmParams p{frames, Lp, dft, Lp, nullptr, nullptr, 0, nullptr, 0, spec, 2 * nbp, numframes, 2 * nbp, Lp, 1, 1};
-    if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_BIAS, p, s)) return -1;                       // DFT: [F, L] x [2*nbins, L]^T
+    GemmParams p{frames, Lp, dft, Lp, nullptr, nullptr, 0, nullptr, 0, spec, 2 * nbp, numframes, 2 * nbp, Lp, 1};
+    if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;                       // DFT: [F, L] x [2*nbins, L]^T
     HIPCHK(launch_mfcc_power(spec, 2 * nbp, nbp, pw, nbp, energy, numframes, nbins, nfft, s));
-    GemmParams q{pw, nbp, mel, nbp, nullptr, nullptr, 0, nullptr, 0, melv, 64, numframes, 64, nbp, 1, 1};
-    if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_BIAS, q, s)) return -1;                       // mel energies
+    GemmParams q{pw, nbp, mel, nbp, nullptr, nullptr, 0, nullptr, 0, melv, 64, numframes, 64, nbp, 1};
+    if (gemm(OUT_ROWS, EPI_BIAS, q, s)) return -1;                       // mel energies
     HIPCHK(launch_mfcc_cepstrum(melv, 64, energy, dct, lifter, mean, stdv, out, numframes, nfilt, numcep, s));
     return 0;
 }
@@ -1304,531 +1284,6 @@ extern "C" int gdx_bench_ffn_gemm(gdx_handle_t h, int32_t iters, float* avg_us, 
     hipStream_t s = (hipStream_t)stream;
     const int N = h->B * h->S, d = h->d;
     const Layer& ly = h->layers[0];
-    GemmParams p{h->xb, d, ly.ff1.w, ly.ff1.kpad, ly.ff1.bias, nullptr, 0, nullptr, 0, h->ffb, h->ff, N, h->ff, d, h->T, h->B};
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_GELU, p, s)) return -1;   // warm
-    HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i)
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_GELU, p, s)) return -1;
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.0f / (float)iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return 0;
-}
-
-// Stand-alone GEMM timing on scratch buffers (measurement helper for tools/gemm_sweep.py and bench.py).
-extern "C" int gdx_bench_gemm(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t iters, float* avg_us, void* stream) {
-    if (!avg_us || M <= 0 || N <= 0 || K <= 0 || K % 32 || iters <= 0) return fail("gdx_bench_gemm: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = gemm_init();
-    if (e != hipSuccess) return fail(std::string("gemm_init: ") + hipGetErrorString(e));
-    const int npad = round_up(N, 128);
-    float *A = nullptr, *W = nullptr, *bias = nullptr, *R = nullptr, *C = nullptr;
-    std::vector<void*> pool;
-    if (dev_alloc(pool, (void**)&A, sizeof(float) * (size_t)(M + GDX_ROW_PAD) * K) || dev_alloc(pool, (void**)&W, sizeof(float) * (size_t)npad * K) ||
-        dev_alloc(pool, (void**)&bias, sizeof(float) * npad) || dev_alloc(pool, (void**)&R, sizeof(float) * (size_t)M * N) ||
-        dev_alloc(pool, (void**)&C, sizeof(float) * (size_t)(M + GDX_ROW_PAD) * N)) {
-        free_pool(pool);
-        return -1;
-    }
-    // non-trivial operand values (zero operands raise the clock: cdna_hip_programming.md rule 25)
-    HIPCHK(gdx_randn(A, 1, (int64_t)M * K, 1, 0, 0, stream) ? hipErrorUnknown : hipSuccess);
-    HIPCHK(gdx_randn(W, 1, (int64_t)npad * K, 2, 0, 0, stream) ? hipErrorUnknown : hipSuccess);
-    HIPCHK(gdx_randn(R, 1, (int64_t)M * N, 3, 0, 0, stream) ? hipErrorUnknown : hipSuccess);
-    HIPCHK(gdx_randn(bias, 1, npad, 4, 0, 0, stream) ? hipErrorUnknown : hipSuccess);
-    GemmParams p{A, K, W, K, bias, R, N, nullptr, 0, C, N, M, N, K, 1, 1};
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i)
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, epi, p, s)) { free_pool(pool); return -1; }
-    HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i)
-        if (gemm(A_ROWS, B_WEIGHT, OUT_ROWS, epi, p, s)) { free_pool(pool); return -1; }
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.0f / (float)iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (getenv("GDX_GEMM_DEBUG")) {      // one extra launch with in-kernel stamps (diagnostic build path only)
-        unsigned long long* d = nullptr;
-        if (!dev_alloc(pool, (void**)&d, 512)) {
-            (void)hipMemsetAsync(d, 0, 512, s);
-            g2_dbg_buf = d;
-            (void)gemm(A_ROWS, B_WEIGHT, OUT_ROWS, epi, p, s);
-            g2_dbg_buf = nullptr;
-            unsigned long long h[40] = {0};
-            (void)hipMemcpyAsync(h, d, 320, hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            if (h[9]) {
-                fprintf(stderr, "[gemm2 stamps] barrier B of step 40, cycles relative to wave0 release (arrive/release):");
-                for (int w = 0; w < 12; ++w)
-                    fprintf(stderr, " w%d:%lld/%lld", w, (long long)(h[8 + 2 * w] - h[9]), (long long)(h[9 + 2 * w] - h[9]));
-                fprintf(stderr, "\n");
-            }
-            if (h[2])
-                fprintf(stderr, "[gemm2 stamps] block0 consumer: %llu cycles, %.2f us, %llu K-steps -> %.0f cycles/step, clock %.2f GHz\n",
-                        h[0], h[1] / 100.0, h[2], (double)h[0] / h[2], h[1] ? (double)h[0] / (h[1] * 10.0) : 0.0);
-        }
-    }
-    free_pool(pool);
-    return 0;
-}
-
-namespace gdx { extern int g2_test_tile[3]; }
-
-// gdx_linear_full / gdx_linear_f32: one launch through gemm() on scratch copies laid out like the workspace.  A and R carry
-// GDX_ROW_PAD rows of NaN bit patterns behind the caller's rows (in the forwards those rows hold whatever the last whole-tile
-// store left there; the kernels read whole tiles of A); C is staged from the caller's own values and copied back whole.
-static int linear_full(const char* who, const float* A, const float* W, const float* bias, const float* R, int32_t ldr,
-                       const float* V, int32_t ldv, float* C, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T,
-                       int32_t rowmap, int32_t gelu, int32_t kernel, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk,
-                       int32_t* launched, hipStream_t s) {
-    // every refusal comes before the first HIP call (tests/test_host_logic.py checks them without a GPU)
-    const std::string w(who);
-    if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || K % 32 || T <= 0) return fail(w + ": bad argument");
-    const long out_rows = rowmap ? (long)M + (M - 1) / T + 1 : M;    // rows the epilogue stores (rowmap: m + m/T + 1)
-    if (c_rows < out_rows) return fail(w + ": c_rows below the stored rows");
-    if ((R && ldr < N) || (V && ldv < N)) return fail(w + ": ldr / ldv below N");
-    if (kernel < 0 || kernel > 2) return fail(w + ": unknown kernel (0 = dispatch, 1 = gemm2.hip, 2 = gemm.hip)");
-    if (tile_mb < 0 || tile_nbw < 0 || tile_bk < 0 || ((tile_mb == 0) != (tile_nbw == 0)) || ((tile_mb == 0) != (tile_bk == 0)))
-        return fail(w + ": (tile_mb, tile_nbw, tile_bk) all positive, or (0, 0, 0)");
-    if (tile_mb && kernel == 2) return fail(w + ": a forced tile is for the persistent kernel (kernel 0 or 1) only");
-    // the mode / epilogue pair of the forward that has this operand set (forward_core); anything else has no launch
-    int om = OUT_ROWS, ep = EPI_BIAS;
-    if (gelu) {
-        if (R || V || rowmap) return fail(w + ": no launch in the forwards: GELU goes with the bias epilogue only (FFN-1)");
-        ep = EPI_GELU;
-    } else if (V) {
-        if (!R || bias || rowmap)
-            return fail(w + ": no launch in the forwards: V goes with R, without bias and without a row map (V2 proj_pose)");
-        ep = EPI_RES_VEC;
-    } else if (R) {
-        ep = EPI_RES;
-        if (rowmap) om = OUT_TOKROWS;
-    } else if (rowmap) {
-        return fail(w + ": no launch in the forwards: the row map goes with R (V1 input linear)");
-    }
-    const size_t arow = (size_t)M + GDX_ROW_PAD, crow = (size_t)c_rows + GDX_ROW_PAD;
-    const size_t r_rows = R ? (size_t)out_rows : 0, rrow = r_rows + GDX_ROW_PAD;
-    if (4 * arow * K >= (1ull << 31) || 4 * crow * N >= (1ull << 31) || (R && 4 * rrow * ldr >= (1ull << 31)))
-        return fail(w + ": an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
-    hipError_t e = gemm_init();
-    if (e != hipSuccess) return fail(std::string("gemm_init: ") + hipGetErrorString(e));
-    const int npad = round_up(N, 128);
-    float *a = nullptr, *wp = nullptr, *r = nullptr, *c = nullptr;
-    std::vector<void*> pool;
-    int rc = 0;
-    if (dev_alloc(pool, (void**)&a, sizeof(float) * arow * K) || dev_alloc(pool, (void**)&wp, sizeof(float) * (size_t)npad * K) ||
-        (R && dev_alloc(pool, (void**)&r, sizeof(float) * rrow * ldr)) || dev_alloc(pool, (void**)&c, sizeof(float) * crow * N))
-        rc = -1;
-    // 0xff bytes: every padding float is a NaN; the packed weight's padding rows are zero, as gdx_set_weight leaves them
-    if (!rc && (hipMemsetAsync(a + (size_t)M * K, 0xff, sizeof(float) * GDX_ROW_PAD * K, s) != hipSuccess ||
-                hipMemsetAsync(wp, 0, sizeof(float) * (size_t)npad * K, s) != hipSuccess ||
-                (R && hipMemsetAsync(r + r_rows * ldr, 0xff, sizeof(float) * GDX_ROW_PAD * ldr, s) != hipSuccess) ||
-                hipMemsetAsync(c + (size_t)c_rows * N, 0xff, sizeof(float) * GDX_ROW_PAD * N, s) != hipSuccess ||
-                hipMemcpyAsync(a, A, sizeof(float) * (size_t)M * K, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(wp, W, sizeof(float) * (size_t)N * K, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                (R && hipMemcpyAsync(r, R, sizeof(float) * r_rows * ldr, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-                hipMemcpyAsync(c, C, sizeof(float) * (size_t)c_rows * N, hipMemcpyDeviceToDevice, s) != hipSuccess))
-        rc = fail(w + ": staging failed");
-    if (!rc) {
-        GemmParams p{a, K, wp, K, bias, r, ldr, V, ldv, c, N, M, N, K, T, 1};
-        g2_test_tile[0] = tile_mb; g2_test_tile[1] = tile_nbw; g2_test_tile[2] = tile_bk;
-        g_gemm_test_kernel = kernel;
-        g_gemm_launched = GemmLaunched{0, 0, 0, 0, 0, 0};
-        rc = gemm(A_ROWS, B_WEIGHT, om, ep, p, s);
-        g_gemm_test_kernel = 0;
-        g2_test_tile[0] = g2_test_tile[1] = g2_test_tile[2] = 0;
-        if (launched) {
-            const GemmLaunched& l = g_gemm_launched;
-            launched[0] = l.file; launched[1] = l.mb; launched[2] = l.nbw; launched[3] = l.bk; launched[4] = l.nst; launched[5] = l.resp;
-        }
-    }
-    if (!rc && hipMemcpyAsync(C, c, sizeof(float) * (size_t)c_rows * N, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        rc = fail(w + ": copy-out failed");
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-extern "C" int gdx_linear_full(const float* A, const float* W, const float* bias, const float* R, int32_t ldr, const float* V,
-                               int32_t ldv, float* C, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T, int32_t rowmap,
-                               int32_t gelu, int32_t kernel, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk,
-                               int32_t* launched, void* stream) {
-    return linear_full("gdx_linear_full", A, W, bias, R, ldr, V, ldv, C, c_rows, M, N, K, T, rowmap, gelu, kernel, tile_mb,
-                       tile_nbw, tile_bk, launched, (hipStream_t)stream);
-}
-
-// the plain / GELU / residual epilogues of the same call, R and C [M][N], through the dispatcher
-extern "C" int gdx_linear_f32(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M,
-                              int32_t N, int32_t K, int32_t epi, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk,
-                              void* stream) {
-    if (epi < EPI_BIAS || epi > EPI_RES || (epi == EPI_RES && !R)) return fail("gdx_linear_f32: bad argument");
-    return linear_full("gdx_linear_f32", A, W, bias, epi == EPI_RES ? R : nullptr, N, nullptr, 0, C, M, M, N, K, 1, 0,
-                       epi == EPI_GELU, 0, tile_mb, tile_nbw, tile_bk, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int gdx_set_test_half_dtype(int32_t dtype) {
-    if (dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) return fail("gdx_set_test_half_dtype: GDX_DTYPE_F16 or GDX_DTYPE_BF16");
-    g_test_bf16 = dtype == GDX_DTYPE_BF16;
-    return 0;
-}
-
-namespace gdx {
-int g_gemmh_force_mb = -1, g_gemmh_force_nbw = -1;
-GemmHLaunched g_gemmh_launched = {0, 0, 0, 0, 0};
-}
-
-extern "C" int gdx_set_test_gemmh_tile(int32_t mb, int32_t nbw) {
-    if (mb < 0 || nbw < 0 || (mb == 0) != (nbw == 0)) return fail("gdx_set_test_gemmh_tile: (mb, nbw) both positive, or (0, 0)");
-    gdx::g_gemmh_force_mb = mb;
-    gdx::g_gemmh_force_nbw = nbw;
-    return 0;
-}
-
-// gdx_linear_half / gdx_linear_f16.  force_mb < 0: the process-wide tile setting (gdx_set_test_gemmh_tile) stays in force.
-static int linear_half(const char* who, const float* A, const float* W, const float* bias, const float* R, int32_t ldr,
-                       const float* V, int32_t ldv, float* C32, float* C16, int32_t c_rows, int32_t M, int32_t N, int32_t K,
-                       int32_t T, int32_t rowmap, int32_t gelu, bool bf, int32_t force_mb, int32_t force_nbw,
-                       int32_t* launched, hipStream_t s) {
-    const std::string w(who);
-    const long out_rows = rowmap ? (long)M + (M - 1) / T + 1 : M;    // rows the epilogue stores (rowmap: m + m/T + 1)
-    if (!A || !W || (!C32 && !C16) || M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 64 || T <= 0 || c_rows < out_rows ||
-        (R && (ldr < N || ldr % 4)) || (V && (ldv < N || ldv % 4)))
-        return fail(w + ": bad argument");
-    const int npad = round_up(N, 256);
-    if (2 * (size_t)M * K >= (1ull << 31) || 2 * (size_t)npad * K >= (1ull << 31) || 2 * (size_t)c_rows * N >= (1ull << 31))
-        return fail(w + ": an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
-    _Float16 *a16 = nullptr, *w16 = nullptr, *c16 = nullptr;
-    std::vector<void*> pool;
-    int rc = 0;
-    if (dev_alloc(pool, (void**)&a16, 2 * (size_t)M * K) || dev_alloc(pool, (void**)&w16, 2 * (size_t)npad * K) ||
-        (C16 && dev_alloc(pool, (void**)&c16, 2 * (size_t)c_rows * N)))
-        rc = -1;
-    if (!rc && HFN(bf, launch_convert_f16, A, a16, (int64_t)M * K, s) != hipSuccess) rc = fail(w + ": convert failed");
-    // the 16-bit output is staged from the caller's C16, so rows the kernel does not store come back unchanged (NaN stays NaN)
-    if (!rc && C16 && HFN(bf, launch_convert_f16, C16, c16, (int64_t)c_rows * N, s) != hipSuccess) rc = fail(w + ": convert failed");
-    if (!rc) rc = pack_f16_into(w16, W, N, K, 0, K, npad, K, s, bf);
-    if (!rc) {
-        GemmHParams p{a16, K, w16, K, (int)((size_t)M * K * 2), (int)((size_t)npad * K * 2), bias, R, ldr, V, ldv,
-                      C32, N, c16, N, M, N, K, T, rowmap, gelu};
-        const int keep_mb = g_gemmh_force_mb, keep_nbw = g_gemmh_force_nbw;
-        if (force_mb >= 0) { g_gemmh_force_mb = force_mb; g_gemmh_force_nbw = force_nbw; }
-        g_gemmh_launched = GemmHLaunched{0, 0, 0, 0, 0};
-        hipError_t e = HFN(bf, launch_gemmh, p, s);
-        if (force_mb >= 0) { g_gemmh_force_mb = keep_mb; g_gemmh_force_nbw = keep_nbw; }
-        if (e != hipSuccess) rc = fail(std::string("launch_gemmh: ") + hipGetErrorString(e));
-        if (launched) {
-            const GemmHLaunched& l = g_gemmh_launched;
-            launched[0] = l.mb; launched[1] = l.nbw; launched[2] = l.main_rows; launched[3] = l.tail_mb; launched[4] = l.tail_nbw;
-        }
-    }
-    if (!rc && C16 && HFN(bf, launch_convert_f32, c16, C16, (int64_t)c_rows * N, s) != hipSuccess) rc = fail(w + ": convert failed");
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-extern "C" int gdx_linear_half(const float* A, const float* W, const float* bias, const float* R, int32_t ldr, const float* V,
-                               int32_t ldv, float* C32, float* C16, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T,
-                               int32_t rowmap, int32_t gelu, int32_t dtype, int32_t tile_mb, int32_t tile_nbw,
-                               int32_t* launched, void* stream) {
-    if ((dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) || tile_mb < 0 || tile_nbw < 0 || (tile_mb == 0) != (tile_nbw == 0))
-        return fail("gdx_linear_half: bad argument");
-    return linear_half("gdx_linear_half", A, W, bias, R, ldr, V, ldv, C32, C16, c_rows, M, N, K, T, rowmap, gelu,
-                       dtype == GDX_DTYPE_BF16, tile_mb, tile_nbw, launched, (hipStream_t)stream);
-}
-
-extern "C" int gdx_linear_f16(const float* A, const float* W, const float* bias, float* C32, float* C16, int32_t M,
-                              int32_t N, int32_t K, int32_t gelu, void* stream) {
-    return linear_half("gdx_linear_f16", A, W, bias, nullptr, 0, nullptr, 0, C32, C16, M, M, N, K, 1, 0, gelu, g_test_bf16, -1,
-                       -1, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int gdx_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float* out32,
-                             float* out16, int32_t out_rows, int32_t rows, int32_t d, int32_t compact_S, int32_t half_input,
-                             int32_t dtype, void* stream) {
-    const long need = compact_S > 0 ? (long)rows - (rows + compact_S - 1) / compact_S : rows;
-    if (!x || !gamma || !beta || (!out32 && !out16) || rows <= 0 || d <= 0 || d % 32 || d > 2048 || compact_S < 0 ||
-        out_rows < need || (dtype != GDX_DTYPE_F32 && dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) ||
-        (dtype == GDX_DTYPE_F32 && (half_input || out16)) || (half_input && !out16))
-        return fail("gdx_layernorm: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const bool bf = dtype == GDX_DTYPE_BF16;
-    const int64_t n_in = (int64_t)rows * d, n_out = (int64_t)out_rows * d;
-    _Float16 *x16 = nullptr, *r16 = nullptr, *o16 = nullptr;
-    std::vector<void*> pool;
-    int rc = 0;
-    if ((half_input && (dev_alloc(pool, (void**)&x16, 2 * (size_t)n_in) || (res && dev_alloc(pool, (void**)&r16, 2 * (size_t)n_in)))) ||
-        (out16 && dev_alloc(pool, (void**)&o16, 2 * (size_t)n_out)))
-        rc = -1;
-    if (!rc && half_input && (HFN(bf, launch_convert_f16, x, x16, n_in, s) != hipSuccess ||
-                              (res && HFN(bf, launch_convert_f16, res, r16, n_in, s) != hipSuccess)))
-        rc = fail("gdx_layernorm: convert failed");
-    if (!rc && out16 && HFN(bf, launch_convert_f16, out16, o16, n_out, s) != hipSuccess) rc = fail("gdx_layernorm: convert failed");
-    if (!rc) {
-        const hipError_t e = half_input ? HFN(bf, launch_layernorm_f16, x16, r16, gamma, beta, o16, out32, rows, d, compact_S, s)
-                                        : HFN(bf, launch_layernorm, x, res, gamma, beta, out32, o16, rows, d, compact_S, s);
-        if (e != hipSuccess) rc = fail(std::string("launch_layernorm: ") + hipGetErrorString(e));
-    }
-    if (!rc && out16 && HFN(bf, launch_convert_f32, o16, out16, n_out, s) != hipSuccess) rc = fail("gdx_layernorm: convert failed");
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-extern "C" int gdx_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc, float* enc16,
-                                   int32_t enc_rows, int32_t B, int32_t T, int32_t d, int32_t heads, int32_t window,
-                                   int32_t dtype, int32_t* kernel, void* stream) {
-    const bool dt_ok = dtype == GDX_DTYPE_F32 || dtype == GDX_DTYPE_F16 || dtype == GDX_DTYPE_BF16;
-    if (!xseq || !cosT || !sinT || !dt_ok || B <= 0 || T <= 0 || heads <= 0 || d <= 0 || d % heads || (d / heads) % 2 ||
-        window <= 0 || T % window || enc_rows < (long)B * (T + 1) || (dtype == GDX_DTYPE_F32 && enc16))
-        return fail("gdx_local_attention: bad argument");
-    const bool half = local_attention_half(dtype, d, heads, window);
-    if (!half && !enc) return fail("gdx_local_attention: the fp32 kernel needs enc");
-    if (half && !enc16) return fail("gdx_local_attention: the 16-bit kernel needs enc16");
-    hipStream_t s = (hipStream_t)stream;
-    const bool bf = dtype == GDX_DTYPE_BF16;
-    const int64_t n_in = (int64_t)B * T * d, n_out = (int64_t)enc_rows * d;
-    _Float16 *x16 = nullptr, *e16 = nullptr;
-    std::vector<void*> pool;
-    int rc = 0;
-    if ((half && dev_alloc(pool, (void**)&x16, 2 * (size_t)n_in)) || (enc16 && dev_alloc(pool, (void**)&e16, 2 * (size_t)n_out)))
-        rc = -1;
-    if (!rc && half && HFN(bf, launch_convert_f16, xseq, x16, n_in, s) != hipSuccess) rc = fail("gdx_local_attention: convert failed");
-    if (!rc && enc16 && HFN(bf, launch_convert_f16, enc16, e16, n_out, s) != hipSuccess) rc = fail("gdx_local_attention: convert failed");
-    if (!rc) {
-        const hipError_t e = launch_local_attention_any(dtype, xseq, x16, cosT, sinT, enc, e16, B, T, d, heads, window, s);
-        if (e != hipSuccess) rc = fail(std::string("launch_local_attention: ") + hipGetErrorString(e));
-    }
-    if (!rc && enc16 && HFN(bf, launch_convert_f32, e16, enc16, n_out, s) != hipSuccess) rc = fail("gdx_local_attention: convert failed");
-    if (kernel) *kernel = half ? 2 : local_attention_mfma_supported(d, heads, window) ? 1 : 0;
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-extern "C" int gdx_attention_f16(const float* qkv, float* ctx, int32_t B, int32_t S, int32_t H, int32_t d, void* stream) {
-    if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H || !HFN(g_test_bf16, attentionh_supported, S, H, d))
-        return fail("gdx_attention_f16: bad argument / unsupported shape");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t rows = (size_t)B * S;
-    _Float16 *q16 = nullptr, *c16 = nullptr;
-    std::vector<void*> pool;
-    int rc = 0;
-    if (dev_alloc(pool, (void**)&q16, 2 * rows * 3 * d) || dev_alloc(pool, (void**)&c16, 2 * rows * d)) rc = -1;
-    if (!rc && HFN(g_test_bf16, launch_convert_f16, qkv, q16, (int64_t)rows * 3 * d, s) != hipSuccess) rc = fail("gdx_attention_f16: convert failed");
-    if (!rc) {
-        hipError_t e = HFN(g_test_bf16, launch_attentionh, q16, c16, B, S, H, d, (long)rows, s);
-        if (e != hipSuccess) rc = fail(std::string("launch_attentionh: ") + hipGetErrorString(e));
-    }
-    if (!rc && HFN(g_test_bf16, launch_convert_f32, c16, ctx, (int64_t)rows * d, s) != hipSuccess) rc = fail("gdx_attention_f16: convert failed");
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-extern "C" int gdx_attention_half(const float* qkv, int32_t qkv_rows, float* ctx, int32_t ctx_rows, int32_t B, int32_t S,
-                                  int32_t H, int32_t d, int32_t dtype, int32_t kernel, int32_t grid, int32_t* launched,
-                                  void* stream) {
-    // every refusal comes before the first HIP call (tests/test_host_logic.py checks them without a GPU)
-    if (dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) return fail("gdx_attention_half: dtype must be GDX_DTYPE_F16 or _BF16");
-    if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H || !HFN(dtype == GDX_DTYPE_BF16, attentionh_supported, S, H, d))
-        return fail("gdx_attention_half: bad argument / unsupported shape (head_dim 32, 64, 128 or 256)");
-    if (kernel < 0 || kernel > 3) return fail("gdx_attention_half: unknown kernel (0 = dispatch, 1 = h8, 2 = h8q, 3 = h8p)");
-    if (kernel >= 2 && d / H < 64) return fail("gdx_attention_half: h8q / h8p have no head_dim 32 instantiation");
-    if (grid < 0 || (grid > 0 && kernel != 3)) return fail("gdx_attention_half: grid is for the persistent kernel (kernel 3) only");
-    if ((long)qkv_rows < (long)B * S || (long)ctx_rows < (long)B * S) return fail("gdx_attention_half: qkv_rows / ctx_rows below B*S");
-    if (2 * (size_t)qkv_rows * 3 * d >= (1ull << 31) || 2 * (size_t)ctx_rows * d >= (1ull << 31))
-        return fail("gdx_attention_half: a buffer exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
-    hipStream_t s = (hipStream_t)stream;
-    const bool bf = dtype == GDX_DTYPE_BF16;
-    const int64_t n_in = (int64_t)qkv_rows * 3 * d, n_out = (int64_t)ctx_rows * d;
-    _Float16 *q16 = nullptr, *c16 = nullptr;
-    std::vector<void*> pool;
-    int rc = 0;
-    if (dev_alloc(pool, (void**)&q16, 2 * (size_t)n_in) || dev_alloc(pool, (void**)&c16, 2 * (size_t)n_out)) rc = -1;
-    if (!rc && HFN(bf, launch_convert_f16, qkv, q16, n_in, s) != hipSuccess) rc = fail("gdx_attention_half: convert failed");
-    // the 16-bit output is staged from the caller's ctx, so rows the kernel does not store come back unchanged (NaN stays NaN)
-    if (!rc && HFN(bf, launch_convert_f16, ctx, c16, n_out, s) != hipSuccess) rc = fail("gdx_attention_half: convert failed");
-    if (!rc) {
-        const hipError_t e = HFN(bf, launch_attentionh_kernel, q16, c16, B, S, H, d, (long)qkv_rows, kernel, grid, launched, s);
-        if (e != hipSuccess) rc = fail(std::string("launch_attentionh_kernel: ") + hipGetErrorString(e));
-    }
-    if (!rc && HFN(bf, launch_convert_f32, c16, ctx, n_out, s) != hipSuccess) rc = fail("gdx_attention_half: convert failed");
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-// fp32 SDPA core on a caller's [B*S][3d] buffer (test entry point).  The kernels read whole K/V tiles past the last
-// sample, so the call works on a scratch copy with GDX_ROW_PAD zero rows behind it, like the workspace of gdx_prepare.
-extern "C" int gdx_attention_f32(const float* qkv, float* ctx, int32_t B, int32_t S, int32_t H, int32_t d, int32_t version,
-                                 void* stream) {
-    if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H) return fail("gdx_attention_f32: bad argument");
-    const int hd = d / H;
-    if (hd != 32 && hd != 64 && hd != 128 && hd != 256) return fail("gdx_attention_f32: head_dim must be 32, 64, 128 or 256");
-    if (version == 2) return fail("gdx_attention_f32: kernel version 2 (attention2.hip) was removed in round 3");
-    if ((version == 3 || version == 5) && !attention3_supported(S, H, d))
-        return fail("gdx_attention_f32: shape not supported by the requested kernel");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t rows = (size_t)B * S, prow = rows + GDX_ROW_PAD;
-    float *q = nullptr, *c = nullptr;
-    std::vector<void*> pool;
-    int rc = 0;
-    if (dev_alloc(pool, (void**)&q, sizeof(float) * prow * 3 * d) || dev_alloc(pool, (void**)&c, sizeof(float) * prow * d)) rc = -1;
-    if (!rc && (hipMemsetAsync(q, 0, sizeof(float) * prow * 3 * d, s) != hipSuccess ||
-                hipMemcpyAsync(q, qkv, sizeof(float) * rows * 3 * d, hipMemcpyDeviceToDevice, s) != hipSuccess))
-        rc = fail("gdx_attention_f32: staging failed");
-    if (!rc) {
-        hipError_t e;
-        if (version == 5) e = launch_attention3(q, c, B, S, H, d, s, (B * H + 2) / 3);   // persistent, ~3 items per workgroup
-        else if (version == 3 || (version == 0 && attention3_supported(S, H, d))) e = launch_attention3(q, c, B, S, H, d, s);
-        else e = launch_attention(q, c, B, S, H, d, s);
-        if (e != hipSuccess) rc = fail(std::string("gdx_attention_f32: ") + hipGetErrorString(e));
-    }
-    if (!rc && hipMemcpyAsync(ctx, c, sizeof(float) * rows * d, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        rc = fail("gdx_attention_f32: copy-out failed");
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-extern "C" int gdx_bench_gemm_f16(int32_t M, int32_t N, int32_t K, int32_t gelu, int32_t iters, float* avg_us, void* stream) {
-    if (!avg_us || M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 64 || iters <= 0) return fail("gdx_bench_gemm_f16: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const int npad = round_up(N, 256);
-    if (2 * (size_t)M * K >= (1ull << 31) || 2 * (size_t)npad * K >= (1ull << 31))
-        return fail("gdx_bench_gemm_f16: an operand exceeds the 2 GiB buffer-descriptor range");
-    float *Af = nullptr, *bias = nullptr;
-    _Float16 *a16 = nullptr, *w16 = nullptr, *c16 = nullptr;
-    std::vector<void*> pool;
-    const size_t nmax = (size_t)(M > npad ? M : npad) * K;
-    if (dev_alloc(pool, (void**)&Af, 4 * nmax) || dev_alloc(pool, (void**)&bias, 4 * (size_t)npad) ||
-        dev_alloc(pool, (void**)&a16, 2 * (size_t)M * K) || dev_alloc(pool, (void**)&w16, 2 * (size_t)npad * K) ||
-        dev_alloc(pool, (void**)&c16, 2 * (size_t)M * N)) {
-        free_pool(pool);
-        return -1;
-    }
-    int rc = 0;
-    // non-trivial operand values (zero operands raise the clock: cdna_hip_programming.md rule 25)
-    if (gdx_randn(Af, 1, (int64_t)M * K, 1, 0, 0, stream) || HFN(g_test_bf16, launch_convert_f16, Af, a16, (int64_t)M * K, s) != hipSuccess ||
-        gdx_randn(Af, 1, (int64_t)npad * K, 2, 0, 0, stream) || HFN(g_test_bf16, launch_convert_f16, Af, w16, (int64_t)npad * K, s) != hipSuccess ||
-        gdx_randn(bias, 1, npad, 4, 0, 0, stream))
-        rc = fail("gdx_bench_gemm_f16: operand fill failed");
-    GemmHParams p{a16, K, w16, K, (int)((size_t)M * K * 2), (int)((size_t)npad * K * 2), bias, nullptr, 0, nullptr, 0,
-                  nullptr, 0, c16, N, M, N, K, 1, 0, gelu};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = fail("hipEventCreate failed");
-    for (int i = 0; !rc && i < 3; ++i)
-        if (HFN(g_test_bf16, launch_gemmh, p, s) != hipSuccess) rc = fail("launch_gemmh failed");
-    if (!rc) (void)hipEventRecord(e0, s);
-    for (int i = 0; !rc && i < iters; ++i)
-        if (HFN(g_test_bf16, launch_gemmh, p, s) != hipSuccess) rc = fail("launch_gemmh failed");
-    if (!rc) {
-        (void)hipEventRecord(e1, s);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *avg_us = ms * 1000.0f / (float)iters;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (!rc && getenv("GDX_GEMM_DEBUG")) {      // one extra launch with loader-wave stamps (diagnostic path only)
-        unsigned long long* dd = nullptr;
-        if (!dev_alloc(pool, (void**)&dd, 512)) {
-            (void)hipMemsetAsync(dd, 0, 512, s);
-            g2_dbg_buf = dd;
-            (void)HFN(g_test_bf16, launch_gemmh, p, s);
-            g2_dbg_buf = nullptr;
-            unsigned long long hh[48] = {0};
-            (void)hipMemcpyAsync(hh, dd, 384, hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            if (hh[12] && hh[11])
-                fprintf(stderr, "[gemmh8 stamps] block 0, wave 0: %llu tiles, loop %.1f us at %.2f GHz; per tile: drain before the stores %.0f cycles, "
-                        "epilogue (bias, convert, stores issued) %.0f; step pair in steady state %.0f cycles (%llu pairs), first two pairs after an "
-                        "epilogue %.0f cycles each\n", hh[12], hh[5] / 100.0, hh[5] ? (double)hh[4] / (hh[5] * 10.0) : 0.0,
-                        (double)hh[6] / hh[12], (double)hh[7] / hh[12], (double)hh[10] / hh[11], hh[11], hh[9] ? (double)hh[8] / hh[9] : 0.0);
-            if (hh[3])
-                fprintf(stderr, "[gemmh stamps] loader wave, block 0: %llu steps; per step: issue %.0f, vmcnt wait %.0f, barrier wait %.0f, total %.0f cycles; loop %.1f us -> s_memtime at %.2f GHz\n",
-                        hh[3], (double)hh[0] / hh[3], (double)hh[1] / hh[3], (double)hh[2] / hh[3], (double)hh[4] / hh[3],
-                        hh[5] / 100.0, hh[5] ? (double)hh[4] / (hh[5] * 10.0) : 0.0);
-        }
-    }
-    (void)hipStreamSynchronize(s);
-    free_pool(pool);
-    return rc;
-}
-
-// Stand-alone attention timing on scratch buffers (measurement helper for tools/attn_one.py).
-extern "C" int gdx_bench_attention(int32_t B, int32_t S, int32_t H, int32_t d, int32_t version, int32_t iters,
-                                   float* avg_us, void* stream) {
-    if (!avg_us || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H || iters <= 0) return fail("gdx_bench_attention: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    float *qkv = nullptr, *ctx = nullptr;
-    std::vector<void*> pool;
-    const size_t rows = (size_t)B * S + GDX_ROW_PAD;
-    if (dev_alloc(pool, (void**)&qkv, sizeof(float) * rows * 3 * d) || dev_alloc(pool, (void**)&ctx, sizeof(float) * rows * d)) {
-        free_pool(pool);
-        return -1;
-    }
-    HIPCHK(gdx_randn(qkv, 1, (int64_t)rows * 3 * d, 5, 0, 0, stream) ? hipErrorUnknown : hipSuccess);
-    _Float16 *qkv16 = nullptr, *ctx16 = nullptr;
-    if (version == 3) {
-        if (!HFN(g_test_bf16, attentionh_supported, S, H, d)) { free_pool(pool); return fail("gdx_bench_attention: shape not supported by the fp16 kernel"); }
-        if (dev_alloc(pool, (void**)&qkv16, 2 * rows * 3 * d) || dev_alloc(pool, (void**)&ctx16, 2 * rows * d)) {
-            free_pool(pool);
-            return -1;
-        }
-        HIPCHK(HFN(g_test_bf16, launch_convert_f16, qkv, qkv16, (int64_t)rows * 3 * d, s));
-    }
-    auto run = [&]() -> hipError_t {
-        if (version == 3) return HFN(g_test_bf16, launch_attentionh, qkv16, ctx16, B, S, H, d, (long)rows, s);
-        if (version == 4 && attention3_supported(S, H, d)) return launch_attention3(qkv, ctx, B, S, H, d, s);
-        return launch_attention(qkv, ctx, B, S, H, d, s);
-    };
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) HIPCHK(run());
-    HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) HIPCHK(run());
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.0f / (float)iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (version == 3 && getenv("GDX_GEMM_DEBUG")) {      // one extra launch with in-kernel stamps (persistent fp16 kernel only)
-        unsigned long long* dd = nullptr;
-        if (!dev_alloc(pool, (void**)&dd, 512)) {
-            (void)hipMemsetAsync(dd, 0, 512, s);
-            g2_dbg_buf = dd;
-            (void)run();
-            g2_dbg_buf = nullptr;
-            unsigned long long hh[16] = {0};
-            (void)hipMemcpyAsync(hh, dd, 128, hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            for (int wv = 0; wv < 2; ++wv) {
-                const unsigned long long* o = hh + 8 * wv;
-                if (o[5])
-                    fprintf(stderr, "[attentionh8p stamps] workgroup 0, wave %d: %llu tiles, kernel %.1f us at %.2f GHz; cycles per tile: DMA issue %.0f, "
-                            "QK^T %.0f, softmax %.0f, PV %.0f, wait + barrier %.0f\n", wv ? 7 : 0, o[5], o[7] / 100.0,
-                            o[7] ? (double)o[6] / (o[7] * 10.0) : 0.0, (double)o[0] / o[5], (double)o[1] / o[5], (double)o[2] / o[5],
-                            (double)o[3] / o[5], (double)o[4] / o[5]);
-            }
-        }
-    }
-    free_pool(pool);
-    return 0;
+    GemmParams p{h->xb, d, ly.ff1.w, ly.ff1.kpad, ly.ff1.bias, nullptr, 0, nullptr, 0, h->ffb, h->ff, N, h->ff, d, h->T};
+    return time_launches(1, iters, s, avg_us, [&] { return gemm(OUT_ROWS, EPI_GELU, p, s); });
 }

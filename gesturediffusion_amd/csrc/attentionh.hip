@@ -38,7 +38,6 @@
 
 namespace gdx {
 int gemm2_num_cus();
-extern unsigned long long* g2_dbg_buf;   // gemm2.hip: set by the bench helpers when GDX_GEMM_DEBUG is set
 GDX_HNS_BEGIN
 
 typedef half_t f16x8 __attribute__((ext_vector_type(8)));
@@ -788,7 +787,7 @@ __global__ __launch_bounds__(512, 1) void attentionh8p_kernel(const _Float16* __
 
 template <int HD>
 static hipError_t launch_ah8p(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_bytes, int grid,
-                              hipStream_t s) {
+                              hipStream_t s, unsigned long long* stamps) {
     const size_t lds = (size_t)3 * 2 * 32 * HD * 2 + (size_t)8 * 16 * HD * 2;   // three K/V stages + a 16-row slice per wave
     static bool attr_done = false;
     if (!attr_done) {
@@ -804,12 +803,12 @@ static hipError_t launch_ah8p(const _Float16* qkv, _Float16* ctx, int B, int S, 
     const int nchunk = (nqb + 15) / 16;
     const int nitems = B * H * nchunk;
     const float c_log2 = 1.4426950408889634f / sqrtf((float)HD);
-    if (g2_dbg_buf)                                               // the stamped build of the kernel (diagnostic launches only)
+    if (stamps)                                                   // the stamped build of the kernel (diagnostic launches only)
         hipLaunchKernelGGL((attentionh8p_kernel<HD, 2, true>), dim3(grid), dim3(512), lds, s, qkv, ctx, S, H, d, nchunk, nitems,
-                           c_log2, qkv_bytes, g2_dbg_buf);
+                           c_log2, qkv_bytes, stamps);
     else
         hipLaunchKernelGGL((attentionh8p_kernel<HD, 2, false>), dim3(grid), dim3(512), lds, s, qkv, ctx, S, H, d, nchunk, nitems,
-                           c_log2, qkv_bytes, g2_dbg_buf);
+                           c_log2, qkv_bytes, stamps);
     return hipGetLastError();
 }
 
@@ -858,9 +857,9 @@ bool attentionh_supported(int S, int H, int d) {
 // 8-wave x 1-block kernel, 2 = 8 x 2 blocks, 3 = the persistent form (the callers refuse 2 / 3 at head_dim 32, which has no
 // instantiation of them); grid > 0: workgroups of the persistent form (0 = one per CU, at most one per item).  launched
 // (optional, 3 entries): the kernel that ran (1-3), its grid and its work-item count.  qkv_rows: rows of the qkv buffer that are
-// readable (>= B*S); reads past them return zeros.
+// readable (>= B*S); reads past them return zeros.  stamps (optional): the persistent form runs its stamped build and writes there.
 hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, int kernel,
-                                    int grid, int* launched, hipStream_t s) {
+                                    int grid, int* launched, hipStream_t s, unsigned long long* stamps) {
     const int hd = d / H;
     const long bytes = qkv_rows * 3L * d * 2;
     // measured (tools/attnh_one.py, us): B=128 S=521 hd=256: 8 waves x 1 block 373, 8 waves x 2 blocks 292, persistent 273-285;
@@ -884,9 +883,9 @@ hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, i
         launched[2] = kernel == 1 ? B * H * ((nqb + 7) / 8) : (int)nitems;
     }
     if (kernel == 3) {
-        if (hd == 256) return launch_ah8p<256>(qkv, ctx, B, S, H, d, bytes, grid, s);
-        if (hd == 128) return launch_ah8p<128>(qkv, ctx, B, S, H, d, bytes, grid, s);
-        if (hd == 64) return launch_ah8p<64>(qkv, ctx, B, S, H, d, bytes, grid, s);
+        if (hd == 256) return launch_ah8p<256>(qkv, ctx, B, S, H, d, bytes, grid, s, stamps);
+        if (hd == 128) return launch_ah8p<128>(qkv, ctx, B, S, H, d, bytes, grid, s, stamps);
+        if (hd == 64) return launch_ah8p<64>(qkv, ctx, B, S, H, d, bytes, grid, s, stamps);
         return hipErrorInvalidValue;
     }
     if (kernel == 2) {

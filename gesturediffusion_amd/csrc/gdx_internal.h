@@ -34,16 +34,10 @@ constexpr int ROW_PAD = GDX_ROW_PAD;
 // ---- GEMM (gemm.hip) ---------------------------------------------------------------------
 // C = A * W^T (+ epilogue).  W is a packed weight [Npad][ldw], K-contiguous, zero padded to
 // multiples of 128 rows / 32 columns, so the weight operand never needs a bounds check.
-// Instantiated (gemm.hip GDX_GEMM_INSTANCES): A_ROWS x B_WEIGHT with OUT_ROWS under each Epi and OUT_TOKROWS under EPI_RES.
-// A_POSE, B_TOKENS and OUT_POSE are branches of the kernel template that no instantiation uses: launch_gemm refuses them.
-enum AMode { A_ROWS = 0,      // A[m][k] = A[m*lda + k]
-             A_POSE = 1 };    // (not instantiated) A[m][k] = x[(b*K + k)*T + t],  m = b*T + t   (pose tensor, k-major)
-enum BMode { B_WEIGHT = 0,    // second operand is the padded weight
-             B_TOKENS = 1 };  // (not instantiated) second operand rows are tokens: row(n) = n + n/T + 1 (skip token 0), n < N
-enum OutMode { OUT_ROWS = 0,     // C[m*ldc + n]
-               OUT_TOKROWS = 1,  // C[(m + m/T + 1)*ldc + n]   (frames into [B, T+1, d], token 0 skipped)
-               OUT_POSE = 2 };   // (not instantiated) C[((n/T)*M + m)*T + n%T]    (swapped GEMM -> pose tensor [B, M=J, 1, T])
-enum Epi { EPI_BIAS = 0,      // + bias[n]      (bias[m] for OUT_POSE)
+// Instantiated (gemm.hip GDX_GEMM_INSTANCES): OUT_ROWS under each Epi and OUT_TOKROWS under EPI_RES.  A[m][k] = A[m*lda + k].
+enum OutMode { OUT_ROWS = 0,      // C[m*ldc + n]
+               OUT_TOKROWS = 1 };  // C[(m + m/T + 1)*ldc + n]   (frames into [B, T+1, d], token 0 skipped)
+enum Epi { EPI_BIAS = 0,      // + bias[n]
            EPI_GELU = 1,      // gelu_erf(. + bias[n])
            EPI_RES = 2,       // + bias[n] + R[row_out*ldr + n]
            EPI_RES_VEC = 3 }; // + R[row_out*ldr + n] + V[(m/T)*ldv + n]
@@ -55,31 +49,40 @@ struct GemmParams {
     const float* R; int ldr;
     const float* V; int ldv;
     float* C; int ldc;
-    int M, N, K;   // K: multiple of 32 (A_ROWS)
+    int M, N, K;   // K: multiple of 32
     int T;         // frames per sample, for the row maps
-    int Bmod;      // read by the A_POSE branch only (not instantiated): source sample = (m / T) % Bmod
+};
+
+// Which kernel a launch takes depends on the problem and the environment only.  What a test or bench entry point (testapi.hip)
+// wants beyond that travels in an optional control argument of the launchers; the forwards pass none.
+// What an fp32 GEMM launch ran, filled in where the launch is decided (launch_gemm / launch_cfg): file 1 = gemm2.hip,
+// 2 = gemm.hip; for gemm2.hip the tile shape (mb, nbw, bk), its LDS ring depth and whether it was the RESP instantiation
+struct GemmLaunched { int file, mb, nbw, bk, nst, resp; };
+struct GemmCtl {
+    int file = 0;                          // 0 = the dispatch of gemm(), 1 = gemm2.hip or an error, 2 = gemm.hip
+    int mb = 0, nbw = 0, bk = 0;           // gemm2.hip tile to force (wins over GDX_GEMM_TILE); 0 = none
+    unsigned long long* stamps = nullptr;  // 512-byte device buffer for the in-kernel stamps of gemm2.hip (GDX_GEMM_DEBUG)
+    GemmLaunched ran = {0, 0, 0, 0, 0, 0}; // out
 };
 
 hipError_t gemm_init();   // raises the dynamic-LDS limit of every instantiation
-hipError_t launch_gemm(int amode, int bmode, int omode, int epi, const GemmParams& p, hipStream_t s);
+hipError_t launch_gemm(int omode, int epi, const GemmParams& p, hipStream_t s, GemmCtl* ctl = nullptr);
 
-// persistent wave-specialised variant for A_ROWS x B_WEIGHT -> OUT_ROWS (gemm2.hip)
+// persistent wave-specialised variant (gemm2.hip)
 bool gemm2_supported(int omode, int epi, const GemmParams& p);
-hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s);
-// what the last fp32 GEMM launch ran, recorded where the launch is decided (launch_gemm / launch_cfg; read by the test entry
-// point gdx_linear_full): file 1 = gemm2.hip, 2 = gemm.hip; for gemm2.hip the tile shape (mb, nbw, bk), its LDS ring depth and
-// whether it was the RESP instantiation
-struct GemmLaunched { int file, mb, nbw, bk, nst, resp; };
-extern GemmLaunched g_gemm_launched;
+hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s, GemmCtl* ctl = nullptr);
 
 // fp16-input / fp32-accumulate persistent GEMM of the reduced-precision mode (gemmh.hip):
 //   C[row_out][n] = act( sum_k A[m][k] W[n][k] + bias[n] + R[row_out][n] + V[m / T][n] ),  row_out = rowmap ? m + m/T + 1 : m
-// forced tile of launch_gemmh (both half-type builds): -1 = not read yet (GDX_GEMMH_TILE), 0 = the cost model's choice
-extern int g_gemmh_force_mb, g_gemmh_force_nbw;
-// what the last launch_gemmh ran (both half-type builds; read by the test entry point gdx_linear_half): the tile of the first
-// launch (mb == 16: the eight-wave kernel), the rows of the row cut's main part (0: no cut) and the tile of the tail launch
+// What a launch_gemmh ran: the tile of the first launch (mb == 16: the eight-wave kernel), the rows of the row cut's main part
+// (0: no cut) and the tile of the tail launch
 struct GemmHLaunched { int mb, nbw, main_rows, tail_mb, tail_nbw; };
-extern GemmHLaunched g_gemmh_launched;
+struct GemmHCtl {
+    int mb = -1, nbw = -1;                 // tile to force; (0, 0) = the cost model with its row cut, GDX_GEMMH_TILE ignored;
+                                           // negative = no say (GDX_GEMMH_TILE, else the cost model)
+    unsigned long long* stamps = nullptr;  // 512-byte device buffer for the in-kernel stamps (GDX_GEMM_DEBUG)
+    GemmHLaunched ran = {0, 0, 0, 0, 0};   // out
+};
 
 struct GemmHParams {
     const _Float16* A; int lda;      // [M][K] halves, K % 64 == 0
@@ -109,14 +112,16 @@ hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, 
 //      their gdx:: (h16) instances are called.
 #define GDX_HALF_API                                                                                                        \
     bool gemmh_supported(const GemmHParams& p);                                                                             \
-    hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s);                                                           \
+    hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s, GemmHCtl* ctl = nullptr);                                  \
     /* reduced-precision attention (attentionh.hip): qkv / ctx in halves, head_dim 32/64/128/256, any S; qkv_rows = readable rows */ \
     bool attentionh_supported(int S, int H, int d);                                                                         \
     hipError_t launch_attentionh(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, hipStream_t s); \
     /* the same dispatch with a forced kernel (0 = the forward's choice, 1 = h8, 2 = h8q, 3 = h8p), the persistent grid      \
-       (0 = its default) and a report of what ran (launched: kernel, grid, work items); used by gdx_attention_half */        \
+       (0 = its default), a report of what ran (launched: kernel, grid, work items) and a 512-byte device buffer for the     \
+       in-kernel stamps of h8p (GDX_GEMM_DEBUG); used by gdx_attention_half and gdx_bench_attention */                       \
     hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows,     \
-                                        int kernel, int grid, int* launched, hipStream_t s);                               \
+                                        int kernel, int grid, int* launched, hipStream_t s,                                \
+                                        unsigned long long* stamps = nullptr);                                              \
     /* out = LayerNorm(x + res) (res may be nullptr); compact_S > 0: rows are [B, S] tokens and token 0 of every sample is  \
        dropped from the output ([B, S-1, d]); out (fp32) and out16 (half copy) are each optional */                         \
     hipError_t launch_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float* out,        \
@@ -132,16 +137,16 @@ hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, 
                                    int M, int N, int K, int act, hipStream_t s);                                            \
     /* out[m][:] = table[idx[m]][:]   (timestep -> sinusoidal row gather) */                                                \
     hipError_t launch_gather_rows(const float* table, const int64_t* idx, float* out, int M, int d, int max_rows, hipStream_t s); \
-    /* out[(b*rps + t + off)*d + n] = sum_c mfcc[((b%Bmod)*C + c)*T + t] * W[n*ldw + c] + bias[n] (+ pe[(t+1)*d + n] if pe) */ \
+    /* out[(b*rps + t + off)*d + n] = sum_c mfcc[((b%Bsrc)*C + c)*T + t] * W[n*ldw + c] + bias[n] (+ pe[(t+1)*d + n] if pe) */ \
     hipError_t launch_mfcc_project(const float* mfcc, const float* W, int ldw, const float* bias, const float* pe, float* out, \
-                                   int B, int Bmod, int C, int T, int d, int rps, int off, hipStream_t s);                  \
-    /* token 0 of the encoder input: enc[b*S*d + n] = temb[(b%Bmod)*tstride + n] + seed[b*d + n] (+ pe0[n]).                \
-       c2 != nullptr (V2): c2[b*d+n] = c2t[(b%Bmod)*tstride + n] + c2_seed[b*d+n] -- the coarse slice of project_to_lat     \
+                                   int B, int Bsrc, int C, int T, int d, int rps, int off, hipStream_t s);                  \
+    /* token 0 of the encoder input: enc[b*S*d + n] = temb[(b%Bsrc)*tstride + n] + seed[b*d + n] (+ pe0[n]).                \
+       c2 != nullptr (V2): c2[b*d+n] = c2t[(b%Bsrc)*tstride + n] + c2_seed[b*d+n] -- the coarse slice of project_to_lat     \
        applied to (temb + seed_emb), split into its timestep half (c2t = W_coa temb rows, same stride as temb) and its seed \
        half (per conditioning) instead of a [B,d] x [d,d] linear per step */                                                \
     hipError_t launch_token0(const float* temb, int tstride, const float* seed_emb, const float* pe0, float* enc,           \
                              _Float16* enc16, const float* c2t, const float* c2_seed, float* c2, const int* state, int B,   \
-                             int Bmod, int S, int d, hipStream_t s);                                                        \
+                             int Bsrc, int S, int d, hipStream_t s);                                                        \
     /* V2 front end: RoPE -> causal local attention (window, look back one window) -> RoPE at pos+1, written into          \
        enc[b][t+1][:].   xseq [B*T][d];  cos/sin tables [>=T+1][e/2], e = d/heads. */                                       \
     hipError_t launch_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc, _Float16* enc16, \

@@ -18,11 +18,6 @@
 //     (one barrier per K tile).
 //   * XCD-aware tile order: blocks that share an A row-panel get consecutive logical ids and the
 //     ids are dealt so that each XCD (private 4 MiB L2) owns a contiguous range.
-//   * The template still carries the pose-tensor operand modes of the first build (A_POSE: [B, J, 1, T] read
-//     k-major and staged [k][m]; B_TOKENS / OUT_POSE: the output projection computed swapped), but nothing
-//     launches them since the forwards transpose the pose tensor once (misc.hip): only the five
-//     A_ROWS x B_WEIGHT instantiations of GDX_GEMM_INSTANCES are compiled, and launch_gemm refuses any other
-//     mode combination (tests/test_gpu_gemm_f32.py tests those five).
 #include "gdx_internal.h"
 
 namespace gdx {
@@ -39,7 +34,7 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return x * 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
-template <int AMODE, int BMODE, int OMODE, int EPI>
+template <int OMODE, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -65,62 +60,38 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     const int lc4 = tid & 7;        // float4 column inside the 32-wide K tile
     const float* a_src[4];
     const float* b_src[4];
-    long a_pose_base = 0;           // A_POSE: offset of (b, k=0, t) for this thread's m
-    if (AMODE == A_ROWS) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int row = m0 + lrow + 32 * r;
-            row = row < p.M ? row : p.M - 1;
-            a_src[r] = p.A + (long)row * p.lda + lc4 * 4;
-        }
-    } else {
-        int m = m0 + (tid & 127);
-        m = m < p.M ? m : p.M - 1;
-        const int b = m / p.T, t = m - b * p.T;
-        a_pose_base = (long)(b % p.Bmod) * p.K * p.T + t;
+    for (int r = 0; r < 4; ++r) {
+        int row = m0 + lrow + 32 * r;
+        row = row < p.M ? row : p.M - 1;
+        a_src[r] = p.A + (long)row * p.lda + lc4 * 4;
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        int row = n0 + lrow + 32 * r;
-        if (BMODE == B_TOKENS) {
-            row = row < p.N ? row : p.N - 1;
-            row = row + row / p.T + 1;
-        }
+        const int row = n0 + lrow + 32 * r;
         b_src[r] = p.W + (long)row * p.ldw + lc4 * 4;
     }
 
     f32x4 ra[4], rb[4];
-    float rap[16];
     const int nk = (p.K + BK - 1) / BK;
 
     auto load_tile = [&](int kt) {
         const int k0 = kt * BK;
-        if (AMODE == A_ROWS) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ra[r] = *reinterpret_cast<const f32x4*>(a_src[r] + k0);
-        } else {
-            const int ksub = tid >> 7;     // 0..1
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int k = k0 + ksub + 2 * r;
-                rap[r] = k < p.K ? p.A[a_pose_base + (long)k * p.T] : 0.0f;
-            }
-        }
+        for (int r = 0; r < 4; ++r) ra[r] = *reinterpret_cast<const f32x4*>(a_src[r] + k0);
+        // Naming p makes this closure capture it, as it did while the pose-tensor operand modes of the first build were branches of
+        // this template.  Without the capture the compiler orders the kernel's instructions differently; with it the five
+        // instantiations are instruction for instruction the code every measurement so far was made with.
+        (void)p;
 #pragma unroll
         for (int r = 0; r < 4; ++r) rb[r] = *reinterpret_cast<const f32x4*>(b_src[r] + k0);
     };
     auto store_tile = [&](int stage) {
         float* As = smem + stage * 2 * TILE_F;
         float* Bs = As + TILE_F;
-        if (AMODE == A_ROWS) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<f32x4*>(&As[(lrow + 32 * r) * LDS_STRIDE + lc4 * 4]) = ra[r];
-        } else {
-            const int ksub = tid >> 7, mloc = tid & 127;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) As[(ksub + 2 * r) * BM + mloc] = rap[r];
-        }
+        for (int r = 0; r < 4; ++r)
+            *reinterpret_cast<f32x4*>(&As[(lrow + 32 * r) * LDS_STRIDE + lc4 * 4]) = ra[r];
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             *reinterpret_cast<f32x4*>(&Bs[(lrow + 32 * r) * LDS_STRIDE + lc4 * 4]) = rb[r];
@@ -150,12 +121,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
                 const int row = wr * 64 + mi * 32 + l31;
-                if (AMODE == A_ROWS) {
-                    a[mi] = *reinterpret_cast<const f32x4*>(&As[row * LDS_STRIDE + koff]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) a[mi][j] = As[(koff + j) * BM + row];
-                }
+                a[mi] = *reinterpret_cast<const f32x4*>(&As[row * LDS_STRIDE + koff]);
             }
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
@@ -182,50 +148,40 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
             const int n = n0 + wc * 64 + ni * 32 + l31;
             if (n >= p.N) continue;
             float bias_n = 0.0f;
-            if (OMODE != OUT_POSE && p.bias) bias_n = p.bias[n];
-            long out_col = n;
-            if (OMODE == OUT_POSE) {
-                const int b = n / p.T, t = n - b * p.T;
-                out_col = (long)b * p.M * p.T + t;
-            }
+            if (p.bias) bias_n = p.bias[n];
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int m = m0 + wr * 64 + mi * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
                 if (m >= p.M) continue;
                 float v = acc[mi][ni][reg];
-                if (OMODE == OUT_POSE) {
-                    if (p.bias) v += p.bias[m];
-                    p.C[out_col + (long)m * p.T] = v;
+                long row_out = m;
+                if (OMODE == OUT_TOKROWS) row_out = m + m / p.T + 1;
+                if (EPI == EPI_BIAS) {
+                    v += bias_n;
+                } else if (EPI == EPI_GELU) {
+                    v = gelu_erf(v + bias_n);
+                } else if (EPI == EPI_RES) {
+                    v = (v + bias_n) + p.R[row_out * p.ldr + n];
                 } else {
-                    long row_out = m;
-                    if (OMODE == OUT_TOKROWS) row_out = m + m / p.T + 1;
-                    if (EPI == EPI_BIAS) {
-                        v += bias_n;
-                    } else if (EPI == EPI_GELU) {
-                        v = gelu_erf(v + bias_n);
-                    } else if (EPI == EPI_RES) {
-                        v = (v + bias_n) + p.R[row_out * p.ldr + n];
-                    } else {
-                        v = (v + p.R[row_out * p.ldr + n]) + p.V[(long)(m / p.T) * p.ldv + n];
-                    }
-                    p.C[row_out * p.ldc + n] = v;
+                    v = (v + p.R[row_out * p.ldr + n]) + p.V[(long)(m / p.T) * p.ldv + n];
                 }
+                p.C[row_out * p.ldc + n] = v;
             }
         }
     }
 }
 
-#define GDX_GEMM_INSTANCES(X)                        \
-    X(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_BIAS)          \
-    X(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_GELU)          \
-    X(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_RES)           \
-    X(A_ROWS, B_WEIGHT, OUT_ROWS, EPI_RES_VEC)       \
-    X(A_ROWS, B_WEIGHT, OUT_TOKROWS, EPI_RES)
+#define GDX_GEMM_INSTANCES(X)    \
+    X(OUT_ROWS, EPI_BIAS)       \
+    X(OUT_ROWS, EPI_GELU)       \
+    X(OUT_ROWS, EPI_RES)        \
+    X(OUT_ROWS, EPI_RES_VEC)    \
+    X(OUT_TOKROWS, EPI_RES)
 
 hipError_t gemm_init() {
     hipError_t e = hipSuccess;
-#define X(a, b, o, ep)                                                                             \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<a, b, o, ep>),              \
+#define X(o, ep)                                                                                   \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<o, ep>),                    \
                             hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);           \
     if (e != hipSuccess) return e;
     GDX_GEMM_INSTANCES(X)
@@ -233,13 +189,13 @@ hipError_t gemm_init() {
     return e;
 }
 
-hipError_t launch_gemm(int amode, int bmode, int omode, int epi, const GemmParams& p, hipStream_t s) {
+hipError_t launch_gemm(int omode, int epi, const GemmParams& p, hipStream_t s, GemmCtl* ctl) {
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
     const dim3 grid(nbm * nbn), block(256);
-#define X(a, b, o, ep)                                                                             \
-    if (amode == a && bmode == b && omode == o && epi == ep) {                                     \
-        g_gemm_launched = GemmLaunched{2, 0, 0, 0, 0, 0};                                          \
-        hipLaunchKernelGGL((gemm_kernel<a, b, o, ep>), grid, block, GEMM_LDS_BYTES, s, p);         \
+#define X(o, ep)                                                                                   \
+    if (omode == o && epi == ep) {                                                                 \
+        if (ctl) ctl->ran = GemmLaunched{2, 0, 0, 0, 0, 0};                                        \
+        hipLaunchKernelGGL((gemm_kernel<o, ep>), grid, block, GEMM_LDS_BYTES, s, p);               \
         return hipGetLastError();                                                                  \
     }
     GDX_GEMM_INSTANCES(X)

@@ -376,10 +376,6 @@ __global__ __launch_bounds__(512, 1) void gemm4_kernel(const GemmParams p, const
 #endif
 }
 
-unsigned long long* g2_dbg_buf = nullptr;   // set by gdx_bench_gemm when GDX_GEMM_DEBUG is set
-int g2_test_tile[3] = {0, 0, 0};            // (MB, NBW, BK) forced by gdx_linear_full for the duration of one call (tests)
-GemmLaunched g_gemm_launched = {0, 0, 0, 0, 0, 0};
-
 template <int MB, int NBW, int BK, int NST>
 constexpr size_t g4_lds_bytes(int N) {
     constexpr int ROWB = (BK + 8) * 4;
@@ -388,9 +384,9 @@ constexpr size_t g4_lds_bytes(int N) {
 }
 
 template <int MB, int NBW, int BK, int NST, bool RESP = false>
-static hipError_t launch_cfg(const GemmParams& p, int epi, int omode, int num_cus, hipStream_t s) {
+static hipError_t launch_cfg(const GemmParams& p, int epi, int omode, int num_cus, hipStream_t s, GemmCtl* ctl) {
     if constexpr (!RESP && MB * NBW <= 10) {                     // (the residual block costs 4 * MB * NBW registers)
-        if (p.R && !p.V && omode == OUT_ROWS && epi == EPI_BIAS) return launch_cfg<MB, NBW, BK, NST, true>(p, epi, omode, num_cus, s);
+        if (p.R && !p.V && omode == OUT_ROWS && epi == EPI_BIAS) return launch_cfg<MB, NBW, BK, NST, true>(p, epi, omode, num_cus, s, ctl);
     }
     constexpr int BM = MB * 16, BN = NBW * 64;
     static_assert(BM <= ROW_PAD, "whole-tile stores of the last row tile must stay inside the workspace padding");
@@ -406,9 +402,9 @@ static hipError_t launch_cfg(const GemmParams& p, int epi, int omode, int num_cu
     const int ntm = (p.M + BM - 1) / BM, ntn = p.N / BN;
     const int ntiles = ntm * ntn;
     const int grid = ntiles < num_cus ? ntiles : num_cus;
-    g_gemm_launched = GemmLaunched{1, MB, NBW, BK, NST, RESP ? 1 : 0};
+    if (ctl) ctl->ran = GemmLaunched{1, MB, NBW, BK, NST, RESP ? 1 : 0};
     hipLaunchKernelGGL((gemm4_kernel<MB, NBW, BK, NST, RESP>), dim3(grid), dim3(512), lds, s, p, epi, omode, ntn, ntiles,
-                       g2_dbg_buf);
+                       ctl ? ctl->stamps : nullptr);
     return hipGetLastError();
 }
 
@@ -458,7 +454,7 @@ bool gemm2_supported(int omode, int epi, const GemmParams& p) {
            (!p.V || (p.ldv % 4 == 0 && ((uintptr_t)p.V & 15) == 0));
 }
 
-hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s) {
+hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s, GemmCtl* ctl) {
     const int num_cus = gemm2_num_cus();
     int best_mb = 0, best_nbw = 0, best_bk = 0;
     static int force_mb = -1, force_nbw = -1, force_bk = -1;
@@ -467,8 +463,8 @@ hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s) 
         if (const char* e = getenv("GDX_GEMM_TILE")) sscanf(e, "%d,%d,%d", &force_mb, &force_nbw, &force_bk);
     }
     static const bool debug = getenv("GDX_GEMM_DEBUG") != nullptr;
-    const int f_mb = g2_test_tile[0] ? g2_test_tile[0] : force_mb, f_nbw = g2_test_tile[0] ? g2_test_tile[1] : force_nbw,
-              f_bk = g2_test_tile[0] ? g2_test_tile[2] : force_bk;     // gdx_linear_f32's tile argument wins over the environment
+    const bool forced = ctl && ctl->mb;                                // the caller's tile wins over the environment
+    const int f_mb = forced ? ctl->mb : force_mb, f_nbw = forced ? ctl->nbw : force_nbw, f_bk = forced ? ctl->bk : force_bk;
     double best = 1e30;
 #define X(mb, nbw, bk, nst)                                                                       \
     if (g4_valid(mb, nbw, bk, nst, p) && !(nst == 2 && p.R)) {                            \
@@ -483,7 +479,7 @@ hipError_t launch_gemm2(int omode, int epi, const GemmParams& p, hipStream_t s) 
         fprintf(stderr, "[gemm2] M=%d N=%d K=%d epi=%d -> tile %dx%d BK=%d\n", p.M, p.N, p.K, epi, best_mb * 16,
                 best_nbw * 64, best_bk);
 #define X(mb, nbw, bk, nst) \
-    if (best_mb == mb && best_nbw == nbw && best_bk == bk) return launch_cfg<mb, nbw, bk, nst>(p, epi, omode, num_cus, s);
+    if (best_mb == mb && best_nbw == nbw && best_bk == bk) return launch_cfg<mb, nbw, bk, nst>(p, epi, omode, num_cus, s, ctl);
     G4_CONFIGS(X)
 #undef X
     return hipErrorInvalidValue;

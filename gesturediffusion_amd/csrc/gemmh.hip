@@ -36,7 +36,6 @@
 
 namespace gdx {
 
-extern unsigned long long* g2_dbg_buf;   // gemm2.hip: set by the bench helpers when GDX_GEMM_DEBUG is set
 int gemm2_num_cus();
 
 GDX_HNS_BEGIN
@@ -723,7 +722,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
 #endif
 }
 
-static hipError_t launch_cfg_h8b(const GemmHParams& p, int num_cus, hipStream_t s) {
+static hipError_t launch_cfg_h8b(const GemmHParams& p, int num_cus, hipStream_t s, unsigned long long* stamps) {
     const size_t lds = (size_t)5 * 32768;                         // all of the CU's LDS
     static bool attr_set = false;
     if (!attr_set) {
@@ -739,7 +738,7 @@ static hipError_t launch_cfg_h8b(const GemmHParams& p, int num_cus, hipStream_t 
     // N = 3 072 449-458 -> 439-449 us, N = 2 048 322 -> 310; N = 1 024 is one group either way (groups of 1 / 2: slower); config 5 in
     // situ, three alternating runs: 10.27-10.33 -> 10.24-10.30 ms/step
     const int cgw = ntn < 4 ? ntn : 4;
-    hipLaunchKernelGGL(gemmh8b_kernel, dim3(grid), dim3(512), lds, s, p, ntn, ntiles, cgw, g2_dbg_buf);
+    hipLaunchKernelGGL(gemmh8b_kernel, dim3(grid), dim3(512), lds, s, p, ntn, ntiles, cgw, stamps);
     return hipGetLastError();
 }
 
@@ -749,7 +748,7 @@ constexpr size_t gh_lds_bytes(int N) {
 }
 
 template <int MB, int NBW, int NST, bool PAIR>
-static hipError_t launch_cfg_hp(const GemmHParams& p, int num_cus, hipStream_t s) {
+static hipError_t launch_cfg_hp(const GemmHParams& p, int num_cus, hipStream_t s, unsigned long long* stamps) {
     constexpr int BM = MB * 16, BN = NBW * 64;
     const size_t lds = gh_lds_bytes<MB, NBW, NST>(p.N);
     static size_t attr_lds = 0;
@@ -762,14 +761,14 @@ static hipError_t launch_cfg_hp(const GemmHParams& p, int num_cus, hipStream_t s
     const int ntm = (p.M + BM - 1) / BM, ntn = p.N / BN;
     const int ntiles = ntm * ntn;
     const int grid = ntiles < num_cus ? ntiles : num_cus;
-    hipLaunchKernelGGL((gemmh_kernel<MB, NBW, NST, PAIR>), dim3(grid), dim3(512), lds, s, p, ntn, ntiles, g2_dbg_buf);
+    hipLaunchKernelGGL((gemmh_kernel<MB, NBW, NST, PAIR>), dim3(grid), dim3(512), lds, s, p, ntn, ntiles, stamps);
     return hipGetLastError();
 }
 
 template <int MB, int NBW, int NST>
-static hipError_t launch_cfg_h(const GemmHParams& p, int num_cus, hipStream_t s) {
-    if (g2_dbg_buf) return launch_cfg_hp<MB, NBW, NST, false>(p, num_cus, s);   // the stamped diagnostic build is the per-slab one
-    return launch_cfg_hp<MB, NBW, NST, true>(p, num_cus, s);
+static hipError_t launch_cfg_h(const GemmHParams& p, int num_cus, hipStream_t s, unsigned long long* stamps) {
+    if (stamps) return launch_cfg_hp<MB, NBW, NST, false>(p, num_cus, s, stamps);   // the stamped diagnostic build is the per-slab one
+    return launch_cfg_hp<MB, NBW, NST, true>(p, num_cus, s, nullptr);
 }
 
 // (MB, NBW, NST): tile = 16*MB rows x 64*NBW columns, NST LDS stages of (16*MB + 64*NBW) * 64 bytes
@@ -834,23 +833,29 @@ static GhChoice gh_choose(const GemmHParams& p, int M, int num_cus, int force_mb
     return c;
 }
 
-static hipError_t launch_gh_choice(const GemmHParams& p, const GhChoice& c, int num_cus, hipStream_t s) {
-    if (c.tmb == 16) return launch_cfg_h8b(p, num_cus, s);
+static hipError_t launch_gh_choice(const GemmHParams& p, const GhChoice& c, int num_cus, hipStream_t s,
+                                   unsigned long long* stamps) {
+    if (c.tmb == 16) return launch_cfg_h8b(p, num_cus, s, stamps);
 #define X(mb, nbw, nst) \
-    if (c.tmb == mb && c.tnbw == nbw) return launch_cfg_h<mb, nbw, nst>(p, num_cus, s);
+    if (c.tmb == mb && c.tnbw == nbw) return launch_cfg_h<mb, nbw, nst>(p, num_cus, s, stamps);
     GH_CONFIGS(X)
 #undef X
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s) {
+hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s, GemmHCtl* ctl) {
     if (!GDX_HNS_NAME::gemmh_supported(p)) return hipErrorInvalidValue;
     const int num_cus = gemm2_num_cus();
-    if (g_gemmh_force_mb < 0) {
-        g_gemmh_force_mb = g_gemmh_force_nbw = 0;
-        if (const char* e = getenv("GDX_GEMMH_TILE")) sscanf(e, "%d,%d", &g_gemmh_force_mb, &g_gemmh_force_nbw);
+    static int env_mb = -1, env_nbw = -1;
+    if (env_mb < 0) {
+        int mb = 0, nbw = 0;
+        if (const char* e = getenv("GDX_GEMMH_TILE")) sscanf(e, "%d,%d", &mb, &nbw);
+        env_nbw = nbw;
+        env_mb = mb < 0 ? 0 : mb;
     }
-    const int force_mb = g_gemmh_force_mb, force_nbw = g_gemmh_force_nbw;
+    const bool forced = ctl && ctl->mb >= 0;                          // the caller's tile, (0, 0) included, wins over the environment
+    const int force_mb = forced ? ctl->mb : env_mb, force_nbw = forced ? ctl->nbw : env_nbw;
+    unsigned long long* const stamps = ctl ? ctl->stamps : nullptr;
     static const bool debug = getenv("GDX_GEMM_DEBUG") != nullptr;
     const bool gelu = p.gelu != 0;
     const GhChoice whole = gh_choose(p, p.M, num_cus, force_mb, force_nbw);
@@ -885,16 +890,16 @@ hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s) {
                 if (debug)
                     fprintf(stderr, "[gemmh] M=%d N=%d K=%d -> rows 0..%d as 256x256 tiles (%ld rounds), %d rows as %dx%d tiles\n",
                             p.M, p.N, p.K, m_main, full, pt.M, tail.tmb * 16, tail.tnbw * 64);
-                g_gemmh_launched = GemmHLaunched{16, 4, m_main, tail.tmb, tail.tnbw};
-                hipError_t e = launch_gh_choice(pm, GhChoice{c_main, 16, 4}, num_cus, s);
+                if (ctl) ctl->ran = GemmHLaunched{16, 4, m_main, tail.tmb, tail.tnbw};
+                hipError_t e = launch_gh_choice(pm, GhChoice{c_main, 16, 4}, num_cus, s, stamps);
                 if (e != hipSuccess) return e;
-                return launch_gh_choice(pt, tail, num_cus, s);
+                return launch_gh_choice(pt, tail, num_cus, s, stamps);
             }
         }
     }
     if (debug) fprintf(stderr, "[gemmh] M=%d N=%d K=%d -> tile %dx%d\n", p.M, p.N, p.K, whole.tmb * 16, whole.tnbw * 64);
-    g_gemmh_launched = GemmHLaunched{whole.tmb, whole.tnbw, 0, 0, 0};
-    return launch_gh_choice(p, whole, num_cus, s);
+    if (ctl) ctl->ran = GemmHLaunched{whole.tmb, whole.tnbw, 0, 0, 0};
+    return launch_gh_choice(p, whole, num_cus, s, stamps);
 }
 
 GDX_HNS_END

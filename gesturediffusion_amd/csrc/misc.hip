@@ -361,7 +361,7 @@ hipError_t launch_gather_rows(const float* table, const int64_t* idx, float* out
 __global__ __launch_bounds__(256) void mfcc_project_kernel(const float* __restrict__ mfcc, const float* __restrict__ W,
                                                            int ldw, const float* __restrict__ bias,
                                                            const float* __restrict__ pe, float* __restrict__ out,
-                                                           int B, int Bmod, int C, int T, int d, int rps, int off, int rows_per_block) {
+                                                           int B, int Bsrc, int C, int T, int d, int rps, int off, int rows_per_block) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     const long row0 = (long)blockIdx.y * rows_per_block;
     const long nrows = (long)B * T;
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void mfcc_project_kernel(const float* __restri
     const float bn = bias[n];
     for (long bt = row0; bt < row0 + rows_per_block && bt < nrows; ++bt) {
         const int t = bt % T, b = bt / T;
-        const float* m = mfcc + ((long)(b % Bmod) * C) * T + t;
+        const float* m = mfcc + ((long)(b % Bsrc) * C) * T + t;
         float s = 0.0f;
 #pragma unroll
         for (int c = 0; c < 32; ++c)
@@ -384,13 +384,13 @@ __global__ __launch_bounds__(256) void mfcc_project_kernel(const float* __restri
 }
 
 hipError_t launch_mfcc_project(const float* mfcc, const float* W, int ldw, const float* bias, const float* pe,
-                               float* out, int B, int Bmod, int C, int T, int d, int rps, int off, hipStream_t s) {
+                               float* out, int B, int Bsrc, int C, int T, int d, int rps, int off, hipStream_t s) {
     if (C > 32) return hipErrorInvalidValue;                      // gdx_create caps mfcc_dim at 32
     const long nrows = (long)B * T;
     if (nrows <= 0) return hipSuccess;
     const int rpb = 64;
     hipLaunchKernelGGL(mfcc_project_kernel, dim3((d + 255) / 256, (unsigned)((nrows + rpb - 1) / rpb)), dim3(256), 0, s, mfcc, W,
-                       ldw, bias, pe, out, B, Bmod, C, T, d, rps, off, rpb);
+                       ldw, bias, pe, out, B, Bsrc, C, T, d, rps, off, rpb);
     return hipGetLastError();
 }
 
@@ -398,7 +398,7 @@ hipError_t launch_mfcc_project(const float* mfcc, const float* W, int ldw, const
 __global__ void token0_kernel(const float* __restrict__ temb, int tstride, const float* __restrict__ seed_emb,
                               const float* __restrict__ pe0, float* __restrict__ enc, half_t* __restrict__ enc16,
                               const float* __restrict__ c2t, const float* __restrict__ c2_seed, float* __restrict__ c2,
-                              const int* __restrict__ state, int B, int Bmod, int S, int d) {
+                              const int* __restrict__ state, int B, int Bsrc, int S, int d) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * d) return;
     const int b = i / d, n = i % d;
@@ -406,7 +406,7 @@ __global__ void token0_kernel(const float* __restrict__ temb, int tstride, const
         temb += (long)state[0] * d;
         if (c2t) c2t += (long)state[0] * d;
     }
-    const long trow = (long)(b % Bmod) * tstride + n;
+    const long trow = (long)(b % Bsrc) * tstride + n;
     float v = temb[trow] + seed_emb[i];
     if (c2) c2[i] = c2t[trow] + c2_seed[i];       // coarse slice of project_to_lat: W_coa temb + W_coa seed_emb
     if (pe0) v += pe0[n];
@@ -416,10 +416,10 @@ __global__ void token0_kernel(const float* __restrict__ temb, int tstride, const
 
 hipError_t launch_token0(const float* temb, int tstride, const float* seed_emb, const float* pe0, float* enc,
                          _Float16* enc16_, const float* c2t, const float* c2_seed, float* c2, const int* state, int B,
-                         int Bmod, int S, int d, hipStream_t s) {
+                         int Bsrc, int S, int d, hipStream_t s) {
     half_t* enc16 = reinterpret_cast<half_t*>(enc16_);
     hipLaunchKernelGGL(token0_kernel, dim3((B * d + 255) / 256), dim3(256), 0, s, temb, tstride, seed_emb, pe0, enc,
-                       enc16, c2t, c2_seed, c2, state, B, Bmod, S, d);
+                       enc16, c2t, c2_seed, c2, state, B, Bsrc, S, d);
     return hipGetLastError();
 }
 
