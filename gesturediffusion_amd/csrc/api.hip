@@ -1,13 +1,9 @@
-// libgdx.so host side: handle, packed weights, workspace, the per-step kernel sequence of the
+// libgdx.so host side: handle, workspace, the per-step kernel sequence of the
 // denoiser (V1 = reference model/mdm_old.py:84-122, V2 = model/mdm.py:105-224) and the sampling
-// loops (diffusion/gaussian_diffusion.py:598-730, 879-993).  C ABI in include/gdx.h.
+// loops (diffusion/gaussian_diffusion.py:598-730, 879-993).  C ABI in include/gdx.h; the handle's weights are in weights.hip.
 #include "gdx_host.h"
 
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -20,105 +16,9 @@ int fail(const std::string& m) {
     return -1;
 }
 
-// dst[r][c] = (r < n && c < k) ? src[r*src_ld + col0 + c] : 0      (dst is [npad][kpad])
-__global__ void pack_weight_kernel(const float* __restrict__ src, int src_ld, int col0, int n, int k,
-                                   float* __restrict__ dst, int npad, int kpad) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)npad * kpad) return;
-    const int r = i / kpad, c = i % kpad;
-    dst[i] = (r < n && c < k) ? src[(long)r * src_ld + col0 + c] : 0.0f;
-}
-
-// dst[r][c] = (r < n && c < k) ? (fp16) src[r*src_ld + col0 + c] : 0      (dst is [npad][kpad] halves)
-__global__ void pack_weight_f16_kernel(const float* __restrict__ src, int src_ld, int col0, int n, int k,
-                                       _Float16* __restrict__ dst, int npad, int kpad) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)npad * kpad) return;
-    const int r = i / kpad, c = i % kpad;
-    dst[i] = (r < n && c < k) ? (_Float16)src[(long)r * src_ld + col0 + c] : (_Float16)0.0f;
-}
-
-// the same with bf16 elements (GDX_DTYPE_BF16); the destination is passed as an opaque 16-bit pointer like every half buffer
-__global__ void pack_weight_bf16_kernel(const float* __restrict__ src, int src_ld, int col0, int n, int k,
-                                        _Float16* __restrict__ dst_, int npad, int kpad) {
-    __bf16* dst = reinterpret_cast<__bf16*>(dst_);
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)npad * kpad) return;
-    const int r = i / kpad, c = i % kpad;
-    dst[i] = (r < n && c < k) ? (__bf16)src[(long)r * src_ld + col0 + c] : (__bf16)0.0f;
-}
-
-struct Packed {          // a Linear weight [n][k] packed to [npad][kpad] (+ bias [npad])
-    float* w = nullptr;
-    float* bias = nullptr;
-    int n = 0, k = 0, npad = 0, kpad = 0;
-    _Float16* w16 = nullptr;             // fp16 mode: [npad16][kpad16], rows padded to 256, K to 64 (gemmh.hip)
-    int npad16 = 0, kpad16 = 0;
-};
-
-struct Layer {
-    Packed qkv, out, ff1, ff2;
-    float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
-};
-
 }  // namespace gdx
 
 using namespace gdx;
-int gdx_sampler_update_state_(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);   // sampler.hip
-int gdx_sampler_update_tm_(int kind, int B, int J, int T, int ldx, int ldo, const float* coef, int step_index, float* xt,
-                           const float* x0t, const float* scale, int const_noise, uint64_t seed, uint64_t sample_offset,
-                           uint32_t rng_step, int clip, float* out_pose, void* xt16, int half_dtype, void* stream, const float* noise);      // sampler.hip
-
-struct gdx_model {
-    gdx_config_t cfg;
-    int d, J, ff, L, H;
-    bool f16 = false;                 // reduced-precision mode (GDX_DTYPE_F16 or _BF16): 16-bit MFMA operands, fp32 accumulate
-    bool bf16 = false;                // ... with bf16 elements (the gdx::b16 kernels)
-    bool stream32 = false;            // 16-bit modes: the residual stream (x + sublayer(x), LayerNorm in / out) stays fp32 and
-                                      // only the GEMM / attention operands are 16-bit copies (default for bf16, see forward_core_f16)
-    _Float16 *xt16 = nullptr, *xa16 = nullptr, *xb16 = nullptr, *qkv16 = nullptr, *ctx16 = nullptr, *ffb16 = nullptr,
-             *emb16 = nullptr, *xc16 = nullptr, *tmp16 = nullptr, *xseq16 = nullptr;
-    std::set<std::string> have;
-    std::vector<std::string> required;
-    std::vector<void*> allocs;        // weight allocations
-    std::vector<void*> ws_allocs;     // workspace allocations
-    Packed time0, time2, seed, in_x, in_mfcc, proj_pose, proj_audio, proj_coa, outp;
-    std::vector<Layer> layers;
-    float* pe = nullptr; int pe_rows = 0;
-    float *rope_cos = nullptr, *rope_sin = nullptr; int rope_rows = 0;
-    // workspace (sized for 2*B samples so that CFG runs as one double batch)
-    int B = 0, T = 0, S = 0;
-    long rows_alloc = 0;              // rows of the [2B*S + pad] token buffers
-    bool cond_set = false;
-    float *xa = nullptr, *xb = nullptr, *qkv = nullptr, *ctx = nullptr, *tmp = nullptr, *ffb = nullptr;
-    float *emb_pose = nullptr, *xseq = nullptr, *addend = nullptr;
-    float *seed_cat = nullptr, *temb_in = nullptr, *temb_h = nullptr, *temb = nullptr, *coa = nullptr, *c2 = nullptr;
-    float* x0 = nullptr;              // [2B, J, T]
-    float *xt = nullptr, *xc = nullptr, *x0t = nullptr;   // token-major pose in / compacted last layer / token-major x0
-    int ldo = 0;                      // row stride of x0t = J rounded up to 64
-    float* temb_table = nullptr; int temb_table_rows = 0;
-    float* c2t_table = nullptr;       // V2: W_coa * temb_table rows (valid while c2t_valid)
-    float* c2_seed = nullptr;         // V2: W_coa * seed_cat rows [2B, d]
-    bool c2t_valid = false;
-    bool tables_valid = false;        // temb_table (and c2t_table) hold the rows of tmap_host under the current weights
-    std::vector<int64_t> tmap_host;
-    float *bpd_xt = nullptr, *bpd_z = nullptr, *bpd_part = nullptr;   // gdx_bpd_loop: x_t, Philox noise [B, J, T], chunk sums
-    // graph replay of launch-bound loops (gdx_sample_loop)
-    bool graph_replay = false;        // gdx_set_graph_replay
-    int* gstate = nullptr;            // device {schedule index, executed-step number}
-    hipStream_t gstream = nullptr;    // capture needs a non-default stream (PyTorch's current stream is usually stream 0)
-    hipEvent_t gev_in = nullptr, gev_out = nullptr;
-    hipGraph_t ggraph = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    int64_t* tmap_dev = nullptr;
-    bool prof = false;                // in-situ FFN-1 GEMM timing (gdx_profile_begin / gdx_profile_end)
-    std::vector<hipEvent_t> prof_ev;  // pairs, recorded around each FFN-1 launch while prof is on
-    size_t prof_used = 0;
-    bool keep_taps = false;
-    std::vector<float*> taps;         // [L+1] x [2B*S*d] when keep_taps
-    bool guards = false;              // gdx_set_guards: every workspace allocation carries a canary zone behind it
-    std::vector<std::pair<unsigned char*, size_t>> guard_zones;
-};
 
 static constexpr size_t GUARD_BYTES = 64 * 1024;
 static constexpr int GUARD_BYTE = 0xA5;
@@ -127,37 +27,6 @@ int gdx::dev_alloc(std::vector<void*>& pool, void** p, size_t bytes) {
     hipError_t e = hipMalloc(p, bytes ? bytes : 16);
     if (e != hipSuccess) return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
     pool.push_back(*p);
-    return 0;
-}
-
-int gdx::pack_f16_into(_Float16* dst, const float* src, int n, int src_ld, int col0, int k, int npad, int kpad, hipStream_t s,
-                       bool bf) {
-    const long total = (long)npad * kpad;
-    hipLaunchKernelGGL(bf ? pack_weight_bf16_kernel : pack_weight_f16_kernel, dim3((total + 255) / 256), dim3(256), 0, s, src,
-                       src_ld, col0, n, k, dst, npad, kpad);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int pack(gdx_model* h, Packed& P, const float* src, int n, int src_ld, int col0, int k, hipStream_t s) {
-    P.n = n; P.k = k; P.npad = round_up(n, 128); P.kpad = round_up(k, 32);
-    if (!P.w && dev_alloc(h->allocs, (void**)&P.w, sizeof(float) * P.npad * (size_t)P.kpad)) return -1;
-    const long total = (long)P.npad * P.kpad;
-    hipLaunchKernelGGL(pack_weight_kernel, dim3((total + 255) / 256), dim3(256), 0, s, src, src_ld, col0, n, k, P.w,
-                       P.npad, P.kpad);
-    HIPCHK(hipGetLastError());
-    if (h->f16) {
-        P.npad16 = round_up(n, 256); P.kpad16 = round_up(k, 64);
-        if (!P.w16 && dev_alloc(h->allocs, (void**)&P.w16, 2 * (size_t)P.npad16 * P.kpad16)) return -1;
-        if (pack_f16_into(P.w16, src, n, src_ld, col0, k, P.npad16, P.kpad16, s, h->bf16)) return -1;
-    }
-    return 0;
-}
-
-static int pack_vec(gdx_model* h, float** dst, const float* src, int n, int npad, hipStream_t s) {
-    if (!*dst && dev_alloc(h->allocs, (void**)dst, sizeof(float) * npad)) return -1;
-    HIPCHK(hipMemsetAsync(*dst, 0, sizeof(float) * npad, s));
-    HIPCHK(hipMemcpyAsync(*dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -195,22 +64,7 @@ extern "C" int gdx_create(const gdx_config_t* cfg, gdx_handle_t* out) {
     h->stream32 = h->bf16;                                        // A/B record: profiles/r03a_bf16_stream32_ab.txt
     h->d = cfg->latent_dim; h->J = cfg->njoints; h->ff = cfg->ff_size; h->L = cfg->num_layers; h->H = cfg->num_heads;
     h->layers.resize(h->L);
-    auto& r = h->required;
-    for (const char* n : {"embed_timestep.time_embed.0.weight", "embed_timestep.time_embed.0.bias",
-                          "embed_timestep.time_embed.2.weight", "embed_timestep.time_embed.2.bias",
-                          "seed_pose_encoder.seed_embed.weight", "seed_pose_encoder.seed_embed.bias",
-                          "input_process.poseEmbedding.weight", "input_process.poseEmbedding.bias",
-                          "output_process.poseFinal.weight", "output_process.poseFinal.bias", "sequence_pos_encoder.pe"})
-        r.push_back(n);
-    if (cfg->arch == GDX_ARCH_MDM)
-        for (const char* n : {"project_to_lat.weight", "project_to_lat.bias", "rope.cos", "rope.sin"}) r.push_back(n);
-    for (int l = 0; l < h->L; ++l) {
-        const std::string p = "seqTransEncoder.layers." + std::to_string(l) + ".";
-        for (const char* n : {"self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight",
-                              "self_attn.out_proj.bias", "linear1.weight", "linear1.bias", "linear2.weight",
-                              "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"})
-            r.push_back(p + n);
-    }
+    describe_weights(h);
     *out = h;
     return 0;
 }
@@ -233,331 +87,6 @@ extern "C" int gdx_destroy(gdx_handle_t h) {
     if (h->gstream) (void)hipStreamDestroy(h->gstream);
     if (h->gstate) (void)hipFree(h->gstate);
     delete h;
-    return 0;
-}
-
-static bool shape_is(const int64_t* shape, int ndim, std::initializer_list<int64_t> want) {
-    if (ndim != (int)want.size()) return false;
-    int i = 0;
-    for (int64_t w : want)
-        if (shape[i++] != w) return false;
-    return true;
-}
-
-extern "C" int gdx_set_weight(gdx_handle_t h, const char* name_c, const float* p, const int64_t* shape, int32_t ndim,
-                              void* stream) {
-    if (!h || !name_c || !p || !shape) return fail("gdx_set_weight: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const std::string name(name_c);
-    const int d = h->d, J = h->J, ff = h->ff, mf = h->cfg.mfcc_dim;
-    auto bad = [&]() { return fail("gdx_set_weight: unexpected shape for " + name); };
-    int rc = 0;
-    if (name == "embed_timestep.time_embed.0.weight") {
-        if (!shape_is(shape, ndim, {d, d})) return bad();
-        rc = pack(h, h->time0, p, d, d, 0, d, s);
-    } else if (name == "embed_timestep.time_embed.0.bias") {
-        if (!shape_is(shape, ndim, {d})) return bad();
-        rc = pack_vec(h, &h->time0.bias, p, d, round_up(d, 128), s);
-    } else if (name == "embed_timestep.time_embed.2.weight") {
-        if (!shape_is(shape, ndim, {d, d})) return bad();
-        rc = pack(h, h->time2, p, d, d, 0, d, s);
-    } else if (name == "embed_timestep.time_embed.2.bias") {
-        if (!shape_is(shape, ndim, {d})) return bad();
-        rc = pack_vec(h, &h->time2.bias, p, d, round_up(d, 128), s);
-    } else if (name == "seed_pose_encoder.seed_embed.weight") {
-        const int k = J * h->cfg.seed_poses;
-        if (!shape_is(shape, ndim, {d, k})) return bad();
-        rc = pack(h, h->seed, p, d, k, 0, k, s);
-    } else if (name == "seed_pose_encoder.seed_embed.bias") {
-        if (!shape_is(shape, ndim, {d})) return bad();
-        rc = pack_vec(h, &h->seed.bias, p, d, round_up(d, 128), s);
-    } else if (name == "input_process.poseEmbedding.weight") {
-        if (h->cfg.arch == GDX_ARCH_MDM) {
-            if (!shape_is(shape, ndim, {d, J})) return bad();
-            rc = pack(h, h->in_x, p, d, J, 0, J, s);
-        } else {
-            if (!shape_is(shape, ndim, {d, J + mf})) return bad();
-            rc = pack(h, h->in_x, p, d, J + mf, 0, J, s);
-            if (!rc) rc = pack(h, h->in_mfcc, p, d, J + mf, J, mf, s);
-        }
-    } else if (name == "input_process.poseEmbedding.bias") {
-        if (!shape_is(shape, ndim, {d})) return bad();
-        rc = pack_vec(h, &h->in_x.bias, p, d, round_up(d, 128), s);
-    } else if (name == "project_to_lat.weight" && h->cfg.arch == GDX_ARCH_MDM) {
-        if (!shape_is(shape, ndim, {d, 2 * d + mf})) return bad();
-        rc = pack(h, h->proj_pose, p, d, 2 * d + mf, 0, d, s);
-        if (!rc) rc = pack(h, h->proj_audio, p, d, 2 * d + mf, d, mf, s);
-        if (!rc) rc = pack(h, h->proj_coa, p, d, 2 * d + mf, d + mf, d, s);
-    } else if (name == "project_to_lat.bias" && h->cfg.arch == GDX_ARCH_MDM) {
-        if (!shape_is(shape, ndim, {d})) return bad();
-        rc = pack_vec(h, &h->proj_pose.bias, p, d, round_up(d, 128), s);
-    } else if (name == "output_process.poseFinal.weight") {
-        if (!shape_is(shape, ndim, {J, d})) return bad();
-        rc = pack(h, h->outp, p, J, d, 0, d, s);
-    } else if (name == "output_process.poseFinal.bias") {
-        if (!shape_is(shape, ndim, {J})) return bad();
-        rc = pack_vec(h, &h->outp.bias, p, J, round_up(J, 128), s);
-    } else if (name == "sequence_pos_encoder.pe") {
-        if (ndim != 3 || shape[1] != 1 || shape[2] != d) return bad();
-        h->pe_rows = (int)shape[0];
-        h->pe = nullptr;
-        rc = pack_vec(h, &h->pe, p, h->pe_rows * d, h->pe_rows * d, s);
-    } else if ((name == "rope.cos" || name == "rope.sin") && h->cfg.arch == GDX_ARCH_MDM) {
-        const int half = d / h->cfg.cl_head / 2;
-        if (ndim != 2 || shape[1] != half) return bad();
-        float** dst = name == "rope.cos" ? &h->rope_cos : &h->rope_sin;
-        *dst = nullptr;
-        h->rope_rows = (int)shape[0];
-        rc = pack_vec(h, dst, p, h->rope_rows * half, h->rope_rows * half, s);
-    } else if (name.rfind("seqTransEncoder.layers.", 0) == 0) {
-        const size_t p0 = strlen("seqTransEncoder.layers.");
-        const size_t dot = name.find('.', p0);
-        if (dot == std::string::npos) return fail("gdx_set_weight: unexpected key " + name);
-        const int l = atoi(name.substr(p0, dot - p0).c_str());
-        if (l < 0 || l >= h->L) return fail("gdx_set_weight: unexpected key " + name);
-        Layer& ly = h->layers[l];
-        const std::string sub = name.substr(dot + 1);
-        if (sub == "self_attn.in_proj_weight") {
-            if (!shape_is(shape, ndim, {3 * d, d})) return bad();
-            rc = pack(h, ly.qkv, p, 3 * d, d, 0, d, s);
-        } else if (sub == "self_attn.in_proj_bias") {
-            if (!shape_is(shape, ndim, {3 * d})) return bad();
-            rc = pack_vec(h, &ly.qkv.bias, p, 3 * d, round_up(3 * d, 128), s);
-        } else if (sub == "self_attn.out_proj.weight") {
-            if (!shape_is(shape, ndim, {d, d})) return bad();
-            rc = pack(h, ly.out, p, d, d, 0, d, s);
-        } else if (sub == "self_attn.out_proj.bias") {
-            if (!shape_is(shape, ndim, {d})) return bad();
-            rc = pack_vec(h, &ly.out.bias, p, d, round_up(d, 128), s);
-        } else if (sub == "linear1.weight") {
-            if (!shape_is(shape, ndim, {ff, d})) return bad();
-            rc = pack(h, ly.ff1, p, ff, d, 0, d, s);
-        } else if (sub == "linear1.bias") {
-            if (!shape_is(shape, ndim, {ff})) return bad();
-            rc = pack_vec(h, &ly.ff1.bias, p, ff, round_up(ff, 128), s);
-        } else if (sub == "linear2.weight") {
-            if (!shape_is(shape, ndim, {d, ff})) return bad();
-            rc = pack(h, ly.ff2, p, d, ff, 0, ff, s);
-        } else if (sub == "linear2.bias") {
-            if (!shape_is(shape, ndim, {d})) return bad();
-            rc = pack_vec(h, &ly.ff2.bias, p, d, round_up(d, 128), s);
-        } else if (sub == "norm1.weight" || sub == "norm1.bias" || sub == "norm2.weight" || sub == "norm2.bias") {
-            if (!shape_is(shape, ndim, {d})) return bad();
-            float** dst = sub == "norm1.weight" ? &ly.g1 : sub == "norm1.bias" ? &ly.b1 : sub == "norm2.weight" ? &ly.g2 : &ly.b2;
-            rc = pack_vec(h, dst, p, d, d, s);
-        } else {
-            return fail("gdx_set_weight: unexpected key " + name);
-        }
-    } else {
-        return fail("gdx_set_weight: unexpected key " + name);   // load_model_wo_clip asserts no unexpected keys
-    }
-    if (rc) return rc;
-    h->have.insert(name);
-    h->cond_set = false;
-    h->c2t_valid = false;
-    h->tables_valid = false;
-    return 0;
-}
-
-extern "C" int gdx_weights_ready(gdx_handle_t h) {
-    if (!h) return fail("gdx_weights_ready: null handle");
-    std::string missing;
-    for (const auto& n : h->required)
-        if (!h->have.count(n)) missing += (missing.empty() ? "" : ", ") + n;
-    if (!missing.empty()) return fail("missing weights: " + missing);
-    return 0;
-}
-
-// ---- packed-weight image (the weight pre-packing cache) ----------------------------------------------
-// Everything gdx_set_weight builds -- the zero-padded K-contiguous fp32 panels, their fp16 twins in the fp16 mode, padded
-// bias vectors, LayerNorm vectors, the positional / rotary tables -- as ONE host blob: a header (magic, the gdx_config_t
-// it was built for, record count) and one {id, dims, byte count, bytes} record per device buffer in a fixed walk order.
-// A blob only loads into a handle created with the same configuration; its records are checked against the sizes the
-// handle computes itself, so a stale or foreign file is rejected instead of producing a wrong model.
-namespace {
-struct PackRec { int32_t id, n, k, npad, kpad, npad16, kpad16, pad; int64_t bytes; };
-struct PackHdr { char magic[8]; gdx_config_t cfg; int32_t nrec, pad; };
-const char PACK_MAGIC[8] = {'G', 'D', 'X', 'P', 'A', 'C', 'K', '3'};
-// 64-bit FNV-1a over the 8-byte words of the payload (records + buffers; everything behind the extras block, whose length is a
-// multiple of 8): the image's integrity check.  It lives in PackHdr::pad (low half) and the fourth extras word (high half).
-static uint64_t pack_hash(const char* p, const char* end) {
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (; p + 8 <= end; p += 8) {
-        uint64_t w;
-        memcpy(&w, p, 8);
-        h = (h ^ w) * 0x100000001b3ull;
-    }
-    for (; p < end; ++p) h = (h ^ (unsigned char)*p) * 0x100000001b3ull;
-    return h;
-}
-struct PackBuf { void** ptr; size_t bytes; PackRec rec; };
-}  // namespace
-
-// the walk: every device weight buffer of the handle with the size it has (export) or must have (import; dims from the config)
-static void pack_walk(gdx_model* h, std::vector<PackBuf>& out) {
-    const int d = h->d, J = h->J, ff = h->ff, mf = h->cfg.mfcc_dim;
-    int id = 0;
-    auto linear = [&](Packed& P, int n, int k, bool bias) {
-        PackRec r{};
-        r.n = n; r.k = k; r.npad = round_up(n, 128); r.kpad = round_up(k, 32);
-        r.npad16 = h->f16 ? round_up(n, 256) : 0; r.kpad16 = h->f16 ? round_up(k, 64) : 0;
-        r.id = id++; r.bytes = (int64_t)sizeof(float) * r.npad * r.kpad;
-        out.push_back({(void**)&P.w, (size_t)r.bytes, r});
-        r.id = id++; r.bytes = bias ? (int64_t)sizeof(float) * round_up(n, 128) : 0;
-        out.push_back({(void**)&P.bias, (size_t)r.bytes, r});
-        r.id = id++; r.bytes = h->f16 ? (int64_t)2 * r.npad16 * r.kpad16 : 0;
-        out.push_back({(void**)&P.w16, (size_t)r.bytes, r});
-    };
-    auto vec = [&](float** p, long n) {
-        PackRec r{};
-        r.id = id++; r.n = (int32_t)n; r.bytes = (int64_t)sizeof(float) * n;
-        out.push_back({(void**)p, (size_t)r.bytes, r});
-    };
-    const bool v2 = h->cfg.arch == GDX_ARCH_MDM;
-    linear(h->time0, d, d, true);
-    linear(h->time2, d, d, true);
-    linear(h->seed, d, J * h->cfg.seed_poses, true);
-    linear(h->in_x, d, J, true);
-    if (!v2) linear(h->in_mfcc, d, mf, false);
-    if (v2) {
-        linear(h->proj_pose, d, d, true);
-        linear(h->proj_audio, d, mf, false);
-        linear(h->proj_coa, d, d, false);
-    }
-    linear(h->outp, J, d, true);
-    for (Layer& ly : h->layers) {
-        linear(ly.qkv, 3 * d, d, true);
-        linear(ly.out, d, d, true);
-        linear(ly.ff1, ff, d, true);
-        linear(ly.ff2, d, ff, true);
-        vec(&ly.g1, d); vec(&ly.b1, d); vec(&ly.g2, d); vec(&ly.b2, d);
-    }
-    vec(&h->pe, (long)h->pe_rows * d);
-    if (v2) {
-        const int half = d / h->cfg.cl_head / 2;
-        vec(&h->rope_cos, (long)h->rope_rows * half);
-        vec(&h->rope_sin, (long)h->rope_rows * half);
-    }
-}
-
-extern "C" int gdx_packed_bytes(gdx_handle_t h, int64_t* bytes) {
-    if (!h || !bytes) return fail("gdx_packed_bytes: null argument");
-    if (gdx_weights_ready(h)) return -1;
-    std::vector<PackBuf> bufs;
-    pack_walk(h, bufs);
-    int64_t total = sizeof(PackHdr) + 3 * sizeof(int32_t) + sizeof(int32_t);     // header + pe_rows, rope_rows, f16, pad
-    for (const PackBuf& b : bufs) total += sizeof(PackRec) + (int64_t)((b.bytes + 15) / 16 * 16);
-    *bytes = total;
-    return 0;
-}
-
-extern "C" int gdx_export_packed(gdx_handle_t h, void* host, int64_t bytes, void* stream) {
-    if (!h || !host) return fail("gdx_export_packed: null argument");
-    int64_t need = 0;
-    if (gdx_packed_bytes(h, &need)) return -1;
-    if (bytes != need) return fail("gdx_export_packed: buffer size does not match gdx_packed_bytes");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<PackBuf> bufs;
-    pack_walk(h, bufs);
-    char* p = (char*)host;
-    PackHdr hd{};
-    memcpy(hd.magic, PACK_MAGIC, 8);
-    hd.cfg = h->cfg; hd.nrec = (int32_t)bufs.size();
-    char* const hd_at = p; p += sizeof(hd);
-    int32_t extra[4] = {h->pe_rows, h->rope_rows, h->cfg.compute_dtype, 0};
-    char* const extra_at = p; p += sizeof(extra);
-    char* const payload = p;
-    memset(payload, 0, (size_t)(bytes - (payload - (char*)host)));  // the 16-byte alignment gaps are part of the hashed payload
-    for (const PackBuf& b : bufs) {
-        memcpy(p, &b.rec, sizeof(PackRec)); p += sizeof(PackRec);
-        if (b.bytes) {
-            if (!*b.ptr) return fail("gdx_export_packed: a weight buffer is missing");
-            HIPCHK(hipMemcpyAsync(p, *b.ptr, b.bytes, hipMemcpyDeviceToHost, s));
-        }
-        p += (b.bytes + 15) / 16 * 16;
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    const uint64_t hash = pack_hash(payload, (char*)host + bytes);
-    hd.pad = (int32_t)(uint32_t)hash;
-    extra[3] = (int32_t)(uint32_t)(hash >> 32);
-    memcpy(hd_at, &hd, sizeof(hd));
-    memcpy(extra_at, extra, sizeof(extra));
-    return 0;
-}
-
-extern "C" int gdx_import_packed(gdx_handle_t h, const void* host, int64_t bytes, void* stream) {
-    if (!h || !host) return fail("gdx_import_packed: null argument");
-    if (bytes < (int64_t)(sizeof(PackHdr) + 16)) return fail("gdx_import_packed: blob too small");
-    const char* p = (const char*)host;
-    const char* end = p + bytes;
-    PackHdr hd;
-    memcpy(&hd, p, sizeof(hd)); p += sizeof(hd);
-    if (memcmp(hd.magic, PACK_MAGIC, 8)) return fail("gdx_import_packed: not a packed-weight image (bad magic)");
-    if (memcmp(&hd.cfg, &h->cfg, sizeof(gdx_config_t))) return fail("gdx_import_packed: image was built for another configuration");
-    int32_t extra[4];
-    memcpy(extra, p, sizeof(extra)); p += sizeof(extra);
-    const uint64_t stored = (uint64_t)(uint32_t)hd.pad | ((uint64_t)(uint32_t)extra[3] << 32);
-    if (extra[2] != h->cfg.compute_dtype) return fail("gdx_import_packed: image was built for another compute dtype");
-    const int rope_need = h->cfg.arch == GDX_ARCH_MDM ? 1 : 0;
-    if (extra[0] <= 0 || extra[0] > (1 << 20) || extra[1] < rope_need || extra[1] > (1 << 20))
-        return fail("gdx_import_packed: implausible table sizes");
-    const int old_pe = h->pe_rows, old_rope = h->rope_rows;
-    h->pe_rows = extra[0]; h->rope_rows = extra[1];               // the walk sizes the tables from these
-    std::vector<PackBuf> bufs;
-    pack_walk(h, bufs);
-    // validate the whole blob before touching the handle
-    const char* why = nullptr;
-    const char* q = p;
-    if (hd.nrec != (int32_t)bufs.size()) why = "gdx_import_packed: record count mismatch";
-    for (size_t i = 0; !why && i < bufs.size(); ++i) {
-        const PackBuf& b = bufs[i];
-        if (q + sizeof(PackRec) > end) { why = "gdx_import_packed: truncated image"; break; }
-        PackRec r;
-        memcpy(&r, q, sizeof(r)); q += sizeof(PackRec);
-        if (memcmp(&r, &b.rec, sizeof(PackRec))) { why = "gdx_import_packed: record does not match this configuration"; break; }
-        q += (b.bytes + 15) / 16 * 16;
-        if (q > end) why = "gdx_import_packed: truncated image";
-    }
-    if (!why && q != end) why = "gdx_import_packed: trailing bytes";
-    if (!why && pack_hash(p, end) != stored) why = "gdx_import_packed: payload checksum mismatch (corrupted image)";
-    if (why) {
-        h->pe_rows = old_pe; h->rope_rows = old_rope;
-        return fail(why);
-    }
-    // the tables may change size with the image: let them be re-allocated
-    if (h->pe_rows != old_pe) h->pe = nullptr;
-    if (h->rope_rows != old_rope) { h->rope_cos = nullptr; h->rope_sin = nullptr; }
-    hipStream_t s = (hipStream_t)stream;
-    // from here on the handle's weights are being overwritten: it is "not ready" until the last byte has arrived (a failed
-    // allocation or copy must not leave a half-uploaded model that gdx_weights_ready accepts)
-    h->have.clear();
-    h->cond_set = false;
-    h->c2t_valid = false;
-    h->tables_valid = false;
-    for (PackBuf& b : bufs) {
-        p += sizeof(PackRec);
-        if (b.bytes) {
-            if (!*b.ptr && dev_alloc(h->allocs, b.ptr, b.bytes)) return -1;
-            HIPCHK(hipMemcpyAsync(*b.ptr, p, b.bytes, hipMemcpyHostToDevice, s));
-        }
-        p += (b.bytes + 15) / 16 * 16;
-    }
-    HIPCHK(hipStreamSynchronize(s));                             // the caller may free the host blob on return
-    // dims of the Packed structs (pack() sets them on the gdx_set_weight path)
-    auto dims = [&](Packed& P, int n, int k) {
-        P.n = n; P.k = k; P.npad = round_up(n, 128); P.kpad = round_up(k, 32);
-        if (h->f16) { P.npad16 = round_up(n, 256); P.kpad16 = round_up(k, 64); }
-    };
-    const int d = h->d, J = h->J, ff = h->ff, mf = h->cfg.mfcc_dim;
-    dims(h->time0, d, d); dims(h->time2, d, d); dims(h->seed, d, J * h->cfg.seed_poses); dims(h->in_x, d, J);
-    if (h->cfg.arch == GDX_ARCH_MDM) { dims(h->proj_pose, d, d); dims(h->proj_audio, d, mf); dims(h->proj_coa, d, d); }
-    else dims(h->in_mfcc, d, mf);
-    dims(h->outp, J, d);
-    for (Layer& ly : h->layers) { dims(ly.qkv, 3 * d, d); dims(ly.out, d, d); dims(ly.ff1, ff, d); dims(ly.ff2, d, ff); }
-    for (const auto& n : h->required) h->have.insert(n);
-    h->cond_set = false;
-    h->c2t_valid = false;
-    h->tables_valid = false;
     return 0;
 }
 
@@ -993,9 +522,6 @@ static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timeste
     h->tables_valid = true;
     return 0;
 }
-
-int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
-                uint32_t step, float* z_out, float* xt_out, void* stream);                                      // sampler.hip
 
 // calc_bpd_loop (gaussian_diffusion.py:1537-1592): per step q_sample -> denoiser -> fused bound terms, through the SAME forward
 // entry (pose-layout x_t, forward_core) the step-wise protocol reaches via gdx_forward, so both give the same bits.

@@ -1,8 +1,9 @@
-// Host-side helpers shared by api.hip (the model handle; defines the functions declared here) and testapi.hip (the handle-free
-// test / bench entry points).
+// Host side shared by api.hip (the model handle, the forwards and the loops; defines the helpers declared here), weights.hip
+// (what the handle's weights are and how they get there) and testapi.hip (the handle-free test / bench entry points).
 #pragma once
 #include "gdx_internal.h"
 
+#include <set>
 #include <string>
 #include <vector>
 
@@ -64,4 +65,96 @@ int time_launches(int warm, int iters, hipStream_t s, float* avg_us, F launch) {
     return rc;
 }
 
+// ---- the model handle ---------------------------------------------------------------------------------------------------
+struct Packed {          // a Linear weight [n][k] packed to [npad][kpad] (+ bias [npad])
+    float* w = nullptr;
+    float* bias = nullptr;
+    int n = 0, k = 0, npad = 0, kpad = 0;
+    _Float16* w16 = nullptr;             // fp16 mode: [npad16][kpad16], rows padded to 256, K to 64 (gemmh.hip)
+    int npad16 = 0, kpad16 = 0;          // 0 in the fp32 mode
+    bool has_bias = false;               // a state-dict key supplies `bias`
+    // n .. has_bias depend on the configuration only: describe_weights sets them, nothing else writes them
+};
+
+struct Layer {
+    Packed qkv, out, ff1, ff2;
+    float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
+};
+
+// One state-dict key of the handle's configuration: the shape it must have and the device buffers it becomes.  The handle's
+// table of these (weights.hip: describe_weights) is the only list of the model's tensors: gdx_set_weight, the
+// "missing weights" report and the packed image are all read off it.
+struct WeightSlice { Packed* P; int col0; };   // P->w (and w16) = rows [0, P->n) x columns [col0, col0 + P->k) of the tensor
+struct WeightSpec {
+    enum Kind { LINEAR,    // a Linear weight: one Packed panel per slice
+                BIAS,      // -> P->bias, zero padded to P->npad
+                VECTOR,    // LayerNorm gamma / beta -> *vec, unpadded
+                TABLE };   // positional / rotary table -> *vec; shape[0] is free and becomes the handle's row count
+    Kind kind;
+    std::string key;
+    std::vector<int64_t> shape;
+    std::vector<WeightSlice> slices;   // LINEAR
+    Packed* P = nullptr;               // BIAS
+    float** vec = nullptr;             // VECTOR, TABLE
+    bool rotary = false;               // TABLE: counted by rope_rows (else pe_rows)
+    int group = 0;                     // place in the "missing weights" report (the table itself is in packed-image order)
+};
+
+}  // namespace gdx
+
+struct gdx_model {
+    gdx_config_t cfg;
+    int d, J, ff, L, H;
+    bool f16 = false;                 // reduced-precision mode (GDX_DTYPE_F16 or _BF16): 16-bit MFMA operands, fp32 accumulate
+    bool bf16 = false;                // ... with bf16 elements (the gdx::b16 kernels)
+    bool stream32 = false;            // 16-bit modes: the residual stream (x + sublayer(x), LayerNorm in / out) stays fp32 and
+                                      // only the GEMM / attention operands are 16-bit copies (default for bf16, see forward_core_f16)
+    _Float16 *xt16 = nullptr, *xa16 = nullptr, *xb16 = nullptr, *qkv16 = nullptr, *ctx16 = nullptr, *ffb16 = nullptr,
+             *emb16 = nullptr, *xc16 = nullptr, *tmp16 = nullptr, *xseq16 = nullptr;
+    std::vector<gdx::WeightSpec> weights;   // describe_weights; points into this handle
+    std::set<std::string> have;
+    std::vector<std::string> required;
+    std::vector<void*> allocs;        // weight allocations
+    std::vector<void*> ws_allocs;     // workspace allocations
+    gdx::Packed time0, time2, seed, in_x, in_mfcc, proj_pose, proj_audio, proj_coa, outp;
+    std::vector<gdx::Layer> layers;
+    float* pe = nullptr; int pe_rows = 0;
+    float *rope_cos = nullptr, *rope_sin = nullptr; int rope_rows = 0;
+    // workspace (sized for 2*B samples so that CFG runs as one double batch)
+    int B = 0, T = 0, S = 0;
+    long rows_alloc = 0;              // rows of the [2B*S + pad] token buffers
+    bool cond_set = false;
+    float *xa = nullptr, *xb = nullptr, *qkv = nullptr, *ctx = nullptr, *tmp = nullptr, *ffb = nullptr;
+    float *emb_pose = nullptr, *xseq = nullptr, *addend = nullptr;
+    float *seed_cat = nullptr, *temb_in = nullptr, *temb_h = nullptr, *temb = nullptr, *coa = nullptr, *c2 = nullptr;
+    float* x0 = nullptr;              // [2B, J, T]
+    float *xt = nullptr, *xc = nullptr, *x0t = nullptr;   // token-major pose in / compacted last layer / token-major x0
+    int ldo = 0;                      // row stride of x0t = J rounded up to 64
+    float* temb_table = nullptr; int temb_table_rows = 0;
+    float* c2t_table = nullptr;       // V2: W_coa * temb_table rows (valid while c2t_valid)
+    float* c2_seed = nullptr;         // V2: W_coa * seed_cat rows [2B, d]
+    bool c2t_valid = false;
+    bool tables_valid = false;        // temb_table (and c2t_table) hold the rows of tmap_host under the current weights
+    std::vector<int64_t> tmap_host;
+    float *bpd_xt = nullptr, *bpd_z = nullptr, *bpd_part = nullptr;   // gdx_bpd_loop: x_t, Philox noise [B, J, T], chunk sums
+    // graph replay of launch-bound loops (gdx_sample_loop)
+    bool graph_replay = false;        // gdx_set_graph_replay
+    int* gstate = nullptr;            // device {schedule index, executed-step number}
+    hipStream_t gstream = nullptr;    // capture needs a non-default stream (PyTorch's current stream is usually stream 0)
+    hipEvent_t gev_in = nullptr, gev_out = nullptr;
+    hipGraph_t ggraph = nullptr;
+    hipGraphExec_t gexec = nullptr;
+    int64_t* tmap_dev = nullptr;
+    bool prof = false;                // in-situ FFN-1 GEMM timing (gdx_profile_begin / gdx_profile_end)
+    std::vector<hipEvent_t> prof_ev;  // pairs, recorded around each FFN-1 launch while prof is on
+    size_t prof_used = 0;
+    bool keep_taps = false;
+    std::vector<float*> taps;         // [L+1] x [2B*S*d] when keep_taps
+    bool guards = false;              // gdx_set_guards: every workspace allocation carries a canary zone behind it
+    std::vector<std::pair<unsigned char*, size_t>> guard_zones;
+};
+
+namespace gdx {
+// weights.hip: fills h->weights, the dimensions of every Packed they name and h->required from h->cfg (gdx_create)
+void describe_weights(gdx_model* h);
 }  // namespace gdx

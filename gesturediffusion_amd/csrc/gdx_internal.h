@@ -181,3 +181,16 @@ hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, 
                             hipStream_t s);
 
 }  // namespace gdx
+
+// the loops' (api.hip) private entries into sampler.hip; each returns 0, or -1 with the error recorded
+// the update of a captured step: schedule index / step number read from `state` (UpdateDev::state)
+int gdx_sampler_update_state_(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
+// one step of the token-major fast path of gdx_sample_loop (update_tm_kernel)
+int gdx_sampler_update_tm_(int kind, int B, int J, int T, int ldx, int ldo, const float* coef, int step_index, float* xt,
+                           const float* x0t, const float* scale, int const_noise, uint64_t seed, uint64_t sample_offset,
+                           uint32_t rng_step, int clip, float* out_pose, void* xt16, int half_dtype, void* stream, const float* noise);
+// gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
+int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
+                uint32_t step, float* z_out, float* xt_out, void* stream);
+// records the text of gdx_last_error and returns -1 (api.hip), for the files that do not include gdx_host.h
+extern "C" int gdx_set_error_(const char* msg);

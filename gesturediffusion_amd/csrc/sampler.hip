@@ -587,11 +587,6 @@ hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, 
     return hipGetLastError();
 }
 
-}  // namespace gdx
-
-extern "C" int gdx_set_error_(const char* msg);   // api.hip
-
-namespace gdx {
 __global__ void set_state_kernel(int* st, int idx, int k) { st[0] = idx; st[1] = k; }
 __global__ void advance_state_kernel(int* st) { st[0] -= 1; st[1] += 1; }
 

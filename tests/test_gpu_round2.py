@@ -603,6 +603,68 @@ def test_packed_image_is_rejected_by_another_configuration():
     assert torch.equal(_forward(d, cfg), _forward(a, cfg))
 
 
+def test_set_weight_refusals_and_the_missing_weights_report():
+    """The texts of gdx_set_weight's refusals and of gdx_weights_ready's report, which lists the absent tensors in a fixed
+    order: the base model, the positional table, what the `mdm` topology adds, then the layers."""
+    import re
+    from gesturediffusion_amd import _lib
+    from gesturediffusion_amd.engine import Engine
+    d, J, ff, L, P, mf, half = 128, 16, 256, 2, 10, 26, 128 // 8 // 2
+    shapes = {"embed_timestep.time_embed.0.weight": (d, d), "embed_timestep.time_embed.0.bias": (d,),
+              "embed_timestep.time_embed.2.weight": (d, d), "embed_timestep.time_embed.2.bias": (d,),
+              "seed_pose_encoder.seed_embed.weight": (d, J * P), "seed_pose_encoder.seed_embed.bias": (d,),
+              "input_process.poseEmbedding.weight": (d, J), "input_process.poseEmbedding.bias": (d,),
+              "output_process.poseFinal.weight": (J, d), "output_process.poseFinal.bias": (J,),
+              "sequence_pos_encoder.pe": (50, 1, d),
+              "project_to_lat.weight": (d, 2 * d + mf), "project_to_lat.bias": (d,), "rope.cos": (40, half), "rope.sin": (40, half)}
+    for l in range(L):
+        p = f"seqTransEncoder.layers.{l}."
+        shapes.update({p + "self_attn.in_proj_weight": (3 * d, d), p + "self_attn.in_proj_bias": (3 * d,),
+                       p + "self_attn.out_proj.weight": (d, d), p + "self_attn.out_proj.bias": (d,),
+                       p + "linear1.weight": (ff, d), p + "linear1.bias": (ff,), p + "linear2.weight": (d, ff),
+                       p + "linear2.bias": (d,), p + "norm1.weight": (d,), p + "norm1.bias": (d,), p + "norm2.weight": (d,),
+                       p + "norm2.bias": (d,)})
+
+    def engine(arch):
+        return Engine(arch, njoints=J, latent_dim=d, ff_size=ff, num_layers=L, num_heads=4, seed_poses=P)
+
+    def refused(eng, name, shape, text):
+        with pytest.raises(_lib.GdxError, match="^" + re.escape(text) + "$"):
+            eng.set_weight(name, torch.zeros(*shape, device=dev()))
+
+    def ready(eng):
+        _lib.check(eng.lib.gdx_weights_ready(eng.handle), eng.lib)
+
+    new = engine(_lib.GDX_ARCH_MDM)
+    with pytest.raises(_lib.GdxError, match="^" + re.escape("missing weights: " + ", ".join(shapes)) + "$"):
+        ready(new)                                                   # nothing set: every name, in the report's order
+    refused(new, "seqTransEncoder.layers.0.linear1.weight", (d, ff), "gdx_set_weight: unexpected shape for seqTransEncoder.layers.0.linear1.weight")
+    refused(new, "output_process.poseFinal.bias", (d,), "gdx_set_weight: unexpected shape for output_process.poseFinal.bias")
+    refused(new, "sequence_pos_encoder.pe", (50, 2, d), "gdx_set_weight: unexpected shape for sequence_pos_encoder.pe")
+    refused(new, "rope.sin", (40, half + 1), "gdx_set_weight: unexpected shape for rope.sin")
+    refused(new, "input_process.poseEmbedding.weight", (d, J + mf), "gdx_set_weight: unexpected shape for input_process.poseEmbedding.weight")
+    refused(new, f"seqTransEncoder.layers.{L}.linear1.weight", (ff, d), f"gdx_set_weight: unexpected key seqTransEncoder.layers.{L}.linear1.weight")
+    refused(new, "seqTransEncoder.layers.0.linear3.weight", (ff, d), "gdx_set_weight: unexpected key seqTransEncoder.layers.0.linear3.weight")
+    refused(new, "embed_text.weight", (d, d), "gdx_set_weight: unexpected key embed_text.weight")
+    absent = ("output_process.poseFinal.bias", f"seqTransEncoder.layers.{L - 1}.norm2.weight")
+    for name, shape in shapes.items():
+        if name not in absent:
+            new.set_weight(name, torch.zeros(*shape, device=dev()))
+    with pytest.raises(_lib.GdxError, match="^" + re.escape("missing weights: " + ", ".join(absent)) + "$"):
+        ready(new)
+    for name in absent:
+        new.set_weight(name, torch.zeros(*shapes[name], device=dev()))
+    ready(new)
+
+    old = engine(_lib.GDX_ARCH_MDM_OLD)                              # no project_to_lat, no rotary tables; pose | mfcc input
+    for name in ("project_to_lat.weight", "project_to_lat.bias", "rope.cos", "rope.sin"):
+        refused(old, name, shapes[name], "gdx_set_weight: unexpected key " + name)
+    refused(old, "input_process.poseEmbedding.weight", (d, J), "gdx_set_weight: unexpected shape for input_process.poseEmbedding.weight")
+    only_old = [n for n in shapes if not n.startswith(("project_to_lat.", "rope."))]
+    with pytest.raises(_lib.GdxError, match="^" + re.escape("missing weights: " + ", ".join(only_old)) + "$"):
+        ready(old)
+
+
 def test_checkpoint_through_the_packed_cache(tmp_path):
     """`sample.generate --model_path ... --packed_cache DIR` twice: the first run reads the checkpoint and writes the image,
     the second uploads the image (the checkpoint file is not even opened for unpickling) and writes the same samples; a

@@ -5,8 +5,9 @@
 
 Every kernel file of csrc/ is compiled to device-only assembly with the Makefile's flags (the half files also with -DGDX_BF16,
 sampler.hip with -ffp-contract=off).  Per kernel the instruction stream (comments dropped) and the .vgpr_count / .sgpr_count /
-LDS / scratch / kernarg sizes of the metadata are compared; kernels are matched by symbol, with the two leading template
-arguments that older trees gave gemm_kernel removed.  Prints one line per difference and a summary line; exit status 1 if any.
+LDS / scratch / kernarg sizes of the metadata are compared; kernels are matched by symbol (and the variant's extra flags) across the whole tree,
+so one that moved to another file compares equal and is reported as moved; the two leading template arguments that older
+trees gave gemm_kernel are removed.  Prints one line per difference or move and a summary line; exit status 1 if any difference.
 """
 import concurrent.futures
 import os
@@ -61,36 +62,41 @@ def kernels(text):
     return out
 
 
+def tree_kernels(csrc, ex, tmp, side):
+    """(symbol, extra flags) -> (variant it was found in, instruction lines, metadata dict), over every kernel file of the tree"""
+    futs = [(tag, extra, ex.submit(emit, csrc, src, extra, os.path.join(tmp, "%s.%s.s" % (tag.replace(" ", "_"), side))))
+            for tag, src, extra in variants(csrc)]
+    out = {}
+    for tag, extra, fut in futs:
+        for n, (lines, meta) in kernels(fut.result()).items():
+            out[n, " ".join(extra)] = (tag, lines, meta)
+    return out
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("-j")]
     jobs = next((int(a[2:]) for a in sys.argv[1:] if a.startswith("-j") and a[2:]), 8)
     old, new = (os.path.join(a, "gesturediffusion_amd", "csrc") for a in args)
-    ndiff = nk = 0
+    ndiff = 0
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(jobs) as ex:
-        futs = []
-        for tag, src, extra in variants(new):
-            if not os.path.exists(os.path.join(old, src)):
-                print("only in the new tree (has kernels):", src)
+        ko, kn = tree_kernels(old, ex, tmp, "old"), tree_kernels(new, ex, tmp, "new")
+    for key in sorted(set(ko) | set(kn)):
+        n = key[0]
+        if key not in ko or key not in kn:
+            print("%s: %s only in the %s tree" % ((ko.get(key) or kn[key])[0], n, "old" if key in ko else "new"))
+            ndiff += 1
+            continue
+        (to, lo, mo), (tag, ln, mn) = ko[key], kn[key]
+        if to != tag:
+            print("%s: %s: moved here from %s" % (tag, n, to))
+        if lo != ln:
+            print("%s: %s: instruction streams differ (%d vs %d lines)" % (tag, n, len(lo), len(ln)))
+            ndiff += 1
+        for k in META:
+            if mo[k] != mn[k]:
+                print("%s: %s: %s %s -> %s" % (tag, n, k, mo[k], mn[k]))
                 ndiff += 1
-                continue
-            base = os.path.join(tmp, tag.replace(" ", "_"))
-            futs.append((tag, ex.submit(emit, old, src, extra, base + ".old.s"), ex.submit(emit, new, src, extra, base + ".new.s")))
-        for tag, fo, fn in futs:
-            ko, kn = kernels(fo.result()), kernels(fn.result())
-            for n in sorted(set(ko) | set(kn)):
-                nk += 1
-                if n not in ko or n not in kn:
-                    print("%s: %s only in the %s tree" % (tag, n, "old" if n in ko else "new"))
-                    ndiff += 1
-                    continue
-                if ko[n][0] != kn[n][0]:
-                    print("%s: %s: instruction streams differ (%d vs %d lines)" % (tag, n, len(ko[n][0]), len(kn[n][0])))
-                    ndiff += 1
-                for k in META:
-                    if ko[n][1][k] != kn[n][1][k]:
-                        print("%s: %s: %s %s -> %s" % (tag, n, k, ko[n][1][k], kn[n][1][k]))
-                        ndiff += 1
-    print("# %d kernels compared, %d differences" % (nk, ndiff))
+    print("# %d kernels compared (%d in the old tree, %d in the new), %d differences" % (len(set(ko) | set(kn)), len(ko), len(kn), ndiff))
     return 1 if ndiff else 0
 
 
