@@ -23,7 +23,7 @@ EXPORTS = [
     "gdx_linear_f16", "gdx_linear_f32", "gdx_bench_gemm_f16", "gdx_attention_f16", "gdx_attention_f32", "gdx_plms_update", "gdx_postprocess", "gdx_q_sample_t", "gdx_masked_l2", "gdx_set_graph_replay", "gdx_mfcc",
     "gdx_set_guards", "gdx_check_guards", "gdx_packed_bytes", "gdx_export_packed", "gdx_import_packed", "gdx_set_test_half_dtype",
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
-    "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full",
+    "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
 ]
 GDX_BPD_CHUNK = 4096   # include/gdx.h
 
@@ -54,6 +54,26 @@ class PlmsArgs(C.Structure):
         ("kind", C.c_int32), ("batch", C.c_int32), ("per_sample", C.c_int64), ("coef", C.c_void_p), ("t", C.c_void_p),
         ("step_index", C.c_int32), ("x", C.c_void_p), ("pred_xstart", C.c_void_p), ("eps", C.c_void_p * 4),
         ("out", C.c_void_p),
+    ]
+
+
+class PlmsStepArgs(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32),
+        ("coef", C.c_void_p), ("t", C.c_void_p), ("t_eps", C.c_void_p), ("step_index", C.c_int32),
+        ("step_index_eps", C.c_int32), ("x", C.c_void_p), ("x_eps", C.c_void_p), ("x0_cond", C.c_void_p),
+        ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p),
+        ("clip_denoised", C.c_int32), ("eps_hist", C.c_void_p * 3), ("pred_prev", C.c_void_p), ("eps_out", C.c_void_p),
+        ("out", C.c_void_p), ("pred_xstart", C.c_void_p),
+    ]
+
+
+class PlmsLoopArgs(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("order", C.c_int32), ("num_steps", C.c_int32), ("first_index", C.c_int32),
+        ("coef", C.c_void_p), ("timestep_map", C.c_void_p), ("x", C.c_void_p), ("scale", C.c_void_p),
+        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32),
+        ("run_steps", C.c_int32), ("k_base", C.c_int32), ("eps_hist", C.c_void_p), ("scratch", C.c_void_p),
     ]
 
 
@@ -141,6 +161,8 @@ def load():
         "gdx_masked_l2": [vp, vp, vp, vp, i32, i32, i32, vp],
         "gdx_postprocess": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
         "gdx_plms_update": [C.POINTER(PlmsArgs), vp],
+        "gdx_plms_step": [C.POINTER(PlmsStepArgs), vp],
+        "gdx_plms_loop": [vp, C.POINTER(PlmsLoopArgs), vp],
         "gdx_attention_f16": [vp, vp, i32, i32, i32, i32, vp],
         "gdx_attention_half": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
         "gdx_attention_f32": [vp, vp, i32, i32, i32, i32, i32, vp],

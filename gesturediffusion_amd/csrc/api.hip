@@ -579,6 +579,62 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     return 0;
 }
 
+// plms_sample_loop (gaussian_diffusion.py:995-1190): per step the denoiser through forward_core on the pose-layout state (the
+// entry gdx_forward uses: same bits as the step-wise protocol) and one fused plms_step_kernel launch (sampler.hip).  No graph
+// replay and no token-major variant: PLMS runs 10-50 steps, and its first step needs the state in the reference layout twice.
+// The argument checks need no handle and come first (then null handle, then not prepared), so every refusal precedes the
+// first HIP call.
+extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void* stream) {
+    if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_plms_loop: null argument");
+    if (a->mode < GDX_COND || a->mode > GDX_CFG) return fail("gdx_plms_loop: bad mode");
+    if (a->mode == GDX_CFG && !a->scale) return fail("gdx_plms_loop: GDX_CFG needs scale");
+    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
+        a->run_steps > a->first_index + 1)
+        return fail("gdx_plms_loop: bad step range");
+    if (a->order < 2 || a->order > 4) return fail("gdx_plms_loop: order must be 2, 3 or 4");
+    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_plms_loop: mask without motion");
+    if (!a->eps_hist || !a->scratch) return fail("gdx_plms_loop: missing history (eps_hist and scratch are the caller's)");
+    if (check_ready(h, "gdx_plms_loop")) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B, d = h->d;
+    const size_t per = (size_t)h->J * h->T;
+    if (B > 65535) return fail("gdx_plms_loop: batch exceeds 65535");
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    const float* table = h->temb_table;
+    auto denoise = [&](const float* x, int idx) {
+        return forward_core(h, x, table + (size_t)idx * d, 0, h->c2t_table ? h->c2t_table + (size_t)idx * d : nullptr, a->mode, h->x0, s);
+    };
+    auto slot = [&](int k) { return a->eps_hist + (size_t)(k % a->order) * B * per; };
+    gdx_plms_step_args_t u;
+    memset(&u, 0, sizeof(u));
+    u.batch = B; u.njoints = h->J; u.frames = h->T;
+    u.coef = a->coef; u.x = a->x;
+    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
+    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
+    int k = a->k_base;
+    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
+        if (denoise(a->x, idx)) return -1;
+        u.step_index = idx;
+        if (k == 0) {                                   // pseudo improved Euler (:1043-1052): predictor, second forward, corrector
+            u.kind = 6; u.eps_out = slot(0); u.out = a->scratch; u.pred_xstart = slot(1);
+            if (gdx_plms_step(&u, stream)) return -1;
+            const int idx2 = (idx - 1 + a->num_steps) % a->num_steps;
+            if (denoise(a->scratch, idx2)) return -1;
+            u.kind = 5; u.step_index_eps = idx2; u.x_eps = a->scratch; u.eps_hist[0] = slot(0); u.pred_prev = slot(1);
+            u.eps_out = nullptr; u.out = a->x; u.pred_xstart = nullptr;
+            if (gdx_plms_step(&u, stream)) return -1;
+            u.x_eps = nullptr; u.pred_prev = nullptr;
+            continue;
+        }
+        u.kind = k + 1 < a->order ? k + 1 : a->order;
+        u.eps_out = slot(k); u.out = a->x;
+        for (int j = 0; j < 3; ++j) u.eps_hist[j] = j < u.kind - 1 ? slot(k - 1 - j) : nullptr;
+        if (gdx_plms_step(&u, stream)) return -1;
+    }
+    return 0;
+}
+
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
     if (check_ready(h, "gdx_sample_loop")) return -1;
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");

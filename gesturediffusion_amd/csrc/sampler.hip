@@ -322,6 +322,109 @@ __global__ void plms_kernel(int kind, const float* __restrict__ coef, const int6
     out[i] = __fadd_rn(__fmul_rn(mean, nz), __fmul_rn(x0[i], __fsub_rn(1.0f, nz)));
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// One whole PLMS step in one pass (gdx.h gdx_plms_step): update_kernel's pred_xstart (CFG blend -> inpainting -> clamp),
+// plms_kernel kind 0 (eps) and plms_kernel kind 1..6 on the values still in registers, every statement and rounding as
+// there, so the result has the bits of the three launches.  Grid (ceil(groups / 256), B): blockIdx.y is the sample, the
+// kind a template argument.  Kind 5 forms eps_2 from the SECOND forward of a loop's first step (state x_eps, row idx_e)
+// and combines it with the stored eps (e1) and the first forward's pred (pred_prev) under row idx.
+struct PlmsStepDev {
+    long per_sample, groups;
+    const float* coef;
+    const int64_t *t, *t_eps;
+    int step_index, step_index_eps;
+    const float *x, *x_eps, *x0c, *x0u, *scale;
+    const uint8_t* mask;
+    const float* motion;
+    const float *e1, *e2, *e3, *pred_prev;
+    int clip;
+    float *eps_out, *out, *pred;
+};
+
+template <bool VEC>
+__device__ __forceinline__ f32x4 load4(const float* p, long e0, int nval) {
+    if (VEC) return *reinterpret_cast<const f32x4*>(p + e0);
+    f32x4 v;
+    for (int i = 0; i < 4; ++i) v[i] = i < nval ? p[e0 + i] : 0.f;
+    return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(float* p, long e0, int nval, const f32x4 v) {
+    if (VEC) *reinterpret_cast<f32x4*>(p + e0) = v;
+    else for (int i = 0; i < nval; ++i) p[e0 + i] = v[i];
+}
+
+template <int KIND, bool VEC>
+__global__ __launch_bounds__(256) void plms_step_kernel(const PlmsStepDev a) {
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    if (grp >= a.groups) return;
+    const int b = blockIdx.y;
+    const long e0 = (long)b * a.per_sample + 4L * grp;
+    const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
+    const long idx = a.t ? a.t[b] : a.step_index;
+    const long idx_e = KIND == 5 ? (a.t_eps ? a.t_eps[b] : a.step_index_eps) : idx;       // row of this launch's eps
+    const float* c = a.coef + idx * 8;
+    const float* ce = a.coef + idx_e * 8;
+
+    const f32x4 x = load4<VEC>(a.x, e0, nval);
+    f32x4 x0 = load4<VEC>(a.x0c, e0, nval);
+    if (a.x0u) {
+        const f32x4 u = load4<VEC>(a.x0u, e0, nval);
+        const float sc = a.scale[b];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x0[i] = __fadd_rn(u[i], __fmul_rn(sc, __fsub_rn(x0[i], u[i])));
+    }
+    if (a.mask) {
+        if (VEC) {
+            const uint32_t m = *reinterpret_cast<const uint32_t*>(a.mask + e0);
+            const f32x4 mo = load4<true>(a.motion, e0, 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if ((m >> (8 * i)) & 0xffu) x0[i] = mo[i];
+        } else {
+            for (int i = 0; i < nval; ++i)
+                if (a.mask[e0 + i]) x0[i] = a.motion[e0 + i];
+        }
+    }
+    if (a.clip) {                                 // torch.clamp semantics: a NaN stays a NaN
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x0[i] = x0[i] < -1.0f ? -1.0f : (x0[i] > 1.0f ? 1.0f : x0[i]);
+    }
+    const f32x4 xe = KIND == 5 ? load4<VEC>(a.x_eps, e0, nval) : x;
+    f32x4 eps;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) eps[i] = __fdiv_rn(__fsub_rn(__fmul_rn(ce[0], xe[i]), x0[i]), ce[1]);
+    f32x4 e1, e2, e3;
+    if (KIND == 2 || KIND == 3 || KIND == 4 || KIND == 5) e1 = load4<VEC>(a.e1, e0, nval);
+    if (KIND == 3 || KIND == 4) e2 = load4<VEC>(a.e2, e0, nval);
+    if (KIND == 4) e3 = load4<VEC>(a.e3, e0, nval);
+    const f32x4 keep = KIND == 5 ? load4<VEC>(a.pred_prev, e0, nval) : x0;                // the (1 - nz) term's pred_xstart
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (KIND == 6) {
+            r[i] = __fadd_rn(__fmul_rn(x0[i], c[2]), __fmul_rn(c[3], eps[i]));
+            continue;
+        }
+        float ep;
+        if (KIND == 1) ep = eps[i];
+        else if (KIND == 2) ep = __fdiv_rn(__fsub_rn(__fmul_rn(3.0f, eps[i]), e1[i]), 2.0f);
+        else if (KIND == 3)
+            ep = __fdiv_rn(__fadd_rn(__fsub_rn(__fmul_rn(23.0f, eps[i]), __fmul_rn(16.0f, e1[i])), __fmul_rn(5.0f, e2[i])), 12.0f);
+        else if (KIND == 4)
+            ep = __fdiv_rn(__fsub_rn(__fadd_rn(__fsub_rn(__fmul_rn(55.0f, eps[i]), __fmul_rn(59.0f, e1[i])), __fmul_rn(37.0f, e2[i])),
+                                     __fmul_rn(9.0f, e3[i])), 24.0f);
+        else ep = __fdiv_rn(__fadd_rn(e1[i], eps[i]), 2.0f);
+        const float pred = __fsub_rn(__fmul_rn(c[0], x[i]), __fmul_rn(c[1], ep));
+        const float mean = __fadd_rn(__fmul_rn(pred, c[2]), __fmul_rn(c[3], ep));
+        const float nz = c[7];
+        r[i] = __fadd_rn(__fmul_rn(mean, nz), __fmul_rn(keep[i], __fsub_rn(1.0f, nz)));
+    }
+    if (a.eps_out) store4<VEC>(a.eps_out, e0, nval, eps);
+    if (a.pred) store4<VEC>(a.pred, e0, nval, x0);
+    store4<VEC>(a.out, e0, nval, r);
+}
+
 // De-normalisation + position / rotation split of a generated chunk (reference sample/generate.py:132-146 with
 // data_loaders/gesture/data/dataset.py:118-119): feature 6j+c is rotation component c of joint j, 6j+3+c its position.
 //   pos[b][j][c][t] = x[b][6j+3+c][t] * std[6j+3+c] + mean[6j+3+c],  rot[b][j][c][t] likewise with feature 6j+c.
@@ -701,6 +804,54 @@ extern "C" int gdx_plms_update(const gdx_plms_args_t* a, void* stream) {
     return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_plms_update: launch failed");
 }
 
+static inline bool aligned16(const void* p) { return !((uintptr_t)p & 15); }
+
+template <bool VEC>
+static void launch_plms_step(int kind, dim3 grid, hipStream_t s, const gdx::PlmsStepDev& d) {
+    using namespace gdx;
+    const dim3 block(256);
+    switch (kind) {
+        case 1: hipLaunchKernelGGL((plms_step_kernel<1, VEC>), grid, block, 0, s, d); break;
+        case 2: hipLaunchKernelGGL((plms_step_kernel<2, VEC>), grid, block, 0, s, d); break;
+        case 3: hipLaunchKernelGGL((plms_step_kernel<3, VEC>), grid, block, 0, s, d); break;
+        case 4: hipLaunchKernelGGL((plms_step_kernel<4, VEC>), grid, block, 0, s, d); break;
+        case 5: hipLaunchKernelGGL((plms_step_kernel<5, VEC>), grid, block, 0, s, d); break;
+        default: hipLaunchKernelGGL((plms_step_kernel<6, VEC>), grid, block, 0, s, d); break;
+    }
+}
+
+extern "C" int gdx_plms_step(const gdx_plms_step_args_t* a, void* stream) {
+    using namespace gdx;
+    if (!a || !a->coef || !a->x || !a->x0_cond || !a->out) return gdx_set_error_("gdx_plms_step: null argument");
+    if (a->kind < 1 || a->kind > 6) return gdx_set_error_("gdx_plms_step: bad kind");
+    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return gdx_set_error_("gdx_plms_step: bad shape");
+    if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_plms_step: CFG needs scale");
+    if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_plms_step: mask without motion");
+    const int k = a->kind;
+    const int older = k <= 4 ? k - 1 : (k == 5 ? 1 : 0);            // history slots this kind reads
+    for (int i = 0; i < older; ++i)
+        if (!a->eps_hist[i]) return gdx_set_error_("gdx_plms_step: missing history for this kind");
+    if (k != 5 && !a->eps_out) return gdx_set_error_("gdx_plms_step: missing history for this kind");
+    if (k == 5 && (!a->x_eps || !a->pred_prev)) return gdx_set_error_("gdx_plms_step: kind 5 needs x_eps and pred_prev");
+    PlmsStepDev d;
+    d.per_sample = (long)a->njoints * a->frames;
+    d.groups = (d.per_sample + 3) / 4;
+    if (a->batch == 0 || d.per_sample == 0) return 0;
+    d.coef = a->coef; d.t = a->t; d.t_eps = a->t_eps; d.step_index = a->step_index; d.step_index_eps = a->step_index_eps;
+    d.x = a->x; d.x_eps = k == 5 ? a->x_eps : nullptr; d.x0c = a->x0_cond; d.x0u = a->x0_uncond; d.scale = a->scale;
+    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion;
+    d.e1 = older > 0 ? a->eps_hist[0] : nullptr; d.e2 = older > 1 ? a->eps_hist[1] : nullptr;
+    d.e3 = older > 2 ? a->eps_hist[2] : nullptr; d.pred_prev = k == 5 ? a->pred_prev : nullptr;
+    d.clip = a->clip_denoised; d.eps_out = a->eps_out; d.out = a->out; d.pred = a->pred_xstart;
+    const bool vec = d.per_sample % 4 == 0 && aligned16(d.x) && aligned16(d.x_eps) && aligned16(d.x0c) && aligned16(d.x0u) &&
+                     !((uintptr_t)d.mask & 3) && aligned16(d.motion) && aligned16(d.e1) && aligned16(d.e2) && aligned16(d.e3) &&
+                     aligned16(d.pred_prev) && aligned16(d.eps_out) && aligned16(d.out) && aligned16(d.pred);
+    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
+    if (vec) launch_plms_step<true>(k, grid, (hipStream_t)stream, d);
+    else launch_plms_step<false>(k, grid, (hipStream_t)stream, d);
+    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_plms_step: launch failed");
+}
+
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,
                                int32_t batch, int32_t n_joints, int32_t frames, void* stream) {
     if (!x || !mean || !stdv || !pos || !rot) return gdx_set_error_("gdx_postprocess: null argument");
@@ -721,8 +872,6 @@ extern "C" int gdx_randn(float* out, int32_t batch, int64_t per_sample, uint64_t
                        (long)per_sample, groups, philox_seed, sample_offset, rng_step);
     return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_randn: launch failed");
 }
-
-static inline bool aligned16(const void* p) { return !((uintptr_t)p & 15); }
 
 extern "C" int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream) {
     using namespace gdx;

@@ -9,6 +9,7 @@ coefficient rows; every per-element operation runs in libgdx.so:
   * `gdx_forward`         the denoiser (through the model callable protocol `model(x, ts, **kw)`)
   * `gdx_sampler_update`  CFG blend + inpainting + posterior mean / DDIM step + noise, one pass
   * `gdx_sample_loop`     the whole loop enqueued from C++ with in-kernel Philox noise
+  * `gdx_plms_step` / `gdx_plms_loop`   plms_sample_loop (`:995-1190`): one fused multistep update per step, the loop in C++
   * `gdx_bpd_terms` / `gdx_bpd_loop`   the variational bound in bits/dim (`_vb_terms_bpd` :1192-1225, `_prior_bpd`
                           :1519-1535, `calc_bpd_loop` :1537-1592, and `training_losses` under LossType.KL / RESCALED_KL)
 
@@ -460,18 +461,13 @@ class GaussianDiffusion:
             yield out
             img = out["sample"]
 
-    def _fused_loop(self, kind, model, img, indices, model_kwargs, eta, const_noise, rng, philox_seed, sample_offset,
-                    noise_tape, dump_steps, progress, clip_denoised=False):
-        """Whole loop inside libgdx (gdx_sample_loop); yields only the final state.  Noise: a recorded tape, in-kernel
-        Philox, or torch's generator -- then one `normal_()` per step in the reference's order (:532: randn_like(x) is
-        empty_like(x).normal_()), drawn NOISE_BLOCK steps ahead into a tape the update kernel reads; the loop is issued
-        block by block with no host synchronisation in between (with `progress` one per block, to report it)."""
+    def _native_loop_setup(self, model, x, model_kwargs):
+        """What every in-library loop does once in front: input checks, the engine prepared for x's shape and conditioned on
+        y['seed'] / y['mfcc'], and the loop's operands -> (engine, mode, scale, inpainting mask, inpainted motion)."""
         from ..model.cfg_sampler import ClassifierFreeSampleModel
-        self._check_supported()
         y = model_kwargs["y"]
         inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
-        x = E.f32c(img, "x_T").clone()
-        B, J, F, T = x.shape
+        B, T = x.shape[0], x.shape[3]
         inner._check_inputs(x, y)
         if hasattr(inner, "cl_head") and T % 10 != 0:
             from ..model.mdm import _window_error
@@ -488,6 +484,18 @@ class GaussianDiffusion:
             mask = E.require_device(y["inpainting_mask"], "inpainting_mask").to(th.bool).contiguous()
             motion = E.f32c(y["inpainted_motion"], "inpainted_motion")
             assert mask.shape == motion.shape == x.shape
+        return eng, mode, scale, mask, motion
+
+    def _fused_loop(self, kind, model, img, indices, model_kwargs, eta, const_noise, rng, philox_seed, sample_offset,
+                    noise_tape, dump_steps, progress, clip_denoised=False):
+        """Whole loop inside libgdx (gdx_sample_loop); yields only the final state.  Noise: a recorded tape, in-kernel
+        Philox, or torch's generator -- then one `normal_()` per step in the reference's order (:532: randn_like(x) is
+        empty_like(x).normal_()), drawn NOISE_BLOCK steps ahead into a tape the update kernel reads; the loop is issued
+        block by block with no host synchronisation in between (with `progress` one per block, to report it)."""
+        self._check_supported()
+        x = E.f32c(img, "x_T").clone()
+        B, J, F, T = x.shape
+        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
         n = len(indices)
         tape = None
         if noise_tape is not None:
@@ -732,28 +740,10 @@ class GaussianDiffusion:
 
     def _fused_bpd_loop(self, model, xs, clip_denoised, model_kwargs, rng, philox_seed, sample_offset, tape, progress):
         """gdx_bpd_loop, issued block by block like _fused_loop (torch-generator noise is drawn NOISE_BLOCK steps ahead)."""
-        from ..model.cfg_sampler import ClassifierFreeSampleModel
-        y = model_kwargs["y"]
-        inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
         B, J, F, T = xs.shape
-        inner._check_inputs(xs, y)
-        if hasattr(inner, "cl_head") and T % 10 != 0:
-            from ..model.mdm import _window_error
-            raise _window_error(T, 10)
         if self.rescale_timesteps:
             raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
-        eng = inner._get_engine(xs.device)
-        eng.prepare(B, T)
-        eng.set_condition(y["seed"], y["mfcc"], cache=False)
-        if isinstance(model, ClassifierFreeSampleModel):
-            mode, scale = GDX_CFG, E.f32c(y["scale"].reshape(-1), "y['scale']")
-        else:
-            mode, scale = (GDX_UNCOND if y.get("uncond", False) else GDX_COND), None
-        mask = motion = None
-        if "inpainting_mask" in y and "inpainted_motion" in y:
-            mask = E.require_device(y["inpainting_mask"], "inpainting_mask").to(th.bool).contiguous()
-            motion = E.f32c(y["inpainted_motion"], "inpainted_motion")
-            assert mask.shape == motion.shape == xs.shape
+        eng, mode, scale, mask, motion = self._native_loop_setup(model, xs, model_kwargs)
         n = self.num_timesteps
         vb, xm, em = (th.empty(B, n, device=xs.device, dtype=th.float32) for _ in range(3))
         prior = th.empty(B, device=xs.device, dtype=th.float32)
@@ -831,24 +821,74 @@ class GaussianDiffusion:
 
     def plms_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                         randomize_class=False, cond_fn_with_grad=False, order=2):
+                         randomize_class=False, cond_fn_with_grad=False, order=2, *, fused=True, rng="torch", philox_seed=0,
+                         sample_offset=0):
+        """plms_sample_loop of the reference (:1081-1134).  A native START_X denoiser (or its ClassifierFreeSampleModel)
+        without cond_fn / denoised_fn runs the whole loop inside libgdx (gdx_plms_loop: one forward and one fused update
+        launch per step); every other case, and fused=False, goes step by step through plms_sample.  Both give the same
+        bits.  rng / philox_seed / sample_offset choose how x_T is drawn when `noise` is None (the sampler draws nothing else)."""
+        if rng not in ("torch", "philox"):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        if (fused and _is_native(model) and denoised_fn is None and cond_fn is None and not cond_fn_with_grad
+                and not randomize_class and self.model_mean_type == ModelMeanType.START_X):
+            if not int(order) or not 1 <= order <= 4:
+                raise ValueError('order is invalid (should be int from 1-4).')
+            if order == 1:          # the reference subscripts old_out = None on the first step (:1053)
+                raise TypeError("'NoneType' object is not subscriptable")
+            if model_kwargs is None:
+                model_kwargs = {}
+            device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                      philox_seed, sample_offset, None)
+            return self._fused_plms_loop(model, img, indices, model_kwargs, int(order), progress, clip_denoised)
         final = None
         for sample in self.plms_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                         denoised_fn=denoised_fn, cond_fn=cond_fn,
                                                         model_kwargs=model_kwargs, device=device, progress=progress,
                                                         skip_timesteps=skip_timesteps, init_image=init_image,
                                                         randomize_class=randomize_class,
-                                                        cond_fn_with_grad=cond_fn_with_grad, order=order):
+                                                        cond_fn_with_grad=cond_fn_with_grad, order=order, rng=rng,
+                                                        philox_seed=philox_seed, sample_offset=sample_offset):
             final = sample
         return final["sample"]
 
+    def _fused_plms_loop(self, model, img, indices, model_kwargs, order, progress, clip_denoised):
+        """Whole loop inside libgdx (gdx_plms_loop).  The eps history and the first step's predictor live in two tensors of
+        this call; with `progress` the loop is issued in blocks of NOISE_BLOCK steps, one synchronisation per block."""
+        self._check_supported()
+        if self.rescale_timesteps:
+            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
+        x = E.f32c(img, "x_T").clone()
+        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
+        n = len(indices)
+        coef, tmap = self.coef_table(GDX_SAMPLER_DDIM, x.device, 0.0), self._timestep_map()
+        hist = th.empty((order, *x.shape), device=x.device, dtype=th.float32)
+        scratch = th.empty_like(x)
+        block = min(n, NOISE_BLOCK) if progress else n
+        bar = None
+        if progress:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=n)
+        k = 0
+        while k < n:
+            nb = min(block, n - k)
+            eng.plms_loop(x, mode, order, coef, tmap, indices[k], hist, scratch, scale=scale, inpaint_mask=mask,
+                          inpaint_motion=motion, clip_denoised=clip_denoised, run_steps=nb, k_base=k)
+            k += nb
+            if bar is not None:
+                th.cuda.current_stream(x.device).synchronize()
+                bar.update(nb)
+        if bar is not None:
+            bar.close()
+        return x
+
     def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, skip_timesteps=0,
-                                     init_image=None, randomize_class=False, cond_fn_with_grad=False, order=2):
+                                     init_image=None, randomize_class=False, cond_fn_with_grad=False, order=2, *,
+                                     rng="torch", philox_seed=0, sample_offset=0):
         if randomize_class:
             raise NotImplementedError("randomize_class is outside the sampling hot path")
-        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, "torch", 0,
-                                                  0, None)
+        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                  philox_seed, sample_offset, None)
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)

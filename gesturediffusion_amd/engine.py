@@ -190,6 +190,19 @@ class Engine:
         _lib.check(self.lib.gdx_bpd_loop(self.handle, C.byref(a), _stream(x_start.device)), self.lib)
         self._keep_loop = (tmap,)
 
+    def plms_loop(self, x, mode, order, coef, timestep_map, first_index, eps_hist, scratch, scale=None, inpaint_mask=None,
+                  inpaint_motion=None, clip_denoised=False, run_steps=0, k_base=0):
+        """gdx_plms_loop: x is updated in place; eps_hist [order, B, J, 1, T] and scratch [B, J, 1, T] are the caller's and
+        carry the multistep history from one block (run_steps / k_base) to the next."""
+        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
+        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        a = _lib.PlmsLoopArgs(mode=mode, order=order, num_steps=len(tmap), first_index=first_index, coef=coef.data_ptr(),
+                              timestep_map=tmap.ctypes.data, x=x.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
+                              inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
+                              k_base=k_base, eps_hist=eps_hist.data_ptr(), scratch=scratch.data_ptr())
+        _lib.check(self.lib.gdx_plms_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
+        self._keep_loop = (tmap,)
+
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
         _lib.check(self.lib.gdx_forward_flops(self.handle, mode, C.byref(f)), self.lib)
@@ -283,6 +296,25 @@ def plms_update(kind, coef, t, x, pred_xstart, eps=(), out=None):
     for i, e in enumerate(eps):
         a.eps[i] = e.data_ptr()
     _lib.check(lib.gdx_plms_update(C.byref(a), _stream(ref.device)), lib)
+    return out
+
+
+def plms_step(kind, coef, x, x0_cond, out, eps_out=None, eps_hist=(), t=None, step_index=0, x0_uncond=None, scale=None,
+              inpaint_mask=None, inpaint_motion=None, clip_denoised=False, pred_xstart=None, x_eps=None, t_eps=None,
+              step_index_eps=0, pred_prev=None):
+    """gdx_plms_step: one whole PLMS step in one pass (include/gdx.h).  kind 1..4 Adams-Bashforth over the eps formed here
+    and eps_hist (older, newest first), 5 the first step's corrector (x_eps / t_eps / pred_prev), 6 its predictor."""
+    lib = _lib.load()
+    B, J, F, T = x0_cond.shape
+    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
+    a = _lib.PlmsStepArgs(kind=kind, batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(), t=p(t), t_eps=p(t_eps),
+                          step_index=step_index, step_index_eps=step_index_eps, x=x.data_ptr(), x_eps=p(x_eps),
+                          x0_cond=x0_cond.data_ptr(), x0_uncond=p(x0_uncond), scale=p(scale), inpaint_mask=p(inpaint_mask),
+                          inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), pred_prev=p(pred_prev),
+                          eps_out=p(eps_out), out=out.data_ptr(), pred_xstart=p(pred_xstart))
+    for i, e in enumerate(eps_hist):
+        a.eps_hist[i] = e.data_ptr()
+    _lib.check(lib.gdx_plms_step(C.byref(a), _stream(x0_cond.device)), lib)
     return out
 
 

@@ -209,6 +209,46 @@ typedef struct {
 } gdx_plms_args_t;
 int gdx_plms_update(const gdx_plms_args_t* a, void* stream);
 
+/* One whole PLMS step over [B,J,1,T] in ONE pass, with the bits of the three launches it replaces (gdx_sampler_update's
+ * pred_xstart output, gdx_plms_update kind 0, gdx_plms_update kind 1..6): per element, every product / sum / quotient rounded
+ * separately, coefficient row c = coef[idx] (DDIM layout at eta = 0 as above), idx = t[b] if t != NULL else step_index:
+ *   pred = x0_cond -> CFG blend u + scale*(c - u) -> inpainting blend -> clamp, exactly as in gdx_sampler_update
+ *   eps  = (c0*x - pred) / c1, written to eps_out (the caller's history slot)
+ *   kind 1..4: eps' = Adams-Bashforth of that order over eps (newest), eps_hist[0], eps_hist[1], eps_hist[2]
+ *   kind 5   : the corrector of a loop's first step.  x0_cond / x0_uncond hold the SECOND forward's output, run on the
+ *              predictor x_eps at row idx_e = t_eps[b] if t_eps != NULL else step_index_eps:  eps = (ce0*x_eps - pred) / ce1,
+ *              eps' = (eps_hist[0] + eps) / 2 with eps_hist[0] the first forward's eps; eps_out may be NULL (the reference keeps
+ *              the first eps in its history, :1043-1052)
+ *   kind 1..5: pred' = c0*x - c1*eps';  out = (pred'*c2 + c3*eps')*nz + keep*(1 - nz),  nz = c7,  keep = pred (kind 5: pred_prev,
+ *              the first forward's pred)
+ *   kind 6   : out = pred*c2 + c3*eps, the improved-Euler predictor of a loop's first step (out must not alias x there:
+ *              kind 5 reads x again)
+ * History slots a kind does not use are never read.  128-bit accesses when J*T % 4 == 0 and every pointer is 16-byte aligned
+ * (the mask 4-byte), a scalar path otherwise.  batch <= 65535 (the grid's second dimension is the sample). */
+typedef struct {
+    int32_t kind;              /* 1..6 */
+    int32_t batch, njoints, frames;
+    const float* coef;         /* [num_steps][8] */
+    const int64_t* t;          /* [B] or NULL */
+    const int64_t* t_eps;      /* kind 5: [B] or NULL */
+    int32_t step_index;        /* used when t == NULL */
+    int32_t step_index_eps;    /* kind 5, used when t_eps == NULL */
+    const float* x;            /* x_t */
+    const float* x_eps;        /* kind 5: the predictor the second forward ran on */
+    const float* x0_cond;      /* model output (cond pass) */
+    const float* x0_uncond;    /* NULL or uncond pass */
+    const float* scale;        /* [B] when x0_uncond != NULL */
+    const uint8_t* inpaint_mask;   /* NULL or bool bytes [B,J,1,T] */
+    const float* inpaint_motion;   /* [B,J,1,T] when mask != NULL */
+    int32_t clip_denoised;
+    const float* eps_hist[3];  /* older eps, newest first: kind k <= 4 reads k - 1 of them, kind 5 one, kind 6 none */
+    const float* pred_prev;    /* kind 5: pred of the first forward */
+    float* eps_out;            /* this launch's eps; required except for kind 5 */
+    float* out;                /* may alias x */
+    float* pred_xstart;        /* NULL or [B,J,1,T]: pred */
+} gdx_plms_step_args_t;
+int gdx_plms_step(const gdx_plms_step_args_t* a, void* stream);
+
 /* q_sample (gaussian_diffusion.py:233-251): out = a*x_start + b*noise, a/b per-sample from
  * coef rows (c[5], c[6]) at idx. */
 int gdx_q_sample(const float* x_start, const float* noise, const float* coef, int32_t idx,
@@ -359,6 +399,37 @@ typedef struct {
     float* prior_bpd;
 } gdx_bpd_loop_args_t;
 int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* stream);
+
+/* replaces plms_sample_loop (gaussian_diffusion.py:1081-1190 around plms_sample :995-1079) for a START_X denoiser without
+ * cond_fn / denoised_fn: per executed step one denoiser call through the same forward entry gdx_forward uses (so the loop has
+ * the bits of the step-wise protocol) and ONE gdx_plms_step launch, all enqueued on `stream` with no host synchronisation.
+ * Executed step k runs index first_index - (k - k_base), model timestep = timestep_map[index]; its eps goes to slot k % order
+ * of eps_hist and its kind is min(order, k + 1).  Step 0 of the whole loop (k_base == 0) is the pseudo improved Euler step:
+ * forward at index i, kind 6 (eps -> slot 0, predictor -> scratch, pred -> slot 1, free until step 1), forward on the
+ * predictor at index (i - 1) mod num_steps (the reference's table gather wraps at i == 0), kind 5 into x; the history keeps
+ * the first eps.  run_steps > 0 executes only that many steps of the loop (block-wise issue, same bits as one call: the
+ * history lives in the caller's eps_hist between calls, first_index is THIS call's first index and k_base the executed-step
+ * number of its first step); 0 = down to index 0.  eps_hist and scratch are the caller's; the library owns only its weights
+ * and workspace.  There is neither graph replay nor a token-major variant of this loop.  Refusals come before the first HIP
+ * call. */
+typedef struct {
+    int32_t mode;              /* GDX_COND / GDX_UNCOND / GDX_CFG */
+    int32_t order;             /* 2..4 */
+    int32_t num_steps;         /* rows of coef / timestep_map */
+    int32_t first_index;       /* index of this call's first step (whole loop: num_steps - 1 - skip_timesteps) */
+    const float* coef;         /* device [num_steps][8], DDIM rows at eta = 0 */
+    const int64_t* timestep_map;   /* HOST [num_steps] */
+    float* x;                  /* in: x_T (or q_sample'd init), out: the sample */
+    const float* scale;        /* [B] for GDX_CFG */
+    const uint8_t* inpaint_mask;
+    const float* inpaint_motion;
+    int32_t clip_denoised;
+    int32_t run_steps;
+    int32_t k_base;
+    float* eps_hist;           /* device [order][B,J,1,T] */
+    float* scratch;            /* device [B,J,1,T]: the predictor of step 0 */
+} gdx_plms_loop_args_t;
+int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void* stream);
 
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  Off by
