@@ -523,6 +523,19 @@ static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timeste
     return 0;
 }
 
+// The denoiser at schedule index `idx` of the loop tables build_step_tables left: x0_out (pose layout) from the state x; tm:
+// the token-major variant (x / x0_out unused); state: a captured step, which reads its row number from the device (idx = 0)
+static int denoise_step(gdx_model* h, const float* x, int idx, int mode, float* x0_out, hipStream_t s, const int* state = nullptr,
+                        bool tm = false) {
+    const size_t row = (size_t)idx * h->d;
+    return forward_core(h, x, h->temb_table + row, 0, h->c2t_table ? h->c2t_table + row : nullptr, mode, x0_out, s, state, tm);
+}
+
+// Executed step k's slice of a noise tape that starts at step k_base and holds `rows` samples ([rows][per]) per step
+static const float* tape_slice(const float* tape, int k, int k_base, size_t rows, size_t per) {
+    return tape ? tape + (ptrdiff_t)(k - k_base) * (ptrdiff_t)(rows * per) : nullptr;
+}
+
 // calc_bpd_loop (gaussian_diffusion.py:1537-1592): per step q_sample -> denoiser -> fused bound terms, through the SAME forward
 // entry (pose-layout x_t, forward_core) the step-wise protocol reaches via gdx_forward, so both give the same bits.
 extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* stream) {
@@ -537,14 +550,13 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
         return fail("gdx_bpd_loop: bad step range");
     if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_bpd_loop: mask without motion");
     hipStream_t s = (hipStream_t)stream;
-    const int B = h->B, d = h->d;
+    const int B = h->B;
     const size_t per = (size_t)h->J * h->T;
     const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
     if (!h->bpd_xt && dev_alloc(h->ws_allocs, (void**)&h->bpd_xt, sizeof(float) * B * per)) return -1;
     if (!h->bpd_part && dev_alloc(h->ws_allocs, (void**)&h->bpd_part, sizeof(float) * 4 * B * chunks)) return -1;
     if (!a->noise_tape && !h->bpd_z && dev_alloc(h->ws_allocs, (void**)&h->bpd_z, sizeof(float) * B * per)) return -1;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
-    const float* table = h->temb_table;
     gdx_bpd_args_t u;
     memset(&u, 0, sizeof(u));
     u.batch = B; u.njoints = h->J; u.frames = h->T;
@@ -558,7 +570,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     for (int k = a->k_base; k < k_end; ++k) {
         const int idx = a->num_steps - 1 - k;
         if (a->noise_tape) {
-            u.noise = a->noise_tape + (size_t)(k - a->k_base) * B * per;
+            u.noise = tape_slice(a->noise_tape, k, a->k_base, B, per);
             if (gdx_q_sample(a->x_start, u.noise, a->coef, idx, (int64_t)(B * per), h->bpd_xt, stream)) return -1;
         } else {
             u.noise = h->bpd_z;
@@ -566,8 +578,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
                             stream))
                 return -1;
         }
-        if (forward_core(h, h->bpd_xt, table + (size_t)idx * d, 0, h->c2t_table ? h->c2t_table + (size_t)idx * d : nullptr, a->mode, h->x0, s))
-            return -1;
+        if (denoise_step(h, h->bpd_xt, idx, a->mode, h->x0, s)) return -1;
         u.step_index = idx; u.col = k;
         if (gdx_bpd_terms(&u, stream)) return -1;
     }
@@ -596,14 +607,11 @@ extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void
     if (!a->eps_hist || !a->scratch) return fail("gdx_plms_loop: missing history (eps_hist and scratch are the caller's)");
     if (check_ready(h, "gdx_plms_loop")) return -1;
     hipStream_t s = (hipStream_t)stream;
-    const int B = h->B, d = h->d;
+    const int B = h->B;
     const size_t per = (size_t)h->J * h->T;
     if (B > 65535) return fail("gdx_plms_loop: batch exceeds 65535");
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
-    const float* table = h->temb_table;
-    auto denoise = [&](const float* x, int idx) {
-        return forward_core(h, x, table + (size_t)idx * d, 0, h->c2t_table ? h->c2t_table + (size_t)idx * d : nullptr, a->mode, h->x0, s);
-    };
+    auto denoise = [&](const float* x, int idx) { return denoise_step(h, x, idx, a->mode, h->x0, s); };
     auto slot = [&](int k) { return a->eps_hist + (size_t)(k % a->order) * B * per; };
     gdx_plms_step_args_t u;
     memset(&u, 0, sizeof(u));
@@ -645,11 +653,11 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     if (a->kind == GDX_SAMPLER_DDIM && (a->const_noise || a->n_dump))
         return fail("gdx_sample_loop: ddim_sample_loop supports neither const_noise nor dump_steps");  // :903-906
     hipStream_t s = (hipStream_t)stream;
-    const int B = h->B, d = h->d;
+    const int B = h->B;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
-    float* table = h->temb_table;
 
     const int64_t per = (int64_t)h->J * h->T;
+    const size_t tape_rows = a->const_noise ? 1 : B;             // samples per step of the noise tape
     int dump_i = 0;
     while (dump_i < a->n_dump && a->dump_steps[dump_i] < a->k_base) ++dump_i;     // entries of earlier blocks
     auto fill_update = [&](gdx_update_args_t& u, int idx, int k) {
@@ -660,15 +668,14 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr;
         u.scale = a->scale;
         u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
-        u.noise = a->noise_tape ? a->noise_tape + (size_t)(k - a->k_base) * (a->const_noise ? 1 : B) * per : nullptr;
+        u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
         u.const_noise = a->const_noise;
         u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset; u.rng_step = (uint32_t)(k + 1);
         u.out = a->x; u.pred_xstart = nullptr;
         u.clip_denoised = a->clip_denoised;
     };
     auto eager_step = [&](int idx, int k) -> int {
-        if (forward_core(h, a->x, table + (size_t)idx * d, 0, h->c2t_table ? h->c2t_table + (size_t)idx * d : nullptr, a->mode, h->x0, s))
-            return -1;
+        if (denoise_step(h, a->x, idx, a->mode, h->x0, s)) return -1;
         gdx_update_args_t u;
         fill_update(u, idx, k);
         if (gdx_sampler_update(&u, stream)) return -1;
@@ -698,17 +705,20 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         const int ldx = h->f16 ? h->in_x.kpad16 : h->in_x.kpad;
         HIPCHK(launch_transpose_in(a->x, h->xt, Beff, B, h->J, h->T, ldx, s));
         if (h->f16) HIPCHK(HFN(h->bf16, launch_transpose_in_f16, a->x, h->xt16, Beff, B, h->J, h->T, ldx, s));
+        gdx::UpdateTmDev u;
+        memset(&u, 0, sizeof(u));
+        u.kind = a->kind; u.B = B; u.J = h->J; u.T = h->T; u.ldx = ldx; u.ldo = h->ldo;
+        u.coef = a->coef; u.xt = h->xt; u.x0t = h->x0t; u.scale = a->mode == GDX_CFG ? a->scale : nullptr;
+        u.const_noise = a->const_noise; u.seed = a->philox_seed; u.sample_offset = a->sample_offset;
+        u.clip = a->clip_denoised;
+        u.xt16 = h->f16 ? (void*)h->xt16 : nullptr; u.half_dtype = h->cfg.compute_dtype;
         int k = a->k_base;
         for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
-            if (forward_core(h, nullptr, table + (size_t)idx * d, 0, h->c2t_table ? h->c2t_table + (size_t)idx * d : nullptr, a->mode,
-                             nullptr, s, nullptr, true))
-                return -1;
-            if (gdx_sampler_update_tm_(a->kind, B, h->J, h->T, ldx, h->ldo, a->coef, idx, h->xt, h->x0t,
-                                       a->mode == GDX_CFG ? a->scale : nullptr, a->const_noise, a->philox_seed, a->sample_offset,
-                                       (uint32_t)(k + 1), a->clip_denoised, idx == last_idx ? a->x : nullptr,
-                                       h->f16 ? (void*)h->xt16 : nullptr, h->cfg.compute_dtype, stream,
-                                       a->noise_tape ? a->noise_tape + (size_t)(k - a->k_base) * (a->const_noise ? 1 : B) * per : nullptr))
-                return -1;
+            if (denoise_step(h, nullptr, idx, a->mode, nullptr, s, nullptr, true)) return -1;
+            u.step_index = idx; u.rng_step = (uint32_t)(k + 1);
+            u.out_pose = idx == last_idx ? a->x : nullptr;
+            u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
+            if (gdx_sampler_update_tm_(u, stream)) return -1;
         }
         return 0;
     }
@@ -735,13 +745,11 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
                  hipStreamWaitEvent(h->gstream, h->gev_in, 0) == hipSuccess;
         }
         if (ok && hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            int rc = forward_core(h, a->x, table, 0, h->c2t_table, a->mode, h->x0, h->gstream, h->gstate);
+            int rc = denoise_step(h, a->x, 0, a->mode, h->x0, h->gstream, h->gstate);
             if (!rc) {
                 gdx_update_args_t u;
-                fill_update(u, 0, 0);
-                u.noise = a->noise_tape ? a->noise_tape - (size_t)a->k_base * (a->const_noise ? 1 : B) * per : nullptr;
-                                                                  // base; the kernel adds state[1] * stride
-                rc = gdx_sampler_update_state_(&u, h->gstate, (long)(a->const_noise ? 1 : B) * per, (void*)h->gstream);
+                fill_update(u, 0, 0);                             // noise: step 0's slice; the kernel adds state[1] * stride
+                rc = gdx_sampler_update_state_(&u, h->gstate, (long)(tape_rows * per), (void*)h->gstream);
             }
             if (!rc && launch_advance_state(h->gstate, h->gstream) != hipSuccess) rc = -1;
             hipGraph_t g = nullptr;

@@ -180,15 +180,30 @@ hipError_t launch_advance_state(int* st, hipStream_t s);
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, float* out, int B, int64_t per_sample,
                             hipStream_t s);
 
+// argument of update_tm_kernel (sampler.hip): one step of gdx_sample_loop's token-major fast path, filled by api.hip
+struct UpdateTmDev {
+    int kind, B, J, T, ldx, ldo;
+    const float* coef; int step_index;
+    float* xt;              // [Beff*T][ldx] in / out
+    const float* x0t;       // [Beff*T][ldo]
+    const float* scale;     // [B] or nullptr: guidance on (Beff = 2B)
+    int const_noise;
+    uint64_t seed, sample_offset;
+    uint32_t rng_step;
+    int clip;
+    float* out_pose;        // [B][J][T] or nullptr (last step)
+    void* xt16;             // half modes: the input GEMM's 16-bit operand [Beff*T][ldx], written beside the fp32 state
+    int half_dtype;         // GDX_DTYPE_F16 or GDX_DTYPE_BF16 (the element type of xt16)
+    const float* noise;     // this step's slice of a noise tape, reference layout [B or 1][J][T], or nullptr (Philox)
+};
+
 }  // namespace gdx
 
 // the loops' (api.hip) private entries into sampler.hip; each returns 0, or -1 with the error recorded
 // the update of a captured step: schedule index / step number read from `state` (UpdateDev::state)
 int gdx_sampler_update_state_(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
-// one step of the token-major fast path of gdx_sample_loop (update_tm_kernel)
-int gdx_sampler_update_tm_(int kind, int B, int J, int T, int ldx, int ldo, const float* coef, int step_index, float* xt,
-                           const float* x0t, const float* scale, int const_noise, uint64_t seed, uint64_t sample_offset,
-                           uint32_t rng_step, int clip, float* out_pose, void* xt16, int half_dtype, void* stream, const float* noise);
+// one step of the token-major fast path of gdx_sample_loop (update_tm_kernel); checks the layout arguments of `d`
+int gdx_sampler_update_tm_(const gdx::UpdateTmDev& d, void* stream);
 // gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
 int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
                 uint32_t step, float* z_out, float* xt_out, void* stream);

@@ -50,6 +50,139 @@ __device__ __forceinline__ f32x4 philox_normal4(uint64_t seed, uint64_t sample, 
     return z;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Device helpers.  Every formula whose bits are pinned to the reference's torch expression is written ONCE, here, and every
+// kernel below calls it: two kernels agree bit for bit because they run the same statements, not because two copies were
+// kept in step.  Each product / sum / quotient is its own __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn in torch's op order;
+// the helpers must stay in this translation unit (contraction off, see the top of the file).
+
+// A group = four consecutive elements of one sample in the pose layout [B][J*T]; the last group of a sample holds `nval` < 4
+// elements when J*T % 4 != 0 (VEC = false).  `grp` is also the Philox group number.
+struct Group {
+    int b;
+    uint32_t grp;
+    long e0;                // flat index of the group's first element
+    int nval;
+};
+template <bool VEC>
+__device__ __forceinline__ Group group_at(int b, long grp, long per_sample) {          // 2-D grids: blockIdx.y = sample
+    return Group{b, (uint32_t)grp, (long)b * per_sample + 4L * grp, VEC ? 4 : (int)min(4L, per_sample - 4L * grp)};
+}
+template <bool VEC>
+__device__ __forceinline__ Group group_of(long gid, long groups, long per_sample) {    // 1-D grids: gid = b * groups + grp
+    const int b = gid / groups;
+    return group_at<VEC>(b, gid - (long)b * groups, per_sample);
+}
+
+template <bool VEC>
+__device__ __forceinline__ f32x4 load4(const float* p, long e0, int nval) {
+    if (VEC) return *reinterpret_cast<const f32x4*>(p + e0);
+    f32x4 v;
+    for (int i = 0; i < 4; ++i) v[i] = i < nval ? p[e0 + i] : 0.f;
+    return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(float* p, long e0, int nval, const f32x4 v) {
+    if (VEC) *reinterpret_cast<f32x4*>(p + e0) = v;
+    else for (int i = 0; i < nval; ++i) p[e0 + i] = v[i];
+}
+// the group's four mask bytes, byte i in bits 8i .. 8i+7 (an element is masked when its byte is non-zero)
+template <bool VEC>
+__device__ __forceinline__ uint32_t mask4(const uint8_t* p, long e0, int nval) {
+    if (VEC) return *reinterpret_cast<const uint32_t*>(p + e0);
+    uint32_t m = 0;
+    for (int i = 0; i < nval; ++i) m |= (uint32_t)p[e0 + i] << (8 * i);
+    return m;
+}
+
+// classifier-free guidance (model/cfg_sampler.py:28): u + sc * (c - u)
+__device__ __forceinline__ float cfg_blend(float c, float u, float sc) { return __fadd_rn(u, __fmul_rn(sc, __fsub_rn(c, u))); }
+// torch.clamp(v, -1, 1): a NaN stays a NaN
+__device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
+
+// pred_xstart of p_mean_variance for a group of sample b: CFG blend (x0u set) -> inpainting (:307-311) -> clip_denoised (:349-355)
+// (the guidance scale scale[b] is read only under guidance)
+template <bool VEC>
+__device__ __forceinline__ f32x4 pred_xstart4(const float* x0c, const float* x0u, const float* scale, int b, const uint8_t* mask,
+                                              const float* motion, int clip, long e0, int nval) {
+    f32x4 x0 = load4<VEC>(x0c, e0, nval);
+    if (x0u) {
+        const f32x4 u = load4<VEC>(x0u, e0, nval);
+        const float sc = scale[b];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x0[i] = cfg_blend(x0[i], u[i], sc);
+    }
+    if (mask) {
+        const uint32_t m = mask4<VEC>(mask, e0, nval);
+        const f32x4 mo = load4<VEC>(motion, e0, nval);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if ((m >> (8 * i)) & 0xffu) x0[i] = mo[i];
+    }
+    if (clip) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x0[i] = clamp1(x0[i]);
+    }
+    return x0;
+}
+
+// _predict_eps_from_xstart (:407-411): (c0*x - x0) / c1, with c0 = sqrt_recip_alphas_cumprod, c1 = sqrt_recipm1_alphas_cumprod
+__device__ __forceinline__ float eps_from_xstart(float c0, float c1, float x, float x0) {
+    return __fdiv_rn(__fsub_rn(__fmul_rn(c0, x), x0), c1);
+}
+// _predict_xstart_from_eps (:390-396): c0*x - c1*eps
+__device__ __forceinline__ float xstart_from_eps(float c0, float c1, float x, float eps) {
+    return __fsub_rn(__fmul_rn(c0, x), __fmul_rn(c1, eps));
+}
+// pred_xstart under condition_score (:452-472): eps - sqrt(1 - alpha_bar) * gradient, and x0 back from it
+__device__ __forceinline__ float cond_score_xstart(float c0, float c1, float s1m, float x, float x0, float grad) {
+    return xstart_from_eps(c0, c1, x, __fsub_rn(eps_from_xstart(c0, c1, x, x0), __fmul_rn(s1m, grad)));
+}
+// a*x0 + b*x: the posterior mean (:253-275) with (a, b) = posterior_mean_coef1/2
+__device__ __forceinline__ float posterior_mean(float a, float b, float x0, float x) { return __fadd_rn(__fmul_rn(a, x0), __fmul_rn(b, x)); }
+// x0*a + b*eps: the DDIM / improved-Euler mean (:766-770, :1046) with (a, b) = sqrt(alpha_bar_prev), sqrt(1 - alpha_bar_prev [- sigma^2])
+__device__ __forceinline__ float ddim_mean(float a, float b, float x0, float eps) { return __fadd_rn(__fmul_rn(x0, a), __fmul_rn(b, eps)); }
+// q_sample (:233-251): sa*x + s1m*z
+__device__ __forceinline__ float q_sample_value(float sa, float s1m, float x, float z) { return __fadd_rn(__fmul_rn(sa, x), __fmul_rn(s1m, z)); }
+
+// The ancestral (p_sample :524-548) / DDIM (:748-782) step of one element, c = the step's coefficient row.  cond: cond_fn
+// guidance with gradient `grad` -- condition_mean (mean + variance * gradient, c[3] = posterior variance) for the ancestral
+// step, condition_score (s1m = sqrt(1 - alpha_bar)) for DDIM.
+__device__ __forceinline__ float update_value(int kind, const float* c, float x, float x0, float z, bool cond = false,
+                                              float grad = 0.f, float s1m = 0.f) {
+    if (kind == GDX_SAMPLER_P) {
+        float mean = posterior_mean(c[0], c[1], x0, x);
+        if (cond) mean = __fadd_rn(mean, __fmul_rn(c[3], grad));
+        return __fadd_rn(mean, __fmul_rn(c[2], z));
+    }
+    if (cond) x0 = cond_score_xstart(c[0], c[1], s1m, x, x0, grad);
+    const float mean = ddim_mean(c[2], c[3], x0, eps_from_xstart(c[0], c[1], x, x0));
+    return __fadd_rn(mean, __fmul_rn(c[4], z));
+}
+
+// eps' of plms_sample (:1053-1066) from the newest eps and the history e1 (newest) .. e3:
+//   kind 1: eps   2: (3 eps - e1)/2   3: (23 eps - 16 e1 + 5 e2)/12   4: (55 eps - 59 e1 + 37 e2 - 9 e3)/24
+//   kind 5: (e1 + eps)/2, the improved-Euler corrector (:1052; e1 = the first forward's eps, eps = eps_2).  Operand order of
+//           plms_step_kernel; plms_kernel used to write (e0 + e1), the same sum with the operands exchanged (same bits)
+__device__ __forceinline__ float plms_combine(int kind, float eps, float e1, float e2, float e3) {
+    if (kind == 1) return eps;
+    float num, den = 2.0f;
+    if (kind == 2) num = __fsub_rn(__fmul_rn(3.0f, eps), e1);
+    else if (kind == 3) { num = __fadd_rn(__fsub_rn(__fmul_rn(23.0f, eps), __fmul_rn(16.0f, e1)), __fmul_rn(5.0f, e2)); den = 12.0f; }
+    else if (kind == 4) {
+        num = __fsub_rn(__fadd_rn(__fsub_rn(__fmul_rn(55.0f, eps), __fmul_rn(59.0f, e1)), __fmul_rn(37.0f, e2)), __fmul_rn(9.0f, e3));
+        den = 24.0f;
+    } else num = __fadd_rn(e1, eps);
+    return __fdiv_rn(num, den);
+}
+// pred' = c0*x - c1*eps';  (pred'*c2 + c3*eps')*nz + keep*(1 - nz), nz = c[7] = (t != 0); keep = the step's pred_xstart (:1067-1078)
+__device__ __forceinline__ float plms_tail(const float* c, float x, float ep, float keep) {
+    const float pred = xstart_from_eps(c[0], c[1], x, ep);
+    const float mean = ddim_mean(c[2], c[3], pred, ep);
+    const float nz = c[7];
+    return __fadd_rn(__fmul_rn(mean, nz), __fmul_rn(keep, __fsub_rn(1.0f, nz)));
+}
+
 struct UpdateDev {
     int kind;
     long per_sample;        // J*T
@@ -80,75 +213,24 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void update_kernel(const UpdateDev a) {
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= a.groups * a.batch) return;
-    const int b = gid / a.groups;
-    const uint32_t grp = gid - (long)b * a.groups;
-    const long e0 = (long)b * a.per_sample + 4L * grp;
-    const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
-    const long idx = a.state ? a.state[0] : (a.t ? a.t[b] : a.step_index);
+    const Group g = group_of<VEC>(gid, a.groups, a.per_sample);
+    const long idx = a.state ? a.state[0] : (a.t ? a.t[g.b] : a.step_index);
     const float* c = a.coef + idx * 8;
     const uint32_t rng_step = a.state ? (uint32_t)a.state[1] + 1u : a.rng_step;
     const float* noise = a.noise && a.state ? a.noise + (long)a.state[1] * a.noise_stride : a.noise;
 
-    f32x4 x, x0, z;
-    if (VEC) {
-        x = *reinterpret_cast<const f32x4*>(a.x + e0);
-        x0 = *reinterpret_cast<const f32x4*>(a.x0c + e0);
-    } else {
-        for (int i = 0; i < 4; ++i) { x[i] = i < nval ? a.x[e0 + i] : 0.f; x0[i] = i < nval ? a.x0c[e0 + i] : 0.f; }
-    }
-    if (a.x0u) {
-        f32x4 u;
-        if (VEC) u = *reinterpret_cast<const f32x4*>(a.x0u + e0);
-        else for (int i = 0; i < 4; ++i) u[i] = i < nval ? a.x0u[e0 + i] : 0.f;
-        const float sc = a.scale[b];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x0[i] = __fadd_rn(u[i], __fmul_rn(sc, __fsub_rn(x0[i], u[i])));
-    }
-    if (a.mask) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (i < nval && a.mask[e0 + i]) x0[i] = a.motion[e0 + i];
-    }
-    if (a.clip) {                                 // torch.clamp semantics: a NaN stays a NaN
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x0[i] = x0[i] < -1.0f ? -1.0f : (x0[i] > 1.0f ? 1.0f : x0[i]);
-    }
-    if (noise) {
-        const long z0 = a.const_noise ? 4L * grp : e0;
-        if (VEC) z = *reinterpret_cast<const f32x4*>(noise + z0);
-        else for (int i = 0; i < 4; ++i) z[i] = i < nval ? noise[z0 + i] : 0.f;
-    } else {
-        const uint64_t sample = a.const_noise ? 0ull : a.sample_offset + (uint64_t)b;
-        z = philox_normal4(a.seed, sample, rng_step, grp);
-    }
+    const f32x4 x = load4<VEC>(a.x, g.e0, g.nval);
+    const f32x4 x0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, g.e0, g.nval);
+    const f32x4 z = noise ? load4<VEC>(noise, a.const_noise ? 4L * g.grp : g.e0, g.nval)
+                          : philox_normal4(a.seed, a.const_noise ? 0ull : a.sample_offset + (uint64_t)g.b, rng_step, g.grp);
+    const bool cond = a.grad != nullptr;
+    const f32x4 grad = cond ? load4<VEC>(a.grad, g.e0, g.nval) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const float s1m = cond && a.kind != GDX_SAMPLER_P ? a.gcoef[idx] : 0.0f;
     f32x4 r;
-    if (a.kind == GDX_SAMPLER_P) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float mean = __fadd_rn(__fmul_rn(c[0], x0[i]), __fmul_rn(c[1], x[i]));
-            if (a.grad && i < nval) mean = __fadd_rn(mean, __fmul_rn(c[3], a.grad[e0 + i]));   // condition_mean: + variance * gradient
-            r[i] = __fadd_rn(mean, __fmul_rn(c[2], z[i]));
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float xs = x0[i];
-            if (a.grad && i < nval) {                         // condition_score: eps - sqrt(1 - alpha_bar) * gradient -> pred_xstart
-                const float e1 = __fdiv_rn(__fsub_rn(__fmul_rn(c[0], x[i]), xs), c[1]);
-                const float e2 = __fsub_rn(e1, __fmul_rn(a.gcoef[idx], a.grad[e0 + i]));
-                xs = __fsub_rn(__fmul_rn(c[0], x[i]), __fmul_rn(c[1], e2));
-            }
-            const float eps = __fdiv_rn(__fsub_rn(__fmul_rn(c[0], x[i]), xs), c[1]);
-            const float mean = __fadd_rn(__fmul_rn(xs, c[2]), __fmul_rn(c[3], eps));
-            r[i] = __fadd_rn(mean, __fmul_rn(c[4], z[i]));
-        }
-    }
-    if (VEC) {
-        *reinterpret_cast<f32x4*>(a.out + e0) = r;
-        if (a.pred) *reinterpret_cast<f32x4*>(a.pred + e0) = x0;
-    } else {
-        for (int i = 0; i < nval; ++i) { a.out[e0 + i] = r[i]; if (a.pred) a.pred[e0 + i] = x0[i]; }
-    }
+    for (int i = 0; i < 4; ++i) r[i] = update_value(a.kind, c, x[i], x0[i], z[i], cond, grad[i], s1m);
+    store4<VEC>(a.out, g.e0, g.nval, r);
+    if (a.pred) store4<VEC>(a.pred, g.e0, g.nval, x0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -160,33 +242,7 @@ __global__ __launch_bounds__(256) void update_kernel(const UpdateDev a) {
 // (both halves under guidance: the same x feeds both passes), plus, on the last step, the sample in the reference
 // layout.  A thread owns a 4 (frames) x 4 (channels) micro-tile: for channel j the four frames t0..t0+3 are exactly
 // Philox group j*T/4 + t0/4 of the pose-layout numbering, so every element gets the very noise value -- and, through
-// update_value(), the very arithmetic -- of update_kernel: the two paths are bit-identical.
-struct UpdateTmDev {
-    int kind, B, J, T, ldx, ldo;
-    const float* coef; int step_index;
-    float* xt;              // [Beff*T][ldx] in / out
-    const float* x0t;       // [Beff*T][ldo]
-    const float* scale;     // [B] or nullptr: guidance on (Beff = 2B)
-    int const_noise;
-    uint64_t seed, sample_offset;
-    uint32_t rng_step;
-    int clip;
-    float* out_pose;        // [B][J][T] or nullptr (last step)
-    void* xt16;             // half modes: the input GEMM's 16-bit operand [Beff*T][ldx], written beside the fp32 state
-    int half_dtype;         // GDX_DTYPE_F16 or GDX_DTYPE_BF16 (the element type of xt16)
-    const float* noise;     // this step's slice of a noise tape, reference layout [B or 1][J][T], or nullptr (Philox)
-};
-
-__device__ __forceinline__ float update_value(int kind, const float* c, float x, float x0, float z) {
-    if (kind == GDX_SAMPLER_P) {
-        const float mean = __fadd_rn(__fmul_rn(c[0], x0), __fmul_rn(c[1], x));
-        return __fadd_rn(mean, __fmul_rn(c[2], z));
-    }
-    const float eps = __fdiv_rn(__fsub_rn(__fmul_rn(c[0], x), x0), c[1]);
-    const float mean = __fadd_rn(__fmul_rn(x0, c[2]), __fmul_rn(c[3], eps));
-    return __fadd_rn(mean, __fmul_rn(c[4], z));
-}
-
+// update_value(), the very arithmetic -- of update_kernel: the two paths are bit-identical.  (UpdateTmDev: gdx_internal.h)
 __global__ __launch_bounds__(256) void update_tm_kernel(const UpdateTmDev a) {
     const int jq_n = (a.J + 3) / 4, tq_n = a.T / 4;
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
@@ -210,14 +266,14 @@ __global__ __launch_bounds__(256) void update_tm_kernel(const UpdateTmDev a) {
         for (int tt = 0; tt < 4; ++tt) {
             const f32x4 u = *reinterpret_cast<const f32x4*>(a.x0t + (urow + row0 + tt) * a.ldo + j0);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) x0[tt][jj] = __fadd_rn(u[jj], __fmul_rn(sc, __fsub_rn(x0[tt][jj], u[jj])));
+            for (int jj = 0; jj < 4; ++jj) x0[tt][jj] = cfg_blend(x0[tt][jj], u[jj], sc);
         }
     }
     if (a.clip) {
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) x0[tt][jj] = x0[tt][jj] < -1.0f ? -1.0f : (x0[tt][jj] > 1.0f ? 1.0f : x0[tt][jj]);
+            for (int jj = 0; jj < 4; ++jj) x0[tt][jj] = clamp1(x0[tt][jj]);
     }
     const uint64_t sample = a.const_noise ? 0ull : a.sample_offset + (uint64_t)b;
     f32x4 r[4];
@@ -270,18 +326,17 @@ __global__ void q_sample_kernel(const float* __restrict__ xs, const float* __res
     if (i >= n) return;
     const long row = t ? (long)t[i / per_sample] : (long)idx;
     const float a = coef[row * 8 + 5], b = coef[row * 8 + 6];
-    out[i] = __fadd_rn(__fmul_rn(a, xs[i]), __fmul_rn(b, nz[i]));
+    out[i] = q_sample_value(a, b, xs[i], nz[i]);
 }
 
 // PLMS pieces (reference gaussian_diffusion.py:995-1079), every product / sum rounded separately in torch's op order.
 // coef row c = coef[t]: c[0] sqrt_recip_alphas_cumprod, c[1] sqrt_recipm1_alphas_cumprod, c[2] sqrt(alpha_bar_prev),
 // c[3] sqrt(1 - alpha_bar_prev), c[7] (t != 0).
-//   kind 0: eps_out = (c0*x - x0) / c1                                        (_predict_eps_from_xstart)
-//   kind 6: out = x0*c2 + c3*e0                                               (improved-Euler predictor)
-//   kind 7: out = c0*x - c1*(((c0*x - x0)/c1) - e1[t]*e0)                     (pred_xstart under condition_score; e0 = gradient)
-//   kind 8: out = c0*x - c1*x0                                                 (pred_xstart from an EPSILON / PREVIOUS_X output)
-//   kind 1..5: eps' = e0 | (3e0 - e1)/2 | (23e0 - 16e1 + 5e2)/12 | (55e0 - 59e1 + 37e2 - 9e3)/24 | (e0 + e1)/2
-//              pred' = c0*x - c1*eps';  out = (pred'*c2 + c3*eps')*nz + x0*(1 - nz)
+//   kind 0: eps_from_xstart                                                   (_predict_eps_from_xstart)
+//   kind 6: ddim_mean(x0, e0)                                                 (improved-Euler predictor)
+//   kind 7: cond_score_xstart with e0 = gradient, e1[t] = sqrt(1 - alpha_bar) (pred_xstart under condition_score)
+//   kind 8: xstart_from_eps(x, x0)                                            (pred_xstart from an EPSILON / PREVIOUS_X output)
+//   kind 1..5: plms_tail(plms_combine(kind, e0, e1, e2, e3)) with keep = x0
 __global__ void plms_kernel(int kind, const float* __restrict__ coef, const int64_t* __restrict__ t, int step_index,
                             const float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ e0,
                             const float* __restrict__ e1, const float* __restrict__ e2, const float* __restrict__ e3,
@@ -290,36 +345,14 @@ __global__ void plms_kernel(int kind, const float* __restrict__ coef, const int6
     if (i >= total) return;
     const long idx = t ? (long)t[i / per_sample] : (long)step_index;
     const float* c = coef + idx * 8;
-    if (kind == 0) {
-        out[i] = __fdiv_rn(__fsub_rn(__fmul_rn(c[0], x[i]), x0[i]), c[1]);
-        return;
+    if (kind == 0) out[i] = eps_from_xstart(c[0], c[1], x[i], x0[i]);
+    else if (kind == 6) out[i] = ddim_mean(c[2], c[3], x0[i], e0[i]);
+    else if (kind == 7) out[i] = cond_score_xstart(c[0], c[1], e1[idx], x[i], x0[i], e0[i]);   // e0 = cond_fn gradient, e1 = sqrt(1 - alpha_bar) table
+    else if (kind == 8) out[i] = xstart_from_eps(c[0], c[1], x[i], x0[i]);   // x0 slot = eps; with the (1/coef1, coef2/coef1) rows, x = xprev, slot = x_t
+    else {
+        const float v1 = kind != 1 ? e1[i] : 0.f, v2 = kind == 3 || kind == 4 ? e2[i] : 0.f, v3 = kind == 4 ? e3[i] : 0.f;
+        out[i] = plms_tail(c, x[i], plms_combine(kind, e0[i], v1, v2, v3), x0[i]);
     }
-    if (kind == 6) {
-        out[i] = __fadd_rn(__fmul_rn(x0[i], c[2]), __fmul_rn(c[3], e0[i]));
-        return;
-    }
-    if (kind == 8) {   // c0*x - c1*x0: _predict_xstart_from_eps (x = x_t, x0 slot = eps) and, with the (1/coef1, coef2/coef1)
-        out[i] = __fsub_rn(__fmul_rn(c[0], x[i]), __fmul_rn(c[1], x0[i]));   // rows, _predict_xstart_from_xprev (x = xprev, slot = x_t)
-        return;
-    }
-    if (kind == 7) {   // condition_score (:452-472): e0 = cond_fn gradient, e1[idx] = sqrt(1 - alpha_bar) table
-        const float eps = __fsub_rn(__fdiv_rn(__fsub_rn(__fmul_rn(c[0], x[i]), x0[i]), c[1]), __fmul_rn(e1[idx], e0[i]));
-        out[i] = __fsub_rn(__fmul_rn(c[0], x[i]), __fmul_rn(c[1], eps));
-        return;
-    }
-    float ep;
-    if (kind == 1) ep = e0[i];
-    else if (kind == 2) ep = __fdiv_rn(__fsub_rn(__fmul_rn(3.0f, e0[i]), e1[i]), 2.0f);
-    else if (kind == 3)
-        ep = __fdiv_rn(__fadd_rn(__fsub_rn(__fmul_rn(23.0f, e0[i]), __fmul_rn(16.0f, e1[i])), __fmul_rn(5.0f, e2[i])), 12.0f);
-    else if (kind == 4)
-        ep = __fdiv_rn(__fsub_rn(__fadd_rn(__fsub_rn(__fmul_rn(55.0f, e0[i]), __fmul_rn(59.0f, e1[i])), __fmul_rn(37.0f, e2[i])),
-                                 __fmul_rn(9.0f, e3[i])), 24.0f);
-    else ep = __fdiv_rn(__fadd_rn(e0[i], e1[i]), 2.0f);
-    const float pred = __fsub_rn(__fmul_rn(c[0], x[i]), __fmul_rn(c[1], ep));
-    const float mean = __fadd_rn(__fmul_rn(pred, c[2]), __fmul_rn(c[3], ep));
-    const float nz = c[7];
-    out[i] = __fadd_rn(__fmul_rn(mean, nz), __fmul_rn(x0[i], __fsub_rn(1.0f, nz)));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -341,60 +374,25 @@ struct PlmsStepDev {
     float *eps_out, *out, *pred;
 };
 
-template <bool VEC>
-__device__ __forceinline__ f32x4 load4(const float* p, long e0, int nval) {
-    if (VEC) return *reinterpret_cast<const f32x4*>(p + e0);
-    f32x4 v;
-    for (int i = 0; i < 4; ++i) v[i] = i < nval ? p[e0 + i] : 0.f;
-    return v;
-}
-template <bool VEC>
-__device__ __forceinline__ void store4(float* p, long e0, int nval, const f32x4 v) {
-    if (VEC) *reinterpret_cast<f32x4*>(p + e0) = v;
-    else for (int i = 0; i < nval; ++i) p[e0 + i] = v[i];
-}
-
 template <int KIND, bool VEC>
 __global__ __launch_bounds__(256) void plms_step_kernel(const PlmsStepDev a) {
     const long grp = (long)blockIdx.x * 256 + threadIdx.x;
     if (grp >= a.groups) return;
-    const int b = blockIdx.y;
-    const long e0 = (long)b * a.per_sample + 4L * grp;
-    const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
-    const long idx = a.t ? a.t[b] : a.step_index;
-    const long idx_e = KIND == 5 ? (a.t_eps ? a.t_eps[b] : a.step_index_eps) : idx;       // row of this launch's eps
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
+    const long e0 = g.e0;
+    const int nval = g.nval;
+    const long idx = a.t ? a.t[g.b] : a.step_index;
+    const long idx_e = KIND == 5 ? (a.t_eps ? a.t_eps[g.b] : a.step_index_eps) : idx;     // row of this launch's eps
     const float* c = a.coef + idx * 8;
     const float* ce = a.coef + idx_e * 8;
 
     const f32x4 x = load4<VEC>(a.x, e0, nval);
-    f32x4 x0 = load4<VEC>(a.x0c, e0, nval);
-    if (a.x0u) {
-        const f32x4 u = load4<VEC>(a.x0u, e0, nval);
-        const float sc = a.scale[b];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x0[i] = __fadd_rn(u[i], __fmul_rn(sc, __fsub_rn(x0[i], u[i])));
-    }
-    if (a.mask) {
-        if (VEC) {
-            const uint32_t m = *reinterpret_cast<const uint32_t*>(a.mask + e0);
-            const f32x4 mo = load4<true>(a.motion, e0, 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if ((m >> (8 * i)) & 0xffu) x0[i] = mo[i];
-        } else {
-            for (int i = 0; i < nval; ++i)
-                if (a.mask[e0 + i]) x0[i] = a.motion[e0 + i];
-        }
-    }
-    if (a.clip) {                                 // torch.clamp semantics: a NaN stays a NaN
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x0[i] = x0[i] < -1.0f ? -1.0f : (x0[i] > 1.0f ? 1.0f : x0[i]);
-    }
+    const f32x4 x0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, e0, nval);
     const f32x4 xe = KIND == 5 ? load4<VEC>(a.x_eps, e0, nval) : x;
     f32x4 eps;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) eps[i] = __fdiv_rn(__fsub_rn(__fmul_rn(ce[0], xe[i]), x0[i]), ce[1]);
-    f32x4 e1, e2, e3;
+    for (int i = 0; i < 4; ++i) eps[i] = eps_from_xstart(ce[0], ce[1], xe[i], x0[i]);
+    f32x4 e1 = {0.f, 0.f, 0.f, 0.f}, e2 = e1, e3 = e1;
     if (KIND == 2 || KIND == 3 || KIND == 4 || KIND == 5) e1 = load4<VEC>(a.e1, e0, nval);
     if (KIND == 3 || KIND == 4) e2 = load4<VEC>(a.e2, e0, nval);
     if (KIND == 4) e3 = load4<VEC>(a.e3, e0, nval);
@@ -402,23 +400,8 @@ __global__ __launch_bounds__(256) void plms_step_kernel(const PlmsStepDev a) {
     f32x4 r;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        if (KIND == 6) {
-            r[i] = __fadd_rn(__fmul_rn(x0[i], c[2]), __fmul_rn(c[3], eps[i]));
-            continue;
-        }
-        float ep;
-        if (KIND == 1) ep = eps[i];
-        else if (KIND == 2) ep = __fdiv_rn(__fsub_rn(__fmul_rn(3.0f, eps[i]), e1[i]), 2.0f);
-        else if (KIND == 3)
-            ep = __fdiv_rn(__fadd_rn(__fsub_rn(__fmul_rn(23.0f, eps[i]), __fmul_rn(16.0f, e1[i])), __fmul_rn(5.0f, e2[i])), 12.0f);
-        else if (KIND == 4)
-            ep = __fdiv_rn(__fsub_rn(__fadd_rn(__fsub_rn(__fmul_rn(55.0f, eps[i]), __fmul_rn(59.0f, e1[i])), __fmul_rn(37.0f, e2[i])),
-                                     __fmul_rn(9.0f, e3[i])), 24.0f);
-        else ep = __fdiv_rn(__fadd_rn(e1[i], eps[i]), 2.0f);
-        const float pred = __fsub_rn(__fmul_rn(c[0], x[i]), __fmul_rn(c[1], ep));
-        const float mean = __fadd_rn(__fmul_rn(pred, c[2]), __fmul_rn(c[3], ep));
-        const float nz = c[7];
-        r[i] = __fadd_rn(__fmul_rn(mean, nz), __fmul_rn(keep[i], __fsub_rn(1.0f, nz)));
+        if (KIND == 6) r[i] = ddim_mean(c[2], c[3], x0[i], eps[i]);
+        else r[i] = plms_tail(c, x[i], plms_combine(KIND, eps[i], e1[i], e2[i], e3[i]), keep[i]);
     }
     if (a.eps_out) store4<VEC>(a.eps_out, e0, nval, eps);
     if (a.pred) store4<VEC>(a.pred, e0, nval, x0);
@@ -478,11 +461,8 @@ __global__ void randn_kernel(float* __restrict__ out, int batch, long per_sample
                              uint64_t sample_offset, uint32_t step) {
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= groups * batch) return;
-    const int b = gid / groups;
-    const uint32_t grp = gid - (long)b * groups;
-    const f32x4 z = philox_normal4(seed, sample_offset + (uint64_t)b, step, grp);
-    const long e0 = (long)b * per_sample + 4L * grp;
-    for (int i = 0; i < 4 && 4L * grp + i < per_sample; ++i) out[e0 + i] = z[i];
+    const Group g = group_of<false>(gid, groups, per_sample);
+    store4<false>(out, g.e0, g.nval, philox_normal4(seed, sample_offset + (uint64_t)g.b, step, g.grp));
 }
 
 // classifier-free guidance blend (model/cfg_sampler.py:28), op order as the reference
@@ -492,8 +472,7 @@ __global__ void cfg_blend_kernel(const float* __restrict__ c, const float* __res
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const float sc = scale[i / per_sample];
-    const float diff = __fsub_rn(c[i], u[i]);
-    out[i] = __fadd_rn(u[i], __fmul_rn(sc, diff));
+    out[i] = cfg_blend(c[i], u[i], sc);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -507,24 +486,15 @@ __global__ __launch_bounds__(256) void bpd_xt_kernel(const float* __restrict__ x
                                                      float* __restrict__ xt_out) {
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= groups * batch) return;
-    const int b = gid / groups;
-    const uint32_t grp = gid - (long)b * groups;
+    const Group g = group_of<VEC>(gid, groups, per_sample);
     const float sa = coef[(long)idx * 8 + 5], s1m = coef[(long)idx * 8 + 6];
-    const f32x4 z = philox_normal4(seed, sample_offset + (uint64_t)b, step, grp);
-    const long e0 = (long)b * per_sample + 4L * grp;
-    if (VEC) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(x0 + e0);
-        f32x4 r;
+    const f32x4 z = philox_normal4(seed, sample_offset + (uint64_t)g.b, step, g.grp);
+    const f32x4 x = load4<VEC>(x0, g.e0, g.nval);
+    f32x4 r;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = __fadd_rn(__fmul_rn(sa, x[i]), __fmul_rn(s1m, z[i]));
-        *reinterpret_cast<f32x4*>(z_out + e0) = z;
-        *reinterpret_cast<f32x4*>(xt_out + e0) = r;
-    } else {
-        for (int i = 0; i < 4 && 4L * grp + i < per_sample; ++i) {
-            z_out[e0 + i] = z[i];
-            xt_out[e0 + i] = __fadd_rn(__fmul_rn(sa, x0[e0 + i]), __fmul_rn(s1m, z[i]));
-        }
-    }
+    for (int i = 0; i < 4; ++i) r[i] = q_sample_value(sa, s1m, x[i], z[i]);
+    store4<VEC>(z_out, g.e0, g.nval, z);
+    store4<VEC>(xt_out, g.e0, g.nval, r);
 }
 
 struct BpdDev {
@@ -576,9 +546,7 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
         if (grp >= a.groups) break;
         const long e0 = base + 4L * grp;
         const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
-        f32x4 x0;
-        if (VEC) x0 = *reinterpret_cast<const f32x4*>(a.x0 + e0);
-        else for (int i = 0; i < 4; ++i) x0[i] = i < nval ? a.x0[e0 + i] : 0.f;
+        const f32x4 x0 = load4<VEC>(a.x0, e0, nval);
         if (a.prior) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -587,19 +555,12 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
             }
             continue;
         }
-        f32x4 xt, p, z, mm;
-        if (VEC) {
-            xt = *reinterpret_cast<const f32x4*>(a.xt + e0);
-            p = *reinterpret_cast<const f32x4*>(a.oc + e0);
-        } else {
-            for (int i = 0; i < 4; ++i) { xt[i] = i < nval ? a.xt[e0 + i] : 0.f; p[i] = i < nval ? a.oc[e0 + i] : 0.f; }
-        }
+        const f32x4 xt = load4<VEC>(a.xt, e0, nval);
+        f32x4 p = load4<VEC>(a.oc, e0, nval);
         if (a.ou) {
-            f32x4 u;
-            if (VEC) u = *reinterpret_cast<const f32x4*>(a.ou + e0);
-            else for (int i = 0; i < 4; ++i) u[i] = i < nval ? a.ou[e0 + i] : 0.f;
+            const f32x4 u = load4<VEC>(a.ou, e0, nval);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) p[i] = __fadd_rn(u[i], __fmul_rn(sc, __fsub_rn(p[i], u[i])));
+            for (int i = 0; i < 4; ++i) p[i] = cfg_blend(p[i], u[i], sc);
         }
         if (a.mask) {
 #pragma unroll
@@ -608,20 +569,15 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
         }
         if (a.clip) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) p[i] = p[i] < -1.0f ? -1.0f : (p[i] > 1.0f ? 1.0f : p[i]);
+            for (int i = 0; i < 4; ++i) p[i] = clamp1(p[i]);
         }
-        if (a.z) {
-            if (VEC) z = *reinterpret_cast<const f32x4*>(a.z + e0);
-            else for (int i = 0; i < 4; ++i) z[i] = i < nval ? a.z[e0 + i] : 0.f;
-        } else {
-            z = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        const f32x4 z = a.z ? load4<VEC>(a.z, e0, nval) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 mm;
         if (a.mean) {
-            if (VEC) mm = *reinterpret_cast<const f32x4*>(a.mean + e0);
-            else for (int i = 0; i < 4; ++i) mm[i] = i < nval ? a.mean[e0 + i] : 0.f;
+            mm = load4<VEC>(a.mean, e0, nval);
         } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) mm[i] = __fadd_rn(__fmul_rn(pm1, p[i]), __fmul_rn(pm2, xt[i]));
+            for (int i = 0; i < 4; ++i) mm[i] = posterior_mean(pm1, pm2, p[i], xt[i]);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -635,12 +591,12 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
                                                  : logf(fmaxf(__fsub_rn(cp, cm), 1e-12f)));
                 v = -lp;
             } else {                // normal_kl (losses.py:33-39)
-                const float mt = __fadd_rn(__fmul_rn(pm1, x0[i]), __fmul_rn(pm2, xt[i]));
+                const float mt = posterior_mean(pm1, pm2, x0[i], xt[i]);
                 const float dm = __fsub_rn(mt, mm[i]);
                 v = __fmul_rn(0.5f, __fadd_rn(klc, __fmul_rn(__fmul_rn(dm, dm), e2)));
             }
             const float dx = __fsub_rn(p[i], x0[i]);
-            const float eps = __fdiv_rn(__fsub_rn(__fmul_rn(sra, xt[i]), p[i]), srm1);
+            const float eps = eps_from_xstart(sra, srm1, xt[i], p[i]);
             const float de = __fsub_rn(eps, z[i]);
             if (i < nval) {
                 s_vb = __fadd_rn(s_vb, v);
@@ -648,10 +604,7 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
                 s_e = __fadd_rn(s_e, __fmul_rn(de, de));
             }
         }
-        if (a.pred) {
-            if (VEC) *reinterpret_cast<f32x4*>(a.pred + e0) = p;
-            else for (int i = 0; i < nval; ++i) a.pred[e0 + i] = p[i];
-        }
+        if (a.pred) store4<VEC>(a.pred, e0, nval, p);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -703,22 +656,29 @@ hipError_t launch_advance_state(int* st, hipStream_t s) {
 }
 }  // namespace gdx
 
+// 0, or -1 with `msg` ("<entry>: launch failed") recorded, from the status of the launch just made
+static int launch_status(const char* msg) { return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_(msg); }
+
+// May a pose-layout kernel take its VEC = true instantiation: whole groups only, and every operand it reads or writes by
+// group (nullptr = absent) aligned for the group access -- 16 bytes for floats, 4 for mask bytes.
+static inline bool group_aligned(const float* p) { return !((uintptr_t)p & 15); }
+static inline bool group_aligned(const uint8_t* p) { return !((uintptr_t)p & 3); }
+template <typename... P>
+static bool vec_ok(long per_sample, const P*... p) { return per_sample % 4 == 0 && (group_aligned(p) && ...); }
+
 static int sampler_update_impl(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
 
 // internal (api.hip, gdx_sample_loop): one step of the token-major fast path (update_tm_kernel)
-int gdx_sampler_update_tm_(int kind, int B, int J, int T, int ldx, int ldo, const float* coef, int step_index, float* xt,
-                           const float* x0t, const float* scale, int const_noise, uint64_t seed, uint64_t sample_offset,
-                           uint32_t rng_step, int clip, float* out_pose, void* xt16, int half_dtype, void* stream, const float* noise) {
+int gdx_sampler_update_tm_(const gdx::UpdateTmDev& d, void* stream) {
     using namespace gdx;
-    if (!coef || !xt || !x0t || T % 4 || ldx % 4 || ldo % 4 || ldx < (J + 3) / 4 * 4 || ldo < (J + 3) / 4 * 4)
+    const int jpad = (d.J + 3) / 4 * 4;
+    if (!d.coef || !d.xt || !d.x0t || d.T % 4 || d.ldx % 4 || d.ldo % 4 || d.ldx < jpad || d.ldo < jpad)
         return gdx_set_error_("gdx_sampler_update_tm_: bad argument");
-    if (noise && ((uintptr_t)noise & 15)) return gdx_set_error_("gdx_sampler_update_tm_: noise tape not 16-byte aligned");
-    UpdateTmDev d{kind, B, J, T, ldx, ldo, coef, step_index, xt, x0t, scale, const_noise, seed, sample_offset, rng_step, clip, out_pose,
-                  xt16, half_dtype, noise};
-    const long total = (long)B * (T / 4) * ((J + 3) / 4);
+    if (d.noise && ((uintptr_t)d.noise & 15)) return gdx_set_error_("gdx_sampler_update_tm_: noise tape not 16-byte aligned");
+    const long total = (long)d.B * (d.T / 4) * (jpad / 4);
     if (total == 0) return 0;
     hipLaunchKernelGGL(update_tm_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, d);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_sampler_update_tm_: launch failed");
+    return launch_status("gdx_sampler_update_tm_: launch failed");
 }
 
 extern "C" int gdx_sampler_update(const gdx_update_args_t* a, void* stream) {
@@ -752,11 +712,11 @@ static int sampler_update_impl(const gdx_update_args_t* a, const int* state, lon
     const long total = d.groups * d.batch;
     if (total == 0) return 0;
     const dim3 grid((total + 255) / 256), block(256);
-    if (d.per_sample % 4 == 0)
+    if (vec_ok(d.per_sample, d.x, d.x0c, d.x0u, d.mask, d.motion, d.noise, d.grad, d.out, d.pred))
         hipLaunchKernelGGL(update_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
     else
         hipLaunchKernelGGL(update_kernel<false>, grid, block, 0, (hipStream_t)stream, d);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_sampler_update: launch failed");
+    return launch_status("gdx_sampler_update: launch failed");
 }
 
 extern "C" int gdx_q_sample(const float* x_start, const float* noise, const float* coef, int32_t idx, int64_t count,
@@ -765,7 +725,7 @@ extern "C" int gdx_q_sample(const float* x_start, const float* noise, const floa
     if (count == 0) return 0;
     hipLaunchKernelGGL(gdx::q_sample_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, x_start,
                        noise, coef, idx, (const int64_t*)nullptr, (long)count, (long)count, out);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_q_sample: launch failed");
+    return launch_status("gdx_q_sample: launch failed");
 }
 
 extern "C" int gdx_q_sample_t(const float* x_start, const float* noise, const float* coef, const int64_t* t,
@@ -775,7 +735,7 @@ extern "C" int gdx_q_sample_t(const float* x_start, const float* noise, const fl
     if (count <= 0) return 0;
     hipLaunchKernelGGL(gdx::q_sample_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, x_start,
                        noise, coef, 0, t, (long)per_sample, count, out);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_q_sample_t: launch failed");
+    return launch_status("gdx_q_sample_t: launch failed");
 }
 
 extern "C" int gdx_masked_l2(const float* a, const float* b, const uint8_t* mask, float* out, int32_t batch,
@@ -784,7 +744,7 @@ extern "C" int gdx_masked_l2(const float* a, const float* b, const uint8_t* mask
     if (batch <= 0 || njoints <= 0 || frames <= 0) return 0;
     hipLaunchKernelGGL(gdx::masked_l2_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, a, b, mask, out, njoints,
                        frames);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_masked_l2: launch failed");
+    return launch_status("gdx_masked_l2: launch failed");
 }
 
 extern "C" int gdx_plms_update(const gdx_plms_args_t* a, void* stream) {
@@ -801,10 +761,8 @@ extern "C" int gdx_plms_update(const gdx_plms_args_t* a, void* stream) {
     hipLaunchKernelGGL(gdx::plms_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, k, a->coef, a->t,
                        a->step_index, a->x, a->pred_xstart, a->eps[0], a->eps[1], a->eps[2], a->eps[3], a->out,
                        (long)a->per_sample, total);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_plms_update: launch failed");
+    return launch_status("gdx_plms_update: launch failed");
 }
-
-static inline bool aligned16(const void* p) { return !((uintptr_t)p & 15); }
 
 template <bool VEC>
 static void launch_plms_step(int kind, dim3 grid, hipStream_t s, const gdx::PlmsStepDev& d) {
@@ -843,13 +801,12 @@ extern "C" int gdx_plms_step(const gdx_plms_step_args_t* a, void* stream) {
     d.e1 = older > 0 ? a->eps_hist[0] : nullptr; d.e2 = older > 1 ? a->eps_hist[1] : nullptr;
     d.e3 = older > 2 ? a->eps_hist[2] : nullptr; d.pred_prev = k == 5 ? a->pred_prev : nullptr;
     d.clip = a->clip_denoised; d.eps_out = a->eps_out; d.out = a->out; d.pred = a->pred_xstart;
-    const bool vec = d.per_sample % 4 == 0 && aligned16(d.x) && aligned16(d.x_eps) && aligned16(d.x0c) && aligned16(d.x0u) &&
-                     !((uintptr_t)d.mask & 3) && aligned16(d.motion) && aligned16(d.e1) && aligned16(d.e2) && aligned16(d.e3) &&
-                     aligned16(d.pred_prev) && aligned16(d.eps_out) && aligned16(d.out) && aligned16(d.pred);
+    const bool vec = vec_ok(d.per_sample, d.x, d.x_eps, d.x0c, d.x0u, d.mask, d.motion, d.e1, d.e2, d.e3, d.pred_prev, d.eps_out, d.out,
+                            d.pred);
     const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
     if (vec) launch_plms_step<true>(k, grid, (hipStream_t)stream, d);
     else launch_plms_step<false>(k, grid, (hipStream_t)stream, d);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_plms_step: launch failed");
+    return launch_status("gdx_plms_step: launch failed");
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,
@@ -859,7 +816,7 @@ extern "C" int gdx_postprocess(const float* x, const double* mean, const double*
     if (total <= 0) return 0;
     hipLaunchKernelGGL(gdx::postprocess_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, mean,
                        stdv, pos, rot, n_joints, frames, total);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_postprocess: launch failed");
+    return launch_status("gdx_postprocess: launch failed");
 }
 
 extern "C" int gdx_randn(float* out, int32_t batch, int64_t per_sample, uint64_t philox_seed, uint64_t sample_offset,
@@ -870,7 +827,7 @@ extern "C" int gdx_randn(float* out, int32_t batch, int64_t per_sample, uint64_t
     if (total == 0) return 0;
     hipLaunchKernelGGL(gdx::randn_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, batch,
                        (long)per_sample, groups, philox_seed, sample_offset, rng_step);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_randn: launch failed");
+    return launch_status("gdx_randn: launch failed");
 }
 
 extern "C" int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream) {
@@ -897,16 +854,15 @@ extern "C" int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream) {
     d.mask = a->inpaint_mask; d.motion = a->inpaint_motion; d.mean = a->model_mean;
     d.clip = a->clip_denoised; d.prior = a->prior; d.prior_lv = a->prior_log_variance;
     d.pred = a->prior ? nullptr : a->pred_xstart; d.part = a->workspace;
-    const bool vec = d.per_sample % 4 == 0 && aligned16(d.x0) && aligned16(d.xt) && aligned16(d.z) && aligned16(d.oc) &&
-                     aligned16(d.ou) && aligned16(d.mean) && aligned16(d.pred);
+    const bool vec = vec_ok(d.per_sample, d.x0, d.xt, d.z, d.oc, d.ou, d.mean, d.pred);   // mask / motion: read per element
     const dim3 grid(d.chunks, a->batch), block(256);
     if (vec) hipLaunchKernelGGL(bpd_terms_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
     else hipLaunchKernelGGL(bpd_terms_kernel<false>, grid, block, 0, (hipStream_t)stream, d);
-    if (hipGetLastError() != hipSuccess) return gdx_set_error_("gdx_bpd_terms: launch failed");
+    if (launch_status("gdx_bpd_terms: launch failed")) return -1;
     hipLaunchKernelGGL(bpd_finish_kernel, dim3((a->batch * 3 + 63) / 64), dim3(64), 0, (hipStream_t)stream, d.part, d.chunks,
                        d.per_sample, a->batch, a->vb, a->prior ? nullptr : a->xstart_mse, a->prior ? nullptr : a->mse, a->ld,
                        a->col);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_bpd_terms: launch failed");
+    return launch_status("gdx_bpd_terms: launch failed");
 }
 
 // internal (api.hip, gdx_bpd_loop): x_t and the stored Philox noise of one step (bpd_xt_kernel)
@@ -916,11 +872,11 @@ int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per
     const long groups = (per_sample + 3) / 4, total = groups * batch;
     if (total == 0) return 0;
     const dim3 grid((total + 255) / 256), block(256);
-    if (per_sample % 4 == 0 && aligned16(x0) && aligned16(z_out) && aligned16(xt_out))
+    if (vec_ok(per_sample, x0, z_out, xt_out))
         hipLaunchKernelGGL(bpd_xt_kernel<true>, grid, block, 0, (hipStream_t)stream, x0, coef, idx, batch, per_sample, groups, seed,
                            sample_offset, step, z_out, xt_out);
     else
         hipLaunchKernelGGL(bpd_xt_kernel<false>, grid, block, 0, (hipStream_t)stream, x0, coef, idx, batch, per_sample, groups,
                            seed, sample_offset, step, z_out, xt_out);
-    return hipGetLastError() == hipSuccess ? 0 : gdx_set_error_("gdx_bpd_loop: x_t launch failed");
+    return launch_status("gdx_bpd_loop: x_t launch failed");
 }

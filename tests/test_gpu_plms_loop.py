@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_err, weights_from
+from misaligned import shifted as _shifted
 from test_gpu_parity import LOOP_TOL, TINY, _diffusion, build_model, dev
 
 pytestmark = pytest.mark.gpu
@@ -33,15 +34,6 @@ def _three_launches(kind, coef, x, oc, ou, scale, mask, motion, clip, t, hist, x
     if kind == 6:
         return E.plms_update(6, coef, t, None, pred, eps=[eps]), eps, pred
     return E.plms_update(kind, coef, t, x, pred, eps=[eps] + hist[:kind - 1]), eps, pred
-
-
-def _shifted(t):
-    """The same values one float off 16-byte alignment (the scalar path of the kernel)."""
-    buf = torch.empty(t.numel() + 1, device=t.device, dtype=t.dtype)
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 @pytest.mark.parametrize("J,T", [(263, 196), (150, 60), (7, 9)])
