@@ -1,5 +1,6 @@
 // libgdx.so host side: handle, workspace, the per-step kernel sequence of the
-// denoiser (V1 = reference model/mdm_old.py:84-122, V2 = model/mdm.py:105-224) and the sampling
+// denoiser (V1 = reference model/mdm_old.py:84-122, V2 = model/mdm.py:105-224; forward_core, once for the three compute modes
+// on top of linear / attend / add_norm) and the sampling
 // loops (diffusion/gaussian_diffusion.py:598-730, 879-993).  C ABI in include/gdx.h; the handle's weights are in weights.hip.
 #include "gdx_host.h"
 
@@ -124,29 +125,33 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
         return 0;
     };
     auto A = [&](float** p, size_t n) { return raw((void**)p, n * sizeof(float)); };
-    if (A(&h->xa, N * d) || A(&h->addend, N * d) || A(&h->seed_cat, B2 * d) || A(&h->temb_in, B2 * d) ||
+    // the sides of an activation pair this mode uses; every fp32 side is allocated before the first 16-bit one, in the order below
+    // (the order of the guard zones gdx_check_guards reports)
+    auto act = [&](Act& a, size_t n, bool want_f32, bool want_16) {
+        return (want_f32 && A(&a.f, n)) || (want_16 && raw((void**)&a.h, n * 2));
+    };
+    const bool half = h->f16, f32 = !half, v2 = h->cfg.arch == GDX_ARCH_MDM;
+    const bool res32 = f32 || h->stream32;                         // the residual stream is fp32 (add_norm)
+    if (act(h->xa, N * d, true, false) || A(&h->addend, N * d) || A(&h->seed_cat, B2 * d) || A(&h->temb_in, B2 * d) ||
         A(&h->temb_h, B2 * d) || A(&h->temb, B2 * d) || A(&h->coa, B2 * d) || A(&h->c2, (B2 + 1) * d) ||
         A(&h->c2_seed, B2 * d) ||
         A(&h->x0, B2 * h->J * (size_t)frames))
         return -1;
-    // fp32 activation buffers of the fp32 mode (the fp16 mode keeps its stream in the *16 buffers below)
-    if (!h->f16 && (A(&h->xb, N * d) || A(&h->qkv, N * 3 * d) || A(&h->ctx, N * d) || A(&h->tmp, N * d) || A(&h->ffb, N * h->ff)))
+    if (act(h->xb, N * d, res32, false) || act(h->qkv, N * 3 * d, f32, false) || act(h->ctx, N * d, f32, false) ||
+        act(h->tmp, N * d, res32, false) || act(h->ffb, N * h->ff, f32, false))
         return -1;
-    if (h->f16 && h->stream32 && (A(&h->xb, N * d) || A(&h->tmp, N * d))) return -1;   // fp32 residual stream of the 16-bit modes
     h->ldo = round_up(h->J, 64);
     const size_t NT = B2 * frames + GDX_ROW_PAD;
-    if (A(&h->x0t, NT * h->ldo)) return -1;
-    if (!h->f16 && (A(&h->xt, NT * round_up(h->J, 32)) || A(&h->xc, NT * d))) return -1;
-    if (h->f16 && A(&h->xt, NT * round_up(h->J, 64))) return -1;      // fp32 loop state of the token-major fast path (gdx_sample_loop)
-    if (h->cfg.arch == GDX_ARCH_MDM && A(&h->xseq, NT * d)) return -1;
-    if (h->cfg.arch == GDX_ARCH_MDM && !h->f16 && A(&h->emb_pose, NT * d)) return -1;
-    if (h->f16) {
-        auto H16 = [&](_Float16** p, size_t n) { return raw((void**)p, n * 2); };
-        if (H16(&h->xt16, NT * round_up(h->J, 64)) || H16(&h->xa16, N * d) || H16(&h->xb16, N * d) ||
-            H16(&h->qkv16, N * 3 * d) || H16(&h->ctx16, N * d) || H16(&h->tmp16, N * d) || H16(&h->ffb16, N * h->ff) || H16(&h->xc16, NT * d))
-            return -1;
-        if (h->cfg.arch == GDX_ARCH_MDM && (H16(&h->emb16, NT * d) || H16(&h->xseq16, NT * d))) return -1;
-    }
+    const size_t ldx = round_up(h->J, half ? 64 : 32);             // row stride of xt: the K padding of the input GEMM's weight
+    // xt.f in the 16-bit modes: the fp32 loop state of the token-major fast path (gdx_sample_loop)
+    if (A(&h->x0t, NT * h->ldo) || act(h->xt, NT * ldx, true, false) || act(h->xc, NT * d, f32, false) ||
+        act(h->xseq, NT * d, v2, false) || act(h->emb, NT * d, v2 && f32, false))
+        return -1;
+    if (act(h->xt, NT * ldx, false, half) || act(h->xa, N * d, false, half) || act(h->xb, N * d, false, half) ||
+        act(h->qkv, N * 3 * d, false, half) || act(h->ctx, N * d, false, half) || act(h->tmp, N * d, false, half) ||
+        act(h->ffb, N * h->ff, false, half) || act(h->xc, NT * d, false, half) || act(h->emb, NT * d, false, half && v2) ||
+        act(h->xseq, NT * d, false, half && v2))
+        return -1;
     if (h->keep_taps) {
         h->taps.resize(h->L + 1);
         for (auto& t : h->taps)
@@ -156,17 +161,19 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     return 0;
 }
 
+// gdx_set_guards / gdx_set_keep_taps: the flag shapes the workspace, so a change re-prepares it at the current shape
+static int set_workspace_flag(gdx_model* h, bool& flag, bool on) {
+    if (flag == on) return 0;
+    flag = on;
+    const int B = h->B, T = h->T;
+    if (!B) return 0;
+    h->B = 0;
+    return gdx_prepare(h, B, T);
+}
+
 extern "C" int gdx_set_guards(gdx_handle_t h, int32_t on) {
     if (!h) return fail("gdx_set_guards: null handle");
-    if (h->guards != (on != 0)) {
-        h->guards = on != 0;
-        const int B = h->B, T = h->T;
-        if (B) {
-            h->B = 0;
-            return gdx_prepare(h, B, T);
-        }
-    }
-    return 0;
+    return set_workspace_flag(h, h->guards, on != 0);
 }
 
 extern "C" int gdx_check_guards(gdx_handle_t h, int64_t* bad_bytes, int32_t* first_bad_zone, void* stream) {
@@ -188,15 +195,7 @@ extern "C" int gdx_check_guards(gdx_handle_t h, int64_t* bad_bytes, int32_t* fir
 
 extern "C" int gdx_set_keep_taps(gdx_handle_t h, int32_t keep) {
     if (!h) return fail("gdx_set_keep_taps: null handle");
-    if (h->keep_taps != (keep != 0)) {
-        h->keep_taps = keep != 0;
-        const int B = h->B, T = h->T;
-        if (B) {
-            h->B = 0;
-            return gdx_prepare(h, B, T);
-        }
-    }
-    return 0;
+    return set_workspace_flag(h, h->keep_taps, keep != 0);
 }
 
 extern "C" int gdx_get_tap(gdx_handle_t h, int32_t which, float* out, int64_t count, void* stream) {
@@ -274,11 +273,66 @@ hipError_t gdx::launch_local_attention_any(int dtype, const float* xseq, const _
     return HFN(bf, launch_local_attention, xseq, cosT, sinT, enc, enc16, B, T, d, heads, window, s);
 }
 
-// The per-step kernel sequence.  temb: [*, d] rows (row stride tstride, 0 = shared by the batch).
-// Writes x0 for Beff samples into x0_out ([Beff, J, T]).
-static int forward_core_f16(gdx_model* h, const float* x, const float* temb, int tstride, const float* c2t, int mode,
-                            float* x0_out, hipStream_t s, const int* state, bool tm = false);
+// ---- the per-step kernel sequence: three helpers that hide the compute mode, and the sequence itself, written once ----
 
+// One GEMM launch, out = act(in W^T + bias + R + V); rowmap: frames into rows (b, t + 1) of [B, T+1, d], token 0 skipped
+struct Terms {
+    const float* bias = nullptr;
+    const float* R = nullptr; int ldr = 0;   // fp32 per-output-row term
+    const float* V = nullptr; int ldv = 0;   // fp32 per-sample vector
+    bool gelu = false, rowmap = false;
+};
+// fp32 mode: in.f -> out.f through gemm().  16-bit modes: gemmh.hip reads in.h ([M][kpad16] halves with exactly M readable rows)
+// and writes each side of `out` that is given.  Rows of `in` are W's padded K wide, rows of `out` ldc.
+static int linear(gdx_model* h, const Act& in, const Packed& W, const Terms& t, Act out, int ldc, int M, int N, hipStream_t s) {
+    if (!h->f16) {
+        const int ep = t.gelu ? EPI_GELU : t.R && t.V ? EPI_RES_VEC : t.R ? EPI_RES : EPI_BIAS;
+        const GemmParams p{in.f, W.kpad, W.w, W.kpad, t.bias, t.R, t.ldr, t.V, t.ldv, out.f, ldc, M, N, W.kpad, h->T};
+        return gemm(t.rowmap ? OUT_TOKROWS : OUT_ROWS, ep, p, s);
+    }
+    const size_t ab = (size_t)M * W.kpad16 * 2, wb = (size_t)W.npad16 * W.kpad16 * 2;
+    if (ab >= (1ull << 31) || wb >= (1ull << 31)) return fail("gemm_f16: an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
+    if (N > W.npad16) return fail("gemm_f16: N exceeds the packed weight");
+    GemmHParams p{in.h, W.kpad16, W.w16, W.kpad16, (int)ab, (int)wb, t.bias, t.R, t.ldr, t.V, t.ldv, out.f, out.f ? ldc : 0,
+                  out.h, out.h ? ldc : 0, M, N, W.kpad16, h->T, t.rowmap, t.gelu};
+    hipError_t e = HFN(h->bf16, launch_gemmh, p, s);
+    if (e != hipSuccess) return fail(std::string("launch_gemmh: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// Self-attention of Beff samples: qkv -> ctx
+static int attend(gdx_model* h, int Beff, hipStream_t s) {
+    if (h->f16)
+        HIPCHK(HFN(h->bf16, launch_attentionh, h->qkv.h, h->ctx.h, Beff, h->S, h->H, h->d, h->rows_alloc, s));
+    else if (attention3_supported(h->S, h->H, h->d))
+        HIPCHK(launch_attention3(h->qkv.f, h->ctx.f, Beff, h->S, h->H, h->d, s));
+    else                                              // other head dims / more than 256 tokens: the general 32 x 32-block kernel
+        HIPCHK(launch_attention(h->qkv.f, h->ctx.f, Beff, h->S, h->H, h->d, s));
+    return 0;
+}
+
+// out = LayerNorm(resid + Linear(in)) over N token rows, through h->tmp: into *out (if given) and, without token 0 of every
+// sample, into *compact (if given); each side of them that is named is written.  The one place that knows where the residual is
+// added.  fp32 residual stream (the fp32 mode, and the 16-bit modes under stream32): in the GEMM epilogue (prefetched one tile
+// ahead, gemm2.hip), which writes fp32; the LayerNorm writes the fp32 stream and / or the 16-bit copy the next GEMM reads.
+// 16-bit stream: the GEMM rounds its output to 16 bits and the LayerNorm adds the 16-bit residual.
+static int add_norm(gdx_model* h, const Act& in, const Packed& W, const Act& resid, const float* gamma, const float* beta,
+                    const Act* out, const Act* compact, int N, hipStream_t s) {
+    const int d = h->d;
+    const bool res32 = !h->f16 || h->stream32;
+    if (res32 ? linear(h, in, W, {.bias = W.bias, .R = resid.f, .ldr = d}, Act{h->tmp.f, nullptr}, d, N, d, s)
+              : linear(h, in, W, {.bias = W.bias}, Act{nullptr, h->tmp.h}, d, N, d, s))
+        return -1;
+    for (const Act* o : {out, compact}) {
+        if (!o) continue;
+        const int cS = o == compact ? h->S : 0;
+        if (res32) HIPCHK(HFN(h->bf16, launch_layernorm, h->tmp.f, nullptr, gamma, beta, o->f, o->h, N, d, cS, s));
+        else HIPCHK(HFN(h->bf16, launch_layernorm_f16, h->tmp.h, resid.h, gamma, beta, o->h, o->f, N, d, cS, s));
+    }
+    return 0;
+}
+
+// The denoiser: x0 for Beff samples into x0_out ([Beff, J, T]).  temb: [*, d] rows (row stride tstride, 0 = shared by the batch).
 // c2t (V2 only): W_coa * temb rows with the same row stride as temb -- the timestep half of the coarse slice of
 // project_to_lat (model/mdm.py:154-169), computed by the caller with the row-independent small_linear kernel: per
 // sample in gdx_forward, once per kept step in gdx_sample_loop, hence the same bits on both sides of the seam.
@@ -286,162 +340,62 @@ static int forward_core_f16(gdx_model* h, const float* x, const float* temb, int
 // read from device memory (state[0]) by the conditioning-token kernel.
 // tm (gdx_sample_loop's token-major fast path): the pose operand is already in h->xt and the prediction is left in h->x0t,
 // both token-major -- neither transpose runs (x / x0_out unused).
+// 16-bit modes: GEMM and attention operands are 16-bit, and so is the residual stream unless stream32; every accumulation (MFMA,
+// the terms of the GEMM epilogues, LayerNorm statistics, softmax) is fp32, and so are the two boundary tensors: the pose tensor
+// read by the input transpose and the x0 prediction.
 static int forward_core(gdx_model* h, const float* x, const float* temb, int tstride, const float* c2t, int mode,
                         float* x0_out, hipStream_t s, const int* state = nullptr, bool tm = false) {
-    if (h->f16) return forward_core_f16(h, x, temb, tstride, c2t, mode, x0_out, s, state, tm);
     const int B = h->B, T = h->T, S = h->S, d = h->d, J = h->J;
     const int Beff = mode == GDX_CFG ? 2 * B : B;
     const float* seed_emb = mode == GDX_UNCOND ? h->seed_cat + (size_t)B * d : h->seed_cat;
     const int N = Beff * S;
-    GemmParams p;
-    // pose tensor [B, J, 1, T] -> token-major [Beff*T, Jpad] once (CFG: the same x feeds both halves)
-    const int Jp = h->in_x.kpad;
-    if (!tm) HIPCHK(launch_transpose_in(x, h->xt, Beff, B, J, T, Jp, s));
+    // the encoder stream as the sublayers write it: in the 16-bit stream its fp32 side only for the parity taps
+    const Act xa{!h->f16 || h->stream32 || h->keep_taps ? h->xa.f : nullptr, h->xa.h};
+    // pose tensor [B, J, 1, T] -> token-major [Beff*T, Jpad] once (CFG: the same x feeds both halves); tm: the update kernel wrote it
+    if (!tm && !h->f16) HIPCHK(launch_transpose_in(x, h->xt.f, Beff, B, J, T, h->in_x.kpad, s));
+    if (!tm && h->f16) HIPCHK(HFN(h->bf16, launch_transpose_in_f16, x, h->xt.h, Beff, B, J, T, h->in_x.kpad16, s));
     if (h->cfg.arch == GDX_ARCH_MDM_OLD) {
-        HIPCHK(launch_token0(temb, tstride, seed_emb, h->pe, h->xa, nullptr, nullptr, nullptr, nullptr, state, Beff, B, S, d, s));
+        HIPCHK(HFN(h->bf16, launch_token0, temb, tstride, seed_emb, h->pe, h->xa.f, h->xa.h, nullptr, nullptr, nullptr, state, Beff, B, S, d, s));
         // frames -> rows (b, t+1) of the encoder input, + hoisted MFCC/bias/PE term      (model/mdm_old.py:104-112)
-        p = GemmParams{h->xt, Jp, h->in_x.w, h->in_x.kpad, nullptr, h->addend, d, nullptr, 0, h->xa, d, Beff * T, d, Jp, T};
-        if (gemm(OUT_TOKROWS, EPI_RES, p, s)) return -1;
+        if (linear(h, h->xt, h->in_x, {.R = h->addend, .ldr = d, .rowmap = true}, xa, d, Beff * T, d, s)) return -1;
     } else {
         // coarse slice of project_to_lat = W_coa temb (c2t, from the caller) + W_coa seed_emb (c2_seed, per conditioning)
         if (!c2t) return fail("forward_core: V2 needs the W_coa * temb rows");
         const float* c2s = mode == GDX_UNCOND ? h->c2_seed + (size_t)B * d : h->c2_seed;
-        HIPCHK(launch_token0(temb, tstride, seed_emb, nullptr, h->xa, nullptr, c2t, c2s, h->c2, state, Beff, B, S, d, s));
-        p = GemmParams{h->xt, Jp, h->in_x.w, h->in_x.kpad, h->in_x.bias, nullptr, 0, nullptr, 0, h->emb_pose, d, Beff * T, d, Jp, T};
-        if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;
-        p = GemmParams{h->emb_pose, d, h->proj_pose.w, h->proj_pose.kpad, nullptr, h->addend, d, h->c2, d, h->xseq, d, Beff * T, d, d, T};
-        if (gemm(OUT_ROWS, EPI_RES_VEC, p, s)) return -1;
-        HIPCHK(launch_local_attention_any(GDX_DTYPE_F32, h->xseq, nullptr, h->rope_cos, h->rope_sin, h->xa, nullptr, Beff, T, d,
-                                          h->cfg.cl_head, h->cfg.window, s));
-    }
-    if (h->keep_taps)
-        HIPCHK(hipMemcpyAsync(h->taps[0], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
-    for (int l = 0; l < h->L; ++l) {
-        const Layer& ly = h->layers[l];
-        p = GemmParams{h->xa, d, ly.qkv.w, ly.qkv.kpad, ly.qkv.bias, nullptr, 0, nullptr, 0, h->qkv, 3 * d, N, 3 * d, d, T};
-        if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;
-        if (attention3_supported(S, h->H, d))
-            HIPCHK(launch_attention3(h->qkv, h->ctx, Beff, S, h->H, d, s));
-        else                                              // other head dims / more than 256 tokens: the general 32 x 32-block kernel
-            HIPCHK(launch_attention(h->qkv, h->ctx, Beff, S, h->H, d, s));
-        // x = LN1(x + out_proj(ctx)): the residual add rides in the GEMM epilogue (prefetched one tile ahead, gemm2.hip)
-        p = GemmParams{h->ctx, d, ly.out.w, ly.out.kpad, ly.out.bias, h->xa, d, nullptr, 0, h->tmp, d, N, d, d, T};
-        if (gemm(OUT_ROWS, EPI_RES, p, s)) return -1;
-        HIPCHK(launch_layernorm(h->tmp, nullptr, ly.g1, ly.b1, h->xb, nullptr, N, d, 0, s));
-        p = GemmParams{h->xb, d, ly.ff1.w, ly.ff1.kpad, ly.ff1.bias, nullptr, 0, nullptr, 0, h->ffb, h->ff, N, h->ff, d, T};
-        const bool stamp = h->prof && h->prof_used + 2 <= h->prof_ev.size();
-        if (stamp) HIPCHK(hipEventRecord(h->prof_ev[h->prof_used], s));
-        if (gemm(OUT_ROWS, EPI_GELU, p, s)) return -1;
-        if (stamp) {
-            HIPCHK(hipEventRecord(h->prof_ev[h->prof_used + 1], s));
-            h->prof_used += 2;
-        }
-        p = GemmParams{h->ffb, h->ff, ly.ff2.w, ly.ff2.kpad, ly.ff2.bias, h->xb, d, nullptr, 0, h->tmp, d, N, d, h->ff, T};
-        if (gemm(OUT_ROWS, EPI_RES, p, s)) return -1;
-        const bool last = l + 1 == h->L;
-        const float* res2 = nullptr;
-        // the last layer's output is only needed without token 0 (model/mdm.py:219): write it compacted [Beff*T, d]
-        if (!last || h->keep_taps) HIPCHK(launch_layernorm(h->tmp, res2, ly.g2, ly.b2, h->xa, nullptr, N, d, 0, s));
-        if (last) HIPCHK(launch_layernorm(h->tmp, res2, ly.g2, ly.b2, h->xc, nullptr, N, d, S, s));
-        if (h->keep_taps)
-            HIPCHK(hipMemcpyAsync(h->taps[l + 1], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
-    }
-    // OutputProcess (model/mdm.py:372-380): token-major GEMM, then the permute back to [B, J, 1, T]
-    p = GemmParams{h->xc, d, h->outp.w, h->outp.kpad, h->outp.bias, nullptr, 0, nullptr, 0, h->x0t, h->ldo, Beff * T, h->ldo, d, T};
-    if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;
-    if (!tm) HIPCHK(launch_transpose_out(h->x0t, x0_out, Beff, J, T, h->ldo, s));
-    return 0;
-}
-
-// fp16 mode: one GEMM through gemmh.hip.  A [M][K16] halves with exactly M readable rows.
-static int gemm_f16(bool bf, const _Float16* A, int lda, const Packed& P, const float* bias, const float* R, int ldr,
-                    const float* V, int ldv, float* C32, int ldc32, _Float16* C16, int ldc16, int M, int N, int T,
-                    int rowmap, int gelu, hipStream_t s) {
-    const size_t ab = (size_t)M * lda * 2, wb = (size_t)P.npad16 * P.kpad16 * 2;
-    if (ab >= (1ull << 31) || wb >= (1ull << 31)) return fail("gemm_f16: an operand exceeds the 2 GiB buffer-descriptor range; run the batch in smaller pieces");
-    if (N > P.npad16) return fail("gemm_f16: N exceeds the packed weight");
-    GemmHParams p{A, lda, P.w16, P.kpad16, (int)ab, (int)wb, bias, R, ldr, V, ldv, C32, ldc32, C16, ldc16,
-                  M, N, P.kpad16, T, rowmap, gelu};
-    hipError_t e = HFN(bf, launch_gemmh, p, s);
-    if (e != hipSuccess) return fail(std::string("launch_gemmh: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// The per-step kernel sequence of the fp16 mode: the whole activation stream (GEMM operands, GEMM outputs, the
-// residual stream xa16 / xb16, LayerNorm inputs and outputs, q/k/v, probabilities, context) is fp16; every
-// accumulation (MFMA, bias / residual terms in the GEMM epilogues, LayerNorm statistics, softmax) is fp32.  The two
-// boundary tensors stay fp32: the pose tensor read by the input transpose and the x0 prediction (fp32 output GEMM).
-static int forward_core_f16(gdx_model* h, const float* x, const float* temb, int tstride, const float* c2t, int mode,
-                            float* x0_out, hipStream_t s, const int* state, bool tm) {
-    const int B = h->B, T = h->T, S = h->S, d = h->d, J = h->J;
-    const int Beff = mode == GDX_CFG ? 2 * B : B;
-    const float* seed_emb = mode == GDX_UNCOND ? h->seed_cat + (size_t)B * d : h->seed_cat;
-    const int N = Beff * S;
-    const int Jp = h->in_x.kpad16;
-    const bool s32 = h->stream32;
-    float* const tap32 = (h->keep_taps || s32) ? h->xa : nullptr;     // fp32 copy of the encoder input: parity taps / fp32 stream
-    if (!tm) HIPCHK(HFN(h->bf16, launch_transpose_in_f16, x, h->xt16, Beff, B, J, T, Jp, s));   // tm: the update kernel wrote xt16
-    if (h->cfg.arch == GDX_ARCH_MDM_OLD) {
-        HIPCHK(HFN(h->bf16, launch_token0, temb, tstride, seed_emb, h->pe, h->xa, h->xa16, nullptr, nullptr, nullptr, state, Beff, B, S, d, s));
-        if (gemm_f16(h->bf16, h->xt16, Jp, h->in_x, nullptr, h->addend, d, nullptr, 0, tap32, d, h->xa16, d, Beff * T, d, T, 1, 0, s))
-            return -1;
-    } else {
-        if (!c2t) return fail("forward_core: V2 needs the W_coa * temb rows");
-        const float* c2s = mode == GDX_UNCOND ? h->c2_seed + (size_t)B * d : h->c2_seed;
-        HIPCHK(HFN(h->bf16, launch_token0, temb, tstride, seed_emb, nullptr, h->xa, h->xa16, c2t, c2s, h->c2, state, Beff, B, S, d, s));
-        if (gemm_f16(h->bf16, h->xt16, Jp, h->in_x, h->in_x.bias, nullptr, 0, nullptr, 0, nullptr, 0, h->emb16, d, Beff * T, d, T, 0, 0, s))
-            return -1;
-        // proj_pose writes the operand the front end's kernel reads: 16-bit xseq16, or fp32 xseq for the fp32 kernel
-        const int dt = h->bf16 ? GDX_DTYPE_BF16 : GDX_DTYPE_F16;
+        HIPCHK(HFN(h->bf16, launch_token0, temb, tstride, seed_emb, nullptr, h->xa.f, h->xa.h, c2t, c2s, h->c2, state, Beff, B, S, d, s));
+        if (linear(h, h->xt, h->in_x, {.bias = h->in_x.bias}, h->emb, d, Beff * T, d, s)) return -1;
+        // proj_pose writes the operand the front end's kernel reads: 16-bit xseq.h, or fp32 xseq.f for the fp32 kernels
+        const int dt = h->cfg.compute_dtype;
         const bool la16 = local_attention_half(dt, d, h->cfg.cl_head, h->cfg.window);
-        if (gemm_f16(h->bf16, h->emb16, d, h->proj_pose, nullptr, h->addend, d, h->c2, d, la16 ? nullptr : h->xseq, d,
-                     la16 ? h->xseq16 : nullptr, d, Beff * T, d, T, 0, 0, s))
-            return -1;
-        HIPCHK(launch_local_attention_any(dt, h->xseq, h->xseq16, h->rope_cos, h->rope_sin, la16 ? tap32 : h->xa, h->xa16, Beff, T,
+        const Act xseq = la16 ? Act{nullptr, h->xseq.h} : Act{h->xseq.f, nullptr};
+        if (linear(h, h->emb, h->proj_pose, {.R = h->addend, .ldr = d, .V = h->c2, .ldv = d}, xseq, d, Beff * T, d, s)) return -1;
+        HIPCHK(launch_local_attention_any(dt, h->xseq.f, h->xseq.h, h->rope_cos, h->rope_sin, la16 ? xa.f : h->xa.f, h->xa.h, Beff, T,
                                           d, h->cfg.cl_head, h->cfg.window, s));
     }
-    if (h->keep_taps)
-        HIPCHK(hipMemcpyAsync(h->taps[0], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
+    auto tap = [&](int l) {
+        if (h->keep_taps) HIPCHK(hipMemcpyAsync(h->taps[l], h->xa.f, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
+        return 0;
+    };
+    if (tap(0)) return -1;
     for (int l = 0; l < h->L; ++l) {
         const Layer& ly = h->layers[l];
-        if (gemm_f16(h->bf16, h->xa16, d, ly.qkv, ly.qkv.bias, nullptr, 0, nullptr, 0, nullptr, 0, h->qkv16, 3 * d, N, 3 * d, T, 0, 0, s))
-            return -1;
-        HIPCHK(HFN(h->bf16, launch_attentionh, h->qkv16, h->ctx16, Beff, S, h->H, d, h->rows_alloc, s));
-        // x = LN1(x + out_proj(ctx)).  16-bit stream: the GEMM rounds its output to 16 bits and the LayerNorm adds the 16-bit
-        // residual; fp32 stream (s32): the GEMM epilogue adds the fp32 residual and writes fp32, the LayerNorm writes the
-        // fp32 stream plus the 16-bit copy the next GEMM reads.
-        if (s32) {
-            if (gemm_f16(h->bf16, h->ctx16, d, ly.out, ly.out.bias, h->xa, d, nullptr, 0, h->tmp, d, nullptr, 0, N, d, T, 0, 0, s)) return -1;
-            HIPCHK(HFN(h->bf16, launch_layernorm, h->tmp, nullptr, ly.g1, ly.b1, h->xb, h->xb16, N, d, 0, s));
-        } else {
-            if (gemm_f16(h->bf16, h->ctx16, d, ly.out, ly.out.bias, nullptr, 0, nullptr, 0, nullptr, 0, h->tmp16, d, N, d, T, 0, 0, s)) return -1;
-            HIPCHK(HFN(h->bf16, launch_layernorm_f16, h->tmp16, h->xa16, ly.g1, ly.b1, h->xb16, nullptr, N, d, 0, s));
-        }
+        if (linear(h, h->xa, ly.qkv, {.bias = ly.qkv.bias}, h->qkv, 3 * d, N, 3 * d, s) || attend(h, Beff, s)) return -1;
+        if (add_norm(h, h->ctx, ly.out, h->xa, ly.g1, ly.b1, &h->xb, nullptr, N, s)) return -1;        // x = LN1(x + out_proj(ctx))
         const bool stamp = h->prof && h->prof_used + 2 <= h->prof_ev.size();
         if (stamp) HIPCHK(hipEventRecord(h->prof_ev[h->prof_used], s));
-        if (gemm_f16(h->bf16, h->xb16, d, ly.ff1, ly.ff1.bias, nullptr, 0, nullptr, 0, nullptr, 0, h->ffb16, h->ff, N, h->ff, T, 0, 1, s))
-            return -1;
+        if (linear(h, h->xb, ly.ff1, {.bias = ly.ff1.bias, .gelu = true}, h->ffb, h->ff, N, h->ff, s)) return -1;
         if (stamp) {
             HIPCHK(hipEventRecord(h->prof_ev[h->prof_used + 1], s));
             h->prof_used += 2;
         }
+        // x = LN2(x + ff2(.)); the last layer's output is only needed without token 0 (model/mdm.py:219): compacted [Beff*T, d]
         const bool last = l + 1 == h->L;
-        if (s32) {
-            if (gemm_f16(h->bf16, h->ffb16, h->ff, ly.ff2, ly.ff2.bias, h->xb, d, nullptr, 0, h->tmp, d, nullptr, 0, N, d, T, 0, 0, s))
-                return -1;
-            if (!last || h->keep_taps) HIPCHK(HFN(h->bf16, launch_layernorm, h->tmp, nullptr, ly.g2, ly.b2, h->xa, h->xa16, N, d, 0, s));
-            if (last) HIPCHK(HFN(h->bf16, launch_layernorm, h->tmp, nullptr, ly.g2, ly.b2, nullptr, h->xc16, N, d, S, s));
-        } else {
-            if (gemm_f16(h->bf16, h->ffb16, h->ff, ly.ff2, ly.ff2.bias, nullptr, 0, nullptr, 0, nullptr, 0, h->tmp16, d, N, d, T, 0, 0, s))
-                return -1;
-            if (!last || h->keep_taps) HIPCHK(HFN(h->bf16, launch_layernorm_f16, h->tmp16, h->xb16, ly.g2, ly.b2, h->xa16, tap32, N, d, 0, s));
-            if (last) HIPCHK(HFN(h->bf16, launch_layernorm_f16, h->tmp16, h->xb16, ly.g2, ly.b2, h->xc16, nullptr, N, d, S, s));
-        }
-        if (h->keep_taps)
-            HIPCHK(hipMemcpyAsync(h->taps[l + 1], h->xa, sizeof(float) * (size_t)N * d, hipMemcpyDeviceToDevice, s));
+        if (add_norm(h, h->ffb, ly.ff2, h->xb, ly.g2, ly.b2, !last || h->keep_taps ? &xa : nullptr, last ? &h->xc : nullptr, N, s))
+            return -1;
+        if (tap(l + 1)) return -1;
     }
-    if (gemm_f16(h->bf16, h->xc16, d, h->outp, h->outp.bias, nullptr, 0, nullptr, 0, h->x0t, h->ldo, nullptr, 0, Beff * T, h->ldo, T, 0, 0, s))
-        return -1;
+    // OutputProcess (model/mdm.py:372-380): token-major fp32 GEMM, then the permute back to [B, J, 1, T]
+    if (linear(h, h->xc, h->outp, {.bias = h->outp.bias}, Act{h->x0t, nullptr}, h->ldo, Beff * T, h->ldo, s)) return -1;
     if (!tm) HIPCHK(launch_transpose_out(h->x0t, x0_out, Beff, J, T, h->ldo, s));
     return 0;
 }
@@ -450,6 +404,12 @@ static int check_ready(gdx_model* h, const char* who) {
     if (!h) return fail(std::string(who) + ": null handle");
     if (!h->B) return fail(std::string(who) + ": call gdx_prepare first");
     if (!h->cond_set) return fail(std::string(who) + ": call gdx_set_condition first");
+    return 0;
+}
+
+static int check_mode(const char* who, int mode, const float* scale) {
+    if (mode < GDX_COND || mode > GDX_CFG) return fail(std::string(who) + ": bad mode");
+    if (mode == GDX_CFG && !scale) return fail(std::string(who) + ": GDX_CFG needs scale");
     return 0;
 }
 
@@ -468,8 +428,7 @@ extern "C" int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timest
                            float* out, void* stream) {
     if (check_ready(h, "gdx_forward")) return -1;
     if (!x || !timesteps || !out) return fail("gdx_forward: null argument");
-    if (mode < GDX_COND || mode > GDX_CFG) return fail("gdx_forward: bad mode");
-    if (mode == GDX_CFG && !scale) return fail("gdx_forward: GDX_CFG needs scale");
+    if (check_mode("gdx_forward", mode, scale)) return -1;
     hipStream_t s = (hipStream_t)stream;
     if (time_embed(h, timesteps, h->B, h->temb_in, h->temb_h, h->temb, s)) return -1;
     const float* c2t = nullptr;
@@ -544,8 +503,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     if (check_ready(h, "gdx_bpd_loop")) return -1;
     if (!a->coef || !a->timestep_map || !a->x_start || !a->vb || !a->xstart_mse || !a->mse)
         return fail("gdx_bpd_loop: null argument");
-    if (a->mode < GDX_COND || a->mode > GDX_CFG) return fail("gdx_bpd_loop: bad mode");
-    if (a->mode == GDX_CFG && !a->scale) return fail("gdx_bpd_loop: GDX_CFG needs scale");
+    if (check_mode("gdx_bpd_loop", a->mode, a->scale)) return -1;
     if (a->num_steps <= 0 || a->k_base < 0 || a->k_base >= a->num_steps || a->run_steps < 0 || a->k_base + a->run_steps > a->num_steps)
         return fail("gdx_bpd_loop: bad step range");
     if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_bpd_loop: mask without motion");
@@ -597,8 +555,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
 // first HIP call.
 extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void* stream) {
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_plms_loop: null argument");
-    if (a->mode < GDX_COND || a->mode > GDX_CFG) return fail("gdx_plms_loop: bad mode");
-    if (a->mode == GDX_CFG && !a->scale) return fail("gdx_plms_loop: GDX_CFG needs scale");
+    if (check_mode("gdx_plms_loop", a->mode, a->scale)) return -1;
     if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
         a->run_steps > a->first_index + 1)
         return fail("gdx_plms_loop: bad step range");
@@ -646,8 +603,7 @@ extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
     if (check_ready(h, "gdx_sample_loop")) return -1;
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");
-    if (a->mode < GDX_COND || a->mode > GDX_CFG) return fail("gdx_sample_loop: bad mode");
-    if (a->mode == GDX_CFG && !a->scale) return fail("gdx_sample_loop: GDX_CFG needs scale");
+    if (check_mode("gdx_sample_loop", a->mode, a->scale)) return -1;
     if (a->num_steps <= 0 || a->first_index >= a->num_steps || a->first_index < 0 || a->run_steps < 0 || a->k_base < 0)
         return fail("gdx_sample_loop: bad step range");
     if (a->kind == GDX_SAMPLER_DDIM && (a->const_noise || a->n_dump))
@@ -703,15 +659,15 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         const int Beff = a->mode == GDX_CFG ? 2 * B : B;
         // half modes: the fp32 state keeps the half operand's row stride, and the update kernel also writes that operand
         const int ldx = h->f16 ? h->in_x.kpad16 : h->in_x.kpad;
-        HIPCHK(launch_transpose_in(a->x, h->xt, Beff, B, h->J, h->T, ldx, s));
-        if (h->f16) HIPCHK(HFN(h->bf16, launch_transpose_in_f16, a->x, h->xt16, Beff, B, h->J, h->T, ldx, s));
+        HIPCHK(launch_transpose_in(a->x, h->xt.f, Beff, B, h->J, h->T, ldx, s));
+        if (h->f16) HIPCHK(HFN(h->bf16, launch_transpose_in_f16, a->x, h->xt.h, Beff, B, h->J, h->T, ldx, s));
         gdx::UpdateTmDev u;
         memset(&u, 0, sizeof(u));
         u.kind = a->kind; u.B = B; u.J = h->J; u.T = h->T; u.ldx = ldx; u.ldo = h->ldo;
-        u.coef = a->coef; u.xt = h->xt; u.x0t = h->x0t; u.scale = a->mode == GDX_CFG ? a->scale : nullptr;
+        u.coef = a->coef; u.xt = h->xt.f; u.x0t = h->x0t; u.scale = a->mode == GDX_CFG ? a->scale : nullptr;
         u.const_noise = a->const_noise; u.seed = a->philox_seed; u.sample_offset = a->sample_offset;
         u.clip = a->clip_denoised;
-        u.xt16 = h->f16 ? (void*)h->xt16 : nullptr; u.half_dtype = h->cfg.compute_dtype;
+        u.xt16 = h->xt.h; u.half_dtype = h->cfg.compute_dtype;
         int k = a->k_base;
         for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
             if (denoise_step(h, nullptr, idx, a->mode, nullptr, s, nullptr, true)) return -1;
@@ -874,6 +830,6 @@ extern "C" int gdx_bench_ffn_gemm(gdx_handle_t h, int32_t iters, float* avg_us, 
     hipStream_t s = (hipStream_t)stream;
     const int N = h->B * h->S, d = h->d;
     const Layer& ly = h->layers[0];
-    GemmParams p{h->xb, d, ly.ff1.w, ly.ff1.kpad, ly.ff1.bias, nullptr, 0, nullptr, 0, h->ffb, h->ff, N, h->ff, d, h->T};
+    GemmParams p{h->xb.f, d, ly.ff1.w, ly.ff1.kpad, ly.ff1.bias, nullptr, 0, nullptr, 0, h->ffb.f, h->ff, N, h->ff, d, h->T};
     return time_launches(1, iters, s, avg_us, [&] { return gemm(OUT_ROWS, EPI_GELU, p, s); });
 }

@@ -81,6 +81,10 @@ struct Layer {
     float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
 };
 
+// An activation buffer of the forward, fp32 side and 16-bit side: gdx_prepare allocates the sides the compute mode uses, the
+// helpers of the per-step sequence (api.hip: linear, attend, add_norm) pick the side they read and write
+struct Act { float* f = nullptr; _Float16* h = nullptr; };
+
 // One state-dict key of the handle's configuration: the shape it must have and the device buffers it becomes.  The handle's
 // table of these (weights.hip: describe_weights) is the only list of the model's tensors: gdx_set_weight, the
 // "missing weights" report and the packed image are all read off it.
@@ -108,9 +112,7 @@ struct gdx_model {
     bool f16 = false;                 // reduced-precision mode (GDX_DTYPE_F16 or _BF16): 16-bit MFMA operands, fp32 accumulate
     bool bf16 = false;                // ... with bf16 elements (the gdx::b16 kernels)
     bool stream32 = false;            // 16-bit modes: the residual stream (x + sublayer(x), LayerNorm in / out) stays fp32 and
-                                      // only the GEMM / attention operands are 16-bit copies (default for bf16, see forward_core_f16)
-    _Float16 *xt16 = nullptr, *xa16 = nullptr, *xb16 = nullptr, *qkv16 = nullptr, *ctx16 = nullptr, *ffb16 = nullptr,
-             *emb16 = nullptr, *xc16 = nullptr, *tmp16 = nullptr, *xseq16 = nullptr;
+                                      // only the GEMM / attention operands are 16-bit copies (default for bf16, see add_norm)
     std::vector<gdx::WeightSpec> weights;   // describe_weights; points into this handle
     std::set<std::string> have;
     std::vector<std::string> required;
@@ -124,11 +126,13 @@ struct gdx_model {
     int B = 0, T = 0, S = 0;
     long rows_alloc = 0;              // rows of the [2B*S + pad] token buffers
     bool cond_set = false;
-    float *xa = nullptr, *xb = nullptr, *qkv = nullptr, *ctx = nullptr, *tmp = nullptr, *ffb = nullptr;
-    float *emb_pose = nullptr, *xseq = nullptr, *addend = nullptr;
+    gdx::Act xa, xb, qkv, ctx, tmp, ffb;   // [rows_alloc] token rows: residual stream (xa, xb), sublayer operands and outputs
+    gdx::Act xt, xc;                       // token-major pose in / compacted last layer, [2B*T + pad] rows
+    gdx::Act emb, xseq;                    // V2 front end: InputProcess output, proj_pose output
+    float* addend = nullptr;
     float *seed_cat = nullptr, *temb_in = nullptr, *temb_h = nullptr, *temb = nullptr, *coa = nullptr, *c2 = nullptr;
     float* x0 = nullptr;              // [2B, J, T]
-    float *xt = nullptr, *xc = nullptr, *x0t = nullptr;   // token-major pose in / compacted last layer / token-major x0
+    float* x0t = nullptr;             // token-major x0
     int ldo = 0;                      // row stride of x0t = J rounded up to 64
     float* temb_table = nullptr; int temb_table_rows = 0;
     float* c2t_table = nullptr;       // V2: W_coa * temb_table rows (valid while c2t_valid)
