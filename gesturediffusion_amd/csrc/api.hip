@@ -46,7 +46,7 @@ extern "C" int gdx_create(const gdx_config_t* cfg, gdx_handle_t* out) {
     if (cfg->ff_size <= 0 || cfg->ff_size % 32) return fail("gdx_create: ff_size must be a multiple of 32");
     if (cfg->num_heads <= 0 || cfg->latent_dim % cfg->num_heads) return fail("gdx_create: latent_dim % num_heads != 0");
     const int hd = cfg->latent_dim / cfg->num_heads;
-    if (hd != 32 && hd != 64 && hd != 128 && hd != 256) return fail("gdx_create: head_dim must be 32/64/128/256");
+    if (!head_dim_supported(hd)) return fail("gdx_create: head_dim must be " GDX_HEAD_DIMS);
     if (cfg->njoints <= 0 || cfg->num_layers <= 0 || cfg->seed_poses <= 0 || cfg->mfcc_dim <= 0 || cfg->mfcc_dim > 32)
         return fail("gdx_create: bad njoints/num_layers/seed_poses/mfcc_dim");
     if (cfg->arch == GDX_ARCH_MDM) {

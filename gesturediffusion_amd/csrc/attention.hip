@@ -18,7 +18,16 @@
 //      the A operand V[key(reg, half)][e] is one conflict-free ds_read_b32 per MFMA.
 //   -> O^T again has the query on the lane, so the online-softmax rescale is a per-lane scalar.
 // K tile rows are padded to hd+4 floats: the b128 fragment reads (4 consecutive e of one key per
-// lane, feeding 4 MFMAs with a permuted-but-consistent k order) are bank-conflict free.
+// lane, feeding 4 MFMAs with a permuted-but-consistent k order) are bank-conflict free: the stride is 4 dwords (one 16-byte
+// slot) past a multiple of the 64-bank row at head_dim 32/64/128/192/256 and 9 slots past one at head_dim 96 (100 dwords =
+// 64 + 36), and a ds_read_b128 lane group holds 16 keys that are distinct mod 16 (0-3, 12-15, 20-27 or 4-11, 16-19, 28-31) at
+// one column: 16 different slots either way, since 1 and 9 are both invertible mod 16.  The V reads are one key row per
+// 32-lane half at consecutive dwords, conflict-free at any stride.
+// head_dim 96 / 192 (latent_dim 384 / 768 at the reference's four heads) are instantiations like the others: every count below
+// (HD/8 fragment groups, HD/32 output blocks, HD/32 float4 per thread and tile) is whole for any multiple of 32, and the tile
+// loader's idx -> (row, column) map divides by the constant HD/4.  Registers: 96 fits two workgroups per CU (48 Q + 48 O + 2 x 16
+// scores + 24 in-flight tile registers: 186 allocated); 192 needs 96 + 96 + 32 + 48 and runs one workgroup per CU, like 256
+// (256 + 146 accumulation registers, no scratch).
 #include "gdx_internal.h"
 
 namespace gdx {
@@ -33,6 +42,14 @@ __global__ __launch_bounds__(256, (HD <= 128 ? 2 : 1)) void attention_kernel(
     constexpr int NKK = HD / 8;           // b128 fragment groups along head_dim
     constexpr int NB = HD / 32;           // 32-wide output blocks along head_dim
     constexpr int LD4 = HD / 32;          // float4 loads per thread per tensor per 32-key tile
+    // score accumulators.  The two widths added last (96 / 192) accumulate the even and the odd fragment groups of the head_dim
+    // contraction apart and add them once: two chains of 24 / 48 dependent MFMAs instead of one of 48 / 96, each rounding after
+    // every step.  Against fp64 on the Q x 3 inputs of tests/test_gpu_heads.py the largest error over S = 1..197 is
+    // 1.18e-6 of max|ctx| (192) and 9.4e-7 (96) with two chains, 2.01e-6 (192, S = 31) and 1.85e-6 (96) with one -- at the
+    // 2e-6 bound the kernel tests hold every width to (profiles/attention_head96_192.txt).  The criterion is not the chain
+    // length: head_dim 256 has the longest chain (128 MFMAs) and measures 3.35e-6 on those inputs at S = 128.  It and the other
+    // widths that existed before keep their one chain only so that their bits do not change.
+    constexpr int NSA = (HD & (HD - 1)) ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;
     float* Vs = smem + 32 * KS;
@@ -99,12 +116,27 @@ __global__ __launch_bounds__(256, (HD <= 128 ? 2 : 1)) void attention_kernel(
             f32x16 s;
 #pragma unroll
             for (int e = 0; e < 16; ++e) s[e] = 0.0f;
+            if constexpr (NSA == 1) {
 #pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(&Ks[l31 * KS + 8 * kk + 4 * lh]);
+                for (int kk = 0; kk < NKK; ++kk) {
+                    const f32x4 kf = *reinterpret_cast<const f32x4*>(&Ks[l31 * KS + 8 * kk + 4 * lh]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j], qf[kk][j], s, 0, 0, 0);
+                    for (int j = 0; j < 4; ++j)
+                        s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j], qf[kk][j], s, 0, 0, 0);
+                }
+            } else {
+                f32x16 s1 = s;
+#pragma unroll
+                for (int kk = 0; kk < NKK; kk += 2) {
+                    const f32x4 kf0 = *reinterpret_cast<const f32x4*>(&Ks[l31 * KS + 8 * kk + 4 * lh]);
+                    const f32x4 kf1 = *reinterpret_cast<const f32x4*>(&Ks[l31 * KS + 8 * kk + 8 + 4 * lh]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf0[j], qf[kk][j], s, 0, 0, 0);
+                        s1 = __builtin_amdgcn_mfma_f32_32x32x2f32(kf1[j], qf[kk + 1][j], s1, 0, 0, 0);
+                    }
+                }
+                s += s1;
             }
             // online softmax over this tile's 32 keys (16 in this lane, 16 in lane^32)
             const int kbase = kt * 32 + 4 * lh;
@@ -183,7 +215,9 @@ hipError_t launch_attention(const float* qkv, float* ctx, int B, int S, int H, i
     switch (hd) {
         case 32: return launch_hd<32>(qkv, ctx, B, S, H, d, s);
         case 64: return launch_hd<64>(qkv, ctx, B, S, H, d, s);
+        case 96: return launch_hd<96>(qkv, ctx, B, S, H, d, s);
         case 128: return launch_hd<128>(qkv, ctx, B, S, H, d, s);
+        case 192: return launch_hd<192>(qkv, ctx, B, S, H, d, s);
         case 256: return launch_hd<256>(qkv, ctx, B, S, H, d, s);
         default: return hipErrorInvalidValue;
     }

@@ -20,11 +20,12 @@
 //     phys = chunk ^ f(row), f = (row & 7) << 1 (rows of >= 256 B), ((row >> 1) & 3) << 1 (128-B rows) or
 //     ((row >> 2) & 1) << 1 (64-B rows), on the DMA
 //     source address and on both kinds of read: every ds_read_b128 lane group and every 32-lane half of a
-//     transposed read then covers all 64 banks exactly once;
+//     transposed read then covers all 64 banks exactly once;  head_dim 96 / 192 (rows of 12 / 24 chunks, 8 x 1 kernel only)
+//     take the function of the power-of-two row with the same stride mod 256 B -- see ah_fswz;
 //   * deferred max in the log2 domain: the reference value is raised (cross-lane shuffles + O rescale) only when a
 //     score exceeds it by more than 8 (p <= 2^8 is far inside fp16 range; the running sum and O are fp32).
 // K/V rows past S are the next sample's rows or read as zeros (exact buffer size in the descriptor); their scores
-// are masked to -inf.
+// are masked to -inf.  (The head_dim 96 / 192 instantiations re-read key S - 1 instead and never look past the sample.)
 #include "gdx_internal.h"
 
 #include <cstdlib>
@@ -67,6 +68,29 @@ __device__ __forceinline__ f16x4 lds_read_tr(const char* p) {
     return __builtin_bit_cast(f16x4, v);
 }
 
+// The chunk swizzle: 16-byte chunk c of tile row `row` lives at chunk c ^ ah_fswz<HD>(row) of that row.  What decides the banks
+// is the row stride mod the 256-byte bank row, so a row of 12 chunks (head_dim 96, 192 B = 256 - 64) takes the function of the
+// 64-byte row and a row of 24 chunks (head_dim 192, 384 B = 256 + 128) that of the 128-byte row.  The function is even and below
+// 4 (96) / 8 (192), and 12 / 24 chunks are whole multiples of 4 / 8: the XOR permutes chunks inside an aligned group of 4 / 8 and
+// never leaves the row, and the two chunks of a 16-column block stay adjacent for the transposed reads.
+// Bank argument, slot = 16-byte position mod 16 inside the bank row, key row r = lane & 15, lq = lane >> 4, k-step ks:
+//   ds_read_b128 (K, Q fragments; a lane group is rows {0-3, 12-15} at lq and rows {4-11} at lq + 1, lq even -- or the converse):
+//     96:  slot = 12 r + ((4 ks + lq) ^ f) = 4 ((ks - r) mod 4) + 2 bit2(r) + (lq & 1) (+ 2 for lq >= 2): rows 0-3 / 12-15 differ in
+//          (r mod 4, bit2), rows 4-7 / 8-11 likewise, and the two row sets differ in lq & 1 -- 16 slots, each once.
+//     192: slot = 8 r + ((4 ks + lq) ^ f) = const ^ (lq & 1) ^ 2 ((r >> 1) & 3) ^ 8 (r & 1): bits 1-3 spell r mod 8, which is
+//          0..7 over rows {0-3, 12-15} and over rows {4-11}, and bit 0 tells the two sets apart -- 16 slots, each once.
+//   ds_read_b64_tr_b16 (V; a 32-lane half is 8 consecutive rows v, four lanes on each 32-byte block nb ^ (f >> 1)):
+//     96:  32-byte position mod 8 = 6 v + (nb ^ bit2(v)): {0, 6, 4, 2} + nb for v = 0..3 and the same set moved by one for
+//          v = 4..7 -- eight positions, each once.
+//     192: 12 v + (nb ^ ((v >> 1) & 3)) = nb ^ ((v >> 1) & 3) ^ 4 (v & 1): the low three bits spell v -- each once.
+// Row + 16 has the same f in every case, so the second 16-key block of a tile is the first one 16 rows further on.
+template <int HD>
+__device__ __forceinline__ constexpr int ah_fswz(int row) {
+    constexpr int RM = (HD * 2) % 256;
+    static_assert(HD == 32 || HD == 64 || HD == 96 || HD == 128 || HD == 192 || HD == 256, "no chunk swizzle for this head_dim");
+    return RM == 64 || RM == 192 ? ((row >> 2) & 1) << 1 : RM == 128 ? ((row >> 1) & 3) << 1 : (row & 7) << 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Eight-compute-wave variant: every wave owns ONE query block of 16 and issues 1/8 of the K/V tile DMA itself.
 // With one MFMA wave per SIMD (kernel above) the softmax VALU work, the fragment-read latency and the MFMAs of a
@@ -98,7 +122,8 @@ __global__ __launch_bounds__(512, 1) void attentionh8_kernel(const _Float16* __r
     const int qb_lo = (int)((long)ci * nqb / nchunk), qb_hi = (int)((long)(ci + 1) * nqb / nchunk);
     const int ntiles = (S + 31) / 32;
     const bool mine = qb_lo + wave < qb_hi;                           // wave-uniform
-    auto fswz = [](int row) { return HD == 32 ? ((row >> 2) & 1) << 1 : HD == 64 ? ((row >> 1) & 3) << 1 : (row & 7) << 1; };
+    constexpr bool POW2 = (HD & (HD - 1)) == 0;                       // rows of 12 / 24 chunks (head_dim 96 / 192) otherwise
+    auto fswz = [](int row) { return ah_fswz<HD>(row); };
 
     // ---- Q fragments first (ordinary loads: their wait must not sit behind the DMA stream)
     f16x8 qf[NKS];
@@ -115,27 +140,36 @@ __global__ __launch_bounds__(512, 1) void attentionh8_kernel(const _Float16* __r
     const long kb_off = (base_off + d) * 2, vb_off = (base_off + 2 * d) * 2;
     const auto rsrcK = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + d), (short)0, ah_records(qkv_bytes - kb_off), 0x00020000);
     const auto rsrcV = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + 2 * d), (short)0, ah_records(qkv_bytes - vb_off), 0x00020000);
-    int voff[PW];
+    int voff[PW], voff_l[PW];
 #pragma unroll
     for (int i = 0; i < PW; ++i) {
         int piece = wave + 8 * i;
         piece = piece < P ? piece : P - 1;
         const int pl = piece < T_P ? piece : piece - T_P;
-        const int row = pl * (1024 / ROWB) + lane / CPR;
-        voff[i] = (int)(row * ld * 2) + (((lane % CPR) ^ fswz(row)) * 16);
+        // a 1 KiB piece is 64 consecutive chunks of the tile image, whole rows (power-of-two head_dim) or not:
+        // lane -> (row, physical chunk) -> source address
+        const int g = POW2 ? lane : pl * 64 + lane;
+        const int row = POW2 ? pl * (1024 / ROWB) + lane / CPR : g / CPR;
+        voff[i] = (int)(row * ld * 2) + (((g % CPR) ^ fswz(row)) * 16);
+        // head_dim 96 / 192: the tile rows past key S - 1 re-read key S - 1 (as the Q rows do), so nothing past the sample is ever
+        // read: a masked key has p = 0, but 0 x V is only 0 for a finite V, and the rows behind the last sample are the caller's
+        const int row_l = min(row, S - 1 - 32 * (ntiles - 1));
+        voff_l[i] = POW2 ? voff[i] : (int)(row_l * ld * 2) + (((g % CPR) ^ fswz(row)) * 16);
     }
     int ld_kt = 0;
     auto issue = [&](int stage) {
         const int so = (int)((long)ld_kt * 32 * ld * 2);
+        const bool last = !POW2 && ld_kt == ntiles - 1;               // wave-uniform
         char* sb = smem + stage * STAGE_BYTES;
 #pragma unroll
         for (int i = 0; i < PW; ++i) {
             int piece = wave + 8 * i;
-            piece = piece < P ? piece : P - 1;                        // surplus issues (head_dim 32) re-write the last piece
+            piece = piece < P ? piece : P - 1;                        // surplus issues (head_dim 32, 96) re-write the last piece
+            const int vo = last ? voff_l[i] : voff[i];
             if (piece < T_P)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcK, (lds_ptr_t)(sb + piece * 1024), 16, voff[i], so, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcK, (lds_ptr_t)(sb + piece * 1024), 16, vo, so, 0, 0);
             else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcV, (lds_ptr_t)(sb + T_BYTES + (piece - T_P) * 1024), 16, voff[i], so, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcV, (lds_ptr_t)(sb + T_BYTES + (piece - T_P) * 1024), 16, vo, so, 0, 0);
         }
         ld_kt = ld_kt + 1 < ntiles ? ld_kt + 1 : ntiles - 1;          // past the end: harmless re-reads of the last tile
     };
@@ -147,6 +181,10 @@ __global__ __launch_bounds__(512, 1) void attentionh8_kernel(const _Float16* __r
     const int kbase = l15 * ROWB + ((lq ^ fswz(l15)) << 4);
     const int vrow = 4 * lq + (l15 >> 2);
     const int vbase = T_BYTES + vrow * ROWB + ((fswz(vrow) >> 1) << 5) + (l15 & 3) * 8;
+    // rows of 12 / 24 chunks do not start on a 256-byte boundary, so there the swizzle cannot be folded into kbase / vbase and
+    // the k-step / column block XORed on top: the chunk (32-byte block) index is formed first, then added to the row
+    const int krow_b = l15 * ROWB, kfz = fswz(l15);
+    const int vrow_b = T_BYTES + vrow * ROWB + (l15 & 3) * 8, vfz = fswz(vrow) >> 1;
 
 #pragma unroll
     for (int s = 0; s < NST - 1; ++s) issue(s);
@@ -162,7 +200,10 @@ __global__ __launch_bounds__(512, 1) void attentionh8_kernel(const _Float16* __r
             f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
             constexpr int NR = 2 * NKS, PD = NR < 4 ? NR - 1 : 3;
             auto kread = [&](int r) {
-                return *reinterpret_cast<const f16x8*>(St + ((kbase + (r / NKS) * 16 * ROWB) ^ ((r % NKS) << 6)));
+                if constexpr (POW2)
+                    return *reinterpret_cast<const f16x8*>(St + ((kbase + (r / NKS) * 16 * ROWB) ^ ((r % NKS) << 6)));
+                else
+                    return *reinterpret_cast<const f16x8*>(St + krow_b + (r / NKS) * 16 * ROWB + (((lq + 4 * (r % NKS)) ^ kfz) << 4));
             };
             f16x8 kring[PD + 1];
 #pragma unroll
@@ -174,7 +215,10 @@ __global__ __launch_bounds__(512, 1) void attentionh8_kernel(const _Float16* __r
                 else s1 = GDX_MFMA16(kring[r % (PD + 1)], qf[r % NKS], s1, 0, 0, 0);
             }
             constexpr int VD = NNB < 4 ? NNB - 1 : 3;
-            auto vread = [&](int nb, int half) { return lds_read_tr(St + ((vbase + half * 16 * ROWB) ^ (nb << 5))); };
+            auto vread = [&](int nb, int half) {
+                if constexpr (POW2) return lds_read_tr(St + ((vbase + half * 16 * ROWB) ^ (nb << 5)));
+                else return lds_read_tr(St + vrow_b + half * 16 * ROWB + ((nb ^ vfz) << 5));
+            };
             f16x4 vring[VD + 1][2];
 #pragma unroll
             for (int nb = 0; nb < VD; ++nb) {
@@ -263,6 +307,7 @@ __global__ __launch_bounds__(512, 1) void attentionh8q_kernel(const _Float16* __
     constexpr int T_P = T_BYTES / 1024, P = 2 * T_P, PW = (P + 7) / 8;
     constexpr int NST = 3;
     constexpr int NKS = HD / 32, NNB = HD / 16;
+    static_assert((HD & (HD - 1)) == 0, "whole rows per 1 KiB piece and XOR-composed fragment addresses: power-of-two head_dim only");
     constexpr float RESCALE_THR = 8.0f;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -506,6 +551,7 @@ __global__ __launch_bounds__(512, 1) void attentionh8p_kernel(const _Float16* __
     constexpr int T_P = T_BYTES / 1024, P = 2 * T_P, PW = (P + 7) / 8;
     constexpr int NST = 3;
     constexpr int NKS = HD / 32, NNB = HD / 16;
+    static_assert((HD & (HD - 1)) == 0, "whole rows per 1 KiB piece and XOR-composed fragment addresses: power-of-two head_dim only");
     constexpr float RESCALE_THR = 8.0f;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -850,12 +896,15 @@ static hipError_t launch_ah8(const _Float16* qkv, _Float16* ctx, int B, int S, i
 
 bool attentionh_supported(int S, int H, int d) {
     const int hd = d / H;
-    return (hd == 32 || hd == 64 || hd == 128 || hd == 256) && d % 8 == 0 && S >= 1;
+    return head_dim_supported(hd) && d % 8 == 0 && S >= 1;
 }
 
+// head widths with an 8 x 2 and a persistent instantiation
+bool attentionh_multiblock(int hd) { return hd == 64 || hd == 128 || hd == 256; }
+
 // The one dispatch of the forward and of the test entry point gdx_attention_half.  kernel: 0 = the forward's choice, 1 = the
-// 8-wave x 1-block kernel, 2 = 8 x 2 blocks, 3 = the persistent form (the callers refuse 2 / 3 at head_dim 32, which has no
-// instantiation of them); grid > 0: workgroups of the persistent form (0 = one per CU, at most one per item).  launched
+// 8-wave x 1-block kernel, 2 = 8 x 2 blocks, 3 = the persistent form (the callers refuse 2 / 3 at head_dim 32, 96 and 192, which
+// have no instantiation of them: attentionh_multiblock); grid > 0: workgroups of the persistent form (0 = one per CU, at most one per item).  launched
 // (optional, 3 entries): the kernel that ran (1-3), its grid and its work-item count.  qkv_rows: rows of the qkv buffer that are
 // readable (>= B*S); reads past them return zeros.  stamps (optional): the persistent form runs its stamped build and writes there.
 hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, int kernel,
@@ -871,11 +920,11 @@ hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, i
     const int num_cus = gemm2_num_cus();
     if (kernel == 0) {
         // persistent form once every CU has at least two items to chain (profiles/r02h_*)
-        if (hd >= 64 && nitems >= 2L * num_cus) kernel = 3;
-        else if (hd >= 64 && nitems >= 128) kernel = 2;
+        if (attentionh_multiblock(hd) && nitems >= 2L * num_cus) kernel = 3;
+        else if (attentionh_multiblock(hd) && nitems >= 128) kernel = 2;
         else kernel = 1;
     }
-    if ((kernel != 1 && (hd < 64 || kernel > 3)) || kernel < 1 || (grid != 0 && kernel != 3) || grid < 0) return hipErrorInvalidValue;
+    if ((kernel != 1 && (!attentionh_multiblock(hd) || kernel > 3)) || kernel < 1 || (grid != 0 && kernel != 3) || grid < 0) return hipErrorInvalidValue;
     if (kernel == 3 && grid == 0) grid = nitems < num_cus ? (int)nitems : num_cus;
     if (launched) {
         launched[0] = kernel;
@@ -895,7 +944,9 @@ hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, i
         return hipErrorInvalidValue;
     }
     if (hd == 256) return launch_ah8<256>(qkv, ctx, B, S, H, d, bytes, s);
+    if (hd == 192) return launch_ah8<192>(qkv, ctx, B, S, H, d, bytes, s);
     if (hd == 128) return launch_ah8<128>(qkv, ctx, B, S, H, d, bytes, s);
+    if (hd == 96) return launch_ah8<96>(qkv, ctx, B, S, H, d, bytes, s);
     if (hd == 64) return launch_ah8<64>(qkv, ctx, B, S, H, d, bytes, s);
     if (hd == 32) return launch_ah8<32>(qkv, ctx, B, S, H, d, bytes, s);
     return hipErrorInvalidValue;

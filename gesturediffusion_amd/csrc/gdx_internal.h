@@ -99,6 +99,9 @@ struct GemmHParams {
 // ---- attention (attention.hip) -----------------------------------------------------------
 // qkv [B*S][3d] (q | k | v, heads contiguous inside each), ctx [B*S][d]
 hipError_t launch_attention(const float* qkv, float* ctx, int B, int S, int H, int d, hipStream_t s);
+// the encoder head widths with a self-attention kernel in every compute mode (attention.hip, attentionh.hip)
+inline bool head_dim_supported(int hd) { return hd == 32 || hd == 64 || hd == 96 || hd == 128 || hd == 192 || hd == 256; }
+#define GDX_HEAD_DIMS "32, 64, 96, 128, 192 or 256"
 
 // eight-wave single-pass variant with the last query block shared out over four waves (attention3.hip); needs 64
 // readable rows past the last sample
@@ -113,8 +116,10 @@ hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, 
 #define GDX_HALF_API                                                                                                        \
     bool gemmh_supported(const GemmHParams& p);                                                                             \
     hipError_t launch_gemmh(const GemmHParams& p, hipStream_t s, GemmHCtl* ctl = nullptr);                                  \
-    /* reduced-precision attention (attentionh.hip): qkv / ctx in halves, head_dim 32/64/128/256, any S; qkv_rows = readable rows */ \
+    /* reduced-precision attention (attentionh.hip): qkv / ctx in halves, head_dim 32/64/96/128/192/256, any S; qkv_rows = readable rows */ \
     bool attentionh_supported(int S, int H, int d);                                                                         \
+    /* true where the 8 x 2 and persistent kernels (2, 3) are instantiated: head_dim 64/128/256 */                          \
+    bool attentionh_multiblock(int hd);                                                                                     \
     hipError_t launch_attentionh(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, hipStream_t s); \
     /* the same dispatch with a forced kernel (0 = the forward's choice, 1 = h8, 2 = h8q, 3 = h8p), the persistent grid      \
        (0 = its default), a report of what ran (launched: kernel, grid, work items) and a 512-byte device buffer for the     \

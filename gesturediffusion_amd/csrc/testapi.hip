@@ -282,7 +282,7 @@ extern "C" int gdx_local_attention(const float* xseq, const float* cosT, const f
 
 extern "C" int gdx_attention_f16(const float* qkv, float* ctx, int32_t B, int32_t S, int32_t H, int32_t d, void* stream) {
     if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H || !HFN(t_bf16, attentionh_supported, S, H, d))
-        return fail("gdx_attention_f16: bad argument / unsupported shape");
+        return fail("gdx_attention_f16: bad argument / unsupported shape (head_dim " GDX_HEAD_DIMS ")");
     hipStream_t s = (hipStream_t)stream;
     const size_t rows = (size_t)B * S;
     _Float16 *q16 = nullptr, *c16 = nullptr;
@@ -299,9 +299,10 @@ extern "C" int gdx_attention_half(const float* qkv, int32_t qkv_rows, float* ctx
     // every refusal comes before the first HIP call (tests/test_host_logic.py checks them without a GPU)
     if (dtype != GDX_DTYPE_F16 && dtype != GDX_DTYPE_BF16) return fail("gdx_attention_half: dtype must be GDX_DTYPE_F16 or _BF16");
     if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H || !HFN(dtype == GDX_DTYPE_BF16, attentionh_supported, S, H, d))
-        return fail("gdx_attention_half: bad argument / unsupported shape (head_dim 32, 64, 128 or 256)");
+        return fail("gdx_attention_half: bad argument / unsupported shape (head_dim " GDX_HEAD_DIMS ")");
     if (kernel < 0 || kernel > 3) return fail("gdx_attention_half: unknown kernel (0 = dispatch, 1 = h8, 2 = h8q, 3 = h8p)");
-    if (kernel >= 2 && d / H < 64) return fail("gdx_attention_half: h8q / h8p have no head_dim 32 instantiation");
+    if (kernel >= 2 && !HFN(dtype == GDX_DTYPE_BF16, attentionh_multiblock, d / H))
+        return fail("gdx_attention_half: h8q / h8p have no head_dim " + std::to_string(d / H) + " instantiation");
     if (grid < 0 || (grid > 0 && kernel != 3)) return fail("gdx_attention_half: grid is for the persistent kernel (kernel 3) only");
     if ((long)qkv_rows < (long)B * S || (long)ctx_rows < (long)B * S) return fail("gdx_attention_half: qkv_rows / ctx_rows below B*S");
     if (2 * (size_t)qkv_rows * 3 * d >= (1ull << 31) || 2 * (size_t)ctx_rows * d >= (1ull << 31))
@@ -322,7 +323,7 @@ extern "C" int gdx_attention_f32(const float* qkv, float* ctx, int32_t B, int32_
                                  void* stream) {
     if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H) return fail("gdx_attention_f32: bad argument");
     const int hd = d / H;
-    if (hd != 32 && hd != 64 && hd != 128 && hd != 256) return fail("gdx_attention_f32: head_dim must be 32, 64, 128 or 256");
+    if (!head_dim_supported(hd)) return fail("gdx_attention_f32: head_dim must be " GDX_HEAD_DIMS);
     if (version == 2) return fail("gdx_attention_f32: kernel version 2 (attention2.hip) was removed in round 3");
     if ((version == 3 || version == 5) && !attention3_supported(S, H, d))
         return fail("gdx_attention_f32: shape not supported by the requested kernel");
@@ -385,6 +386,7 @@ extern "C" int gdx_bench_gemm_f16(int32_t M, int32_t N, int32_t K, int32_t gelu,
 extern "C" int gdx_bench_attention(int32_t B, int32_t S, int32_t H, int32_t d, int32_t version, int32_t iters,
                                    float* avg_us, void* stream) {
     if (!avg_us || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H || iters <= 0) return fail("gdx_bench_attention: bad argument");
+    if (!head_dim_supported(d / H)) return fail("gdx_bench_attention: head_dim must be " GDX_HEAD_DIMS);
     hipStream_t s = (hipStream_t)stream;
     float *qkv = nullptr, *ctx = nullptr;
     Scratch sc("gdx_bench_attention", s, t_bf16);

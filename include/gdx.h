@@ -60,7 +60,7 @@ typedef struct {
     int32_t latent_dim;  /* d, multiple of 32 */
     int32_t ff_size;     /* multiple of 32 */
     int32_t num_layers;
-    int32_t num_heads;   /* d / num_heads must be a multiple of 32 */
+    int32_t num_heads;   /* head_dim = latent_dim / num_heads in {32, 64, 96, 128, 192, 256} */
     int32_t seed_poses;
     int32_t mfcc_dim;    /* 26 (model/mdm.py:57) */
     int32_t cl_head;     /* 8  (model/mdm.py:71), V2 only */
@@ -494,14 +494,15 @@ int gdx_local_attention(const float* xseq, const float* cosT, const float* sinT,
                         void* stream);
 /* ctx = softmax(Q K^T / sqrt(hd)) V per (sample, head) through the fp16 attention kernel
  * (csrc/attentionh.hip): qkv [B*S][3d] and ctx [B*S][d] are fp32 device arrays converted to / from
- * fp16 by the call.  head_dim = d / H in {32, 64, 128, 256}.  Synchronises the stream. */
+ * fp16 by the call.  head_dim = d / H in {32, 64, 96, 128, 192, 256}.  Synchronises the stream. */
 int gdx_attention_f16(const float* qkv, float* ctx, int32_t B, int32_t S, int32_t H, int32_t d, void* stream);
 /* The same attention with the element type as an argument (GDX_DTYPE_F16 / _BF16, not the process-wide setting) and a
  * forced kernel: qkv [qkv_rows][3d] fp32 (qkv_rows >= B*S), ALL of it converted to dtype; the kernel reads qkv_rows rows, as
  * the forward reads its padded workspace (rows past B*S are the caller's).  ctx [ctx_rows][d] fp32 (ctx_rows >= B*S) receives
  * the 16-bit output widened, staged from ctx's own values: rows the kernel does not store come back unchanged.
  * kernel: 0 = the forward's dispatch, 1 = attentionh8_kernel (8 waves x 1 query block), 2 = attentionh8q_kernel (8 x 2),
- * 3 = attentionh8p_kernel (persistent); 2 and 3 exist for head_dim 64 / 128 / 256 only.  grid > 0 (kernel 3 only): workgroups
+ * 3 = attentionh8p_kernel (persistent); 2 and 3 exist for head_dim 64 / 128 / 256 only (32, 96 and 192 are
+ * refused for them; the forward's dispatch keeps those widths on kernel 1).  head_dim in {32, 64, 96, 128, 192, 256}.  grid > 0 (kernel 3 only): workgroups
  * of the persistent kernel (0 = min(work items, CUs)).  launched (optional, 3 entries) receives the kernel that ran (1-3), its
  * grid and its work-item count.  Every refusal comes before the first HIP call.  Synchronises the stream. */
 int gdx_attention_half(const float* qkv, int32_t qkv_rows, float* ctx, int32_t ctx_rows, int32_t B, int32_t S, int32_t H,

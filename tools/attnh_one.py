@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """fp16 attention core (csrc/attentionh.hip): correctness vs torch (fp64 on the fp16-rounded inputs) + timing.
-python tools/attnh_one.py B S H d"""
+python tools/attnh_one.py B S H d      (head widths d / H: 32, 64, 96, 128, 192, 256)"""
 import ctypes as C, sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch

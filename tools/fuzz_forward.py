@@ -21,8 +21,8 @@ bad = 0
 t00 = time.time()
 for case in range(n):
     arch = rnd.choice(["mdm", "mdm_old"])
-    dm = rnd.choice([128, 256, 512] + ([1024] if case % 7 == 0 else []))
-    H = rnd.choice([h for h in (2, 4, 8) if dm // h in (32, 64, 128, 256)])      # gdx_create: head widths 32 / 64 / 128 / 256
+    dm = rnd.choice([128, 256, 384, 512, 768] + ([1024] if case % 7 == 0 else []))
+    H = rnd.choice([h for h in (2, 4, 8) if dm // h in (32, 64, 96, 128, 192, 256)])   # gdx_create: head widths 32 / 64 / 96 / 128 / 192 / 256
     T = rnd.choice([10, 20, 30, 40, 60, 120, 200, 250]) if arch == "mdm" else rnd.choice([1, 7, 15, 16, 33, 64, 100, 196, 255, 300])
     J = rnd.choice([3, 16, 37, 150, 263, 498])
     L = rnd.choice([1, 2, 3])
