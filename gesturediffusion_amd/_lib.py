@@ -24,6 +24,7 @@ EXPORTS = [
     "gdx_set_guards", "gdx_check_guards", "gdx_packed_bytes", "gdx_export_packed", "gdx_import_packed", "gdx_set_test_half_dtype",
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
     "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
+    "gdx_transpose_in", "gdx_transpose_out", "gdx_small_linear", "gdx_gather_rows", "gdx_mfcc_project", "gdx_token0",
 ]
 GDX_BPD_CHUNK = 4096   # include/gdx.h
 
@@ -155,6 +156,12 @@ def load():
                             C.POINTER(i32), vp],
         "gdx_layernorm": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
         "gdx_local_attention": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
+        "gdx_transpose_in": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+        "gdx_transpose_out": [vp, vp, i32, i32, i32, i32, i32, vp],
+        "gdx_small_linear": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+        "gdx_gather_rows": [vp, vp, vp, i32, i32, i32, i32, vp],
+        "gdx_mfcc_project": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+        "gdx_token0": [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp],
         "gdx_set_graph_replay": [vp, i32],
         "gdx_mfcc": [vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "gdx_q_sample_t": [vp, vp, vp, vp, i32, i64, vp, vp],

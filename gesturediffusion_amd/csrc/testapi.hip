@@ -39,6 +39,18 @@ struct Scratch {
         if (HFN(bf, launch_convert_f32, h, dst, n, s) != hipSuccess) return fail(who + ": convert failed");
         return 0;
     }
+    // the same for an fp32 output: *d = n floats staged from the caller's own values; unstage copies all of them back
+    int stage(float** d, const float* src, int64_t n) {
+        if (alloc(d, sizeof(float) * (size_t)n)) return -1;
+        if (hipMemcpyAsync(*d, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(who + ": staging failed");
+        return 0;
+    }
+    int unstage(const float* d, float* dst, int64_t n) {
+        if (hipMemcpyAsync(dst, d, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(who + ": copy-out failed");
+        return 0;
+    }
 };
 
 // One extra launch with in-kernel stamps when GDX_GEMM_DEBUG is set (diagnostic path only): launch(stamps) gets a zeroed
@@ -278,6 +290,125 @@ extern "C" int gdx_local_attention(const float* xseq, const float* cosT, const f
     const hipError_t e = launch_local_attention_any(dtype, xseq, x16, cosT, sinT, enc, e16, B, T, d, heads, window, s);
     if (e != hipSuccess) return fail(std::string("launch_local_attention: ") + hipGetErrorString(e));
     return enc16 ? sc.widen(e16, enc16, n_out) : 0;
+}
+
+// ---- the boundary kernels of the denoiser step (misc.hip), each through the launcher the forwards call.  Inputs are read where
+// the caller put them (strides and the rows behind them included); every output is staged from the caller's own values and
+// copied back whole, so elements the kernel does not store come back unchanged.  Every refusal comes before the first HIP call
+// (tests/test_host_logic.py checks them without a GPU).
+static bool dtype_known(int dtype) { return dtype == GDX_DTYPE_F32 || dtype == GDX_DTYPE_F16 || dtype == GDX_DTYPE_BF16; }
+
+extern "C" int gdx_transpose_in(const float* x, float* xt, int32_t xt_rows, int32_t B, int32_t Bsrc, int32_t J, int32_t T,
+                                int32_t ldx, int32_t dtype, void* stream) {
+    if (!x || !xt || B <= 0 || B > 65535 || Bsrc <= 0 || Bsrc > B || J <= 0 || T <= 0) return fail("gdx_transpose_in: bad argument");
+    if (!dtype_known(dtype)) return fail("gdx_transpose_in: unknown dtype");
+    if (ldx < J) return fail("gdx_transpose_in: ldx below J");
+    if (xt_rows < (long)B * T) return fail("gdx_transpose_in: xt_rows below B*T");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)xt_rows * ldx;
+    Scratch sc("gdx_transpose_in", s, dtype == GDX_DTYPE_BF16);
+    if (dtype == GDX_DTYPE_F32) {
+        float* o = nullptr;
+        if (sc.stage(&o, xt, n)) return -1;
+        const hipError_t e = launch_transpose_in(x, o, B, Bsrc, J, T, ldx, s);
+        if (e != hipSuccess) return fail(std::string("launch_transpose_in: ") + hipGetErrorString(e));
+        return sc.unstage(o, xt, n);
+    }
+    _Float16* o16 = nullptr;
+    if (sc.to_half(&o16, xt, n)) return -1;
+    const hipError_t e = HFN(sc.bf, launch_transpose_in_f16, x, o16, B, Bsrc, J, T, ldx, s);
+    if (e != hipSuccess) return fail(std::string("launch_transpose_in_f16: ") + hipGetErrorString(e));
+    return sc.widen(o16, xt, n);
+}
+
+extern "C" int gdx_transpose_out(const float* yt, float* y, int32_t y_rows, int32_t B, int32_t J, int32_t T, int32_t ldy,
+                                 void* stream) {
+    if (!yt || !y || B <= 0 || B > 65535 || J <= 0 || T <= 0) return fail("gdx_transpose_out: bad argument");
+    if (ldy < J) return fail("gdx_transpose_out: ldy below J");
+    if (y_rows < (long)B * J) return fail("gdx_transpose_out: y_rows below B*J");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)y_rows * T;
+    float* o = nullptr;
+    Scratch sc("gdx_transpose_out", s);
+    if (sc.stage(&o, y, n)) return -1;
+    const hipError_t e = launch_transpose_out(yt, o, B, J, T, ldy, s);
+    if (e != hipSuccess) return fail(std::string("launch_transpose_out: ") + hipGetErrorString(e));
+    return sc.unstage(o, y, n);
+}
+
+extern "C" int gdx_small_linear(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float* out,
+                                int32_t out_rows, int32_t ldo, int32_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+    if (!A || !W || !out || M <= 0 || M > 4 * 65535 || N <= 0 || K <= 0) return fail("gdx_small_linear: bad argument");
+    if (act != 0 && act != 1) return fail("gdx_small_linear: unknown act (0 = none, 1 = SiLU)");
+    if (lda < K || ldw < K) return fail("gdx_small_linear: lda / ldw below K");
+    if (ldo < N) return fail("gdx_small_linear: ldo below N");
+    if (out_rows < M) return fail("gdx_small_linear: out_rows below M");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)out_rows * ldo;
+    float* o = nullptr;
+    Scratch sc("gdx_small_linear", s);
+    if (sc.stage(&o, out, n)) return -1;
+    const hipError_t e = launch_small_linear(A, lda, W, ldw, bias, o, ldo, M, N, K, act, s);
+    if (e != hipSuccess) return fail(std::string("launch_small_linear: ") + hipGetErrorString(e));
+    return sc.unstage(o, out, n);
+}
+
+extern "C" int gdx_gather_rows(const float* table, const int64_t* idx, float* out, int32_t out_rows, int32_t M, int32_t d,
+                               int32_t max_rows, void* stream) {
+    if (!table || !idx || !out || M <= 0 || d <= 0 || max_rows <= 0) return fail("gdx_gather_rows: bad argument");
+    if (out_rows < M) return fail("gdx_gather_rows: out_rows below M");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)out_rows * d;
+    float* o = nullptr;
+    Scratch sc("gdx_gather_rows", s);
+    if (sc.stage(&o, out, n)) return -1;
+    const hipError_t e = launch_gather_rows(table, idx, o, M, d, max_rows, s);
+    if (e != hipSuccess) return fail(std::string("launch_gather_rows: ") + hipGetErrorString(e));
+    return sc.unstage(o, out, n);
+}
+
+extern "C" int gdx_mfcc_project(const float* mfcc, const float* W, int32_t ldw, const float* bias, const float* pe, float* out,
+                                int32_t out_rows, int32_t B, int32_t Bsrc, int32_t C, int32_t T, int32_t d, int32_t rps,
+                                int32_t off, void* stream) {
+    if (!mfcc || !W || !bias || !out || B <= 0 || Bsrc <= 0 || Bsrc > B || C <= 0 || T <= 0 || d <= 0 || off < 0 ||
+        (long)B * T > 64l * 65535)
+        return fail("gdx_mfcc_project: bad argument");
+    if (C > 32) return fail("gdx_mfcc_project: C above 32 (the kernel holds a weight row in 32 registers)");
+    if (ldw < C) return fail("gdx_mfcc_project: ldw below C");
+    if (rps < (long)T + off) return fail("gdx_mfcc_project: rps below T + off");
+    if (out_rows < (long)(B - 1) * rps + off + T) return fail("gdx_mfcc_project: out_rows below the stored rows");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)out_rows * d;
+    float* o = nullptr;
+    Scratch sc("gdx_mfcc_project", s);
+    if (sc.stage(&o, out, n)) return -1;
+    const hipError_t e = launch_mfcc_project(mfcc, W, ldw, bias, pe, o, B, Bsrc, C, T, d, rps, off, s);
+    if (e != hipSuccess) return fail(std::string("launch_mfcc_project: ") + hipGetErrorString(e));
+    return sc.unstage(o, out, n);
+}
+
+extern "C" int gdx_token0(const float* temb, int32_t tstride, const float* seed_emb, const float* pe0, float* enc, float* enc16,
+                          int32_t enc_rows, const float* c2t, const float* c2_seed, float* c2, int32_t c2_rows,
+                          const int32_t* state, int32_t B, int32_t Bsrc, int32_t S, int32_t d, int32_t dtype, void* stream) {
+    if (!temb || !seed_emb || !enc || B <= 0 || Bsrc <= 0 || Bsrc > B || S <= 0 || d <= 0 || (long)B * d >= (1l << 31))
+        return fail("gdx_token0: bad argument");
+    if (!dtype_known(dtype)) return fail("gdx_token0: unknown dtype");
+    if (enc16 && dtype == GDX_DTYPE_F32) return fail("gdx_token0: GDX_DTYPE_F32 takes no enc16");
+    if (tstride != 0 && tstride < d) return fail("gdx_token0: tstride must be 0 (one row for the batch) or at least d");
+    if ((c2 != nullptr) != (c2t != nullptr) || (c2 != nullptr) != (c2_seed != nullptr))
+        return fail("gdx_token0: c2t, c2_seed and c2 go together");
+    if (enc_rows < (long)(B - 1) * S + 1) return fail("gdx_token0: enc_rows below the stored rows");
+    if (c2 && c2_rows < B) return fail("gdx_token0: c2_rows below B");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_enc = (int64_t)enc_rows * d, n_c2 = (int64_t)c2_rows * d;
+    float *e32 = nullptr, *o2 = nullptr;
+    _Float16* e16 = nullptr;
+    Scratch sc("gdx_token0", s, dtype == GDX_DTYPE_BF16);
+    if (sc.stage(&e32, enc, n_enc) || (enc16 && sc.to_half(&e16, enc16, n_enc)) || (c2 && sc.stage(&o2, c2, n_c2))) return -1;
+    const hipError_t e = HFN(sc.bf, launch_token0, temb, tstride, seed_emb, pe0, e32, e16, c2t, c2_seed, o2, state, B, Bsrc, S, d, s);
+    if (e != hipSuccess) return fail(std::string("launch_token0: ") + hipGetErrorString(e));
+    if (sc.unstage(e32, enc, n_enc) || (c2 && sc.unstage(o2, c2, n_c2))) return -1;
+    return enc16 ? sc.widen(e16, enc16, n_enc) : 0;
 }
 
 extern "C" int gdx_attention_f16(const float* qkv, float* ctx, int32_t B, int32_t S, int32_t H, int32_t d, void* stream) {

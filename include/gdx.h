@@ -492,6 +492,47 @@ int gdx_layernorm(const float* x, const float* res, const float* gamma, const fl
 int gdx_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc, float* enc16, int32_t enc_rows,
                         int32_t B, int32_t T, int32_t d, int32_t heads, int32_t window, int32_t dtype, int32_t* kernel,
                         void* stream);
+/* ---- the boundary kernels of the denoiser step (csrc/misc.hip; tests) -------------------- */
+/* Each of the six calls below runs one launcher exactly as the forwards call it.  Inputs are fp32 device arrays read in
+ * place, with the caller's strides.  Every output is an fp32 device array of a stated row capacity (at least the rows the
+ * kernel stores); it is staged from the caller's own values and copied back whole, so elements the kernel does not store
+ * come back unchanged (NaN stays NaN); a 16-bit output travels as fp32, rounded to dtype on the way in and widened on the
+ * way out.  Every refusal (a null pointer, a non-positive size, a stride below the row it must hold, a capacity below the
+ * stored rows, an unknown dtype or act) comes before the first HIP call.  Each call synchronises the stream. */
+/* Pose tensor x [Bsrc, J, T] -> token-major xt[(b*T + t)*ldx + j] for b < B (source sample b % Bsrc: B = 2*Bsrc feeds both
+ * halves of a CFG batch), columns J..ldx-1 zeroed.  xt [xt_rows >= B*T][ldx >= J].  dtype GDX_DTYPE_F32: the fp32 kernel;
+ * GDX_DTYPE_F16 / _BF16: the 16-bit kernel of that element type, xt = its output widened.  Bsrc <= B. */
+int gdx_transpose_in(const float* x, float* xt, int32_t xt_rows, int32_t B, int32_t Bsrc, int32_t J, int32_t T, int32_t ldx,
+                     int32_t dtype, void* stream);
+/* Token-major prediction yt[(b*T + t)*ldy + j] -> y[(b*J + j)*T + t].  yt [B*T][ldy >= J] (columns J..ldy-1 are not read),
+ * y [y_rows >= B*J][T]. */
+int gdx_transpose_out(const float* yt, float* y, int32_t y_rows, int32_t B, int32_t J, int32_t T, int32_t ldy, void* stream);
+/* out[m*ldo + n] = act(sum_{k<K} A[m*lda + k] * W[n*ldw + k] + bias[n]) for m < M, n < N; act 0 = none, 1 = SiLU; bias may
+ * be NULL.  The timestep MLP, the seed-pose encoder and the coarse slices of project_to_lat.  lda, ldw >= K; out
+ * [out_rows >= M][ldo >= N]. */
+int gdx_small_linear(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float* out, int32_t out_rows,
+                     int32_t ldo, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+/* out[m][:] = table[clamp(idx[m], 0, max_rows - 1)][:] (timestep -> positional-encoding row).  table [>= max_rows][d],
+ * idx [M] int64 (device), out [out_rows >= M][d]. */
+int gdx_gather_rows(const float* table, const int64_t* idx, float* out, int32_t out_rows, int32_t M, int32_t d,
+                    int32_t max_rows, void* stream);
+/* The hoisted MFCC slice of the input linear:
+ *   out[(b*rps + t + off)*d + n] = sum_{c<C} mfcc[((b % Bsrc)*C + c)*T + t] * W[n*ldw + c] + bias[n] (+ pe[(t+1)*d + n])
+ * for b < B, t < T, n < d.  V1 passes rps = T + 1, off = 1 and pe; V2 rps = T, off = 0 and no pe.  mfcc [Bsrc, C, T],
+ * W [d][ldw >= C], bias [d], pe [>= T+1][d] or NULL, out [out_rows >= (B-1)*rps + off + T][d].  C <= 32, rps >= T + off,
+ * Bsrc <= B. */
+int gdx_mfcc_project(const float* mfcc, const float* W, int32_t ldw, const float* bias, const float* pe, float* out,
+                     int32_t out_rows, int32_t B, int32_t Bsrc, int32_t C, int32_t T, int32_t d, int32_t rps, int32_t off,
+                     void* stream);
+/* The conditioning token: enc[b*S*d + n] = temb[(b % Bsrc)*tstride + n] + seed_emb[b*d + n] (+ pe0[n]) for b < B, n < d
+ * (row 0 of each sample's S rows; the others are not stored), and enc16 (optional, 16-bit modes) the same value rounded to
+ * dtype.  tstride = 0: one temb row for the batch, else >= d.  c2t, c2_seed, c2 (all three or none; V2):
+ * c2[b*d + n] = c2t[(b % Bsrc)*tstride + n] + c2_seed[b*d + n].  state (optional; graph replay): a device int[2]; temb and
+ * c2t are then table bases and row state[0] of them is used.  enc / enc16 [enc_rows >= (B-1)*S + 1][d], c2 [c2_rows >= B][d].
+ * GDX_DTYPE_F32 takes no enc16.  Bsrc <= B. */
+int gdx_token0(const float* temb, int32_t tstride, const float* seed_emb, const float* pe0, float* enc, float* enc16,
+               int32_t enc_rows, const float* c2t, const float* c2_seed, float* c2, int32_t c2_rows, const int32_t* state,
+               int32_t B, int32_t Bsrc, int32_t S, int32_t d, int32_t dtype, void* stream);
 /* ctx = softmax(Q K^T / sqrt(hd)) V per (sample, head) through the fp16 attention kernel
  * (csrc/attentionh.hip): qkv [B*S][3d] and ctx [B*S][d] are fp32 device arrays converted to / from
  * fp16 by the call.  head_dim = d / H in {32, 64, 96, 128, 192, 256}.  Synchronises the stream. */

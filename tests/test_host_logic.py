@@ -216,6 +216,70 @@ def test_linear_full_refuses_what_the_forwards_do_not_launch_without_gpu():
     assert lib.gdx_linear_f32(p, p, p, None, p, 77, 128, 48, 0, 0, 0, 0, None) != 0 and b"gdx_linear_f32" in lib.gdx_last_error()
 
 
+def test_boundary_kernel_entry_points_refuse_bad_arguments_without_gpu():
+    """gdx_transpose_in / _out, gdx_small_linear, gdx_gather_rows, gdx_mfcc_project and gdx_token0 validate before their
+    first HIP call: null pointers, non-positive sizes, a stride below the row it must hold, an output capacity below the
+    rows the kernel stores, C > 32, an unknown dtype or act and a 16-bit output in GDX_DTYPE_F32 are refused with a message
+    that names the entry point (the pointers are never dereferenced)."""
+    import ctypes as C
+    from gesturediffusion_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgdx.so not built")
+    lib = _lib.load()
+    p = C.c_void_p(0x1000)
+
+    def refused(name, order, ok, cases):
+        fn = getattr(lib, name)
+        for change, msg in cases:
+            a = dict(ok, **change)
+            rc = fn(*[a[k] for k in order], None)
+            err = lib.gdx_last_error()
+            assert rc != 0 and name.encode() in err and msg in err, (name, change, err)
+
+    refused("gdx_transpose_in", "x xt xt_rows B Bsrc J T ldx dtype".split(),
+            dict(x=p, xt=p, xt_rows=4 * 9, B=4, Bsrc=2, J=7, T=9, ldx=32, dtype=0), [
+                (dict(x=None), b"bad argument"), (dict(xt=None), b"bad argument"),
+                (dict(B=0), b"bad argument"), (dict(Bsrc=0), b"bad argument"), (dict(Bsrc=5), b"bad argument"),
+                (dict(J=0), b"bad argument"), (dict(T=-1), b"bad argument"),
+                (dict(dtype=3), b"unknown dtype"), (dict(dtype=-1), b"unknown dtype"),
+                (dict(ldx=6), b"ldx below J"), (dict(xt_rows=35), b"xt_rows below B*T")])
+    refused("gdx_transpose_out", "yt y y_rows B J T ldy".split(),
+            dict(yt=p, y=p, y_rows=3 * 7, B=3, J=7, T=9, ldy=8), [
+                (dict(yt=None), b"bad argument"), (dict(y=None), b"bad argument"), (dict(B=0), b"bad argument"),
+                (dict(J=0), b"bad argument"), (dict(T=0), b"bad argument"),
+                (dict(ldy=6), b"ldy below J"), (dict(y_rows=20), b"y_rows below B*J")])
+    refused("gdx_small_linear", "A lda W ldw bias out out_rows ldo M N K act".split(),
+            dict(A=p, lda=70, W=p, ldw=96, bias=None, out=p, out_rows=5, ldo=384, M=5, N=384, K=65, act=1), [
+                (dict(A=None), b"bad argument"), (dict(W=None), b"bad argument"), (dict(out=None), b"bad argument"),
+                (dict(M=0, out_rows=0), b"bad argument"), (dict(N=0), b"bad argument"), (dict(K=0), b"bad argument"),
+                (dict(act=2), b"unknown act"), (dict(act=-1), b"unknown act"),
+                (dict(lda=64), b"lda / ldw below K"), (dict(ldw=64), b"lda / ldw below K"),
+                (dict(ldo=383), b"ldo below N"), (dict(out_rows=4), b"out_rows below M")])
+    refused("gdx_gather_rows", "table idx out out_rows M d max_rows".split(),
+            dict(table=p, idx=p, out=p, out_rows=5, M=5, d=384, max_rows=100), [
+                (dict(table=None), b"bad argument"), (dict(idx=None), b"bad argument"), (dict(out=None), b"bad argument"),
+                (dict(M=0), b"bad argument"), (dict(d=0), b"bad argument"), (dict(max_rows=0), b"bad argument"),
+                (dict(out_rows=4), b"out_rows below M")])
+    refused("gdx_mfcc_project", "mfcc W ldw bias pe out out_rows B Bsrc C T d rps off".split(),
+            dict(mfcc=p, W=p, ldw=32, bias=p, pe=None, out=p, out_rows=4 * 66, B=4, Bsrc=2, C=26, T=65, d=512, rps=66, off=1), [
+                (dict(mfcc=None), b"bad argument"), (dict(W=None), b"bad argument"), (dict(bias=None), b"bad argument"),
+                (dict(out=None), b"bad argument"), (dict(B=0), b"bad argument"), (dict(Bsrc=3, B=2), b"bad argument"),
+                (dict(C=0), b"bad argument"), (dict(T=0), b"bad argument"), (dict(d=0), b"bad argument"),
+                (dict(off=-1), b"bad argument"),
+                (dict(C=33, ldw=40), b"C above 32"), (dict(ldw=25), b"ldw below C"), (dict(rps=65), b"rps below T + off"),
+                (dict(out_rows=3 * 66 + 65), b"out_rows below the stored rows")])
+    refused("gdx_token0", "temb tstride seed_emb pe0 enc enc16 enc_rows c2t c2_seed c2 c2_rows state B Bsrc S d dtype".split(),
+            dict(temb=p, tstride=512, seed_emb=p, pe0=None, enc=p, enc16=p, enc_rows=3 * 7 + 1, c2t=p, c2_seed=p, c2=p, c2_rows=4,
+                 state=None, B=4, Bsrc=2, S=7, d=512, dtype=1), [
+                (dict(temb=None), b"bad argument"), (dict(seed_emb=None), b"bad argument"), (dict(enc=None), b"bad argument"),
+                (dict(B=0), b"bad argument"), (dict(Bsrc=0), b"bad argument"), (dict(Bsrc=5), b"bad argument"),
+                (dict(S=0), b"bad argument"), (dict(d=0), b"bad argument"),
+                (dict(dtype=3), b"unknown dtype"), (dict(dtype=0), b"takes no enc16"),
+                (dict(tstride=511), b"tstride"), (dict(tstride=-512), b"tstride"),
+                (dict(c2=None), b"go together"), (dict(c2t=None), b"go together"), (dict(c2_seed=None), b"go together"),
+                (dict(enc_rows=3 * 7), b"enc_rows below the stored rows"), (dict(c2_rows=3), b"c2_rows below B")])
+
+
 # ------------------------------------------------------------------------------- schedule / coefficients
 @pytest.mark.parametrize("sched", ["cosine", "linear"])
 @pytest.mark.parametrize("tag,resp", [("1000", ""), ("ddim10", "ddim10"), ("ddim100", "ddim100"), ("s20", [20])])
