@@ -3,12 +3,17 @@
 Keeps the reference CLI's flags and flow (`sample/generate.py:23-183`): args.json override,
 fixseed, model + diffusion factory, checkpoint load, optional classifier-free-guidance wrapper,
 then `chunks` autoregressive chunks, each a full sampling loop whose seed poses are the last
-`seed_poses` frames of the previous chunk (`:104-107`).  Dataset loading and BVH/MP4 writing
-(GENEA data, bvhsdk, ffmpeg) are out of scope; with `--synthetic` the conditioning is N(0,1).  The chunk tail of the
-reference (`:132-146`: inv_transform with the dataset statistics, position / rotation split; rot2xyz is the identity for
-pose_rep 'xyz') runs on the device (`gdx_postprocess`) whenever the feature count is 6 per joint (GENEA: 83 x 6 = 498),
-with synthetic statistics; `results.npy` then holds `motion` [B, n_joints, 3, T*chunks] and `motion_rot` like the
-reference's, otherwise the normalised poses [B, J, 1, T*chunks].
+`seed_poses` frames of the previous chunk (`:104-107`).  The chunk tail of the reference (`:132-146`: inv_transform with
+the dataset statistics, position / rotation split; rot2xyz is the identity for pose_rep 'xyz') runs on the device
+(`gdx_postprocess`) whenever the feature count is 6 per joint (GENEA: 83 x 6 = 498); `results.npy` then holds `motion`
+[B, n_joints, 3, T*chunks] and `motion_rot` like the reference's, otherwise the normalised poses [B, J, 1, T*chunks].
+
+Two sources of conditioning.  `--dataset genea2023 [--data_dir D]` is the reference's flow (`:45-216`): take k of the
+validation split is sample k, chunk c of it is item `samples_cumulative[k-1] + c` of `Genea2023`; seed poses of chunk 0,
+MFCCs (computed on the GPU), text, lengths, raw audio and ground-truth motion come from the data directory, the tail uses
+its statistics, and `results.npy` / `results.txt` / `results_len.txt` are written.  The BVH, MP4 and WAV files of
+`:218-301` are not: bvhsdk, ffmpeg and soundfile are not dependencies of this project, and what they would hold is in
+`results.npy`.  `--synthetic` needs no data: seed poses and MFCCs are N(0,1) and the tail's statistics are synthetic.
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N ...`; the batch is
 sharded across ranks and gathered once at the end of every chunk (RCCL over xGMI).  Sharded runs draw their noise from
@@ -23,6 +28,8 @@ from .. import engine as E
 from ..model.cfg_sampler import ClassifierFreeSampleModel
 from ..utils import dist_util
 from ..utils.fixseed import fixseed
+from ..data_loaders.get_data import get_dataset_loader
+from ..data_loaders.tensors import gg_collate
 from ..utils.init import init_state_dict, MFCC_DIM
 from ..utils.model_util import create_model_and_diffusion, load_checkpoint, load_model_cached, load_model_wo_clip
 from ..utils.parser_util import generate_args
@@ -72,23 +79,61 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     return outs
 
 
+def chunk_items(samples_cumulative, num_samples, n_chunks):
+    """Dataset index of every (take, chunk) pair, [n_chunks][num_samples]: chunk c of take k is item
+    `samples_cumulative[k-1] + c` (reference `:94-99`).  All pairs are checked here, in the reference's order and with its
+    error, before anything is sampled."""
+    if num_samples > len(samples_cumulative):
+        raise ValueError(f"{num_samples} takes asked for, the split holds {len(samples_cumulative)}")
+    index = []
+    for chunk in range(n_chunks):
+        row = []
+        for take in range(num_samples):
+            item = (0 if take == 0 else int(samples_cumulative[take - 1])) + chunk
+            if item >= samples_cumulative[take]:
+                raise ValueError(f'Chunk {chunk} is out of range for take {take}.')
+            row.append(item)
+        index.append(row)
+    return index
+
+
+def check_data_width(data_width, njoints):
+    """The model is built for `njoints` pose features; a data directory of another width cannot condition or de-normalise it."""
+    if data_width != njoints:
+        raise ValueError(f"the data directory's poses have {data_width} features, the model is built for {njoints}")
+
+
+def host_item(ds, idx):
+    """Item `idx` of a Genea2023 without its MFCCs (zeros stand in): everything `gg_collate` needs that is host data."""
+    take, sample = ds.locate(idx)
+    motion, seed = ds.motion_window(take, sample)
+    return (motion, ds.text_window(take, sample), ds.window, ds.audio_window(take, sample),
+            np.zeros((ds.window, MFCC_DIM), dtype=np.float32), seed)
+
+
 def main(argv=None):
     args = generate_args(argv)
     fixseed(args.seed)
-    rank, world, device = dist_util.init_from_env()
+    rank, world, device = dist_util.init_from_env(arg_device=args.device)   # makes `device` current: nothing exists yet
     if device.type != "cuda":
         raise RuntimeError("sample.generate needs an MI355X GPU: the native path has no CPU fallback")
-    if not args.synthetic:
-        raise NotImplementedError("GENEA dataset loading is outside the hot path; use --synthetic "
-                                  "(checkpoints still load through --model_path)")
     rng = resolve_rng(args.rng, world)
     num_samples = min(args.num_samples if args.num_samples else 41, args.batch_size)
     dist_util.check_world(num_samples, world)       # the same refusal on every rank, before any of them builds a model
     if args.dataset not in ("genea2022", "genea2023") and not args.synthetic_njoints:
         args.synthetic_njoints = 263
-    args.mfcc_input = True if args.synthetic else args.mfcc_input
+    if args.synthetic or not args.model_path:       # random weights: the conditioning this CLI can feed is MFCCs
+        args.mfcc_input = True
+    T = args.num_frames
+    ds = index = None
+    if not args.synthetic:
+        ds = get_dataset_loader(args.dataset, num_samples, T, split='val', hml_mode='text_only', seed_poses=args.seed_poses,
+                                datapath=args.data_dir or None, device=device).dataset
+        index = chunk_items(ds.samples_cumulative, num_samples, args.chunks)
 
     model, diffusion = create_model_and_diffusion(args, None)
+    if ds is not None:
+        check_data_width(ds.mean.shape[-1], model.njoints)
     if args.model_path and args.packed_cache:
         model.to(device)
         how = load_model_cached(model, args.model_path, device, args.packed_cache)
@@ -107,32 +152,47 @@ def main(argv=None):
     model.eval()
 
     lo, hi = dist_util.shard_range(num_samples, rank, world)
-    J, T = model.njoints, args.num_frames
-    g = torch.Generator().manual_seed(args.seed)
-    seed_all = torch.randn(num_samples, J, 1, args.seed_poses, generator=g)
-    split6 = J % 6 == 0                                   # GENEA layout: 3 rotation + 3 position features per joint
-    if split6:
-        stat_rng = np.random.default_rng(args.seed)       # stand-in for the dataset's Mean.npy / Std.npy (fp64)
-        mean, std = stat_rng.normal(size=J), stat_rng.uniform(0.5, 2.0, size=J)
-    extractor = None
-    if args.synthetic_audio:
-        # the reference's audio path (dataset.py:81-95) at its GENEA settings: 22 050 Hz, 30 fps, one MFCC vector per frame
-        from ..data_loaders.mfcc import MfccExtractor
-        stat = np.random.default_rng(args.seed + 1)
-        extractor = MfccExtractor(device, sr=22050, fps=30, mfcc_mean=stat.normal(size=MFCC_DIM),
-                                  mfcc_std=stat.uniform(0.5, 2.0, size=MFCC_DIM))
+    J = model.njoints
+    if ds is not None:
+        shard = {}
 
-    def mfcc_of_chunk(chunk):          # called once per chunk, in order: the host generator's stream is part of the recipe
-        if extractor is not None:
-            audio = 0.1 * torch.randn(num_samples, T * 735, generator=g)[lo:hi].to(device)
-            return torch.stack([extractor(a)[:T].t() for a in audio]).unsqueeze(2).contiguous()     # [nb, 26, 1, T]
-        return torch.randn(num_samples, MFCC_DIM, 1, T, generator=g)[lo:hi].to(device)
+        def shard_y(chunk):            # this rank's takes of one chunk, collated; their MFCCs are computed here, on the device
+            if chunk not in shard:
+                shard.clear()
+                shard[chunk] = gg_collate([ds[i] for i in index[chunk][lo:hi]])[1]["y"]
+            return shard[chunk]
+
+        split6, mean, std = True, ds.mean, ds.std
+        first_seed = shard_y(0)["seed"].to(device)
+
+        def mfcc_of_chunk(chunk):
+            return shard_y(chunk)["mfcc"]
+    else:
+        g = torch.Generator().manual_seed(args.seed)
+        first_seed = torch.randn(num_samples, J, 1, args.seed_poses, generator=g)[lo:hi].to(device)
+        split6 = J % 6 == 0                                   # GENEA layout: 3 rotation + 3 position features per joint
+        if split6:
+            stat_rng = np.random.default_rng(args.seed)       # stand-in for the dataset's Mean.npy / Std.npy (fp64)
+            mean, std = stat_rng.normal(size=J), stat_rng.uniform(0.5, 2.0, size=J)
+        extractor = None
+        if args.synthetic_audio:
+            # the reference's audio path (dataset.py:81-95) at its GENEA settings: 22 050 Hz, 30 fps, one MFCC vector per frame
+            from ..data_loaders.mfcc import MfccExtractor
+            stat = np.random.default_rng(args.seed + 1)
+            extractor = MfccExtractor(device, sr=22050, fps=30, mfcc_mean=stat.normal(size=MFCC_DIM),
+                                      mfcc_std=stat.uniform(0.5, 2.0, size=MFCC_DIM))
+
+        def mfcc_of_chunk(chunk):          # called once per chunk, in order: the host generator's stream is part of the recipe
+            if extractor is not None:
+                audio = 0.1 * torch.randn(num_samples, T * 735, generator=g)[lo:hi].to(device)
+                return torch.stack([extractor(a)[:T].t() for a in audio]).unsqueeze(2).contiguous()     # [nb, 26, 1, T]
+            return torch.randn(num_samples, MFCC_DIM, 1, T, generator=g)[lo:hi].to(device)
 
     def on_chunk(chunk):
         if rank == 0:
             print(f"### Sampling chunk {chunk + 1} of {args.chunks}")
 
-    outs = sample_chunks(model, diffusion, seed_all[lo:hi].to(device), mfcc_of_chunk, args.chunks, T, args.seed_poses,
+    outs = sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, args.chunks, T, args.seed_poses,
                          guidance_param=args.guidance_param, sampler=args.sampler, eta=args.eta, rng=rng,
                          philox_seed=args.seed, sample_offset=lo, progress=args.progress and rank == 0, on_chunk=on_chunk,
                          plms_order=args.plms_order)
@@ -147,15 +207,43 @@ def main(argv=None):
             else:
                 out_chunks.append(full.cpu().numpy())
     if rank == 0:
-        out_path = args.output_dir or os.path.join(os.getcwd(), f"samples_synthetic_seed{args.seed}")
+        out_path = args.output_dir or os.path.join(os.getcwd(), f"samples_{'synthetic' if args.synthetic else args.dataset}_seed{args.seed}")
         os.makedirs(out_path, exist_ok=True)
         motion = np.concatenate(out_chunks, axis=3)
         res = {"motion": motion, "num_samples": num_samples, "num_chunks": args.chunks}
         if split6:
             res["motion_rot"] = np.concatenate(rot_chunks, axis=3)
-        np.save(os.path.join(out_path, "results.npy"), res, allow_pickle=True)
-        print(f"saved results to [{os.path.join(out_path, 'results.npy')}] motion {motion.shape}")
+        if ds is not None:
+            res.update(ground_truth(ds, index, device))
+        npy_path = os.path.join(out_path, "results.npy")
+        np.save(npy_path, res, allow_pickle=True)
+        if ds is not None:
+            with open(npy_path.replace('.npy', '.txt'), 'w') as f:
+                f.write('\n'.join(res["text"]))
+            with open(npy_path.replace('.npy', '_len.txt'), 'w') as f:
+                f.write('\n'.join(str(n) for n in res["lengths"]))
+            print("BVH, MP4 and WAV files are not written (they need bvhsdk, ffmpeg and soundfile): "
+                  "results.npy holds the motion, the ground truth and the audio they would contain")
+        print(f"saved results to [{npy_path}] motion {motion.shape}")
     return 0
+
+
+def ground_truth(ds, index, device):
+    """What the data directory itself says about the sampled takes (reference `:149-193`), read on the host by the rank
+    that writes the results: per chunk the collated ground-truth motion through the same tail as the samples, the text, the
+    lengths and the raw audio; chunks are joined along time, text and lengths listed chunk by chunk."""
+    pos_chunks, rot_chunks, audio, text, lengths = [], [], [], [], []
+    for row in index:
+        gt_motion, cond = gg_collate([host_item(ds, i) for i in row])
+        pos, rot = E.postprocess(gt_motion.to(device), ds.mean, ds.std)
+        pos_chunks.append(pos.cpu().numpy())
+        rot_chunks.append(rot.cpu().numpy())
+        audio.append(cond["y"]["audio"].numpy())
+        text += cond["y"]["text"]
+        lengths.append(cond["y"]["lengths"].numpy())
+    return {"gt_motion": np.concatenate(pos_chunks, axis=3), "gt_motion_rot": np.concatenate(rot_chunks, axis=3),
+            "audio": np.concatenate(audio, axis=1), "text": text, "lengths": np.concatenate(lengths, axis=0),
+            "takes": [ds.takes[k][0] for k in range(len(index[0]))]}
 
 
 if __name__ == "__main__":

@@ -6,7 +6,8 @@ is commented out, `:26-41`); multi-GPU here is new functionality around the hot 
 a batch are independent, so each rank samples a contiguous shard with zero communication and one
 RCCL gather over xGMI at the end returns the batch to rank 0.  N > 1 has only been
 exercised on CPU (gloo, world size 2) and as several ranks sharing one GPU; RCCL across GPUs is the driver's run.
-`check_world(total)` is the callers' up-front refusal of more ranks than samples.
+`check_world(total)` is the callers' up-front refusal of more ranks than samples.  `select_device(arg, environ)` decides which
+GPU a process uses: `--device N` on its own, LOCAL_RANK under a launcher.
 """
 import os
 
@@ -33,13 +34,30 @@ def load_state_dict(path, **kwargs):
     return th.load(path, **kwargs)
 
 
+def select_device(arg_device=0, environ=None):
+    """The GPU of this process.  Started on its own (no LOCAL_RANK in `environ`) it is `--device`; under a launcher every
+    rank takes the GPU of its LOCAL_RANK, and a `--device` other than the default 0 that names another GPU is refused:
+    one of the two would be ignored silently."""
+    environ = os.environ if environ is None else environ
+    arg = int(arg_device or 0)
+    if "LOCAL_RANK" not in environ:
+        return th.device(f"cuda:{arg}")
+    local = int(environ["LOCAL_RANK"])
+    if arg not in (0, local):
+        raise ValueError(f"--device {arg} conflicts with LOCAL_RANK={local}: under a launcher each rank uses the GPU of "
+                         f"its LOCAL_RANK (leave --device at its default)")
+    return th.device(f"cuda:{local}")
+
+
 # --------------------------------------------------------------------------- multi-GPU sharding
-def init_from_env(backend=None):
-    """One process per GPU (torchrun / torch.distributed.run env).  Returns (rank, world, device)."""
+def init_from_env(backend=None, arg_device=0):
+    """One process per GPU (torchrun / torch.distributed.run env), or one process on GPU `arg_device`.  Makes that GPU the
+    current device -- before the caller creates a model, an engine or a tensor: libgdx allocates on the current device --
+    and returns (rank, world, device)."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
     use_cuda = th.cuda.is_available()
+    local = select_device(arg_device, os.environ).index
     if use_cuda and os.environ.get("GDX_SINGLE_GPU_RANKS"):   # rehearsal: several ranks share GPU 0 (gloo backend)
         local = 0
     device = th.device(f"cuda:{local}") if use_cuda else th.device("cpu")

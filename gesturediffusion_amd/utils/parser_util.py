@@ -23,7 +23,9 @@ def parse_and_load_from_model(parser, argv=None):
     for add in (add_data_options, add_model_options, add_diffusion_options, add_native_options):
         add(parser)
     args = parser.parse_args(argv)
-    if not (args.synthetic and not args.model_path):     # additive: --synthetic without a checkpoint has no args.json
+    asked_data_dir = args.data_dir
+    # additive: without a checkpoint there is no args.json -- --synthetic, or a data directory sampled with random weights
+    if not (not args.model_path and (args.synthetic or args.data_dir)):
         stored_path = os.path.join(os.path.dirname(args.model_path), "args.json")
         assert os.path.exists(stored_path), "Arguments json file was not found!"
         with open(stored_path) as f:
@@ -33,6 +35,8 @@ def parse_and_load_from_model(parser, argv=None):
                 setattr(args, name, stored[name])
             else:
                 print("Warning: was not able to load [{}], using default value [{}] instead.".format(name, getattr(args, name)))
+    if asked_data_dir:       # additive: where the data lies is this machine's business, not the training run's
+        args.data_dir = asked_data_dir
     if args.cond_mask_prob == 0:
         args.guidance_param = 1
     return args
@@ -84,14 +88,15 @@ def add_model_options(parser):
 def add_data_options(parser):
     group = parser.add_argument_group('dataset')
     group.add_argument("--dataset", default='humanml', choices=['genea2022', 'genea2023'], type=str)
-    group.add_argument("--data_dir", default="", type=str)
+    group.add_argument("--data_dir", default="", type=str,
+                       help="GENEA 2023 data directory ('' = the reference's ./dataset/Genea2023/).")
     group.add_argument("--num_frames", default=120, type=int)
 
 
 def add_sampling_options(parser):
     group = parser.add_argument_group('sampling')
     group.add_argument("--model_path", default='', type=str,
-                       help="Path to model####.pt (required unless --synthetic).")
+                       help="Path to model####.pt (without it --synthetic and --data_dir runs use random weights).")
     group.add_argument("--output_dir", default='', type=str)
     group.add_argument("--num_samples", default=10, type=int)
     group.add_argument("--num_repetitions", default=3, type=int)
