@@ -4,6 +4,7 @@
 // loops (diffusion/gaussian_diffusion.py:598-730, 879-993).  C ABI in include/gdx.h; the handle's weights are in weights.hip.
 #include "gdx_host.h"
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -596,6 +597,45 @@ extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void
         u.eps_out = slot(k); u.out = a->x;
         for (int j = 0; j < 3; ++j) u.eps_hist[j] = j < u.kind - 1 ? slot(k - 1 - j) : nullptr;
         if (gdx_plms_step(&u, stream)) return -1;
+    }
+    return 0;
+}
+
+// dpm_solver_sample_loop (DPM-Solver++ multistep, gdx.h): per step the denoiser through forward_core on the pose-layout state
+// (the entry gdx_forward uses: same bits as the step-wise protocol) and one fused dpm_step_kernel launch (sampler.hip).  No
+// graph replay and no token-major variant: the solver runs 10-40 steps.  The argument checks need no handle and come first
+// (then null handle, then not prepared), so every refusal precedes the first HIP call.
+extern "C" int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* stream) {
+    if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_dpm_loop: null argument");
+    if (check_mode("gdx_dpm_loop", a->mode, a->scale)) return -1;
+    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
+        a->run_steps > a->first_index + 1)
+        return fail("gdx_dpm_loop: bad step range");
+    if (a->order < 1 || a->order > 3) return fail("gdx_dpm_loop: order must be 1, 2 or 3");
+    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_dpm_loop: mask without motion");
+    if (a->order > 1 && !a->hist) return fail("gdx_dpm_loop: missing history (hist is the caller's)");
+    if (check_ready(h, "gdx_dpm_loop")) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B;
+    const size_t per = (size_t)h->J * h->T;
+    if (B > 65535) return fail("gdx_dpm_loop: batch exceeds 65535");
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    auto slot = [&](int k) { return a->hist + (size_t)(k % a->order) * B * per; };
+    gdx_dpm_step_args_t u;
+    memset(&u, 0, sizeof(u));
+    u.batch = B; u.njoints = h->J; u.frames = h->T;
+    u.coef = a->coef; u.x = a->x; u.out = a->x;
+    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
+    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
+    int k = a->k_base;
+    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
+        if (denoise_step(h, a->x, idx, a->mode, h->x0, s)) return -1;
+        u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, lower order at the end
+        u.step_index = idx;
+        for (int j = 0; j < 2; ++j) u.hist[j] = j < u.order - 1 ? slot(k - 1 - j) : nullptr;
+        u.pred_out = a->order > 1 ? slot(k) : nullptr;
+        if (gdx_dpm_step(&u, stream)) return -1;
     }
     return 0;
 }

@@ -183,6 +183,18 @@ __device__ __forceinline__ float plms_tail(const float* c, float x, float ep, fl
     return __fadd_rn(__fmul_rn(mean, nz), __fmul_rn(keep, __fsub_rn(1.0f, nz)));
 }
 
+// DPM-Solver++ multistep update in the data-prediction form (Lu et al. 2022, arXiv:2211.01095, Algorithm 2 and its third-order
+// extension; gdx.h gdx_dpm_step): a*x + (w0*m0 [+ w1*m1 [+ w2*m2]]) with m0 this step's x0 prediction and m1 / m2 the two
+// before it.  Every order is linear in the predictions, so the host collects the weights in fp64 and rounds them once; NH =
+// history terms read, w = the row's columns of the launched order.
+template <int NH>
+__device__ __forceinline__ float dpm_multistep(float a, const float* w, float x, float m0, float m1, float m2) {
+    float d = __fmul_rn(w[0], m0);
+    if (NH >= 1) d = __fadd_rn(d, __fmul_rn(w[1], m1));
+    if (NH >= 2) d = __fadd_rn(d, __fmul_rn(w[2], m2));
+    return __fadd_rn(__fmul_rn(a, x), d);
+}
+
 struct UpdateDev {
     int kind;
     long per_sample;        // J*T
@@ -405,6 +417,48 @@ __global__ __launch_bounds__(256) void plms_step_kernel(const PlmsStepDev a) {
     }
     if (a.eps_out) store4<VEC>(a.eps_out, e0, nval, eps);
     if (a.pred) store4<VEC>(a.pred, e0, nval, x0);
+    store4<VEC>(a.out, e0, nval, r);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// One DPM-Solver++ multistep step in one pass (gdx.h gdx_dpm_step): update_kernel's pred_xstart (CFG blend -> inpainting ->
+// clamp) as m0, then dpm_multistep over it and NH older predictions.  Grid (ceil(groups / 256), B): blockIdx.y is the sample,
+// NH a template argument.  The row's weights of order NH + 1 start at column 1 + NH*(NH + 1)/2: (a, w1_0, w2_0, w2_1, w3_0,
+// w3_1, w3_2, 0).  Memory-bound: per element 2 + NH reads (3 + NH under guidance, + mask and motion under inpainting) and
+// two writes.
+struct DpmStepDev {
+    long per_sample, groups;
+    const float* coef;
+    const int64_t* t;
+    int step_index;
+    const float *x, *x0c, *x0u, *scale;
+    const uint8_t* mask;
+    const float* motion;
+    const float *m1, *m2;
+    int clip;
+    float *out, *pred;
+};
+
+template <int NH, bool VEC>
+__global__ __launch_bounds__(256) void dpm_step_kernel(const DpmStepDev a) {
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    if (grp >= a.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
+    const long e0 = g.e0;
+    const int nval = g.nval;
+    const long idx = a.t ? a.t[g.b] : a.step_index;
+    const float* c = a.coef + idx * 8;
+    const float* w = c + 1 + NH * (NH + 1) / 2;
+
+    const f32x4 x = load4<VEC>(a.x, e0, nval);
+    const f32x4 m0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, e0, nval);
+    f32x4 m1 = {0.f, 0.f, 0.f, 0.f}, m2 = m1;
+    if (NH >= 1) m1 = load4<VEC>(a.m1, e0, nval);
+    if (NH >= 2) m2 = load4<VEC>(a.m2, e0, nval);
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = dpm_multistep<NH>(c[0], w, x[i], m0[i], m1[i], m2[i]);
+    if (a.pred) store4<VEC>(a.pred, e0, nval, m0);
     store4<VEC>(a.out, e0, nval, r);
 }
 
@@ -807,6 +861,45 @@ extern "C" int gdx_plms_step(const gdx_plms_step_args_t* a, void* stream) {
     if (vec) launch_plms_step<true>(k, grid, (hipStream_t)stream, d);
     else launch_plms_step<false>(k, grid, (hipStream_t)stream, d);
     return launch_status("gdx_plms_step: launch failed");
+}
+
+template <bool VEC>
+static void launch_dpm_step(int nh, dim3 grid, hipStream_t s, const gdx::DpmStepDev& d) {
+    using namespace gdx;
+    const dim3 block(256);
+    switch (nh) {
+        case 0: hipLaunchKernelGGL((dpm_step_kernel<0, VEC>), grid, block, 0, s, d); break;
+        case 1: hipLaunchKernelGGL((dpm_step_kernel<1, VEC>), grid, block, 0, s, d); break;
+        default: hipLaunchKernelGGL((dpm_step_kernel<2, VEC>), grid, block, 0, s, d); break;
+    }
+}
+
+extern "C" int gdx_dpm_step(const gdx_dpm_step_args_t* a, void* stream) {
+    using namespace gdx;
+    if (!a || !a->coef || !a->x || !a->x0_cond || !a->out) return gdx_set_error_("gdx_dpm_step: null argument");
+    if (a->order < 1 || a->order > 3) return gdx_set_error_("gdx_dpm_step: order must be 1, 2 or 3");
+    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return gdx_set_error_("gdx_dpm_step: bad shape");
+    if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_dpm_step: CFG needs scale");
+    if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_dpm_step: mask without motion");
+    const int nh = a->order - 1;                                     // history slots this order reads
+    for (int i = 0; i < nh; ++i) {
+        if (!a->hist[i]) return gdx_set_error_("gdx_dpm_step: missing history for this order");
+        if (a->pred_out && a->pred_out == a->hist[i]) return gdx_set_error_("gdx_dpm_step: pred_out aliases a history slot it reads");
+    }
+    DpmStepDev d;
+    d.per_sample = (long)a->njoints * a->frames;
+    d.groups = (d.per_sample + 3) / 4;
+    if (a->batch == 0 || d.per_sample == 0) return 0;
+    d.coef = a->coef; d.t = a->t; d.step_index = a->step_index;
+    d.x = a->x; d.x0c = a->x0_cond; d.x0u = a->x0_uncond; d.scale = a->scale;
+    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion;
+    d.m1 = nh > 0 ? a->hist[0] : nullptr; d.m2 = nh > 1 ? a->hist[1] : nullptr;
+    d.clip = a->clip_denoised; d.out = a->out; d.pred = a->pred_out;
+    const bool vec = vec_ok(d.per_sample, d.x, d.x0c, d.x0u, d.mask, d.motion, d.m1, d.m2, d.out, d.pred);
+    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
+    if (vec) launch_dpm_step<true>(nh, grid, (hipStream_t)stream, d);
+    else launch_dpm_step<false>(nh, grid, (hipStream_t)stream, d);
+    return launch_status("gdx_dpm_step: launch failed");
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,

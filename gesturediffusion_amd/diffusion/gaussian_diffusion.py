@@ -10,6 +10,7 @@ coefficient rows; every per-element operation runs in libgdx.so:
   * `gdx_sampler_update`  CFG blend + inpainting + posterior mean / DDIM step + noise, one pass
   * `gdx_sample_loop`     the whole loop enqueued from C++ with in-kernel Philox noise
   * `gdx_plms_step` / `gdx_plms_loop`   plms_sample_loop (`:995-1190`): one fused multistep update per step, the loop in C++
+  * `gdx_dpm_step` / `gdx_dpm_loop`     dpm_solver_sample_loop: DPM-Solver++ multistep (2M / 3M), additive, same pattern
   * `gdx_bpd_terms` / `gdx_bpd_loop`   the variational bound in bits/dim (`_vb_terms_bpd` :1192-1225, `_prior_bpd`
                           :1519-1535, `calc_bpd_loop` :1537-1592, and `training_losses` under LossType.KL / RESCALED_KL)
 
@@ -899,6 +900,158 @@ class GaussianDiffusion:
                 out = self.plms_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                        cond_fn=cond_fn, model_kwargs=model_kwargs,
                                        cond_fn_with_grad=cond_fn_with_grad, order=order, old_out=old_out)
+            yield out
+            old_out = out
+            img = out["sample"]
+
+    # ------------------------------------------------------------------ DPM-Solver++ multistep (no counterpart in the reference)
+    def dpm_coef_rows(self):
+        """The fp64 rows behind dpm_coef_table: [num_timesteps, 8] = (a, w1_0, w2_0, w2_1, w3_0, w3_1, w3_2, 0), the
+        DPM-Solver++ multistep update of order 1..3 (Lu et al. 2022, arXiv:2211.01095) collected into weights of the x0
+        predictions m0 (this step), m1, m2 (the two executed before it, at indices i + 1, i + 2): x' = a*x + sum_j w_j*m_j.
+        Formulas, special rows and the order rule: include/gdx.h at gdx_dpm_step / gdx_dpm_loop."""
+        n = self.num_timesteps
+        ab, abp = self.alphas_cumprod, self.alphas_cumprod_prev
+        lam = 0.5 * np.log(ab / (1.0 - ab))
+        rows = np.zeros((n, 8), dtype=np.float64)
+        rows[0, 1] = 1.0                                  # abar_p = 1: sigma_p = 0, h = inf, a = 0, phi = 1
+        for i in range(1, n):
+            alpha_p = math.sqrt(abp[i])
+            h = 0.5 * math.log(abp[i] / (1.0 - abp[i])) - lam[i]
+            em1 = math.expm1(-h)
+            phi = -alpha_p * em1
+            rows[i, 0] = math.sqrt(1.0 - abp[i]) / math.sqrt(1.0 - ab[i])
+            rows[i, 1] = phi
+            if i + 1 < n:
+                r0 = (lam[i] - lam[i + 1]) / h
+                rows[i, 2] = phi + 0.5 * phi / r0
+                rows[i, 3] = -0.5 * phi / r0
+            if i + 2 < n:
+                r1 = (lam[i + 1] - lam[i + 2]) / h
+                c1 = alpha_p * (em1 / h + 1.0)
+                c2 = alpha_p * ((em1 + h) / (h * h) - 0.5)
+                rho = r0 / (r0 + r1)
+                d10 = c1 * (1.0 + rho) - c2 / (r0 + r1)   # weight of D1_0 = (m0 - m1) / r0
+                d11 = c2 / (r0 + r1) - c1 * rho           # weight of D1_1 = (m1 - m2) / r1
+                rows[i, 4] = phi + d10 / r0
+                rows[i, 5] = d11 / r1 - d10 / r0
+                rows[i, 6] = -d11 / r1
+        return rows
+
+    def dpm_coef_table(self, device):
+        """[num_timesteps, 8] fp32 rows consumed by gdx_dpm_step / gdx_dpm_loop: dpm_coef_rows rounded once (.float(), the
+        convention of every other table here)."""
+        key = ("dpm", str(device))
+        if key not in self._coef_cache:
+            self._coef_cache[key] = th.from_numpy(self.dpm_coef_rows()).float().to(device)
+        return self._coef_cache[key]
+
+    def dpm_solver_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, order=2,
+                          old_out=None):
+        """One DPM-Solver++ multistep step (gdx_dpm_step): the x0 prediction from _pred_xstart (so EPSILON / PREVIOUS_X /
+        denoised_fn work as elsewhere; cond_fn through condition_score), then the update of order min(order, predictions
+        kept + 1, t + 1) over it and old_out["old_pred"] (oldest first, at most order - 1 kept).  t must be the same for the
+        whole batch: the history belongs to one index sequence.  Returns {"sample", "pred_xstart", "old_pred"}."""
+        if order not in (1, 2, 3):
+            raise ValueError('order is invalid (should be int from 1-3).')
+        xc = E.f32c(x, "x")
+        tt = E.require_device(t, "t").to(th.int64).contiguous()
+        rows = set(tt.tolist())
+        if len(rows) != 1:
+            raise ValueError("dpm_solver_sample: t must be the same for the whole batch")
+        i = rows.pop()
+        pred = self._pred_xstart(model, xc, tt, clip_denoised, denoised_fn, model_kwargs)
+        used = pred
+        if cond_fn is not None:                           # condition_score (reference :452-472)
+            grad = E.f32c(self._call_cond_fn(cond_fn, xc, tt, model_kwargs or {}), "cond_fn gradient")
+            used = E.plms_update(7, self.coef_table(GDX_SAMPLER_DDIM, xc.device, 0.0), tt, xc, pred,
+                                 eps=[grad, self._cond_coef(xc.device)])
+        old_pred = list(old_out["old_pred"]) if old_out is not None else []
+        cur = min(order, len(old_pred) + 1, i + 1)
+        sample = E.dpm_step(cur, self.dpm_coef_table(xc.device), xc, used, th.empty_like(xc), hist=old_pred[::-1][:cur - 1],
+                            step_index=i)
+        old_pred.append(used)
+        return {"sample": sample, "pred_xstart": pred, "old_pred": old_pred[-(order - 1):] if order > 1 else []}
+
+    def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                               model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                               randomize_class=False, cond_fn_with_grad=False, order=2, *, fused=True, rng="torch",
+                               philox_seed=0, sample_offset=0):
+        """DPM-Solver++ multistep sampling (2M by default) with plms_sample_loop's signature.  A native START_X denoiser (or
+        its ClassifierFreeSampleModel) without cond_fn / denoised_fn runs the whole loop inside libgdx (gdx_dpm_loop: one
+        forward and one fused update launch per step); every other case, and fused=False, goes step by step through
+        dpm_solver_sample.  Both give the same bits.  The solver gains its order only on steps spaced evenly in log-SNR:
+        use the "logsnrN" respacing.  rng / philox_seed / sample_offset choose how x_T is drawn when `noise` is None (the
+        sampler draws nothing else)."""
+        if rng not in ("torch", "philox"):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        if order not in (1, 2, 3):
+            raise ValueError('order is invalid (should be int from 1-3).')
+        if cond_fn_with_grad or randomize_class:
+            raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
+        if (fused and _is_native(model) and denoised_fn is None and cond_fn is None
+                and self.model_mean_type == ModelMeanType.START_X):
+            if model_kwargs is None:
+                model_kwargs = {}
+            device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                      philox_seed, sample_offset, None)
+            return self._fused_dpm_loop(model, img, indices, model_kwargs, int(order), progress, clip_denoised)
+        final = None
+        for sample in self.dpm_solver_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                              denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                                              model_kwargs=model_kwargs, device=device, progress=progress,
+                                                              skip_timesteps=skip_timesteps, init_image=init_image,
+                                                              order=order, rng=rng, philox_seed=philox_seed,
+                                                              sample_offset=sample_offset):
+            final = sample
+        return final["sample"]
+
+    def _fused_dpm_loop(self, model, img, indices, model_kwargs, order, progress, clip_denoised):
+        """Whole loop inside libgdx (gdx_dpm_loop).  The history of x0 predictions lives in a tensor of this call; with
+        `progress` the loop is issued in blocks of NOISE_BLOCK steps, one synchronisation per block."""
+        self._check_supported()
+        if self.rescale_timesteps:
+            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
+        x = E.f32c(img, "x_T").clone()
+        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
+        n = len(indices)
+        coef, tmap = self.dpm_coef_table(x.device), self._timestep_map()
+        hist = th.empty((order, *x.shape), device=x.device, dtype=th.float32) if order > 1 else None
+        block = min(n, NOISE_BLOCK) if progress else n
+        bar = None
+        if progress:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=n)
+        k = 0
+        while k < n:
+            nb = min(block, n - k)
+            eng.dpm_loop(x, mode, order, coef, tmap, indices[k], hist, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+                         clip_denoised=clip_denoised, run_steps=nb, k_base=k)
+            k += nb
+            if bar is not None:
+                th.cuda.current_stream(x.device).synchronize()
+                bar.update(nb)
+        if bar is not None:
+            bar.close()
+        return x
+
+    def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                           cond_fn=None, model_kwargs=None, device=None, progress=False, skip_timesteps=0,
+                                           init_image=None, randomize_class=False, cond_fn_with_grad=False, order=2, *,
+                                           rng="torch", philox_seed=0, sample_offset=0):
+        if cond_fn_with_grad or randomize_class:
+            raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
+        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                  philox_seed, sample_offset, None)
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        old_out = None
+        for i in indices:
+            t = th.full((shape[0],), i, device=device, dtype=th.long)
+            with th.no_grad():
+                out = self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                             cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, old_out=old_out)
             yield out
             old_out = out
             img = out["sample"]

@@ -11,10 +11,29 @@ import torch as th
 from .gaussian_diffusion import GaussianDiffusion
 
 
-def space_timesteps(num_timesteps, section_counts):
+def space_timesteps(num_timesteps, section_counts, betas=None):
     """Set of original timesteps to keep.  "ddimN": the first integer stride that yields exactly N steps; otherwise
     a list (or comma-separated string) of per-section counts, each section sampled at an even fractional stride whose
-    running position is accumulated in floating point and rounded (the accumulation order decides ties)."""
+    running position is accumulated in floating point and rounded (the accumulation order decides ties).
+
+    "logsnrN" (additive; the spacing the DPM-Solver++ sampler needs): for each of N targets uniform in lambda =
+    0.5*log(abar / (1 - abar)) between lambda of the last and of the first timestep, the timestep whose lambda is nearest;
+    0 and num_timesteps - 1 are always kept.  Near t = 0 lambda moves by more than a target gap per timestep, so neighbouring
+    targets can pick the same timestep: duplicates collapse and FEWER than N steps can result.  `betas` is the schedule the
+    lambdas are taken from (the linear schedule of num_timesteps steps when not given); the other spacings ignore it."""
+    if isinstance(section_counts, str) and section_counts.startswith("logsnr"):
+        want = int(section_counts[6:])
+        if want < 2:
+            raise ValueError(f"logsnr spacing needs at least 2 steps, got {want}")
+        if betas is None:
+            from .gaussian_diffusion import get_named_beta_schedule
+            betas = get_named_beta_schedule("linear", num_timesteps)
+        abar = np.cumprod(1.0 - np.asarray(betas, dtype=np.float64))
+        assert abar.shape == (num_timesteps,)
+        lam = 0.5 * np.log(abar / (1.0 - abar))
+        targets = np.linspace(lam[-1], lam[0], want)
+        kept = {int(np.argmin(np.abs(lam - target))) for target in targets}
+        return kept | {0, num_timesteps - 1}
     if isinstance(section_counts, str) and section_counts.startswith("ddim"):
         want = int(section_counts[4:])
         stride = next((s for s in range(1, num_timesteps) if -(-num_timesteps // s) == want), None)

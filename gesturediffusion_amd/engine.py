@@ -203,6 +203,19 @@ class Engine:
         _lib.check(self.lib.gdx_plms_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
         self._keep_loop = (tmap,)
 
+    def dpm_loop(self, x, mode, order, coef, timestep_map, first_index, hist=None, scale=None, inpaint_mask=None,
+                 inpaint_motion=None, clip_denoised=False, run_steps=0, k_base=0):
+        """gdx_dpm_loop: x is updated in place; hist [order, B, J, 1, T] (order > 1) is the caller's and carries the x0
+        predictions of the multistep history from one block (run_steps / k_base) to the next."""
+        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
+        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        a = _lib.DpmLoopArgs(mode=mode, order=order, num_steps=len(tmap), first_index=first_index, coef=coef.data_ptr(),
+                             timestep_map=tmap.ctypes.data, x=x.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
+                             inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
+                             k_base=k_base, hist=p(hist))
+        _lib.check(self.lib.gdx_dpm_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
+        self._keep_loop = (tmap,)
+
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
         _lib.check(self.lib.gdx_forward_flops(self.handle, mode, C.byref(f)), self.lib)
@@ -315,6 +328,23 @@ def plms_step(kind, coef, x, x0_cond, out, eps_out=None, eps_hist=(), t=None, st
     for i, e in enumerate(eps_hist):
         a.eps_hist[i] = e.data_ptr()
     _lib.check(lib.gdx_plms_step(C.byref(a), _stream(x0_cond.device)), lib)
+    return out
+
+
+def dpm_step(order, coef, x, x0_cond, out, hist=(), t=None, step_index=0, x0_uncond=None, scale=None, inpaint_mask=None,
+             inpaint_motion=None, clip_denoised=False, pred_out=None):
+    """gdx_dpm_step: one DPM-Solver++ multistep step in one pass (include/gdx.h).  order 1..3 over the x0 prediction formed
+    here and hist (older predictions, newest first; order - 1 of them are read); coef = dpm_coef_table rows."""
+    lib = _lib.load()
+    B, J, F, T = x0_cond.shape
+    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
+    a = _lib.DpmStepArgs(order=order, batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(), t=p(t), step_index=step_index,
+                         x=x.data_ptr(), x0_cond=x0_cond.data_ptr(), x0_uncond=p(x0_uncond), scale=p(scale),
+                         inpaint_mask=p(inpaint_mask), inpaint_motion=p(inpaint_motion),
+                         clip_denoised=int(bool(clip_denoised)), out=out.data_ptr(), pred_out=p(pred_out))
+    for i, m in enumerate(hist):
+        a.hist[i] = p(m)
+    _lib.check(lib.gdx_dpm_step(C.byref(a), _stream(x0_cond.device)), lib)
     return out
 
 

@@ -101,8 +101,9 @@ def create_gaussian_diffusion(args):
     additive (the reference hard-codes ''): '' keeps every step."""
     respacing = getattr(args, "timestep_respacing", "") or [DIFFUSION_STEPS]
     variance = gd.ModelVarType.FIXED_SMALL if args.sigma_small else gd.ModelVarType.FIXED_LARGE
-    return SpacedDiffusion(use_timesteps=space_timesteps(DIFFUSION_STEPS, respacing),
-                           betas=gd.get_named_beta_schedule(args.noise_schedule, DIFFUSION_STEPS),
+    betas = gd.get_named_beta_schedule(args.noise_schedule, DIFFUSION_STEPS)
+    return SpacedDiffusion(use_timesteps=space_timesteps(DIFFUSION_STEPS, respacing, betas=betas),   # betas: "logsnrN" only
+                           betas=betas,
                            model_mean_type=gd.ModelMeanType.START_X, model_var_type=variance,
                            loss_type=gd.LossType.MSE, rescale_timesteps=False, lambda_vel=args.lambda_vel,
                            lambda_rcxyz=args.lambda_rcxyz, lambda_fc=args.lambda_fc)

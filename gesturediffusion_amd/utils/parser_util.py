@@ -121,11 +121,15 @@ def add_native_options(parser):
                        help="Pose channels for --synthetic when --dataset is not a GENEA set (e.g. 263).")
     group.add_argument("--arch_version", default='mdm', choices=['mdm', 'mdm_old'],
                        help="mdm = V2 (model/mdm.py), mdm_old = V1 encoder-only topology (model/mdm_old.py).")
-    group.add_argument("--sampler", default='p', choices=['p', 'ddim', 'plms'],
-                       help="p_sample_loop (reference default), ddim_sample_loop or plms_sample_loop.")
+    group.add_argument("--sampler", default='p', choices=['p', 'ddim', 'plms', 'dpmpp'],
+                       help="p_sample_loop (reference default), ddim_sample_loop, plms_sample_loop or dpm_solver_sample_loop "
+                            "(DPM-Solver++ multistep; use it with --timestep_respacing logsnrN).")
     group.add_argument("--plms_order", default=2, type=int, choices=[2, 3, 4],
                        help="--sampler plms: order of the Adams-Bashforth multistep update.")
-    group.add_argument("--timestep_respacing", default='', type=str, help="e.g. ddim100; '' = all 1000 steps.")
+    group.add_argument("--dpm_order", default=2, type=int, choices=[1, 2, 3],
+                       help="--sampler dpmpp: order of the multistep update (1 = DDIM at eta 0, 2 = 2M, 3 = 3M).")
+    group.add_argument("--timestep_respacing", default='', type=str,
+                       help="e.g. ddim100, or logsnr20 (at most 20 steps, even in log-SNR); '' = all 1000 steps.")
     group.add_argument("--eta", default=0.0, type=float)
     group.add_argument("--rng", default=None, choices=['torch', 'philox'],
                        help="torch = the reference's generator and draw order (single-GPU default); philox = in-kernel "

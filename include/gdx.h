@@ -249,6 +249,45 @@ typedef struct {
 } gdx_plms_step_args_t;
 int gdx_plms_step(const gdx_plms_step_args_t* a, void* stream);
 
+/* One DPM-Solver++ multistep step over [B,J,1,T] in ONE pass (Lu et al. 2022, arXiv:2211.01095: the data-prediction solver of
+ * Algorithm 2 and its third-order extension; no counterpart in the reference).  With the diffusion's own (possibly respaced)
+ * tables at index i: abar_i = alphas_cumprod[i], alpha_i = sqrt(abar_i), sigma_i = sqrt(1 - abar_i), lambda_i =
+ * 0.5*log(abar_i / (1 - abar_i)); subscript p = the step's target, from alphas_cumprod_prev[i];  h = lambda_p - lambda_i,
+ * a = sigma_p / sigma_i, phi = -alpha_p*expm1(-h);  m0 = this step's x0 prediction, m1 / m2 those of the two previous executed
+ * steps (indices i+1, i+2);  r0 = (lambda_i - lambda_{i+1}) / h, r1 = (lambda_{i+1} - lambda_{i+2}) / h:
+ *   order 1: x' = a*x + phi*m0                                     (DDIM at eta = 0)
+ *   order 2: x' = a*x + phi*m0 + 0.5*phi*(m0 - m1)/r0                                                    (2M)
+ *   order 3: D1_0 = (m0 - m1)/r0, D1_1 = (m1 - m2)/r1, D1 = D1_0 + r0/(r0 + r1)*(D1_0 - D1_1), D2 = (D1_0 - D1_1)/(r0 + r1),
+ *            x' = a*x + phi*m0 + alpha_p*(expm1(-h)/h + 1)*D1 - alpha_p*((expm1(-h) + h)/h^2 - 0.5)*D2    (3M)
+ * Every order is linear in (m0, m1, m2): the host collects the weights in fp64 and rounds them once to fp32.  coef: device
+ * [num_steps][8] fp32 rows (a, w1_0, w2_0, w2_1, w3_0, w3_1, w3_2, 0), w{order}_{j} the weight of m_j; for every row and
+ * order the weights sum to phi.  Row 0 (abar_p = 1, sigma_p = 0, h = inf) is (0, 1, 0, ...): x' = m0.  Entries that would
+ * need an index >= num_steps are 0.  Neither kind of zero is selected by the order rule of gdx_dpm_loop.
+ * Per element, row c = coef[idx], idx = t[b] if t != NULL else step_index, every product / sum rounded separately:
+ *   m0 = x0_cond -> CFG blend u + scale*(c - u) -> inpainting blend -> clamp, exactly as in gdx_sampler_update
+ *   D = w0*m0;  order >= 2: D = D + w1*hist[0];  order 3: D = D + w2*hist[1];  out = a*x + D
+ * m0 is written to pred_out (optional; it must not be a history slot this order reads).  History slots the order does not use
+ * are never read.  128-bit accesses when J*T % 4 == 0 and every pointer is 16-byte aligned (the mask 4-byte), a scalar path
+ * otherwise.  batch <= 65535 (the grid's second dimension is the sample).  Refusals come before the first HIP call. */
+typedef struct {
+    int32_t order;             /* 1..3 */
+    int32_t batch, njoints, frames;
+    const float* coef;         /* [num_steps][8], rows as above */
+    const int64_t* t;          /* [B] or NULL */
+    int32_t step_index;        /* used when t == NULL */
+    const float* x;            /* x_t */
+    const float* x0_cond;      /* model output (cond pass) */
+    const float* x0_uncond;    /* NULL or uncond pass */
+    const float* scale;        /* [B] when x0_uncond != NULL */
+    const uint8_t* inpaint_mask;   /* NULL or bool bytes [B,J,1,T] */
+    const float* inpaint_motion;   /* [B,J,1,T] when mask != NULL */
+    int32_t clip_denoised;
+    const float* hist[2];      /* older x0 predictions, newest first: order k reads k - 1 of them */
+    float* out;                /* may alias x */
+    float* pred_out;           /* NULL or [B,J,1,T]: m0 */
+} gdx_dpm_step_args_t;
+int gdx_dpm_step(const gdx_dpm_step_args_t* a, void* stream);
+
 /* q_sample (gaussian_diffusion.py:233-251): out = a*x_start + b*noise, a/b per-sample from
  * coef rows (c[5], c[6]) at idx. */
 int gdx_q_sample(const float* x_start, const float* noise, const float* coef, int32_t idx,
@@ -430,6 +469,34 @@ typedef struct {
     float* scratch;            /* device [B,J,1,T]: the predictor of step 0 */
 } gdx_plms_loop_args_t;
 int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void* stream);
+
+/* DPM-Solver++ multistep sampling loop (dpm_solver_sample_loop; the update, the coefficient rows and their source are at
+ * gdx_dpm_step) for a START_X denoiser without cond_fn / denoised_fn: per executed step one denoiser call through the same
+ * forward entry gdx_forward uses (so the loop has the bits of the step-wise protocol) and ONE gdx_dpm_step launch, all enqueued
+ * on `stream` with no host synchronisation.  Executed step k runs index i = first_index - (k - k_base), model timestep =
+ * timestep_map[i], at order min(order, k + 1, i + 1): a warm-up at the start and a lower order at the end, the step to sigma = 0
+ * (index 0) always first order, x' = m0.  Its prediction goes to slot k % order of hist.  run_steps > 0 executes only that many
+ * steps of the loop (block-wise issue, same bits as one call: the history lives in the caller's hist between calls,
+ * first_index is THIS call's first index and k_base the executed-step number of its first step); 0 = down to index 0.  hist is
+ * the caller's; the library owns only its weights and workspace.  There is neither graph replay nor a token-major variant of
+ * this loop.  Argument checks come first, then the null handle, then readiness: every refusal precedes the first HIP call. */
+typedef struct {
+    int32_t mode;              /* GDX_COND / GDX_UNCOND / GDX_CFG */
+    int32_t order;             /* 1..3 */
+    int32_t num_steps;         /* rows of coef / timestep_map */
+    int32_t first_index;       /* index of this call's first step (whole loop: num_steps - 1 - skip_timesteps) */
+    const float* coef;         /* device [num_steps][8], rows of gdx_dpm_step */
+    const int64_t* timestep_map;   /* HOST [num_steps] */
+    float* x;                  /* in: x_T (or q_sample'd init), out: the sample */
+    const float* scale;        /* [B] for GDX_CFG */
+    const uint8_t* inpaint_mask;
+    const float* inpaint_motion;
+    int32_t clip_denoised;
+    int32_t run_steps;
+    int32_t k_base;
+    float* hist;               /* device [order][B,J,1,T]; required when order > 1 */
+} gdx_dpm_loop_args_t;
+int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* stream);
 
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  Off by
