@@ -640,6 +640,46 @@ extern "C" int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* 
     return 0;
 }
 
+// dpm_solver_sde_sample_loop (SDE-DPM-Solver++ multistep, gdx.h): gdx_dpm_loop with one fused dpm_sde_step_kernel launch per
+// step, whose noise is slice k - k_base of the tape or Philox draw k + 1.  Same order of refusals, all before the first HIP call.
+extern "C" int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a, void* stream) {
+    if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_dpm_sde_loop: null argument");
+    if (check_mode("gdx_dpm_sde_loop", a->mode, a->scale)) return -1;
+    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
+        a->run_steps > a->first_index + 1)
+        return fail("gdx_dpm_sde_loop: bad step range");
+    if (a->order < 1 || a->order > 2) return fail("gdx_dpm_sde_loop: order must be 1 or 2");
+    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_dpm_sde_loop: mask without motion");
+    if (a->order > 1 && !a->hist) return fail("gdx_dpm_sde_loop: missing history (hist is the caller's)");
+    if (check_ready(h, "gdx_dpm_sde_loop")) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B;
+    const size_t per = (size_t)h->J * h->T;
+    if (B > 65535) return fail("gdx_dpm_sde_loop: batch exceeds 65535");
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    auto slot = [&](int k) { return a->hist + (size_t)(k % a->order) * B * per; };
+    gdx_dpm_sde_step_args_t u;
+    memset(&u, 0, sizeof(u));
+    u.batch = B; u.njoints = h->J; u.frames = h->T;
+    u.coef = a->coef; u.x = a->x; u.out = a->x;
+    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
+    u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset;
+    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
+    int k = a->k_base;
+    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
+        if (denoise_step(h, a->x, idx, a->mode, h->x0, s)) return -1;
+        u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, first order on the step to sigma = 0
+        u.step_index = idx;
+        u.hist[0] = u.order > 1 ? slot(k - 1) : nullptr;
+        u.pred_out = a->order > 1 ? slot(k) : nullptr;
+        u.noise = tape_slice(a->noise_tape, k, a->k_base, B, per);
+        u.rng_step = (uint32_t)(k + 1);
+        if (gdx_dpm_sde_step(&u, stream)) return -1;
+    }
+    return 0;
+}
+
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
     if (check_ready(h, "gdx_sample_loop")) return -1;
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");

@@ -194,6 +194,12 @@ __device__ __forceinline__ float dpm_multistep(float a, const float* w, float x,
     if (NH >= 2) d = __fadd_rn(d, __fmul_rn(w[2], m2));
     return __fadd_rn(__fmul_rn(a, x), d);
 }
+// SDE-DPM-Solver++ (gdx.h gdx_dpm_sde_step): the multistep update with the row's noise scale s times a standard normal z added
+// last, (a*x + D) + s*z.
+template <int NH>
+__device__ __forceinline__ float dpm_sde_multistep(float a, const float* w, float s, float x, float m0, float m1, float z) {
+    return __fadd_rn(dpm_multistep<NH>(a, w, x, m0, m1, 0.f), __fmul_rn(s, z));
+}
 
 struct UpdateDev {
     int kind;
@@ -458,6 +464,49 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const DpmStepDev a) {
     f32x4 r;
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = dpm_multistep<NH>(c[0], w, x[i], m0[i], m1[i], m2[i]);
+    if (a.pred) store4<VEC>(a.pred, e0, nval, m0);
+    store4<VEC>(a.out, e0, nval, r);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// One SDE-DPM-Solver++ multistep step in one pass (gdx.h gdx_dpm_sde_step): dpm_step_kernel with the noise term.  Same grid,
+// same weight columns (order NH + 1 starts at column 1 + NH*(NH + 1)/2), the noise scale in column 7; z from the tape or from
+// philox_normal4 keyed like update_kernel (sample_offset + b, rng_step, group).  Memory-bound: dpm_step_kernel's traffic plus
+// one read under a tape, or one Philox draw per group without.
+struct DpmSdeStepDev {
+    long per_sample, groups;
+    const float* coef;
+    const int64_t* t;
+    int step_index;
+    const float *x, *x0c, *x0u, *scale;
+    const uint8_t* mask;
+    const float* motion;
+    const float *m1, *noise;
+    uint64_t seed, sample_offset;
+    uint32_t rng_step;
+    int clip;
+    float *out, *pred;
+};
+
+template <int NH, bool VEC>
+__global__ __launch_bounds__(256) void dpm_sde_step_kernel(const DpmSdeStepDev a) {
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    if (grp >= a.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
+    const long e0 = g.e0;
+    const int nval = g.nval;
+    const long idx = a.t ? a.t[g.b] : a.step_index;
+    const float* c = a.coef + idx * 8;
+    const float* w = c + 1 + NH * (NH + 1) / 2;
+
+    const f32x4 x = load4<VEC>(a.x, e0, nval);
+    const f32x4 m0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, e0, nval);
+    f32x4 m1 = {0.f, 0.f, 0.f, 0.f};
+    if (NH >= 1) m1 = load4<VEC>(a.m1, e0, nval);
+    const f32x4 z = a.noise ? load4<VEC>(a.noise, e0, nval) : philox_normal4(a.seed, a.sample_offset + (uint64_t)g.b, a.rng_step, g.grp);
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = dpm_sde_multistep<NH>(c[0], w, c[7], x[i], m0[i], m1[i], z[i]);
     if (a.pred) store4<VEC>(a.pred, e0, nval, m0);
     store4<VEC>(a.out, e0, nval, r);
 }
@@ -900,6 +949,41 @@ extern "C" int gdx_dpm_step(const gdx_dpm_step_args_t* a, void* stream) {
     if (vec) launch_dpm_step<true>(nh, grid, (hipStream_t)stream, d);
     else launch_dpm_step<false>(nh, grid, (hipStream_t)stream, d);
     return launch_status("gdx_dpm_step: launch failed");
+}
+
+template <bool VEC>
+static void launch_dpm_sde_step(int nh, dim3 grid, hipStream_t s, const gdx::DpmSdeStepDev& d) {
+    using namespace gdx;
+    const dim3 block(256);
+    if (nh == 0) hipLaunchKernelGGL((dpm_sde_step_kernel<0, VEC>), grid, block, 0, s, d);
+    else hipLaunchKernelGGL((dpm_sde_step_kernel<1, VEC>), grid, block, 0, s, d);
+}
+
+extern "C" int gdx_dpm_sde_step(const gdx_dpm_sde_step_args_t* a, void* stream) {
+    using namespace gdx;
+    if (!a || !a->coef || !a->x || !a->x0_cond || !a->out) return gdx_set_error_("gdx_dpm_sde_step: null argument");
+    if (a->order < 1 || a->order > 2) return gdx_set_error_("gdx_dpm_sde_step: order must be 1 or 2");
+    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return gdx_set_error_("gdx_dpm_sde_step: bad shape");
+    if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_dpm_sde_step: CFG needs scale");
+    if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_dpm_sde_step: mask without motion");
+    const int nh = a->order - 1;                                     // history slots this order reads
+    if (nh && !a->hist[0]) return gdx_set_error_("gdx_dpm_sde_step: missing history for this order");
+    if (nh && a->pred_out && a->pred_out == a->hist[0]) return gdx_set_error_("gdx_dpm_sde_step: pred_out aliases a history slot it reads");
+    DpmSdeStepDev d;
+    d.per_sample = (long)a->njoints * a->frames;
+    d.groups = (d.per_sample + 3) / 4;
+    if (a->batch == 0 || d.per_sample == 0) return 0;
+    d.coef = a->coef; d.t = a->t; d.step_index = a->step_index;
+    d.x = a->x; d.x0c = a->x0_cond; d.x0u = a->x0_uncond; d.scale = a->scale;
+    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion;
+    d.m1 = nh ? a->hist[0] : nullptr; d.noise = a->noise;
+    d.seed = a->philox_seed; d.sample_offset = a->sample_offset; d.rng_step = a->rng_step;
+    d.clip = a->clip_denoised; d.out = a->out; d.pred = a->pred_out;
+    const bool vec = vec_ok(d.per_sample, d.x, d.x0c, d.x0u, d.mask, d.motion, d.m1, d.noise, d.out, d.pred);
+    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
+    if (vec) launch_dpm_sde_step<true>(nh, grid, (hipStream_t)stream, d);
+    else launch_dpm_sde_step<false>(nh, grid, (hipStream_t)stream, d);
+    return launch_status("gdx_dpm_sde_step: launch failed");
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,

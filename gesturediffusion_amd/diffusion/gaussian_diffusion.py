@@ -11,6 +11,7 @@ coefficient rows; every per-element operation runs in libgdx.so:
   * `gdx_sample_loop`     the whole loop enqueued from C++ with in-kernel Philox noise
   * `gdx_plms_step` / `gdx_plms_loop`   plms_sample_loop (`:995-1190`): one fused multistep update per step, the loop in C++
   * `gdx_dpm_step` / `gdx_dpm_loop`     dpm_solver_sample_loop: DPM-Solver++ multistep (2M / 3M), additive, same pattern
+  * `gdx_dpm_sde_step` / `gdx_dpm_sde_loop`   dpm_solver_sde_sample_loop: its stochastic twin (SDE-DPM-Solver++, orders 1 / 2)
   * `gdx_bpd_terms` / `gdx_bpd_loop`   the variational bound in bits/dim (`_vb_terms_bpd` :1192-1225, `_prior_bpd`
                           :1519-1535, `calc_bpd_loop` :1537-1592, and `training_losses` under LossType.KL / RESCALED_KL)
 
@@ -1052,6 +1053,180 @@ class GaussianDiffusion:
             with th.no_grad():
                 out = self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                              cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, old_out=old_out)
+            yield out
+            old_out = out
+            img = out["sample"]
+
+
+    # ------------------------------------------------------------------ SDE-DPM-Solver++ multistep (no counterpart in the reference)
+    def dpm_sde_coef_rows(self, eta=1.0):
+        """The fp64 rows behind dpm_sde_coef_table: [num_timesteps, 8] = (a, w1_0, w2_0, w2_1, 0, 0, 0, s), the stochastic
+        DPM-Solver++ multistep update of order 1..2 (Lu et al. 2022, arXiv:2211.01095, at eta = 1; eta scales the injected
+        noise): x' = a*x + sum_j w_j*m_j + s*z.  The layout of dpm_coef_rows with the noise scale in column 7; at eta = 0
+        columns 0..3 are dpm_coef_rows bit for bit (the expressions below are those, with the factors eta adds written so
+        that they are exact there) and s = 0.  Formulas and special rows: include/gdx.h at gdx_dpm_sde_step."""
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta!r}")
+        n = self.num_timesteps
+        ab, abp = self.alphas_cumprod, self.alphas_cumprod_prev
+        lam = 0.5 * np.log(ab / (1.0 - ab))
+        rows = np.zeros((n, 8), dtype=np.float64)
+        rows[0, 1] = 1.0                                  # abar_p = 1: sigma_p = 0, h = inf, a = 0, phi = 1, s = 0
+        for i in range(1, n):
+            alpha_p = math.sqrt(abp[i])
+            h = 0.5 * math.log(abp[i] / (1.0 - abp[i])) - lam[i]
+            em1 = math.expm1(-((1.0 + eta) * h))
+            phi = -alpha_p * em1
+            rows[i, 0] = math.sqrt(1.0 - abp[i]) / math.sqrt(1.0 - ab[i]) * math.exp(-eta * h)
+            rows[i, 1] = phi
+            if i + 1 < n:
+                r0 = (lam[i] - lam[i + 1]) / h
+                rows[i, 2] = phi + 0.5 * phi / r0
+                rows[i, 3] = -0.5 * phi / r0
+            rows[i, 7] = math.sqrt(1.0 - abp[i]) * math.sqrt(-math.expm1(-2.0 * eta * h))
+        return rows
+
+    def dpm_sde_coef_table(self, device, eta=1.0):
+        """[num_timesteps, 8] fp32 rows consumed by gdx_dpm_sde_step / gdx_dpm_sde_loop: dpm_sde_coef_rows(eta) rounded once
+        (.float()), cached per (device, eta)."""
+        key = ("dpm_sde", str(device), float(eta))
+        if key not in self._coef_cache:
+            self._coef_cache[key] = th.from_numpy(self.dpm_sde_coef_rows(eta)).float().to(device)
+        return self._coef_cache[key]
+
+    def dpm_solver_sde_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, order=2,
+                              eta=1.0, old_out=None, *, noise=None, philox_seed=0, sample_offset=0, rng_step=None):
+        """One SDE-DPM-Solver++ multistep step (gdx_dpm_sde_step): dpm_solver_sample's x0 prediction and history protocol, then
+        the update of order min(order, predictions kept + 1, t + 1) with noise.  z is `noise` if given, else the in-kernel
+        Philox draw (philox_seed, sample_offset + b, rng_step) if rng_step is given, else th.empty_like(x).normal_().  t must
+        be the same for the whole batch.  Returns {"sample", "pred_xstart", "old_pred"}."""
+        if order not in (1, 2):
+            raise ValueError('order is invalid (should be int from 1-2).')
+        xc = E.f32c(x, "x")
+        tt = E.require_device(t, "t").to(th.int64).contiguous()
+        rows = set(tt.tolist())
+        if len(rows) != 1:
+            raise ValueError("dpm_solver_sde_sample: t must be the same for the whole batch")
+        i = rows.pop()
+        coef = self.dpm_sde_coef_table(xc.device, eta)
+        pred = self._pred_xstart(model, xc, tt, clip_denoised, denoised_fn, model_kwargs)
+        used = pred
+        if cond_fn is not None:                           # condition_score (reference :452-472)
+            grad = E.f32c(self._call_cond_fn(cond_fn, xc, tt, model_kwargs or {}), "cond_fn gradient")
+            used = E.plms_update(7, self.coef_table(GDX_SAMPLER_DDIM, xc.device, 0.0), tt, xc, pred,
+                                 eps=[grad, self._cond_coef(xc.device)])
+        if noise is not None:
+            noise = E.f32c(noise, "noise")
+            assert noise.shape == xc.shape
+        elif rng_step is None:
+            noise = th.empty_like(xc).normal_()
+        old_pred = list(old_out["old_pred"]) if old_out is not None else []
+        cur = min(order, len(old_pred) + 1, i + 1)
+        sample = E.dpm_sde_step(cur, coef, xc, used, th.empty_like(xc), hist=old_pred[::-1][:cur - 1], step_index=i,
+                                noise=noise, philox_seed=philox_seed, sample_offset=sample_offset,
+                                rng_step=0 if rng_step is None else int(rng_step))
+        old_pred.append(used)
+        return {"sample": sample, "pred_xstart": pred, "old_pred": old_pred[-(order - 1):] if order > 1 else []}
+
+    def dpm_solver_sde_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                   model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                                   randomize_class=False, cond_fn_with_grad=False, order=2, eta=1.0, *, fused=True, rng="torch",
+                                   philox_seed=0, sample_offset=0, noise_tape=None):
+        """SDE-DPM-Solver++ multistep sampling (second order by default; eta = 1 injects the ancestral sampler's noise, eta =
+        0 is dpm_solver_sample_loop): dpm_solver_sample_loop's signature and routes.  A native START_X denoiser (or its
+        ClassifierFreeSampleModel) without cond_fn / denoised_fn runs inside libgdx (gdx_dpm_sde_loop: one forward and one
+        fused update launch per step); every other case, and fused=False, goes step by step through dpm_solver_sde_sample.
+        Noise as in p_sample_loop: a recorded noise_tape (entry 0 = x_T, entry 1 + k = step k), in-kernel Philox (draw 0 = x_T,
+        draw k + 1 = step k), or torch's generator (one normal_() per step in step order).  Both routes give the same bits."""
+        if rng not in ("torch", "philox"):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        if order not in (1, 2):
+            raise ValueError('order is invalid (should be int from 1-2).')
+        if not float(eta) >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta!r}")
+        if cond_fn_with_grad or randomize_class:
+            raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
+        if (fused and _is_native(model) and denoised_fn is None and cond_fn is None
+                and self.model_mean_type == ModelMeanType.START_X):
+            if model_kwargs is None:
+                model_kwargs = {}
+            device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                      philox_seed, sample_offset, noise_tape)
+            return self._fused_dpm_sde_loop(model, img, indices, model_kwargs, int(order), float(eta), progress, clip_denoised,
+                                            rng, philox_seed, sample_offset, noise_tape)
+        final = None
+        for sample in self.dpm_solver_sde_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                                  denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                                                  model_kwargs=model_kwargs, device=device, progress=progress,
+                                                                  skip_timesteps=skip_timesteps, init_image=init_image,
+                                                                  order=order, eta=eta, rng=rng, philox_seed=philox_seed,
+                                                                  sample_offset=sample_offset, noise_tape=noise_tape):
+            final = sample
+        return final["sample"]
+
+    def _fused_dpm_sde_loop(self, model, img, indices, model_kwargs, order, eta, progress, clip_denoised, rng, philox_seed,
+                            sample_offset, noise_tape):
+        """Whole loop inside libgdx (gdx_dpm_sde_loop).  The history of x0 predictions lives in a tensor of this call.  Noise: a
+        recorded tape, in-kernel Philox, or torch's generator -- then one normal_() per step in step order, drawn
+        noise_block_steps ahead into a tape the kernel reads, exactly as _fused_loop does; the loop is issued block by block
+        with no host synchronisation in between (with `progress` one per block, to report it)."""
+        self._check_supported()
+        if self.rescale_timesteps:
+            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
+        x = E.f32c(img, "x_T").clone()
+        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
+        n = len(indices)
+        tape = E.f32c(noise_tape[1:1 + n], "noise_tape") if noise_tape is not None else None
+        coef, tmap = self.dpm_sde_coef_table(x.device, eta), self._timestep_map()
+        hist = th.empty((order, *x.shape), device=x.device, dtype=th.float32) if order > 1 else None
+        draw = tape is None and rng == "torch"
+        block = noise_block_steps(n, x.numel()) if draw else (min(n, NOISE_BLOCK) if progress else n)
+        buf = th.empty((block, *x.shape), device=x.device, dtype=th.float32) if draw else None
+        bar = None
+        if progress:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=n)
+        k = 0
+        while k < n:
+            nb = min(block, n - k)
+            if draw:
+                for j in range(nb):
+                    buf[j].normal_()
+                blk = buf
+            else:
+                blk = tape[k:] if tape is not None else None
+            eng.dpm_sde_loop(x, mode, order, coef, tmap, indices[k], hist, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+                             clip_denoised=clip_denoised, run_steps=nb, k_base=k, noise_tape=blk, philox_seed=philox_seed,
+                             sample_offset=sample_offset)
+            k += nb
+            if bar is not None:
+                th.cuda.current_stream(x.device).synchronize()
+                bar.update(nb)
+        if bar is not None:
+            bar.close()
+        return x
+
+    def dpm_solver_sde_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                               cond_fn=None, model_kwargs=None, device=None, progress=False, skip_timesteps=0,
+                                               init_image=None, randomize_class=False, cond_fn_with_grad=False, order=2,
+                                               eta=1.0, *, rng="torch", philox_seed=0, sample_offset=0, noise_tape=None):
+        if cond_fn_with_grad or randomize_class:
+            raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
+        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                  philox_seed, sample_offset, noise_tape)
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        old_out = None
+        for k, i in enumerate(indices):
+            t = th.full((shape[0],), i, device=device, dtype=th.long)
+            z = noise_tape[1 + k] if noise_tape is not None else None
+            with th.no_grad():
+                out = self.dpm_solver_sde_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                 cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, eta=eta,
+                                                 old_out=old_out, noise=z, philox_seed=philox_seed, sample_offset=sample_offset,
+                                                 rng_step=k + 1 if z is None and rng == "philox" else None)
             yield out
             old_out = out
             img = out["sample"]

@@ -216,6 +216,21 @@ class Engine:
         _lib.check(self.lib.gdx_dpm_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
         self._keep_loop = (tmap,)
 
+    def dpm_sde_loop(self, x, mode, order, coef, timestep_map, first_index, hist=None, scale=None, inpaint_mask=None,
+                     inpaint_motion=None, clip_denoised=False, run_steps=0, k_base=0, noise_tape=None, philox_seed=0,
+                     sample_offset=0):
+        """gdx_dpm_sde_loop: dpm_loop with noise -- noise_tape [steps of this call, B, J, 1, T] (slice 0 = this call's first
+        step) or, without one, Philox draw k + 1 at executed step k."""
+        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
+        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        a = _lib.DpmSdeLoopArgs(mode=mode, order=order, num_steps=len(tmap), first_index=first_index, coef=coef.data_ptr(),
+                                timestep_map=tmap.ctypes.data, x=x.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
+                                inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
+                                k_base=k_base, hist=p(hist), noise_tape=p(noise_tape), philox_seed=philox_seed,
+                                sample_offset=sample_offset)
+        _lib.check(self.lib.gdx_dpm_sde_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
+        self._keep_loop = (tmap,)
+
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
         _lib.check(self.lib.gdx_forward_flops(self.handle, mode, C.byref(f)), self.lib)
@@ -345,6 +360,25 @@ def dpm_step(order, coef, x, x0_cond, out, hist=(), t=None, step_index=0, x0_unc
     for i, m in enumerate(hist):
         a.hist[i] = p(m)
     _lib.check(lib.gdx_dpm_step(C.byref(a), _stream(x0_cond.device)), lib)
+    return out
+
+
+def dpm_sde_step(order, coef, x, x0_cond, out, hist=(), t=None, step_index=0, x0_uncond=None, scale=None, inpaint_mask=None,
+                 inpaint_motion=None, clip_denoised=False, pred_out=None, noise=None, philox_seed=0, sample_offset=0, rng_step=0):
+    """gdx_dpm_sde_step: one SDE-DPM-Solver++ multistep step in one pass (include/gdx.h).  order 1..2 over the x0 prediction
+    formed here and hist (the previous prediction, read at order 2); coef = dpm_sde_coef_table rows of one eta; z = noise, or
+    the in-kernel Philox draw (philox_seed, sample_offset + b, rng_step) when noise is None."""
+    lib = _lib.load()
+    B, J, F, T = x0_cond.shape
+    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
+    a = _lib.DpmSdeStepArgs(order=order, batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(), t=p(t), step_index=step_index,
+                            x=x.data_ptr(), x0_cond=x0_cond.data_ptr(), x0_uncond=p(x0_uncond), scale=p(scale),
+                            inpaint_mask=p(inpaint_mask), inpaint_motion=p(inpaint_motion),
+                            clip_denoised=int(bool(clip_denoised)), out=out.data_ptr(), pred_out=p(pred_out), noise=p(noise),
+                            philox_seed=philox_seed, sample_offset=sample_offset, rng_step=rng_step)
+    for i, m in enumerate(hist):
+        a.hist[i] = p(m)
+    _lib.check(lib.gdx_dpm_sde_step(C.byref(a), _stream(x0_cond.device)), lib)
     return out
 
 

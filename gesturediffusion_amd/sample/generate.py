@@ -54,10 +54,12 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
     of chunk outputs [b, J, 1, frames].  noise_tapes: optional list of recorded noise tapes, one per chunk (tests); the PLMS
-    and DPM-Solver++ ("dpmpp") samplers draw nothing after x_T and take entry 0 of a tape as that."""
+    and DPM-Solver++ ("dpmpp") samplers draw nothing after x_T and take entry 0 of a tape as that, the stochastic
+    DPM-Solver++ ("dpmpp_sde": order `dpm_order`, 1 or 2, noise scale `eta`) draws per step like "p" and is handed the whole
+    tape."""
     b, J = first_seed.shape[0], first_seed.shape[1]
     sample_fn = {"p": diffusion.p_sample_loop, "ddim": diffusion.ddim_sample_loop, "plms": diffusion.plms_sample_loop,
-                 "dpmpp": diffusion.dpm_solver_sample_loop}[sampler]
+                 "dpmpp": diffusion.dpm_solver_sample_loop, "dpmpp_sde": diffusion.dpm_solver_sde_sample_loop}[sampler]
     outs, sample_out = [], None
     for chunk in range(n_chunks):
         y = {"mfcc": mfcc_of_chunk(chunk), "seed": first_seed if chunk == 0 else sample_out[..., -seed_poses:]}
@@ -70,6 +72,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             kw.update(dump_steps=None, const_noise=False)
         elif sampler == "ddim":
             kw.update(eta=eta)
+        elif sampler == "dpmpp_sde":
+            kw.update(order=dpm_order, eta=eta)
         else:
             tape = kw.pop("noise_tape")
             kw.update(order=dpm_order if sampler == "dpmpp" else plms_order, noise=tape[0] if tape is not None else None)
@@ -194,7 +198,8 @@ def main(argv=None):
             print(f"### Sampling chunk {chunk + 1} of {args.chunks}")
 
     outs = sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, args.chunks, T, args.seed_poses,
-                         guidance_param=args.guidance_param, sampler=args.sampler, eta=args.eta, rng=rng,
+                         guidance_param=args.guidance_param, sampler=args.sampler,
+                         eta=args.dpm_eta if args.sampler == "dpmpp_sde" else args.eta, rng=rng,
                          philox_seed=args.seed, sample_offset=lo, progress=args.progress and rank == 0, on_chunk=on_chunk,
                          plms_order=args.plms_order, dpm_order=args.dpm_order)
     out_chunks, rot_chunks = [], []

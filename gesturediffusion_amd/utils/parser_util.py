@@ -23,6 +23,11 @@ def parse_and_load_from_model(parser, argv=None):
     for add in (add_data_options, add_model_options, add_diffusion_options, add_native_options):
         add(parser)
     args = parser.parse_args(argv)
+    if args.sampler == "dpmpp_sde" and args.dpm_order == 3:
+        parser.error("--sampler dpmpp_sde has orders 1 and 2 only (a third-order stochastic step is unstable below about 20 "
+                     "steps and no more accurate above): use --dpm_order 1 or 2, or --sampler dpmpp for order 3")
+    if args.dpm_eta < 0:
+        parser.error("--dpm_eta must be >= 0")
     asked_data_dir = args.data_dir
     # additive: without a checkpoint there is no args.json -- --synthetic, or a data directory sampled with random weights
     if not (not args.model_path and (args.synthetic or args.data_dir)):
@@ -121,13 +126,17 @@ def add_native_options(parser):
                        help="Pose channels for --synthetic when --dataset is not a GENEA set (e.g. 263).")
     group.add_argument("--arch_version", default='mdm', choices=['mdm', 'mdm_old'],
                        help="mdm = V2 (model/mdm.py), mdm_old = V1 encoder-only topology (model/mdm_old.py).")
-    group.add_argument("--sampler", default='p', choices=['p', 'ddim', 'plms', 'dpmpp'],
-                       help="p_sample_loop (reference default), ddim_sample_loop, plms_sample_loop or dpm_solver_sample_loop "
-                            "(DPM-Solver++ multistep; use it with --timestep_respacing logsnrN).")
+    group.add_argument("--sampler", default='p', choices=['p', 'ddim', 'plms', 'dpmpp', 'dpmpp_sde'],
+                       help="p_sample_loop (reference default), ddim_sample_loop, plms_sample_loop, dpm_solver_sample_loop "
+                            "(DPM-Solver++ multistep) or dpm_solver_sde_sample_loop (its stochastic twin, orders 1 and 2); use "
+                            "the last two with --timestep_respacing logsnrN.")
     group.add_argument("--plms_order", default=2, type=int, choices=[2, 3, 4],
                        help="--sampler plms: order of the Adams-Bashforth multistep update.")
     group.add_argument("--dpm_order", default=2, type=int, choices=[1, 2, 3],
-                       help="--sampler dpmpp: order of the multistep update (1 = DDIM at eta 0, 2 = 2M, 3 = 3M).")
+                       help="--sampler dpmpp: order of the multistep update (1 = DDIM at eta 0, 2 = 2M, 3 = 3M); "
+                            "--sampler dpmpp_sde: 1 or 2.")
+    group.add_argument("--dpm_eta", default=1.0, type=float,
+                       help="--sampler dpmpp_sde: scale of the injected noise (1 = the ancestral sampler's, 0 = --sampler dpmpp).")
     group.add_argument("--timestep_respacing", default='', type=str,
                        help="e.g. ddim100, or logsnr20 (at most 20 steps, even in log-SNR); '' = all 1000 steps.")
     group.add_argument("--eta", default=0.0, type=float)

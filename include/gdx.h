@@ -288,6 +288,47 @@ typedef struct {
 } gdx_dpm_step_args_t;
 int gdx_dpm_step(const gdx_dpm_step_args_t* a, void* stream);
 
+/* One SDE-DPM-Solver++ multistep step over [B,J,1,T] in ONE pass: the stochastic twin of gdx_dpm_step, orders 1 and 2 (Lu et
+ * al. 2022, arXiv:2211.01095, the SDE solver at eta = 1; eta >= 0 scales the injected noise in the midpoint form known from
+ * k-diffusion's dpmpp_2m_sde, written here with alpha != 1; no counterpart in the reference).  Notation of gdx_dpm_step, and
+ * z ~ N(0, I):
+ *   a = (sigma_p / sigma_i)*exp(-eta*h),  phi = -alpha_p*expm1(-(1 + eta)*h),  s = sigma_p*sqrt(-expm1(-2*eta*h))
+ *   order 1: x' = a*x + phi*m0 + s*z                (eta = 1: the ancestral step with the posterior variance; eta = 0: DDIM)
+ *   order 2: x' = a*x + phi*m0 + 0.5*phi*(m0 - m1)/r0 + s*z
+ * coef: device [num_steps][8] fp32 rows (a, w1_0, w2_0, w2_1, 0, 0, 0, s) for ONE eta, w1_0 = phi, w2_0 = phi + 0.5*phi/r0,
+ * w2_1 = -0.5*phi/r0: the layout of gdx_dpm_step's rows with the noise scale in the spare column 7.  At eta = 0 columns 0..3
+ * are those rows bit for bit and s = 0.  Row 0 is (0, 1, 0, 0, 0, 0, 0, 0): x' = m0 and no noise is applied (for finite x and
+ * z).  Entries that would need an index >= num_steps are 0.
+ * Per element, row c = coef[idx], idx = t[b] if t != NULL else step_index, every product / sum rounded separately:
+ *   m0 as in gdx_dpm_step;  D = w0*m0;  order 2: D = D + w1*hist[0];  out = (a*x + D) + s*z
+ * z = noise[b][..] when noise != NULL, else Philox N(0,1) keyed by (philox_seed; sample_offset + b; rng_step; element), the
+ * keying of gdx_sampler_update and gdx_randn: a sample's noise does not depend on the batch it is drawn in.  m0 is written to
+ * pred_out (optional; it must not be the history slot this order reads).  128-bit accesses when J*T % 4 == 0 and every
+ * pointer is 16-byte aligned (the mask 4-byte), a scalar path otherwise.  batch <= 65535.  Refusals come before the first
+ * HIP call. */
+typedef struct {
+    int32_t order;             /* 1..2 */
+    int32_t batch, njoints, frames;
+    const float* coef;         /* [num_steps][8], rows as above */
+    const int64_t* t;          /* [B] or NULL */
+    int32_t step_index;        /* used when t == NULL */
+    const float* x;            /* x_t */
+    const float* x0_cond;      /* model output (cond pass) */
+    const float* x0_uncond;    /* NULL or uncond pass */
+    const float* scale;        /* [B] when x0_uncond != NULL */
+    const uint8_t* inpaint_mask;   /* NULL or bool bytes [B,J,1,T] */
+    const float* inpaint_motion;   /* [B,J,1,T] when mask != NULL */
+    int32_t clip_denoised;
+    const float* hist[1];      /* the previous executed step's x0 prediction: read at order 2 */
+    float* out;                /* may alias x */
+    float* pred_out;           /* NULL or [B,J,1,T]: m0 */
+    const float* noise;        /* NULL -> in-kernel Philox; else [B,J,1,T] */
+    uint64_t philox_seed;
+    uint64_t sample_offset;    /* global index of sample 0 of this shard */
+    uint32_t rng_step;
+} gdx_dpm_sde_step_args_t;
+int gdx_dpm_sde_step(const gdx_dpm_sde_step_args_t* a, void* stream);
+
 /* q_sample (gaussian_diffusion.py:233-251): out = a*x_start + b*noise, a/b per-sample from
  * coef rows (c[5], c[6]) at idx. */
 int gdx_q_sample(const float* x_start, const float* noise, const float* coef, int32_t idx,
@@ -497,6 +538,32 @@ typedef struct {
     float* hist;               /* device [order][B,J,1,T]; required when order > 1 */
 } gdx_dpm_loop_args_t;
 int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* stream);
+
+/* SDE-DPM-Solver++ multistep sampling loop (dpm_solver_sde_sample_loop; the update and its rows are at gdx_dpm_sde_step): the
+ * loop of gdx_dpm_loop -- same step numbering, order rule min(order, k + 1, i + 1), history slots, run_steps / k_base block-wise
+ * issue and order of refusals -- with ONE gdx_dpm_sde_step launch per executed step.  Executed step k takes its noise from
+ * slice k - k_base of noise_tape, or, without a tape, from Philox draw k + 1 (x_T is draw 0: the convention of
+ * gdx_sample_loop).  Block-wise issue gives the bits of one call.  There is neither graph replay nor a token-major variant. */
+typedef struct {
+    int32_t mode;              /* GDX_COND / GDX_UNCOND / GDX_CFG */
+    int32_t order;             /* 1..2 */
+    int32_t num_steps;         /* rows of coef / timestep_map */
+    int32_t first_index;       /* index of this call's first step */
+    const float* coef;         /* device [num_steps][8], rows of gdx_dpm_sde_step */
+    const int64_t* timestep_map;   /* HOST [num_steps] */
+    float* x;                  /* in: x_T (or q_sample'd init), out: the sample */
+    const float* scale;        /* [B] for GDX_CFG */
+    const uint8_t* inpaint_mask;
+    const float* inpaint_motion;
+    int32_t clip_denoised;
+    int32_t run_steps;
+    int32_t k_base;
+    float* hist;               /* device [order][B,J,1,T]; required when order > 1 */
+    const float* noise_tape;   /* NULL -> Philox; else device [steps of THIS call][B,J,1,T], slice 0 = this call's first step */
+    uint64_t philox_seed;
+    uint64_t sample_offset;
+} gdx_dpm_sde_loop_args_t;
+int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a, void* stream);
 
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  Off by

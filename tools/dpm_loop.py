@@ -2,7 +2,10 @@
 """ms/step of dpm_solver_sample_loop (orders 1 to 3) next to ddim_sample_loop and plms_sample_loop (order 2) on the same
 respacing, in one process:
     python tools/dpm_loop.py [--config genea|2|1] [--dtype fp32|fp16|bf16] [--respacing logsnr20] [--repeats 5]
-                             [--out profiles/FILE.txt]
+                             [--sde] [--out profiles/FILE.txt]
+--sde measures dpm_solver_sde_sample_loop (orders 1 and 2, eta = 1, in-kernel Philox noise) next to dpm_solver_sample_loop at
+order 2 and p_sample_loop (Philox) on the same respacing instead; the expectation is one Philox draw per element on top of the
+ODE step.
 Every loop runs once as a warm-up at the timed shape, then `repeats` times between two events on the stream, the loops
 alternating inside each repeat; the median is reported with the spread, per step of the respacing ("logsnrN" can keep fewer
 than N steps: the record says how many; PLMS runs one forward more than it has steps).  One JSON line per run; kernel-level
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--dtype", default=None, choices=["fp32", "fp16", "bf16"])
     ap.add_argument("--respacing", default="logsnr20")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sde", action="store_true", help="time the stochastic loop against the ODE loop and p_sample_loop")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -62,9 +66,15 @@ def main():
         y["scale"] = torch.full((B,), 2.5, device=dev)
         m = ClassifierFreeSampleModel(model)
     kw = dict(noise=x, clip_denoised=False, model_kwargs={"y": y})
-    loops = {f"dpm_order{o}": (lambda o=o: df.dpm_solver_sample_loop(m, (B, J, 1, T), order=o, **kw)) for o in (1, 2, 3)}
-    loops["ddim"] = lambda: df.ddim_sample_loop(m, (B, J, 1, T), eta=0.0, rng="philox", **kw)
-    loops["plms_order2"] = lambda: df.plms_sample_loop(m, (B, J, 1, T), order=2, **kw)
+    if a.sde:
+        loops = {f"dpm_sde_order{o}": (lambda o=o: df.dpm_solver_sde_sample_loop(m, (B, J, 1, T), order=o, eta=1.0, rng="philox",
+                                                                                 philox_seed=10, **kw)) for o in (1, 2)}
+        loops["dpm_order2"] = lambda: df.dpm_solver_sample_loop(m, (B, J, 1, T), order=2, **kw)
+        loops["p_sample"] = lambda: df.p_sample_loop(m, (B, J, 1, T), rng="philox", philox_seed=10, **kw)
+    else:
+        loops = {f"dpm_order{o}": (lambda o=o: df.dpm_solver_sample_loop(m, (B, J, 1, T), order=o, **kw)) for o in (1, 2, 3)}
+        loops["ddim"] = lambda: df.ddim_sample_loop(m, (B, J, 1, T), eta=0.0, rng="philox", **kw)
+        loops["plms_order2"] = lambda: df.plms_sample_loop(m, (B, J, 1, T), order=2, **kw)
     first = {k: timed(fn)[1] for k, fn in loops.items()}                       # warm-up at the timed shape
     ms = {k: [] for k in loops}
     for _ in range(a.repeats):
@@ -72,11 +82,14 @@ def main():
             t, r = timed(fn)
             assert torch.equal(r, first[k]) and torch.isfinite(r).all(), k
             ms[k].append(t / steps)
-    ref = first["ddim"].double()
     rec = dict(tool="dpm_loop", config=a.config, label=p["label"], arch=p["arch"], B=B, T=T, J=J, d=p["d"], dtype=dtype,
                guidance=bool(p["cfg"]), respacing=a.respacing, steps=steps, repeats=a.repeats,
-               device=torch.cuda.get_device_name(0),
-               order1_vs_ddim_rel=float((first["dpm_order1"].double() - ref).abs().max() / ref.abs().max()))
+               device=torch.cuda.get_device_name(0))
+    if a.sde:
+        rec["sde"] = True
+    else:
+        ref = first["ddim"].double()
+        rec["order1_vs_ddim_rel"] = float((first["dpm_order1"].double() - ref).abs().max() / ref.abs().max())
     for k, v in ms.items():
         rec[k + "_ms_per_step"] = round(statistics.median(v), 5)
         rec[k + "_ms_per_step_min_max"] = [round(min(v), 5), round(max(v), 5)]
