@@ -25,9 +25,11 @@ EXPORTS = [
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
     "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
     "gdx_dpm_step", "gdx_dpm_loop", "gdx_dpm_sde_step", "gdx_dpm_sde_loop",
+    "gdx_set_guidance_interval", "gdx_forward_samples",
     "gdx_transpose_in", "gdx_transpose_out", "gdx_small_linear", "gdx_gather_rows", "gdx_mfcc_project", "gdx_token0",
 ]
 GDX_BPD_CHUNK = 4096   # include/gdx.h
+INT64_MIN, INT64_MAX = -2**63, 2**63 - 1   # gdx_set_guidance_interval's default: every timestep
 
 
 class GdxError(RuntimeError):
@@ -226,6 +228,8 @@ def load():
         "gdx_import_packed": [vp, vp, i64, vp],
         "gdx_bpd_terms": [C.POINTER(BpdArgs), vp],
         "gdx_bpd_loop": [vp, C.POINTER(BpdLoopArgs), vp],
+        "gdx_set_guidance_interval": [vp, i64, i64],
+        "gdx_forward_samples": [vp, C.POINTER(i64)],
         "gdx_profile_begin": [vp, i32],
         "gdx_profile_end": [vp, C.POINTER(C.c_float), C.POINTER(i32)],
     }

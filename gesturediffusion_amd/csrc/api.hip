@@ -5,6 +5,7 @@
 #include "gdx_host.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -348,6 +349,7 @@ static int forward_core(gdx_model* h, const float* x, const float* temb, int tst
                         float* x0_out, hipStream_t s, const int* state = nullptr, bool tm = false) {
     const int B = h->B, T = h->T, S = h->S, d = h->d, J = h->J;
     const int Beff = mode == GDX_CFG ? 2 * B : B;
+    h->forward_samples += Beff;                                   // gdx_forward_samples (host side only)
     const float* seed_emb = mode == GDX_UNCOND ? h->seed_cat + (size_t)B * d : h->seed_cat;
     const int N = Beff * S;
     // the encoder stream as the sublayers write it: in the 16-bit stream its fp32 side only for the parity taps
@@ -414,6 +416,28 @@ static int check_mode(const char* who, int mode, const float* scale) {
     return 0;
 }
 
+// Guidance interval (gdx.h): the model timesteps, bounds inclusive, at which GDX_CFG means guidance.  Per-handle state like the
+// conditioning; the default is every timestep.
+extern "C" int gdx_set_guidance_interval(gdx_handle_t h, int64_t lo, int64_t hi) {
+    if (!h) return fail("gdx_set_guidance_interval: null handle");
+    h->guide_lo = lo; h->guide_hi = hi;
+    return 0;
+}
+
+extern "C" int gdx_forward_samples(gdx_handle_t h, int64_t* samples) {
+    if (!h || !samples) return fail("gdx_forward_samples: null argument");
+    *samples = h->forward_samples;
+    return 0;
+}
+
+// The mode of ONE step of a loop whose mode is `mode`: guidance only while the step's model timestep lies in the handle's
+// interval, else the plain conditional pass (B samples, no blend).  Every in-library loop asks here.
+static int step_mode(const gdx_model* h, int mode, const int64_t* timestep_map, int idx) {
+    if (mode != GDX_CFG) return mode;
+    const int64_t tau = timestep_map[idx];
+    return h->guide_lo <= tau && tau <= h->guide_hi ? GDX_CFG : GDX_COND;
+}
+
 // timestep embedding rows for idx[M] (model/mdm.py:296-310): pe gather -> Linear -> SiLU -> Linear.  The same
 // row-independent kernel serves the per-sample rows of gdx_forward and the whole-loop table of gdx_sample_loop, so a
 // timestep's embedding has the same bits on both sides of the seam (fused loop == step-wise protocol, bit for bit).
@@ -440,7 +464,8 @@ extern "C" int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timest
     if (mode != GDX_CFG) return forward_core(h, x, h->temb, h->d, c2t, mode, out, s);
     if (forward_core(h, x, h->temb, h->d, c2t, mode, h->x0, s)) return -1;
     const int64_t per = (int64_t)h->J * h->T;
-    HIPCHK(launch_cfg_blend(h->x0, h->x0 + (size_t)h->B * per, scale, out, h->B, per, s));
+    // the timesteps are on the device: the double batch stays, the blend selects per sample (guided: blend, else c)
+    HIPCHK(launch_cfg_blend(h->x0, h->x0 + (size_t)h->B * per, scale, timesteps, h->guide_lo, h->guide_hi, out, h->B, per, s));
     return 0;
 }
 
@@ -520,7 +545,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     memset(&u, 0, sizeof(u));
     u.batch = B; u.njoints = h->J; u.frames = h->T;
     u.coef = a->coef; u.x_start = a->x_start; u.x_t = h->bpd_xt;
-    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.x0_cond = h->x0;
     u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
     u.clip_denoised = a->clip_denoised;
     u.vb = a->vb; u.xstart_mse = a->xstart_mse; u.mse = a->mse; u.ld = a->num_steps;
@@ -537,7 +562,9 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
                             stream))
                 return -1;
         }
-        if (denoise_step(h, h->bpd_xt, idx, a->mode, h->x0, s)) return -1;
+        const int m = step_mode(h, a->mode, a->timestep_map, idx);
+        if (denoise_step(h, h->bpd_xt, idx, m, h->x0, s)) return -1;
+        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
         u.step_index = idx; u.col = k;
         if (gdx_bpd_terms(&u, stream)) return -1;
     }
@@ -569,13 +596,18 @@ extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void
     const size_t per = (size_t)h->J * h->T;
     if (B > 65535) return fail("gdx_plms_loop: batch exceeds 65535");
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
-    auto denoise = [&](const float* x, int idx) { return denoise_step(h, x, idx, a->mode, h->x0, s); };
     auto slot = [&](int k) { return a->eps_hist + (size_t)(k % a->order) * B * per; };
     gdx_plms_step_args_t u;
     memset(&u, 0, sizeof(u));
     u.batch = B; u.njoints = h->J; u.frames = h->T;
     u.coef = a->coef; u.x = a->x;
-    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.x0_cond = h->x0;
+    // the forward at index idx in the mode of its own timestep (guidance interval), and the update's view of its output
+    auto denoise = [&](const float* x, int idx) {
+        const int m = step_mode(h, a->mode, a->timestep_map, idx);
+        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
+        return denoise_step(h, x, idx, m, h->x0, s);
+    };
     u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
     const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
     int k = a->k_base;
@@ -625,12 +657,14 @@ extern "C" int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* 
     memset(&u, 0, sizeof(u));
     u.batch = B; u.njoints = h->J; u.frames = h->T;
     u.coef = a->coef; u.x = a->x; u.out = a->x;
-    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.x0_cond = h->x0;
     u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
     const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
     int k = a->k_base;
     for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
-        if (denoise_step(h, a->x, idx, a->mode, h->x0, s)) return -1;
+        const int m = step_mode(h, a->mode, a->timestep_map, idx);
+        if (denoise_step(h, a->x, idx, m, h->x0, s)) return -1;
+        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
         u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, lower order at the end
         u.step_index = idx;
         for (int j = 0; j < 2; ++j) u.hist[j] = j < u.order - 1 ? slot(k - 1 - j) : nullptr;
@@ -662,13 +696,15 @@ extern "C" int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a
     memset(&u, 0, sizeof(u));
     u.batch = B; u.njoints = h->J; u.frames = h->T;
     u.coef = a->coef; u.x = a->x; u.out = a->x;
-    u.x0_cond = h->x0; u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = a->scale;
+    u.x0_cond = h->x0;
     u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
     u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset;
     const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
     int k = a->k_base;
     for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
-        if (denoise_step(h, a->x, idx, a->mode, h->x0, s)) return -1;
+        const int m = step_mode(h, a->mode, a->timestep_map, idx);
+        if (denoise_step(h, a->x, idx, m, h->x0, s)) return -1;
+        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
         u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, first order on the step to sigma = 0
         u.step_index = idx;
         u.hist[0] = u.order > 1 ? slot(k - 1) : nullptr;
@@ -696,13 +732,14 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     const size_t tape_rows = a->const_noise ? 1 : B;             // samples per step of the noise tape
     int dump_i = 0;
     while (dump_i < a->n_dump && a->dump_steps[dump_i] < a->k_base) ++dump_i;     // entries of earlier blocks
-    auto fill_update = [&](gdx_update_args_t& u, int idx, int k) {
+    auto mode_at = [&](int idx) { return step_mode(h, a->mode, a->timestep_map, idx); };
+    auto fill_update = [&](gdx_update_args_t& u, int idx, int k, int mode) {
         memset(&u, 0, sizeof(u));
         u.kind = a->kind; u.batch = B; u.njoints = h->J; u.frames = h->T;
         u.coef = a->coef; u.t = nullptr; u.step_index = idx;
         u.x = a->x; u.x0_cond = h->x0;
-        u.x0_uncond = a->mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr;
-        u.scale = a->scale;
+        u.x0_uncond = mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr;
+        u.scale = mode == GDX_CFG ? a->scale : nullptr;
         u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
         u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
         u.const_noise = a->const_noise;
@@ -711,9 +748,10 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         u.clip_denoised = a->clip_denoised;
     };
     auto eager_step = [&](int idx, int k) -> int {
-        if (denoise_step(h, a->x, idx, a->mode, h->x0, s)) return -1;
+        const int m = mode_at(idx);
+        if (denoise_step(h, a->x, idx, m, h->x0, s)) return -1;
         gdx_update_args_t u;
-        fill_update(u, idx, k);
+        fill_update(u, idx, k, m);
         if (gdx_sampler_update(&u, stream)) return -1;
         while (a->dump && dump_i < a->n_dump && a->dump_steps[dump_i] <= k) {      // duplicates / stale entries never stall
             if (a->dump_steps[dump_i] == k)
@@ -731,12 +769,25 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     // ~65 small kernels of a step are bound by their GPU-side dispatch + ramp, not by host launch time, and a graph
     // node costs slightly more than a stream launch; so it is OFF by default and kept as a switch.
     const int last_idx = a->run_steps > 0 && a->run_steps <= a->first_index ? a->first_index - a->run_steps + 1 : 0;
+    // guidance interval: the modes this call's steps take (all the loop's own mode unless it is GDX_CFG)
+    const int mode0 = mode_at(a->first_index);
+    bool uniform = true, any_guided = false;
+    for (int i = a->first_index; i >= last_idx; --i) {
+        const int m = mode_at(i);
+        uniform = uniform && m == mode0;
+        any_guided = any_guided || m == GDX_CFG;
+    }
     // Token-major fast path (sampler.hip, update_tm_kernel): with nothing but the noise tape living in the reference layout
     // (no inpainting, no dumps; the tape is read in place), the state stays in the input GEMM's operand layout for the whole
     // call -- one transpose in front, none per step (2 launches and ~40 MB per step less), the last update also writes the
     // sample in the reference layout.  Bit-identical to the general path (tests: fused Philox loop == step-wise Philox loop).
     if (!((uintptr_t)a->noise_tape & 15) && !a->inpaint_mask && !a->n_dump && !h->graph_replay && !h->keep_taps && h->T % 4 == 0) {
-        const int Beff = a->mode == GDX_CFG ? 2 * B : B;
+        // guided loop: the state holds both halves (the same x feeds both passes).  An unguided step reads and writes the cond
+        // half and mirrors into the uncond half only when the NEXT step of this call is guided (every call transposes the
+        // state in afresh); a call without a guided step keeps one half, like a loop that is not guided at all.
+        // GDX_TM_MIRROR=always mirrors on every unguided step of such a call (the A/B of DESIGN 4f).
+        static const bool mirror_always = [] { const char* e = getenv("GDX_TM_MIRROR"); return e && !strcmp(e, "always"); }();
+        const int Beff = any_guided ? 2 * B : B;
         // half modes: the fp32 state keeps the half operand's row stride, and the update kernel also writes that operand
         const int ldx = h->f16 ? h->in_x.kpad16 : h->in_x.kpad;
         HIPCHK(launch_transpose_in(a->x, h->xt.f, Beff, B, h->J, h->T, ldx, s));
@@ -744,13 +795,16 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         gdx::UpdateTmDev u;
         memset(&u, 0, sizeof(u));
         u.kind = a->kind; u.B = B; u.J = h->J; u.T = h->T; u.ldx = ldx; u.ldo = h->ldo;
-        u.coef = a->coef; u.xt = h->xt.f; u.x0t = h->x0t; u.scale = a->mode == GDX_CFG ? a->scale : nullptr;
+        u.coef = a->coef; u.xt = h->xt.f; u.x0t = h->x0t;
         u.const_noise = a->const_noise; u.seed = a->philox_seed; u.sample_offset = a->sample_offset;
         u.clip = a->clip_denoised;
         u.xt16 = h->xt.h; u.half_dtype = h->cfg.compute_dtype;
         int k = a->k_base;
         for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
-            if (denoise_step(h, nullptr, idx, a->mode, nullptr, s, nullptr, true)) return -1;
+            const int m = mode_at(idx);
+            if (denoise_step(h, nullptr, idx, m, nullptr, s, nullptr, true)) return -1;
+            u.scale = m == GDX_CFG ? a->scale : nullptr;
+            u.mirror = any_guided && m != GDX_CFG && (mirror_always || (idx > last_idx && mode_at(idx - 1) == GDX_CFG));
             u.step_index = idx; u.rng_step = (uint32_t)(k + 1);
             u.out_pose = idx == last_idx ? a->x : nullptr;
             u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
@@ -758,7 +812,8 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         }
         return 0;
     }
-    const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8;
+    // the graph is ONE captured step: only a call whose steps all take the same mode can replay it
+    const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8 && uniform;
     int idx = a->first_index, k = a->k_base;
     if (want_graph) {
         if (eager_step(idx, k)) return -1;                        // step 0 eagerly: it also sets every kernel attribute
@@ -781,10 +836,12 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
                  hipStreamWaitEvent(h->gstream, h->gev_in, 0) == hipSuccess;
         }
         if (ok && hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            int rc = denoise_step(h, a->x, 0, a->mode, h->x0, h->gstream, h->gstate);
+            const int64_t counted = h->forward_samples;          // the capture enqueues no forward: the replays are counted
+            int rc = denoise_step(h, a->x, 0, mode0, h->x0, h->gstream, h->gstate);
+            h->forward_samples = counted;
             if (!rc) {
                 gdx_update_args_t u;
-                fill_update(u, 0, 0);                             // noise: step 0's slice; the kernel adds state[1] * stride
+                fill_update(u, 0, 0, mode0);                      // noise: step 0's slice; the kernel adds state[1] * stride
                 rc = gdx_sampler_update_state_(&u, h->gstate, (long)(tape_rows * per), (void*)h->gstream);
             }
             if (!rc && launch_advance_state(h->gstate, h->gstream) != hipSuccess) rc = -1;
@@ -807,7 +864,10 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
             (void)hipGetLastError();
         }
         if (ok) {
-            for (; idx >= last_idx; --idx, ++k) HIPCHK(hipGraphLaunch(h->gexec, h->gstream));
+            for (; idx >= last_idx; --idx, ++k) {
+                HIPCHK(hipGraphLaunch(h->gexec, h->gstream));
+                h->forward_samples += mode0 == GDX_CFG ? 2 * B : B;
+            }
             HIPCHK(hipEventRecord(h->gev_out, h->gstream));
             HIPCHK(hipStreamWaitEvent(s, h->gev_out, 0));
             return 0;

@@ -126,6 +126,8 @@ struct gdx_model {
     int B = 0, T = 0, S = 0;
     long rows_alloc = 0;              // rows of the [2B*S + pad] token buffers
     bool cond_set = false;
+    int64_t guide_lo = INT64_MIN, guide_hi = INT64_MAX;   // gdx_set_guidance_interval: model timesteps that get guidance
+    int64_t forward_samples = 0;      // gdx_forward_samples: samples pushed through forward_core since gdx_create
     gdx::Act xa, xb, qkv, ctx, tmp, ffb;   // [rows_alloc] token rows: residual stream (xa, xb), sublayer operands and outputs
     gdx::Act xt, xc;                       // token-major pose in / compacted last layer, [2B*T + pad] rows
     gdx::Act emb, xseq;                    // V2 front end: InputProcess output, proj_pose output

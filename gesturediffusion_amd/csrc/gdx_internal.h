@@ -181,9 +181,9 @@ namespace b16 { GDX_HALF_API }
 // graph replay of the sampling loop: device-resident {schedule index, executed-step number}
 hipError_t launch_set_state(int* st, int idx, int k, hipStream_t s);
 hipError_t launch_advance_state(int* st, hipStream_t s);
-// out = u + scale[b]*(c - u)
-hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, float* out, int B, int64_t per_sample,
-                            hipStream_t s);
+// out = u + scale[b]*(c - u) where lo <= t[b] <= hi (the handle's guidance interval), else c
+hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
+                            float* out, int B, int64_t per_sample, hipStream_t s);
 
 // argument of update_tm_kernel (sampler.hip): one step of gdx_sample_loop's token-major fast path, filled by api.hip
 struct UpdateTmDev {
@@ -200,6 +200,7 @@ struct UpdateTmDev {
     void* xt16;             // half modes: the input GEMM's 16-bit operand [Beff*T][ldx], written beside the fp32 state
     int half_dtype;         // GDX_DTYPE_F16 or GDX_DTYPE_BF16 (the element type of xt16)
     const float* noise;     // this step's slice of a noise tape, reference layout [B or 1][J][T], or nullptr (Philox)
+    int mirror;             // an unguided step (scale == nullptr) of a guided loop: write the uncond half of xt / xt16 as well
 };
 
 }  // namespace gdx

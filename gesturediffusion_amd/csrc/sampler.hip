@@ -261,6 +261,8 @@ __global__ __launch_bounds__(256) void update_kernel(const UpdateDev a) {
 // layout.  A thread owns a 4 (frames) x 4 (channels) micro-tile: for channel j the four frames t0..t0+3 are exactly
 // Philox group j*T/4 + t0/4 of the pose-layout numbering, so every element gets the very noise value -- and, through
 // update_value(), the very arithmetic -- of update_kernel: the two paths are bit-identical.  (UpdateTmDev: gdx_internal.h)
+// An unguided step of a guided loop (guidance interval) has no scale: x0 is the cond half alone (the denoiser ran B samples),
+// and `mirror` makes it write the uncond half of the state all the same, for the guided step that follows.
 __global__ __launch_bounds__(256) void update_tm_kernel(const UpdateTmDev a) {
     const int jq_n = (a.J + 3) / 4, tq_n = a.T / 4;
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
@@ -272,6 +274,7 @@ __global__ __launch_bounds__(256) void update_tm_kernel(const UpdateTmDev a) {
     const float* c = a.coef + (long)a.step_index * 8;
     const long row0 = (long)b * a.T + t0;                        // first of the tile's four token rows
     const long urow = (long)a.B * a.T;                           // offset of the uncond half (guidance)
+    const bool both = a.scale || a.mirror;                       // the state's uncond half is written too
     f32x4 x[4], x0[4];                                           // [frame][channel]
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) {
@@ -311,7 +314,7 @@ __global__ __launch_bounds__(256) void update_tm_kernel(const UpdateTmDev a) {
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) {
         *reinterpret_cast<f32x4*>(a.xt + (row0 + tt) * a.ldx + j0) = r[tt];
-        if (a.scale) *reinterpret_cast<f32x4*>(a.xt + (urow + row0 + tt) * a.ldx + j0) = r[tt];
+        if (both) *reinterpret_cast<f32x4*>(a.xt + (urow + row0 + tt) * a.ldx + j0) = r[tt];
     }
     if (a.xt16) {                                                  // the same values rounded once, as transpose_in_f16 would
         typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -322,11 +325,11 @@ __global__ __launch_bounds__(256) void update_tm_kernel(const UpdateTmDev a) {
             if (a.half_dtype == GDX_DTYPE_BF16) {
                 const b4 v = b4{(__bf16)r[tt][0], (__bf16)r[tt][1], (__bf16)r[tt][2], (__bf16)r[tt][3]};
                 *reinterpret_cast<b4*>((__bf16*)a.xt16 + o0) = v;
-                if (a.scale) *reinterpret_cast<b4*>((__bf16*)a.xt16 + o1) = v;
+                if (both) *reinterpret_cast<b4*>((__bf16*)a.xt16 + o1) = v;
             } else {
                 const h4 v = h4{(_Float16)r[tt][0], (_Float16)r[tt][1], (_Float16)r[tt][2], (_Float16)r[tt][3]};
                 *reinterpret_cast<h4*>((_Float16*)a.xt16 + o0) = v;
-                if (a.scale) *reinterpret_cast<h4*>((_Float16*)a.xt16 + o1) = v;
+                if (both) *reinterpret_cast<h4*>((_Float16*)a.xt16 + o1) = v;
             }
         }
     }
@@ -568,14 +571,16 @@ __global__ void randn_kernel(float* __restrict__ out, int batch, long per_sample
     store4<false>(out, g.e0, g.nval, philox_normal4(seed, sample_offset + (uint64_t)g.b, step, g.grp));
 }
 
-// classifier-free guidance blend (model/cfg_sampler.py:28), op order as the reference
+// classifier-free guidance blend (model/cfg_sampler.py:28), op order as the reference.  Guidance interval
+// (gdx_set_guidance_interval): a sample whose timestep t[b] lies outside [lo, hi] takes the conditional output c itself
 __global__ void cfg_blend_kernel(const float* __restrict__ c, const float* __restrict__ u,
-                                 const float* __restrict__ scale, float* __restrict__ out, long per_sample,
-                                 long total) {
+                                 const float* __restrict__ scale, const int64_t* __restrict__ t, int64_t lo, int64_t hi,
+                                 float* __restrict__ out, long per_sample, long total) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const float sc = scale[i / per_sample];
-    out[i] = cfg_blend(c[i], u[i], sc);
+    const long b = i / per_sample;
+    const int64_t tb = t[b];
+    out[i] = lo <= tb && tb <= hi ? cfg_blend(c[i], u[i], scale[b]) : c[i];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -738,10 +743,10 @@ __global__ void bpd_finish_kernel(const float* __restrict__ part, int chunks, lo
     out[(long)b * ld + col] = m;
 }
 
-hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, float* out, int B, int64_t per_sample,
-                            hipStream_t s) {
+hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
+                            float* out, int B, int64_t per_sample, hipStream_t s) {
     const long total = (long)B * per_sample;
-    hipLaunchKernelGGL(cfg_blend_kernel, dim3((total + 255) / 256), dim3(256), 0, s, c, u, scale, out,
+    hipLaunchKernelGGL(cfg_blend_kernel, dim3((total + 255) / 256), dim3(256), 0, s, c, u, scale, t, lo, hi, out,
                        (long)per_sample, total);
     return hipGetLastError();
 }

@@ -474,10 +474,13 @@ class GaussianDiffusion:
         if hasattr(inner, "cl_head") and T % 10 != 0:
             from ..model.mdm import _window_error
             raise _window_error(T, 10)
+        guided = isinstance(model, ClassifierFreeSampleModel)
+        interval = E.guidance_interval_of(y, guided)
         eng = inner._get_engine(x.device)
         eng.prepare(B, T)
         eng.set_condition(y["seed"], y["mfcc"], cache=False)
-        if isinstance(model, ClassifierFreeSampleModel):
+        eng.set_guidance_interval(interval)          # at every loop; None resets a reused handle to "every timestep"
+        if guided:
             mode, scale = GDX_CFG, E.f32c(y["scale"].reshape(-1), "y['scale']")
         else:
             mode, scale = (GDX_UNCOND if y.get("uncond", False) else GDX_COND), None
@@ -546,6 +549,17 @@ class GaussianDiffusion:
 
     def _timestep_map(self):
         return list(range(self.num_timesteps))
+
+    def guided_steps(self, guidance_interval):
+        """Per-step guidance flags of a loop under y['guidance_interval'] = (lo, hi): entry i is True when the MODEL timestep
+        of this diffusion's index i -- the respacing map's value, what the denoiser sees -- satisfies lo <= t <= hi (inclusive;
+        lo > hi is the empty interval; None = every step).  A loop visits the indices in descending order.  The rule of
+        gdx_set_guidance_interval, on the host."""
+        tmap = self._timestep_map()
+        if guidance_interval is None:
+            return [True] * len(tmap)
+        lo, hi = guidance_interval
+        return [lo <= t <= hi for t in tmap]
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,

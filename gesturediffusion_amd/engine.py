@@ -126,6 +126,17 @@ class Engine:
         self._keep = [seed, mfcc, seed_c, mfcc_c]
         self._cond_key = key if cache else None
 
+    def set_guidance_interval(self, interval=None):
+        """(lo, hi): GDX_CFG guides only model timesteps lo <= t <= hi (gdx_set_guidance_interval); None = every timestep."""
+        lo, hi = interval if interval is not None else (_lib.INT64_MIN, _lib.INT64_MAX)
+        _lib.check(self.lib.gdx_set_guidance_interval(self.handle, lo, hi), self.lib)
+
+    def forward_samples(self):
+        """Samples pushed through the denoiser since the handle was created (gdx_forward_samples; host-side counter)."""
+        n = C.c_int64()
+        _lib.check(self.lib.gdx_forward_samples(self.handle, C.byref(n)), self.lib)
+        return n.value
+
     # ------------------------------------------------------------------ compute
     def forward(self, x, timesteps, mode=GDX_COND, scale=None):
         x = f32c(x, "x")
@@ -248,6 +259,27 @@ class Engine:
         us = C.c_float()
         _lib.check(self.lib.gdx_bench_ffn_gemm(self.handle, iters, C.byref(us), _stream(device)), self.lib)
         return us.value
+
+
+def guidance_interval_of(y, guided_model):
+    """y['guidance_interval'] validated -> (lo, hi) Python ints in MODEL timesteps, bounds inclusive (lo > hi: the empty
+    interval), or None when the key is absent.  ValueError for anything but two ints -- a tensor is refused because reading it
+    would synchronise -- and for a key on a model that is not a ClassifierFreeSampleModel (`guided_model` False)."""
+    if "guidance_interval" not in y:
+        return None
+    iv = y["guidance_interval"]
+    if not guided_model:
+        raise ValueError("y['guidance_interval'] needs a ClassifierFreeSampleModel: this model runs no guidance to limit")
+    ok = (isinstance(iv, (tuple, list)) and len(iv) == 2
+          and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in iv))
+    if not ok:
+        raise ValueError(f"y['guidance_interval'] must be two Python ints (lo, hi) in model timesteps, got {iv!r}"
+                         if not isinstance(iv, torch.Tensor) else
+                         "y['guidance_interval'] must be two Python ints (lo, hi), not a tensor: reading it would synchronise")
+    lo, hi = int(iv[0]), int(iv[1])
+    if not (_lib.INT64_MIN <= lo <= _lib.INT64_MAX and _lib.INT64_MIN <= hi <= _lib.INT64_MAX):
+        raise ValueError(f"y['guidance_interval'] bounds must fit 64 bits, got {iv!r}")
+    return lo, hi
 
 
 # ---------------------------------------------------------------------- standalone kernels

@@ -5,10 +5,13 @@ The reference runs the inner model twice per step (cond, then a deep copy of `y`
 passes run as ONE double batch through the HIP kernels (only the seed-pose embedding differs
 between them; the MFCC conditioning feeds both, as in the reference) and the blend is a fused
 kernel.  Nothing is deep-copied.
+
+`y['guidance_interval'] = (lo, hi)` (additive) limits guidance to model timesteps lo <= t <= hi; a sample outside it gets
+the conditional output itself.
 """
 import torch.nn as nn
 
-from ..engine import GDX_CFG
+from ..engine import GDX_CFG, guidance_interval_of
 from .mdm import _NativeDenoiser
 
 
@@ -41,8 +44,12 @@ class ClassifierFreeSampleModel(nn.Module):
             raise _window_error(nframes, 10)
         if m.data_rep != "genea_vec":
             raise NotImplementedError
+        interval = guidance_interval_of(y, True)
         eng = m._get_engine(x.device)
         eng.prepare(bs, nframes)
         eng.set_condition(seed, mfcc)
+        # per-sample choice in the blend kernel: guided where lo <= timesteps[b] <= hi, else the conditional output; set on
+        # every call (None: every timestep), so a handle never keeps the interval of an earlier call
+        eng.set_guidance_interval(interval)
         out = eng.forward(x, timesteps, GDX_CFG, scale.reshape(-1))
         return out.view(bs, njoints, nfeats, nframes)

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..engine import GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError
+from ..engine import GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_interval_of
 from .rotation2xyz import Rotation2xyz
 
 ROPE_ROWS = 4096
@@ -303,6 +303,7 @@ class MDM(_NativeDenoiser):
         """x [B, njoints, nfeats, T]; timesteps [B] int; y: dict with 'seed' [B,J,1,P], 'mfcc'
         [B,26,1,T], optional 'uncond'.  Returns [B, njoints, nfeats, T] (contiguous)."""
         self._check_inputs(x, y)
+        guidance_interval_of(y, False)                     # the key needs a ClassifierFreeSampleModel: ValueError here
         bs, njoints, nfeats, nframes = x.shape
         force_mask = y.get("uncond", False)
         seed = y["seed"]                                   # KeyError like the reference (model/mdm.py:125)

@@ -44,6 +44,8 @@ def parse_and_load_from_model(parser, argv=None):
         args.data_dir = asked_data_dir
     if args.cond_mask_prob == 0:
         args.guidance_param = 1
+    if args.guidance_interval is not None and args.guidance_param == 1:
+        parser.error("--guidance_interval needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     return args
 
 
@@ -140,6 +142,10 @@ def add_native_options(parser):
     group.add_argument("--timestep_respacing", default='', type=str,
                        help="e.g. ddim100, or logsnr20 (at most 20 steps, even in log-SNR); '' = all 1000 steps.")
     group.add_argument("--eta", default=0.0, type=float)
+    group.add_argument("--guidance_interval", default=None, type=int, nargs=2, metavar=("LO", "HI"),
+                       help="Classifier-free guidance only while LO <= model timestep <= HI (0..999, after respacing; "
+                            "inclusive); other steps take the conditional prediction and skip the unconditional pass. "
+                            "Every sampler; an error with --guidance_param 1.")
     group.add_argument("--rng", default=None, choices=['torch', 'philox'],
                        help="torch = the reference's generator and draw order (single-GPU default); philox = in-kernel "
                             "counter-based noise keyed by the global sample index (shard invariant; multi-GPU default).")

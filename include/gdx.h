@@ -118,11 +118,33 @@ int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames);
  * linear (model/mdm.py:133-169, model/mdm_old.py:104-108).  seed [B,J,1,P], mfcc [B,26,1,T]. */
 int gdx_set_condition(gdx_handle_t h, const float* seed, const float* mfcc, void* stream);
 
+/* Guidance interval (limited-interval guidance, Kynkaanniemi et al. 2024, arXiv:2404.07724; no counterpart in the reference):
+ * the MODEL timesteps -- the values the denoiser sees after the respacing map, 0..999 for the reference's schedule -- at which
+ * GDX_CFG means guidance, bounds inclusive.  Per-handle state like the conditioning; after gdx_create it is every timestep
+ * (INT64_MIN, INT64_MAX).  One rule everywhere:
+ *   lo <= tau <= hi : guided, exactly u + scale*(c - u)
+ *   otherwise       : unguided, the x0 prediction is the conditional output c itself (not a blend at scale 1: other bits)
+ *   lo > hi         : a legal empty interval, never guided
+ * In the loops (gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop, gdx_bpd_loop) the host decides per step from
+ * timestep_map[index]: an unguided step of a GDX_CFG loop runs the denoiser as GDX_COND on B samples -- the unconditional
+ * pass is never computed -- and its update gets x0_uncond = scale = NULL; both forwards of gdx_plms_loop's first step take
+ * the mode of their own timestep.  Inpainting, clip_denoised, the noise and the multistep history apply after the choice of
+ * x0, unchanged.  gdx_forward under GDX_CFG has its timesteps on the device, so it keeps the double batch and selects per
+ * sample in the blend kernel (no saving there).  Modes other than GDX_CFG ignore the interval.  A null handle fails before
+ * any HIP call. */
+int gdx_set_guidance_interval(gdx_handle_t h, int64_t lo, int64_t hi);
+
+/* Host-side count of the samples pushed through the denoiser since gdx_create: every forward adds the batch it ran (2 * batch
+ * under guidance, batch otherwise; a replayed graph step counts like an eager one).  Issues no GPU work: a test reads off it
+ * that an unguided step skipped the unconditional pass instead of computing and discarding it. */
+int gdx_forward_samples(gdx_handle_t h, int64_t* samples);
+
 /* ---- denoiser -------------------------------------------------------------------------- */
 /* replaces MDM.forward / MDM_Old.forward / ClassifierFreeSampleModel.forward
  * (model/mdm.py:105-224, model/mdm_old.py:84-122, model/cfg_sampler.py:23-28).
  * x [B,J,1,T]; timesteps int64 [B] (already mapped through timestep_map); mode GDX_COND /
- * GDX_UNCOND / GDX_CFG; scale [B] (GDX_CFG only, y['scale']); out [B,J,1,T] contiguous. */
+ * GDX_UNCOND / GDX_CFG; scale [B] (GDX_CFG only, y['scale']); out [B,J,1,T] contiguous.  Under GDX_CFG sample b is blended
+ * when timesteps[b] lies in the handle's guidance interval and is the conditional output otherwise. */
 int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timesteps, int32_t mode,
                 const float* scale, float* out, void* stream);
 
@@ -566,7 +588,8 @@ typedef struct {
 int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a, void* stream);
 
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
- * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  Off by
+ * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  A call whose
+ * steps do not all take the same mode (a guidance interval that begins or ends inside it) runs eagerly.  Off by
  * default: on ROCm 7.2 the replay measured ~10 % slower than eager launches even for launch-dominated small batches
  * (csrc/api.hip, gdx_sample_loop).  Ignored while taps, dump_steps or in-situ profiling are active. */
 int gdx_set_graph_replay(gdx_handle_t h, int32_t on);
