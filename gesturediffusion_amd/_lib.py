@@ -25,7 +25,7 @@ EXPORTS = [
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
     "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
     "gdx_dpm_step", "gdx_dpm_loop", "gdx_dpm_sde_step", "gdx_dpm_sde_loop",
-    "gdx_set_guidance_interval", "gdx_forward_samples",
+    "gdx_set_guidance_interval", "gdx_forward_samples", "gdx_set_guidance_rescale", "gdx_cfg_rescale",
     "gdx_transpose_in", "gdx_transpose_out", "gdx_small_linear", "gdx_gather_rows", "gdx_mfcc_project", "gdx_token0",
 ]
 GDX_BPD_CHUNK = 4096   # include/gdx.h
@@ -151,6 +151,14 @@ class BpdLoopArgs(C.Structure):
     ]
 
 
+class CfgRescaleArgs(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32), ("x0_cond", C.c_void_p),
+        ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("phi", C.c_float), ("t", C.c_void_p), ("lo", C.c_int64),
+        ("hi", C.c_int64), ("workspace", C.c_void_p), ("factor", C.c_void_p), ("out", C.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -230,6 +238,8 @@ def load():
         "gdx_bpd_loop": [vp, C.POINTER(BpdLoopArgs), vp],
         "gdx_set_guidance_interval": [vp, i64, i64],
         "gdx_forward_samples": [vp, C.POINTER(i64)],
+        "gdx_set_guidance_rescale": [vp, C.c_float],
+        "gdx_cfg_rescale": [C.POINTER(CfgRescaleArgs), vp],
         "gdx_profile_begin": [vp, i32],
         "gdx_profile_end": [vp, C.POINTER(C.c_float), C.POINTER(i32)],
     }

@@ -108,6 +108,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     h->temb_table = nullptr; h->temb_table_rows = 0; h->tmap_dev = nullptr; h->c2t_table = nullptr; h->c2t_valid = false;
     h->tables_valid = false;
     h->bpd_xt = h->bpd_z = h->bpd_part = nullptr;
+    h->rs_part = nullptr; h->rs_factor = nullptr;
     // the shape is recorded only once every allocation has succeeded: after a failed hipMalloc a retry with the same
     // shape must allocate again instead of returning early on partial buffers
     h->B = 0; h->T = 0; h->S = frames + 1; h->cond_set = false;
@@ -424,6 +425,14 @@ extern "C" int gdx_set_guidance_interval(gdx_handle_t h, int64_t lo, int64_t hi)
     return 0;
 }
 
+// Guidance rescale (gdx.h): per-handle phi, 0 = off.  Refusals precede any HIP call.
+extern "C" int gdx_set_guidance_rescale(gdx_handle_t h, float phi) {
+    if (!h) return fail("gdx_set_guidance_rescale: null handle");
+    if (!(phi >= 0.0f && phi <= 1.0f)) return fail("gdx_set_guidance_rescale: phi must lie in [0, 1]");
+    h->guide_phi = phi;
+    return 0;
+}
+
 extern "C" int gdx_forward_samples(gdx_handle_t h, int64_t* samples) {
     if (!h || !samples) return fail("gdx_forward_samples: null argument");
     *samples = h->forward_samples;
@@ -436,6 +445,34 @@ static int step_mode(const gdx_model* h, int mode, const int64_t* timestep_map, 
     if (mode != GDX_CFG) return mode;
     const int64_t tau = timestep_map[idx];
     return h->guide_lo <= tau && tau <= h->guide_hi ? GDX_CFG : GDX_COND;
+}
+
+// gdx_cfg_rescale on the handle's buffers: c, u -> out for the B samples of the workspace, guided where t == nullptr or
+// lo <= t[b] <= hi.  The chunk sums and factors belong to the handle (first use allocates, gdx_prepare resets).
+static int rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s) {
+    const size_t per = (size_t)h->J * h->T, chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
+    if (!h->rs_part && dev_alloc(h->ws_allocs, (void**)&h->rs_part, sizeof(double) * 4 * h->B * chunks)) return -1;
+    if (!h->rs_factor && dev_alloc(h->ws_allocs, (void**)&h->rs_factor, sizeof(float) * h->B)) return -1;
+    gdx_cfg_rescale_args_t r;
+    memset(&r, 0, sizeof(r));
+    r.batch = h->B; r.njoints = h->J; r.frames = h->T;
+    r.x0_cond = c; r.x0_uncond = u; r.scale = scale; r.phi = h->guide_phi;
+    r.t = t; r.lo = h->guide_lo; r.hi = h->guide_hi;
+    r.workspace = h->rs_part; r.factor = h->rs_factor; r.out = out;
+    return gdx_cfg_rescale(&r, (void*)s);
+}
+
+// What the step kernel of a loop step in mode m gets as (x0_uncond, scale) after denoise_step left the prediction in h->x0.
+// Guided without rescale: the uncond half and the scales, the kernel blends.  Guided with the handle's phi > 0: the rescaled
+// guided prediction is formed here, in place on the cond half, and the kernel is called like on an unguided step (NULL, NULL).
+// Every in-library loop asks here.
+static int guided_operands(gdx_model* h, int m, const float* scale, hipStream_t s, const float** x0_uncond, const float** sc) {
+    *x0_uncond = nullptr; *sc = nullptr;
+    if (m != GDX_CFG) return 0;
+    const float* u = h->x0 + (size_t)h->B * h->J * h->T;
+    if (h->guide_phi > 0.0f) return rescale_x0(h, h->x0, u, scale, nullptr, h->x0, s);
+    *x0_uncond = u; *sc = scale;
+    return 0;
 }
 
 // timestep embedding rows for idx[M] (model/mdm.py:296-310): pe gather -> Linear -> SiLU -> Linear.  The same
@@ -465,6 +502,7 @@ extern "C" int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timest
     if (forward_core(h, x, h->temb, h->d, c2t, mode, h->x0, s)) return -1;
     const int64_t per = (int64_t)h->J * h->T;
     // the timesteps are on the device: the double batch stays, the blend selects per sample (guided: blend, else c)
+    if (h->guide_phi > 0.0f) return rescale_x0(h, h->x0, h->x0 + (size_t)h->B * per, scale, timesteps, out, s);
     HIPCHK(launch_cfg_blend(h->x0, h->x0 + (size_t)h->B * per, scale, timesteps, h->guide_lo, h->guide_hi, out, h->B, per, s));
     return 0;
 }
@@ -563,8 +601,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
                 return -1;
         }
         const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        if (denoise_step(h, h->bpd_xt, idx, m, h->x0, s)) return -1;
-        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
+        if (denoise_step(h, h->bpd_xt, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale)) return -1;
         u.step_index = idx; u.col = k;
         if (gdx_bpd_terms(&u, stream)) return -1;
     }
@@ -605,8 +642,7 @@ extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void
     // the forward at index idx in the mode of its own timestep (guidance interval), and the update's view of its output
     auto denoise = [&](const float* x, int idx) {
         const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
-        return denoise_step(h, x, idx, m, h->x0, s);
+        return denoise_step(h, x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale) ? -1 : 0;
     };
     u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
     const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
@@ -663,8 +699,7 @@ extern "C" int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* 
     int k = a->k_base;
     for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
         const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        if (denoise_step(h, a->x, idx, m, h->x0, s)) return -1;
-        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
+        if (denoise_step(h, a->x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale)) return -1;
         u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, lower order at the end
         u.step_index = idx;
         for (int j = 0; j < 2; ++j) u.hist[j] = j < u.order - 1 ? slot(k - 1 - j) : nullptr;
@@ -703,8 +738,7 @@ extern "C" int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a
     int k = a->k_base;
     for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
         const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        if (denoise_step(h, a->x, idx, m, h->x0, s)) return -1;
-        u.x0_uncond = m == GDX_CFG ? h->x0 + (size_t)B * per : nullptr; u.scale = m == GDX_CFG ? a->scale : nullptr;
+        if (denoise_step(h, a->x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale)) return -1;
         u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, first order on the step to sigma = 0
         u.step_index = idx;
         u.hist[0] = u.order > 1 ? slot(k - 1) : nullptr;
@@ -733,13 +767,13 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     int dump_i = 0;
     while (dump_i < a->n_dump && a->dump_steps[dump_i] < a->k_base) ++dump_i;     // entries of earlier blocks
     auto mode_at = [&](int idx) { return step_mode(h, a->mode, a->timestep_map, idx); };
-    auto fill_update = [&](gdx_update_args_t& u, int idx, int k, int mode) {
+    // (x0_uncond, scale): guided_operands' answer for the step
+    auto fill_update = [&](gdx_update_args_t& u, int idx, int k, const float* x0_uncond, const float* scale) {
         memset(&u, 0, sizeof(u));
         u.kind = a->kind; u.batch = B; u.njoints = h->J; u.frames = h->T;
         u.coef = a->coef; u.t = nullptr; u.step_index = idx;
         u.x = a->x; u.x0_cond = h->x0;
-        u.x0_uncond = mode == GDX_CFG ? h->x0 + (size_t)B * per : nullptr;
-        u.scale = mode == GDX_CFG ? a->scale : nullptr;
+        u.x0_uncond = x0_uncond; u.scale = scale;
         u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
         u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
         u.const_noise = a->const_noise;
@@ -749,9 +783,10 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     };
     auto eager_step = [&](int idx, int k) -> int {
         const int m = mode_at(idx);
-        if (denoise_step(h, a->x, idx, m, h->x0, s)) return -1;
+        const float *x0u, *sc;
+        if (denoise_step(h, a->x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &x0u, &sc)) return -1;
         gdx_update_args_t u;
-        fill_update(u, idx, k, m);
+        fill_update(u, idx, k, x0u, sc);
         if (gdx_sampler_update(&u, stream)) return -1;
         while (a->dump && dump_i < a->n_dump && a->dump_steps[dump_i] <= k) {      // duplicates / stale entries never stall
             if (a->dump_steps[dump_i] == k)
@@ -781,7 +816,10 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     // (no inpainting, no dumps; the tape is read in place), the state stays in the input GEMM's operand layout for the whole
     // call -- one transpose in front, none per step (2 launches and ~40 MB per step less), the last update also writes the
     // sample in the reference layout.  Bit-identical to the general path (tests: fused Philox loop == step-wise Philox loop).
-    if (!((uintptr_t)a->noise_tape & 15) && !a->inpaint_mask && !a->n_dump && !h->graph_replay && !h->keep_taps && h->T % 4 == 0) {
+    // the guidance rescale has no token-major variant: a call that rescales a step takes the general path
+    const bool rescales = h->guide_phi > 0.0f && any_guided;
+    if (!((uintptr_t)a->noise_tape & 15) && !a->inpaint_mask && !a->n_dump && !h->graph_replay && !h->keep_taps && h->T % 4 == 0 &&
+        !rescales) {
         // guided loop: the state holds both halves (the same x feeds both passes).  An unguided step reads and writes the cond
         // half and mirrors into the uncond half only when the NEXT step of this call is guided (every call transposes the
         // state in afresh); a call without a guided step keeps one half, like a loop that is not guided at all.
@@ -839,9 +877,11 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
             const int64_t counted = h->forward_samples;          // the capture enqueues no forward: the replays are counted
             int rc = denoise_step(h, a->x, 0, mode0, h->x0, h->gstream, h->gstate);
             h->forward_samples = counted;
+            const float *x0u = nullptr, *sc = nullptr;           // the rescale's launches depend on no per-step state: captured as they are
+            if (!rc) rc = guided_operands(h, mode0, a->scale, h->gstream, &x0u, &sc);
             if (!rc) {
                 gdx_update_args_t u;
-                fill_update(u, 0, 0, mode0);                      // noise: step 0's slice; the kernel adds state[1] * stride
+                fill_update(u, 0, 0, x0u, sc);                    // noise: step 0's slice; the kernel adds state[1] * stride
                 rc = gdx_sampler_update_state_(&u, h->gstate, (long)(tape_rows * per), (void*)h->gstream);
             }
             if (!rc && launch_advance_state(h->gstate, h->gstream) != hipSuccess) rc = -1;

@@ -127,7 +127,10 @@ struct gdx_model {
     long rows_alloc = 0;              // rows of the [2B*S + pad] token buffers
     bool cond_set = false;
     int64_t guide_lo = INT64_MIN, guide_hi = INT64_MAX;   // gdx_set_guidance_interval: model timesteps that get guidance
-    int64_t forward_samples = 0;      // gdx_forward_samples: samples pushed through forward_core since gdx_create
+    float guide_phi = 0.f;            // gdx_set_guidance_rescale: 0 = off
+    double* rs_part = nullptr;        // guidance rescale: chunk sums [B][chunks][4] and factors [B], allocated on first use
+    float* rs_factor = nullptr;
+    int64_t forward_samples = 0;     // gdx_forward_samples: samples pushed through forward_core since gdx_create
     gdx::Act xa, xb, qkv, ctx, tmp, ffb;   // [rows_alloc] token rows: residual stream (xa, xb), sublayer operands and outputs
     gdx::Act xt, xc;                       // token-major pose in / compacted last layer, [2B*T + pad] rows
     gdx::Act emb, xseq;                    // V2 front end: InputProcess output, proj_pose output

@@ -743,6 +743,107 @@ __global__ void bpd_finish_kernel(const float* __restrict__ part, int chunks, lo
     out[(long)b * ld + col] = m;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Guidance rescale (Lin et al. 2023, arXiv:2305.08891 section 3.4; gdx.h gdx_cfg_rescale): the guided output g = cfg_blend(c, u, s)
+// of a sample scaled by f = phi * std(c)/std(g) + (1 - phi).  Three launches: per-chunk sums of c, c^2, g, g^2 in fp64 (an fp32
+// value widens exactly and its square is exact in fp64, so only the additions round), the sample's factor, the streaming pass.
+// A sample is guided when t == NULL or lo <= t[b] <= hi; an unguided one keeps c and gets the factor 1.
+struct CfgRescaleDev {
+    long per_sample, groups;
+    int chunks, batch;
+    const float *c, *u, *scale;
+    const int64_t* t;
+    int64_t lo, hi;
+    double phi;
+    double* part;
+    float *factor, *out;
+};
+__device__ __forceinline__ bool rescale_guided(const CfgRescaleDev& a, int b) {
+    if (!a.t) return true;
+    const int64_t tb = a.t[b];
+    return a.lo <= tb && tb <= a.hi;
+}
+
+// bpd_terms_kernel's decomposition and summation order (grid (chunks, B), thread -> wave -> block -> one ordinary store of the
+// block's four sums to part[(b*chunks + chunk)*4 ..]): a function of J*T alone, no atomics.
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_rescale_stats_kernel(const CfgRescaleDev a) {
+    __shared__ double red[4][4];
+    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    if (!rescale_guided(a, b)) return;                             // block-uniform
+    const float sc = a.scale[b];
+    const long base = (long)b * a.per_sample;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                            // sum c, sum c^2, sum g, sum g^2
+    for (int it = 0; it < BPD_GROUPS / 256; ++it) {
+        const long grp = (long)chunk * BPD_GROUPS + it * 256 + tid;
+        if (grp >= a.groups) break;
+        const long e0 = base + 4L * grp;
+        const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
+        const f32x4 c = load4<VEC>(a.c, e0, nval);
+        const f32x4 u = load4<VEC>(a.u, e0, nval);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < nval) {
+                const double dc = (double)c[i], dg = (double)cfg_blend(c[i], u[i], sc);
+                s[0] = __dadd_rn(s[0], dc);
+                s[1] = __dadd_rn(s[1], __dmul_rn(dc, dc));
+                s[2] = __dadd_rn(s[2], dg);
+                s[3] = __dadd_rn(s[3], __dmul_rn(dg, dg));
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] = __dadd_rn(s[q], __shfl_down(s[q], off, 64));
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) red[tid >> 6][q] = s[q];
+    }
+    __syncthreads();
+    if (tid < 4)
+        a.part[((long)b * a.chunks + chunk) * 4 + tid] =
+            __dadd_rn(__dadd_rn(__dadd_rn(red[0][tid], red[1][tid]), red[2][tid]), red[3][tid]);
+}
+
+// One thread per sample: the chunk sums in chunk order, then f = (float)(phi * sqrt(SS_c / SS_g) + (1 - phi)) with
+// SS = max(Q - S^2/N, 0), all in fp64 and rounded once.  SS_g == 0 (a constant guided output) gives 1; a NaN or infinity in the
+// sample makes SS NaN, which passes both comparisons and reaches f.
+__global__ void cfg_rescale_factor_kernel(const CfgRescaleDev a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    if (!rescale_guided(a, b)) { a.factor[b] = 1.0f; return; }
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int ch = 0; ch < a.chunks; ++ch) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] = __dadd_rn(s[q], a.part[((long)b * a.chunks + ch) * 4 + q]);
+    }
+    const double n = (double)a.per_sample;
+    double ss_c = __dsub_rn(s[1], __ddiv_rn(__dmul_rn(s[0], s[0]), n));
+    double ss_g = __dsub_rn(s[3], __ddiv_rn(__dmul_rn(s[2], s[2]), n));
+    if (ss_c < 0.0) ss_c = 0.0;
+    if (ss_g < 0.0) ss_g = 0.0;
+    const double r = ss_g == 0.0 ? 1.0 : __dsqrt_rn(__ddiv_rn(ss_c, ss_g));
+    a.factor[b] = (float)__dadd_rn(__dmul_rn(a.phi, r), __dsub_rn(1.0, a.phi));
+}
+
+// out = guided ? g * f : c, grid (ceil(groups / 256), B) like dpm_step_kernel; out may alias c (a thread reads its group first)
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_rescale_apply_kernel(const CfgRescaleDev a) {
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    if (grp >= a.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
+    f32x4 x0 = load4<VEC>(a.c, g.e0, g.nval);
+    if (rescale_guided(a, g.b)) {
+        const f32x4 u = load4<VEC>(a.u, g.e0, g.nval);
+        const float sc = a.scale[g.b], f = a.factor[g.b];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x0[i] = __fmul_rn(cfg_blend(x0[i], u[i], sc), f);
+    }
+    store4<VEC>(a.out, g.e0, g.nval, x0);
+}
+
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
                             float* out, int B, int64_t per_sample, hipStream_t s) {
     const long total = (long)B * per_sample;
@@ -1045,6 +1146,36 @@ extern "C" int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream) {
                        d.per_sample, a->batch, a->vb, a->prior ? nullptr : a->xstart_mse, a->prior ? nullptr : a->mse, a->ld,
                        a->col);
     return launch_status("gdx_bpd_terms: launch failed");
+}
+
+extern "C" int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream) {
+    using namespace gdx;
+    if (!a) return gdx_set_error_("gdx_cfg_rescale: null argument");
+    if (!a->x0_cond || !a->x0_uncond || !a->scale || !a->workspace || !a->factor || !a->out)
+        return gdx_set_error_("gdx_cfg_rescale: null argument");
+    if (a->batch <= 0 || a->njoints <= 0 || a->frames <= 0 || a->batch > 65535) return gdx_set_error_("gdx_cfg_rescale: bad shape");
+    if (!(a->phi >= 0.0f && a->phi <= 1.0f)) return gdx_set_error_("gdx_cfg_rescale: phi must lie in [0, 1]");
+    if ((uintptr_t)a->workspace & 7) return gdx_set_error_("gdx_cfg_rescale: workspace not 8-byte aligned");
+    CfgRescaleDev d;
+    d.per_sample = (long)a->njoints * a->frames;
+    d.groups = (d.per_sample + 3) / 4;
+    d.chunks = (int)((d.per_sample + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK);
+    d.batch = a->batch;
+    d.c = a->x0_cond; d.u = a->x0_uncond; d.scale = a->scale;
+    d.t = a->t; d.lo = a->lo; d.hi = a->hi;
+    d.phi = (double)a->phi;
+    d.part = a->workspace; d.factor = a->factor; d.out = a->out;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 block(256);
+    if (vec_ok(d.per_sample, d.c, d.u)) hipLaunchKernelGGL(cfg_rescale_stats_kernel<true>, dim3(d.chunks, a->batch), block, 0, s, d);
+    else hipLaunchKernelGGL(cfg_rescale_stats_kernel<false>, dim3(d.chunks, a->batch), block, 0, s, d);
+    if (launch_status("gdx_cfg_rescale: launch failed")) return -1;
+    hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3((a->batch + 63) / 64), dim3(64), 0, s, d);
+    if (launch_status("gdx_cfg_rescale: launch failed")) return -1;
+    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
+    if (vec_ok(d.per_sample, d.c, d.u, d.out)) hipLaunchKernelGGL(cfg_rescale_apply_kernel<true>, grid, block, 0, s, d);
+    else hipLaunchKernelGGL(cfg_rescale_apply_kernel<false>, grid, block, 0, s, d);
+    return launch_status("gdx_cfg_rescale: launch failed");
 }
 
 // internal (api.hip, gdx_bpd_loop): x_t and the stored Philox noise of one step (bpd_xt_kernel)

@@ -476,10 +476,12 @@ class GaussianDiffusion:
             raise _window_error(T, 10)
         guided = isinstance(model, ClassifierFreeSampleModel)
         interval = E.guidance_interval_of(y, guided)
+        phi = E.guidance_rescale_of(y, guided)
         eng = inner._get_engine(x.device)
         eng.prepare(B, T)
         eng.set_condition(y["seed"], y["mfcc"], cache=False)
         eng.set_guidance_interval(interval)          # at every loop; None resets a reused handle to "every timestep"
+        eng.set_guidance_rescale(phi)                # likewise: an absent key sets 0 (off)
         if guided:
             mode, scale = GDX_CFG, E.f32c(y["scale"].reshape(-1), "y['scale']")
         else:

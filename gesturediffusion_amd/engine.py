@@ -131,6 +131,29 @@ class Engine:
         lo, hi = interval if interval is not None else (_lib.INT64_MIN, _lib.INT64_MAX)
         _lib.check(self.lib.gdx_set_guidance_interval(self.handle, lo, hi), self.lib)
 
+    def set_guidance_rescale(self, phi=0.0):
+        """phi in [0, 1]: guided x0 predictions are rescaled to the conditional output's per-sample standard deviation and mixed
+        with the unscaled ones by phi (gdx_set_guidance_rescale); 0 = off."""
+        _lib.check(self.lib.gdx_set_guidance_rescale(self.handle, float(phi)), self.lib)
+
+    def cfg_rescale(self, c, u, scale, phi, t=None, interval=None, out=None):
+        """The stand-alone gdx_cfg_rescale on [B,J,1,T] device tensors -> (out, factor [B]); t (int64 [B]) with interval (lo, hi)
+        marks the guided samples (None: all); out may be c itself.  Operands are taken as they are (no copies): tests hand it
+        misaligned views."""
+        B, J, F, T = c.shape
+        dev = c.device
+        if out is None:
+            out = torch.empty_like(c)
+        factor = torch.empty(B, device=dev, dtype=torch.float32)
+        chunks = (J * F * T + _lib.GDX_BPD_CHUNK - 1) // _lib.GDX_BPD_CHUNK
+        ws = torch.empty(4 * B * chunks, device=dev, dtype=torch.float64)
+        lo, hi = interval if interval is not None else (_lib.INT64_MIN, _lib.INT64_MAX)
+        a = _lib.CfgRescaleArgs(batch=B, njoints=J * F, frames=T, x0_cond=c.data_ptr(), x0_uncond=u.data_ptr(),
+                                scale=scale.data_ptr(), phi=float(phi), t=t.data_ptr() if t is not None else None, lo=lo, hi=hi,
+                                workspace=ws.data_ptr(), factor=factor.data_ptr(), out=out.data_ptr())
+        _lib.check(self.lib.gdx_cfg_rescale(C.byref(a), _stream(dev)), self.lib)
+        return out, factor
+
     def forward_samples(self):
         """Samples pushed through the denoiser since the handle was created (gdx_forward_samples; host-side counter)."""
         n = C.c_int64()
@@ -280,6 +303,24 @@ def guidance_interval_of(y, guided_model):
     if not (_lib.INT64_MIN <= lo <= _lib.INT64_MAX and _lib.INT64_MIN <= hi <= _lib.INT64_MAX):
         raise ValueError(f"y['guidance_interval'] bounds must fit 64 bits, got {iv!r}")
     return lo, hi
+
+
+def guidance_rescale_of(y, guided_model):
+    """y['guidance_rescale'] validated -> phi, a Python float with 0 <= phi <= 1 (0.0 when the key is absent: off).  ValueError
+    for anything but a finite Python float or int in that range -- a bool is refused, and a tensor because reading it would
+    synchronise -- and for a key on a model that is not a ClassifierFreeSampleModel (`guided_model` False)."""
+    if "guidance_rescale" not in y:
+        return 0.0
+    phi = y["guidance_rescale"]
+    if not guided_model:
+        raise ValueError("y['guidance_rescale'] needs a ClassifierFreeSampleModel: this model runs no guidance to rescale")
+    if isinstance(phi, torch.Tensor):
+        raise ValueError("y['guidance_rescale'] must be a Python float, not a tensor: reading it would synchronise")
+    if isinstance(phi, bool) or not isinstance(phi, (int, float)):
+        raise ValueError(f"y['guidance_rescale'] must be a Python float in [0, 1], got {phi!r}")
+    if not 0 <= phi <= 1:                                    # False for NaN and the infinities too
+        raise ValueError(f"y['guidance_rescale'] must be finite and satisfy 0 <= phi <= 1, got {phi!r}")
+    return float(phi)
 
 
 # ---------------------------------------------------------------------- standalone kernels

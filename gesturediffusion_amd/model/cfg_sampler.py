@@ -7,11 +7,12 @@ between them; the MFCC conditioning feeds both, as in the reference) and the ble
 kernel.  Nothing is deep-copied.
 
 `y['guidance_interval'] = (lo, hi)` (additive) limits guidance to model timesteps lo <= t <= hi; a sample outside it gets
-the conditional output itself.
+the conditional output itself.  `y['guidance_rescale'] = phi` (additive, 0 <= phi <= 1) rescales a guided output to the
+conditional output's per-sample standard deviation and mixes it with the unscaled one by phi (include/gdx.h).
 """
 import torch.nn as nn
 
-from ..engine import GDX_CFG, guidance_interval_of
+from ..engine import GDX_CFG, guidance_interval_of, guidance_rescale_of
 from .mdm import _NativeDenoiser
 
 
@@ -45,11 +46,13 @@ class ClassifierFreeSampleModel(nn.Module):
         if m.data_rep != "genea_vec":
             raise NotImplementedError
         interval = guidance_interval_of(y, True)
+        phi = guidance_rescale_of(y, True)
         eng = m._get_engine(x.device)
         eng.prepare(bs, nframes)
         eng.set_condition(seed, mfcc)
         # per-sample choice in the blend kernel: guided where lo <= timesteps[b] <= hi, else the conditional output; set on
         # every call (None: every timestep), so a handle never keeps the interval of an earlier call
         eng.set_guidance_interval(interval)
+        eng.set_guidance_rescale(phi)              # likewise: an absent key sets 0
         out = eng.forward(x, timesteps, GDX_CFG, scale.reshape(-1))
         return out.view(bs, njoints, nfeats, nframes)

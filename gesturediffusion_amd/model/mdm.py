@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..engine import GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_interval_of
+from ..engine import GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_interval_of, guidance_rescale_of
 from .rotation2xyz import Rotation2xyz
 
 ROPE_ROWS = 4096
@@ -304,6 +304,7 @@ class MDM(_NativeDenoiser):
         [B,26,1,T], optional 'uncond'.  Returns [B, njoints, nfeats, T] (contiguous)."""
         self._check_inputs(x, y)
         guidance_interval_of(y, False)                     # the key needs a ClassifierFreeSampleModel: ValueError here
+        guidance_rescale_of(y, False)
         bs, njoints, nfeats, nframes = x.shape
         force_mask = y.get("uncond", False)
         seed = y["seed"]                                   # KeyError like the reference (model/mdm.py:125)

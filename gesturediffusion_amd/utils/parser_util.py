@@ -46,6 +46,10 @@ def parse_and_load_from_model(parser, argv=None):
         args.guidance_param = 1
     if args.guidance_interval is not None and args.guidance_param == 1:
         parser.error("--guidance_interval needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
+    if not 0 <= args.guidance_rescale <= 1:
+        parser.error("--guidance_rescale must lie in [0, 1]")
+    if args.guidance_rescale > 0 and args.guidance_param == 1:
+        parser.error("--guidance_rescale needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     return args
 
 
@@ -145,6 +149,10 @@ def add_native_options(parser):
     group.add_argument("--guidance_interval", default=None, type=int, nargs=2, metavar=("LO", "HI"),
                        help="Classifier-free guidance only while LO <= model timestep <= HI (0..999, after respacing; "
                             "inclusive); other steps take the conditional prediction and skip the unconditional pass. "
+                            "Every sampler; an error with --guidance_param 1.")
+    group.add_argument("--guidance_rescale", default=0.0, type=float, metavar="PHI",
+                       help="Guidance rescale (Lin et al. 2023): scale each guided x0 prediction to the conditional one's "
+                            "per-sample standard deviation and mix it with the unscaled one by PHI in [0, 1]; 0 = off. "
                             "Every sampler; an error with --guidance_param 1.")
     group.add_argument("--rng", default=None, choices=['torch', 'philox'],
                        help="torch = the reference's generator and draw order (single-GPU default); philox = in-kernel "

@@ -134,6 +134,49 @@ int gdx_set_condition(gdx_handle_t h, const float* seed, const float* mfcc, void
  * any HIP call. */
 int gdx_set_guidance_interval(gdx_handle_t h, int64_t lo, int64_t hi);
 
+/* Guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", arXiv:2305.08891,
+ * section 3.4; no counterpart in the reference): the guided x0 prediction of a sample is scaled so that its standard deviation
+ * over the sample's N = J*T elements matches the conditional output's, mixed with the unscaled one by phi.  One rule everywhere,
+ * for sample b with conditional output c, unconditional u and s = scale[b]:
+ *   g_i  = u_i + s*(c_i - u_i)                        fp32, exactly the blend of today
+ *   S_c = sum c_i, Q_c = sum c_i^2, S_g = sum g_i, Q_g = sum g_i^2         accumulated in fp64
+ *   SS_c = max(Q_c - S_c^2/N, 0),  SS_g = max(Q_g - S_g^2/N, 0)
+ *   r    = SS_g > 0 ? sqrt(SS_c / SS_g) : 1           (= std(c)/std(g))
+ *   f    = (float)(phi*r + (1 - phi))                 fp64 expression on phi widened from float, rounded once
+ *   out_i = fl32(g_i * f)
+ * The statistics are over the raw model outputs of the whole sample; inpainting and clip_denoised apply afterwards, in the step
+ * kernel, unchanged.  An unguided sample (guidance interval) keeps c, f = 1.  A constant guided output gives f = 1.  A NaN or
+ * infinity in a sample makes that sample's f and output NaN and touches no other sample.  fp64 sums: an fp32 value widens
+ * exactly and its square is exact in fp64, so f is within one fp32 ulp of any other fp64 evaluation whatever the summation
+ * order; an fp32 one-pass sum loses the variance at |mean| >> std.
+ *
+ * gdx_set_guidance_rescale: per-handle state like the guidance interval, 0 (off) after gdx_create; phi outside [0, 1] (NaN
+ * included) or a null handle is refused before any HIP call.  With phi > 0, gdx_forward under GDX_CFG and every guided step of
+ * the in-library loops (gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop, gdx_bpd_loop) run gdx_cfg_rescale between
+ * the denoiser and the step kernel, which then gets x0_uncond = scale = NULL like an unguided step; a guided step still runs
+ * 2 * batch samples.  With phi == 0 nothing is launched and every result keeps its bits.  There is no token-major variant of
+ * the rescale: a gdx_sample_loop call with phi > 0 and at least one guided step takes the pose-layout path (two transposes per
+ * step more than the token-major path).  Graph replay captures the three launches with the step. */
+int gdx_set_guidance_rescale(gdx_handle_t h, float phi);
+
+/* The stand-alone operation, three launches on `stream`: per-chunk fp64 sums (grid (ceil(J*T / GDX_BPD_CHUNK), batch), no
+ * atomics: a sample's numbers do not depend on the batch around it), the factor of every sample, the streaming pass.
+ * Refusals (a null struct or pointer other than t, non-positive sizes, batch > 65535, phi outside [0, 1]) come before the first
+ * HIP call.  At phi = 0 it still computes: f = 1 exactly and out = g. */
+typedef struct {
+    int32_t batch, njoints, frames;
+    const float* x0_cond;      /* [B,J,1,T] */
+    const float* x0_uncond;    /* [B,J,1,T] */
+    const float* scale;        /* [B] */
+    float phi;
+    const int64_t* t;          /* device [B] model timesteps, or NULL: every sample guided */
+    int64_t lo, hi;            /* with t: sample b is guided when lo <= t[b] <= hi (the rule of gdx_set_guidance_interval) */
+    double* workspace;         /* device, 4 * batch * ceil(J*T / GDX_BPD_CHUNK) doubles, the caller's */
+    float* factor;             /* out [B]: f, 1 for an unguided sample */
+    float* out;                /* [B,J,1,T]; may alias x0_cond */
+} gdx_cfg_rescale_args_t;
+int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream);
+
 /* Host-side count of the samples pushed through the denoiser since gdx_create: every forward adds the batch it ran (2 * batch
  * under guidance, batch otherwise; a replayed graph step counts like an eager one).  Issues no GPU work: a test reads off it
  * that an unguided step skipped the unconditional pass instead of computing and discarding it. */
