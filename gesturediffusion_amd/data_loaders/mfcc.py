@@ -76,12 +76,36 @@ class MfccExtractor:
     def num_frames(self, n):
         return 1 if n <= self.frame_len else 1 + int(math.ceil((1.0 * n - self.frame_len) / self.frame_step))
 
-    def __call__(self, signal):
+    def _stage_widths(self):
+        """Row widths of the workspace's four row-major stages (csrc/api.hip, above gdx_mfcc): frames | spec | pw | mel."""
+        return self.Lp, 2 * self.nbp, self.nbp, 64
+
+    def workspace_size(self, F):
+        return (F + _lib.GDX_ROW_PAD) * sum(self._stage_widths()) + F     # gdx.h: F + GDX_ROW_PAD rows per stage, then energy [F]
+
+    def workspace(self, F, fill=0.0, device=None):
+        """The workspace gdx_mfcc needs for F frames; the library asks nothing of its contents."""
+        return torch.full((self.workspace_size(F),), fill, device=device or self.device, dtype=torch.float32)
+
+    def stage_views(self, work, F):
+        """Views of a workspace after a call: frames [F, Lp], spec [F, 2*nbp] (re | im), pw [F, nbp], mel [F, 64], energy [F]."""
+        if work.dim() != 1 or work.numel() < self.workspace_size(F):
+            raise ValueError(f"workspace of {work.numel()} floats is below the {self.workspace_size(F)} that {F} frames need")
+        rows, off, views = F + _lib.GDX_ROW_PAD, 0, []
+        for w in self._stage_widths():
+            views.append(work[off: off + rows * w].view(rows, w)[:F])
+            off += rows * w
+        return (*views, work[off: off + F])
+
+    def __call__(self, signal, work=None):
         x = f32c(signal, "signal").reshape(-1)
         n = x.numel()
         F = self.num_frames(n)
-        rows = F + _lib.GDX_ROW_PAD                # gdx.h: workspace rows per stage
-        work = torch.zeros(rows * (self.Lp + 3 * self.nbp + 64) + F, device=x.device, dtype=torch.float32)
+        if work is None:
+            work = self.workspace(F, device=x.device)
+        elif (work.dtype != torch.float32 or work.device != x.device or not work.is_contiguous()
+              or work.dim() != 1 or work.numel() < self.workspace_size(F)):
+            raise ValueError(f"work: a contiguous fp32 vector of at least {self.workspace_size(F)} floats on the signal's device")
         out = torch.empty(F, self.numcep, device=x.device, dtype=torch.float32)
         lib = _lib.load()
         _lib.check(lib.gdx_mfcc(_ptr(x), n, self.frame_len, self.frame_step, F, self.nfft, self.nfilt, self.numcep,
