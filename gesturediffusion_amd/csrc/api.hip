@@ -559,6 +559,14 @@ static const float* tape_slice(const float* tape, int k, int k_base, size_t rows
     return tape ? tape + (ptrdiff_t)(k - k_base) * (ptrdiff_t)(rows * per) : nullptr;
 }
 
+// One forward of a loop at schedule index idx on the state x, in the mode of its own timestep (guidance interval), and the
+// step kernel's view of its output in h->x0: (x0_uncond, scale).  Every in-library loop's eager step asks here; A: its arguments.
+template <typename A>
+static int denoise_guided(gdx_model* h, const A* a, const float* x, int idx, hipStream_t s, const float** x0_uncond, const float** scale) {
+    const int m = step_mode(h, a->mode, a->timestep_map, idx);
+    return denoise_step(h, x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, x0_uncond, scale) ? -1 : 0;
+}
+
 // calc_bpd_loop (gaussian_diffusion.py:1537-1592): per step q_sample -> denoiser -> fused bound terms, through the SAME forward
 // entry (pose-layout x_t, forward_core) the step-wise protocol reaches via gdx_forward, so both give the same bits.
 extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* stream) {
@@ -600,8 +608,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
                             stream))
                 return -1;
         }
-        const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        if (denoise_step(h, h->bpd_xt, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale)) return -1;
+        if (denoise_guided(h, a, h->bpd_xt, idx, s, &u.x0_uncond, &u.scale)) return -1;
         u.step_index = idx; u.col = k;
         if (gdx_bpd_terms(&u, stream)) return -1;
     }
@@ -613,141 +620,106 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     return 0;
 }
 
-// plms_sample_loop (gaussian_diffusion.py:995-1190): per step the denoiser through forward_core on the pose-layout state (the
-// entry gdx_forward uses: same bits as the step-wise protocol) and one fused plms_step_kernel launch (sampler.hip).  No graph
-// replay and no token-major variant: PLMS runs 10-50 steps, and its first step needs the state in the reference layout twice.
-// The argument checks need no handle and come first (then null handle, then not prepared), so every refusal precedes the
-// first HIP call.
+// The arguments U of a loop's step kernel at index idx, as far as every pose-layout step struct names them alike: the handle's
+// shape, the loop's coefficients / state (updated in place) / inpainting / clip, and the denoiser's output as denoise_guided left it
+template <typename U, typename A>
+static U step_args(const gdx_model* h, const A* a, int idx, const float* x0_uncond, const float* scale) {
+    U u;
+    memset(&u, 0, sizeof(u));
+    u.batch = h->B; u.njoints = h->J; u.frames = h->T;
+    u.coef = a->coef; u.step_index = idx; u.x = a->x; u.out = a->x;
+    u.x0_cond = h->x0; u.x0_uncond = x0_uncond; u.scale = scale;
+    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
+    return u;
+}
+
+// The scaffold of the multistep loops gdx_plms_loop, gdx_dpm_loop and gdx_dpm_sde_loop (`who`), whose argument structs A name
+// the fields mode .. k_base alike: per step the denoiser through forward_core on the pose-layout state (the entry gdx_forward
+// uses: same bits as the step-wise protocol), then step(idx, k, x0_uncond, scale, slot), the entry's own fused launch; slot(k) =
+// executed step k's place in the caller's ring of a->order buffers at a->*hist.  No graph replay and no token-major variant:
+// these solvers run 10-50 steps.  The argument checks need no handle and come first (then null handle, then not prepared), so
+// every refusal precedes the first HIP call; missing() gives the entry's history refusal or nullptr.  A new multistep sampler
+// is one more caller of this function ("Where a new in-library loop goes").
+template <typename A, typename Missing, typename Step>
+static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_lo, int order_hi, const char* order_msg,
+                          float* A::*hist, Missing missing, hipStream_t s, Step step) {
+    const std::string w = std::string(who) + ": ";
+    if (!a || !a->coef || !a->timestep_map || !a->x) return fail(w + "null argument");
+    if (check_mode(who, a->mode, a->scale)) return -1;
+    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
+        a->run_steps > a->first_index + 1)
+        return fail(w + "bad step range");
+    if (a->order < order_lo || a->order > order_hi) return fail(w + order_msg);
+    if (a->inpaint_mask && !a->inpaint_motion) return fail(w + "mask without motion");
+    if (const char* m = missing()) return fail(w + m);
+    if (check_ready(h, who)) return -1;
+    if (h->B > 65535) return fail(w + "batch exceeds 65535");
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    const size_t n = (size_t)h->B * h->J * h->T;
+    auto slot = [&](int k) { return a->*hist + (size_t)(k % a->order) * n; };
+    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
+    int k = a->k_base;
+    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
+        const float *x0u, *sc;
+        if (denoise_guided(h, a, a->x, idx, s, &x0u, &sc) || step(idx, k, x0u, sc, slot)) return -1;
+    }
+    return 0;
+}
+
+// plms_sample_loop (gaussian_diffusion.py:995-1190): one fused plms_step_kernel launch per step (sampler.hip); the first step
+// needs the state in the reference layout twice.
 extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void* stream) {
-    if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_plms_loop: null argument");
-    if (check_mode("gdx_plms_loop", a->mode, a->scale)) return -1;
-    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
-        a->run_steps > a->first_index + 1)
-        return fail("gdx_plms_loop: bad step range");
-    if (a->order < 2 || a->order > 4) return fail("gdx_plms_loop: order must be 2, 3 or 4");
-    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_plms_loop: mask without motion");
-    if (!a->eps_hist || !a->scratch) return fail("gdx_plms_loop: missing history (eps_hist and scratch are the caller's)");
-    if (check_ready(h, "gdx_plms_loop")) return -1;
     hipStream_t s = (hipStream_t)stream;
-    const int B = h->B;
-    const size_t per = (size_t)h->J * h->T;
-    if (B > 65535) return fail("gdx_plms_loop: batch exceeds 65535");
-    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
-    auto slot = [&](int k) { return a->eps_hist + (size_t)(k % a->order) * B * per; };
-    gdx_plms_step_args_t u;
-    memset(&u, 0, sizeof(u));
-    u.batch = B; u.njoints = h->J; u.frames = h->T;
-    u.coef = a->coef; u.x = a->x;
-    u.x0_cond = h->x0;
-    // the forward at index idx in the mode of its own timestep (guidance interval), and the update's view of its output
-    auto denoise = [&](const float* x, int idx) {
-        const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        return denoise_step(h, x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale) ? -1 : 0;
-    };
-    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
-    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
-    int k = a->k_base;
-    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
-        if (denoise(a->x, idx)) return -1;
-        u.step_index = idx;
-        if (k == 0) {                                   // pseudo improved Euler (:1043-1052): predictor, second forward, corrector
-            u.kind = 6; u.eps_out = slot(0); u.out = a->scratch; u.pred_xstart = slot(1);
-            if (gdx_plms_step(&u, stream)) return -1;
-            const int idx2 = (idx - 1 + a->num_steps) % a->num_steps;
-            if (denoise(a->scratch, idx2)) return -1;
-            u.kind = 5; u.step_index_eps = idx2; u.x_eps = a->scratch; u.eps_hist[0] = slot(0); u.pred_prev = slot(1);
-            u.eps_out = nullptr; u.out = a->x; u.pred_xstart = nullptr;
-            if (gdx_plms_step(&u, stream)) return -1;
-            u.x_eps = nullptr; u.pred_prev = nullptr;
-            continue;
-        }
-        u.kind = k + 1 < a->order ? k + 1 : a->order;
-        u.eps_out = slot(k); u.out = a->x;
-        for (int j = 0; j < 3; ++j) u.eps_hist[j] = j < u.kind - 1 ? slot(k - 1 - j) : nullptr;
-        if (gdx_plms_step(&u, stream)) return -1;
-    }
-    return 0;
+    return multistep_loop(
+        "gdx_plms_loop", h, a, 2, 4, "order must be 2, 3 or 4", &gdx_plms_loop_args_t::eps_hist,
+        [&] { return !a->eps_hist || !a->scratch ? "missing history (eps_hist and scratch are the caller's)" : nullptr; }, s,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot) -> int {
+            auto u = step_args<gdx_plms_step_args_t>(h, a, idx, x0u, sc);
+            if (k == 0) {                               // pseudo improved Euler (:1043-1052): predictor, second forward, corrector
+                u.kind = 6; u.eps_out = slot(0); u.out = a->scratch; u.pred_xstart = slot(1);
+                if (gdx_plms_step(&u, stream)) return -1;
+                const int idx2 = (idx - 1 + a->num_steps) % a->num_steps;
+                if (denoise_guided(h, a, a->scratch, idx2, s, &u.x0_uncond, &u.scale)) return -1;
+                u.kind = 5; u.step_index_eps = idx2; u.x_eps = a->scratch; u.eps_hist[0] = slot(0); u.pred_prev = slot(1);
+                u.eps_out = nullptr; u.out = a->x; u.pred_xstart = nullptr;
+                return gdx_plms_step(&u, stream);
+            }
+            u.kind = k + 1 < a->order ? k + 1 : a->order;
+            u.eps_out = slot(k);
+            for (int j = 0; j < u.kind - 1; ++j) u.eps_hist[j] = slot(k - 1 - j);
+            return gdx_plms_step(&u, stream);
+        });
 }
 
-// dpm_solver_sample_loop (DPM-Solver++ multistep, gdx.h): per step the denoiser through forward_core on the pose-layout state
-// (the entry gdx_forward uses: same bits as the step-wise protocol) and one fused dpm_step_kernel launch (sampler.hip).  No
-// graph replay and no token-major variant: the solver runs 10-40 steps.  The argument checks need no handle and come first
-// (then null handle, then not prepared), so every refusal precedes the first HIP call.
+// dpm_solver_sample_loop (DPM-Solver++ multistep, gdx.h): one fused dpm_step_kernel launch per step (sampler.hip)
 extern "C" int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* stream) {
-    if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_dpm_loop: null argument");
-    if (check_mode("gdx_dpm_loop", a->mode, a->scale)) return -1;
-    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
-        a->run_steps > a->first_index + 1)
-        return fail("gdx_dpm_loop: bad step range");
-    if (a->order < 1 || a->order > 3) return fail("gdx_dpm_loop: order must be 1, 2 or 3");
-    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_dpm_loop: mask without motion");
-    if (a->order > 1 && !a->hist) return fail("gdx_dpm_loop: missing history (hist is the caller's)");
-    if (check_ready(h, "gdx_dpm_loop")) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    const int B = h->B;
-    const size_t per = (size_t)h->J * h->T;
-    if (B > 65535) return fail("gdx_dpm_loop: batch exceeds 65535");
-    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
-    auto slot = [&](int k) { return a->hist + (size_t)(k % a->order) * B * per; };
-    gdx_dpm_step_args_t u;
-    memset(&u, 0, sizeof(u));
-    u.batch = B; u.njoints = h->J; u.frames = h->T;
-    u.coef = a->coef; u.x = a->x; u.out = a->x;
-    u.x0_cond = h->x0;
-    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
-    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
-    int k = a->k_base;
-    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
-        const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        if (denoise_step(h, a->x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale)) return -1;
-        u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, lower order at the end
-        u.step_index = idx;
-        for (int j = 0; j < 2; ++j) u.hist[j] = j < u.order - 1 ? slot(k - 1 - j) : nullptr;
-        u.pred_out = a->order > 1 ? slot(k) : nullptr;
-        if (gdx_dpm_step(&u, stream)) return -1;
-    }
-    return 0;
+    return multistep_loop(
+        "gdx_dpm_loop", h, a, 1, 3, "order must be 1, 2 or 3", &gdx_dpm_loop_args_t::hist,
+        [&] { return a->order > 1 && !a->hist ? "missing history (hist is the caller's)" : nullptr; }, (hipStream_t)stream,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot) -> int {
+            auto u = step_args<gdx_dpm_step_args_t>(h, a, idx, x0u, sc);
+            u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, lower order at the end
+            for (int j = 0; j < u.order - 1; ++j) u.hist[j] = slot(k - 1 - j);
+            u.pred_out = a->order > 1 ? slot(k) : nullptr;
+            return gdx_dpm_step(&u, stream);
+        });
 }
 
-// dpm_solver_sde_sample_loop (SDE-DPM-Solver++ multistep, gdx.h): gdx_dpm_loop with one fused dpm_sde_step_kernel launch per
-// step, whose noise is slice k - k_base of the tape or Philox draw k + 1.  Same order of refusals, all before the first HIP call.
+// dpm_solver_sde_sample_loop (SDE-DPM-Solver++ multistep, gdx.h): gdx_dpm_loop with the noisy instantiation of dpm_step_kernel,
+// whose noise is slice k - k_base of the tape or Philox draw k + 1
 extern "C" int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a, void* stream) {
-    if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_dpm_sde_loop: null argument");
-    if (check_mode("gdx_dpm_sde_loop", a->mode, a->scale)) return -1;
-    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
-        a->run_steps > a->first_index + 1)
-        return fail("gdx_dpm_sde_loop: bad step range");
-    if (a->order < 1 || a->order > 2) return fail("gdx_dpm_sde_loop: order must be 1 or 2");
-    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_dpm_sde_loop: mask without motion");
-    if (a->order > 1 && !a->hist) return fail("gdx_dpm_sde_loop: missing history (hist is the caller's)");
-    if (check_ready(h, "gdx_dpm_sde_loop")) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    const int B = h->B;
-    const size_t per = (size_t)h->J * h->T;
-    if (B > 65535) return fail("gdx_dpm_sde_loop: batch exceeds 65535");
-    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
-    auto slot = [&](int k) { return a->hist + (size_t)(k % a->order) * B * per; };
-    gdx_dpm_sde_step_args_t u;
-    memset(&u, 0, sizeof(u));
-    u.batch = B; u.njoints = h->J; u.frames = h->T;
-    u.coef = a->coef; u.x = a->x; u.out = a->x;
-    u.x0_cond = h->x0;
-    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
-    u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset;
-    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
-    int k = a->k_base;
-    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
-        const int m = step_mode(h, a->mode, a->timestep_map, idx);
-        if (denoise_step(h, a->x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &u.x0_uncond, &u.scale)) return -1;
-        u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, first order on the step to sigma = 0
-        u.step_index = idx;
-        u.hist[0] = u.order > 1 ? slot(k - 1) : nullptr;
-        u.pred_out = a->order > 1 ? slot(k) : nullptr;
-        u.noise = tape_slice(a->noise_tape, k, a->k_base, B, per);
-        u.rng_step = (uint32_t)(k + 1);
-        if (gdx_dpm_sde_step(&u, stream)) return -1;
-    }
-    return 0;
+    return multistep_loop(
+        "gdx_dpm_sde_loop", h, a, 1, 2, "order must be 1 or 2", &gdx_dpm_sde_loop_args_t::hist,
+        [&] { return a->order > 1 && !a->hist ? "missing history (hist is the caller's)" : nullptr; }, (hipStream_t)stream,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot) -> int {
+            auto u = step_args<gdx_dpm_sde_step_args_t>(h, a, idx, x0u, sc);
+            u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, first order on the step to sigma = 0
+            u.hist[0] = u.order > 1 ? slot(k - 1) : nullptr;
+            u.pred_out = a->order > 1 ? slot(k) : nullptr;
+            u.noise = tape_slice(a->noise_tape, k, a->k_base, h->B, (size_t)h->J * h->T);
+            u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset; u.rng_step = (uint32_t)(k + 1);
+            return gdx_dpm_sde_step(&u, stream);
+        });
 }
 
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
@@ -769,22 +741,15 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     auto mode_at = [&](int idx) { return step_mode(h, a->mode, a->timestep_map, idx); };
     // (x0_uncond, scale): guided_operands' answer for the step
     auto fill_update = [&](gdx_update_args_t& u, int idx, int k, const float* x0_uncond, const float* scale) {
-        memset(&u, 0, sizeof(u));
-        u.kind = a->kind; u.batch = B; u.njoints = h->J; u.frames = h->T;
-        u.coef = a->coef; u.t = nullptr; u.step_index = idx;
-        u.x = a->x; u.x0_cond = h->x0;
-        u.x0_uncond = x0_uncond; u.scale = scale;
-        u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
+        u = step_args<gdx_update_args_t>(h, a, idx, x0_uncond, scale);
+        u.kind = a->kind;
         u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
         u.const_noise = a->const_noise;
         u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset; u.rng_step = (uint32_t)(k + 1);
-        u.out = a->x; u.pred_xstart = nullptr;
-        u.clip_denoised = a->clip_denoised;
     };
     auto eager_step = [&](int idx, int k) -> int {
-        const int m = mode_at(idx);
         const float *x0u, *sc;
-        if (denoise_step(h, a->x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, &x0u, &sc)) return -1;
+        if (denoise_guided(h, a, a->x, idx, s, &x0u, &sc)) return -1;
         gdx_update_args_t u;
         fill_update(u, idx, k, x0u, sc);
         if (gdx_sampler_update(&u, stream)) return -1;

@@ -12,6 +12,8 @@
 // NOTE: HIP's __fmul_rn/__fadd_rn are plain * and + and hipcc defaults to -ffp-contract=fast, so this
 // file is compiled with -ffp-contract=off (Makefile) AND carries the pragma below: bit-exactness against
 // the torch expression depends on no mul+add pair being fused.
+#include <string>
+
 #include "gdx_internal.h"
 #include "../../include/gdx.h"
 
@@ -100,26 +102,42 @@ __device__ __forceinline__ float cfg_blend(float c, float u, float sc) { return 
 // torch.clamp(v, -1, 1): a NaN stays a NaN
 __device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
 
-// pred_xstart of p_mean_variance for a group of sample b: CFG blend (x0u set) -> inpainting (:307-311) -> clip_denoised (:349-355)
+// What every pose-layout step kernel is given besides its own operands: the group geometry, the coefficient row selection,
+// the state x, the x0 operands of pred_xstart4, and the outputs (x_{t-1}, and pred = the x0 it formed, or nullptr).
+struct StepSrc {
+    long per_sample;        // J*T
+    long groups;            // ceil(per_sample/4)
+    const float* coef;
+    const int64_t* t;
+    int step_index;
+    const float *x, *x0c, *x0u, *scale;
+    const uint8_t* mask;
+    const float* motion;
+    int clip;               // clip_denoised: x0 clamped to [-1, 1] after the CFG / inpainting blends (reference :349-355)
+    float *out, *pred;
+};
+// the coefficient row of sample b
+__device__ __forceinline__ long coef_row(const StepSrc& s, int b) { return s.t ? s.t[b] : s.step_index; }
+
+// pred_xstart of p_mean_variance for group g: CFG blend (x0u set) -> inpainting (:307-311) -> clip_denoised (:349-355)
 // (the guidance scale scale[b] is read only under guidance)
 template <bool VEC>
-__device__ __forceinline__ f32x4 pred_xstart4(const float* x0c, const float* x0u, const float* scale, int b, const uint8_t* mask,
-                                              const float* motion, int clip, long e0, int nval) {
-    f32x4 x0 = load4<VEC>(x0c, e0, nval);
-    if (x0u) {
-        const f32x4 u = load4<VEC>(x0u, e0, nval);
-        const float sc = scale[b];
+__device__ __forceinline__ f32x4 pred_xstart4(const StepSrc& s, const Group& g) {
+    f32x4 x0 = load4<VEC>(s.x0c, g.e0, g.nval);
+    if (s.x0u) {
+        const f32x4 u = load4<VEC>(s.x0u, g.e0, g.nval);
+        const float sc = s.scale[g.b];
 #pragma unroll
         for (int i = 0; i < 4; ++i) x0[i] = cfg_blend(x0[i], u[i], sc);
     }
-    if (mask) {
-        const uint32_t m = mask4<VEC>(mask, e0, nval);
-        const f32x4 mo = load4<VEC>(motion, e0, nval);
+    if (s.mask) {
+        const uint32_t m = mask4<VEC>(s.mask, g.e0, g.nval);
+        const f32x4 mo = load4<VEC>(s.motion, g.e0, g.nval);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if ((m >> (8 * i)) & 0xffu) x0[i] = mo[i];
     }
-    if (clip) {
+    if (s.clip) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) x0[i] = clamp1(x0[i]);
     }
@@ -202,20 +220,12 @@ __device__ __forceinline__ float dpm_sde_multistep(float a, const float* w, floa
 }
 
 struct UpdateDev {
-    int kind;
-    long per_sample;        // J*T
-    long groups;            // ceil(per_sample/4)
-    int batch;
-    const float* coef;
-    const int64_t* t;
-    int step_index;
-    const float *x, *x0c, *x0u, *scale;
-    const uint8_t* mask;
-    const float *motion, *noise;
+    StepSrc s;
+    int kind, batch;
+    const float* noise;
     int const_noise;
     uint64_t seed, sample_offset;
     uint32_t rng_step;
-    float *out, *pred;
     // graph replay (gdx_sample_loop): when `state` is set the step-dependent values come from device memory, so one
     // captured step can be replayed for every step: state[0] = schedule index, state[1] = executed-step number k
     // (rng_step = k + 1, noise = noise + k * noise_stride)
@@ -224,21 +234,20 @@ struct UpdateDev {
     // cond_fn guidance (reference :418-494): gradient tensor and, for DDIM, the per-step sqrt(1 - alpha_bar) table
     const float* grad;
     const float* gcoef;
-    int clip;               // clip_denoised: x0 clamped to [-1, 1] after the CFG / inpainting blends (reference :349-355)
 };
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void update_kernel(const UpdateDev a) {
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= a.groups * a.batch) return;
-    const Group g = group_of<VEC>(gid, a.groups, a.per_sample);
-    const long idx = a.state ? a.state[0] : (a.t ? a.t[g.b] : a.step_index);
-    const float* c = a.coef + idx * 8;
+    if (gid >= a.s.groups * a.batch) return;
+    const Group g = group_of<VEC>(gid, a.s.groups, a.s.per_sample);
+    const long idx = a.state ? a.state[0] : coef_row(a.s, g.b);
+    const float* c = a.s.coef + idx * 8;
     const uint32_t rng_step = a.state ? (uint32_t)a.state[1] + 1u : a.rng_step;
     const float* noise = a.noise && a.state ? a.noise + (long)a.state[1] * a.noise_stride : a.noise;
 
-    const f32x4 x = load4<VEC>(a.x, g.e0, g.nval);
-    const f32x4 x0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, g.e0, g.nval);
+    const f32x4 x = load4<VEC>(a.s.x, g.e0, g.nval);
+    const f32x4 x0 = pred_xstart4<VEC>(a.s, g);
     const f32x4 z = noise ? load4<VEC>(noise, a.const_noise ? 4L * g.grp : g.e0, g.nval)
                           : philox_normal4(a.seed, a.const_noise ? 0ull : a.sample_offset + (uint64_t)g.b, rng_step, g.grp);
     const bool cond = a.grad != nullptr;
@@ -247,8 +256,8 @@ __global__ __launch_bounds__(256) void update_kernel(const UpdateDev a) {
     f32x4 r;
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = update_value(a.kind, c, x[i], x0[i], z[i], cond, grad[i], s1m);
-    store4<VEC>(a.out, g.e0, g.nval, r);
-    if (a.pred) store4<VEC>(a.pred, g.e0, g.nval, x0);
+    store4<VEC>(a.s.out, g.e0, g.nval, r);
+    if (a.s.pred) store4<VEC>(a.s.pred, g.e0, g.nval, x0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -383,32 +392,27 @@ __global__ void plms_kernel(int kind, const float* __restrict__ coef, const int6
 // kind a template argument.  Kind 5 forms eps_2 from the SECOND forward of a loop's first step (state x_eps, row idx_e)
 // and combines it with the stored eps (e1) and the first forward's pred (pred_prev) under row idx.
 struct PlmsStepDev {
-    long per_sample, groups;
-    const float* coef;
-    const int64_t *t, *t_eps;
-    int step_index, step_index_eps;
-    const float *x, *x_eps, *x0c, *x0u, *scale;
-    const uint8_t* mask;
-    const float* motion;
-    const float *e1, *e2, *e3, *pred_prev;
-    int clip;
-    float *eps_out, *out, *pred;
+    StepSrc s;
+    const int64_t* t_eps;
+    int step_index_eps;
+    const float *x_eps, *e1, *e2, *e3, *pred_prev;
+    float* eps_out;
 };
 
 template <int KIND, bool VEC>
 __global__ __launch_bounds__(256) void plms_step_kernel(const PlmsStepDev a) {
     const long grp = (long)blockIdx.x * 256 + threadIdx.x;
-    if (grp >= a.groups) return;
-    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
+    if (grp >= a.s.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.s.per_sample);
     const long e0 = g.e0;
     const int nval = g.nval;
-    const long idx = a.t ? a.t[g.b] : a.step_index;
+    const long idx = coef_row(a.s, g.b);
     const long idx_e = KIND == 5 ? (a.t_eps ? a.t_eps[g.b] : a.step_index_eps) : idx;     // row of this launch's eps
-    const float* c = a.coef + idx * 8;
-    const float* ce = a.coef + idx_e * 8;
+    const float* c = a.s.coef + idx * 8;
+    const float* ce = a.s.coef + idx_e * 8;
 
-    const f32x4 x = load4<VEC>(a.x, e0, nval);
-    const f32x4 x0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, e0, nval);
+    const f32x4 x = load4<VEC>(a.s.x, e0, nval);
+    const f32x4 x0 = pred_xstart4<VEC>(a.s, g);
     const f32x4 xe = KIND == 5 ? load4<VEC>(a.x_eps, e0, nval) : x;
     f32x4 eps;
 #pragma unroll
@@ -425,93 +429,50 @@ __global__ __launch_bounds__(256) void plms_step_kernel(const PlmsStepDev a) {
         else r[i] = plms_tail(c, x[i], plms_combine(KIND, eps[i], e1[i], e2[i], e3[i]), keep[i]);
     }
     if (a.eps_out) store4<VEC>(a.eps_out, e0, nval, eps);
-    if (a.pred) store4<VEC>(a.pred, e0, nval, x0);
-    store4<VEC>(a.out, e0, nval, r);
+    if (a.s.pred) store4<VEC>(a.s.pred, e0, nval, x0);
+    store4<VEC>(a.s.out, e0, nval, r);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// One DPM-Solver++ multistep step in one pass (gdx.h gdx_dpm_step): update_kernel's pred_xstart (CFG blend -> inpainting ->
-// clamp) as m0, then dpm_multistep over it and NH older predictions.  Grid (ceil(groups / 256), B): blockIdx.y is the sample,
-// NH a template argument.  The row's weights of order NH + 1 start at column 1 + NH*(NH + 1)/2: (a, w1_0, w2_0, w2_1, w3_0,
-// w3_1, w3_2, 0).  Memory-bound: per element 2 + NH reads (3 + NH under guidance, + mask and motion under inpainting) and
-// two writes.
+// One DPM-Solver++ multistep step in one pass (gdx.h gdx_dpm_step, gdx_dpm_sde_step): update_kernel's pred_xstart (CFG blend ->
+// inpainting -> clamp) as m0, then dpm_multistep over it and NH older predictions, or (NOISE: SDE-DPM-Solver++)
+// dpm_sde_multistep with the noise scale in column 7 and z from the tape or from philox_normal4 keyed like update_kernel
+// (sample_offset + b, rng_step, group).  Grid (ceil(groups / 256), B): blockIdx.y is the sample, NH a template argument.  The
+// row's weights of order NH + 1 start at column 1 + NH*(NH + 1)/2: (a, w1_0, w2_0, w2_1, w3_0, w3_1, w3_2, 0 or s).
+// Memory-bound: per element 2 + NH reads (3 + NH under guidance, + mask and motion under inpainting, + one under a tape; one
+// Philox draw per group without) and two writes.
 struct DpmStepDev {
-    long per_sample, groups;
-    const float* coef;
-    const int64_t* t;
-    int step_index;
-    const float *x, *x0c, *x0u, *scale;
-    const uint8_t* mask;
-    const float* motion;
+    StepSrc s;
     const float *m1, *m2;
-    int clip;
-    float *out, *pred;
-};
-
-template <int NH, bool VEC>
-__global__ __launch_bounds__(256) void dpm_step_kernel(const DpmStepDev a) {
-    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
-    if (grp >= a.groups) return;
-    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
-    const long e0 = g.e0;
-    const int nval = g.nval;
-    const long idx = a.t ? a.t[g.b] : a.step_index;
-    const float* c = a.coef + idx * 8;
-    const float* w = c + 1 + NH * (NH + 1) / 2;
-
-    const f32x4 x = load4<VEC>(a.x, e0, nval);
-    const f32x4 m0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, e0, nval);
-    f32x4 m1 = {0.f, 0.f, 0.f, 0.f}, m2 = m1;
-    if (NH >= 1) m1 = load4<VEC>(a.m1, e0, nval);
-    if (NH >= 2) m2 = load4<VEC>(a.m2, e0, nval);
-    f32x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = dpm_multistep<NH>(c[0], w, x[i], m0[i], m1[i], m2[i]);
-    if (a.pred) store4<VEC>(a.pred, e0, nval, m0);
-    store4<VEC>(a.out, e0, nval, r);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// One SDE-DPM-Solver++ multistep step in one pass (gdx.h gdx_dpm_sde_step): dpm_step_kernel with the noise term.  Same grid,
-// same weight columns (order NH + 1 starts at column 1 + NH*(NH + 1)/2), the noise scale in column 7; z from the tape or from
-// philox_normal4 keyed like update_kernel (sample_offset + b, rng_step, group).  Memory-bound: dpm_step_kernel's traffic plus
-// one read under a tape, or one Philox draw per group without.
-struct DpmSdeStepDev {
-    long per_sample, groups;
-    const float* coef;
-    const int64_t* t;
-    int step_index;
-    const float *x, *x0c, *x0u, *scale;
-    const uint8_t* mask;
-    const float* motion;
-    const float *m1, *noise;
+    const float* noise;     // NOISE only, like seed, sample_offset and rng_step
     uint64_t seed, sample_offset;
     uint32_t rng_step;
-    int clip;
-    float *out, *pred;
 };
 
-template <int NH, bool VEC>
-__global__ __launch_bounds__(256) void dpm_sde_step_kernel(const DpmSdeStepDev a) {
+template <int NH, bool NOISE, bool VEC>
+__global__ __launch_bounds__(256) void dpm_step_kernel(const DpmStepDev a) {
     const long grp = (long)blockIdx.x * 256 + threadIdx.x;
-    if (grp >= a.groups) return;
-    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
+    if (grp >= a.s.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.s.per_sample);
     const long e0 = g.e0;
     const int nval = g.nval;
-    const long idx = a.t ? a.t[g.b] : a.step_index;
-    const float* c = a.coef + idx * 8;
+    const float* c = a.s.coef + coef_row(a.s, g.b) * 8;
     const float* w = c + 1 + NH * (NH + 1) / 2;
 
-    const f32x4 x = load4<VEC>(a.x, e0, nval);
-    const f32x4 m0 = pred_xstart4<VEC>(a.x0c, a.x0u, a.scale, g.b, a.mask, a.motion, a.clip, e0, nval);
-    f32x4 m1 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 x = load4<VEC>(a.s.x, e0, nval);
+    const f32x4 m0 = pred_xstart4<VEC>(a.s, g);
+    f32x4 m1 = {0.f, 0.f, 0.f, 0.f}, m2 = m1, z = m1;
     if (NH >= 1) m1 = load4<VEC>(a.m1, e0, nval);
-    const f32x4 z = a.noise ? load4<VEC>(a.noise, e0, nval) : philox_normal4(a.seed, a.sample_offset + (uint64_t)g.b, a.rng_step, g.grp);
+    if (NH >= 2) m2 = load4<VEC>(a.m2, e0, nval);
+    if (NOISE) z = a.noise ? load4<VEC>(a.noise, e0, nval) : philox_normal4(a.seed, a.sample_offset + (uint64_t)g.b, a.rng_step, g.grp);
     f32x4 r;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = dpm_sde_multistep<NH>(c[0], w, c[7], x[i], m0[i], m1[i], z[i]);
-    if (a.pred) store4<VEC>(a.pred, e0, nval, m0);
-    store4<VEC>(a.out, e0, nval, r);
+    for (int i = 0; i < 4; ++i) {
+        if (NOISE) r[i] = dpm_sde_multistep<NH>(c[0], w, c[7], x[i], m0[i], m1[i], z[i]);
+        else r[i] = dpm_multistep<NH>(c[0], w, x[i], m0[i], m1[i], m2[i]);
+    }
+    if (a.s.pred) store4<VEC>(a.s.pred, e0, nval, m0);
+    store4<VEC>(a.s.out, e0, nval, r);
 }
 
 // De-normalisation + position / rotation split of a generated chunk (reference sample/generate.py:132-146 with
@@ -606,17 +567,12 @@ __global__ __launch_bounds__(256) void bpd_xt_kernel(const float* __restrict__ x
 }
 
 struct BpdDev {
-    long per_sample, groups;
+    StepSrc s;              // x = x_t; out unused
     int chunks;
-    const float* coef;
-    const int64_t* t;
-    int step_index;
-    const float *x0, *xt, *z, *oc, *ou, *scale;
-    const uint8_t* mask;
-    const float *motion, *mean;
-    int clip, prior;
+    const float *x0, *z, *mean;
+    int prior;
     float prior_lv;
-    float *pred, *part;
+    float* part;
 };
 
 // approx_standard_normal_cdf (losses.py:42-47); th.pow(x, 3) is x*x*x
@@ -636,8 +592,8 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
     __shared__ float red[4][3];
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const long idx = a.t ? a.t[b] : a.step_index;
-    const float* c = a.coef + idx * 8;
+    const long idx = coef_row(a.s, b);
+    const float* c = a.s.coef + idx * 8;
     const float pm1 = c[0], pm2 = c[1], lv1 = c[2], lv2 = c[3], sra = c[4], sa = c[5], srm1 = c[7];
     // the per-step scalars of normal_kl / the decoder term, in torch's op order on the expanded fp32 tables
     const float klc = a.prior ? __fadd_rn(__fsub_rn(-1.0f, a.prior_lv), expf(a.prior_lv))
@@ -646,14 +602,13 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
     const float inv_std = expf(-__fmul_rn(0.5f, lv2));
     const float bin = (float)(1.0 / 255.0);
     const bool first = idx == 0;
-    const float sc = a.ou ? a.scale[b] : 0.0f;
-    const long base = (long)b * a.per_sample;
     float s_vb = 0.0f, s_x = 0.0f, s_e = 0.0f;
     for (int it = 0; it < BPD_GROUPS / 256; ++it) {
         const long grp = (long)chunk * BPD_GROUPS + it * 256 + tid;
-        if (grp >= a.groups) break;
-        const long e0 = base + 4L * grp;
-        const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
+        if (grp >= a.s.groups) break;
+        const Group g = group_at<VEC>(b, grp, a.s.per_sample);
+        const long e0 = g.e0;
+        const int nval = g.nval;
         const f32x4 x0 = load4<VEC>(a.x0, e0, nval);
         if (a.prior) {
 #pragma unroll
@@ -663,22 +618,8 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
             }
             continue;
         }
-        const f32x4 xt = load4<VEC>(a.xt, e0, nval);
-        f32x4 p = load4<VEC>(a.oc, e0, nval);
-        if (a.ou) {
-            const f32x4 u = load4<VEC>(a.ou, e0, nval);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) p[i] = cfg_blend(p[i], u[i], sc);
-        }
-        if (a.mask) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nval && a.mask[e0 + i]) p[i] = a.motion[e0 + i];
-        }
-        if (a.clip) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) p[i] = clamp1(p[i]);
-        }
+        const f32x4 xt = load4<VEC>(a.s.x, e0, nval);
+        const f32x4 p = pred_xstart4<VEC>(a.s, g);
         const f32x4 z = a.z ? load4<VEC>(a.z, e0, nval) : f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 mm;
         if (a.mean) {
@@ -712,7 +653,7 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdDev a) {
                 s_e = __fadd_rn(s_e, __fmul_rn(de, de));
             }
         }
-        if (a.pred) store4<VEC>(a.pred, e0, nval, p);
+        if (a.s.pred) store4<VEC>(a.s.pred, e0, nval, p);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -874,6 +815,43 @@ static inline bool group_aligned(const float* p) { return !((uintptr_t)p & 15); 
 static inline bool group_aligned(const uint8_t* p) { return !((uintptr_t)p & 3); }
 template <typename... P>
 static bool vec_ok(long per_sample, const P*... p) { return per_sample % 4 == 0 && (group_aligned(p) && ...); }
+// ... of a kernel over a StepSrc: its operands and whatever else (`more`) the kernel reads or writes by group
+template <typename... P>
+static bool vec_ok(const gdx::StepSrc& s, const P*... more) {
+    return vec_ok(s.per_sample, s.x, s.x0c, s.x0u, s.mask, s.motion, s.out, s.pred, more...);
+}
+
+static int refuse(const char* who, const char* what) { return gdx_set_error_((std::string(who) + ": " + what).c_str()); }
+
+// The kernels' StepSrc from an entry's argument struct (every step struct names these fields alike); pred: where x0 goes
+template <typename A>
+static gdx::StepSrc step_src(const A* a, float* pred) {
+    gdx::StepSrc s;
+    s.per_sample = (long)a->njoints * a->frames;
+    s.groups = (s.per_sample + 3) / 4;
+    s.coef = a->coef; s.t = a->t; s.step_index = a->step_index;
+    s.x = a->x; s.x0c = a->x0_cond; s.x0u = a->x0_uncond; s.scale = a->scale;
+    s.mask = a->inpaint_mask; s.motion = a->inpaint_motion; s.clip = a->clip_denoised;
+    s.out = a->out; s.pred = pred;
+    return s;
+}
+
+// What gdx_plms_step, gdx_dpm_step and gdx_dpm_sde_step (`who`) share in front of their launch: the refusals in their order
+// -- null argument, the entry's own kind / order check, shape, CFG, mask, the entry's history check (both return the
+// refusal's text or nullptr) --, then the StepSrc and the (ceil(groups / 256), B) grid.  -1: refused, 1: nothing to do, 0: launch.
+template <typename A, typename Entry, typename Hist>
+static int step_begin(const char* who, const A* a, float* A::*pred, Entry entry_check, Hist hist_check, gdx::StepSrc& s, dim3& grid) {
+    if (!a || !a->coef || !a->x || !a->x0_cond || !a->out) return refuse(who, "null argument");
+    if (const char* m = entry_check()) return refuse(who, m);
+    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return refuse(who, "bad shape");
+    if (a->x0_uncond && !a->scale) return refuse(who, "CFG needs scale");
+    if (a->inpaint_mask && !a->inpaint_motion) return refuse(who, "mask without motion");
+    if (const char* m = hist_check()) return refuse(who, m);
+    s = step_src(a, a->*pred);
+    if (a->batch == 0 || s.per_sample == 0) return 1;
+    grid = dim3((unsigned)((s.groups + 255) / 256), (unsigned)a->batch);
+    return 0;
+}
 
 static int sampler_update_impl(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
 
@@ -905,23 +883,17 @@ static int sampler_update_impl(const gdx_update_args_t* a, const int* state, lon
     if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_sampler_update: CFG needs scale");
     if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_sampler_update: mask without motion");
     UpdateDev d;
-    d.kind = a->kind;
-    d.per_sample = (long)a->njoints * a->frames;
-    d.groups = (d.per_sample + 3) / 4;
-    d.batch = a->batch;
-    d.coef = a->coef; d.t = a->t; d.step_index = a->step_index;
-    d.x = a->x; d.x0c = a->x0_cond; d.x0u = a->x0_uncond; d.scale = a->scale;
-    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion; d.noise = a->noise;
-    d.const_noise = a->const_noise; d.seed = a->philox_seed; d.sample_offset = a->sample_offset;
-    d.rng_step = a->rng_step; d.out = a->out; d.pred = a->pred_xstart;
+    d.s = step_src(a, a->pred_xstart);
+    d.kind = a->kind; d.batch = a->batch;
+    d.noise = a->noise; d.const_noise = a->const_noise;
+    d.seed = a->philox_seed; d.sample_offset = a->sample_offset; d.rng_step = a->rng_step;
     d.state = state; d.noise_stride = noise_stride;
     d.grad = a->cond_grad; d.gcoef = a->cond_coef;
-    d.clip = a->clip_denoised;
     if (d.grad && a->kind != GDX_SAMPLER_P && !d.gcoef) return gdx_set_error_("gdx_sampler_update: cond_grad needs cond_coef for DDIM");
-    const long total = d.groups * d.batch;
+    const long total = d.s.groups * d.batch;
     if (total == 0) return 0;
     const dim3 grid((total + 255) / 256), block(256);
-    if (vec_ok(d.per_sample, d.x, d.x0c, d.x0u, d.mask, d.motion, d.noise, d.grad, d.out, d.pred))
+    if (vec_ok(d.s, d.noise, d.grad))
         hipLaunchKernelGGL(update_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
     else
         hipLaunchKernelGGL(update_kernel<false>, grid, block, 0, (hipStream_t)stream, d);
@@ -989,107 +961,73 @@ static void launch_plms_step(int kind, dim3 grid, hipStream_t s, const gdx::Plms
 
 extern "C" int gdx_plms_step(const gdx_plms_step_args_t* a, void* stream) {
     using namespace gdx;
-    if (!a || !a->coef || !a->x || !a->x0_cond || !a->out) return gdx_set_error_("gdx_plms_step: null argument");
-    if (a->kind < 1 || a->kind > 6) return gdx_set_error_("gdx_plms_step: bad kind");
-    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return gdx_set_error_("gdx_plms_step: bad shape");
-    if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_plms_step: CFG needs scale");
-    if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_plms_step: mask without motion");
-    const int k = a->kind;
-    const int older = k <= 4 ? k - 1 : (k == 5 ? 1 : 0);            // history slots this kind reads
-    for (int i = 0; i < older; ++i)
-        if (!a->eps_hist[i]) return gdx_set_error_("gdx_plms_step: missing history for this kind");
-    if (k != 5 && !a->eps_out) return gdx_set_error_("gdx_plms_step: missing history for this kind");
-    if (k == 5 && (!a->x_eps || !a->pred_prev)) return gdx_set_error_("gdx_plms_step: kind 5 needs x_eps and pred_prev");
     PlmsStepDev d;
-    d.per_sample = (long)a->njoints * a->frames;
-    d.groups = (d.per_sample + 3) / 4;
-    if (a->batch == 0 || d.per_sample == 0) return 0;
-    d.coef = a->coef; d.t = a->t; d.t_eps = a->t_eps; d.step_index = a->step_index; d.step_index_eps = a->step_index_eps;
-    d.x = a->x; d.x_eps = k == 5 ? a->x_eps : nullptr; d.x0c = a->x0_cond; d.x0u = a->x0_uncond; d.scale = a->scale;
-    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion;
+    dim3 grid;
+    int older = 0;                                                  // history slots this kind reads
+    const int rc = step_begin(
+        "gdx_plms_step", a, &gdx_plms_step_args_t::pred_xstart, [&] { return a->kind < 1 || a->kind > 6 ? "bad kind" : nullptr; },
+        [&]() -> const char* {
+            const int k = a->kind;
+            older = k <= 4 ? k - 1 : (k == 5 ? 1 : 0);
+            for (int i = 0; i < older; ++i)
+                if (!a->eps_hist[i]) return "missing history for this kind";
+            if (k != 5 && !a->eps_out) return "missing history for this kind";
+            if (k == 5 && (!a->x_eps || !a->pred_prev)) return "kind 5 needs x_eps and pred_prev";
+            return nullptr;
+        },
+        d.s, grid);
+    if (rc) return rc < 0 ? -1 : 0;
+    const int k = a->kind;
+    d.t_eps = a->t_eps; d.step_index_eps = a->step_index_eps;
+    d.x_eps = k == 5 ? a->x_eps : nullptr; d.pred_prev = k == 5 ? a->pred_prev : nullptr;
     d.e1 = older > 0 ? a->eps_hist[0] : nullptr; d.e2 = older > 1 ? a->eps_hist[1] : nullptr;
-    d.e3 = older > 2 ? a->eps_hist[2] : nullptr; d.pred_prev = k == 5 ? a->pred_prev : nullptr;
-    d.clip = a->clip_denoised; d.eps_out = a->eps_out; d.out = a->out; d.pred = a->pred_xstart;
-    const bool vec = vec_ok(d.per_sample, d.x, d.x_eps, d.x0c, d.x0u, d.mask, d.motion, d.e1, d.e2, d.e3, d.pred_prev, d.eps_out, d.out,
-                            d.pred);
-    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
-    if (vec) launch_plms_step<true>(k, grid, (hipStream_t)stream, d);
+    d.e3 = older > 2 ? a->eps_hist[2] : nullptr; d.eps_out = a->eps_out;
+    if (vec_ok(d.s, d.x_eps, d.e1, d.e2, d.e3, d.pred_prev, d.eps_out)) launch_plms_step<true>(k, grid, (hipStream_t)stream, d);
     else launch_plms_step<false>(k, grid, (hipStream_t)stream, d);
     return launch_status("gdx_plms_step: launch failed");
 }
 
-template <bool VEC>
+template <bool NOISE, bool VEC>
 static void launch_dpm_step(int nh, dim3 grid, hipStream_t s, const gdx::DpmStepDev& d) {
     using namespace gdx;
     const dim3 block(256);
-    switch (nh) {
-        case 0: hipLaunchKernelGGL((dpm_step_kernel<0, VEC>), grid, block, 0, s, d); break;
-        case 1: hipLaunchKernelGGL((dpm_step_kernel<1, VEC>), grid, block, 0, s, d); break;
-        default: hipLaunchKernelGGL((dpm_step_kernel<2, VEC>), grid, block, 0, s, d); break;
-    }
+    if (nh == 0) hipLaunchKernelGGL((dpm_step_kernel<0, NOISE, VEC>), grid, block, 0, s, d);
+    else if (NOISE || nh == 1) hipLaunchKernelGGL((dpm_step_kernel<1, NOISE, VEC>), grid, block, 0, s, d);
+    else hipLaunchKernelGGL((dpm_step_kernel<2, false, VEC>), grid, block, 0, s, d);
 }
 
-extern "C" int gdx_dpm_step(const gdx_dpm_step_args_t* a, void* stream) {
+// gdx_dpm_step (NOISE = false: orders 1..3) and gdx_dpm_sde_step (NOISE = true: orders 1..2, the noise fields)
+template <bool NOISE, typename A>
+static int dpm_step_impl(const char* who, const A* a, void* stream) {
     using namespace gdx;
-    if (!a || !a->coef || !a->x || !a->x0_cond || !a->out) return gdx_set_error_("gdx_dpm_step: null argument");
-    if (a->order < 1 || a->order > 3) return gdx_set_error_("gdx_dpm_step: order must be 1, 2 or 3");
-    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return gdx_set_error_("gdx_dpm_step: bad shape");
-    if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_dpm_step: CFG needs scale");
-    if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_dpm_step: mask without motion");
-    const int nh = a->order - 1;                                     // history slots this order reads
-    for (int i = 0; i < nh; ++i) {
-        if (!a->hist[i]) return gdx_set_error_("gdx_dpm_step: missing history for this order");
-        if (a->pred_out && a->pred_out == a->hist[i]) return gdx_set_error_("gdx_dpm_step: pred_out aliases a history slot it reads");
+    DpmStepDev d = {};
+    dim3 grid;
+    const int rc = step_begin(
+        who, a, &A::pred_out,
+        [&] { return a->order >= 1 && a->order <= (NOISE ? 2 : 3) ? nullptr : (NOISE ? "order must be 1 or 2" : "order must be 1, 2 or 3"); },
+        [&]() -> const char* {
+            for (int i = 0; i < a->order - 1; ++i) {                // history slots this order reads
+                if (!a->hist[i]) return "missing history for this order";
+                if (a->pred_out && a->pred_out == a->hist[i]) return "pred_out aliases a history slot it reads";
+            }
+            return nullptr;
+        },
+        d.s, grid);
+    if (rc) return rc < 0 ? -1 : 0;
+    const int nh = a->order - 1;
+    d.m1 = nh > 0 ? a->hist[0] : nullptr;
+    if constexpr (NOISE) {
+        d.noise = a->noise; d.seed = a->philox_seed; d.sample_offset = a->sample_offset; d.rng_step = a->rng_step;
+    } else {
+        d.m2 = nh > 1 ? a->hist[1] : nullptr;
     }
-    DpmStepDev d;
-    d.per_sample = (long)a->njoints * a->frames;
-    d.groups = (d.per_sample + 3) / 4;
-    if (a->batch == 0 || d.per_sample == 0) return 0;
-    d.coef = a->coef; d.t = a->t; d.step_index = a->step_index;
-    d.x = a->x; d.x0c = a->x0_cond; d.x0u = a->x0_uncond; d.scale = a->scale;
-    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion;
-    d.m1 = nh > 0 ? a->hist[0] : nullptr; d.m2 = nh > 1 ? a->hist[1] : nullptr;
-    d.clip = a->clip_denoised; d.out = a->out; d.pred = a->pred_out;
-    const bool vec = vec_ok(d.per_sample, d.x, d.x0c, d.x0u, d.mask, d.motion, d.m1, d.m2, d.out, d.pred);
-    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
-    if (vec) launch_dpm_step<true>(nh, grid, (hipStream_t)stream, d);
-    else launch_dpm_step<false>(nh, grid, (hipStream_t)stream, d);
-    return launch_status("gdx_dpm_step: launch failed");
+    if (vec_ok(d.s, d.m1, d.m2, d.noise)) launch_dpm_step<NOISE, true>(nh, grid, (hipStream_t)stream, d);
+    else launch_dpm_step<NOISE, false>(nh, grid, (hipStream_t)stream, d);
+    return hipGetLastError() == hipSuccess ? 0 : refuse(who, "launch failed");
 }
-
-template <bool VEC>
-static void launch_dpm_sde_step(int nh, dim3 grid, hipStream_t s, const gdx::DpmSdeStepDev& d) {
-    using namespace gdx;
-    const dim3 block(256);
-    if (nh == 0) hipLaunchKernelGGL((dpm_sde_step_kernel<0, VEC>), grid, block, 0, s, d);
-    else hipLaunchKernelGGL((dpm_sde_step_kernel<1, VEC>), grid, block, 0, s, d);
-}
-
+extern "C" int gdx_dpm_step(const gdx_dpm_step_args_t* a, void* stream) { return dpm_step_impl<false>("gdx_dpm_step", a, stream); }
 extern "C" int gdx_dpm_sde_step(const gdx_dpm_sde_step_args_t* a, void* stream) {
-    using namespace gdx;
-    if (!a || !a->coef || !a->x || !a->x0_cond || !a->out) return gdx_set_error_("gdx_dpm_sde_step: null argument");
-    if (a->order < 1 || a->order > 2) return gdx_set_error_("gdx_dpm_sde_step: order must be 1 or 2");
-    if (a->batch < 0 || a->njoints < 0 || a->frames < 0 || a->batch > 65535) return gdx_set_error_("gdx_dpm_sde_step: bad shape");
-    if (a->x0_uncond && !a->scale) return gdx_set_error_("gdx_dpm_sde_step: CFG needs scale");
-    if (a->inpaint_mask && !a->inpaint_motion) return gdx_set_error_("gdx_dpm_sde_step: mask without motion");
-    const int nh = a->order - 1;                                     // history slots this order reads
-    if (nh && !a->hist[0]) return gdx_set_error_("gdx_dpm_sde_step: missing history for this order");
-    if (nh && a->pred_out && a->pred_out == a->hist[0]) return gdx_set_error_("gdx_dpm_sde_step: pred_out aliases a history slot it reads");
-    DpmSdeStepDev d;
-    d.per_sample = (long)a->njoints * a->frames;
-    d.groups = (d.per_sample + 3) / 4;
-    if (a->batch == 0 || d.per_sample == 0) return 0;
-    d.coef = a->coef; d.t = a->t; d.step_index = a->step_index;
-    d.x = a->x; d.x0c = a->x0_cond; d.x0u = a->x0_uncond; d.scale = a->scale;
-    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion;
-    d.m1 = nh ? a->hist[0] : nullptr; d.noise = a->noise;
-    d.seed = a->philox_seed; d.sample_offset = a->sample_offset; d.rng_step = a->rng_step;
-    d.clip = a->clip_denoised; d.out = a->out; d.pred = a->pred_out;
-    const bool vec = vec_ok(d.per_sample, d.x, d.x0c, d.x0u, d.mask, d.motion, d.m1, d.noise, d.out, d.pred);
-    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
-    if (vec) launch_dpm_sde_step<true>(nh, grid, (hipStream_t)stream, d);
-    else launch_dpm_sde_step<false>(nh, grid, (hipStream_t)stream, d);
-    return launch_status("gdx_dpm_sde_step: launch failed");
+    return dpm_step_impl<true>("gdx_dpm_sde_step", a, stream);
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,
@@ -1128,22 +1066,25 @@ extern "C" int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream) {
     }
     if (a->ld <= 0 || a->col < 0 || a->col >= a->ld) return gdx_set_error_("gdx_bpd_terms: bad output column");
     BpdDev d;
-    d.per_sample = (long)a->njoints * a->frames;
-    d.groups = (d.per_sample + 3) / 4;
-    d.chunks = (int)((d.per_sample + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK);
-    if (a->batch == 0 || d.per_sample == 0) return 0;
-    d.coef = a->coef; d.t = a->t; d.step_index = a->step_index;
-    d.x0 = a->x_start; d.xt = a->x_t; d.z = a->noise; d.oc = a->x0_cond; d.ou = a->x0_uncond; d.scale = a->scale;
-    d.mask = a->inpaint_mask; d.motion = a->inpaint_motion; d.mean = a->model_mean;
-    d.clip = a->clip_denoised; d.prior = a->prior; d.prior_lv = a->prior_log_variance;
-    d.pred = a->prior ? nullptr : a->pred_xstart; d.part = a->workspace;
-    const bool vec = vec_ok(d.per_sample, d.x0, d.xt, d.z, d.oc, d.ou, d.mean, d.pred);   // mask / motion: read per element
+    StepSrc& s = d.s;
+    s.per_sample = (long)a->njoints * a->frames;
+    s.groups = (s.per_sample + 3) / 4;
+    d.chunks = (int)((s.per_sample + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK);
+    if (a->batch == 0 || s.per_sample == 0) return 0;
+    s.coef = a->coef; s.t = a->t; s.step_index = a->step_index;
+    s.x = a->x_t; s.x0c = a->x0_cond; s.x0u = a->x0_uncond; s.scale = a->scale;
+    s.mask = a->inpaint_mask; s.motion = a->inpaint_motion; s.clip = a->clip_denoised;
+    s.out = nullptr; s.pred = a->prior ? nullptr : a->pred_xstart;
+    d.x0 = a->x_start; d.z = a->noise; d.mean = a->model_mean;
+    d.prior = a->prior; d.prior_lv = a->prior_log_variance; d.part = a->workspace;
+    // mask / motion are read by group through pred_xstart4 like everywhere else: a mask not 4-byte aligned or a motion tensor
+    // not 16-byte aligned selects the scalar instantiation, which gives the same bits
     const dim3 grid(d.chunks, a->batch), block(256);
-    if (vec) hipLaunchKernelGGL(bpd_terms_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
+    if (vec_ok(s, d.x0, d.z, d.mean)) hipLaunchKernelGGL(bpd_terms_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
     else hipLaunchKernelGGL(bpd_terms_kernel<false>, grid, block, 0, (hipStream_t)stream, d);
     if (launch_status("gdx_bpd_terms: launch failed")) return -1;
     hipLaunchKernelGGL(bpd_finish_kernel, dim3((a->batch * 3 + 63) / 64), dim3(64), 0, (hipStream_t)stream, d.part, d.chunks,
-                       d.per_sample, a->batch, a->vb, a->prior ? nullptr : a->xstart_mse, a->prior ? nullptr : a->mse, a->ld,
+                       s.per_sample, a->batch, a->vb, a->prior ? nullptr : a->xstart_mse, a->prior ? nullptr : a->mse, a->ld,
                        a->col);
     return launch_status("gdx_bpd_terms: launch failed");
 }

@@ -441,8 +441,7 @@ class GaussianDiffusion:
             raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
         device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
                                                   philox_seed, sample_offset, noise_tape)
-        fused = (not every_step and _is_native(model) and denoised_fn is None and cond_fn is None
-                 and self.model_mean_type == ModelMeanType.START_X)
+        fused = self._runs_fused(not every_step, model, denoised_fn, cond_fn)
         if fused:
             yield from self._fused_loop(kind, model, img, indices, model_kwargs, eta, const_noise, rng, philox_seed,
                                         sample_offset, noise_tape, dump_steps, progress, clip_denoised)
@@ -493,15 +492,63 @@ class GaussianDiffusion:
             assert mask.shape == motion.shape == x.shape
         return eng, mode, scale, mask, motion
 
+    def _runs_fused(self, fused, model, denoised_fn, cond_fn):
+        """The route of every sampling loop: inside libgdx for a native START_X denoiser (or its ClassifierFreeSampleModel)
+        without cond_fn / denoised_fn when the caller allows it (`fused`), else step by step."""
+        return (fused and _is_native(model) and denoised_fn is None and cond_fn is None
+                and self.model_mean_type == ModelMeanType.START_X)
+
+    @staticmethod
+    def _issue_blocks(n, device, progress, issue, block=None):
+        """A fused loop of n steps as calls issue(k, nb) -- nb steps from executed step k --, back to back with no host
+        synchronisation in between; with `progress` one per block, to report it.  block: most steps per call (_step_noise's);
+        None: the whole loop at once, or NOISE_BLOCK steps under `progress`."""
+        if block is None:
+            block = min(n, NOISE_BLOCK) if progress else n
+        bar = None
+        if progress:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=n)
+        k = 0
+        while k < n:
+            nb = min(block, n - k)
+            issue(k, nb)
+            k += nb
+            if bar is not None:
+                th.cuda.current_stream(device).synchronize()
+                bar.update(nb)
+        if bar is not None:
+            bar.close()
+
+    @staticmethod
+    def _step_noise(tape, rng, n, x, const_noise=False):
+        """The step noise of a fused loop of n steps on the state x -> (block, tape_of): tape_of(k, nb) is the noise tape
+        of the block of nb steps from executed step k, slice 0 = step k (None: in-kernel Philox).  A recorded `tape` is sliced
+        (block None: _issue_blocks chooses).  rng == "torch" without one: one `normal_()` per step in the reference's order
+        (:532: randn_like(x) is empty_like(x).normal_()), drawn `block` = noise_block_steps ahead into a buffer the kernels
+        read; under const_noise the full draw, sample 0 kept (:534-535)."""
+        if tape is not None or rng != "torch":
+            return None, lambda k, nb: tape[k:] if tape is not None else None
+        rows = 1 if const_noise else x.shape[0]
+        block = noise_block_steps(n, rows * math.prod(x.shape[1:]))
+        buf = th.empty((block, rows, *x.shape[1:]), device=x.device, dtype=th.float32)
+        full = th.empty_like(x) if const_noise else None
+
+        def draw(k, nb):
+            for j in range(nb):
+                if const_noise:
+                    buf[j].copy_(full.normal_()[:1])
+                else:
+                    buf[j].normal_()
+            return buf
+        return block, draw
+
     def _fused_loop(self, kind, model, img, indices, model_kwargs, eta, const_noise, rng, philox_seed, sample_offset,
                     noise_tape, dump_steps, progress, clip_denoised=False):
         """Whole loop inside libgdx (gdx_sample_loop); yields only the final state.  Noise: a recorded tape, in-kernel
-        Philox, or torch's generator -- then one `normal_()` per step in the reference's order (:532: randn_like(x) is
-        empty_like(x).normal_()), drawn NOISE_BLOCK steps ahead into a tape the update kernel reads; the loop is issued
-        block by block with no host synchronisation in between (with `progress` one per block, to report it)."""
+        Philox, or torch's generator (_step_noise); issued block by block (_issue_blocks)."""
         self._check_supported()
         x = E.f32c(img, "x_T").clone()
-        B, J, F, T = x.shape
         eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
         n = len(indices)
         tape = None
@@ -516,37 +563,12 @@ class GaussianDiffusion:
             dump = th.empty(len(dump_steps), *x.shape, device=x.device, dtype=th.float32)
         if self.rescale_timesteps:
             raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
-        draw = tape is None and rng == "torch"
-        block = noise_block_steps(n, (1 if const_noise else B) * J * F * T) if draw else (min(n, NOISE_BLOCK) if progress else n)
-        bar = None
-        if progress:
-            from tqdm.auto import tqdm
-            bar = tqdm(total=n)
+        block, tape_of = self._step_noise(tape, rng, n, x, const_noise)
         coef = self.coef_table(kind, x.device, eta)
-        buf = th.empty((block, 1 if const_noise else B, J, F, T), device=x.device, dtype=th.float32) if draw else None
-        full = th.empty_like(x) if draw and const_noise else None
-        k = 0
-        while k < n:
-            nb = min(block, n - k)
-            if draw:
-                for j in range(nb):
-                    if const_noise:
-                        buf[j].copy_(full.normal_()[:1])      # reference :534-535: the full draw, sample 0 kept
-                    else:
-                        buf[j].normal_()
-                blk = buf
-            else:
-                blk = tape[k:] if tape is not None else None
-            eng.sample_loop(x, kind, mode, coef, tmap, indices[k], scale=scale, inpaint_mask=mask,
-                            inpaint_motion=motion, noise_tape=blk, const_noise=const_noise, philox_seed=philox_seed,
-                            sample_offset=sample_offset, dump=dump, dump_steps=dump_steps, run_steps=nb, k_base=k,
-                            clip_denoised=clip_denoised)
-            k += nb
-            if bar is not None:
-                th.cuda.current_stream(x.device).synchronize()
-                bar.update(nb)
-        if bar is not None:
-            bar.close()
+        self._issue_blocks(n, x.device, progress, lambda k, nb: eng.sample_loop(
+            x, kind, mode, coef, tmap, indices[k], scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+            noise_tape=tape_of(k, nb), const_noise=const_noise, philox_seed=philox_seed, sample_offset=sample_offset, dump=dump,
+            dump_steps=dump_steps, run_steps=nb, k_base=k, clip_denoised=clip_denoised), block)
         yield {"sample": x, "pred_xstart": None, "dump": dump, "fused": True}
 
     def _timestep_map(self):
@@ -734,7 +756,7 @@ class GaussianDiffusion:
         tape = E.f32c(noise_tape, "noise_tape") if noise_tape is not None else None
         if tape is not None:
             assert tuple(tape.shape) == (n, *xs.shape), "noise_tape must be [num_timesteps, B, J, 1, T]"
-        if fused and _is_native(model) and self.model_mean_type == ModelMeanType.START_X:
+        if self._runs_fused(fused, model, None, None):
             vb, xm, em, prior = self._fused_bpd_loop(model, xs, clip_denoised, model_kwargs, rng, philox_seed, sample_offset,
                                                      tape, progress)
         else:
@@ -758,40 +780,18 @@ class GaussianDiffusion:
 
     def _fused_bpd_loop(self, model, xs, clip_denoised, model_kwargs, rng, philox_seed, sample_offset, tape, progress):
         """gdx_bpd_loop, issued block by block like _fused_loop (torch-generator noise is drawn NOISE_BLOCK steps ahead)."""
-        B, J, F, T = xs.shape
         if self.rescale_timesteps:
             raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
         eng, mode, scale, mask, motion = self._native_loop_setup(model, xs, model_kwargs)
-        n = self.num_timesteps
+        B, n = xs.shape[0], self.num_timesteps
         vb, xm, em = (th.empty(B, n, device=xs.device, dtype=th.float32) for _ in range(3))
         prior = th.empty(B, device=xs.device, dtype=th.float32)
-        draw = tape is None and rng == "torch"
-        block = noise_block_steps(n, B * J * F * T) if draw else (min(n, NOISE_BLOCK) if progress else n)
-        buf = th.empty((block, B, J, F, T), device=xs.device, dtype=th.float32) if draw else None
-        bar = None
-        if progress:
-            from tqdm.auto import tqdm
-            bar = tqdm(total=n)
+        block, tape_of = self._step_noise(tape, rng, n, xs)
         coef, tmap = self.bpd_table(xs.device), self._timestep_map()
-        k = 0
-        while k < n:
-            nb = min(block, n - k)
-            if draw:
-                for j in range(nb):
-                    buf[j].normal_()
-                blk = buf
-            else:
-                blk = tape[k:] if tape is not None else None
-            eng.bpd_loop(xs, mode, coef, tmap, vb, xm, em, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
-                         noise_tape=blk, philox_seed=philox_seed, sample_offset=sample_offset, clip_denoised=clip_denoised,
-                         run_steps=nb, k_base=k, prior_bpd=prior if k + nb == n else None,
-                         prior_log_variance=self._prior_log_variance())
-            k += nb
-            if bar is not None:
-                th.cuda.current_stream(xs.device).synchronize()
-                bar.update(nb)
-        if bar is not None:
-            bar.close()
+        self._issue_blocks(n, xs.device, progress, lambda k, nb: eng.bpd_loop(
+            xs, mode, coef, tmap, vb, xm, em, scale=scale, inpaint_mask=mask, inpaint_motion=motion, noise_tape=tape_of(k, nb),
+            philox_seed=philox_seed, sample_offset=sample_offset, clip_denoised=clip_denoised, run_steps=nb, k_base=k,
+            prior_bpd=prior if k + nb == n else None, prior_log_variance=self._prior_log_variance()), block)
         return vb, xm, em, prior
 
     # ------------------------------------------------------------------ PLMS (reference :995-1190)
@@ -799,6 +799,36 @@ class GaussianDiffusion:
         """p_mean_variance's pred_xstart (model output after CFG / inpainting / clipping)."""
         return self._step(GDX_SAMPLER_P, model, x, t, clip_denoised, denoised_fn, None, model_kwargs,
                           noise=th.zeros_like(x))["pred_xstart"]
+
+    def _condition_score_xstart(self, cond_fn, x, t, pred, model_kwargs):
+        """pred_xstart under condition_score (reference :452-472), or `pred` itself without a cond_fn."""
+        if cond_fn is None:
+            return pred
+        grad = E.f32c(self._call_cond_fn(cond_fn, x, t, model_kwargs), "cond_fn gradient")
+        return E.plms_update(7, self.coef_table(GDX_SAMPLER_DDIM, x.device, 0.0), t, x, pred,
+                             eps=[grad, self._cond_coef(x.device)])
+
+    @staticmethod
+    def _uniform_t(who, x, t):
+        """The operands of a DPM-Solver++ step `who` -> (x, t, i): t must be the index i for the whole batch (the history
+        belongs to one index sequence)."""
+        xc = E.f32c(x, "x")
+        tt = E.require_device(t, "t").to(th.int64).contiguous()
+        rows = set(tt.tolist())
+        if len(rows) != 1:
+            raise ValueError(f"{who}: t must be the same for the whole batch")
+        return xc, tt, rows.pop()
+
+    @staticmethod
+    def _history_step(order, old_out, i, used, step):
+        """The history protocol of the DPM-Solver++ steps: sample = step(cur, hist) with cur = min(order, predictions kept
+        + 1, i + 1) and hist the cur - 1 newest of old_out["old_pred"], newest first -> (sample, the old_pred to hand on:
+        oldest first, at most order - 1 kept)."""
+        old_pred = list(old_out["old_pred"]) if old_out is not None else []
+        cur = min(order, len(old_pred) + 1, i + 1)
+        sample = step(cur, old_pred[::-1][:cur - 1])
+        old_pred.append(used)
+        return sample, old_pred[-(order - 1):] if order > 1 else []
 
     def plms_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                     cond_fn_with_grad=False, order=2, old_out=None):
@@ -816,10 +846,7 @@ class GaussianDiffusion:
         def get_model_output(xx, ts):
             """(eps, pred_xstart used downstream, original pred_xstart), reference get_model_output :1015-1041."""
             orig = self._pred_xstart(model, xx, ts, clip_denoised, denoised_fn, model_kwargs)
-            used = orig
-            if cond_fn is not None:                       # condition_score (:452-472)
-                grad = E.f32c(self._call_cond_fn(cond_fn, xx, ts, model_kwargs), "cond_fn gradient")
-                used = E.plms_update(7, coef, ts, xx, orig, eps=[grad, self._cond_coef(xx.device)])
+            used = self._condition_score_xstart(cond_fn, xx, ts, orig, model_kwargs)
             return E.plms_update(0, coef, ts, xx, used), used, orig
         eps, x0, x0_orig = get_model_output(xc, tt)
         if order > 1 and old_out is None:
@@ -847,8 +874,7 @@ class GaussianDiffusion:
         bits.  rng / philox_seed / sample_offset choose how x_T is drawn when `noise` is None (the sampler draws nothing else)."""
         if rng not in ("torch", "philox"):
             raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
-        if (fused and _is_native(model) and denoised_fn is None and cond_fn is None and not cond_fn_with_grad
-                and not randomize_class and self.model_mean_type == ModelMeanType.START_X):
+        if self._runs_fused(fused, model, denoised_fn, cond_fn) and not cond_fn_with_grad and not randomize_class:
             if not int(order) or not 1 <= order <= 4:
                 raise ValueError('order is invalid (should be int from 1-4).')
             if order == 1:          # the reference subscripts old_out = None on the first step (:1053)
@@ -858,45 +884,61 @@ class GaussianDiffusion:
             device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
                                                       philox_seed, sample_offset, None)
             return self._fused_plms_loop(model, img, indices, model_kwargs, int(order), progress, clip_denoised)
+        return self._final_sample(self.plms_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, skip_timesteps=skip_timesteps, init_image=init_image,
+            randomize_class=randomize_class, cond_fn_with_grad=cond_fn_with_grad, order=order, rng=rng, philox_seed=philox_seed,
+            sample_offset=sample_offset))
+
+    @staticmethod
+    def _final_sample(steps):
         final = None
-        for sample in self.plms_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                        denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                                        model_kwargs=model_kwargs, device=device, progress=progress,
-                                                        skip_timesteps=skip_timesteps, init_image=init_image,
-                                                        randomize_class=randomize_class,
-                                                        cond_fn_with_grad=cond_fn_with_grad, order=order, rng=rng,
-                                                        philox_seed=philox_seed, sample_offset=sample_offset):
+        for sample in steps:
             final = sample
         return final["sample"]
 
-    def _fused_plms_loop(self, model, img, indices, model_kwargs, order, progress, clip_denoised):
-        """Whole loop inside libgdx (gdx_plms_loop).  The eps history and the first step's predictor live in two tensors of
-        this call; with `progress` the loop is issued in blocks of NOISE_BLOCK steps, one synchronisation per block."""
+    def _fused_setup(self, model, img, model_kwargs):
+        """The front of a fused multistep loop -> (x, engine, mode, scale, mask, motion): x = a private copy of the start
+        state, updated in place by the loop; the rest from _native_loop_setup."""
         self._check_supported()
         if self.rescale_timesteps:
             raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
         x = E.f32c(img, "x_T").clone()
-        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
-        n = len(indices)
+        return (x, *self._native_loop_setup(model, x, model_kwargs))
+
+    def _stepwise(self, step, model, shape, noise, device, progress, skip_timesteps, init_image, rng, philox_seed,
+                  sample_offset, noise_tape=None, step_noise=False, **step_kw):
+        """The step-by-step form of a multistep sampling loop: yields step(model, x, t, old_out=previous, **step_kw) per
+        index.  step_noise: the steps take noise -- entry 1 + k of the tape, or the Philox draw k + 1 (rng == "philox"), or
+        the step's own draw from torch's generator."""
+        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                  philox_seed, sample_offset, noise_tape)
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        old_out = None
+        for k, i in enumerate(indices):
+            t = th.full((shape[0],), i, device=device, dtype=th.long)
+            if step_noise:
+                z = noise_tape[1 + k] if noise_tape is not None else None
+                step_kw.update(noise=z, philox_seed=philox_seed, sample_offset=sample_offset,
+                               rng_step=k + 1 if z is None and rng == "philox" else None)
+            with th.no_grad():
+                out = step(model, img, t, old_out=old_out, **step_kw)
+            yield out
+            old_out = out
+            img = out["sample"]
+
+    def _fused_plms_loop(self, model, img, indices, model_kwargs, order, progress, clip_denoised):
+        """Whole loop inside libgdx (gdx_plms_loop).  The eps history and the first step's predictor live in two tensors of
+        this call; with `progress` the loop is issued in blocks of NOISE_BLOCK steps, one synchronisation per block."""
+        x, eng, mode, scale, mask, motion = self._fused_setup(model, img, model_kwargs)
         coef, tmap = self.coef_table(GDX_SAMPLER_DDIM, x.device, 0.0), self._timestep_map()
         hist = th.empty((order, *x.shape), device=x.device, dtype=th.float32)
         scratch = th.empty_like(x)
-        block = min(n, NOISE_BLOCK) if progress else n
-        bar = None
-        if progress:
-            from tqdm.auto import tqdm
-            bar = tqdm(total=n)
-        k = 0
-        while k < n:
-            nb = min(block, n - k)
-            eng.plms_loop(x, mode, order, coef, tmap, indices[k], hist, scratch, scale=scale, inpaint_mask=mask,
-                          inpaint_motion=motion, clip_denoised=clip_denoised, run_steps=nb, k_base=k)
-            k += nb
-            if bar is not None:
-                th.cuda.current_stream(x.device).synchronize()
-                bar.update(nb)
-        if bar is not None:
-            bar.close()
+        self._issue_blocks(len(indices), x.device, progress, lambda k, nb: eng.plms_loop(
+            x, mode, order, coef, tmap, indices[k], hist, scratch, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+            clip_denoised=clip_denoised, run_steps=nb, k_base=k))
         return x
 
     def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
@@ -905,21 +947,9 @@ class GaussianDiffusion:
                                      rng="torch", philox_seed=0, sample_offset=0):
         if randomize_class:
             raise NotImplementedError("randomize_class is outside the sampling hot path")
-        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
-                                                  philox_seed, sample_offset, None)
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        old_out = None
-        for i in indices:
-            t = th.full((shape[0],), i, device=device, dtype=th.long)
-            with th.no_grad():
-                out = self.plms_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                       cond_fn=cond_fn, model_kwargs=model_kwargs,
-                                       cond_fn_with_grad=cond_fn_with_grad, order=order, old_out=old_out)
-            yield out
-            old_out = out
-            img = out["sample"]
+        yield from self._stepwise(self.plms_sample, model, shape, noise, device, progress, skip_timesteps, init_image, rng,
+                                  philox_seed, sample_offset, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                  cond_fn=cond_fn, model_kwargs=model_kwargs, cond_fn_with_grad=cond_fn_with_grad, order=order)
 
     # ------------------------------------------------------------------ DPM-Solver++ multistep (no counterpart in the reference)
     def dpm_coef_rows(self):
@@ -971,24 +1001,12 @@ class GaussianDiffusion:
         whole batch: the history belongs to one index sequence.  Returns {"sample", "pred_xstart", "old_pred"}."""
         if order not in (1, 2, 3):
             raise ValueError('order is invalid (should be int from 1-3).')
-        xc = E.f32c(x, "x")
-        tt = E.require_device(t, "t").to(th.int64).contiguous()
-        rows = set(tt.tolist())
-        if len(rows) != 1:
-            raise ValueError("dpm_solver_sample: t must be the same for the whole batch")
-        i = rows.pop()
+        xc, tt, i = self._uniform_t("dpm_solver_sample", x, t)
         pred = self._pred_xstart(model, xc, tt, clip_denoised, denoised_fn, model_kwargs)
-        used = pred
-        if cond_fn is not None:                           # condition_score (reference :452-472)
-            grad = E.f32c(self._call_cond_fn(cond_fn, xc, tt, model_kwargs or {}), "cond_fn gradient")
-            used = E.plms_update(7, self.coef_table(GDX_SAMPLER_DDIM, xc.device, 0.0), tt, xc, pred,
-                                 eps=[grad, self._cond_coef(xc.device)])
-        old_pred = list(old_out["old_pred"]) if old_out is not None else []
-        cur = min(order, len(old_pred) + 1, i + 1)
-        sample = E.dpm_step(cur, self.dpm_coef_table(xc.device), xc, used, th.empty_like(xc), hist=old_pred[::-1][:cur - 1],
-                            step_index=i)
-        old_pred.append(used)
-        return {"sample": sample, "pred_xstart": pred, "old_pred": old_pred[-(order - 1):] if order > 1 else []}
+        used = self._condition_score_xstart(cond_fn, xc, tt, pred, model_kwargs or {})
+        sample, old_pred = self._history_step(order, old_out, i, used, lambda cur, hist: E.dpm_step(
+            cur, self.dpm_coef_table(xc.device), xc, used, th.empty_like(xc), hist=hist, step_index=i))
+        return {"sample": sample, "pred_xstart": pred, "old_pred": old_pred}
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
@@ -1006,50 +1024,26 @@ class GaussianDiffusion:
             raise ValueError('order is invalid (should be int from 1-3).')
         if cond_fn_with_grad or randomize_class:
             raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
-        if (fused and _is_native(model) and denoised_fn is None and cond_fn is None
-                and self.model_mean_type == ModelMeanType.START_X):
+        if self._runs_fused(fused, model, denoised_fn, cond_fn):
             if model_kwargs is None:
                 model_kwargs = {}
             device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
                                                       philox_seed, sample_offset, None)
             return self._fused_dpm_loop(model, img, indices, model_kwargs, int(order), progress, clip_denoised)
-        final = None
-        for sample in self.dpm_solver_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                              denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                                              model_kwargs=model_kwargs, device=device, progress=progress,
-                                                              skip_timesteps=skip_timesteps, init_image=init_image,
-                                                              order=order, rng=rng, philox_seed=philox_seed,
-                                                              sample_offset=sample_offset):
-            final = sample
-        return final["sample"]
+        return self._final_sample(self.dpm_solver_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, skip_timesteps=skip_timesteps, init_image=init_image,
+            order=order, rng=rng, philox_seed=philox_seed, sample_offset=sample_offset))
 
     def _fused_dpm_loop(self, model, img, indices, model_kwargs, order, progress, clip_denoised):
         """Whole loop inside libgdx (gdx_dpm_loop).  The history of x0 predictions lives in a tensor of this call; with
         `progress` the loop is issued in blocks of NOISE_BLOCK steps, one synchronisation per block."""
-        self._check_supported()
-        if self.rescale_timesteps:
-            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
-        x = E.f32c(img, "x_T").clone()
-        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
-        n = len(indices)
+        x, eng, mode, scale, mask, motion = self._fused_setup(model, img, model_kwargs)
         coef, tmap = self.dpm_coef_table(x.device), self._timestep_map()
         hist = th.empty((order, *x.shape), device=x.device, dtype=th.float32) if order > 1 else None
-        block = min(n, NOISE_BLOCK) if progress else n
-        bar = None
-        if progress:
-            from tqdm.auto import tqdm
-            bar = tqdm(total=n)
-        k = 0
-        while k < n:
-            nb = min(block, n - k)
-            eng.dpm_loop(x, mode, order, coef, tmap, indices[k], hist, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
-                         clip_denoised=clip_denoised, run_steps=nb, k_base=k)
-            k += nb
-            if bar is not None:
-                th.cuda.current_stream(x.device).synchronize()
-                bar.update(nb)
-        if bar is not None:
-            bar.close()
+        self._issue_blocks(len(indices), x.device, progress, lambda k, nb: eng.dpm_loop(
+            x, mode, order, coef, tmap, indices[k], hist, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+            clip_denoised=clip_denoised, run_steps=nb, k_base=k))
         return x
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
@@ -1058,21 +1052,9 @@ class GaussianDiffusion:
                                            rng="torch", philox_seed=0, sample_offset=0):
         if cond_fn_with_grad or randomize_class:
             raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
-        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
-                                                  philox_seed, sample_offset, None)
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        old_out = None
-        for i in indices:
-            t = th.full((shape[0],), i, device=device, dtype=th.long)
-            with th.no_grad():
-                out = self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                             cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, old_out=old_out)
-            yield out
-            old_out = out
-            img = out["sample"]
-
+        yield from self._stepwise(self.dpm_solver_sample, model, shape, noise, device, progress, skip_timesteps, init_image, rng,
+                                  philox_seed, sample_offset, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                  cond_fn=cond_fn, model_kwargs=model_kwargs, order=order)
 
     # ------------------------------------------------------------------ SDE-DPM-Solver++ multistep (no counterpart in the reference)
     def dpm_sde_coef_rows(self, eta=1.0):
@@ -1119,31 +1101,19 @@ class GaussianDiffusion:
         be the same for the whole batch.  Returns {"sample", "pred_xstart", "old_pred"}."""
         if order not in (1, 2):
             raise ValueError('order is invalid (should be int from 1-2).')
-        xc = E.f32c(x, "x")
-        tt = E.require_device(t, "t").to(th.int64).contiguous()
-        rows = set(tt.tolist())
-        if len(rows) != 1:
-            raise ValueError("dpm_solver_sde_sample: t must be the same for the whole batch")
-        i = rows.pop()
+        xc, tt, i = self._uniform_t("dpm_solver_sde_sample", x, t)
         coef = self.dpm_sde_coef_table(xc.device, eta)
         pred = self._pred_xstart(model, xc, tt, clip_denoised, denoised_fn, model_kwargs)
-        used = pred
-        if cond_fn is not None:                           # condition_score (reference :452-472)
-            grad = E.f32c(self._call_cond_fn(cond_fn, xc, tt, model_kwargs or {}), "cond_fn gradient")
-            used = E.plms_update(7, self.coef_table(GDX_SAMPLER_DDIM, xc.device, 0.0), tt, xc, pred,
-                                 eps=[grad, self._cond_coef(xc.device)])
+        used = self._condition_score_xstart(cond_fn, xc, tt, pred, model_kwargs or {})
         if noise is not None:
             noise = E.f32c(noise, "noise")
             assert noise.shape == xc.shape
         elif rng_step is None:
             noise = th.empty_like(xc).normal_()
-        old_pred = list(old_out["old_pred"]) if old_out is not None else []
-        cur = min(order, len(old_pred) + 1, i + 1)
-        sample = E.dpm_sde_step(cur, coef, xc, used, th.empty_like(xc), hist=old_pred[::-1][:cur - 1], step_index=i,
-                                noise=noise, philox_seed=philox_seed, sample_offset=sample_offset,
-                                rng_step=0 if rng_step is None else int(rng_step))
-        old_pred.append(used)
-        return {"sample": sample, "pred_xstart": pred, "old_pred": old_pred[-(order - 1):] if order > 1 else []}
+        sample, old_pred = self._history_step(order, old_out, i, used, lambda cur, hist: E.dpm_sde_step(
+            cur, coef, xc, used, th.empty_like(xc), hist=hist, step_index=i, noise=noise, philox_seed=philox_seed,
+            sample_offset=sample_offset, rng_step=0 if rng_step is None else int(rng_step)))
+        return {"sample": sample, "pred_xstart": pred, "old_pred": old_pred}
 
     def dpm_solver_sde_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                    model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
@@ -1163,64 +1133,33 @@ class GaussianDiffusion:
             raise ValueError(f"eta must be >= 0, got {eta!r}")
         if cond_fn_with_grad or randomize_class:
             raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
-        if (fused and _is_native(model) and denoised_fn is None and cond_fn is None
-                and self.model_mean_type == ModelMeanType.START_X):
+        if self._runs_fused(fused, model, denoised_fn, cond_fn):
             if model_kwargs is None:
                 model_kwargs = {}
             device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
                                                       philox_seed, sample_offset, noise_tape)
             return self._fused_dpm_sde_loop(model, img, indices, model_kwargs, int(order), float(eta), progress, clip_denoised,
                                             rng, philox_seed, sample_offset, noise_tape)
-        final = None
-        for sample in self.dpm_solver_sde_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                                  denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                                                  model_kwargs=model_kwargs, device=device, progress=progress,
-                                                                  skip_timesteps=skip_timesteps, init_image=init_image,
-                                                                  order=order, eta=eta, rng=rng, philox_seed=philox_seed,
-                                                                  sample_offset=sample_offset, noise_tape=noise_tape):
-            final = sample
-        return final["sample"]
+        return self._final_sample(self.dpm_solver_sde_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, skip_timesteps=skip_timesteps, init_image=init_image,
+            order=order, eta=eta, rng=rng, philox_seed=philox_seed, sample_offset=sample_offset, noise_tape=noise_tape))
 
     def _fused_dpm_sde_loop(self, model, img, indices, model_kwargs, order, eta, progress, clip_denoised, rng, philox_seed,
                             sample_offset, noise_tape):
         """Whole loop inside libgdx (gdx_dpm_sde_loop).  The history of x0 predictions lives in a tensor of this call.  Noise: a
-        recorded tape, in-kernel Philox, or torch's generator -- then one normal_() per step in step order, drawn
-        noise_block_steps ahead into a tape the kernel reads, exactly as _fused_loop does; the loop is issued block by block
-        with no host synchronisation in between (with `progress` one per block, to report it)."""
-        self._check_supported()
-        if self.rescale_timesteps:
-            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
-        x = E.f32c(img, "x_T").clone()
-        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
+        recorded tape, in-kernel Philox, or torch's generator, exactly as in _fused_loop (_step_noise); issued block by block
+        (_issue_blocks)."""
+        x, eng, mode, scale, mask, motion = self._fused_setup(model, img, model_kwargs)
         n = len(indices)
         tape = E.f32c(noise_tape[1:1 + n], "noise_tape") if noise_tape is not None else None
         coef, tmap = self.dpm_sde_coef_table(x.device, eta), self._timestep_map()
         hist = th.empty((order, *x.shape), device=x.device, dtype=th.float32) if order > 1 else None
-        draw = tape is None and rng == "torch"
-        block = noise_block_steps(n, x.numel()) if draw else (min(n, NOISE_BLOCK) if progress else n)
-        buf = th.empty((block, *x.shape), device=x.device, dtype=th.float32) if draw else None
-        bar = None
-        if progress:
-            from tqdm.auto import tqdm
-            bar = tqdm(total=n)
-        k = 0
-        while k < n:
-            nb = min(block, n - k)
-            if draw:
-                for j in range(nb):
-                    buf[j].normal_()
-                blk = buf
-            else:
-                blk = tape[k:] if tape is not None else None
-            eng.dpm_sde_loop(x, mode, order, coef, tmap, indices[k], hist, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
-                             clip_denoised=clip_denoised, run_steps=nb, k_base=k, noise_tape=blk, philox_seed=philox_seed,
-                             sample_offset=sample_offset)
-            k += nb
-            if bar is not None:
-                th.cuda.current_stream(x.device).synchronize()
-                bar.update(nb)
-        if bar is not None:
-            bar.close()
+        block, tape_of = self._step_noise(tape, rng, n, x)
+        self._issue_blocks(n, x.device, progress, lambda k, nb: eng.dpm_sde_loop(
+            x, mode, order, coef, tmap, indices[k], hist, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+            clip_denoised=clip_denoised, run_steps=nb, k_base=k, noise_tape=tape_of(k, nb), philox_seed=philox_seed,
+            sample_offset=sample_offset), block)
         return x
 
     def dpm_solver_sde_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
@@ -1229,23 +1168,9 @@ class GaussianDiffusion:
                                                eta=1.0, *, rng="torch", philox_seed=0, sample_offset=0, noise_tape=None):
         if cond_fn_with_grad or randomize_class:
             raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
-        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
-                                                  philox_seed, sample_offset, noise_tape)
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        old_out = None
-        for k, i in enumerate(indices):
-            t = th.full((shape[0],), i, device=device, dtype=th.long)
-            z = noise_tape[1 + k] if noise_tape is not None else None
-            with th.no_grad():
-                out = self.dpm_solver_sde_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                                 cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, eta=eta,
-                                                 old_out=old_out, noise=z, philox_seed=philox_seed, sample_offset=sample_offset,
-                                                 rng_step=k + 1 if z is None and rng == "philox" else None)
-            yield out
-            old_out = out
-            img = out["sample"]
+        yield from self._stepwise(self.dpm_solver_sde_sample, model, shape, noise, device, progress, skip_timesteps, init_image,
+                                  rng, philox_seed, sample_offset, noise_tape, step_noise=True, clip_denoised=clip_denoised,
+                                  denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, eta=eta)
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

@@ -19,6 +19,28 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _p(t):
+    """A tensor's address for a ctypes pointer field; None (NULL) for an absent operand."""
+    return t.data_ptr() if t is not None else None
+
+
+def _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base):
+    """The fields every in-library loop's argument struct shares, as keywords, and the host timestep map they point into
+    (the caller keeps it alive while the loop is enqueued)."""
+    tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
+    return dict(num_steps=len(tmap), coef=coef.data_ptr(), timestep_map=tmap.ctypes.data, scale=_p(scale),
+                inpaint_mask=_p(inpaint_mask), inpaint_motion=_p(inpaint_motion), clip_denoised=int(bool(clip_denoised)),
+                run_steps=run_steps, k_base=k_base), tmap
+
+
+def _step_fields(shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised):
+    """The fields every pose-layout step struct shares, as keywords; shape = the [B, J, F, T] of the operands."""
+    B, J, F, T = shape
+    return dict(batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(), t=_p(t), step_index=step_index,
+                x0_cond=x0_cond.data_ptr(), x0_uncond=_p(x0_uncond), scale=_p(scale), inpaint_mask=_p(inpaint_mask),
+                inpaint_motion=_p(inpaint_motion), clip_denoised=int(bool(clip_denoised)))
+
+
 def require_device(t, what):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what} must be a torch.Tensor")
@@ -190,80 +212,57 @@ class Engine:
         _lib.check(self.lib.gdx_get_tap(self.handle, which, _ptr(out), out.numel(), _stream(device)), self.lib)
         return out
 
+    def _run_loop(self, fn, args, device, *keep):
+        _lib.check(fn(self.handle, C.byref(args), _stream(device)), self.lib)
+        self._keep_loop = keep
+
     def sample_loop(self, x, kind, mode, coef, timestep_map, first_index, scale=None, inpaint_mask=None,
                     inpaint_motion=None, noise_tape=None, const_noise=False, philox_seed=0, sample_offset=0,
                     dump=None, dump_steps=None, run_steps=0, k_base=0, clip_denoised=False):
         """x is updated in place (x_T in, final sample out).  run_steps / k_base: one block of a loop (gdx.h)."""
-        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base)
         ds = np.ascontiguousarray(np.asarray(dump_steps if dump_steps is not None else [], dtype=np.int32))
-        a = _lib.LoopArgs(kind=kind, mode=mode, num_steps=len(tmap), first_index=first_index, coef=coef.data_ptr(),
-                          timestep_map=tmap.ctypes.data, x=x.data_ptr(),
-                          scale=scale.data_ptr() if scale is not None else None,
-                          inpaint_mask=inpaint_mask.data_ptr() if inpaint_mask is not None else None,
-                          inpaint_motion=inpaint_motion.data_ptr() if inpaint_motion is not None else None,
-                          noise_tape=noise_tape.data_ptr() if noise_tape is not None else None,
-                          const_noise=int(const_noise), philox_seed=philox_seed, sample_offset=sample_offset,
-                          dump=dump.data_ptr() if dump is not None else None,
-                          dump_steps=ds.ctypes.data if len(ds) else None, n_dump=len(ds), run_steps=run_steps,
-                          k_base=k_base, clip_denoised=int(bool(clip_denoised)))
-        _lib.check(self.lib.gdx_sample_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
-        self._keep_loop = (tmap, ds)
+        a = _lib.LoopArgs(kind=kind, mode=mode, first_index=first_index, x=x.data_ptr(), noise_tape=_p(noise_tape),
+                          const_noise=int(const_noise), philox_seed=philox_seed, sample_offset=sample_offset, dump=_p(dump),
+                          dump_steps=ds.ctypes.data if len(ds) else None, n_dump=len(ds), **kw)
+        self._run_loop(self.lib.gdx_sample_loop, a, x.device, tmap, ds)
 
     def bpd_loop(self, x_start, mode, coef, timestep_map, vb, xstart_mse, mse, scale=None, inpaint_mask=None,
                  inpaint_motion=None, noise_tape=None, philox_seed=0, sample_offset=0, clip_denoised=True, run_steps=0,
                  k_base=0, prior_bpd=None, prior_log_variance=0.0):
         """gdx_bpd_loop: steps k_base .. of the variational bound into column k of vb / xstart_mse / mse [B, num_steps]."""
-        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
-        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        a = _lib.BpdLoopArgs(mode=mode, num_steps=len(tmap), coef=coef.data_ptr(), timestep_map=tmap.ctypes.data,
-                             x_start=x_start.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
-                             inpaint_motion=p(inpaint_motion), noise_tape=p(noise_tape), philox_seed=philox_seed,
-                             sample_offset=sample_offset, clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
-                             k_base=k_base, prior_log_variance=prior_log_variance, vb=vb.data_ptr(),
-                             xstart_mse=xstart_mse.data_ptr(), mse=mse.data_ptr(), prior_bpd=p(prior_bpd))
-        _lib.check(self.lib.gdx_bpd_loop(self.handle, C.byref(a), _stream(x_start.device)), self.lib)
-        self._keep_loop = (tmap,)
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base)
+        a = _lib.BpdLoopArgs(mode=mode, x_start=x_start.data_ptr(), noise_tape=_p(noise_tape), philox_seed=philox_seed,
+                             sample_offset=sample_offset, prior_log_variance=prior_log_variance, vb=vb.data_ptr(),
+                             xstart_mse=xstart_mse.data_ptr(), mse=mse.data_ptr(), prior_bpd=_p(prior_bpd), **kw)
+        self._run_loop(self.lib.gdx_bpd_loop, a, x_start.device, tmap)
 
     def plms_loop(self, x, mode, order, coef, timestep_map, first_index, eps_hist, scratch, scale=None, inpaint_mask=None,
                   inpaint_motion=None, clip_denoised=False, run_steps=0, k_base=0):
         """gdx_plms_loop: x is updated in place; eps_hist [order, B, J, 1, T] and scratch [B, J, 1, T] are the caller's and
         carry the multistep history from one block (run_steps / k_base) to the next."""
-        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
-        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        a = _lib.PlmsLoopArgs(mode=mode, order=order, num_steps=len(tmap), first_index=first_index, coef=coef.data_ptr(),
-                              timestep_map=tmap.ctypes.data, x=x.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
-                              inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
-                              k_base=k_base, eps_hist=eps_hist.data_ptr(), scratch=scratch.data_ptr())
-        _lib.check(self.lib.gdx_plms_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
-        self._keep_loop = (tmap,)
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base)
+        a = _lib.PlmsLoopArgs(mode=mode, order=order, first_index=first_index, x=x.data_ptr(), eps_hist=eps_hist.data_ptr(),
+                              scratch=scratch.data_ptr(), **kw)
+        self._run_loop(self.lib.gdx_plms_loop, a, x.device, tmap)
 
     def dpm_loop(self, x, mode, order, coef, timestep_map, first_index, hist=None, scale=None, inpaint_mask=None,
                  inpaint_motion=None, clip_denoised=False, run_steps=0, k_base=0):
         """gdx_dpm_loop: x is updated in place; hist [order, B, J, 1, T] (order > 1) is the caller's and carries the x0
         predictions of the multistep history from one block (run_steps / k_base) to the next."""
-        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
-        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        a = _lib.DpmLoopArgs(mode=mode, order=order, num_steps=len(tmap), first_index=first_index, coef=coef.data_ptr(),
-                             timestep_map=tmap.ctypes.data, x=x.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
-                             inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
-                             k_base=k_base, hist=p(hist))
-        _lib.check(self.lib.gdx_dpm_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
-        self._keep_loop = (tmap,)
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base)
+        a = _lib.DpmLoopArgs(mode=mode, order=order, first_index=first_index, x=x.data_ptr(), hist=_p(hist), **kw)
+        self._run_loop(self.lib.gdx_dpm_loop, a, x.device, tmap)
 
     def dpm_sde_loop(self, x, mode, order, coef, timestep_map, first_index, hist=None, scale=None, inpaint_mask=None,
                      inpaint_motion=None, clip_denoised=False, run_steps=0, k_base=0, noise_tape=None, philox_seed=0,
                      sample_offset=0):
         """gdx_dpm_sde_loop: dpm_loop with noise -- noise_tape [steps of this call, B, J, 1, T] (slice 0 = this call's first
         step) or, without one, Philox draw k + 1 at executed step k."""
-        tmap = np.ascontiguousarray(np.asarray(timestep_map, dtype=np.int64))
-        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        a = _lib.DpmSdeLoopArgs(mode=mode, order=order, num_steps=len(tmap), first_index=first_index, coef=coef.data_ptr(),
-                                timestep_map=tmap.ctypes.data, x=x.data_ptr(), scale=p(scale), inpaint_mask=p(inpaint_mask),
-                                inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), run_steps=run_steps,
-                                k_base=k_base, hist=p(hist), noise_tape=p(noise_tape), philox_seed=philox_seed,
-                                sample_offset=sample_offset)
-        _lib.check(self.lib.gdx_dpm_sde_loop(self.handle, C.byref(a), _stream(x.device)), self.lib)
-        self._keep_loop = (tmap,)
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base)
+        a = _lib.DpmSdeLoopArgs(mode=mode, order=order, first_index=first_index, x=x.data_ptr(), hist=_p(hist),
+                                noise_tape=_p(noise_tape), philox_seed=philox_seed, sample_offset=sample_offset, **kw)
+        self._run_loop(self.lib.gdx_dpm_sde_loop, a, x.device, tmap)
 
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
@@ -328,19 +327,10 @@ def sampler_update(kind, coef, x, x0_cond, out, t=None, step_index=0, x0_uncond=
                    inpaint_motion=None, noise=None, const_noise=False, philox_seed=0, sample_offset=0, rng_step=0,
                    pred_xstart=None, cond_grad=None, cond_coef=None, clip_denoised=False):
     lib = _lib.load()
-    B, J, F, T = x.shape
-    a = _lib.UpdateArgs(kind=kind, batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(),
-                        t=t.data_ptr() if t is not None else None, step_index=step_index, x=x.data_ptr(),
-                        x0_cond=x0_cond.data_ptr(), x0_uncond=x0_uncond.data_ptr() if x0_uncond is not None else None,
-                        scale=scale.data_ptr() if scale is not None else None,
-                        inpaint_mask=inpaint_mask.data_ptr() if inpaint_mask is not None else None,
-                        inpaint_motion=inpaint_motion.data_ptr() if inpaint_motion is not None else None,
-                        noise=noise.data_ptr() if noise is not None else None, const_noise=int(const_noise),
-                        philox_seed=philox_seed, sample_offset=sample_offset, rng_step=rng_step, out=out.data_ptr(),
-                        pred_xstart=pred_xstart.data_ptr() if pred_xstart is not None else None,
-                        cond_grad=cond_grad.data_ptr() if cond_grad is not None else None,
-                        cond_coef=cond_coef.data_ptr() if cond_coef is not None else None,
-                        clip_denoised=int(bool(clip_denoised)))
+    kw = _step_fields(x.shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised)
+    a = _lib.UpdateArgs(kind=kind, x=x.data_ptr(), noise=_p(noise), const_noise=int(const_noise), philox_seed=philox_seed,
+                        sample_offset=sample_offset, rng_step=rng_step, out=out.data_ptr(), pred_xstart=_p(pred_xstart),
+                        cond_grad=_p(cond_grad), cond_coef=_p(cond_coef), **kw)
     _lib.check(lib.gdx_sampler_update(C.byref(a), _stream(x.device)), lib)
     return out
 
@@ -361,13 +351,10 @@ def bpd_terms(coef, x_start, x_t, x0_cond, noise=None, t=None, step_index=0, x0_
     pred = torch.empty_like(x_start) if want_pred else None
     ws = bpd_workspace(B, J * F * T, dev)
     want_mse = want_mse and noise is not None
-    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
-    a = _lib.BpdArgs(batch=B, njoints=J * F, frames=T, step_index=step_index, coef=coef.data_ptr(), t=p(t),
-                     x_start=x_start.data_ptr(), x_t=x_t.data_ptr(), noise=p(noise), x0_cond=x0_cond.data_ptr(),
-                     x0_uncond=p(x0_uncond), scale=p(scale), inpaint_mask=p(inpaint_mask), inpaint_motion=p(inpaint_motion),
-                     model_mean=p(model_mean), clip_denoised=int(bool(clip_denoised)), prior=0, prior_log_variance=0.0,
-                     vb=out[0].data_ptr(), xstart_mse=out[1].data_ptr(), mse=out[2].data_ptr() if want_mse else None,
-                     ld=1, col=0, pred_xstart=p(pred), workspace=ws.data_ptr())
+    kw = _step_fields(x_start.shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised)
+    a = _lib.BpdArgs(x_start=x_start.data_ptr(), x_t=x_t.data_ptr(), noise=_p(noise), model_mean=_p(model_mean), prior=0,
+                     prior_log_variance=0.0, vb=out[0].data_ptr(), xstart_mse=out[1].data_ptr(),
+                     mse=out[2].data_ptr() if want_mse else None, ld=1, col=0, pred_xstart=_p(pred), workspace=ws.data_ptr(), **kw)
     _lib.check(lib.gdx_bpd_terms(C.byref(a), _stream(dev)), lib)
     return out[0], out[1], (out[2] if want_mse else None), pred
 
@@ -406,13 +393,9 @@ def plms_step(kind, coef, x, x0_cond, out, eps_out=None, eps_hist=(), t=None, st
     """gdx_plms_step: one whole PLMS step in one pass (include/gdx.h).  kind 1..4 Adams-Bashforth over the eps formed here
     and eps_hist (older, newest first), 5 the first step's corrector (x_eps / t_eps / pred_prev), 6 its predictor."""
     lib = _lib.load()
-    B, J, F, T = x0_cond.shape
-    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
-    a = _lib.PlmsStepArgs(kind=kind, batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(), t=p(t), t_eps=p(t_eps),
-                          step_index=step_index, step_index_eps=step_index_eps, x=x.data_ptr(), x_eps=p(x_eps),
-                          x0_cond=x0_cond.data_ptr(), x0_uncond=p(x0_uncond), scale=p(scale), inpaint_mask=p(inpaint_mask),
-                          inpaint_motion=p(inpaint_motion), clip_denoised=int(bool(clip_denoised)), pred_prev=p(pred_prev),
-                          eps_out=p(eps_out), out=out.data_ptr(), pred_xstart=p(pred_xstart))
+    kw = _step_fields(x0_cond.shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised)
+    a = _lib.PlmsStepArgs(kind=kind, t_eps=_p(t_eps), step_index_eps=step_index_eps, x=x.data_ptr(), x_eps=_p(x_eps),
+                          pred_prev=_p(pred_prev), eps_out=_p(eps_out), out=out.data_ptr(), pred_xstart=_p(pred_xstart), **kw)
     for i, e in enumerate(eps_hist):
         a.eps_hist[i] = e.data_ptr()
     _lib.check(lib.gdx_plms_step(C.byref(a), _stream(x0_cond.device)), lib)
@@ -424,14 +407,10 @@ def dpm_step(order, coef, x, x0_cond, out, hist=(), t=None, step_index=0, x0_unc
     """gdx_dpm_step: one DPM-Solver++ multistep step in one pass (include/gdx.h).  order 1..3 over the x0 prediction formed
     here and hist (older predictions, newest first; order - 1 of them are read); coef = dpm_coef_table rows."""
     lib = _lib.load()
-    B, J, F, T = x0_cond.shape
-    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
-    a = _lib.DpmStepArgs(order=order, batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(), t=p(t), step_index=step_index,
-                         x=x.data_ptr(), x0_cond=x0_cond.data_ptr(), x0_uncond=p(x0_uncond), scale=p(scale),
-                         inpaint_mask=p(inpaint_mask), inpaint_motion=p(inpaint_motion),
-                         clip_denoised=int(bool(clip_denoised)), out=out.data_ptr(), pred_out=p(pred_out))
+    kw = _step_fields(x0_cond.shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised)
+    a = _lib.DpmStepArgs(order=order, x=x.data_ptr(), out=out.data_ptr(), pred_out=_p(pred_out), **kw)
     for i, m in enumerate(hist):
-        a.hist[i] = p(m)
+        a.hist[i] = _p(m)
     _lib.check(lib.gdx_dpm_step(C.byref(a), _stream(x0_cond.device)), lib)
     return out
 
@@ -442,15 +421,11 @@ def dpm_sde_step(order, coef, x, x0_cond, out, hist=(), t=None, step_index=0, x0
     formed here and hist (the previous prediction, read at order 2); coef = dpm_sde_coef_table rows of one eta; z = noise, or
     the in-kernel Philox draw (philox_seed, sample_offset + b, rng_step) when noise is None."""
     lib = _lib.load()
-    B, J, F, T = x0_cond.shape
-    p = lambda v: v.data_ptr() if v is not None else None   # noqa: E731
-    a = _lib.DpmSdeStepArgs(order=order, batch=B, njoints=J * F, frames=T, coef=coef.data_ptr(), t=p(t), step_index=step_index,
-                            x=x.data_ptr(), x0_cond=x0_cond.data_ptr(), x0_uncond=p(x0_uncond), scale=p(scale),
-                            inpaint_mask=p(inpaint_mask), inpaint_motion=p(inpaint_motion),
-                            clip_denoised=int(bool(clip_denoised)), out=out.data_ptr(), pred_out=p(pred_out), noise=p(noise),
-                            philox_seed=philox_seed, sample_offset=sample_offset, rng_step=rng_step)
+    kw = _step_fields(x0_cond.shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised)
+    a = _lib.DpmSdeStepArgs(order=order, x=x.data_ptr(), out=out.data_ptr(), pred_out=_p(pred_out), noise=_p(noise),
+                            philox_seed=philox_seed, sample_offset=sample_offset, rng_step=rng_step, **kw)
     for i, m in enumerate(hist):
-        a.hist[i] = p(m)
+        a.hist[i] = _p(m)
     _lib.check(lib.gdx_dpm_sde_step(C.byref(a), _stream(x0_cond.device)), lib)
     return out
 

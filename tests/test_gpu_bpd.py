@@ -115,6 +115,43 @@ def test_bpd_terms_kernel_batch_independent_and_vs_restatement(J, T):
     assert torch.equal(prior[2:3], E.bpd_prior(coef, dv[0][2:3].clone(), 999, df._prior_log_variance()))
 
 
+@pytest.mark.parametrize("J,T,misaligned", [(3, 4, True), (3, 5, False)])
+def test_bpd_terms_kernel_forms_pred_by_group_whatever_the_mask_alignment(J, T, misaligned):
+    """bpd_terms_kernel forms its prediction through the shared group-wise CFG -> inpainting -> clamp helper.  (3, 4): whole
+    groups (J*T % 4 == 0); a mask that starts one byte into a larger byte buffer cannot be read four bytes at a time, so the
+    call takes the element-wise instantiation: the three sums and pred_xstart must have the bits of the call with an aligned
+    copy of the same mask.  (3, 5): a partial last group, aligned mask only.  pred_xstart against the fp64 restatement as in
+    the kernel test above."""
+    from gesturediffusion_amd import engine as E
+    from gesturediffusion_amd.diffusion import gaussian_diffusion as gd
+    d = dev()
+    df = gd.GaussianDiffusion(betas=gd.get_named_beta_schedule("cosine", 1000), model_mean_type=gd.ModelMeanType.START_X,
+                              model_var_type=gd.ModelVarType.FIXED_LARGE, loss_type=gd.LossType.MSE)
+    coef = df.bpd_table(d)
+    gen = torch.Generator().manual_seed(100 * J + T)
+    B = 2
+    x0, z, oc, ou, motion = (torch.randn(B, J, 1, T, generator=gen) * s for s in (0.6, 1.0, 0.7, 0.7, 0.5))
+    mask = torch.rand(B, J, 1, T, generator=gen) < 0.4
+    t, scale = torch.tensor([0, 500]), torch.tensor([2.5, -1.0])
+    xt = df.q_sample(x0.to(d), t.to(d), noise=z.to(d))
+    x0_d, z_d, oc_d, ou_d, motion_d, mask_d, scale_d, t_d = (v.to(d) for v in (x0, z, oc, ou, motion, mask, scale, t))
+
+    def terms(m):
+        return E.bpd_terms(coef, x0_d, xt, oc_d, noise=z_d, t=t_d, x0_uncond=ou_d, scale=scale_d, inpaint_mask=m,
+                           inpaint_motion=motion_d, clip_denoised=True)
+    assert mask_d.data_ptr() % 4 == 0
+    aligned = terms(mask_d)
+    if misaligned:
+        buf = torch.zeros(mask.numel() + 8, dtype=torch.bool, device=d)
+        off = buf[1:1 + mask.numel()].view(mask.shape)
+        off.copy_(mask_d)
+        assert off.data_ptr() % 4 == 1
+        for a, w in zip(terms(off), aligned):
+            assert torch.equal(a, w)
+    pred = R.blend(oc.numpy(), ou.numpy(), scale.numpy(), mask.numpy(), motion.numpy(), clip=True)
+    assert rel_err(aligned[3].cpu(), pred) < 1e-6
+
+
 @pytest.mark.parametrize("arch", ARCHS)
 def test_philox_loop_batch_independent_and_shard_invariant(arch):
     """3 / 5. In-kernel Philox noise of the loop: sample b as a B=1 run with sample_offset=b == row b of the whole batch; a

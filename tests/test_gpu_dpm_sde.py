@@ -209,7 +209,9 @@ def test_one_call_equals_blockwise_issue(arch, run_steps, monkeypatch):
 
 @pytest.mark.parametrize("order", [1, 2])
 def test_eta_zero_is_the_ode_solver(order):
-    """At eta = 0 the rows are dpm_coef_table's and s = 0: the loop gives dpm_solver_sample_loop's sample from the same x_T."""
+    """At eta = 0 the rows are dpm_coef_table's and s = 0: the loop gives dpm_solver_sample_loop's sample from the same x_T,
+    through the library loops and through the step entry points (gdx_dpm_sde_step / gdx_dpm_step, fused=False) alike -- the
+    noisy and the noise-free instantiations of the one step kernel agree."""
     g, m = _tiny("mdm")
     df = diffusion("cosine", "logsnr20")
     tape = _tape(g, df.num_timesteps)
@@ -218,6 +220,9 @@ def test_eta_zero_is_the_ode_solver(order):
     ode = df.dpm_solver_sample_loop(model, tuple(tape.shape[1:]), noise=tape[0].clone(), **kw)
     sde = df.dpm_solver_sde_sample_loop(model, tuple(tape.shape[1:]), eta=0.0, noise_tape=tape, **kw)
     assert torch.isfinite(sde).all() and torch.equal(sde, ode)
+    ode_step = df.dpm_solver_sample_loop(model, tuple(tape.shape[1:]), noise=tape[0].clone(), fused=False, **kw)
+    sde_step = df.dpm_solver_sde_sample_loop(model, tuple(tape.shape[1:]), eta=0.0, noise_tape=tape, fused=False, **kw)
+    assert torch.equal(sde_step, ode_step) and torch.equal(sde_step, sde)
 
 
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])

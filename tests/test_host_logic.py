@@ -539,3 +539,53 @@ def test_noise_block_is_sized_by_bytes():
     assert c2 == NOISE_BLOCK_BYTES // (4 * 64 * 263 * 196) == 20 and c2 * 4 * 64 * 263 * 196 <= NOISE_BLOCK_BYTES
     assert noise_block_steps(1000, 128 * 498 * 520) == 2                            # config 5
     assert noise_block_steps(1000, 10 ** 10) == 1 and noise_block_steps(7, 10) == 7
+
+
+# ---- which refusal wins when an argument struct has two defects (recorded from the build before the loops shared one driver)
+_P = 4096                                               # a non-null address; a refused call reads nothing through it
+_LOOP_WINNERS = [
+    # entry, struct, its history fields, (mode 3 + num_steps 0, num_steps 0 + order 7, order 7 + mask without motion)
+    ("gdx_plms_loop", "PlmsLoopArgs", dict(eps_hist=_P, scratch=_P),
+     ("gdx_plms_loop: bad mode", "gdx_plms_loop: bad step range", "gdx_plms_loop: order must be 2, 3 or 4")),
+    ("gdx_dpm_loop", "DpmLoopArgs", dict(hist=_P),
+     ("gdx_dpm_loop: bad mode", "gdx_dpm_loop: bad step range", "gdx_dpm_loop: order must be 1, 2 or 3")),
+    ("gdx_dpm_sde_loop", "DpmSdeLoopArgs", dict(hist=_P),
+     ("gdx_dpm_sde_loop: bad mode", "gdx_dpm_sde_loop: bad step range", "gdx_dpm_sde_loop: order must be 1 or 2")),
+]
+_STEP_WINNERS = [
+    # entry, struct, its bad kind / order, (null `out` + that, that + batch 65536)
+    ("gdx_plms_step", "PlmsStepArgs", dict(kind=0), ("gdx_plms_step: null argument", "gdx_plms_step: bad kind")),
+    ("gdx_dpm_step", "DpmStepArgs", dict(order=0), ("gdx_dpm_step: null argument", "gdx_dpm_step: order must be 1, 2 or 3")),
+    ("gdx_dpm_sde_step", "DpmSdeStepArgs", dict(order=0),
+     ("gdx_dpm_sde_step: null argument", "gdx_dpm_sde_step: order must be 1 or 2")),
+]
+
+
+def _gdx_or_skip():
+    from gesturediffusion_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgdx.so not built (run python __graft_entry__.py)")
+    return _lib, _lib.load()
+
+
+@pytest.mark.parametrize("entry,struct,hist,winners", _LOOP_WINNERS, ids=[w[0] for w in _LOOP_WINNERS])
+def test_multistep_loop_refusal_order_with_two_defects(entry, struct, hist, winners):
+    """The three multistep loops check their arguments in one order -- mode, step range, order, mask -- before the handle."""
+    import ctypes as C
+    _lib, lib = _gdx_or_skip()
+    ok = dict(mode=0, order=2, num_steps=10, first_index=9, coef=_P, timestep_map=_P, x=_P, **hist)
+    pairs = (dict(mode=3, num_steps=0), dict(num_steps=0, order=7), dict(order=7, inpaint_mask=_P))
+    for defects, want in zip(pairs, winners):
+        rc = getattr(lib, entry)(None, C.byref(getattr(_lib, struct)(**{**ok, **defects})), None)
+        assert rc == -1 and lib.gdx_last_error().decode() == want, defects
+
+
+@pytest.mark.parametrize("entry,struct,bad,winners", _STEP_WINNERS, ids=[w[0] for w in _STEP_WINNERS])
+def test_step_entry_refusal_order_with_two_defects(entry, struct, bad, winners):
+    """A step entry's own kind / order check sits between the null-argument refusal and the shape refusal."""
+    import ctypes as C
+    _lib, lib = _gdx_or_skip()
+    ok = dict(batch=2, njoints=3, frames=5, coef=_P, x=_P, x0_cond=_P, out=_P)
+    for defects, want in zip((dict(out=None, **bad), dict(batch=65536, **bad)), winners):
+        rc = getattr(lib, entry)(C.byref(getattr(_lib, struct)(**{**ok, **defects})), None)
+        assert rc == -1 and lib.gdx_last_error().decode() == want, defects

@@ -5,9 +5,11 @@
 
 Each library runs, in a fresh child process of its own (GDX_LIBGDX), one after the other, every public sampler entry point on
 the same seeded inputs and reports a SHA-256 per output: gdx_sampler_update (P / DDIM x CFG x inpainting x clip x tape /
-Philox x cond_grad), gdx_plms_update kinds 0-8, gdx_plms_step kinds 1-6, gdx_bpd_terms and its prior mode, gdx_q_sample(_t)
-and gdx_randn, each at (B, J, T) = (5, 16, 20) and (5, 7, 9) and with the operands one float off 16-byte alignment; then a
-6-step gdx_sample_loop of the tiny model (T = 20, CFG + clip, Philox noise: the token-major path) in fp32, fp16 and bf16.
+Philox x cond_grad), gdx_plms_update kinds 0-8, gdx_plms_step kinds 1-6, gdx_dpm_step orders 1-3, gdx_dpm_sde_step orders 1-2
+(tape / Philox), gdx_cfg_rescale, gdx_bpd_terms (also with its mask one byte off) and its prior mode, gdx_q_sample(_t) and
+gdx_randn, each at (B, J, T) = (5, 16, 20) and (5, 7, 9) and with the operands one float off 16-byte alignment; then 6-step
+loops of the tiny model (T = 20, CFG + clip): gdx_sample_loop (Philox noise: the token-major path), plms_sample_loop,
+dpm_solver_sample_loop (order 3) and dpm_solver_sde_sample_loop (order 2, Philox), in fp32, fp16 and bf16.
 Prints one line per output and a summary line; exit status 1 on any difference."""
 import hashlib
 import itertools
@@ -53,6 +55,10 @@ def child(out_path):
     n = df.num_timesteps
     coefs = {0: df.coef_table(0, dev, 0.0), 1: df.coef_table(1, dev, 0.5)}
     bpd_coef = diffusion([20], "FIXED_LARGE").bpd_table(dev)
+    dpm_coef, sde_coef = df.dpm_coef_table(dev), df.dpm_sde_coef_table(dev, 1.0)
+
+    class Lib:                                           # Engine.cfg_rescale needs nothing of a handle but the library
+        lib = E._lib.load()
     for (J, T), shift in [((16, 20), False), ((7, 9), False), ((16, 20), True)]:
         tag = f"J{J}T{T}{'s' if shift else ''}"
         shape = (5, J, 1, T)
@@ -85,6 +91,19 @@ def child(out_path):
                         x_eps=x_eps if kind == 5 else None, t_eps=t2 if kind == 5 else None,
                         pred_prev=pred_prev if kind == 5 else None)
             put(f"plms_step.{tag}.k{kind}.cfg{cfg:d}.inp{inp:d}.clip{clip:d}", out, eps, pred)
+        for order, cfg, inp, clip in itertools.product((1, 2, 3), *[(False, True)] * 3):
+            guide = dict(t=t, x0_uncond=ou if cfg else None, scale=scale if cfg else None, inpaint_mask=mask if inp else None,
+                         inpaint_motion=motion if inp else None, clip_denoised=clip)
+            out, pred = new(), new()
+            E.dpm_step(order, dpm_coef, x, oc, out, hist=hist[:order - 1], pred_out=pred, **guide)
+            put(f"dpm_step.{tag}.o{order}.cfg{cfg:d}.inp{inp:d}.clip{clip:d}", out, pred)
+            for tape in (False, True) if order < 3 else ():
+                out, pred = new(), new()
+                E.dpm_sde_step(order, sde_coef, x, oc, out, hist=hist[:order - 1], pred_out=pred, noise=z if tape else None,
+                               philox_seed=77, sample_offset=3, rng_step=5, **guide)
+                put(f"dpm_sde_step.{tag}.o{order}.cfg{cfg:d}.inp{inp:d}.clip{clip:d}.tape{tape:d}", out, pred)
+        for tt, iv in ((None, None), (t, (1, n // 2))):
+            put(f"cfg_rescale.{tag}.t{tt is not None:d}", *E.Engine.cfg_rescale(Lib, oc, ou, scale, 0.7, t=tt, interval=iv, out=new()))
         x0 = rnd(0.6)
         xt = f(E.q_sample_t(x0, z, coefs[0], t))
         put(f"q_sample_t.{tag}", xt, E.q_sample(x0, z, coefs[0], 7))
@@ -92,6 +111,10 @@ def child(out_path):
             put(f"bpd_terms.{tag}.cfg{cfg:d}.inp{inp:d}.clip{clip:d}",
                 *E.bpd_terms(bpd_coef, x0, xt, oc, noise=z, t=t, x0_uncond=ou if cfg else None, scale=scale if cfg else None,
                              inpaint_mask=mask if inp else None, inpaint_motion=motion if inp else None, clip_denoised=clip))
+        mask1 = torch.zeros(mask.numel() + 8, dtype=torch.bool, device=dev)[1:1 + mask.numel()].view(shape)
+        mask1.copy_(mask)
+        put(f"bpd_terms.{tag}.mask1", *E.bpd_terms(bpd_coef, x0, xt, oc, noise=z, t=t, x0_uncond=ou, scale=scale, inpaint_mask=mask1,
+                                                    inpaint_motion=motion, clip_denoised=True))
         put(f"bpd_terms.{tag}.mean", *E.bpd_terms(bpd_coef, x0, xt, oc, noise=z, t=t, model_mean=pred_prev))
         put(f"bpd_prior.{tag}", E.bpd_prior(bpd_coef, x0, n - 1, -0.25))
         z_out = new()
@@ -107,8 +130,12 @@ def child(out_path):
         m.to(dev).eval()
         _, seedp, mfcc = synthetic_inputs(TINY, 3, 20, seed=5)
         y = {"seed": seedp.to(dev), "mfcc": mfcc.to(dev), "scale": torch.tensor([2.5, 1.0, 0.5], device=dev)}
-        put(f"sample_loop.{dtype}", loop_df.p_sample_loop(ClassifierFreeSampleModel(m), (3, 16, 1, 20), clip_denoised=True,
-                                                          model_kwargs={"y": y}, rng="philox", philox_seed=9))
+        kw = dict(clip_denoised=True, model_kwargs={"y": y}, rng="philox", philox_seed=9)
+        cfg_model = ClassifierFreeSampleModel(m)
+        put(f"sample_loop.{dtype}", loop_df.p_sample_loop(cfg_model, (3, 16, 1, 20), **kw))
+        put(f"plms_loop.{dtype}", loop_df.plms_sample_loop(cfg_model, (3, 16, 1, 20), order=2, **kw))
+        put(f"dpm_loop.{dtype}", loop_df.dpm_solver_sample_loop(cfg_model, (3, 16, 1, 20), order=3, **kw))
+        put(f"dpm_sde_loop.{dtype}", loop_df.dpm_solver_sde_sample_loop(cfg_model, (3, 16, 1, 20), order=2, **kw))
     json.dump(report, open(out_path, "w"))
 
 
