@@ -29,11 +29,11 @@
 // scores + 24 in-flight tile registers: 186 allocated); 192 needs 96 + 96 + 32 + 48 and runs one workgroup per CU, like 256
 // (256 + 146 accumulation registers, no scratch).
 #include "gdx_internal.h"
+#include "gdx_device.h"
 
 namespace gdx {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int HD>
 __global__ __launch_bounds__(256, (HD <= 128 ? 2 : 1)) void attention_kernel(

@@ -21,6 +21,7 @@
 //     wave of the SIMD keeps the matrix pipe busy meanwhile).
 // MFMA / softmax / fragment layout: S^T = K Q^T, O^T += V^T P^T, deferred max, register rings (as in attentionh.hip).
 #include "gdx_internal.h"
+#include "gdx_device.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -29,7 +30,6 @@ namespace gdx {
 
 int gemm2_num_cus();
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr3_t;
 
 // PERSIST (round 2; batches with several (sample, head) items per CU, e.g. BASELINE configs 3 / 4): one workgroup per CU

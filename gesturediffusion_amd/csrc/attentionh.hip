@@ -26,42 +26,36 @@
 //     score exceeds it by more than 8 (p <= 2^8 is far inside fp16 range; the running sum and O are fp32).
 // K/V rows past S are the next sample's rows or read as zeros (exact buffer size in the descriptor); their scores
 // are masked to -inf.  (The head_dim 96 / 192 instantiations re-read key S - 1 instead and never look past the sample.)
+//
+// Layout of this file: the three kernels (8 waves x 1 block, 8 x 2 blocks, 8 x 2 persistent) are the same arithmetic per query
+// block, and every piece of it is written ONCE, in front of them: the geometry (AhGeom), the per-wave DMA piece table and the
+// piece loop of one stage (ah_piece_table, ah_issue), the fragment addresses (AhFrag), the tile body (ah_qk, ah_v_prefetch,
+// ah_softmax, ah_pv, composed by ah_tile with a stamp hook between the pieces), the stage hand-over (ah_handover), Q through
+// the slice (ah_q_dma, ah_q_read), the output (ah_inv_l, ah_store_rows) and an item's geometry (ah_item); the one-liners shared with the other kernel files
+// (xcd_lid, wait_vm, GDX_MFMA16, vector types) are in gdx_device.h.  A kernel is what is
+// left: which tile / item the stream fetches next, when Q arrives and when the output leaves.  The host side likewise has one
+// launcher template (launch_ah), one head-width ladder and one function for the (chunks, items, grid) of a kernel (ah_plan).
 #include "gdx_internal.h"
+#include "gdx_device.h"
 
 #include <cstdlib>
 #include <type_traits>
-
-#ifdef GDX_BF16
-#define GDX_MFMA16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#else
-#define GDX_MFMA16 __builtin_amdgcn_mfma_f32_16x16x32_f16
-#endif
 
 namespace gdx {
 int gemm2_num_cus();
 GDX_HNS_BEGIN
 
-typedef half_t f16x8 __attribute__((ext_vector_type(8)));
-typedef half_t f16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// Logical workgroup id with the workgroups of one XCD contiguous (blocks b, b + 8, b + 16, ... share an XCD and its L2; bijective
-// for any grid size, as in gemm2.hip).  The query chunks of one (sample, head) are consecutive items and read the same K / V:
-// numbered this way they run on ONE XCD at about the same time, so the K / V tiles are fetched into that L2 once instead of once
-// per chunk through three different L2s (round 3).
-__device__ __forceinline__ int ah_xcd_lid(int bid, int G) {
-    const int q = G >> 3, r = G & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
-template <int N>
-__device__ __forceinline__ void ah_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+typedef __amdgpu_buffer_rsrc_t ah_rsrc_t;
 
 // bytes readable from a (sample, head) base: the descriptor's range check only matters at the very end of the buffer,
 // so a remaining size above the 2 GiB descriptor range is clamped (a workgroup reads < S + 32 rows from its base)
 __device__ __forceinline__ int ah_records(long remaining) { return remaining > 0x7ffffff0L ? 0x7ffffff0 : (int)remaining; }
+
+// descriptor of the rest of qkv from element `off` on
+__device__ __forceinline__ ah_rsrc_t ah_rsrc(const _Float16* qkv, long off, long qkv_bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(qkv + off), (short)0, ah_records(qkv_bytes - off * 2), 0x00020000);
+}
 
 __device__ __forceinline__ f16x4 lds_read_tr(const char* p) {
     const fp16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4_t*)(p));
@@ -92,8 +86,318 @@ __device__ __forceinline__ constexpr int ah_fswz(int row) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Eight-compute-wave variant: every wave owns ONE query block of 16 and issues 1/8 of the K/V tile DMA itself.
-// With one MFMA wave per SIMD (kernel above) the softmax VALU work, the fragment-read latency and the MFMAs of a
+// Geometry of a head width: the kernels' pointer arithmetic and the launcher's LDS size both read it here.  A stage of the ring is
+// a K tile and a V tile of 32 rows; a tile is T_P pieces of 1 KiB (one LDS-DMA instruction of a wave), a wave issues PW of the
+// 2 T_P pieces of a stage.  SLICES: eight 16-row slices, one per wave, behind the ring (Q in, output out, as whole rows).
+template <int HD_, int NST_, bool SLICES>
+struct AhGeom {
+    static constexpr int HD = HD_, NST = NST_;
+    static constexpr int ROWB = HD * 2, CPR = ROWB / 16, T_BYTES = 32 * ROWB, STAGE_BYTES = 2 * T_BYTES;
+    static constexpr int T_P = T_BYTES / 1024, P = 2 * T_P, PW = (P + 7) / 8;
+    static constexpr int NKS = HD / 32, NNB = HD / 16;
+    static constexpr int NR = 2 * NKS, PD = NR < 4 ? NR - 1 : 3;        // K fragment reads of a tile, depth of their register ring
+    static constexpr int VD = NNB < 4 ? NNB - 1 : 3;                    // depth of the V ring
+    static constexpr bool POW2 = (HD & (HD - 1)) == 0;                  // rows of 12 / 24 chunks (head_dim 96 / 192) otherwise
+    static constexpr int RPP = 1024 / ROWB;                             // rows per 1 KiB piece (16 at head_dim 32)
+    static constexpr int NPQ = 16 / RPP;                                // pieces per 16-row block
+    static constexpr int GM = CPR < 16 ? CPR - 1 : 15;                  // row mask of the output slice's chunk permutation
+    static constexpr int RING_BYTES = NST * STAGE_BYTES, SLICE_BYTES = 16 * ROWB;
+    static constexpr int LDS_BYTES = RING_BYTES + (SLICES ? 8 * SLICE_BYTES : 0);
+    static constexpr int VM_TILE = (NST - 2) * PW;                      // a wave's DMA still in flight when its next tile has landed
+    static_assert(!SLICES || POW2, "whole rows per 1 KiB piece and XOR-composed fragment addresses: power-of-two head_dim only");
+};
+template <int HD> using AhGeom1 = AhGeom<HD, 4, false>;                 // 8 waves x 1 block
+template <int HD> using AhGeom2 = AhGeom<HD, 3, true>;                  // 8 waves x 2 blocks, also persistent
+
+constexpr float AH_RESCALE_THR = 8.0f;
+
+// ---- the K/V stream ---------------------------------------------------------------------------------------------
+// This wave's pieces (piece = wave + 8i) of every tile: a 1 KiB piece is 64 consecutive chunks of the tile image, whole rows
+// (power-of-two head_dim) or not: lane -> (row, physical chunk) -> source address.  CLAMP: the table of the LAST tile at
+// head_dim 96 / 192, whose rows past key S - 1 (row_cap) re-read key S - 1 (as the Q rows do), so nothing past the sample is
+// ever read: a masked key has p = 0, but 0 x V is only 0 for a finite V, and the rows behind the last sample are the caller's.
+template <class G, bool CLAMP>
+__device__ __forceinline__ void ah_piece_table(int (&voff)[G::PW], int wave, int lane, long ld, int row_cap = 0) {
+#pragma unroll
+    for (int i = 0; i < G::PW; ++i) {
+        int piece = wave + 8 * i;
+        piece = piece < G::P ? piece : G::P - 1;
+        const int pl = piece < G::T_P ? piece : piece - G::T_P;
+        const int g = G::POW2 ? lane : pl * 64 + lane;
+        const int row = G::POW2 ? pl * G::RPP + lane / G::CPR : g / G::CPR;
+        voff[i] = (int)((CLAMP ? min(row, row_cap) : row) * ld * 2) + (((g % G::CPR) ^ ah_fswz<G::HD>(row)) * 16);
+    }
+}
+
+// One stage's LDS-DMA of this wave: EVERY wave issues exactly PW pieces per tile, whatever it computes -- the counted
+// wait_vm<G::VM_TILE> is only right then.  `last` (wave-uniform) takes the offsets from voff_l.
+template <class G>
+__device__ __forceinline__ void ah_issue(ah_rsrc_t rsrcK, ah_rsrc_t rsrcV, char* sb, const int (&voff)[G::PW],
+                                         const int (&voff_l)[G::PW], bool last, int so, int wave) {
+#pragma unroll
+    for (int i = 0; i < G::PW; ++i) {
+        int piece = wave + 8 * i;
+        piece = piece < G::P ? piece : G::P - 1;                        // surplus issues (head_dim 32, 96) re-write the last piece
+        const int vo = last ? voff_l[i] : voff[i];
+        if (piece < G::T_P)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcK, (lds_ptr_t)(sb + piece * 1024), 16, vo, so, 0, 0);
+        else
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcV, (lds_ptr_t)(sb + G::T_BYTES + (piece - G::T_P) * 1024), 16, vo, so, 0, 0);
+    }
+}
+
+// Stage hand-over at the end of a tile: this wave's pieces of the next tile have landed, its fragment reads of this one are
+// done; behind the barrier that holds for all waves, and the stage just read is the one the next issue may overwrite.
+template <class G>
+__device__ __forceinline__ void ah_handover(int& stage, int& wst) {
+    wait_vm<G::VM_TILE>();
+    __builtin_amdgcn_s_waitcnt(0xc07f);                                 // lgkmcnt(0)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    stage = stage == G::NST - 1 ? 0 : stage + 1;
+    wst = wst == G::NST - 1 ? 0 : wst + 1;
+}
+
+// ---- fragment addresses -------------------------------------------------------------------------------------------
+// K fragment r of a stage (or of a slice holding a query block): rows l15 (+ 16 for the second key block), k-step r % NKS;
+// V fragment: column block nb, key half.  Power-of-two rows start on a 256-byte boundary, so the swizzle is folded into the
+// base and the k-step / column block XORed on top; rows of 12 / 24 chunks do not, and there the chunk (32-byte block) index is
+// formed first, then added to the row.
+template <class G>
+struct AhFrag {
+    int kb, kz, vb, vz, lq;
+    __device__ __forceinline__ AhFrag(int l15, int lq_) : lq(lq_) {
+        const int vrow = 4 * lq + (l15 >> 2);
+        kz = ah_fswz<G::HD>(l15);
+        vz = ah_fswz<G::HD>(vrow) >> 1;
+        kb = l15 * G::ROWB + (G::POW2 ? (lq ^ kz) << 4 : 0);
+        vb = G::T_BYTES + vrow * G::ROWB + (G::POW2 ? vz << 5 : 0) + (l15 & 3) * 8;
+    }
+    __device__ __forceinline__ f16x8 kread(const char* St, int r) const {
+        if constexpr (G::POW2)
+            return *reinterpret_cast<const f16x8*>(St + ((kb + (r / G::NKS) * 16 * G::ROWB) ^ ((r % G::NKS) << 6)));
+        else
+            return *reinterpret_cast<const f16x8*>(St + kb + (r / G::NKS) * 16 * G::ROWB + (((lq + 4 * (r % G::NKS)) ^ kz) << 4));
+    }
+    __device__ __forceinline__ f16x4 vread(const char* St, int nb, int half) const {
+        if constexpr (G::POW2) return lds_read_tr(St + ((vb + half * 16 * G::ROWB) ^ (nb << 5)));
+        else return lds_read_tr(St + vb + half * 16 * G::ROWB + ((nb ^ vz) << 5));
+    }
+};
+
+// ---- the tile body ------------------------------------------------------------------------------------------------
+// S^T = K Q^T for the wave's NQ query blocks, K fragments through a register ring PD reads ahead
+template <class G, int QB, int NQ>
+__device__ __forceinline__ void ah_qk(const AhFrag<G>& fr, const char* St, const f16x8 (&qf)[QB][G::NKS], f32x4 (&s)[NQ][2]) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) s[qi][0] = s[qi][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f16x8 kring[G::PD + 1];
+#pragma unroll
+    for (int r = 0; r < G::PD; ++r) kring[r] = fr.kread(St, r);
+#pragma unroll
+    for (int r = 0; r < G::NR; ++r) {
+        if (r + G::PD < G::NR) kring[(r + G::PD) % (G::PD + 1)] = fr.kread(St, r + G::PD);
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi)
+            s[qi][r / G::NKS] = GDX_MFMA16(kring[r % (G::PD + 1)], qf[qi][r % G::NKS], s[qi][r / G::NKS], 0, 0, 0);
+    }
+}
+
+// the first VD column blocks of V, on their way while the softmax runs
+template <class G>
+__device__ __forceinline__ void ah_v_prefetch(const AhFrag<G>& fr, const char* St, f16x4 (&vring)[G::VD + 1][2]) {
+#pragma unroll
+    for (int nb = 0; nb < G::VD; ++nb) {
+        vring[nb][0] = fr.vread(St, nb, 0);
+        vring[nb][1] = fr.vread(St, nb, 1);
+    }
+}
+
+// One query block's softmax step on the raw scores of tile kt; the scale (log2 e / sqrt(hd) > 0) is applied inside the exp2
+// argument (one fma per element).  Returns the 8 probabilities of the lane, packed: the B operand of P V.
+template <class G>
+__device__ __forceinline__ f16x8 ah_softmax(const f32x4 (&s)[2], int kt, int S, int lq, float c_log2, float& m_run, float& l_run,
+                                            f32x4 (&o)[G::NNB]) {
+    float v[8];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[kb * 4 + e] = s[kb][e];
+    if (kt * 32 + 32 > S) {                                             // block-uniform: only the last tile masks
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (kt * 32 + (j >> 2) * 16 + 4 * lq + (j & 3) >= S) v[j] = -INFINITY;
+    }
+    float mx = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7]))) * c_log2;
+    if (__any(mx > m_run + AH_RESCALE_THR)) {                           // every lane votes, also those of query rows past S
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        l_run *= alpha;
+#pragma unroll
+        for (int nb = 0; nb < G::NNB; ++nb) o[nb] *= alpha;
+        m_run = m_new;
+    }
+    float psum = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        v[j] = __builtin_amdgcn_exp2f(fmaf(v[j], c_log2, -m_run));
+        psum += v[j];
+    }
+    l_run += psum;
+    return f16x8{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3], (half_t)v[4], (half_t)v[5], (half_t)v[6], (half_t)v[7]};
+}
+
+// O^T += V^T P^T, V fragments through a ring VD column blocks ahead (ah_v_prefetch filled it)
+template <class G, int QB, int NQ>
+__device__ __forceinline__ void ah_pv(const AhFrag<G>& fr, const char* St, f16x4 (&vring)[G::VD + 1][2], const f16x8 (&pf)[NQ],
+                                      f32x4 (&o)[QB][G::NNB]) {
+#pragma unroll
+    for (int nb = 0; nb < G::NNB; ++nb) {
+        if (nb + G::VD < G::NNB) {
+            vring[(nb + G::VD) % (G::VD + 1)][0] = fr.vread(St, nb + G::VD, 0);
+            vring[(nb + G::VD) % (G::VD + 1)][1] = fr.vread(St, nb + G::VD, 1);
+        }
+        const f16x4 v0 = vring[nb % (G::VD + 1)][0], v1 = vring[nb % (G::VD + 1)][1];
+        const f16x8 vf = f16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) o[qi][nb] = GDX_MFMA16(vf, pf[qi], o[qi][nb], 0, 0, 0);
+    }
+}
+
+// Diagnostic stamps of the persistent kernel (GDX_GEMM_DEBUG only): cycles per tile spent issuing the DMA pieces, in QK^T, in
+// the softmax, in PV and in the wait + barrier.  The plain build carries an empty hook.
+template <bool DBG>
+struct AhStamps {
+    unsigned long long d_is = 0, d_qk = 0, d_sm = 0, d_pv = 0, d_bar = 0, n_t = 0, t_a = 0;
+    __device__ __forceinline__ void start() {
+        if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); t_a = __builtin_amdgcn_s_memtime(); }
+    }
+    __device__ __forceinline__ void mark(unsigned long long& acc) {
+        if constexpr (DBG) {
+            __builtin_amdgcn_sched_barrier(0);
+            const unsigned long long t_b = __builtin_amdgcn_s_memtime();
+            acc += t_b - t_a;
+            t_a = t_b;
+        }
+    }
+};
+
+// One K/V tile for the wave's NQ (of QB) query blocks; NQ = 0: a wave without a block only streams.
+template <class G, int QB, int NQ, bool DBG>
+__device__ __forceinline__ void ah_tile(const AhFrag<G>& fr, const char* St, const f16x8 (&qf)[QB][G::NKS], int kt, int S, float c_log2,
+                                        float (&m_run)[QB], float (&l_run)[QB], f32x4 (&o)[QB][G::NNB], AhStamps<DBG>& st) {
+    if constexpr (NQ > 0) {
+        f32x4 s[NQ][2];
+        ah_qk<G, QB, NQ>(fr, St, qf, s);
+        st.mark(st.d_qk);
+        f16x4 vring[G::VD + 1][2];
+        ah_v_prefetch<G>(fr, St, vring);
+        f16x8 pf[NQ];
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) pf[qi] = ah_softmax<G>(s[qi], kt, S, fr.lq, c_log2, m_run[qi], l_run[qi], o[qi]);
+        st.mark(st.d_sm);
+        ah_pv<G, QB, NQ>(fr, St, vring, pf, o);
+    }
+    st.mark(st.d_pv);
+}
+
+// ---- items, Q through the slice, output -----------------------------------------------------------------------------
+// Work item w = (sample, head, query chunk): element offset of its (sample, head) inside qkv, its first query block and its block
+// count (<= 8 * QB).  SCALAR: the results are forced into scalar registers -- integer division runs on the vector ALU, and
+// without the readfirstlanes these wave-uniform values sit in vector registers through the whole tile loop of the persistent
+// kernel, which has none to spare.
+struct AhItem {
+    long off;
+    int b, h, qb_lo, nblk;
+};
+template <bool SCALAR>
+__device__ __forceinline__ AhItem ah_item(int w, int nchunk, int H, int S, long ld, int hd) {
+    auto u = [](int x) { return SCALAR ? __builtin_amdgcn_readfirstlane(x) : x; };
+    const int nqb = (S + 15) / 16;
+    AhItem it;
+    const int ci = u(w % nchunk);
+    it.h = u((w / nchunk) % H);
+    it.b = u(w / (nchunk * H));
+    it.off = (long)it.b * S * ld + it.h * hd;
+    it.qb_lo = u((int)((long)ci * nqb / nchunk));
+    it.nblk = u((int)((long)(ci + 1) * nqb / nchunk)) - it.qb_lo;
+    return it;
+}
+// the query blocks of a chunk go to the waves round-robin: blocks qb_lo + wave + 8 qi, qi < this
+template <int QB>
+__device__ __forceinline__ int ah_my_blocks(int nblk, int wave) { return wave < nblk ? min((nblk - wave + 7) / 8, QB) : 0; }
+
+// Q fragments and output blocks travel as WHOLE ROWS through the wave's own 16-row slice of LDS (behind the K/V ring).
+// Loaded straight into the fragment layout a Q load instruction takes 64 bytes from each of 16 rows, and an output store puts
+// 32 bytes into each of 16 rows: 6 144 partial-line requests per workgroup and item, which the CU's address unit serves at
+// about two cycles each -- round-3 stamps: 6-10 k cycles to ISSUE a wave's 16 Q loads and 5.9 k for its 32 stores, ~13 us per
+// item outside the tile loop.  A query block is 16 rows of ROWB bytes, exactly a 16-key K block: staged by LDS-DMA with K's
+// chunk swizzle it is read back with K's fragment read; an output block is written to the slice in the accumulator layout
+// (chunk-swizzled by row) and leaves as 16-byte pieces of whole rows.
+// Rows past S repeat row S - 1 (as in attentionh8_kernel): a query that is never stored still takes part in the block's
+// rescale vote, so it must not come from the next sample or the pad -- or a sample's bits would depend on its neighbours.
+template <class G>
+__device__ __forceinline__ void ah_q_dma(ah_rsrc_t rsrcQ, char* sl, int q0, int S, long ld, int ln) {
+#pragma unroll
+    for (int j = 0; j < G::NPQ; ++j) {
+        const int row = j * G::RPP + ln / G::CPR;
+        const int vo = (int)(min(q0 + row, S - 1) * ld * 2) + (((ln % G::CPR) ^ ah_fswz<G::HD>(row)) * 16);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcQ, (lds_ptr_t)(sl + j * 1024), 16, vo, 0, 0, 0);
+    }
+}
+template <class G>
+__device__ __forceinline__ void ah_q_read(const AhFrag<G>& fr, const char* sl, f16x8 (&qf)[G::NKS]) {
+#pragma unroll
+    for (int ks = 0; ks < G::NKS; ++ks) qf[ks] = fr.kread(sl, ks);
+}
+template <class G>
+__device__ __forceinline__ void ah_q_zero(f16x8 (&qf)[G::NKS]) {
+#pragma unroll
+    for (int ks = 0; ks < G::NKS; ++ks) qf[ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+}
+
+// 1 / (the softmax denominator of the lane's query): the four lanes of a query hold a quarter of the keys each
+__device__ __forceinline__ float ah_inv_l(float l_run) {
+    float l_tot = l_run;
+    l_tot += __shfl_xor(l_tot, 16);
+    l_tot += __shfl_xor(l_tot, 32);
+    return 1.0f / l_tot;
+}
+
+// Output of the wave's query blocks (the first `mine` of QB; block qi is query block qb0 + 8 qi): a lane holds columns
+// 16 nb + 4 lq .. + 3 of query l15; through the slice (16-byte chunk c of row r at c ^ (r mod chunks-per-row, at most 16): the
+// sixteen rows of a column land in sixteen different bank groups) and out as whole rows.  ln: the lane id (the persistent kernel
+// passes its laundered copy).  The loop over the blocks is in here on purpose: as a helper for ONE block, called from a loop in the
+// kernel, it cost attentionh8p_kernel<256, 2> 33 spilled registers instead of 2 (profiles/attnh_once_isa_compare.txt).
+template <class G, int QB>
+__device__ __forceinline__ void ah_store_rows(const f32x4 (&o)[QB][G::NNB], const float (&l_run)[QB], int mine, char* sl, int ln,
+                                              _Float16* ctx, int b, int h, int qb0, int S, int d) {
+    const int e15 = ln & 15, eq = ln >> 4;
+#pragma unroll
+    for (int qi = 0; qi < QB; ++qi) {
+        if (qi >= mine) continue;
+        const float inv = ah_inv_l(l_run[qi]);
+#pragma unroll
+        for (int nb = 0; nb < G::NNB; ++nb) {
+            const f32x4 r = o[qi][nb] * inv;
+            *reinterpret_cast<f16x4*>(sl + e15 * G::ROWB + (((2 * nb + (eq >> 1)) ^ (e15 & G::GM)) << 4) + (eq & 1) * 8) =
+                f16x4{(half_t)r[0], (half_t)r[1], (half_t)r[2], (half_t)r[3]};
+        }
+        const int q0 = 16 * (qb0 + 8 * qi);
+#pragma unroll
+        for (int j = 0; j < G::NPQ; ++j) {
+            const int row = j * G::RPP + ln / G::CPR, c = ln % G::CPR;
+            const f16x8 v = *reinterpret_cast<const f16x8*>(sl + row * G::ROWB + ((c ^ (row & G::GM)) << 4));
+            if (q0 + row < S) *reinterpret_cast<f16x8*>(ctx + ((long)b * S + q0 + row) * d + h * G::HD + 8 * c) = v;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Eight compute waves, every wave owns ONE query block of 16 and issues 1/8 of the K/V tile DMA itself.
+// With one MFMA wave per SIMD (the removed 4 + 4 kernel) the softmax VALU work, the fragment-read latency and the MFMAs of a
 // wave are serial (measured 3 300 cycles per 32-key tile at head_dim 256 against 1 024 cycles of MFMA); two waves
 // per SIMD cover each other's softmax and LDS latency, and a wave needs half the registers (64 accumulators + 32
 // Q-fragment registers at head_dim 256), which leaves room for the fragment prefetch rings.
@@ -102,190 +406,68 @@ __global__ __launch_bounds__(512, 1) void attentionh8_kernel(const _Float16* __r
                                                              int S, int H, int d, int nchunk, float c_log2,
                                                              long qkv_bytes) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int ROWB = HD * 2, CPR = ROWB / 16, T_BYTES = 32 * ROWB, STAGE_BYTES = 2 * T_BYTES;
-    constexpr int T_P = T_BYTES / 1024, P = 2 * T_P, PW = (P + 7) / 8;
-    constexpr int NST = 4;
-    constexpr int NKS = HD / 32, NNB = HD / 16;
-    constexpr float RESCALE_THR = 8.0f;
+    using G = AhGeom1<HD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
-    const int wg = ah_xcd_lid((int)blockIdx.x, (int)gridDim.x);
-    const int ci = wg % nchunk;
-    const int h = (wg / nchunk) % H, b = wg / (nchunk * H);
     const long ld = 3L * d;
-    const long base_off = (long)b * S * ld + h * HD;
-    const _Float16* base = qkv + base_off;
-    const int nqb = (S + 15) / 16;
-    const int qb_lo = (int)((long)ci * nqb / nchunk), qb_hi = (int)((long)(ci + 1) * nqb / nchunk);
+    const AhItem im = ah_item<false>(xcd_lid((int)blockIdx.x, (int)gridDim.x), nchunk, H, S, ld, HD);
     const int ntiles = (S + 31) / 32;
-    const bool mine = qb_lo + wave < qb_hi;                           // wave-uniform
-    constexpr bool POW2 = (HD & (HD - 1)) == 0;                       // rows of 12 / 24 chunks (head_dim 96 / 192) otherwise
-    auto fswz = [](int row) { return ah_fswz<HD>(row); };
+    const bool mine = wave < im.nblk;                                 // wave-uniform
 
     // ---- Q fragments first (ordinary loads: their wait must not sit behind the DMA stream)
-    f16x8 qf[NKS];
+    f16x8 qf[1][G::NKS];
     {
-        int q = 16 * (qb_lo + wave) + l15;
+        int q = 16 * (im.qb_lo + wave) + l15;
         q = q < S ? q : S - 1;
-        const _Float16* qp = base + (long)q * ld + 8 * lq;
+        const _Float16* qp = qkv + im.off + (long)q * ld + 8 * lq;
 #pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const f16x8*>(qp + 32 * ks);
+        for (int ks = 0; ks < G::NKS; ++ks) qf[0][ks] = *reinterpret_cast<const f16x8*>(qp + 32 * ks);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
 
-    // ---- DMA: this wave's pieces (piece = wave + 8i) of every tile
-    const long kb_off = (base_off + d) * 2, vb_off = (base_off + 2 * d) * 2;
-    const auto rsrcK = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + d), (short)0, ah_records(qkv_bytes - kb_off), 0x00020000);
-    const auto rsrcV = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + 2 * d), (short)0, ah_records(qkv_bytes - vb_off), 0x00020000);
-    int voff[PW], voff_l[PW];
-#pragma unroll
-    for (int i = 0; i < PW; ++i) {
-        int piece = wave + 8 * i;
-        piece = piece < P ? piece : P - 1;
-        const int pl = piece < T_P ? piece : piece - T_P;
-        // a 1 KiB piece is 64 consecutive chunks of the tile image, whole rows (power-of-two head_dim) or not:
-        // lane -> (row, physical chunk) -> source address
-        const int g = POW2 ? lane : pl * 64 + lane;
-        const int row = POW2 ? pl * (1024 / ROWB) + lane / CPR : g / CPR;
-        voff[i] = (int)(row * ld * 2) + (((g % CPR) ^ fswz(row)) * 16);
-        // head_dim 96 / 192: the tile rows past key S - 1 re-read key S - 1 (as the Q rows do), so nothing past the sample is ever
-        // read: a masked key has p = 0, but 0 x V is only 0 for a finite V, and the rows behind the last sample are the caller's
-        const int row_l = min(row, S - 1 - 32 * (ntiles - 1));
-        voff_l[i] = POW2 ? voff[i] : (int)(row_l * ld * 2) + (((g % CPR) ^ fswz(row)) * 16);
-    }
+    // ---- the K/V stream: past the end, harmless re-reads of the last tile
+    const ah_rsrc_t rsrcK = ah_rsrc(qkv, im.off + d, qkv_bytes), rsrcV = ah_rsrc(qkv, im.off + 2 * d, qkv_bytes);
+    int voff[G::PW], voff_l[G::PW];
+    ah_piece_table<G, false>(voff, wave, lane, ld);
+    ah_piece_table<G, !G::POW2>(voff_l, wave, lane, ld, S - 1 - 32 * (ntiles - 1));
     int ld_kt = 0;
     auto issue = [&](int stage) {
-        const int so = (int)((long)ld_kt * 32 * ld * 2);
-        const bool last = !POW2 && ld_kt == ntiles - 1;               // wave-uniform
-        char* sb = smem + stage * STAGE_BYTES;
-#pragma unroll
-        for (int i = 0; i < PW; ++i) {
-            int piece = wave + 8 * i;
-            piece = piece < P ? piece : P - 1;                        // surplus issues (head_dim 32, 96) re-write the last piece
-            const int vo = last ? voff_l[i] : voff[i];
-            if (piece < T_P)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcK, (lds_ptr_t)(sb + piece * 1024), 16, vo, so, 0, 0);
-            else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcV, (lds_ptr_t)(sb + T_BYTES + (piece - T_P) * 1024), 16, vo, so, 0, 0);
-        }
-        ld_kt = ld_kt + 1 < ntiles ? ld_kt + 1 : ntiles - 1;          // past the end: harmless re-reads of the last tile
+        ah_issue<G>(rsrcK, rsrcV, smem + stage * G::STAGE_BYTES, voff, voff_l, !G::POW2 && ld_kt == ntiles - 1,
+                    (int)((long)ld_kt * 32 * ld * 2), wave);
+        ld_kt = ld_kt + 1 < ntiles ? ld_kt + 1 : ntiles - 1;
     };
 
-    f32x4 o[NNB];
+    f32x4 o[1][G::NNB];
 #pragma unroll
-    for (int nb = 0; nb < NNB; ++nb) o[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.0f;
-    const int kbase = l15 * ROWB + ((lq ^ fswz(l15)) << 4);
-    const int vrow = 4 * lq + (l15 >> 2);
-    const int vbase = T_BYTES + vrow * ROWB + ((fswz(vrow) >> 1) << 5) + (l15 & 3) * 8;
-    // rows of 12 / 24 chunks do not start on a 256-byte boundary, so there the swizzle cannot be folded into kbase / vbase and
-    // the k-step / column block XORed on top: the chunk (32-byte block) index is formed first, then added to the row
-    const int krow_b = l15 * ROWB, kfz = fswz(l15);
-    const int vrow_b = T_BYTES + vrow * ROWB + (l15 & 3) * 8, vfz = fswz(vrow) >> 1;
+    for (int nb = 0; nb < G::NNB; ++nb) o[0][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run[1] = {-INFINITY}, l_run[1] = {0.0f};
+    const AhFrag<G> fr(l15, lq);
+    AhStamps<false> st;
 
 #pragma unroll
-    for (int s = 0; s < NST - 1; ++s) issue(s);
-    ah_wait_vm<(NST - 2) * PW>();                                     // this wave's pieces of tile 0
+    for (int s = 0; s < G::NST - 1; ++s) issue(s);
+    wait_vm<G::VM_TILE>();                                            // this wave's pieces of tile 0
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    int stage = 0, wst = NST - 1;
+    int stage = 0, wst = G::NST - 1;
     for (int kt = 0; kt < ntiles; ++kt) {
-        const char* St = smem + stage * STAGE_BYTES;
+        const char* St = smem + stage * G::STAGE_BYTES;
         issue(wst);                                                   // tile kt+NST-1 -> the stage freed by the last barrier
-        wst = wst == NST - 1 ? 0 : wst + 1;
-        if (mine) {
-            f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
-            constexpr int NR = 2 * NKS, PD = NR < 4 ? NR - 1 : 3;
-            auto kread = [&](int r) {
-                if constexpr (POW2)
-                    return *reinterpret_cast<const f16x8*>(St + ((kbase + (r / NKS) * 16 * ROWB) ^ ((r % NKS) << 6)));
-                else
-                    return *reinterpret_cast<const f16x8*>(St + krow_b + (r / NKS) * 16 * ROWB + (((lq + 4 * (r % NKS)) ^ kfz) << 4));
-            };
-            f16x8 kring[PD + 1];
-#pragma unroll
-            for (int r = 0; r < PD; ++r) kring[r] = kread(r);
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                if (r + PD < NR) kring[(r + PD) % (PD + 1)] = kread(r + PD);
-                if (r < NKS) s0 = GDX_MFMA16(kring[r % (PD + 1)], qf[r % NKS], s0, 0, 0, 0);
-                else s1 = GDX_MFMA16(kring[r % (PD + 1)], qf[r % NKS], s1, 0, 0, 0);
-            }
-            constexpr int VD = NNB < 4 ? NNB - 1 : 3;
-            auto vread = [&](int nb, int half) {
-                if constexpr (POW2) return lds_read_tr(St + ((vbase + half * 16 * ROWB) ^ (nb << 5)));
-                else return lds_read_tr(St + vrow_b + half * 16 * ROWB + ((nb ^ vfz) << 5));
-            };
-            f16x4 vring[VD + 1][2];
-#pragma unroll
-            for (int nb = 0; nb < VD; ++nb) {
-                vring[nb][0] = vread(nb, 0);
-                vring[nb][1] = vread(nb, 1);
-            }
-            float v[8];
-            // raw scores; the scale (log2 e / sqrt(hd) > 0) is applied inside the exp2 argument (one fma per element)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = s0[e];
-                v[4 + e] = s1[e];
-            }
-            if (kt * 32 + 32 > S) {                                   // block-uniform: only the last tile masks
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (kt * 32 + (j >> 2) * 16 + 4 * lq + (j & 3) >= S) v[j] = -INFINITY;
-            }
-            float mx = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7]))) * c_log2;
-            if (__any(mx > m_run + RESCALE_THR)) {
-                mx = fmaxf(mx, __shfl_xor(mx, 16));
-                mx = fmaxf(mx, __shfl_xor(mx, 32));
-                const float m_new = fmaxf(m_run, mx);
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-                l_run *= alpha;
-#pragma unroll
-                for (int nb = 0; nb < NNB; ++nb) o[nb] *= alpha;
-                m_run = m_new;
-            }
-            float psum = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                v[j] = __builtin_amdgcn_exp2f(fmaf(v[j], c_log2, -m_run));
-                psum += v[j];
-            }
-            l_run += psum;
-            const f16x8 pf = f16x8{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3],
-                                   (half_t)v[4], (half_t)v[5], (half_t)v[6], (half_t)v[7]};
-#pragma unroll
-            for (int nb = 0; nb < NNB; ++nb) {
-                if (nb + VD < NNB) {
-                    vring[(nb + VD) % (VD + 1)][0] = vread(nb + VD, 0);
-                    vring[(nb + VD) % (VD + 1)][1] = vread(nb + VD, 1);
-                }
-                const f16x4 v0 = vring[nb % (VD + 1)][0], v1 = vring[nb % (VD + 1)][1];
-                const f16x8 vf = f16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                o[nb] = GDX_MFMA16(vf, pf, o[nb], 0, 0, 0);
-            }
-        }
-        ah_wait_vm<(NST - 2) * PW>();                                 // this wave's pieces of tile kt+1
-        __builtin_amdgcn_s_waitcnt(0xc07f);                           // lgkmcnt(0): fragment reads of this tile done
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        stage = stage == NST - 1 ? 0 : stage + 1;
+        if (mine) ah_tile<G, 1, 1>(fr, St, qf, kt, S, c_log2, m_run, l_run, o, st);
+        ah_handover<G>(stage, wst);
     }
-    ah_wait_vm<0>();
+    wait_vm<0>();
     if (mine) {
-        float l_tot = l_run;
-        l_tot += __shfl_xor(l_tot, 16);
-        l_tot += __shfl_xor(l_tot, 32);
-        const float inv = 1.0f / l_tot;
-        const int q = 16 * (qb_lo + wave) + l15;
+        const float inv = ah_inv_l(l_run[0]);
+        const int q = 16 * (im.qb_lo + wave) + l15;
         if (q < S) {
-            _Float16* op = ctx + ((long)b * S + q) * d + h * HD + 4 * lq;
+            _Float16* op = ctx + ((long)im.b * S + q) * d + im.h * HD + 4 * lq;
 #pragma unroll
-            for (int nb = 0; nb < NNB; ++nb) {
-                const f32x4 r = o[nb] * inv;
+            for (int nb = 0; nb < G::NNB; ++nb) {
+                const f32x4 r = o[0][nb] * inv;
                 *reinterpret_cast<f16x4*>(op + 16 * nb) = f16x4{(half_t)r[0], (half_t)r[1], (half_t)r[2], (half_t)r[3]};
             }
         }
@@ -295,241 +477,82 @@ __global__ __launch_bounds__(512, 1) void attentionh8_kernel(const _Float16* __r
 
 // ---------------------------------------------------------------------------------------------------------------
 // Eight compute waves x QB = 2 query blocks each (256 queries per workgroup): the K/V fragments are shared by a wave's
-// two blocks as in the 4 + 4 kernel, every K/V tile is staged once for twice as many queries, and the two waves of a
-// SIMD cover each other's softmax / latency as in the kernel above.  The query blocks of a chunk go to the waves
-// round-robin (block qb_lo + w + 8 qi), so the two waves of a SIMD (w, w + 4) hold 4, 3 or 2 blocks between them.
+// two blocks, every K/V tile is staged once for twice as many queries, and the two waves of a SIMD cover each other's
+// softmax / latency as in the kernel above.  The query blocks of a chunk go to the waves round-robin (block
+// qb_lo + w + 8 qi), so the two waves of a SIMD (w, w + 4) hold 4, 3 or 2 blocks between them.
 template <int HD, int QB>
 __global__ __launch_bounds__(512, 1) void attentionh8q_kernel(const _Float16* __restrict__ qkv, _Float16* __restrict__ ctx,
                                                               int S, int H, int d, int nchunk, float c_log2,
                                                               long qkv_bytes) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int ROWB = HD * 2, CPR = ROWB / 16, T_BYTES = 32 * ROWB, STAGE_BYTES = 2 * T_BYTES;
-    constexpr int T_P = T_BYTES / 1024, P = 2 * T_P, PW = (P + 7) / 8;
-    constexpr int NST = 3;
-    constexpr int NKS = HD / 32, NNB = HD / 16;
-    static_assert((HD & (HD - 1)) == 0, "whole rows per 1 KiB piece and XOR-composed fragment addresses: power-of-two head_dim only");
-    constexpr float RESCALE_THR = 8.0f;
+    using G = AhGeom2<HD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
-    const int wg = ah_xcd_lid((int)blockIdx.x, (int)gridDim.x);
-    const int ci = wg % nchunk;
-    const int h = (wg / nchunk) % H, b = wg / (nchunk * H);
     const long ld = 3L * d;
-    const long base_off = (long)b * S * ld + h * HD;
-    const _Float16* base = qkv + base_off;
-    const int nqb = (S + 15) / 16;
-    const int qb_lo = (int)((long)ci * nqb / nchunk), qb_hi = (int)((long)(ci + 1) * nqb / nchunk);
+    const AhItem im = ah_item<false>(xcd_lid((int)blockIdx.x, (int)gridDim.x), nchunk, H, S, ld, HD);
     const int ntiles = (S + 31) / 32;
-    const int nblk = qb_hi - qb_lo;                                   // <= 8 * QB
-    const int mine = wave < nblk ? min((nblk - wave + 7) / 8, QB) : 0;   // blocks qb_lo + wave + 8*qi
-    auto fswz = [](int row) { return HD == 32 ? ((row >> 2) & 1) << 1 : HD == 64 ? ((row >> 1) & 3) << 1 : (row & 7) << 1; };
+    const int mine = ah_my_blocks<QB>(im.nblk, wave);
 
-    // Q fragments and output blocks travel as WHOLE ROWS through the wave's own 16-row slice of LDS (behind the K/V ring).
-    // Loaded straight into the fragment layout a Q load instruction takes 64 bytes from each of 16 rows, and an output store puts
-    // 32 bytes into each of 16 rows: 6 144 partial-line requests per workgroup and item, which the CU's address unit serves at
-    // about two cycles each -- round-3 stamps: 6-10 k cycles to ISSUE a wave's 16 Q loads and 5.9 k for its 32 stores, ~13 us per
-    // item outside the tile loop.  A query block is 16 rows of ROWB bytes, exactly a 16-key K block: staged by LDS-DMA with K's
-    // chunk swizzle it is read back with K's fragment read; an output block is written to the slice in the accumulator layout
-    // (chunk-swizzled by row) and leaves as 16-byte pieces of whole rows.
-    constexpr int RPP = 1024 / ROWB;                                    // rows per 1 KiB piece (16 at head_dim 32)
-    constexpr int NPQ = 16 / RPP;                                       // pieces per 16-row block
-    char* sl = smem + NST * STAGE_BYTES + wave * (16 * ROWB);
-    const int kbase = l15 * ROWB + ((lq ^ fswz(l15)) << 4);
-    const auto rsrcQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), (short)0, ah_records(qkv_bytes - base_off * 2), 0x00020000);
-    // rows past S repeat row S - 1 (as in attentionh8_kernel): a query that is never stored still takes part in the block's
-    // rescale vote, so it must not come from the next sample or the pad -- or a sample's bits would depend on its neighbours
-    auto dma_q = [&](int qi) {
-        const int q0 = 16 * (qb_lo + wave + 8 * qi);
+    char* sl = smem + G::RING_BYTES + wave * G::SLICE_BYTES;
+    const AhFrag<G> fr(l15, lq);
+    const ah_rsrc_t rsrcQ = ah_rsrc(qkv, im.off, qkv_bytes);
+    auto dma_q = [&](int qi) { ah_q_dma<G>(rsrcQ, sl, 16 * (im.qb_lo + wave + 8 * qi), S, ld, lane); };
+    f16x8 qf[QB][G::NKS];
 #pragma unroll
-        for (int j = 0; j < NPQ; ++j) {
-            const int row = j * RPP + lane / CPR;
-            const int vo = (int)(min(q0 + row, S - 1) * ld * 2) + (((lane % CPR) ^ fswz(row)) * 16);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcQ, (lds_ptr_t)(sl + j * 1024), 16, vo, 0, 0, 0);
-        }
-    };
-    f16x8 qf[QB][NKS];
-    auto read_q = [&](int qi) {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) qf[qi][ks] = *reinterpret_cast<const f16x8*>(sl + (kbase ^ (ks << 6)));
-    };
-#pragma unroll
-    for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) qf[qi][ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    for (int qi = 0; qi < QB; ++qi) ah_q_zero<G>(qf[qi]);
     if (mine > 0) dma_q(0);                                             // block 0 travels with the ring fill below
 
-    const long kb_off = (base_off + d) * 2, vb_off = (base_off + 2 * d) * 2;
-    const auto rsrcK = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + d), (short)0, ah_records(qkv_bytes - kb_off), 0x00020000);
-    const auto rsrcV = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + 2 * d), (short)0, ah_records(qkv_bytes - vb_off), 0x00020000);
-    int voff[PW];
-#pragma unroll
-    for (int i = 0; i < PW; ++i) {
-        int piece = wave + 8 * i;
-        piece = piece < P ? piece : P - 1;
-        const int pl = piece < T_P ? piece : piece - T_P;
-        const int row = pl * (1024 / ROWB) + lane / CPR;
-        voff[i] = (int)(row * ld * 2) + (((lane % CPR) ^ fswz(row)) * 16);
-    }
+    // ---- the K/V stream: past the end, harmless re-reads of the last tile
+    const ah_rsrc_t rsrcK = ah_rsrc(qkv, im.off + d, qkv_bytes), rsrcV = ah_rsrc(qkv, im.off + 2 * d, qkv_bytes);
+    int voff[G::PW];
+    ah_piece_table<G, false>(voff, wave, lane, ld);
     int ld_kt = 0;
     auto issue = [&](int stage) {
-        const int so = (int)((long)ld_kt * 32 * ld * 2);
-        char* sb = smem + stage * STAGE_BYTES;
-#pragma unroll
-        for (int i = 0; i < PW; ++i) {
-            int piece = wave + 8 * i;
-            piece = piece < P ? piece : P - 1;
-            if (piece < T_P)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcK, (lds_ptr_t)(sb + piece * 1024), 16, voff[i], so, 0, 0);
-            else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcV, (lds_ptr_t)(sb + T_BYTES + (piece - T_P) * 1024), 16, voff[i], so, 0, 0);
-        }
+        ah_issue<G>(rsrcK, rsrcV, smem + stage * G::STAGE_BYTES, voff, voff, false, (int)((long)ld_kt * 32 * ld * 2), wave);
         ld_kt = ld_kt + 1 < ntiles ? ld_kt + 1 : ntiles - 1;
     };
 
-    f32x4 o[QB][NNB];
+    f32x4 o[QB][G::NNB];
     float m_run[QB], l_run[QB];
 #pragma unroll
     for (int qi = 0; qi < QB; ++qi) {
 #pragma unroll
-        for (int nb = 0; nb < NNB; ++nb) o[qi][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int nb = 0; nb < G::NNB; ++nb) o[qi][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
         m_run[qi] = -INFINITY;
         l_run[qi] = 0.0f;
     }
-    const int vrow = 4 * lq + (l15 >> 2);
-    const int vbase = T_BYTES + vrow * ROWB + ((fswz(vrow) >> 1) << 5) + (l15 & 3) * 8;
+    AhStamps<false> st;
 
 #pragma unroll
-    for (int s = 0; s < NST - 1; ++s) issue(s);
-    ah_wait_vm<0>();
-    if (mine > 0) read_q(0);
+    for (int s = 0; s < G::NST - 1; ++s) issue(s);
+    wait_vm<0>();
+    if (mine > 0) ah_q_read<G>(fr, sl, qf[0]);
     if (mine > 1) {                                                     // the slice is reused once block 0 is in registers
         __builtin_amdgcn_s_waitcnt(0xc07f);
         asm volatile("" ::: "memory");
         dma_q(1);
-        ah_wait_vm<0>();
-        read_q(1);
+        wait_vm<0>();
+        ah_q_read<G>(fr, sl, qf[1]);
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    int stage = 0, wst = NST - 1;
+    int stage = 0, wst = G::NST - 1;
     auto run_tiles = [&](auto nq_tag) {
-        constexpr int NQ = decltype(nq_tag)::value;
         for (int kt = 0; kt < ntiles; ++kt) {
-            const char* St = smem + stage * STAGE_BYTES;
+            const char* St = smem + stage * G::STAGE_BYTES;
             issue(wst);
-            wst = wst == NST - 1 ? 0 : wst + 1;
-            if constexpr (NQ > 0) {
-                f32x4 s[QB][2];
-#pragma unroll
-                for (int qi = 0; qi < QB; ++qi) s[qi][0] = s[qi][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-                constexpr int NR = 2 * NKS, PD = NR < 4 ? NR - 1 : 3;
-                auto kread = [&](int r) {
-                    return *reinterpret_cast<const f16x8*>(St + ((kbase + (r / NKS) * 16 * ROWB) ^ ((r % NKS) << 6)));
-                };
-                f16x8 kring[PD + 1];
-#pragma unroll
-                for (int r = 0; r < PD; ++r) kring[r] = kread(r);
-#pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    if (r + PD < NR) kring[(r + PD) % (PD + 1)] = kread(r + PD);
-#pragma unroll
-                    for (int qi = 0; qi < NQ; ++qi)
-                        s[qi][r / NKS] = GDX_MFMA16(kring[r % (PD + 1)], qf[qi][r % NKS], s[qi][r / NKS], 0, 0, 0);
-                }
-                constexpr int VD = NNB < 4 ? NNB - 1 : 3;
-                auto vread = [&](int nb, int half) { return lds_read_tr(St + ((vbase + half * 16 * ROWB) ^ (nb << 5))); };
-                f16x4 vring[VD + 1][2];
-#pragma unroll
-                for (int nb = 0; nb < VD; ++nb) {
-                    vring[nb][0] = vread(nb, 0);
-                    vring[nb][1] = vread(nb, 1);
-                }
-                f16x8 pf[QB];
-                const bool tail = kt * 32 + 32 > S;
-#pragma unroll
-                for (int qi = 0; qi < NQ; ++qi) {
-                    float v[8];
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[kb * 4 + e] = s[qi][kb][e];
-                    if (tail) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j)
-                            if (kt * 32 + (j >> 2) * 16 + 4 * lq + (j & 3) >= S) v[j] = -INFINITY;
-                    }
-                    float mx = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7]))) * c_log2;
-                    if (__any(mx > m_run[qi] + RESCALE_THR)) {
-                        mx = fmaxf(mx, __shfl_xor(mx, 16));
-                        mx = fmaxf(mx, __shfl_xor(mx, 32));
-                        const float m_new = fmaxf(m_run[qi], mx);
-                        const float alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new);
-                        l_run[qi] *= alpha;
-#pragma unroll
-                        for (int nb = 0; nb < NNB; ++nb) o[qi][nb] *= alpha;
-                        m_run[qi] = m_new;
-                    }
-                    float psum = 0.0f;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        v[j] = __builtin_amdgcn_exp2f(fmaf(v[j], c_log2, -m_run[qi]));
-                        psum += v[j];
-                    }
-                    l_run[qi] += psum;
-                    pf[qi] = f16x8{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3],
-                                   (half_t)v[4], (half_t)v[5], (half_t)v[6], (half_t)v[7]};
-                }
-#pragma unroll
-                for (int nb = 0; nb < NNB; ++nb) {
-                    if (nb + VD < NNB) {
-                        vring[(nb + VD) % (VD + 1)][0] = vread(nb + VD, 0);
-                        vring[(nb + VD) % (VD + 1)][1] = vread(nb + VD, 1);
-                    }
-                    const f16x4 v0 = vring[nb % (VD + 1)][0], v1 = vring[nb % (VD + 1)][1];
-                    const f16x8 vf = f16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#pragma unroll
-                    for (int qi = 0; qi < NQ; ++qi)
-                        o[qi][nb] = GDX_MFMA16(vf, pf[qi], o[qi][nb], 0, 0, 0);
-                }
-            }
-            ah_wait_vm<(NST - 2) * PW>();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            stage = stage == NST - 1 ? 0 : stage + 1;
+            ah_tile<G, QB, decltype(nq_tag)::value>(fr, St, qf, kt, S, c_log2, m_run, l_run, o, st);
+            ah_handover<G>(stage, wst);
         }
     };
     if (mine == 2) run_tiles(std::integral_constant<int, 2>{});
     else if (mine == 1) run_tiles(std::integral_constant<int, 1>{});
     else run_tiles(std::integral_constant<int, 0>{});
-    ah_wait_vm<0>();
-    // output: a lane holds columns 16 nb + 4 lq .. + 3 of query l15; through the slice (16-byte chunk c of row r at c ^ (r mod
-    // chunks-per-row, at most 16): the sixteen rows of a column land in sixteen different bank groups) and out as whole rows
-    constexpr int GM = CPR < 16 ? CPR - 1 : 15;
-#pragma unroll
-    for (int qi = 0; qi < QB; ++qi) {
-        if (qi >= mine) continue;
-        float l_tot = l_run[qi];
-        l_tot += __shfl_xor(l_tot, 16);
-        l_tot += __shfl_xor(l_tot, 32);
-        const float inv = 1.0f / l_tot;
-#pragma unroll
-        for (int nb = 0; nb < NNB; ++nb) {
-            const f32x4 r = o[qi][nb] * inv;
-            *reinterpret_cast<f16x4*>(sl + l15 * ROWB + (((2 * nb + (lq >> 1)) ^ (l15 & GM)) << 4) + (lq & 1) * 8) =
-                f16x4{(half_t)r[0], (half_t)r[1], (half_t)r[2], (half_t)r[3]};
-        }
-        const int q0 = 16 * (qb_lo + wave + 8 * qi);
-#pragma unroll
-        for (int j = 0; j < NPQ; ++j) {
-            const int row = j * RPP + lane / CPR, c = lane % CPR;
-            const f16x8 v = *reinterpret_cast<const f16x8*>(sl + row * ROWB + ((c ^ (row & GM)) << 4));
-            if (q0 + row < S) *reinterpret_cast<f16x8*>(ctx + ((long)b * S + q0 + row) * d + h * HD + 8 * c) = v;
-        }
-    }
+    wait_vm<0>();
+    ah_store_rows<G, QB>(o, l_run, mine, sl, lane, ctx, im.b, im.h, im.qb_lo + wave, S, d);
 #endif
 }
 
@@ -541,245 +564,106 @@ __global__ __launch_bounds__(512, 1) void attentionh8q_kernel(const _Float16* __
 // tiles are being multiplied (the ring and its stage counters never restart), and the output stores of an item drain under
 // the next item's first tiles.  The counted vmcnt waits stay valid with the extra Q loads / stores in the queue: memory
 // operations retire in order, so "all but the youngest N" can only cover MORE than the tile it is meant to cover.  Per item
-// the arithmetic is the kernel above's, statement for statement (same tile order, same online-softmax state): bit-identical.
+// the arithmetic is the kernel above's -- the same ah_tile in the same tile order on the same online-softmax state: bit-identical.
 template <int HD, int QB, bool DBG>
 __global__ __launch_bounds__(512, 1) void attentionh8p_kernel(const _Float16* __restrict__ qkv, _Float16* __restrict__ ctx,
                                                               int S, int H, int d, int nchunk, int nitems, float c_log2,
                                                               long qkv_bytes, unsigned long long* dbg) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int ROWB = HD * 2, CPR = ROWB / 16, T_BYTES = 32 * ROWB, STAGE_BYTES = 2 * T_BYTES;
-    constexpr int T_P = T_BYTES / 1024, P = 2 * T_P, PW = (P + 7) / 8;
-    constexpr int NST = 3;
-    constexpr int NKS = HD / 32, NNB = HD / 16;
-    static_assert((HD & (HD - 1)) == 0, "whole rows per 1 KiB piece and XOR-composed fragment addresses: power-of-two head_dim only");
-    constexpr float RESCALE_THR = 8.0f;
+    using G = AhGeom2<HD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
     const long ld = 3L * d;
-    const int nqb = (S + 15) / 16;
     const int ntiles = (S + 31) / 32;
-    const int G = gridDim.x;
-    const int lid = ah_xcd_lid((int)blockIdx.x, G);
-    const int my_items = lid < nitems ? (nitems - lid + G - 1) / G : 0;
+    const int NG = gridDim.x;
+    const int lid = xcd_lid((int)blockIdx.x, NG);
+    const int my_items = lid < nitems ? (nitems - lid + NG - 1) / NG : 0;
     if (my_items == 0) return;
-    auto fswz = [](int row) { return HD == 32 ? ((row >> 2) & 1) << 1 : HD == 64 ? ((row >> 1) & 3) << 1 : (row & 7) << 1; };
     // item i of this workgroup -> element offset of its (sample, head) inside qkv
-    auto item_off = [&](int i) -> long {
-        const int w = lid + (i < my_items ? i : my_items - 1) * G;    // past the end: harmless re-reads of the last item
-        const int hh = (w / nchunk) % H, bb = w / (nchunk * H);
-        return (long)bb * S * ld + hh * HD;
+    auto item_off = [&](int i) -> long {                              // past the end: harmless re-reads of the last item
+        return ah_item<false>(lid + (i < my_items ? i : my_items - 1) * NG, nchunk, H, S, ld, HD).off;
     };
 
     // ---- the K/V stream: tile ld_kt of stream item ld_it goes to ring stage wst; it runs NST - 1 tiles ahead of the MFMAs
-    int voff[PW];
-#pragma unroll
-    for (int i = 0; i < PW; ++i) {
-        int piece = wave + 8 * i;
-        piece = piece < P ? piece : P - 1;
-        const int pl = piece < T_P ? piece : piece - T_P;
-        const int row = pl * (1024 / ROWB) + lane / CPR;
-        voff[i] = (int)(row * ld * 2) + (((lane % CPR) ^ fswz(row)) * 16);
-    }
+    int voff[G::PW];
+    ah_piece_table<G, false>(voff, wave, lane, ld);
     int ld_it = 0, ld_kt = 0;
     long st_off = item_off(0);
     auto issue = [&](int stage) {
-        const long kb_off = (st_off + d) * 2, vb_off = (st_off + 2 * d) * 2;
-        const auto rsrcK = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(qkv + st_off + d), (short)0, ah_records(qkv_bytes - kb_off), 0x00020000);
-        const auto rsrcV = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(qkv + st_off + 2 * d), (short)0, ah_records(qkv_bytes - vb_off), 0x00020000);
-        const int so = (int)((long)ld_kt * 32 * ld * 2);
-        char* sb = smem + stage * STAGE_BYTES;
-#pragma unroll
-        for (int i = 0; i < PW; ++i) {
-            int piece = wave + 8 * i;
-            piece = piece < P ? piece : P - 1;
-            if (piece < T_P)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcK, (lds_ptr_t)(sb + piece * 1024), 16, voff[i], so, 0, 0);
-            else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcV, (lds_ptr_t)(sb + T_BYTES + (piece - T_P) * 1024), 16, voff[i], so, 0, 0);
-        }
+        ah_issue<G>(ah_rsrc(qkv, st_off + d, qkv_bytes), ah_rsrc(qkv, st_off + 2 * d, qkv_bytes), smem + stage * G::STAGE_BYTES, voff,
+                    voff, false, (int)((long)ld_kt * 32 * ld * 2), wave);
         if (++ld_kt == ntiles) {                                      // on into the next item's tiles
             ld_kt = 0;
             ++ld_it;
             st_off = item_off(ld_it);
         }
     };
-    const int kbase = l15 * ROWB + ((lq ^ fswz(l15)) << 4);
-    const int vrow = 4 * lq + (l15 >> 2);
-    const int vbase = T_BYTES + vrow * ROWB + ((fswz(vrow) >> 1) << 5) + (l15 & 3) * 8;
+    const AhFrag<G> fr(l15, lq);
 
-    // Q fragments and output blocks travel as whole rows through the wave's 16-row slice of LDS (see attentionh8q_kernel).  Item
+    // Q fragments and output blocks travel as whole rows through the wave's 16-row slice of LDS (see ah_q_dma).  Item
     // i + 1's fragments are fetched at the END of item i, once its accumulators are packed to 16 bits, and IN FRONT of its output
     // stores: vector-memory operations retire in order, and nothing should have to wait for a store's acknowledgement.
-    constexpr int RPP = 1024 / ROWB, NPQ = 16 / RPP, GM = CPR < 16 ? CPR - 1 : 15;
-    char* sl = smem + NST * STAGE_BYTES + wave * (16 * ROWB);
-    f16x8 qf[QB][NKS];
-    auto item_geom = [&](int i, long& off, int& qb_lo, int& mine, int& b, int& h) {
-        // (integer division runs on the vector ALU: without the readfirstlanes these wave-uniform results sit in vector registers
-        //  through the whole tile loop, which has none to spare)
-        const int w = lid + i * G;
-        const int ci = __builtin_amdgcn_readfirstlane(w % nchunk);
-        h = __builtin_amdgcn_readfirstlane((w / nchunk) % H);
-        b = __builtin_amdgcn_readfirstlane(w / (nchunk * H));
-        off = (long)b * S * ld + h * HD;
-        qb_lo = __builtin_amdgcn_readfirstlane((int)((long)ci * nqb / nchunk));
-        const int nblk = __builtin_amdgcn_readfirstlane((int)((long)(ci + 1) * nqb / nchunk)) - qb_lo;   // <= 8 * QB
-        mine = wave < nblk ? min((nblk - wave + 7) / 8, QB) : 0;         // blocks qb_lo + wave + 8*qi
-    };
+    char* sl = smem + G::RING_BYTES + wave * G::SLICE_BYTES;
+    f16x8 qf[QB][G::NKS];
     auto load_q = [&](int i) {
-        long off;
-        int qb_lo, mine, b, h;
-        item_geom(i, off, qb_lo, mine, b, h);
-        const auto rsrcQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(qkv + off), (short)0, ah_records(qkv_bytes - off * 2), 0x00020000);
+        const AhItem im = ah_item<true>(lid + i * NG, nchunk, H, S, ld, HD);
+        const int mine = ah_my_blocks<QB>(im.nblk, wave);
+        const ah_rsrc_t rsrcQ = ah_rsrc(qkv, im.off, qkv_bytes);
         int ln = lane;                                                  // laundered: per-lane address arithmetic derived from it stays
         asm volatile("" : "+v"(ln));                                    // here instead of being hoisted out of the item loop (and spilled)
-        const int kb2 = (ln & 15) * ROWB + (((ln >> 4) ^ fswz(ln & 15)) << 4);
+        const AhFrag<G> frq(ln & 15, ln >> 4);
 #pragma unroll
         for (int qi = 0; qi < QB; ++qi) {
             if (qi >= mine) {                                           // wave-uniform.  (Every fragment register is written on every
-#pragma unroll                                                          //  path: a conditionally kept one stays live through the
-                for (int ks = 0; ks < NKS; ++ks) qf[qi][ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};   // epilogue, beside O and its packed copy: spills)
-                continue;
+                ah_q_zero<G>(qf[qi]);                                   //  path: a conditionally kept one stays live through the
+                continue;                                               //  epilogue, beside O and its packed copy: spills)
             }
-            const int q0 = 16 * (qb_lo + wave + 8 * qi);
             __builtin_amdgcn_s_waitcnt(0xc07f);                          // the slice's previous reads
             asm volatile("" ::: "memory");
-#pragma unroll
-            for (int j = 0; j < NPQ; ++j) {
-                const int row = j * RPP + ln / CPR;                      // rows past S repeat row S - 1 (see attentionh8q_kernel)
-                const int vo = (int)(min(q0 + row, S - 1) * ld * 2) + (((ln % CPR) ^ fswz(row)) * 16);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcQ, (lds_ptr_t)(sl + j * 1024), 16, vo, 0, 0, 0);
-            }
-            ah_wait_vm<0>();
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) qf[qi][ks] = *reinterpret_cast<const f16x8*>(sl + (kb2 ^ (ks << 6)));
+            ah_q_dma<G>(rsrcQ, sl, 16 * (im.qb_lo + wave + 8 * qi), S, ld, ln);
+            wait_vm<0>();
+            ah_q_read<G>(frq, sl, qf[qi]);
         }
     };
 #pragma unroll
-    for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) qf[qi][ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    for (int qi = 0; qi < QB; ++qi) ah_q_zero<G>(qf[qi]);
 
 #pragma unroll
-    for (int s = 0; s < NST - 1; ++s) issue(s);
+    for (int s = 0; s < G::NST - 1; ++s) issue(s);
     load_q(0);
-    ah_wait_vm<0>();
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    int stage = 0, wst = NST - 1;
-    // diagnostic stamps (GDX_GEMM_DEBUG only; waves 0 and 7 of workgroup 0): cycles per tile spent issuing the DMA pieces, in
-    // QK^T, in the softmax, in PV and in the wait + barrier
-    unsigned long long d_is = 0, d_qk = 0, d_sm = 0, d_pv = 0, d_bar = 0, n_t = 0, t_a = 0, t_b = 0;
+    int stage = 0, wst = G::NST - 1;
+    AhStamps<DBG> st;                                                 // (waves 0 and 7 of workgroup 0 report)
     const unsigned long long tk0 = DBG ? __builtin_amdgcn_s_memtime() : 0, tr0 = DBG ? __builtin_amdgcn_s_memrealtime() : 0;
 
     for (int it = 0; it < my_items; ++it) {
-        long base_off;
-        int qb_lo, mine, b, h;
-        item_geom(it, base_off, qb_lo, mine, b, h);
+        const AhItem im = ah_item<true>(lid + it * NG, nchunk, H, S, ld, HD);
+        const int mine = ah_my_blocks<QB>(im.nblk, wave);
 
-        f32x4 o[QB][NNB];
+        f32x4 o[QB][G::NNB];
         float m_run[QB], l_run[QB];
 #pragma unroll
         for (int qi = 0; qi < QB; ++qi) {
 #pragma unroll
-            for (int nb = 0; nb < NNB; ++nb) o[qi][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int nb = 0; nb < G::NNB; ++nb) o[qi][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
             m_run[qi] = -INFINITY;
             l_run[qi] = 0.0f;
         }
         auto run_tiles = [&](auto nq_tag) {
-            constexpr int NQ = decltype(nq_tag)::value;
             for (int kt = 0; kt < ntiles; ++kt) {
-                const char* St = smem + stage * STAGE_BYTES;
-                if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); t_a = __builtin_amdgcn_s_memtime(); }
+                const char* St = smem + stage * G::STAGE_BYTES;
+                st.start();
                 issue(wst);
-                wst = wst == NST - 1 ? 0 : wst + 1;
-                if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); t_b = __builtin_amdgcn_s_memtime(); d_is += t_b - t_a; t_a = t_b; }
-                if constexpr (NQ > 0) {
-                    f32x4 s[QB][2];
-#pragma unroll
-                    for (int qi = 0; qi < QB; ++qi) s[qi][0] = s[qi][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    constexpr int NR = 2 * NKS, PD = NR < 4 ? NR - 1 : 3;
-                    auto kread = [&](int r) {
-                        return *reinterpret_cast<const f16x8*>(St + ((kbase + (r / NKS) * 16 * ROWB) ^ ((r % NKS) << 6)));
-                    };
-                    f16x8 kring[PD + 1];
-#pragma unroll
-                    for (int r = 0; r < PD; ++r) kring[r] = kread(r);
-#pragma unroll
-                    for (int r = 0; r < NR; ++r) {
-                        if (r + PD < NR) kring[(r + PD) % (PD + 1)] = kread(r + PD);
-#pragma unroll
-                        for (int qi = 0; qi < NQ; ++qi)
-                            s[qi][r / NKS] = GDX_MFMA16(kring[r % (PD + 1)], qf[qi][r % NKS], s[qi][r / NKS], 0, 0, 0);
-                    }
-                    if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); t_b = __builtin_amdgcn_s_memtime(); d_qk += t_b - t_a; t_a = t_b; }
-                    constexpr int VD = NNB < 4 ? NNB - 1 : 3;
-                    auto vread = [&](int nb, int half) { return lds_read_tr(St + ((vbase + half * 16 * ROWB) ^ (nb << 5))); };
-                    f16x4 vring[VD + 1][2];
-#pragma unroll
-                    for (int nb = 0; nb < VD; ++nb) {
-                        vring[nb][0] = vread(nb, 0);
-                        vring[nb][1] = vread(nb, 1);
-                    }
-                    f16x8 pf[QB];
-                    const bool tail = kt * 32 + 32 > S;
-#pragma unroll
-                    for (int qi = 0; qi < NQ; ++qi) {
-                        float v[8];
-#pragma unroll
-                        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[kb * 4 + e] = s[qi][kb][e];
-                        if (tail) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j)
-                                if (kt * 32 + (j >> 2) * 16 + 4 * lq + (j & 3) >= S) v[j] = -INFINITY;
-                        }
-                        float mx = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7]))) * c_log2;
-                        if (__any(mx > m_run[qi] + RESCALE_THR)) {
-                            mx = fmaxf(mx, __shfl_xor(mx, 16));
-                            mx = fmaxf(mx, __shfl_xor(mx, 32));
-                            const float m_new = fmaxf(m_run[qi], mx);
-                            const float alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new);
-                            l_run[qi] *= alpha;
-#pragma unroll
-                            for (int nb = 0; nb < NNB; ++nb) o[qi][nb] *= alpha;
-                            m_run[qi] = m_new;
-                        }
-                        float psum = 0.0f;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            v[j] = __builtin_amdgcn_exp2f(fmaf(v[j], c_log2, -m_run[qi]));
-                            psum += v[j];
-                        }
-                        l_run[qi] += psum;
-                        pf[qi] = f16x8{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3],
-                                       (half_t)v[4], (half_t)v[5], (half_t)v[6], (half_t)v[7]};
-                    }
-                    if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); t_b = __builtin_amdgcn_s_memtime(); d_sm += t_b - t_a; t_a = t_b; }
-#pragma unroll
-                    for (int nb = 0; nb < NNB; ++nb) {
-                        if (nb + VD < NNB) {
-                            vring[(nb + VD) % (VD + 1)][0] = vread(nb + VD, 0);
-                            vring[(nb + VD) % (VD + 1)][1] = vread(nb + VD, 1);
-                        }
-                        const f16x4 v0 = vring[nb % (VD + 1)][0], v1 = vring[nb % (VD + 1)][1];
-                        const f16x8 vf = f16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#pragma unroll
-                        for (int qi = 0; qi < NQ; ++qi)
-                            o[qi][nb] = GDX_MFMA16(vf, pf[qi], o[qi][nb], 0, 0, 0);
-                    }
-                }
-                if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); t_b = __builtin_amdgcn_s_memtime(); d_pv += t_b - t_a; t_a = t_b; }
-                ah_wait_vm<(NST - 2) * PW>();
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                stage = stage == NST - 1 ? 0 : stage + 1;
-                if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); t_b = __builtin_amdgcn_s_memtime(); d_bar += t_b - t_a; ++n_t; }
+                st.mark(st.d_is);
+                ah_tile<G, QB, decltype(nq_tag)::value>(fr, St, qf, kt, S, c_log2, m_run, l_run, o, st);
+                ah_handover<G>(stage, wst);
+                st.mark(st.d_bar);
+                if constexpr (DBG) ++st.n_t;
             }
         };
         if (mine == 2) run_tiles(std::integral_constant<int, 2>{});
@@ -792,106 +676,85 @@ __global__ __launch_bounds__(512, 1) void attentionh8p_kernel(const _Float16* __
             load_q(it + 1);                                               // in front of the stores
         } else {
 #pragma unroll
-            for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) qf[qi][ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            for (int qi = 0; qi < QB; ++qi) ah_q_zero<G>(qf[qi]);
         }
         asm volatile("" ::: "memory");
         int ln = lane;
         asm volatile("" : "+v"(ln));                                      // (as in load_q)
-        const int e15 = ln & 15, eq = ln >> 4;
-#pragma unroll
-        for (int qi = 0; qi < QB; ++qi) {
-            if (qi >= mine) continue;
-            float l_tot = l_run[qi];
-            l_tot += __shfl_xor(l_tot, 16);
-            l_tot += __shfl_xor(l_tot, 32);
-            const float inv = 1.0f / l_tot;
-#pragma unroll
-            for (int nb = 0; nb < NNB; ++nb) {
-                const f32x4 r = o[qi][nb] * inv;
-                *reinterpret_cast<f16x4*>(sl + e15 * ROWB + (((2 * nb + (eq >> 1)) ^ (e15 & GM)) << 4) + (eq & 1) * 8) =
-                    f16x4{(half_t)r[0], (half_t)r[1], (half_t)r[2], (half_t)r[3]};
-            }
-            const int q0 = 16 * (qb_lo + wave + 8 * qi);
-#pragma unroll
-            for (int j = 0; j < NPQ; ++j) {
-                const int row = j * RPP + ln / CPR, c = ln % CPR;
-                const f16x8 v = *reinterpret_cast<const f16x8*>(sl + row * ROWB + ((c ^ (row & GM)) << 4));
-                if (q0 + row < S) *reinterpret_cast<f16x8*>(ctx + ((long)b * S + q0 + row) * d + h * HD + 8 * c) = v;
-            }
-        }
+        ah_store_rows<G, QB>(o, l_run, mine, sl, ln, ctx, im.b, im.h, im.qb_lo + wave, S, d);
     }
     if (DBG && dbg && blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 7)) {
         unsigned long long* o = dbg + (wave == 0 ? 0 : 8);
-        o[0] = d_is; o[1] = d_qk; o[2] = d_sm; o[3] = d_pv; o[4] = d_bar; o[5] = n_t;
+        o[0] = st.d_is; o[1] = st.d_qk; o[2] = st.d_sm; o[3] = st.d_pv; o[4] = st.d_bar; o[5] = st.n_t;
         o[6] = __builtin_amdgcn_s_memtime() - tk0; o[7] = __builtin_amdgcn_s_memrealtime() - tr0;
     }
-    ah_wait_vm<0>();
+    wait_vm<0>();
 #endif
 }
 
-template <int HD>
-static hipError_t launch_ah8p(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_bytes, int grid,
-                              hipStream_t s, unsigned long long* stamps) {
-    const size_t lds = (size_t)3 * 2 * 32 * HD * 2 + (size_t)8 * 16 * HD * 2;   // three K/V stages + a 16-row slice per wave
+// ---- host -------------------------------------------------------------------------------------------------------
+// kernel: 1 = attentionh8_kernel, 2 = attentionh8q_kernel, 3 = attentionh8p_kernel
+// The query chunks (8 blocks of 16 per workgroup pass for kernel 1, 16 for 2 / 3), work items and workgroups of a kernel choice.
+// grid: the persistent form's workgroups, 0 = one per CU and at most one per item.
+struct AhPlan {
+    int nchunk;
+    long items;
+    int grid;
+};
+static AhPlan ah_plan(int kernel, int B, int S, int H, int grid, int num_cus) {
+    const int nqb = (S + 15) / 16;
+    AhPlan p;
+    p.nchunk = kernel == 1 ? (nqb + 7) / 8 : (nqb + 15) / 16;
+    p.items = (long)B * H * p.nchunk;
+    p.grid = kernel != 3 ? (int)p.items : grid != 0 ? grid : p.items < num_cus ? (int)p.items : num_cus;
+    return p;
+}
+
+// head widths with an 8 x 2 and a persistent instantiation
+constexpr bool ah_multiblock(int hd) { return hd == 64 || hd == 128 || hd == 256; }
+
+template <int KERNEL, int HD>
+static hipError_t launch_ah(const _Float16* qkv, _Float16* ctx, int S, int H, int d, long qkv_bytes, const AhPlan& p, hipStream_t s,
+                            unsigned long long* stamps) {
+    using G = std::conditional_t<KERNEL == 1, AhGeom1<HD>, AhGeom2<HD>>;
+    constexpr size_t lds = G::LDS_BYTES;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attentionh8p_kernel<HD, 2, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attentionh8p_kernel<HD, 2, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        auto raise = [&](auto* k) {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        };
+        hipError_t e;
+        if constexpr (KERNEL == 1) e = raise(&attentionh8_kernel<HD>);
+        else if constexpr (KERNEL == 2) e = raise(&attentionh8q_kernel<HD, 2>);
+        else {
+            e = raise(&attentionh8p_kernel<HD, 2, false>);
+            if (e == hipSuccess) e = raise(&attentionh8p_kernel<HD, 2, true>);
+        }
         if (e != hipSuccess) return e;
         attr_done = true;
     }
-    const int nqb = (S + 15) / 16;
-    const int nchunk = (nqb + 15) / 16;
-    const int nitems = B * H * nchunk;
     const float c_log2 = 1.4426950408889634f / sqrtf((float)HD);
-    if (stamps)                                                   // the stamped build of the kernel (diagnostic launches only)
-        hipLaunchKernelGGL((attentionh8p_kernel<HD, 2, true>), dim3(grid), dim3(512), lds, s, qkv, ctx, S, H, d, nchunk, nitems,
-                           c_log2, qkv_bytes, stamps);
+    if constexpr (KERNEL == 1)
+        hipLaunchKernelGGL((attentionh8_kernel<HD>), dim3(p.grid), dim3(512), lds, s, qkv, ctx, S, H, d, p.nchunk, c_log2, qkv_bytes);
+    else if constexpr (KERNEL == 2)
+        hipLaunchKernelGGL((attentionh8q_kernel<HD, 2>), dim3(p.grid), dim3(512), lds, s, qkv, ctx, S, H, d, p.nchunk, c_log2, qkv_bytes);
+    else if (stamps)                                              // the stamped build of the kernel (diagnostic launches only)
+        hipLaunchKernelGGL((attentionh8p_kernel<HD, 2, true>), dim3(p.grid), dim3(512), lds, s, qkv, ctx, S, H, d, p.nchunk,
+                           (int)p.items, c_log2, qkv_bytes, stamps);
     else
-        hipLaunchKernelGGL((attentionh8p_kernel<HD, 2, false>), dim3(grid), dim3(512), lds, s, qkv, ctx, S, H, d, nchunk, nitems,
-                           c_log2, qkv_bytes, stamps);
+        hipLaunchKernelGGL((attentionh8p_kernel<HD, 2, false>), dim3(p.grid), dim3(512), lds, s, qkv, ctx, S, H, d, p.nchunk,
+                           (int)p.items, c_log2, qkv_bytes, stamps);
     return hipGetLastError();
 }
 
 template <int HD>
-static hipError_t launch_ah8q(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_bytes, hipStream_t s) {
-    const size_t lds = (size_t)3 * 2 * 32 * HD * 2 + (size_t)8 * 16 * HD * 2;   // three K/V stages + a 16-row slice per wave
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attentionh8q_kernel<HD, 2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
+static hipError_t launch_ah_kernel(int kernel, const _Float16* qkv, _Float16* ctx, int S, int H, int d, long qkv_bytes, const AhPlan& p,
+                                   hipStream_t s, unsigned long long* stamps) {
+    if constexpr (ah_multiblock(HD)) {
+        if (kernel == 3) return launch_ah<3, HD>(qkv, ctx, S, H, d, qkv_bytes, p, s, stamps);
+        if (kernel == 2) return launch_ah<2, HD>(qkv, ctx, S, H, d, qkv_bytes, p, s, stamps);
     }
-    const int nqb = (S + 15) / 16;
-    const int nchunk = (nqb + 15) / 16;
-    const float c_log2 = 1.4426950408889634f / sqrtf((float)HD);
-    hipLaunchKernelGGL((attentionh8q_kernel<HD, 2>), dim3(B * H * nchunk), dim3(512), lds, s, qkv, ctx, S, H, d, nchunk,
-                       c_log2, qkv_bytes);
-    return hipGetLastError();
-}
-
-template <int HD>
-static hipError_t launch_ah8(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_bytes, hipStream_t s) {
-    const size_t lds = (size_t)4 * 2 * 32 * HD * 2;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attentionh8_kernel<HD>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    const int nqb = (S + 15) / 16;
-    const int nchunk = (nqb + 7) / 8;
-    const float c_log2 = 1.4426950408889634f / sqrtf((float)HD);
-    hipLaunchKernelGGL((attentionh8_kernel<HD>), dim3(B * H * nchunk), dim3(512), lds, s, qkv, ctx, S, H, d, nchunk,
-                       c_log2, qkv_bytes);
-    return hipGetLastError();
+    return kernel == 1 ? launch_ah<1, HD>(qkv, ctx, S, H, d, qkv_bytes, p, s, stamps) : hipErrorInvalidValue;
 }
 
 bool attentionh_supported(int S, int H, int d) {
@@ -899,8 +762,7 @@ bool attentionh_supported(int S, int H, int d) {
     return head_dim_supported(hd) && d % 8 == 0 && S >= 1;
 }
 
-// head widths with an 8 x 2 and a persistent instantiation
-bool attentionh_multiblock(int hd) { return hd == 64 || hd == 128 || hd == 256; }
+bool attentionh_multiblock(int hd) { return ah_multiblock(hd); }
 
 // The one dispatch of the forward and of the test entry point gdx_attention_half.  kernel: 0 = the forward's choice, 1 = the
 // 8-wave x 1-block kernel, 2 = 8 x 2 blocks, 3 = the persistent form (the callers refuse 2 / 3 at head_dim 32, 96 and 192, which
@@ -915,40 +777,29 @@ hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, i
     // B=16 (config 5's per-GPU share): 58.9 / 37.4;  B=64 S=197 hd=128: 19.9 / 18.7.  The 8 x 2 kernels need enough
     // workgroups to fill the chip (they make half as many), so small problems keep one block per wave.
     // (Round 3, XCD-aware items + whole-row Q / output traffic: persistent 257-261, B=16 33.0, B=256 S=197 hd=128 55.7.)
-    const int nqb = (S + 15) / 16;
-    const long nitems = (long)B * H * ((nqb + 15) / 16);
     const int num_cus = gemm2_num_cus();
     if (kernel == 0) {
+        const long nitems = ah_plan(2, B, S, H, 0, num_cus).items;
         // persistent form once every CU has at least two items to chain (profiles/r02h_*)
-        if (attentionh_multiblock(hd) && nitems >= 2L * num_cus) kernel = 3;
-        else if (attentionh_multiblock(hd) && nitems >= 128) kernel = 2;
+        if (ah_multiblock(hd) && nitems >= 2L * num_cus) kernel = 3;
+        else if (ah_multiblock(hd) && nitems >= 128) kernel = 2;
         else kernel = 1;
     }
-    if ((kernel != 1 && (!attentionh_multiblock(hd) || kernel > 3)) || kernel < 1 || (grid != 0 && kernel != 3) || grid < 0) return hipErrorInvalidValue;
-    if (kernel == 3 && grid == 0) grid = nitems < num_cus ? (int)nitems : num_cus;
+    if ((kernel != 1 && (!ah_multiblock(hd) || kernel > 3)) || kernel < 1 || (grid != 0 && kernel != 3) || grid < 0) return hipErrorInvalidValue;
+    const AhPlan p = ah_plan(kernel, B, S, H, grid, num_cus);
     if (launched) {
         launched[0] = kernel;
-        launched[1] = kernel == 3 ? grid : kernel == 2 ? (int)nitems : B * H * ((nqb + 7) / 8);
-        launched[2] = kernel == 1 ? B * H * ((nqb + 7) / 8) : (int)nitems;
+        launched[1] = p.grid;
+        launched[2] = (int)p.items;
     }
-    if (kernel == 3) {
-        if (hd == 256) return launch_ah8p<256>(qkv, ctx, B, S, H, d, bytes, grid, s, stamps);
-        if (hd == 128) return launch_ah8p<128>(qkv, ctx, B, S, H, d, bytes, grid, s, stamps);
-        if (hd == 64) return launch_ah8p<64>(qkv, ctx, B, S, H, d, bytes, grid, s, stamps);
-        return hipErrorInvalidValue;
+    switch (hd) {
+    case 256: return launch_ah_kernel<256>(kernel, qkv, ctx, S, H, d, bytes, p, s, stamps);
+    case 192: return launch_ah_kernel<192>(kernel, qkv, ctx, S, H, d, bytes, p, s, stamps);
+    case 128: return launch_ah_kernel<128>(kernel, qkv, ctx, S, H, d, bytes, p, s, stamps);
+    case 96: return launch_ah_kernel<96>(kernel, qkv, ctx, S, H, d, bytes, p, s, stamps);
+    case 64: return launch_ah_kernel<64>(kernel, qkv, ctx, S, H, d, bytes, p, s, stamps);
+    case 32: return launch_ah_kernel<32>(kernel, qkv, ctx, S, H, d, bytes, p, s, stamps);
     }
-    if (kernel == 2) {
-        if (hd == 256) return launch_ah8q<256>(qkv, ctx, B, S, H, d, bytes, s);
-        if (hd == 128) return launch_ah8q<128>(qkv, ctx, B, S, H, d, bytes, s);
-        if (hd == 64) return launch_ah8q<64>(qkv, ctx, B, S, H, d, bytes, s);
-        return hipErrorInvalidValue;
-    }
-    if (hd == 256) return launch_ah8<256>(qkv, ctx, B, S, H, d, bytes, s);
-    if (hd == 192) return launch_ah8<192>(qkv, ctx, B, S, H, d, bytes, s);
-    if (hd == 128) return launch_ah8<128>(qkv, ctx, B, S, H, d, bytes, s);
-    if (hd == 96) return launch_ah8<96>(qkv, ctx, B, S, H, d, bytes, s);
-    if (hd == 64) return launch_ah8<64>(qkv, ctx, B, S, H, d, bytes, s);
-    if (hd == 32) return launch_ah8<32>(qkv, ctx, B, S, H, d, bytes, s);
     return hipErrorInvalidValue;
 }
 

@@ -123,7 +123,9 @@ hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, 
     hipError_t launch_attentionh(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows, hipStream_t s); \
     /* the same dispatch with a forced kernel (0 = the forward's choice, 1 = h8, 2 = h8q, 3 = h8p), the persistent grid      \
        (0 = its default), a report of what ran (launched: kernel, grid, work items) and a 512-byte device buffer for the     \
-       in-kernel stamps of h8p (GDX_GEMM_DEBUG); used by gdx_attention_half and gdx_bench_attention */                       \
+       in-kernel stamps of h8p (GDX_GEMM_DEBUG); used by gdx_attention_half and gdx_bench_attention.  Inside: ah_plan gives   \
+       the (chunks, items, grid) of the kernel choice for the launch and for the report, one head-width ladder reaches the  \
+       one launcher template launch_ah<KERNEL, HD> */                                                                       \
     hipError_t launch_attentionh_kernel(const _Float16* qkv, _Float16* ctx, int B, int S, int H, int d, long qkv_rows,     \
                                         int kernel, int grid, int* launched, hipStream_t s,                                \
                                         unsigned long long* stamps = nullptr);                                              \

@@ -19,11 +19,11 @@
 //   * XCD-aware tile order: blocks that share an A row-panel get consecutive logical ids and the
 //     ids are dealt so that each XCD (private 4 MiB L2) owns a contiguous range.
 #include "gdx_internal.h"
+#include "gdx_device.h"
 
 namespace gdx {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int LDS_STRIDE = BK + 4;          // 36 floats
@@ -46,12 +46,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     // ---- XCD-aware bijective block -> tile map (blocks b, b+8, ... share an XCD) -------------
     const int nbn = (p.N + BN - 1) / BN;
     const int total = gridDim.x;
-    int lid;
-    {
-        const int bid = blockIdx.x;
-        const int q = total >> 3, r = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lid = xcd_lid((int)blockIdx.x, total);
     const int m0 = (lid / nbn) * BM;
     const int n0 = (lid % nbn) * BN;
 

@@ -44,14 +44,12 @@
 // tests/test_gpu_gemm_f32.py::test_tile_and_batch_independence_bitwise at kernel level: all 21 shapes, both slab depths, every
 // epilogue, GELU included, give identical bits).
 #include "gdx_internal.h"
+#include "gdx_device.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace gdx {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // erf(x), Abramowitz & Stegun 7.1.26 (max abs error 1.5e-7), branch-free
 __device__ __forceinline__ float erf_as(float x) {
@@ -69,7 +67,6 @@ __device__ __forceinline__ float gelu_fast(float x) { return x * 0.5f * (1.0f + 
 // The same GELU on two values at once: every multiply / FMA is a packed-fp32 instruction (v_pk_fma_f32 / v_pk_mul_f32:
 // two values per lane for the issue cost of one); only the reciprocal and the exponential stay scalar.  Same formula
 // as gelu_fast (results may differ in the last bit where the compiler contracts a multiply-add differently).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 gelu_fast2(f32x2 x) {
     const f32x2 z = x * 0.70710678118654752440f;
     const f32x2 ax = f32x2{fabsf(z.x), fabsf(z.y)};
@@ -85,9 +82,6 @@ __device__ __forceinline__ f32x2 gelu_fast2(f32x2 x) {
     const f32x2 er = f32x2{copysignf(r.x, z.x), copysignf(r.y, z.y)};
     return x * 0.5f * (1.0f + er);
 }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int R, int NRD, int NMM>
 __device__ __forceinline__ void g4_sched_interleave() {
@@ -131,11 +125,7 @@ __global__ __launch_bounds__(512, 1) void gemm4_kernel(const GemmParams p, const
     const int lane = tid & 63;
     const int l15 = lane & 15, lq = lane >> 4;
     const int G = gridDim.x;
-    int lid;
-    {   // XCD-aware bijective remap (blocks b, b+8, ... share an XCD)
-        const int bid = blockIdx.x, q = G >> 3, r = G & 7, xcd = bid & 7, idx = bid >> 3;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lid = xcd_lid((int)blockIdx.x, G);                  // XCD-aware bijective remap (blocks b, b+8, ... share an XCD)
     const int my_tiles = lid < ntiles ? (ntiles - lid + G - 1) / G : 0;
     const int nk = p.K / BK;
     const int total = my_tiles * nk;

@@ -23,31 +23,17 @@
 //   * the A operand's buffer descriptor carries the exact size, so rows past M read as zeros and are never stored.
 // Summation order per output element is k-slab by k-slab and independent of the tile shape.
 #include "gdx_internal.h"
+#include "gdx_device.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
-
-#ifdef GDX_BF16
-#define GDX_MFMA16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#else
-#define GDX_MFMA16 __builtin_amdgcn_mfma_f32_16x16x32_f16
-#endif
 
 namespace gdx {
 
 int gemm2_num_cus();
 
 GDX_HNS_BEGIN
-
-typedef half_t f16x8 __attribute__((ext_vector_type(8)));
-typedef half_t f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void wait_vm_h() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // gelu_erf on two values at once (packed fp32 VALU, no transcendental): erf(z) = z * P(2 z^2 / 9 - 1) on |z| <= 3
 // (degree-10 Chebyshev fit, |err| <= 1.2e-6), z clamped to +-3 beyond (1 - erf(3) = 2.2e-5).  |gelu err| <= 2.5e-6
@@ -197,11 +183,7 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
     const int lane = tid & 63;
     const int l15 = lane & 15, lq = lane >> 4;
     const int G = gridDim.x;
-    int lid;
-    {   // XCD-aware bijective remap (blocks b, b+8, ... share an XCD)
-        const int bid = blockIdx.x, q = G >> 3, r = G & 7, xcd = bid & 7, idx = bid >> 3;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lid = xcd_lid((int)blockIdx.x, G);                  // XCD-aware bijective remap (blocks b, b+8, ... share an XCD)
     const int my_tiles = lid < ntiles ? (ntiles - lid + G - 1) / G : 0;
     const int nk = p.K / 32;
     const int total = my_tiles * nk;                              // even: K % 64 == 0
@@ -293,21 +275,21 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
             };
             issue2(0);
             issue2(1);
-            wait_vm_h<PW2>();                                     // slab 0 has landed
+            wait_vm<PW2>();                                     // slab 0 has landed
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             int wst = 2;
             for (int g = 0; g < total; g += 2) {
                 issue2(wst);                                      // slab g/2 + 2 -> the slot of the slab consumed before the last barrier
                 wst = wst == 2 ? 0 : wst + 1;
-                wait_vm_h<PW2>();                                 // slab g/2 + 1 has landed
+                wait_vm<PW2>();                                 // slab g/2 + 1 has landed
                 asm volatile("s_barrier" ::: "memory");
             }
-            wait_vm_h<0>();
+            wait_vm<0>();
             return;
         }
 #pragma unroll
         for (int s = 0; s < NST - 1; ++s) issue(s);
-        wait_vm_h<VM_STEP>();
+        wait_vm<VM_STEP>();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         int wst = NST - 1;
         if (dbg) {                                                // diagnostic build path (GDX_GEMM_DEBUG): where a loader spends its cycles
@@ -318,7 +300,7 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
                 issue(wst);
                 wst = wst == NST - 1 ? 0 : wst + 1;
                 const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-                wait_vm_h<VM_STEP>();
+                wait_vm<VM_STEP>();
                 const unsigned long long t2 = __builtin_amdgcn_s_memtime();
                 asm volatile("s_barrier" ::: "memory");
                 const unsigned long long t3 = __builtin_amdgcn_s_memtime();
@@ -329,16 +311,16 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
                 dbg[4] = __builtin_amdgcn_s_memtime() - t_begin;
                 dbg[5] = __builtin_amdgcn_s_memrealtime() - r_begin;   // 100 MHz
             }
-            wait_vm_h<0>();
+            wait_vm<0>();
             return;
         }
         for (int g = 0; g < total; ++g) {
             issue(wst);                                           // slab g+NST-1 -> the stage freed by the last barrier
             wst = wst == NST - 1 ? 0 : wst + 1;
-            wait_vm_h<VM_STEP>();                                 // slab g+2 has landed
+            wait_vm<VM_STEP>();                                 // slab g+2 has landed
             asm volatile("s_barrier" ::: "memory");
         }
-        wait_vm_h<0>();
+        wait_vm<0>();
         return;
     }
 
@@ -497,11 +479,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
     const int lane = tid & 63;
     const int l15 = lane & 15, lq = lane >> 4;
     const int G = gridDim.x;
-    int lid;
-    {
-        const int bid = blockIdx.x, q = G >> 3, r = G & 7, xcd = bid & 7, idx = bid >> 3;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lid = xcd_lid((int)blockIdx.x, G);                  // XCD-aware bijective remap (blocks b, b+8, ... share an XCD)
     const int my_tiles = lid < ntiles ? (ntiles - lid + G - 1) / G : 0;
     const int nk = p.K / 64;                                      // 64-deep slabs per tile (>= 4)
     const int total = my_tiles * nk;
@@ -608,7 +586,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
     };
     auto sync_wait = [&]() {                                      // end of step (j, 0): slab j+1 has landed
         __builtin_amdgcn_sched_barrier(0);
-        wait_vm_h<PW>();
+        wait_vm<PW>();
         __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -638,7 +616,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
     using H1 = std::integral_constant<int, 1>;
 
     issue_A(); issue_W(); issue_A(); issue_W();                   // A_0, W_0, A_1, W_1
-    wait_vm_h<2 * PW>();                                          // slab 0 (this wave's pieces)
+    wait_vm<2 * PW>();                                          // slab 0 (this wave's pieces)
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -682,7 +660,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
             for (int j = 0; j < NBW; ++j) bv[j] = bp ? *reinterpret_cast<const f32x4*>(bp + CM::blk(j)) : f32x4{0.f, 0.f, 0.f, 0.f};
             unsigned long long te0 = 0, te1 = 0;
             if (dbg) te0 = __builtin_amdgcn_s_memtime();
-            wait_vm_h<0>();
+            wait_vm<0>();
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -718,7 +696,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
         dbg[5] = __builtin_amdgcn_s_memrealtime() - r0;
         dbg[3] = (unsigned long long)total * 2;
     }
-    wait_vm_h<0>();
+    wait_vm<0>();
 #endif
 }
 

@@ -2,18 +2,10 @@
 // (timestep / seed embedding), the MFCC projection hoisted out of the loop, the conditioning
 // token, the fused V2 front end (RoPE -> causal local attention -> RoPE) and the CFG blend.
 #include "gdx_internal.h"
-
-#ifdef GDX_BF16
-#define GDX_MFMA16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#else
-#define GDX_MFMA16 __builtin_amdgcn_mfma_f32_16x16x32_f16
-#endif
+#include "gdx_device.h"
 
 namespace gdx {
 GDX_HNS_BEGIN
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef half_t f16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -127,8 +119,6 @@ hipError_t launch_layernorm(const float* x, const float* res, const float* gamma
 // fp16-mode LayerNorm: x and the residual are fp16 (the whole activation stream of the fp16 mode is fp16), statistics
 // and the affine transform are fp32, output fp16 (+ optional fp32 copy for the parity taps).  One wave per row,
 // 8 halves (16 B) per lane per load.  HBM-bound: 3 * rows * d * 2 bytes.
-typedef half_t f16x8 __attribute__((ext_vector_type(8)));
-
 template <int NV>   // 16-byte loads per lane: d = 512 * NV
 __global__ __launch_bounds__(256) void layernorm_h_vec_kernel(const half_t* __restrict__ x, const half_t* __restrict__ res,
                                                                const float* __restrict__ g, const float* __restrict__ bta,

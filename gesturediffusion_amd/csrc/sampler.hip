@@ -15,13 +15,13 @@
 #include <string>
 
 #include "gdx_internal.h"
+#include "gdx_device.h"
 #include "../../include/gdx.h"
 
 #pragma clang fp contract(off)
 
 namespace gdx {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct Philox {
     static constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
