@@ -26,6 +26,7 @@ EXPORTS = [
     "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
     "gdx_dpm_step", "gdx_dpm_loop", "gdx_dpm_sde_step", "gdx_dpm_sde_loop",
     "gdx_set_guidance_interval", "gdx_forward_samples", "gdx_set_guidance_rescale", "gdx_cfg_rescale",
+    "gdx_set_guidance_refresh", "gdx_cfg_delta",
     "gdx_transpose_in", "gdx_transpose_out", "gdx_small_linear", "gdx_gather_rows", "gdx_mfcc_project", "gdx_token0",
 ]
 GDX_BPD_CHUNK = 4096   # include/gdx.h
@@ -159,6 +160,10 @@ class CfgRescaleArgs(C.Structure):
     ]
 
 
+class CfgDeltaArgs(C.Structure):
+    _fields_ = [("count", C.c_int64), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -240,6 +245,8 @@ def load():
         "gdx_forward_samples": [vp, C.POINTER(i64)],
         "gdx_set_guidance_rescale": [vp, C.c_float],
         "gdx_cfg_rescale": [C.POINTER(CfgRescaleArgs), vp],
+        "gdx_set_guidance_refresh": [vp, i32],
+        "gdx_cfg_delta": [C.POINTER(CfgDeltaArgs), vp],
         "gdx_profile_begin": [vp, i32],
         "gdx_profile_end": [vp, C.POINTER(C.c_float), C.POINTER(i32)],
     }

@@ -93,6 +93,18 @@ extern "C" int gdx_destroy(gdx_handle_t h) {
     return 0;
 }
 
+// A zero-filled workspace buffer of the handle, with its canary zone behind it under gdx_set_guards (`who`: the entry that asks)
+static int ws_alloc(gdx_model* h, const char* who, void** p, size_t bytes) {
+    if (dev_alloc(h->ws_allocs, p, bytes + (h->guards ? GUARD_BYTES : 0))) return -1;
+    if (hipMemset(*p, 0, bytes) != hipSuccess) return fail(std::string(who) + ": hipMemset failed");
+    if (h->guards) {
+        unsigned char* g = (unsigned char*)*p + bytes;
+        if (hipMemset(g, GUARD_BYTE, GUARD_BYTES) != hipSuccess) return fail(std::string(who) + ": hipMemset failed");
+        h->guard_zones.emplace_back(g, bytes);
+    }
+    return 0;
+}
+
 extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     if (!h) return fail("gdx_prepare: null handle");
     if (batch <= 0 || frames <= 0) return fail("gdx_prepare: batch and frames must be positive");
@@ -101,6 +113,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     if (h->pe && frames + 1 > h->pe_rows) return fail("gdx_prepare: frames exceed positional table");
     if (h->cfg.arch == GDX_ARCH_MDM && h->rope_cos && frames + 1 > h->rope_rows)
         return fail("gdx_prepare: frames exceed rotary table");
+    h->gd_valid = false;                                          // guidance refresh: a stored difference never outlives a prepare
     if (h->B == batch && h->T == frames) return 0;
     free_pool(h->ws_allocs);
     h->guard_zones.clear();
@@ -108,7 +121,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     h->temb_table = nullptr; h->temb_table_rows = 0; h->tmap_dev = nullptr; h->c2t_table = nullptr; h->c2t_valid = false;
     h->tables_valid = false;
     h->bpd_xt = h->bpd_z = h->bpd_part = nullptr;
-    h->rs_part = nullptr; h->rs_factor = nullptr;
+    h->rs_part = nullptr; h->rs_factor = nullptr; h->gd = nullptr;
     // the shape is recorded only once every allocation has succeeded: after a failed hipMalloc a retry with the same
     // shape must allocate again instead of returning early on partial buffers
     h->B = 0; h->T = 0; h->S = frames + 1; h->cond_set = false;
@@ -117,16 +130,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     const size_t B2 = 2 * (size_t)batch, N = B2 * h->S + GDX_ROW_PAD, d = h->d;
     h->rows_alloc = (long)N;
     // zero-filled: the padding rows are read by whole-tile GEMMs / K-V tiles and must stay finite
-    auto raw = [&](void** p, size_t bytes) {
-        if (dev_alloc(h->ws_allocs, p, bytes + (h->guards ? GUARD_BYTES : 0))) return -1;
-        if (hipMemset(*p, 0, bytes) != hipSuccess) return fail("gdx_prepare: hipMemset failed");
-        if (h->guards) {
-            unsigned char* g = (unsigned char*)*p + bytes;
-            if (hipMemset(g, GUARD_BYTE, GUARD_BYTES) != hipSuccess) return fail("gdx_prepare: hipMemset failed");
-            h->guard_zones.emplace_back(g, bytes);
-        }
-        return 0;
-    };
+    auto raw = [&](void** p, size_t bytes) { return ws_alloc(h, "gdx_prepare", p, bytes); };
     auto A = [&](float** p, size_t n) { return raw((void**)p, n * sizeof(float)); };
     // the sides of an activation pair this mode uses; every fp32 side is allocated before the first 16-bit one, in the order below
     // (the order of the guard zones gdx_check_guards reports)
@@ -234,6 +238,7 @@ extern "C" int gdx_set_condition(gdx_handle_t h, const float* seed, const float*
         HIPCHK(launch_small_linear(h->seed_cat, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2_seed, d, 2 * B, d, d, 0, s));
     }
     h->cond_set = true;
+    h->gd_valid = false;                                          // guidance refresh: the difference of another conditioning
     return 0;
 }
 
@@ -433,18 +438,75 @@ extern "C" int gdx_set_guidance_rescale(gdx_handle_t h, float phi) {
     return 0;
 }
 
+// Guidance refresh (gdx.h): per-handle `every`, 1 = off.  Refusals precede any HIP call.
+extern "C" int gdx_set_guidance_refresh(gdx_handle_t h, int32_t every) {
+    if (!h) return fail("gdx_set_guidance_refresh: null handle");
+    if (every < 1) return fail("gdx_set_guidance_refresh: every must be at least 1");
+    h->guide_every = every;
+    h->gd_valid = false;
+    return 0;
+}
+
 extern "C" int gdx_forward_samples(gdx_handle_t h, int64_t* samples) {
     if (!h || !samples) return fail("gdx_forward_samples: null argument");
     *samples = h->forward_samples;
     return 0;
 }
 
-// The mode of ONE step of a loop whose mode is `mode`: guidance only while the step's model timestep lies in the handle's
-// interval, else the plain conditional pass (B samples, no blend).  Every in-library loop asks here.
-static int step_mode(const gdx_model* h, int mode, const int64_t* timestep_map, int idx) {
-    if (mode != GDX_CFG) return mode;
-    const int64_t tau = timestep_map[idx];
-    return h->guide_lo <= tau && tau <= h->guide_hi ? GDX_CFG : GDX_COND;
+// step_mode's internal answers under the guidance refresh (gdx.h), never a loop's own mode: a guided call that stores the
+// difference c - u, and one that runs the conditional pass alone and reuses the stored difference
+static constexpr int GDX_CFG_REFRESH = GDX_CFG + 1, GDX_CFG_REUSE = GDX_CFG + 2;
+
+// The sequence of denoiser calls a call belongs to, as far as the numbering of its guided calls needs it: the loop's mode and
+// timestep map, the WHOLE loop's first index (first_index + k_base of a block), the index of the second call of gdx_plms_loop's
+// step 0 (-1: the loop has none), and whether the loop takes part in the refresh at all (gdx_bpd_loop does not)
+struct CallSeq {
+    int mode;
+    const int64_t* timestep_map;
+    int first, second;
+    bool refresh;
+};
+template <typename A>
+static CallSeq call_seq(const A* a, bool two_calls) {
+    const int first = a->first_index + a->k_base;
+    return CallSeq{a->mode, a->timestep_map, first, two_calls ? (first - 1 + a->num_steps) % a->num_steps : -1, true};
+}
+
+static bool guided_at(const gdx_model* h, const CallSeq& q, int idx) {
+    const int64_t tau = q.timestep_map[idx];
+    return q.mode == GDX_CFG && h->guide_lo <= tau && tau <= h->guide_hi;
+}
+
+// The mode of ONE denoiser call of a loop, at index idx (second: the second call of gdx_plms_loop's step 0, at q.second):
+// guidance only while the call's model timestep lies in the handle's interval, else the plain conditional pass (B samples, no
+// blend).  With gdx_set_guidance_refresh's every > 1 a guided call is numbered n = the guided calls of the loop before it, in
+// execution order q.first, q.second, q.first - 1, q.first - 2, ..., and n % every decides between GDX_CFG_REFRESH and
+// GDX_CFG_REUSE.  Every in-library loop asks here.
+static int step_mode(const gdx_model* h, const CallSeq& q, int idx, bool second = false) {
+    if (q.mode != GDX_CFG) return q.mode;
+    if (!guided_at(h, q, idx)) return GDX_COND;
+    if (h->guide_every == 1 || !q.refresh) return GDX_CFG;
+    int n = 0;
+    if (second) {
+        n = guided_at(h, q, q.first);
+    } else {
+        for (int j = q.first; j > idx; --j) n += guided_at(h, q, j);
+        if (q.second >= 0 && idx < q.first) n += guided_at(h, q, q.second);
+    }
+    return n % h->guide_every == 0 ? GDX_CFG_REFRESH : GDX_CFG_REUSE;
+}
+
+// A call that issues the steps first_index .. last_idx of q's loop must not begin with a reuse that has nothing to reuse: asked
+// before the call's first launch
+static int check_reuse(const gdx_model* h, const char* who, const CallSeq& q, int first_index, int last_idx) {
+    for (int idx = first_index; idx >= last_idx; --idx) {
+        const int m = step_mode(h, q, idx);
+        if (m == GDX_CFG_REUSE && !h->gd_valid)
+            return fail(std::string(who) + ": a guided call would reuse the guidance difference, but none is stored: a block-wise "
+                        "call (run_steps / k_base) must continue the loop that stored the difference");
+        if (m >= GDX_CFG) break;
+    }
+    return 0;
 }
 
 // gdx_cfg_rescale on the handle's buffers: c, u -> out for the B samples of the workspace, guided where t == nullptr or
@@ -465,11 +527,24 @@ static int rescale_x0(gdx_model* h, const float* c, const float* u, const float*
 // What the step kernel of a loop step in mode m gets as (x0_uncond, scale) after denoise_step left the prediction in h->x0.
 // Guided without rescale: the uncond half and the scales, the kernel blends.  Guided with the handle's phi > 0: the rescaled
 // guided prediction is formed here, in place on the cond half, and the kernel is called like on an unguided step (NULL, NULL).
-// Every in-library loop asks here.
+// Under the guidance refresh (m = GDX_CFG_REFRESH / GDX_CFG_REUSE) the difference is stored or applied first (gdx_cfg_delta on
+// the handle's buffer), and the step then continues as a guided one with (c, u or u', scale).  Every in-library loop asks here.
 static int guided_operands(gdx_model* h, int m, const float* scale, hipStream_t s, const float** x0_uncond, const float** sc) {
     *x0_uncond = nullptr; *sc = nullptr;
-    if (m != GDX_CFG) return 0;
-    const float* u = h->x0 + (size_t)h->B * h->J * h->T;
+    if (m < GDX_CFG) return 0;
+    const size_t n = (size_t)h->B * h->J * h->T;
+    float* u = h->x0 + n;
+    if (m != GDX_CFG) {
+        // guidance refresh: a refresh stores d = c - u; a reuse, whose forward left only c, forms u' = c - d in u's place
+        if (!h->gd) {
+            if (ws_alloc(h, "guidance refresh", (void**)&h->gd, sizeof(float) * n)) return -1;
+            HIPCHK(hipStreamSynchronize(nullptr));                 // the fill is on the null stream, the first store on s
+        }
+        const bool store = m == GDX_CFG_REFRESH;
+        const gdx_cfg_delta_args_t g{(int64_t)n, h->x0, store ? u : h->gd, store ? h->gd : u};
+        if (gdx_cfg_delta(&g, (void*)s)) return -1;
+        if (store) h->gd_valid = true;
+    }
     if (h->guide_phi > 0.0f) return rescale_x0(h, h->x0, u, scale, nullptr, h->x0, s);
     *x0_uncond = u; *sc = scale;
     return 0;
@@ -551,7 +626,9 @@ static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timeste
 static int denoise_step(gdx_model* h, const float* x, int idx, int mode, float* x0_out, hipStream_t s, const int* state = nullptr,
                         bool tm = false) {
     const size_t row = (size_t)idx * h->d;
-    return forward_core(h, x, h->temb_table + row, 0, h->c2t_table ? h->c2t_table + row : nullptr, mode, x0_out, s, state, tm);
+    // step_mode's refresh answers: a refresh is the full guided forward, a reuse the conditional pass alone
+    const int fm = mode == GDX_CFG_REFRESH ? GDX_CFG : mode == GDX_CFG_REUSE ? GDX_COND : mode;
+    return forward_core(h, x, h->temb_table + row, 0, h->c2t_table ? h->c2t_table + row : nullptr, fm, x0_out, s, state, tm);
 }
 
 // Executed step k's slice of a noise tape that starts at step k_base and holds `rows` samples ([rows][per]) per step
@@ -560,11 +637,12 @@ static const float* tape_slice(const float* tape, int k, int k_base, size_t rows
 }
 
 // One forward of a loop at schedule index idx on the state x, in the mode of its own timestep (guidance interval), and the
-// step kernel's view of its output in h->x0: (x0_uncond, scale).  Every in-library loop's eager step asks here; A: its arguments.
-template <typename A>
-static int denoise_guided(gdx_model* h, const A* a, const float* x, int idx, hipStream_t s, const float** x0_uncond, const float** scale) {
-    const int m = step_mode(h, a->mode, a->timestep_map, idx);
-    return denoise_step(h, x, idx, m, h->x0, s) || guided_operands(h, m, a->scale, s, x0_uncond, scale) ? -1 : 0;
+// step kernel's view of its output in h->x0: (x0_uncond, scale).  Every in-library loop's eager step asks here; q: the loop's
+// call sequence, sc_in: its scales, second: step_mode's.
+static int denoise_guided(gdx_model* h, const CallSeq& q, const float* sc_in, const float* x, int idx, hipStream_t s,
+                          const float** x0_uncond, const float** scale, bool second = false) {
+    const int m = step_mode(h, q, idx, second);
+    return denoise_step(h, x, idx, m, h->x0, s) || guided_operands(h, m, sc_in, s, x0_uncond, scale) ? -1 : 0;
 }
 
 // calc_bpd_loop (gaussian_diffusion.py:1537-1592): per step q_sample -> denoiser -> fused bound terms, through the SAME forward
@@ -597,6 +675,8 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     u.vb = a->vb; u.xstart_mse = a->xstart_mse; u.mse = a->mse; u.ld = a->num_steps;
     u.workspace = h->bpd_part;
     const int k_end = a->run_steps > 0 ? a->k_base + a->run_steps : a->num_steps;
+    // no guidance refresh here: the steps draw independent x_t, so every guided call is a full one
+    const CallSeq q{a->mode, a->timestep_map, a->num_steps - 1, -1, false};
     for (int k = a->k_base; k < k_end; ++k) {
         const int idx = a->num_steps - 1 - k;
         if (a->noise_tape) {
@@ -608,7 +688,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
                             stream))
                 return -1;
         }
-        if (denoise_guided(h, a, h->bpd_xt, idx, s, &u.x0_uncond, &u.scale)) return -1;
+        if (denoise_guided(h, q, a->scale, h->bpd_xt, idx, s, &u.x0_uncond, &u.scale)) return -1;
         u.step_index = idx; u.col = k;
         if (gdx_bpd_terms(&u, stream)) return -1;
     }
@@ -636,13 +716,14 @@ static U step_args(const gdx_model* h, const A* a, int idx, const float* x0_unco
 // The scaffold of the multistep loops gdx_plms_loop, gdx_dpm_loop and gdx_dpm_sde_loop (`who`), whose argument structs A name
 // the fields mode .. k_base alike: per step the denoiser through forward_core on the pose-layout state (the entry gdx_forward
 // uses: same bits as the step-wise protocol), then step(idx, k, x0_uncond, scale, slot), the entry's own fused launch; slot(k) =
-// executed step k's place in the caller's ring of a->order buffers at a->*hist.  No graph replay and no token-major variant:
+// executed step k's place in the caller's ring of a->order buffers at a->*hist; two_calls: step 0 makes a second denoiser call
+// (call_seq; the entry's step issues it).  No graph replay and no token-major variant:
 // these solvers run 10-50 steps.  The argument checks need no handle and come first (then null handle, then not prepared), so
 // every refusal precedes the first HIP call; missing() gives the entry's history refusal or nullptr.  A new multistep sampler
 // is one more caller of this function ("Where a new in-library loop goes").
 template <typename A, typename Missing, typename Step>
 static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_lo, int order_hi, const char* order_msg,
-                          float* A::*hist, Missing missing, hipStream_t s, Step step) {
+                          float* A::*hist, Missing missing, hipStream_t s, Step step, bool two_calls = false) {
     const std::string w = std::string(who) + ": ";
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail(w + "null argument");
     if (check_mode(who, a->mode, a->scale)) return -1;
@@ -654,14 +735,16 @@ static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_l
     if (const char* m = missing()) return fail(w + m);
     if (check_ready(h, who)) return -1;
     if (h->B > 65535) return fail(w + "batch exceeds 65535");
+    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
+    const CallSeq q = call_seq(a, two_calls);
+    if (check_reuse(h, who, q, a->first_index, last_idx)) return -1;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
     const size_t n = (size_t)h->B * h->J * h->T;
     auto slot = [&](int k) { return a->*hist + (size_t)(k % a->order) * n; };
-    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
     int k = a->k_base;
     for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
         const float *x0u, *sc;
-        if (denoise_guided(h, a, a->x, idx, s, &x0u, &sc) || step(idx, k, x0u, sc, slot)) return -1;
+        if (denoise_guided(h, q, a->scale, a->x, idx, s, &x0u, &sc) || step(idx, k, x0u, sc, slot)) return -1;
     }
     return 0;
 }
@@ -679,7 +762,7 @@ extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void
                 u.kind = 6; u.eps_out = slot(0); u.out = a->scratch; u.pred_xstart = slot(1);
                 if (gdx_plms_step(&u, stream)) return -1;
                 const int idx2 = (idx - 1 + a->num_steps) % a->num_steps;
-                if (denoise_guided(h, a, a->scratch, idx2, s, &u.x0_uncond, &u.scale)) return -1;
+                if (denoise_guided(h, call_seq(a, true), a->scale, a->scratch, idx2, s, &u.x0_uncond, &u.scale, true)) return -1;
                 u.kind = 5; u.step_index_eps = idx2; u.x_eps = a->scratch; u.eps_hist[0] = slot(0); u.pred_prev = slot(1);
                 u.eps_out = nullptr; u.out = a->x; u.pred_xstart = nullptr;
                 return gdx_plms_step(&u, stream);
@@ -688,7 +771,8 @@ extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void
             u.eps_out = slot(k);
             for (int j = 0; j < u.kind - 1; ++j) u.eps_hist[j] = slot(k - 1 - j);
             return gdx_plms_step(&u, stream);
-        });
+        },
+        true);
 }
 
 // dpm_solver_sample_loop (DPM-Solver++ multistep, gdx.h): one fused dpm_step_kernel launch per step (sampler.hip)
@@ -732,13 +816,19 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         return fail("gdx_sample_loop: ddim_sample_loop supports neither const_noise nor dump_steps");  // :903-906
     hipStream_t s = (hipStream_t)stream;
     const int B = h->B;
+    const int last_idx = a->run_steps > 0 && a->run_steps <= a->first_index ? a->first_index - a->run_steps + 1 : 0;
+    // guidance refresh: the guided calls are numbered from the whole loop's first index
+    const bool refresh_on = h->guide_every > 1 && a->mode == GDX_CFG;
+    if (refresh_on && a->first_index + a->k_base >= a->num_steps) return fail("gdx_sample_loop: bad step range");
+    const CallSeq q{a->mode, a->timestep_map, a->first_index + a->k_base, -1, true};        // first: read only when refresh_on
+    if (check_reuse(h, "gdx_sample_loop", q, a->first_index, last_idx)) return -1;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
 
     const int64_t per = (int64_t)h->J * h->T;
     const size_t tape_rows = a->const_noise ? 1 : B;             // samples per step of the noise tape
     int dump_i = 0;
     while (dump_i < a->n_dump && a->dump_steps[dump_i] < a->k_base) ++dump_i;     // entries of earlier blocks
-    auto mode_at = [&](int idx) { return step_mode(h, a->mode, a->timestep_map, idx); };
+    auto mode_at = [&](int idx) { return step_mode(h, q, idx); };
     // (x0_uncond, scale): guided_operands' answer for the step
     auto fill_update = [&](gdx_update_args_t& u, int idx, int k, const float* x0_uncond, const float* scale) {
         u = step_args<gdx_update_args_t>(h, a, idx, x0_uncond, scale);
@@ -749,7 +839,7 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     };
     auto eager_step = [&](int idx, int k) -> int {
         const float *x0u, *sc;
-        if (denoise_guided(h, a, a->x, idx, s, &x0u, &sc)) return -1;
+        if (denoise_guided(h, q, a->scale, a->x, idx, s, &x0u, &sc)) return -1;
         gdx_update_args_t u;
         fill_update(u, idx, k, x0u, sc);
         if (gdx_sampler_update(&u, stream)) return -1;
@@ -768,23 +858,24 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     // ROCm 7.2 (tools/small_loop.py, 1000 steps, B=4 T=60 d=512 fp16): eager 0.307 ms/step, graph replay 0.337 -- the
     // ~65 small kernels of a step are bound by their GPU-side dispatch + ramp, not by host launch time, and a graph
     // node costs slightly more than a stream launch; so it is OFF by default and kept as a switch.
-    const int last_idx = a->run_steps > 0 && a->run_steps <= a->first_index ? a->first_index - a->run_steps + 1 : 0;
     // guidance interval: the modes this call's steps take (all the loop's own mode unless it is GDX_CFG)
     const int mode0 = mode_at(a->first_index);
     bool uniform = true, any_guided = false;
     for (int i = a->first_index; i >= last_idx; --i) {
         const int m = mode_at(i);
         uniform = uniform && m == mode0;
-        any_guided = any_guided || m == GDX_CFG;
+        any_guided = any_guided || m >= GDX_CFG;
     }
     // Token-major fast path (sampler.hip, update_tm_kernel): with nothing but the noise tape living in the reference layout
     // (no inpainting, no dumps; the tape is read in place), the state stays in the input GEMM's operand layout for the whole
     // call -- one transpose in front, none per step (2 launches and ~40 MB per step less), the last update also writes the
     // sample in the reference layout.  Bit-identical to the general path (tests: fused Philox loop == step-wise Philox loop).
-    // the guidance rescale has no token-major variant: a call that rescales a step takes the general path
+    // the guidance rescale has no token-major variant: a call that rescales a step takes the general path; nor has the guidance
+    // refresh, whose calls also run eagerly under graph replay (the stored difference is host-tracked state)
     const bool rescales = h->guide_phi > 0.0f && any_guided;
+    const bool refreshes = h->guide_every > 1 && any_guided;
     if (!((uintptr_t)a->noise_tape & 15) && !a->inpaint_mask && !a->n_dump && !h->graph_replay && !h->keep_taps && h->T % 4 == 0 &&
-        !rescales) {
+        !rescales && !refreshes) {
         // guided loop: the state holds both halves (the same x feeds both passes).  An unguided step reads and writes the cond
         // half and mirrors into the uncond half only when the NEXT step of this call is guided (every call transposes the
         // state in afresh); a call without a guided step keeps one half, like a loop that is not guided at all.
@@ -816,7 +907,7 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         return 0;
     }
     // the graph is ONE captured step: only a call whose steps all take the same mode can replay it
-    const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8 && uniform;
+    const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8 && uniform && !refreshes;
     int idx = a->first_index, k = a->k_base;
     if (want_graph) {
         if (eager_step(idx, k)) return -1;                        // step 0 eagerly: it also sets every kernel attribute

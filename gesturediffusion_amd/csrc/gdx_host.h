@@ -130,6 +130,9 @@ struct gdx_model {
     float guide_phi = 0.f;            // gdx_set_guidance_rescale: 0 = off
     double* rs_part = nullptr;        // guidance rescale: chunk sums [B][chunks][4] and factors [B], allocated on first use
     float* rs_factor = nullptr;
+    int guide_every = 1;              // gdx_set_guidance_refresh: the unconditional pass runs on every guide_every-th guided call
+    float* gd = nullptr;              // guidance refresh: the stored difference c - u [B, J, T], allocated on first use
+    bool gd_valid = false;            // ... holds a refresh call's difference under the current conditioning
     int64_t forward_samples = 0;     // gdx_forward_samples: samples pushed through forward_core since gdx_create
     gdx::Act xa, xb, qkv, ctx, tmp, ffb;   // [rows_alloc] token rows: residual stream (xa, xb), sublayer operands and outputs
     gdx::Act xt, xc;                       // token-major pose in / compacted last layer, [2B*T + pad] rows

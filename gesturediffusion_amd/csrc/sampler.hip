@@ -12,6 +12,7 @@
 // NOTE: HIP's __fmul_rn/__fadd_rn are plain * and + and hipcc defaults to -ffp-contract=fast, so this
 // file is compiled with -ffp-contract=off (Makefile) AND carries the pragma below: bit-exactness against
 // the torch expression depends on no mul+add pair being fused.
+#include <algorithm>
 #include <string>
 
 #include "gdx_internal.h"
@@ -785,6 +786,25 @@ __global__ __launch_bounds__(256) void cfg_rescale_apply_kernel(const CfgRescale
     store4<VEC>(a.out, g.e0, g.nval, x0);
 }
 
+// Guidance refresh (gdx.h gdx_cfg_delta): out = fl32(a - b) over `count` elements, the one pass behind both uses -- storing the
+// guidance difference d = c - u on a refresh call and forming u' = c - d on a reuse call.  A thread handles groups of four
+// consecutive elements, grid-strided; VEC: count % 4 == 0 and every pointer 16-byte aligned, else the scalar form, whose last
+// group holds count % 4 elements.  out may alias b (no __restrict__: a thread reads its group before it writes it, and no other
+// thread touches that group).
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_delta_kernel(const float* a, const float* b, float* out, long count, long groups) {
+    const long stride = (long)gridDim.x * 256;
+    for (long grp = (long)blockIdx.x * 256 + threadIdx.x; grp < groups; grp += stride) {
+        const long e0 = 4L * grp;
+        const int nval = VEC ? 4 : (int)min(4L, count - e0);
+        const f32x4 x = load4<VEC>(a, e0, nval), y = load4<VEC>(b, e0, nval);
+        f32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = __fsub_rn(x[i], y[i]);
+        store4<VEC>(out, e0, nval, r);
+    }
+}
+
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
                             float* out, int B, int64_t per_sample, hipStream_t s) {
     const long total = (long)B * per_sample;
@@ -1117,6 +1137,19 @@ extern "C" int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream) {
     if (vec_ok(d.per_sample, d.c, d.u, d.out)) hipLaunchKernelGGL(cfg_rescale_apply_kernel<true>, grid, block, 0, s, d);
     else hipLaunchKernelGGL(cfg_rescale_apply_kernel<false>, grid, block, 0, s, d);
     return launch_status("gdx_cfg_rescale: launch failed");
+}
+
+extern "C" int gdx_cfg_delta(const gdx_cfg_delta_args_t* a, void* stream) {
+    using namespace gdx;
+    if (!a) return gdx_set_error_("gdx_cfg_delta: null argument");
+    if (!a->a || !a->b || !a->out) return gdx_set_error_("gdx_cfg_delta: null argument");
+    if (a->count <= 0) return gdx_set_error_("gdx_cfg_delta: count must be positive");
+    const long count = (long)a->count, groups = (count + 3) / 4;
+    // memory-bound: at most 2048 blocks, the rest grid-strided
+    const dim3 grid((unsigned)std::min(2048L, (groups + 255) / 256)), block(256);
+    if (vec_ok(count, a->a, a->b, a->out)) hipLaunchKernelGGL(cfg_delta_kernel<true>, grid, block, 0, (hipStream_t)stream, a->a, a->b, a->out, count, groups);
+    else hipLaunchKernelGGL(cfg_delta_kernel<false>, grid, block, 0, (hipStream_t)stream, a->a, a->b, a->out, count, groups);
+    return launch_status("gdx_cfg_delta: launch failed");
 }
 
 // internal (api.hip, gdx_bpd_loop): x_t and the stored Philox noise of one step (bpd_xt_kernel)

@@ -446,6 +446,8 @@ class GaussianDiffusion:
             yield from self._fused_loop(kind, model, img, indices, model_kwargs, eta, const_noise, rng, philox_seed,
                                         sample_offset, noise_tape, dump_steps, progress, clip_denoised)
             return
+        self._refuse_refresh(model, model_kwargs, "a loop that runs step by step (fused=False, a progressive generator, "
+                                                  "cond_fn, denoised_fn or a non-native model)")
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
@@ -476,11 +478,13 @@ class GaussianDiffusion:
         guided = isinstance(model, ClassifierFreeSampleModel)
         interval = E.guidance_interval_of(y, guided)
         phi = E.guidance_rescale_of(y, guided)
+        every = E.guidance_refresh_of(y, guided)
         eng = inner._get_engine(x.device)
         eng.prepare(B, T)
         eng.set_condition(y["seed"], y["mfcc"], cache=False)
         eng.set_guidance_interval(interval)          # at every loop; None resets a reused handle to "every timestep"
         eng.set_guidance_rescale(phi)                # likewise: an absent key sets 0 (off)
+        eng.set_guidance_refresh(every)              # likewise: an absent key sets 1 (off); every loop starts with a refresh
         if guided:
             mode, scale = GDX_CFG, E.f32c(y["scale"].reshape(-1), "y['scale']")
         else:
@@ -491,6 +495,14 @@ class GaussianDiffusion:
             motion = E.f32c(y["inpainted_motion"], "inpainted_motion")
             assert mask.shape == motion.shape == x.shape
         return eng, mode, scale, mask, motion
+
+    @staticmethod
+    def _refuse_refresh(model, model_kwargs, who):
+        """A path that calls the model step by step cannot serve y['guidance_refresh'] > 1 (engine.refuse_guidance_refresh)."""
+        from ..model.cfg_sampler import ClassifierFreeSampleModel
+        y = (model_kwargs or {}).get("y")
+        if isinstance(y, dict):
+            E.refuse_guidance_refresh(y, isinstance(model, ClassifierFreeSampleModel), who)
 
     def _runs_fused(self, fused, model, denoised_fn, cond_fn):
         """The route of every sampling loop: inside libgdx for a native START_X denoiser (or its ClassifierFreeSampleModel)
@@ -584,6 +596,28 @@ class GaussianDiffusion:
             return [True] * len(tmap)
         lo, hi = guidance_interval
         return [lo <= t <= hi for t in tmap]
+
+    def guidance_plan(self, guidance_interval=None, guidance_refresh=1, plms=False, skip_timesteps=0):
+        """What each denoiser call of a sampling loop does under y['guidance_interval'] / y['guidance_refresh'], in execution
+        order: "off" (unguided: the conditional pass alone), "refresh" (guided, conditional and unconditional pass) or "reuse"
+        (guided, conditional pass alone, the stored difference stands in for the unconditional one).  The loop visits this
+        diffusion's indices num_timesteps - 1 - skip_timesteps .. 0; plms: step 0 makes a second call at the index below the
+        first (modulo num_timesteps), as plms_sample_loop does.  The guided calls are numbered n = 0, 1, ... in this order and
+        call n refreshes when n % guidance_refresh == 0: the rule of gdx_set_guidance_refresh, on the host."""
+        every = E.guidance_refresh_of({"guidance_refresh": guidance_refresh}, True)
+        flags = self.guided_steps(guidance_interval)
+        n_t = self.num_timesteps
+        calls = list(range(n_t - skip_timesteps))[::-1]
+        if plms and calls:
+            calls.insert(1, (calls[0] - 1) % n_t)
+        plan, n = [], 0
+        for i in calls:
+            if not flags[i]:
+                plan.append("off")
+                continue
+            plan.append("refresh" if n % every == 0 else "reuse")
+            n += 1
+        return plan
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
@@ -750,6 +784,7 @@ class GaussianDiffusion:
             raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
         if model_kwargs is None:
             model_kwargs = {}
+        self._refuse_refresh(model, model_kwargs, "calc_bpd_loop (its steps draw independent x_t)")
         self._check_supported()
         xs = E.f32c(x_start, "x_start")
         B, n, dev_ = xs.shape[0], self.num_timesteps, xs.device
@@ -911,6 +946,8 @@ class GaussianDiffusion:
         """The step-by-step form of a multistep sampling loop: yields step(model, x, t, old_out=previous, **step_kw) per
         index.  step_noise: the steps take noise -- entry 1 + k of the tape, or the Philox draw k + 1 (rng == "philox"), or
         the step's own draw from torch's generator."""
+        self._refuse_refresh(model, step_kw.get("model_kwargs"), "a loop that runs step by step (fused=False, a progressive "
+                                                                 "generator, cond_fn, denoised_fn or a non-native model)")
         device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
                                                   philox_seed, sample_offset, noise_tape)
         if progress:

@@ -158,6 +158,11 @@ class Engine:
         with the unscaled ones by phi (gdx_set_guidance_rescale); 0 = off."""
         _lib.check(self.lib.gdx_set_guidance_rescale(self.handle, float(phi)), self.lib)
 
+    def set_guidance_refresh(self, every=1):
+        """every >= 1: the in-library sampling loops run the unconditional pass on every `every`-th guided denoiser call and
+        reuse the stored cond-uncond difference in between (gdx_set_guidance_refresh); 1 = off.  Clears the stored difference."""
+        _lib.check(self.lib.gdx_set_guidance_refresh(self.handle, int(every)), self.lib)
+
     def cfg_rescale(self, c, u, scale, phi, t=None, interval=None, out=None):
         """The stand-alone gdx_cfg_rescale on [B,J,1,T] device tensors -> (out, factor [B]); t (int64 [B]) with interval (lo, hi)
         marks the guided samples (None: all); out may be c itself.  Operands are taken as they are (no copies): tests hand it
@@ -322,7 +327,47 @@ def guidance_rescale_of(y, guided_model):
     return float(phi)
 
 
+def guidance_refresh_of(y, guided_model):
+    """y['guidance_refresh'] validated -> every, a Python int >= 1 (1 when the key is absent: off).  ValueError for anything but
+    a Python int >= 1 -- a bool and a float are refused, and a tensor because reading it would synchronise -- and for a key on
+    a model that is not a ClassifierFreeSampleModel (`guided_model` False)."""
+    if "guidance_refresh" not in y:
+        return 1
+    every = y["guidance_refresh"]
+    if not guided_model:
+        raise ValueError("y['guidance_refresh'] needs a ClassifierFreeSampleModel: this model runs no guidance to refresh")
+    if isinstance(every, torch.Tensor):
+        raise ValueError("y['guidance_refresh'] must be a Python int, not a tensor: reading it would synchronise")
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)):
+        raise ValueError(f"y['guidance_refresh'] must be a Python int >= 1, got {every!r}")
+    if not 1 <= every <= 2**31 - 1:
+        raise ValueError(f"y['guidance_refresh'] must satisfy 1 <= every < 2**31, got {every!r}")
+    return int(every)
+
+
+def refuse_guidance_refresh(y, guided_model, who):
+    """The guidance refresh needs memory across denoiser calls, which only the in-library loops have: ValueError when
+    y['guidance_refresh'] > 1 reaches `who`, a path that makes every call on its own."""
+    every = guidance_refresh_of(y, guided_model)
+    if every > 1:
+        raise ValueError(f"y['guidance_refresh'] = {every} needs the in-library loop (p_sample_loop, ddim_sample_loop, "
+                         f"plms_sample_loop, dpm_solver_sample_loop or dpm_solver_sde_sample_loop with fused=True on a native "
+                         f"model, without cond_fn / denoised_fn): {who} cannot carry the guidance difference from one call to "
+                         f"the next")
+
+
 # ---------------------------------------------------------------------- standalone kernels
+def cfg_delta(a, b, out=None, count=None):
+    """The stand-alone gdx_cfg_delta: out = a - b (fp32) over the first `count` elements (default: all of a) of device tensors
+    taken as they are (no copies: tests hand it misaligned views); out may be b itself."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(a)
+    args = _lib.CfgDeltaArgs(count=a.numel() if count is None else count, a=a.data_ptr(), b=b.data_ptr(), out=out.data_ptr())
+    _lib.check(lib.gdx_cfg_delta(C.byref(args), _stream(a.device)), lib)
+    return out
+
+
 def sampler_update(kind, coef, x, x0_cond, out, t=None, step_index=0, x0_uncond=None, scale=None, inpaint_mask=None,
                    inpaint_motion=None, noise=None, const_noise=False, philox_seed=0, sample_offset=0, rng_step=0,
                    pred_xstart=None, cond_grad=None, cond_coef=None, clip_denoised=False):

@@ -49,7 +49,8 @@ def resolve_rng(rng, world):
 
 def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames, seed_poses, guidance_param=1.0,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
-                  on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0):
+                  on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
+                  guidance_refresh=1):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -57,11 +58,17 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     and DPM-Solver++ ("dpmpp") samplers draw nothing after x_T and take entry 0 of a tape as that, the stochastic
     DPM-Solver++ ("dpmpp_sde": order `dpm_order`, 1 or 2, noise scale `eta`) draws per step like "p" and is handed the whole
     tape.  guidance_interval (lo, hi): guidance only on model timesteps lo <= t <= hi (y['guidance_interval']; needs
-    guidance_param != 1).  guidance_rescale phi > 0: the guidance rescale (y['guidance_rescale']; needs guidance_param != 1)."""
+    guidance_param != 1).  guidance_rescale phi > 0: the guidance rescale (y['guidance_rescale']; needs guidance_param != 1).
+    guidance_refresh k > 1: the unconditional pass on every k-th guided denoiser call, the stored cond-uncond difference in
+    between (y['guidance_refresh']; needs guidance_param != 1); each chunk is its own loop and starts with a refresh."""
     if guidance_interval is not None and guidance_param == 1:
         raise ValueError("guidance_interval needs guidance_param != 1: without guidance there is nothing to limit")
     if guidance_rescale > 0 and guidance_param == 1:
         raise ValueError("guidance_rescale needs guidance_param != 1: without guidance there is nothing to rescale")
+    if isinstance(guidance_refresh, bool) or not isinstance(guidance_refresh, int) or guidance_refresh < 1:
+        raise ValueError(f"guidance_refresh must be an int >= 1, got {guidance_refresh!r}")
+    if guidance_refresh > 1 and guidance_param == 1:
+        raise ValueError("guidance_refresh needs guidance_param != 1: without guidance there is nothing to refresh")
     b, J = first_seed.shape[0], first_seed.shape[1]
     sample_fn = {"p": diffusion.p_sample_loop, "ddim": diffusion.ddim_sample_loop, "plms": diffusion.plms_sample_loop,
                  "dpmpp": diffusion.dpm_solver_sample_loop, "dpmpp_sde": diffusion.dpm_solver_sde_sample_loop}[sampler]
@@ -74,6 +81,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             y["guidance_interval"] = (int(guidance_interval[0]), int(guidance_interval[1]))
         if guidance_rescale > 0:
             y["guidance_rescale"] = float(guidance_rescale)
+        if guidance_refresh > 1:
+            y["guidance_refresh"] = guidance_refresh
         kw = dict(clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=0, init_image=None, progress=progress,
                   noise=None, rng=rng, philox_seed=philox_seed + 1000 * chunk, sample_offset=sample_offset,
                   noise_tape=noise_tapes[chunk] if noise_tapes is not None else None)
@@ -212,12 +221,15 @@ def main(argv=None):
         print(f"### guidance on {sum(flags)} of {len(flags)} steps (model timesteps {interval[0]}..{interval[1]})")
     if args.guidance_rescale > 0 and rank == 0:
         print(f"### guidance rescale {args.guidance_rescale:.2f}")
+    if args.guidance_refresh > 1 and rank == 0:
+        plan = diffusion.guidance_plan(interval, args.guidance_refresh, plms=args.sampler == "plms")
+        print(f"### unconditional pass on {plan.count('refresh')} of {len(plan) - plan.count('off')} guided calls")
     outs = sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, args.chunks, T, args.seed_poses,
                          guidance_param=args.guidance_param, sampler=args.sampler,
                          eta=args.dpm_eta if args.sampler == "dpmpp_sde" else args.eta, rng=rng,
                          philox_seed=args.seed, sample_offset=lo, progress=args.progress and rank == 0, on_chunk=on_chunk,
                          plms_order=args.plms_order, dpm_order=args.dpm_order, guidance_interval=interval,
-                         guidance_rescale=args.guidance_rescale)
+                         guidance_rescale=args.guidance_rescale, guidance_refresh=args.guidance_refresh)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

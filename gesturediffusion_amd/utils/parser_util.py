@@ -50,6 +50,12 @@ def parse_and_load_from_model(parser, argv=None):
         parser.error("--guidance_rescale must lie in [0, 1]")
     if args.guidance_rescale > 0 and args.guidance_param == 1:
         parser.error("--guidance_rescale needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
+    if args.guidance_refresh is not None and args.guidance_refresh < 1:
+        parser.error("--guidance_refresh must be at least 1")
+    if args.guidance_refresh is not None and args.guidance_param == 1:
+        parser.error("--guidance_refresh needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
+    if args.guidance_refresh is None:
+        args.guidance_refresh = 1
     return args
 
 
@@ -154,6 +160,10 @@ def add_native_options(parser):
                        help="Guidance rescale (Lin et al. 2023): scale each guided x0 prediction to the conditional one's "
                             "per-sample standard deviation and mix it with the unscaled one by PHI in [0, 1]; 0 = off. "
                             "Every sampler; an error with --guidance_param 1.")
+    group.add_argument("--guidance_refresh", default=None, type=int, metavar="K",
+                       help="Guidance refresh: run the unconditional pass only on every K-th guided denoiser call of a chunk's "
+                            "loop and reuse the stored cond-uncond difference in between (1 = every call, the default). "
+                            "Every sampler; an error with --guidance_param 1 or K < 1.")
     group.add_argument("--rng", default=None, choices=['torch', 'philox'],
                        help="torch = the reference's generator and draw order (single-GPU default); philox = in-kernel "
                             "counter-based noise keyed by the global sample index (shard invariant; multi-GPU default).")

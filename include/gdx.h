@@ -177,6 +177,49 @@ typedef struct {
 } gdx_cfg_rescale_args_t;
 int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream);
 
+/* Guidance refresh (the cond-uncond difference reused between guided calls, after "compress guidance" / CFG-cache samplers;
+ * no counterpart in the reference): the unconditional pass runs only on every `every`-th guided denoiser call of a loop, the
+ * calls in between reuse the stored difference d = c - u.  every = 1 (the state after gdx_create) is the behaviour without
+ * the feature: nothing new is launched and every result keeps its bits.  One rule everywhere:
+ *   Number the loop's guided denoiser calls n = 0, 1, 2, ... in execution order.  A call is guided when the loop's mode is
+ *   GDX_CFG and the call's model timestep passes the handle's guidance interval.  gdx_plms_loop's first step makes two calls,
+ *   at index i and then at (i - 1) mod num_steps; each is numbered on its own timestep, like any other call.
+ *   refresh call (n % every == 0): exactly the guided call of every = 1 -- the 2 * batch forward, raw outputs c and u -- and in
+ *     addition d_i = fl32(c_i - u_i) is stored for every element of the batch; then the step continues unchanged (the step
+ *     kernel blends, or gdx_cfg_rescale runs when phi > 0).  A refresh step's output has the bits of every = 1.
+ *   reuse call (otherwise): the denoiser runs as GDX_COND on batch samples -- the unconditional pass is never computed,
+ *     gdx_forward_samples advances by batch -- and u'_i = fl32(c_i - d_i) is written where the unconditional half of the
+ *     output would be; the step continues exactly like a guided step with operands (c, u', scale): the blend u' + s*(c - u')
+ *     in the unchanged step kernel, or the unchanged rescale when phi > 0.  Inpainting, clip_denoised, the noise and the
+ *     multistep history follow, untouched.
+ *   unguided calls (outside the interval) are neither counted nor changed.
+ * State: the stored difference belongs to the handle (first use allocates it, gdx_prepare resets it) and carries a validity
+ * flag that a refresh sets and gdx_prepare, gdx_set_condition and gdx_set_guidance_refresh clear.  A reuse call without a
+ * valid difference is refused before anything is launched: a block-wise call must continue the loop that stored the
+ * difference.  Block-wise issue (run_steps / k_base): the host derives the n of a call from timestep_map, the whole loop's
+ * first index first_index + k_base and, for gdx_plms_loop, the second call of step 0 -- no counter lives in the handle -- so
+ * issue in blocks gives the bits of one call.
+ * It applies in gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop and gdx_dpm_sde_loop.  There is no token-major variant: a
+ * gdx_sample_loop call with every > 1 and at least one guided step takes the pose-layout path (two transposes per step more
+ * than the token-major path), and graph replay runs such a call eagerly.  gdx_forward and gdx_bpd_loop keep every guided call a
+ * full one and never touch the stored difference: the step-wise forward has no memory, and the bound's steps draw independent
+ * x_t.  How far the result moves from the fully guided loop depends on the model; nothing is claimed about a trained
+ * checkpoint.
+ * gdx_set_guidance_refresh: every < 1 or a null handle is refused before any HIP call. */
+int gdx_set_guidance_refresh(gdx_handle_t h, int32_t every);
+
+/* The stand-alone pass behind both uses, one launch on `stream`: out_i = fl32(a_i - b_i) for i < count, a plain fp32
+ * subtraction (store: a = c, b = u; apply: a = c, b = d).  128-bit accesses when count % 4 == 0 and every pointer is 16-byte
+ * aligned, a scalar path with a tail otherwise; nothing is written past count.  out may alias b.  Refusals (a null struct or
+ * pointer, a non-positive count) come before the first HIP call. */
+typedef struct {
+    int64_t count;
+    const float* a;
+    const float* b;
+    float* out;
+} gdx_cfg_delta_args_t;
+int gdx_cfg_delta(const gdx_cfg_delta_args_t* a, void* stream);
+
 /* Host-side count of the samples pushed through the denoiser since gdx_create: every forward adds the batch it ran (2 * batch
  * under guidance, batch otherwise; a replayed graph step counts like an eager one).  Issues no GPU work: a test reads off it
  * that an unguided step skipped the unconditional pass instead of computing and discarding it. */
