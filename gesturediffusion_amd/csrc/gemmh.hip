@@ -5,14 +5,20 @@
 // Same skeleton as gemm2.hip (one 512-thread workgroup per CU walking tiles lid, lid+G, ...; waves 0-3 run
 // ds_read_b128 + MFMA and store their accumulators straight from registers, waves 4-7 only issue LDS-DMA), re-cut
 // for v_mfma_f32_16x16x32_f16, which is 16x the fp32 MFMA rate, so everything around the MFMA had to shrink:
-//   * K slab = 32 halves = ONE MFMA k-step; LDS rows are 64 B, un-padded (an LDS-DMA piece is 1 KiB lane-linear,
-//     so rows cannot be padded); bank conflicts are removed by permuting the four 16-B chunks of a row,
-//     phys = chunk ^ ((-(row >> sh)) & 3), applied on the DMA *source* address and on the fragment read address.
-//     With ds_read_b128's lane groups {0-3,12-15,20-27},{4-11,16-19,28-31} (+32) every group then touches all
-//     64 banks exactly once (MI355X_MICROARCH.md, LDS table);
-//   * a 6-stage ring of 24 KiB stages (128 x 256 tile) keeps three slabs of DMA in flight across the per-slab
-//     barrier (counted s_waitcnt vmcnt, raw s_barrier): a slab is issued four steps (about 2 000 cycles) before
-//     its first read;
+//   * K slab = 64 halves = TWO MFMA k-steps, staged as WHOLE 128-byte lines: LDS rows are 128 B, un-padded (an LDS-DMA
+//     piece is 1 KiB lane-linear = 8 rows x 128 B, so rows cannot be padded); bank conflicts are removed by permuting the
+//     eight 16-B chunks of a row, phys = chunk ^ (((row >> 1) ^ (row >> 3)) & 7), applied on the DMA *source* address and on
+//     the fragment read address.  Every ds_read_b128 lane group {0-3,12-15,20-27},{4-11,16-19,28-31} (+32) then touches all
+//     64 banks exactly once for both operands' row maps (MI355X_MICROARCH.md, LDS table; the map was searched by brute
+//     force over XOR-linear maps, tools/probe notes in DESIGN.md).  Why whole lines: a piece that takes 64 bytes from each
+//     of 16 rows (the 32-deep slabs this file began with) fetches every line twice, half at a time, and the CU's
+//     vector-memory pipe sustains only 25 B/clk for such pieces (17 KB per 696 cycles; tools/probe/dma_probe: 50 against
+//     78 GB/s per CU for pieces of 8 whole lines), which bound the kernel at the staging rate;
+//   * three slab slots of (16 MB + 64 NBW) * 128 bytes (48 KiB for the 128 x 256 tile): the slab being read, the slab
+//     that has landed, the slab in flight.  ONE barrier per 64-deep slab (counted s_waitcnt vmcnt, raw s_barrier): with
+//     18-32 MFMAs per k-step and wave (288-512 cycles) a wait + barrier per k-step was as long as the arithmetic (stamps
+//     at M = 8 336, tile 144 x 128: 693 cycles per k-step against 288 of MFMA issue).  Both k-steps' fragments are read
+//     after the barrier, the second between the first one's MFMAs;
 //   * the MFMA runs "swapped": the weight fragment is the A operand and the activation fragment the B operand, so
 //     the accumulator has the output ROW on the lane (lane & 15) and output columns in its registers.  The W rows
 //     are dealt to the lanes as n = q*4*NBW + j*4 + e (q = lane >> 4 of the accumulator, j = column block,
@@ -21,7 +27,7 @@
 //     instead of 16*NBW 2-byte stores, and the token-row map / residual terms of the boundary linears are
 //     one division and NBW float4 loads per row;
 //   * the A operand's buffer descriptor carries the exact size, so rows past M read as zeros and are never stored.
-// Summation order per output element is k-slab by k-slab and independent of the tile shape.
+// Summation order per output element is k ascending by 32 (one MFMA k-step) and independent of the tile shape.
 #include "gdx_internal.h"
 #include "gdx_device.h"
 
@@ -64,7 +70,6 @@ __device__ __forceinline__ f32x2 gelu2(f32x2 x) {
 template <int NBW>
 struct ColMap {
     static constexpr int QS = NBW == 1 ? 4 : 8;                                  // columns between quads
-    static constexpr int QSH = NBW == 1 ? 2 : 3;                                 // log2(QS): the W rows' swizzle shift
     __host__ __device__ static constexpr int blk(int j) { return NBW == 1 ? 0 : (j >> 1) * 32 + (j & 1) * 4; }
 };
 
@@ -156,27 +161,97 @@ __device__ __forceinline__ void sched_interleave() {
     }
 }
 
-// PAIR (round 2): one barrier per TWO 32-deep slabs.  With 18-32 MFMAs per slab and wave (288-512 cycles) the per-slab
-// lgkmcnt wait + barrier was as long as the arithmetic (stamps at M = 8 336, tile 144x128: 693 cycles per slab against 288 of
-// MFMA issue).  The loaders then run two pairs ahead (ring of 6: the pair being read, the pair that has landed, the pair in
-// flight), and a pair's first fragment group is read after the barrier instead of across it.  The pair is staged as ONE 64-deep
-// slab of whole 128-byte lines (gemmh8b_kernel's LDS image): the half-line pieces of the 32-deep slabs bound the per-slab
-// kernel at the staging rate (17 KB per 696 cycles = 25 B/clk; tools/probe/dma_probe: 50 against 78 GB/s per CU).
-template <int MB, int NBW, int NST, bool PAIR>
+// ---------------------------------------------------------------------------------------------------------------
+// The whole-line LDS image, written once for both kernels below.  A staged operand is rows of 128 B (64 halves of K); a DMA
+// piece is 8 rows x 128 B = 1 KiB, lane-linear in LDS (lane -> row lane >> 3, chunk lane & 7).
+
+// chunk c of row r is stored at c ^ gh_line_swz(r)
+__device__ __forceinline__ int gh_line_swz(int r) { return ((r >> 1) ^ (r >> 3)) & 7; }
+
+// per-lane source byte offset of the piece whose first row is row0 (ld = the operand's row stride in halves): the LDS chunk
+// lane & 7 holds the row's chunk (lane & 7) ^ swizzle
+__device__ __forceinline__ int gh_piece_voff(int row0, int lane, int ld) {
+    const int r = row0 + (lane >> 3);
+    return r * ld * 2 + (((lane & 7) ^ gh_line_swz(r)) * 16);
+}
+
+// A fragments of a wave's rows 16 i + l15 (+ a multiple of 128): swizzle ((l15 >> 1) & 7) ^ (l15 >> 3) ^ (2 i & 7), chunk of
+// k-step h: 4 h + lq -> a lane part ^ an even constant, so four offsets off[K / 2], K in {0, 2, 4, 6}, cover every read;
+// gh_ksel(h, c) picks the one of k-step h for a row whose compile-time swizzle part is c.  row_bytes: the byte offset of row l15.
+__device__ __forceinline__ void gh_frag_a_offsets(int (&off)[4], int row_bytes, int l15, int lq) {
+    const int laneA = lq ^ ((l15 >> 1) & 7) ^ (l15 >> 3);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) off[k] = row_bytes + ((laneA ^ (2 * k)) << 4);
+}
+__host__ __device__ constexpr int gh_ksel(int h, int c) { return ((4 * h) ^ (c & 7)) >> 1; }
+
+template <int H, int MB>
+__device__ __forceinline__ void gh_read_a(f16x8 (&fa)[MB], const char* S, const int (&off)[4]) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i) fa[i] = *reinterpret_cast<const f16x8*>(S + off[gh_ksel(H, 2 * i)] + i * 2048);
+}
+
+template <int MB, int NBW>
+__device__ __forceinline__ void gh_mm(f32x4 (&acc)[MB][NBW], const f16x8 (&fa)[MB], const f16x8 (&fw)[NBW]) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < NBW; ++j) acc[i][j] = GDX_MFMA16(fw[j], fa[i], acc[i][j], 0, 0, 0);
+}
+
+template <int MB, int NBW>
+__device__ __forceinline__ void gh_clear(f32x4 (&acc)[MB][NBW]) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < NBW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// End of a K step of an MFMA wave: (all but the youngest VM of the wave's DMA pieces landed,) fragment reads done, barrier.
+// The lgkmcnt wait and the barrier are builtins (not inline asm) so that the compiler's waitcnt pass knows the fragment reads
+// have completed and inserts no conservative waits in front of the next step's MFMAs, and sched_barrier pins the sequence
+// behind the step's MFMAs (as inline asm it was hoisted above them, leaving the LDS latency of the 12 fragment reads exposed
+// in every step: 1050 cycles per step instead of ~550).
+template <int VM = -1>
+__device__ __forceinline__ void gh_step_sync() {
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (VM >= 0) wait_vm<VM>();
+    __builtin_amdgcn_s_waitcnt(0xc07f);                           // lgkmcnt(0)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");                                // LDS contents change across the barrier (DMA)
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// The ti-th tile of workgroup lid's walk lid, lid + G, ...; the DMA runs ahead of the MFMAs and so asks past the last tile:
+// harmless re-reads of the last one.
+__device__ __forceinline__ int gh_walk_tile(int lid, int ti, int my_tiles, int G) {
+    return lid + (ti < my_tiles ? ti : my_tiles - 1) * G;
+}
+
+// Geometry of the 4 + 4-wave kernel's tile (MB 16-row blocks x NBW 16-column blocks per MFMA wave), for the kernel, its
+// launcher and the dispatcher: three slab slots of (A rows + W rows) x 128 B, then the bias.
+template <int MB_, int NBW_>
+struct GhGeom {
+    static constexpr int MB = MB_, NBW = NBW_, BM = MB * 16, WN = NBW * 16, BN = WN * 4;
+    static constexpr int NSLOT = 3, A_BYTES = BM * 128, SLOT_BYTES = (BM + BN) * 128;
+    static constexpr int A_P = BM / 8, P = (BM + BN) / 8, PW = (P + 3) / 4;    // pieces: of A, of a slab, per loader wave
+    static constexpr size_t lds_bytes(int N) { return (size_t)NSLOT * SLOT_BYTES + (size_t)N * 4; }
+    static_assert(NBW == 1 || NBW == 2 || NBW == 4, "NBW must be 1, 2 or 4");
+    static_assert(PW < 64, "vmcnt range");
+};
+
+// Waves 4-7 stage slab after slab (loaders run two slabs ahead of the MFMAs: slots = the slab being read, the slab that has
+// landed, the slab in flight); waves 0-3 read both k-steps' fragments of a slab after the barrier that published it, the
+// second k-step's between the first one's MFMAs.
+template <int MB, int NBW>
 __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, const int ntn, const int ntiles,
                                                        unsigned long long* dbg) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (buffer-resource builtins are device-only)
-    constexpr int BM = MB * 16, WN = NBW * 16, BN = WN * 4;
-    constexpr int A_BYTES = BM * 64, W_BYTES = BN * 64, STAGE_BYTES = A_BYTES + W_BYTES;
-    constexpr int A_P = A_BYTES / 1024, P = STAGE_BYTES / 1024;   // 1 KiB DMA pieces (16 rows x 64 B) per slab
-    constexpr int PW = (P + 3) / 4;                               // pieces per loader wave per slab
-    constexpr int SHW = ColMap<NBW>::QSH;                         // log2(columns between accumulator quads)
-    constexpr int VM_STEP = (NST - 3) * PW;                       // DMA pieces younger than the slab a step waits for
-    static_assert(NBW == 1 || NBW == 2 || NBW == 4, "NBW must be 1, 2 or 4");
-    static_assert(NST >= 3 && VM_STEP < 64, "ring depth / vmcnt range");
-    static_assert(!PAIR || (NST == 6 && 2 * PW < 64), "the pair protocol is written for a ring of six");
+    using Geo = GhGeom<MB, NBW>;
+    constexpr int BM = Geo::BM, WN = Geo::WN, BN = Geo::BN, A_BYTES = Geo::A_BYTES, SLOT_BYTES = Geo::SLOT_BYTES;
+    constexpr int A_P = Geo::A_P, P = Geo::P, PW = Geo::PW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* const bias_lds = reinterpret_cast<float*>(smem + NST * STAGE_BYTES);
+    float* const bias_lds = reinterpret_cast<float*>(smem + Geo::NSLOT * SLOT_BYTES);
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
@@ -185,8 +260,8 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
     const int G = gridDim.x;
     const int lid = xcd_lid((int)blockIdx.x, G);                  // XCD-aware bijective remap (blocks b, b+8, ... share an XCD)
     const int my_tiles = lid < ntiles ? (ntiles - lid + G - 1) / G : 0;
-    const int nk = p.K / 32;
-    const int total = my_tiles * nk;                              // even: K % 64 == 0
+    const int nk = p.K / 64;                                      // 64-deep slabs per tile
+    const int total = my_tiles * nk;
     if (total == 0) return;
 
     if (wave < 4)
@@ -202,17 +277,14 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
             int piece = (wave & 3) + 4 * i;
             piece = piece < P ? piece : P - 1;                    // surplus issues re-write the last piece (same bytes)
             const bool isA = piece < A_P;
-            const int row = (isA ? piece : piece - A_P) * 16 + (lane >> 2);
-            const int g = (-(row >> (isA ? 2 : SHW))) & 3;
-            const int chunk = (lane & 3) ^ g;
-            voff[i] = row * (isA ? p.lda : p.ldw) * 2 + chunk * 16;
+            voff[i] = gh_piece_voff((isA ? piece : piece - A_P) * 8, lane, isA ? p.lda : p.ldw);
         }
         int ld_tile_i = 0, ld_ks = 0;                             // next slab to issue
         int ld_m0 = (lid / ntn) * BM, ld_n0 = (lid % ntn) * BN;
-        auto issue = [&](int stage) {                             // exactly PW DMA instructions, no VALU
-            const int a_so = (ld_m0 * p.lda + ld_ks * 32) * 2;
-            const int w_so = (ld_n0 * p.ldw + ld_ks * 32) * 2;
-            char* sb = smem + stage * STAGE_BYTES;
+        auto issue = [&](int slot) {                              // exactly PW DMA instructions, no VALU
+            const int a_so = (ld_m0 * p.lda + ld_ks * 64) * 2;
+            const int w_so = (ld_n0 * p.ldw + ld_ks * 64) * 2;
+            char* sb = smem + slot * SLOT_BYTES;
 #pragma unroll
             for (int i = 0; i < PW; ++i) {
                 int piece = (wave & 3) + 4 * i;
@@ -226,215 +298,88 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
             asm volatile("" ::: "memory");                        // keep the DMA issue where it is (counted waits)
             if (++ld_ks == nk) {
                 ld_ks = 0;
-                ++ld_tile_i;
-                const int ti = ld_tile_i < my_tiles ? ld_tile_i : my_tiles - 1;   // past the end: harmless re-reads
-                const int tile = lid + ti * G;
+                const int tile = gh_walk_tile(lid, ++ld_tile_i, my_tiles, G);
                 ld_m0 = (tile / ntn) * BM;
                 ld_n0 = (tile % ntn) * BN;
             }
         };
-        if constexpr (PAIR) {
-            // 64-deep slabs staged as WHOLE 128-byte lines (the image of gemmh8b_kernel): a piece is 8 rows x 128 B, chunk c of
-            // row r sits at c ^ (((r >> 1) ^ (r >> 3)) & 7); three slab slots of 2 * STAGE_BYTES.
-            constexpr int P2 = (BM + BN) / 8, A_P2 = BM / 8, PW2 = (P2 + 3) / 4, A2_BYTES = BM * 128;
-            static_assert(PW2 < 64, "vmcnt range");
-            int voff2[PW2];
-#pragma unroll
-            for (int i = 0; i < PW2; ++i) {
-                int piece = (wave & 3) + 4 * i;
-                piece = piece < P2 ? piece : P2 - 1;              // surplus issues re-write the last piece (same bytes)
-                const bool isA = piece < A_P2;
-                const int r = (isA ? piece : piece - A_P2) * 8 + (lane >> 3);
-                const int sw = ((r >> 1) ^ (r >> 3)) & 7;
-                voff2[i] = r * (isA ? p.lda : p.ldw) * 2 + (((lane & 7) ^ sw) * 16);
-            }
-            const int nk2 = nk >> 1;
-            auto issue2 = [&](int slot) {
-                const int a_so = (ld_m0 * p.lda + ld_ks * 64) * 2;
-                const int w_so = (ld_n0 * p.ldw + ld_ks * 64) * 2;
-                char* sb = smem + slot * 2 * STAGE_BYTES;
-#pragma unroll
-                for (int i = 0; i < PW2; ++i) {
-                    int piece = (wave & 3) + 4 * i;
-                    piece = piece < P2 ? piece : P2 - 1;
-                    if (piece < A_P2)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_ptr_t)(sb + piece * 1024), 16, voff2[i], a_so, 0, 0);
-                    else
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcW, (lds_ptr_t)(sb + A2_BYTES + (piece - A_P2) * 1024), 16,
-                                                                 voff2[i], w_so, 0, 0);
-                }
-                asm volatile("" ::: "memory");
-                if (++ld_ks == nk2) {
-                    ld_ks = 0;
-                    ++ld_tile_i;
-                    const int ti = ld_tile_i < my_tiles ? ld_tile_i : my_tiles - 1;   // past the end: harmless re-reads
-                    const int tile = lid + ti * G;
-                    ld_m0 = (tile / ntn) * BM;
-                    ld_n0 = (tile % ntn) * BN;
-                }
-            };
-            issue2(0);
-            issue2(1);
-            wait_vm<PW2>();                                     // slab 0 has landed
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            int wst = 2;
-            for (int g = 0; g < total; g += 2) {
-                issue2(wst);                                      // slab g/2 + 2 -> the slot of the slab consumed before the last barrier
-                wst = wst == 2 ? 0 : wst + 1;
-                wait_vm<PW2>();                                 // slab g/2 + 1 has landed
-                asm volatile("s_barrier" ::: "memory");
-            }
-            wait_vm<0>();
-            return;
-        }
-#pragma unroll
-        for (int s = 0; s < NST - 1; ++s) issue(s);
-        wait_vm<VM_STEP>();
+        issue(0);
+        issue(1);
+        wait_vm<PW>();                                            // slab 0 has landed
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        int wst = NST - 1;
-        if (dbg) {                                                // diagnostic build path (GDX_GEMM_DEBUG): where a loader spends its cycles
-            unsigned long long t_issue = 0, t_wait = 0, t_bar = 0;
-            const unsigned long long t_begin = __builtin_amdgcn_s_memtime(), r_begin = __builtin_amdgcn_s_memrealtime();
+        // One step per slab; with the stamped tag (GDX_GEMM_DEBUG, dbg != nullptr) it also records where a loader spends its
+        // cycles.  Only the loader waves branch on dbg.
+        auto steps = [&](auto stamped) {
+            constexpr bool ST = decltype(stamped)::value;
+            unsigned long long t_issue = 0, t_wait = 0, t_bar = 0, t_begin = 0, r_begin = 0, t0 = 0, t1 = 0, t2 = 0;
+            if constexpr (ST) { t_begin = __builtin_amdgcn_s_memtime(); r_begin = __builtin_amdgcn_s_memrealtime(); }
+            int wst = 2;
             for (int g = 0; g < total; ++g) {
-                const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-                issue(wst);
-                wst = wst == NST - 1 ? 0 : wst + 1;
-                const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-                wait_vm<VM_STEP>();
-                const unsigned long long t2 = __builtin_amdgcn_s_memtime();
+                if constexpr (ST) t0 = __builtin_amdgcn_s_memtime();
+                issue(wst);                                       // slab g + 2 -> the slot of the slab consumed before the last barrier
+                wst = wst == 2 ? 0 : wst + 1;
+                if constexpr (ST) t1 = __builtin_amdgcn_s_memtime();
+                wait_vm<PW>();                                    // slab g + 1 has landed
+                if constexpr (ST) t2 = __builtin_amdgcn_s_memtime();
                 asm volatile("s_barrier" ::: "memory");
-                const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-                t_issue += t1 - t0; t_wait += t2 - t1; t_bar += t3 - t2;
+                if constexpr (ST) { t_issue += t1 - t0; t_wait += t2 - t1; t_bar += __builtin_amdgcn_s_memtime() - t2; }
             }
-            if (blockIdx.x == 0 && tid == 256) {
-                dbg[0] = t_issue; dbg[1] = t_wait; dbg[2] = t_bar; dbg[3] = (unsigned long long)total;
-                dbg[4] = __builtin_amdgcn_s_memtime() - t_begin;
-                dbg[5] = __builtin_amdgcn_s_memrealtime() - r_begin;   // 100 MHz
+            if constexpr (ST) {
+                if (blockIdx.x == 0 && tid == 256) {
+                    dbg[0] = t_issue; dbg[1] = t_wait; dbg[2] = t_bar; dbg[3] = (unsigned long long)total;
+                    dbg[4] = __builtin_amdgcn_s_memtime() - t_begin;
+                    dbg[5] = __builtin_amdgcn_s_memrealtime() - r_begin;   // 100 MHz
+                }
             }
-            wait_vm<0>();
-            return;
-        }
-        for (int g = 0; g < total; ++g) {
-            issue(wst);                                           // slab g+NST-1 -> the stage freed by the last barrier
-            wst = wst == NST - 1 ? 0 : wst + 1;
-            wait_vm<VM_STEP>();                                 // slab g+2 has landed
-            asm volatile("s_barrier" ::: "memory");
-        }
+        };
+        if (dbg) steps(std::true_type{}); else steps(std::false_type{});
         wait_vm<0>();
         return;
     }
 
-    // ---- consumer state --------------------------------------------------------------------------------------
+    // ================================================================== MFMA waves
     f32x4 acc[MB][NBW];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NBW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int gq = (-(l15 >> 2)) & 3;
-    const int a_off = l15 * 64 + ((lq ^ gq) * 16);                                   // activation fragment, bytes
-    const int w_off = A_BYTES + (wave * WN + (l15 >> 2) * ColMap<NBW>::QS + (l15 & 3)) * 64 + ((lq ^ gq) * 16);
+    gh_clear(acc);
     f16x8 fa0[MB], fw0[NBW], fa1[MB], fw1[NBW];
-    auto rd = [&](f16x8 (&fa)[MB], f16x8 (&fw)[NBW], int stage) {
-        const char* S = smem + stage * STAGE_BYTES;
-#pragma unroll
-        for (int j = 0; j < NBW; ++j) fw[j] = *reinterpret_cast<const f16x8*>(S + w_off + ColMap<NBW>::blk(j) * 64);
-#pragma unroll
-        for (int i = 0; i < MB; ++i) fa[i] = *reinterpret_cast<const f16x8*>(S + a_off + i * 1024);
-    };
-    auto mm = [&](const f16x8 (&fa)[MB], const f16x8 (&fw)[NBW]) {
-#pragma unroll
-        for (int i = 0; i < MB; ++i)
-#pragma unroll
-            for (int j = 0; j < NBW; ++j)
-                acc[i][j] = GDX_MFMA16(fw[j], fa[i], acc[i][j], 0, 0, 0);
-    };
-    int ks = 0, stage = 0, tile_i = 0;
+    int ks = 0, slot = 0, tile_i = 0;
     auto epilogue = [&]() {
         const int tile = lid + tile_i * G;
         ++tile_i;
         wave_epilogue<MB, NBW>(p, acc, bias_lds, (tile / ntn) * BM, (tile % ntn) * BN + wave * WN, l15, lq);
     };
-
-    // End of a K step.  The wait and the barrier are builtins (not inline asm) so that the compiler's waitcnt pass
-    // knows the fragment reads have completed and inserts no conservative waits in front of the next step's MFMAs,
-    // and sched_barrier pins the pair behind the step's MFMAs (as inline asm it was hoisted above them, leaving the
-    // LDS latency of the 12 fragment reads exposed in every step: 1050 cycles per step instead of ~550).
-    auto step_sync = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");                            // LDS contents change across the barrier (DMA)
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // One K step: the MB + NBW fragment reads of the NEXT slab are spread between this slab's MB * NBW MFMAs
-    // (an MFMA holds the SIMD's vector issue for only half of its 16 cycles, so a ds_read in its shadow is free,
-    // while a block of 12 reads in front of the MFMAs idles the matrix pipe for ~100 cycles per step).
-    auto interleave = [&]() { sched_interleave<0, MB + NBW, MB * NBW>(); };
-    step_sync();                                                  // slabs 0 and 1 landed (loaders waited)
-    if constexpr (PAIR) {
-        constexpr int A2_BYTES = BM * 128;
-        // A row 16 i + l15: swizzle ((l15 >> 1) & 7) ^ (l15 >> 3) ^ (2 i & 7); chunk of k-step h: 4 h + lq -> lane part ^ an even
-        // constant, four offsets cover every read.  W row r_j = wave WN + (l15 >> 2) QS + (l15 & 3) + blk(j): swizzle at run time.
-        const int laneA = lq ^ ((l15 >> 1) & 7) ^ (l15 >> 3);
-        int offA[4], offW[NBW][2];
+    gh_step_sync();                                               // slab 0 landed (loaders waited)
+    // A row 16 i + l15.  W row r_j = wave WN + (l15 >> 2) QS + (l15 & 3) + blk(j): its swizzle is taken at run time.
+    int offA[4], offW[NBW][2];
+    gh_frag_a_offsets(offA, l15 * 128, l15, lq);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) offA[k] = l15 * 128 + ((laneA ^ (2 * k)) << 4);
+    for (int j = 0; j < NBW; ++j) {
+        const int r = wave * WN + (l15 >> 2) * ColMap<NBW>::QS + (l15 & 3) + ColMap<NBW>::blk(j);
 #pragma unroll
-        for (int j = 0; j < NBW; ++j) {
-            const int r = wave * WN + (l15 >> 2) * ColMap<NBW>::QS + (l15 & 3) + ColMap<NBW>::blk(j);
-            const int sw = ((r >> 1) ^ (r >> 3)) & 7;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) offW[j][h] = A2_BYTES + r * 128 + (((4 * h + lq) ^ sw) << 4);
-        }
-        auto rd2 = [&](f16x8 (&fa)[MB], f16x8 (&fw)[NBW], const char* S, auto h_tag) {
-            constexpr int h = decltype(h_tag)::value;
-#pragma unroll
-            for (int j = 0; j < NBW; ++j) fw[j] = *reinterpret_cast<const f16x8*>(S + offW[j][h]);
-#pragma unroll
-            for (int i = 0; i < MB; ++i) {
-                const int K = ((4 * h) ^ ((2 * i) & 7)) >> 1;
-                fa[i] = *reinterpret_cast<const f16x8*>(S + offA[K] + i * 2048);
-            }
-        };
-        for (int g = 0; g < total; g += 2) {
-            const char* S = smem + stage * STAGE_BYTES;           // the slab landed before the last barrier
-            rd2(fa0, fw0, S, std::integral_constant<int, 0>{});
-            rd2(fa1, fw1, S, std::integral_constant<int, 1>{});
-            mm(fa0, fw0);
-            __builtin_amdgcn_sched_group_barrier(0x100, MB + NBW, 0);   // slab g's fragments first,
-            interleave();                                               // slab g+1's between slab g's MFMAs
-            mm(fa1, fw1);
-            ks += 2;
-            if (ks == nk) {
-                ks = 0;
-                epilogue();
-            }
-            step_sync();
-            stage = stage == NST - 2 ? 0 : stage + 2;
-        }
-        return;
+        for (int h = 0; h < 2; ++h) offW[j][h] = A_BYTES + r * 128 + (((4 * h + lq) ^ gh_line_swz(r)) << 4);
     }
-    rd(fa0, fw0, 0);
-    for (int g = 0; g < total; g += 2) {
-        // ---- even step: fragments of slab g are in (fa0, fw0)
-        int nstage = stage == NST - 1 ? 0 : stage + 1;
-        rd(fa1, fw1, nstage);                                     // slab g+1: landed before the last barrier
-        mm(fa0, fw0);
-        interleave();
-        step_sync();
-        stage = nstage;
-        // ---- odd step (nk is even, so a tile always ends on an odd step)
-        nstage = stage == NST - 1 ? 0 : stage + 1;
-        rd(fa0, fw0, nstage);                                     // past the last slab: reads a stale stage, never used
-        mm(fa1, fw1);
-        interleave();
-        ks += 2;
-        if (ks == nk) {
+    auto rd = [&](f16x8 (&fa)[MB], f16x8 (&fw)[NBW], const char* S, auto h_tag) {
+        constexpr int h = decltype(h_tag)::value;
+#pragma unroll
+        for (int j = 0; j < NBW; ++j) fw[j] = *reinterpret_cast<const f16x8*>(S + offW[j][h]);
+        gh_read_a<h>(fa, S, offA);
+    };
+    for (int g = 0; g < total; ++g) {
+        const char* S = smem + slot * SLOT_BYTES;                 // the slab landed before the last barrier
+        rd(fa0, fw0, S, std::integral_constant<int, 0>{});
+        rd(fa1, fw1, S, std::integral_constant<int, 1>{});
+        // The MB + NBW fragment reads of k-step 1 are spread between k-step 0's MB * NBW MFMAs (an MFMA holds the SIMD's
+        // vector issue for only half of its 16 cycles, so a ds_read in its shadow is free, while a block of 12 reads in
+        // front of the MFMAs idles the matrix pipe for ~100 cycles per step).
+        gh_mm(acc, fa0, fw0);
+        __builtin_amdgcn_sched_group_barrier(0x100, MB + NBW, 0);     // k-step 0's fragments first,
+        sched_interleave<0, MB + NBW, MB * NBW>();                    // k-step 1's between k-step 0's MFMAs
+        gh_mm(acc, fa1, fw1);
+        if (++ks == nk) {
             ks = 0;
             epilogue();
         }
-        step_sync();
-        stage = nstage;
+        gh_step_sync();
+        slot = slot == Geo::NSLOT - 1 ? 0 : slot + 1;
     }
 #endif
 }
@@ -450,26 +395,31 @@ __global__ __launch_bounds__(512, 1) void gemmh_kernel(const GemmHParams p, cons
 // K steps takes 2 620 cycles in steady state against 2 048 of MFMA issue -- 64 KiB staged per pair = 25 B/clk, the rate
 // the CU's vector-memory pipe sustains for LDS-DMA pieces that take 64 bytes from each of 16 rows (tools/probe/dma_probe:
 // 49 GB/s per CU; 78 GB/s when a piece takes 128 bytes from each of 8 rows, i.e. whole lines).  With 64-byte LDS rows
-// (one 32-deep K slab per stage) every line is fetched twice, half at a time.  Here a stage UNIT is one operand's 64-deep
-// K slab: 256 rows x 128 B = 32 KiB, a DMA piece is 8 rows x 128 B, and the CU's 160 KiB of LDS hold five units in one
-// ring that alternates operands:  X_0 = A_0, X_1 = W_0, X_2 = A_1, X_3 = W_1, ...  (unit n lives in slot n % 5).
+// (one 32-deep K slab per stage) every line is fetched twice, half at a time: the whole-line image was written for this
+// kernel first.  Here a stage UNIT is one operand's 64-deep K slab: 256 rows x 128 B = 32 KiB, and the CU's 160 KiB of LDS
+// hold five units in one ring that alternates operands:  X_0 = A_0, X_1 = W_0, X_2 = A_1, X_3 = W_1, ...  (unit n lives in
+// slot n % 5).
 // A 64-deep slab j is two MFMA k-steps (h = 0, 1: bytes 64 h .. 64 h + 63 of each row); fragments run one step ahead in
 // registers as before, so A_j and W_j are last read during step (j, 0) and their slots are free from step (j, 1):
 //     step (j, 0): issue A_{j+2}   (first read during step (j+1, 1): three steps ahead)
 //     step (j, 1): issue W_{j+2}   (first read during step (j+1, 1): two steps ahead, the old ring's distance)
 // 4 pieces per wave and step, as before.  Counted waits: end of (j, 0) needs slab j+1 landed -- only A_{j+2} is younger
 // (vmcnt 4); the end of (j, 1) needs nothing new.  Bias is read from global memory (no LDS left), in front of the
-// drain that precedes the stores.  LDS rows are 128 B = 8 chunks of 16 B; chunk c of row r is stored at
-// c ^ (((r >> 1) ^ (r >> 3)) & 7), which makes every ds_read_b128 lane group touch all 64 banks once for both operands'
-// row maps (searched by brute force over XOR-linear maps; tools/probe notes in DESIGN.md).  For a lane the swizzle is
-// (lane part) ^ (a compile-time even constant K in {0, 2, 4, 6}), so four lane offsets per operand cover every read.
+// drain that precedes the stores.  Here the W rows' swizzle, too, is (lane part) ^ (a compile-time even constant K in
+// {0, 2, 4, 6}) for a lane, so four lane offsets per operand cover every read.
 // Summation order per output element is k ascending by 32, as in the small-tile kernel: bit-identical results whichever runs.
+struct Gh8Geom {
+    static constexpr int MB = 8, NBW = 4, WM = 128, WN = 64, BM = 256, BN = 256;   // per wave: 8 x 4 blocks = 128 x 64
+    static constexpr int UNIT = 256 * 128, NU = 5;                // 32 KiB per unit, five units: all of the CU's LDS
+    static constexpr int PW = 4;                                  // pieces (8 rows x 128 B) per wave and unit
+    static constexpr size_t LDS_BYTES = (size_t)NU * UNIT;
+};
+
 __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, const int ntn, const int ntiles, const int cgw,
                                                          unsigned long long* dbg) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int MB = 8, NBW = 4, WM = 128, WN = 64, BM = 256, BN = 256;
-    constexpr int UNIT = 256 * 128, NU = 5;                       // 32 KiB per unit, five units
-    constexpr int PW = 4;                                         // pieces (8 rows x 128 B) per wave and unit
+    constexpr int MB = Gh8Geom::MB, NBW = Gh8Geom::NBW, WM = Gh8Geom::WM, WN = Gh8Geom::WN, BM = Gh8Geom::BM, BN = Gh8Geom::BN;
+    constexpr int UNIT = Gh8Geom::UNIT, NU = Gh8Geom::NU, PW = Gh8Geom::PW;
     using CM = ColMap<NBW>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -485,14 +435,12 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
     const int total = my_tiles * nk;
     if (total == 0) return;
 
-    // ---- DMA: piece i of a unit = rows 8 (wave + 8 i) .. + 7; lane -> row lane >> 3, LDS chunk lane & 7, which holds the
-    //      row's chunk (lane & 7) ^ f(row).  f(row) does not depend on i (rows 64 apart), so ONE per-lane offset per operand.
+    // ---- DMA: piece i of a unit = rows 8 (wave + 8 i) .. + 7.  The swizzle of a row does not depend on i (rows 64 apart),
+    //      so ONE per-lane offset per operand.
     const auto rsrcA = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(p.A), (short)0, p.a_bytes, 0x00020000);
     const auto rsrcW = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(p.W), (short)0, p.w_bytes, 0x00020000);
-    const int drow = wave * 8 + (lane >> 3);
-    const int dsw = ((drow >> 1) ^ (drow >> 3)) & 7;
-    const int voffA = drow * p.lda * 2 + (((lane & 7) ^ dsw) * 16);
-    const int voffW = drow * p.ldw * 2 + (((lane & 7) ^ dsw) * 16);
+    const int voffA = gh_piece_voff(wave * 8, lane, p.lda);
+    const int voffW = gh_piece_voff(wave * 8, lane, p.ldw);
     // Tile order: column tiles in groups of cgw, row panels inside a group, columns of the group innermost.  The 32 workgroups of
     // an XCD hold consecutive tiles, i.e. 32 / cgw row panels x the group's cgw column tiles, and every XCD works on the same
     // group at the same time: the group's W tiles (cgw x 512 KiB at K = 1 024) stay in each L2 while the A panels stream through
@@ -506,9 +454,8 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
         ct = cgw * g + (i - rp * cg);
     };
     auto tile_base = [&](int ti, int& a_so, int& w_so) {
-        const int t = ti < my_tiles ? ti : my_tiles - 1;          // past the end: harmless re-reads
         int rp, ct;
-        tile_rc(lid + t * G, rp, ct);
+        tile_rc(gh_walk_tile(lid, ti, my_tiles, G), rp, ct);
         a_so = rp * BM * p.lda * 2;
         w_so = ct * BN * p.ldw * 2;
     };
@@ -546,58 +493,24 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
     };
 
     f32x4 acc[MB][NBW];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NBW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // ---- fragment addresses.  A row = 128 wr + 16 i + l15: swizzle = ((l15 >> 1) & 7) ^ (l15 >> 3) ^ (2 i & 7);
+    gh_clear(acc);
+    // ---- fragment addresses.  A row = 128 wr + 16 i + l15 (gh_frag_a_offsets);
     //      W row = 64 wc + 8 (l15 >> 2) + (l15 & 3) + blk(j): swizzle = (((l15 & 3) >> 1) | ((l15 >> 2 & 1) << 2)) ^ (l15 >> 2)
     //      ^ (((j & 1) << 1) | ((j >> 1) << 2)).  Chunk of k-step h: 4 h + lq.  Lane part ^ even constant K:
-    const int laneA = lq ^ ((l15 >> 1) & 7) ^ (l15 >> 3);
     const int laneW = lq ^ ((((l15 & 3) >> 1) | (((l15 >> 2) & 1) << 2)) ^ (l15 >> 2));
-    const int rowA = (wr * WM + l15) * 128, rowW = (wc * WN + (l15 >> 2) * CM::QS + (l15 & 3)) * 128;
+    const int rowW = (wc * WN + (l15 >> 2) * CM::QS + (l15 & 3)) * 128;
     int offA[4], offW[4];                                         // byte offsets inside a unit for K = 0, 2, 4, 6
+    gh_frag_a_offsets(offA, (wr * WM + l15) * 128, l15, lq);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        offA[k] = rowA + ((laneA ^ (2 * k)) << 4);
-        offW[k] = rowW + ((laneW ^ (2 * k)) << 4);
-    }
+    for (int k = 0; k < 4; ++k) offW[k] = rowW + ((laneW ^ (2 * k)) << 4);
     f16x8 fa0[MB], fw0[NBW], fa1[MB], fw1[NBW];
     // fragments of k-step h of the slab whose units sit at LDS byte offsets ua / uw
     auto rd = [&](f16x8 (&fa)[MB], f16x8 (&fw)[NBW], int ua, int uw, auto h_tag) {
         constexpr int h = decltype(h_tag)::value;
 #pragma unroll
-        for (int j = 0; j < NBW; ++j) {
-            const int K = ((4 * h) ^ (((j & 1) << 1) | ((j >> 1) << 2))) >> 1;
-            fw[j] = *reinterpret_cast<const f16x8*>(smem + uw + offW[K] + CM::blk(j) * 128);
-        }
-#pragma unroll
-        for (int i = 0; i < MB; ++i) {
-            const int K = ((4 * h) ^ ((2 * i) & 7)) >> 1;
-            fa[i] = *reinterpret_cast<const f16x8*>(smem + ua + offA[K] + i * 2048);
-        }
-    };
-    auto mm = [&](const f16x8 (&fa)[MB], const f16x8 (&fw)[NBW]) {
-#pragma unroll
-        for (int i = 0; i < MB; ++i)
-#pragma unroll
-            for (int j = 0; j < NBW; ++j)
-                acc[i][j] = GDX_MFMA16(fw[j], fa[i], acc[i][j], 0, 0, 0);
-    };
-    auto sync_wait = [&]() {                                      // end of step (j, 0): slab j+1 has landed
-        __builtin_amdgcn_sched_barrier(0);
-        wait_vm<PW>();
-        __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto sync_nowait = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        for (int j = 0; j < NBW; ++j)
+            fw[j] = *reinterpret_cast<const f16x8*>(smem + uw + offW[gh_ksel(h, ((j & 1) << 1) | ((j >> 1) << 2))] + CM::blk(j) * 128);
+        gh_read_a<h>(fa, smem + ua, offA);
     };
     auto interleave = [&]() {                                     // 4 DMA pieces, then 12 fragment reads, among the 32 MFMAs
 #pragma unroll
@@ -637,13 +550,13 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
         // ---- step (g, 0): MFMAs of k-half 0; fragments of k-half 1 of the same slab; A_{g+2} -> the free slot
         issue_A();
         rd(fa1, fw1, ua, uw, H1{});
-        mm(fa0, fw0);
+        gh_mm(acc, fa0, fw0);
         interleave();
-        if (skip) { skip = false; sync_nowait(); } else { sync_wait(); }
+        if (skip) { skip = false; gh_step_sync(); } else { gh_step_sync<PW>(); }   // slab g+1 has landed
         // ---- step (g, 1): MFMAs of k-half 1; fragments of slab g+1; W_{g+2} -> A_g's slot (dead since the barrier)
         issue_W();
         rd(fa0, fw0, una, unw, H0{});                             // past the last slab: a stale unit, never used
-        mm(fa1, fw1);
+        gh_mm(acc, fa1, fw1);
         interleave();
         if (++ks == nk) {
             // Tile end: drain the DMA queue BEFORE the stores are issued (a counted wait behind them would stall every
@@ -660,11 +573,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
             for (int j = 0; j < NBW; ++j) bv[j] = bp ? *reinterpret_cast<const f32x4*>(bp + CM::blk(j)) : f32x4{0.f, 0.f, 0.f, 0.f};
             unsigned long long te0 = 0, te1 = 0;
             if (dbg) te0 = __builtin_amdgcn_s_memtime();
-            wait_vm<0>();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
+            gh_step_sync<0>();
             if (dbg) te1 = __builtin_amdgcn_s_memtime();
             wave_epilogue<MB, NBW>(p, acc, nullptr, t_rp * BM + wr * WM, t_ct * BN + wc * WN, l15, lq, bv);
             tile_base(tile_i + 1, a_nxt, w_nxt);                  // the streams are already inside tile tile_i
@@ -676,7 +585,7 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
                 since_epi = -1;
             }
         } else {
-            sync_nowait();
+            gh_step_sync();
         }
         ua = una; uw = unw;
         if (dbg) {
@@ -701,61 +610,50 @@ __global__ __launch_bounds__(512, 1) void gemmh8b_kernel(const GemmHParams p, co
 }
 
 static hipError_t launch_cfg_h8b(const GemmHParams& p, int num_cus, hipStream_t s, unsigned long long* stamps) {
-    const size_t lds = (size_t)5 * 32768;                         // all of the CU's LDS
+    using Geo = Gh8Geom;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemmh8b_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
+                                           (int)Geo::LDS_BYTES);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    const int ntm = (p.M + 255) / 256, ntn = p.N / 256;
+    const int ntm = (p.M + Geo::BM - 1) / Geo::BM, ntn = p.N / Geo::BN;
     const int ntiles = ntm * ntn;
     const int grid = ntiles < num_cus ? ntiles : num_cus;
     // column tiles walked in groups of four (see the kernel's tile order): M = 66 688, K = 1 024, same box, 50 launches each:
     // N = 3 072 449-458 -> 439-449 us, N = 2 048 322 -> 310; N = 1 024 is one group either way (groups of 1 / 2: slower); config 5 in
     // situ, three alternating runs: 10.27-10.33 -> 10.24-10.30 ms/step
     const int cgw = ntn < 4 ? ntn : 4;
-    hipLaunchKernelGGL(gemmh8b_kernel, dim3(grid), dim3(512), lds, s, p, ntn, ntiles, cgw, stamps);
+    hipLaunchKernelGGL(gemmh8b_kernel, dim3(grid), dim3(512), Geo::LDS_BYTES, s, p, ntn, ntiles, cgw, stamps);
     return hipGetLastError();
 }
 
-template <int MB, int NBW, int NST>
-constexpr size_t gh_lds_bytes(int N) {
-    return (size_t)NST * (MB * 16 + NBW * 64) * 64 + (size_t)N * 4;
-}
-
-template <int MB, int NBW, int NST, bool PAIR>
-static hipError_t launch_cfg_hp(const GemmHParams& p, int num_cus, hipStream_t s, unsigned long long* stamps) {
-    constexpr int BM = MB * 16, BN = NBW * 64;
-    const size_t lds = gh_lds_bytes<MB, NBW, NST>(p.N);
+template <int MB, int NBW>
+static hipError_t launch_cfg_h(const GemmHParams& p, int num_cus, hipStream_t s, unsigned long long* stamps) {
+    using Geo = GhGeom<MB, NBW>;
+    const size_t lds = Geo::lds_bytes(p.N);
     static size_t attr_lds = 0;
     if (lds > attr_lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemmh_kernel<MB, NBW, NST, PAIR>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemmh_kernel<MB, NBW>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         attr_lds = lds;
     }
-    const int ntm = (p.M + BM - 1) / BM, ntn = p.N / BN;
+    const int ntm = (p.M + Geo::BM - 1) / Geo::BM, ntn = p.N / Geo::BN;
     const int ntiles = ntm * ntn;
     const int grid = ntiles < num_cus ? ntiles : num_cus;
-    hipLaunchKernelGGL((gemmh_kernel<MB, NBW, NST, PAIR>), dim3(grid), dim3(512), lds, s, p, ntn, ntiles, stamps);
+    hipLaunchKernelGGL((gemmh_kernel<MB, NBW>), dim3(grid), dim3(512), lds, s, p, ntn, ntiles, stamps);
     return hipGetLastError();
 }
 
-template <int MB, int NBW, int NST>
-static hipError_t launch_cfg_h(const GemmHParams& p, int num_cus, hipStream_t s, unsigned long long* stamps) {
-    if (stamps) return launch_cfg_hp<MB, NBW, NST, false>(p, num_cus, s, stamps);   // the stamped diagnostic build is the per-slab one
-    return launch_cfg_hp<MB, NBW, NST, true>(p, num_cus, s, nullptr);
-}
-
-// (MB, NBW, NST): tile = 16*MB rows x 64*NBW columns, NST LDS stages of (16*MB + 64*NBW) * 64 bytes
+// (MB, NBW): tile = 16*MB rows x 64*NBW columns (GhGeom)
 #define GH_CONFIGS(X) \
-    X(8, 4, 6) X(7, 4, 6) X(6, 4, 6) X(5, 4, 6) X(4, 4, 6) X(12, 2, 6) X(10, 2, 6) X(9, 2, 6) X(8, 2, 6) X(6, 2, 6) X(5, 2, 6) \
-    X(4, 2, 6) X(8, 1, 6) X(4, 1, 6) X(2, 1, 6)
+    X(8, 4) X(7, 4) X(6, 4) X(5, 4) X(4, 4) X(12, 2) X(10, 2) X(9, 2) X(8, 2) X(6, 2) X(5, 2) X(4, 2) X(8, 1) X(4, 1) X(2, 1)
 
-static bool gh_valid(int mb, int nbw, int nst, const GemmHParams& p) {
-    return p.N % (nbw * 64) == 0 && (size_t)nst * (mb * 16 + nbw * 64) * 64 + (size_t)p.N * 4 <= 160 * 1024;
+template <int MB, int NBW>
+static bool gh_valid(const GemmHParams& p) {
+    return p.N % GhGeom<MB, NBW>::BN == 0 && GhGeom<MB, NBW>::lds_bytes(p.N) <= 160 * 1024;
 }
 
 // Estimated microseconds: rounds * (K steps * measured step time + epilogue).  Step times measured on MI355X at
@@ -795,15 +693,15 @@ bool gemmh_supported(const GemmHParams& p) {
 struct GhChoice { double cost; int tmb, tnbw; };
 static GhChoice gh_choose(const GemmHParams& p, int M, int num_cus, int force_mb, int force_nbw) {
     GhChoice c{1e30, 0, 0};
-#define X(mb, nbw, nst)                                                           \
-    if (gh_valid(mb, nbw, nst, p)) {                                              \
+#define X(mb, nbw)                                                                \
+    if (gh_valid<mb, nbw>(p)) {                                                   \
         double e = gh_cost(mb, nbw, M, p.N, p.K, num_cus, p.gelu != 0);           \
         if (force_mb == mb && force_nbw == nbw) e = 0.0;                          \
         if (e < c.cost) c = GhChoice{e, mb, nbw};                                 \
     }
     GH_CONFIGS(X)
 #undef X
-    const bool ok8 = p.K >= 256 && p.N % 256 == 0 && (size_t)4 * 32768 + (size_t)p.N * 4 <= 160 * 1024;
+    const bool ok8 = p.K >= 256 && p.N % Gh8Geom::BN == 0;
     if (ok8) {
         const double e = force_mb == 16 ? 0.0 : gh_cost(16, 4, M, p.N, p.K, num_cus, p.gelu != 0);
         if ((force_mb == 16 || !force_mb) && e < c.cost) c = GhChoice{e, 16, 4};
@@ -814,8 +712,8 @@ static GhChoice gh_choose(const GemmHParams& p, int M, int num_cus, int force_mb
 static hipError_t launch_gh_choice(const GemmHParams& p, const GhChoice& c, int num_cus, hipStream_t s,
                                    unsigned long long* stamps) {
     if (c.tmb == 16) return launch_cfg_h8b(p, num_cus, s, stamps);
-#define X(mb, nbw, nst) \
-    if (c.tmb == mb && c.tnbw == nbw) return launch_cfg_h<mb, nbw, nst>(p, num_cus, s, stamps);
+#define X(mb, nbw) \
+    if (c.tmb == mb && c.tnbw == nbw) return launch_cfg_h<mb, nbw>(p, num_cus, s, stamps);
     GH_CONFIGS(X)
 #undef X
     return hipErrorInvalidValue;

@@ -795,7 +795,8 @@ int gdx_attention_half(const float* qkv, int32_t qkv_rows, float* ctx, int32_t c
  * gdx_attention_f16, gdx_bench_gemm_f16 and gdx_bench_attention's reduced-precision version; process-wide, tests only */
 int gdx_set_test_half_dtype(int32_t dtype);
 /* tile shape of the reduced-precision GEMM (csrc/gemmh.hip) for every later call of the stand-alone entry points
- * gdx_linear_f16 and gdx_bench_gemm_f16: 16 * mb rows x 64 * nbw columns, (16, 4) = the 256 x 256 eight-wave kernel with its
+ * gdx_linear_f16 and gdx_bench_gemm_f16: 16 * mb rows x 64 * nbw columns (the fifteen shapes of gemmh.hip's GH_CONFIGS: four
+ * MFMA + four loader waves, three slots of 64-deep K slabs), (16, 4) = the 256 x 256 eight-wave kernel with its
  * grouped tile order, (0, 0) = the cost model (with its row cut; GDX_GEMMH_TILE ignored).  It applies to those entry points
  * only, NOT to a model's forwards in the same process: the GDX_GEMMH_TILE=mb,nbw environment variable remains the way to
  * force a tile for a whole forward.  Process-wide, tests only */
@@ -832,7 +833,9 @@ int gdx_linear_full(const float* A, const float* W, const float* bias, const flo
                     int32_t ldv, float* C, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T, int32_t rowmap,
                     int32_t gelu, int32_t kernel, int32_t tile_mb, int32_t tile_nbw, int32_t tile_bk, int32_t* launched,
                     void* stream);
-/* Time `iters` launches of the fp16 GEMM on scratch operands filled with N(0,1). */
+/* Time `iters` launches of the fp16 GEMM on scratch operands filled with N(0,1).  With GDX_GEMM_DEBUG set, one more launch
+ * carries in-kernel stamps and prints them to stderr: `[gemmh8 stamps]` (eight-wave kernel, per tile) and `[gemmh stamps]`
+ * (a loader wave of the 4 + 4-wave kernel that ran; its "step" is one 64-deep K slab of whole 128-byte lines). */
 int gdx_bench_gemm_f16(int32_t M, int32_t N, int32_t K, int32_t gelu, int32_t iters, float* avg_us,
                        void* stream);
 /* Algorithmic FLOPs of one forward at the prepared shape (SURVEY.md 8d formula). */

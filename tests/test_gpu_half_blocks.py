@@ -76,8 +76,11 @@ def within_one_rounding(c16, ref, dtype, abs_tol):
 # 16-bit GEMM: every tile x every epilogue of the forwards
 #   (M, N, K, T): one row; fewer rows than any tile with T = 7 (the 16-row blocks cross sample boundaries); a ragged last
 #   tile with T = 37; at M = 20 000, more tiles than CUs for every tile but the eight-wave kernel (which gets several
-#   rounds in test_half_gemm_row_cut_config5), with T = 197 (config 5's S)
-GEMM_SHAPES = [(1, 256, 256, 1), (50, 256, 320, 7), (333, 512, 256, 37), (3000, 256, 256, 120), (20000, 512, 256, 197)]
+#   rounds in test_half_gemm_row_cut_config5 and test_half_gemm_eight_wave_three_rounds_odd_slabs), with T = 197 (config 5's
+#   S); the same M at K = 320: an odd number (five) of 64-deep K slabs with several tiles per workgroup, so the three slab
+#   slots do not come back to slot 0 at a tile's first slab
+GEMM_SHAPES = [(1, 256, 256, 1), (50, 256, 320, 7), (333, 512, 256, 37), (3000, 256, 256, 120), (20000, 512, 256, 197),
+               (20000, 512, 320, 197)]
 # C32: fp32 round-off of a K <= 320 sum; measured worst 2.1e-7 (GELU 1.3e-5 -- the polynomial erf), bounds as
 # test_fp16_gemm_vs_torch
 GEMM_TOL32, GEMM_TOL32_GELU = 2e-6, 3e-5
@@ -206,9 +209,58 @@ def test_half_gemm_row_cut_config5():
     assert rel(c32[rows], ref) < GEMM_TOL32
 
 
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
+def test_half_gemm_eight_wave_three_rounds_odd_slabs(dtype):
+    """The eight-wave kernel with three tiles on a workgroup (2 cus + 1 tiles of 256 x 256 at N = 512), an odd number (five) of
+    64-deep K slabs per tile, a ragged last row panel, under the plain epilogue and under the row-indexed one (token-row map
+    + addend rows, T = 197): its DMA streams cross every tile boundary two slabs ahead of the MFMAs, and the five-unit ring
+    meets a tile's first slab in a different slot every time.  C32 against float64 on 2 048 sampled rows and the last 256,
+    C16 = C32 rounded, and the same bits as the forced 128 x 256 tile over every row."""
+    lib = _lib.load()
+    d = dev()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ntm = (2 * cus + 1 + 1) // 2
+    M, N, K, T = 256 * ntm - 100, 512, 320, 197
+    g = torch.Generator(device=d).manual_seed(M + dtype)
+    A = torch.randn(M, K, device=d, generator=g)
+    W = torch.randn(N, K, device=d, generator=g) / K ** 0.5
+    bias = torch.randn(N, device=d, generator=g)
+    out_map = torch.arange(M, device=d) + torch.arange(M, device=d) // T + 1
+    rows_map = M + (M - 1) // T + 1
+    ldr = N + 4
+    R = torch.randn(rows_map, ldr, device=d, generator=g)
+    rows = torch.cat([torch.randint(0, M, (2048,), generator=torch.Generator().manual_seed(2)), torch.arange(M - 256, M)]).to(d)
+    prod = A[rows].to(TDT[dtype]).double() @ W.to(TDT[dtype]).double().t()
+    for ename in ("bias", "res_rowmap"):
+        ub, gelu, uR, uV, rowmap, w32, w16 = EPILOGUES[ename]
+        rows_out = rows_map if rowmap else M
+        rsel = out_map if rowmap else torch.arange(M, device=d)
+        ref = prod + (bias.double() if ub else 0.0) + (R[rsel[rows], :N].double() if uR else 0.0)
+        written = torch.zeros(rows_out + 3, dtype=torch.bool, device=d)
+        written[rsel] = True
+        outs = {}
+        for tile in [(16, 4), (8, 4)]:
+            c32 = torch.full((rows_out + 3, N), float("nan"), device=d)
+            c16 = torch.full((rows_out + 3, N), float("nan"), device=d)
+            la = run_linear_half(lib, A, W, bias if ub else None, R if uR else None, ldr, None, N, c32, c16, M, N, K, T, rowmap,
+                                 gelu, dtype, tile)
+            what = f"{NAME[dtype]} {ename} M={M} tile {tile} launched {la}"
+            assert la == (tile[0], tile[1], 0, 0, 0), f"{what}: the forced tile did not run"
+            assert_rows(c32, written, what + " C32")
+            assert_rows(c16, written, what + " C16")
+            outs[tile] = (c32, c16, what)
+        c32, c16, what = outs[(16, 4)]
+        e = rel(c32[rsel[rows]], ref)
+        print(f"\n[gemmh {what}] C32 rel err {e:.2e} on {rows.numel()} rows")
+        assert e < GEMM_TOL32, f"{what}: C32 rel err {e:.2e}"
+        assert_rounded(c16[rsel], c32[rsel], dtype, what)
+        assert torch.equal(bits(c32), bits(outs[(8, 4)][0])), f"{what}: C32 bits differ from tile (8, 4)"
+        assert torch.equal(bits(c16), bits(outs[(8, 4)][1])), f"{what}: C16 bits differ from tile (8, 4)"
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # LayerNorm
-LN_D = [256, 512, 1024, 96, 128, 384, 768, 2048]      # vec kernels (fp32: all three; 16-bit: 512, 1 024), then generic
+LN_D =[256, 512, 1024, 96, 128, 384, 768, 2048]      # vec kernels (fp32: all three; 16-bit: 512, 1 024), then generic
 # fp32 statistics over rows of up to 2 048: measured worst 1.0e-6 (out32, d = 256, both input kinds; 7e-7 - 9e-7 at the
 # other widths), so a margin of 2x; the offset rows lose log10(offset / spread) digits of the mean to fp32, which stays
 # inside this bound at offset 20

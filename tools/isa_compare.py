@@ -7,7 +7,7 @@ Every kernel file of csrc/ is compiled to device-only assembly with the Makefile
 sampler.hip with -ffp-contract=off).  Per kernel the instruction stream (comments dropped) and the .vgpr_count / .sgpr_count /
 LDS / scratch / kernarg sizes of the metadata are compared; kernels are matched by symbol (and the variant's extra flags) across the whole tree,
 so one that moved to another file compares equal and is reported as moved; the two leading template arguments that older
-trees gave gemm_kernel are removed.  Prints one line per difference or move and a summary line; exit status 1 if any difference.
+trees gave gemm_kernel are removed, and so are the two trailing ones (ring depth 6, whole-line pipeline) of older trees' gemmh_kernel.  Prints one line per difference or move and a summary line; exit status 1 if any difference.
 """
 import concurrent.futures
 import os
@@ -40,7 +40,8 @@ def emit(csrc, src, extra, out):
 
 
 def norm(text):
-    return re.sub(r"gemm_kernelILi\dELi\dELi(\d)ELi(\d)EEE", r"gemm_kernelILi\1ELi\2EEE", text)
+    text = re.sub(r"gemm_kernelILi\dELi\dELi(\d)ELi(\d)EEE", r"gemm_kernelILi\1ELi\2EEE", text)
+    return re.sub(r"gemmh_kernelILi(\d+)ELi(\d)ELi6ELb1EEE", r"gemmh_kernelILi\1ELi\2EEE", text)
 
 
 def kernels(text):
