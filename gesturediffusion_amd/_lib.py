@@ -23,6 +23,7 @@ EXPORTS = [
     "gdx_linear_f16", "gdx_linear_f32", "gdx_bench_gemm_f16", "gdx_attention_f16", "gdx_attention_f32", "gdx_plms_update", "gdx_postprocess", "gdx_q_sample_t", "gdx_masked_l2", "gdx_set_graph_replay", "gdx_mfcc",
     "gdx_set_guards", "gdx_check_guards", "gdx_packed_bytes", "gdx_export_packed", "gdx_import_packed", "gdx_set_test_half_dtype",
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
+    "gdx_attention_f32_rows",
     "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
     "gdx_dpm_step", "gdx_dpm_loop", "gdx_dpm_sde_step", "gdx_dpm_sde_loop",
     "gdx_set_guidance_interval", "gdx_forward_samples", "gdx_set_guidance_rescale", "gdx_cfg_rescale",
@@ -231,6 +232,7 @@ def load():
         "gdx_attention_f16": [vp, vp, i32, i32, i32, i32, vp],
         "gdx_attention_half": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
         "gdx_attention_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
+        "gdx_attention_f32_rows": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
         "gdx_bench_gemm_f16": [i32, i32, i32, i32, i32, C.POINTER(C.c_float), vp],
         "gdx_set_guards": [vp, i32],
         "gdx_check_guards": [vp, C.POINTER(i64), C.POINTER(i32), vp],

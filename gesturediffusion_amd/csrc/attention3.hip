@@ -141,9 +141,18 @@ __global__ __launch_bounds__(512, 1) void attention3_kernel(const float* __restr
     const int kfrag = l15 * ROWB + ((lq ^ ((l15 & 7) << 1)) << 4);
     auto key_block = [&](auto nq_tag, const char* Ks, const float* Vs, int kb, int key0) {
         constexpr int NQ = decltype(nq_tag)::value;
-        f32x4 s[QB];
+        // score accumulators.  head_dim 128 accumulates the even and the odd fragment groups of the head_dim contraction apart
+        // and adds them once: two chains of 16 dependent MFMAs instead of one of 32, each rounding after every step.  With one
+        // chain the Q x 3 rows of tests/test_gpu_attention_f32.py at B = 3, S = 197, H = 2 measured 2.12e-6 of max|ctx| against
+        // fp64 -- past the 2e-6 the kernel tests hold this shape to, where a plain fp32 attention has 1.6e-6 -- with two 7.5e-7
+        // (worst over that file 2.12e-6 -> 1.25e-6; profiles/attention_f32_bounds.txt).  head_dim 64 (16 MFMAs) is inside the
+        // bound with one chain (1.61e-6) and keeps its bits.
+        constexpr int NSC = HD >= 128 ? 2 : 1;
+        f32x4 sc[NSC][QB];
 #pragma unroll
-        for (int qi = 0; qi < QB; ++qi) s[qi] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NSC; ++i)
+#pragma unroll
+            for (int qi = 0; qi < QB; ++qi) sc[i][qi] = f32x4{0.f, 0.f, 0.f, 0.f};
         constexpr int PD = 2;                                         // fragment reads run two ahead of their MFMAs
         const int kofs = kb * 16 * ROWB + kfrag;
         auto kread = [&](int kk) { return *reinterpret_cast<const f32x4*>(Ks + (kofs ^ (kk * 64))); };
@@ -162,9 +171,12 @@ __global__ __launch_bounds__(512, 1) void attention3_kernel(const float* __restr
             for (int c = 0; c < 4; ++c)
 #pragma unroll
                 for (int qi = 0; qi < NQ; ++qi)
-                    s[qi] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[c], qf[qi][kk][c], s[qi], 0, 0, 0);
+                    sc[kk % NSC][qi] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[c], qf[qi][kk][c], sc[kk % NSC][qi], 0, 0, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 4 * NQ, 0);
         }
+        f32x4 s[QB];
+#pragma unroll
+        for (int qi = 0; qi < QB; ++qi) s[qi] = NSC == 2 ? sc[0][qi] + sc[NSC - 1][qi] : sc[0][qi];
         // online softmax per query (lane column l15; keys 4lq+e in this lane), deferred max
         const bool tail = key0 + 16 > S;                              // wave-uniform: only the last key block masks
 #pragma unroll
@@ -431,8 +443,8 @@ bool attention3_supported(int S, int H, int d) {
 
 // grid = 0: one workgroup per (sample, head), or -- with at least two items per workgroup slot of that launch -- the
 // persistent variant on one workgroup per CU; grid > 0 forces the persistent variant on that many workgroups (tests,
-// A/B).
-hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, int d, hipStream_t s, int grid) {
+// A/B).  launched (optional, 3 entries): the form that ran (3 = item-resident, 5 = persistent), its grid, the item count.
+hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, int d, hipStream_t s, int grid, int* launched) {
     const int hd = d / H, nitems = B * H;
     if (hd != 128 && hd != 64) return hipErrorInvalidValue;
     const int cus = gemm2_num_cus();
@@ -440,6 +452,11 @@ hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, 
     bool persist = grid > 0 || nitems >= 2 * cus * (hd == 64 ? 2 : 1);
     if (grid <= 0) grid = cus;
     if (grid >= nitems) persist = false;                              // nothing to walk
+    if (launched) {
+        launched[0] = persist ? 5 : 3;
+        launched[1] = persist ? grid : nitems;
+        launched[2] = nitems;
+    }
     if (!persist) return hd == 128 ? launch_a3<128, false>(qkv, ctx, B, S, H, d, nitems, s) : launch_a3<64, false>(qkv, ctx, B, S, H, d, nitems, s);
     return hd == 128 ? launch_a3<128, true>(qkv, ctx, B, S, H, d, grid, s) : launch_a3<64, true>(qkv, ctx, B, S, H, d, grid, s);
 }

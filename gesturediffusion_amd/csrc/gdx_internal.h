@@ -106,8 +106,10 @@ inline bool head_dim_supported(int hd) { return hd == 32 || hd == 64 || hd == 96
 // eight-wave single-pass variant with the last query block shared out over four waves (attention3.hip); needs 64
 // readable rows past the last sample
 bool attention3_supported(int S, int H, int d);
-// grid > 0: the persistent variant on that many workgroups (default: chosen from the item count)
-hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, int d, hipStream_t s, int grid = 0);
+// grid > 0: the persistent variant on that many workgroups (default: chosen from the item count); launched (optional, 3
+// entries) receives what ran: 3 (item-resident) or 5 (persistent), the grid, the (sample, head) item count
+hipError_t launch_attention3(const float* qkv, float* ctx, int B, int S, int H, int d, hipStream_t s, int grid = 0,
+                             int* launched = nullptr);
 
 // ---- misc (misc.hip) ---------------------------------------------------------------------
 // ---- everything below exists once per half type (see the top of this file): gdx::X is the fp16 / fp32 build, gdx::b16::X

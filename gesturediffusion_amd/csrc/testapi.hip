@@ -476,6 +476,42 @@ extern "C" int gdx_attention_f32(const float* qkv, float* ctx, int32_t B, int32_
     return 0;
 }
 
+// The same kernels on exactly the caller's buffers' extents: device copies of qkv_rows x 3d inputs (no hidden pad: what lies
+// behind B*S is the caller's) and of the whole ctx_rows x d output, which comes back whole.
+extern "C" int gdx_attention_f32_rows(const float* qkv, int32_t qkv_rows, float* ctx, int32_t ctx_rows, int32_t B, int32_t S,
+                                      int32_t H, int32_t d, int32_t kernel, int32_t grid, int32_t* launched, void* stream) {
+    // every refusal comes before the first HIP call (tests/test_host_logic.py checks them without a GPU)
+    if (!qkv || !ctx || B <= 0 || S <= 0 || H <= 0 || d <= 0 || d % H) return fail("gdx_attention_f32_rows: bad argument");
+    if (!head_dim_supported(d / H)) return fail("gdx_attention_f32_rows: head_dim must be " GDX_HEAD_DIMS);
+    if (kernel != 0 && kernel != 1 && kernel != 3 && kernel != 5)
+        return fail("gdx_attention_f32_rows: unknown kernel (0 = dispatch, 1 = attention.hip, 3 = attention3.hip, 5 = its persistent form)");
+    const bool a3 = kernel == 3 || kernel == 5 || (kernel == 0 && attention3_supported(S, H, d));   // the rule of attend() (api.hip)
+    if (kernel && a3 && !attention3_supported(S, H, d))
+        return fail("gdx_attention_f32_rows: shape not supported by attention3.hip (head_dim 64 / 128, at most 256 tokens)");
+    if (grid < 0 || (grid > 0 && kernel != 5) || (grid == 0 && kernel == 5))
+        return fail("gdx_attention_f32_rows: grid is for the persistent form (kernel 5) only, which needs one");
+    if (kernel == 5 && (long)grid >= (long)B * H)
+        return fail("gdx_attention_f32_rows: the persistent form walks items: grid must be below B*H");
+    if ((long)qkv_rows < (long)B * S || (long)ctx_rows < (long)B * S) return fail("gdx_attention_f32_rows: qkv_rows / ctx_rows below B*S");
+    if (a3 && (long)qkv_rows < (long)B * S + 64)
+        return fail("gdx_attention_f32_rows: attention3.hip reads whole 64-key tiles: qkv_rows below B*S + 64");
+    // attention.hip addresses with 64-bit offsets and puts the items on grid.y; attention3.hip's buffer loads carry 32-bit byte
+    // offsets from each item's base and its items are an int
+    if ((long)B * H > (a3 ? (1l << 31) - 1 : 65535l) || (a3 && (S + 64l) * 12 * d >= (1l << 31)))
+        return fail("gdx_attention_f32_rows: a buffer exceeds the kernel's addressing (B*H items, or one sample's rows past 2 GiB)");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_in = (int64_t)qkv_rows * 3 * d, n_out = (int64_t)ctx_rows * d;
+    float *q = nullptr, *c = nullptr;
+    Scratch sc("gdx_attention_f32_rows", s);
+    if (sc.stage(&q, qkv, n_in) || sc.stage(&c, ctx, n_out)) return -1;
+    int ran[3] = {1, (S + 127) / 128, B * H};
+    const hipError_t e = a3 ? launch_attention3(q, c, B, S, H, d, s, grid, ran) : launch_attention(q, c, B, S, H, d, s);
+    if (e != hipSuccess) return fail(std::string("gdx_attention_f32_rows: ") + hipGetErrorString(e));
+    if (launched)
+        for (int i = 0; i < 3; ++i) launched[i] = ran[i];
+    return sc.unstage(c, ctx, n_out);
+}
+
 extern "C" int gdx_bench_gemm_f16(int32_t M, int32_t N, int32_t K, int32_t gelu, int32_t iters, float* avg_us, void* stream) {
     if (!avg_us || M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 64 || iters <= 0) return fail("gdx_bench_gemm_f16: bad argument");
     hipStream_t s = (hipStream_t)stream;

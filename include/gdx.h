@@ -791,6 +791,17 @@ int gdx_attention_f16(const float* qkv, float* ctx, int32_t B, int32_t S, int32_
  * grid and its work-item count.  Every refusal comes before the first HIP call.  Synchronises the stream. */
 int gdx_attention_half(const float* qkv, int32_t qkv_rows, float* ctx, int32_t ctx_rows, int32_t B, int32_t S, int32_t H,
                        int32_t d, int32_t dtype, int32_t kernel, int32_t grid, int32_t* launched, void* stream);
+/* The fp32 self-attention kernels on the caller's own extents, with a forced kernel (test entry point, the fp32 counterpart of
+ * gdx_attention_half): the kernels run on device copies of exactly qkv [qkv_rows][3d] -- no hidden pad: rows past B*S are the
+ * caller's, finite by contract -- and of the whole ctx [ctx_rows][d], which is copied back whole, so rows the kernel does not
+ * store come back unchanged.  kernel: 0 = the choice gdx_forward makes (attention3.hip where it takes the shape, and its own
+ * choice of the persistent form), 1 = attention_kernel (attention.hip), 3 = attention3.hip item-resident, 5 = attention3.hip
+ * persistent on `grid` workgroups (0 < grid < B*H; grid must be 0 for every other kernel).  3 and 5 need head_dim 64 / 128
+ * and S <= 256.  Whenever attention3.hip runs, qkv_rows >= B*S + 64 (it stages whole 64-key tiles); attention.hip clamps
+ * and takes qkv_rows = B*S.  launched (optional, 3 entries) receives the kernel that ran (1, 3 or 5), its grid (grid.x for
+ * kernel 1) and the (sample, head) item count.  Every refusal comes before the first HIP call.  Synchronises the stream. */
+int gdx_attention_f32_rows(const float* qkv, int32_t qkv_rows, float* ctx, int32_t ctx_rows, int32_t B, int32_t S, int32_t H,
+                           int32_t d, int32_t kernel, int32_t grid, int32_t* launched, void* stream);
 /* element type (GDX_DTYPE_F16, the default, or GDX_DTYPE_BF16) of the stand-alone entry points gdx_linear_f16,
  * gdx_attention_f16, gdx_bench_gemm_f16 and gdx_bench_attention's reduced-precision version; process-wide, tests only */
 int gdx_set_test_half_dtype(int32_t dtype);

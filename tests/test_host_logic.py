@@ -170,6 +170,58 @@ def test_attention_half_refuses_what_has_no_kernel_without_gpu():
         assert list(rep) == [-1, -1, -1], change              # refused before anything ran
 
 
+def test_attention_f32_rows_refuses_without_gpu():
+    """gdx_attention_f32_rows validates before its first HIP call: null pointers, bad sizes, a head width or kernel it does not
+    have, attention3 forced on a shape it does not take, short buffers (attention3 needs 64 rows behind B*S, attention.hip
+    none), a grid without the persistent form or the persistent form without one, and sizes past the kernels' addressing are
+    refused with a message (the pointers are never dereferenced, `launched` is not touched)."""
+    import ctypes as C
+    from gesturediffusion_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgdx.so not built")
+    lib = _lib.load()
+    p = C.c_void_p(0x1000)
+    rep = (C.c_int32 * 3)(-1, -1, -1)
+    ok = dict(qkv=p, qkv_rows=2 * 61 + 64, ctx=p, ctx_rows=2 * 61, B=2, S=61, H=4, d=512, kernel=0, grid=0)
+    cases = [
+        (dict(qkv=None), b"bad argument"),
+        (dict(ctx=None), b"bad argument"),
+        (dict(B=0), b"bad argument"),
+        (dict(S=-1), b"bad argument"),
+        (dict(H=0), b"bad argument"),
+        (dict(d=0), b"bad argument"),
+        (dict(H=3), b"bad argument"),                              # d % H
+        (dict(d=4 * 48), b"head_dim"),                             # head_dim 48
+        (dict(kernel=2), b"unknown kernel"),
+        (dict(kernel=4), b"unknown kernel"),
+        (dict(kernel=6), b"unknown kernel"),
+        (dict(kernel=-1), b"unknown kernel"),
+        (dict(kernel=3, d=4 * 96), b"not supported by attention3"),
+        (dict(kernel=5, grid=2, d=4 * 256), b"not supported by attention3"),
+        (dict(kernel=3, S=257, qkv_rows=1000, ctx_rows=1000), b"not supported by attention3"),
+        (dict(qkv_rows=2 * 61 - 1, kernel=1), b"below B*S"),
+        (dict(ctx_rows=2 * 61 - 1), b"below B*S"),
+        (dict(qkv_rows=2 * 61 + 63), b"below B*S + 64"),           # the forward's choice here is attention3
+        (dict(qkv_rows=2 * 61 + 63, kernel=3), b"below B*S + 64"),
+        (dict(qkv_rows=2 * 61, kernel=5, grid=2), b"below B*S + 64"),
+        (dict(kernel=1, grid=8), b"persistent form"),              # grid for a kernel that is not the persistent form
+        (dict(kernel=3, grid=8), b"persistent form"),
+        (dict(kernel=0, grid=8), b"persistent form"),
+        (dict(kernel=5, grid=-1), b"persistent form"),
+        (dict(kernel=5, grid=0), b"persistent form"),              # the persistent form needs one
+        (dict(kernel=5, grid=8), b"below B*H"),                    # 8 items: nothing to walk
+        (dict(kernel=1, B=20000, qkv_rows=20000 * 61, ctx_rows=20000 * 61), b"addressing"),   # 80 000 items on grid.y
+        (dict(kernel=3, H=12000, d=128 * 12000), b"addressing"),   # attention3: (S + 64) rows of 12 d bytes pass 2 GiB
+        (dict(kernel=0, H=12000, d=128 * 12000), b"addressing"),
+    ]
+    for change, msg in cases:
+        a = dict(ok, **change)
+        rc = lib.gdx_attention_f32_rows(a["qkv"], a["qkv_rows"], a["ctx"], a["ctx_rows"], a["B"], a["S"], a["H"], a["d"],
+                                        a["kernel"], a["grid"], rep, None)
+        assert rc != 0 and msg in lib.gdx_last_error(), (change, lib.gdx_last_error())
+        assert list(rep) == [-1, -1, -1], change              # refused before anything ran
+
+
 def test_linear_full_refuses_what_the_forwards_do_not_launch_without_gpu():
     """gdx_linear_full validates before its first HIP call: operand sets the fp32 forwards have no launch for, unknown
     kernels, a tile forced on gemm.hip, short buffers and operands past 2 GiB are refused with a message (the pointers are
