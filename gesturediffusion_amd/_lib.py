@@ -25,7 +25,7 @@ EXPORTS = [
     "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
     "gdx_attention_f32_rows",
     "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
-    "gdx_dpm_step", "gdx_dpm_loop", "gdx_dpm_sde_step", "gdx_dpm_sde_loop",
+    "gdx_dpm_step", "gdx_dpm_loop", "gdx_dpm_sde_step", "gdx_dpm_sde_loop", "gdx_unipc_step", "gdx_unipc_loop",
     "gdx_set_guidance_interval", "gdx_forward_samples", "gdx_set_guidance_rescale", "gdx_cfg_rescale",
     "gdx_set_guidance_refresh", "gdx_cfg_delta",
     "gdx_transpose_in", "gdx_transpose_out", "gdx_small_linear", "gdx_gather_rows", "gdx_mfcc_project", "gdx_token0",
@@ -118,6 +118,25 @@ class DpmSdeLoopArgs(C.Structure):
         ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32),
         ("run_steps", C.c_int32), ("k_base", C.c_int32), ("hist", C.c_void_p), ("noise_tape", C.c_void_p),
         ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64),
+    ]
+
+
+class UnipcStepArgs(C.Structure):
+    _fields_ = [
+        ("corr_order", C.c_int32), ("pred_order", C.c_int32), ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32),
+        ("coef", C.c_void_p), ("coef_c", C.c_void_p), ("t", C.c_void_p), ("step_index", C.c_int32), ("x", C.c_void_p),
+        ("x0_cond", C.c_void_p), ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p),
+        ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32), ("hist", C.c_void_p * 3), ("base_out", C.c_void_p),
+        ("out", C.c_void_p), ("pred_out", C.c_void_p),
+    ]
+
+
+class UnipcLoopArgs(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("order", C.c_int32), ("num_steps", C.c_int32), ("first_index", C.c_int32),
+        ("coef", C.c_void_p), ("timestep_map", C.c_void_p), ("x", C.c_void_p), ("scale", C.c_void_p),
+        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32),
+        ("run_steps", C.c_int32), ("k_base", C.c_int32), ("hist", C.c_void_p), ("base", C.c_void_p), ("coef_c", C.c_void_p),
     ]
 
 
@@ -229,6 +248,8 @@ def load():
         "gdx_dpm_loop": [vp, C.POINTER(DpmLoopArgs), vp],
         "gdx_dpm_sde_step": [C.POINTER(DpmSdeStepArgs), vp],
         "gdx_dpm_sde_loop": [vp, C.POINTER(DpmSdeLoopArgs), vp],
+        "gdx_unipc_step": [C.POINTER(UnipcStepArgs), vp],
+        "gdx_unipc_loop": [vp, C.POINTER(UnipcLoopArgs), vp],
         "gdx_attention_f16": [vp, vp, i32, i32, i32, i32, vp],
         "gdx_attention_half": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
         "gdx_attention_f32": [vp, vp, i32, i32, i32, i32, i32, vp],

@@ -713,17 +713,17 @@ static U step_args(const gdx_model* h, const A* a, int idx, const float* x0_unco
     return u;
 }
 
-// The scaffold of the multistep loops gdx_plms_loop, gdx_dpm_loop and gdx_dpm_sde_loop (`who`), whose argument structs A name
-// the fields mode .. k_base alike: per step the denoiser through forward_core on the pose-layout state (the entry gdx_forward
-// uses: same bits as the step-wise protocol), then step(idx, k, x0_uncond, scale, slot), the entry's own fused launch; slot(k) =
-// executed step k's place in the caller's ring of a->order buffers at a->*hist; two_calls: step 0 makes a second denoiser call
-// (call_seq; the entry's step issues it).  No graph replay and no token-major variant:
+// The scaffold of the multistep loops gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop and gdx_unipc_loop (`who`), whose argument
+// structs A name the fields mode .. k_base alike: per step the denoiser through forward_core on the pose-layout state (the entry
+// gdx_forward uses: same bits as the step-wise protocol), then step(idx, k, x0_uncond, scale, slot), the entry's own fused launch;
+// slot(k) = executed step k's place in the caller's ring of `ring` buffers (0: a->order of them) at a->*hist; two_calls: step 0
+// makes a second denoiser call (call_seq; the entry's step issues it).  No graph replay and no token-major variant:
 // these solvers run 10-50 steps.  The argument checks need no handle and come first (then null handle, then not prepared), so
 // every refusal precedes the first HIP call; missing() gives the entry's history refusal or nullptr.  A new multistep sampler
 // is one more caller of this function ("Where a new in-library loop goes").
 template <typename A, typename Missing, typename Step>
 static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_lo, int order_hi, const char* order_msg,
-                          float* A::*hist, Missing missing, hipStream_t s, Step step, bool two_calls = false) {
+                          float* A::*hist, Missing missing, hipStream_t s, Step step, bool two_calls = false, int ring = 0) {
     const std::string w = std::string(who) + ": ";
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail(w + "null argument");
     if (check_mode(who, a->mode, a->scale)) return -1;
@@ -740,7 +740,8 @@ static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_l
     if (check_reuse(h, who, q, a->first_index, last_idx)) return -1;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
     const size_t n = (size_t)h->B * h->J * h->T;
-    auto slot = [&](int k) { return a->*hist + (size_t)(k % a->order) * n; };
+    const int depth = ring > 0 ? ring : a->order;
+    auto slot = [&](int k) { return a->*hist + (size_t)(k % depth) * n; };
     int k = a->k_base;
     for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
         const float *x0u, *sc;
@@ -804,6 +805,26 @@ extern "C" int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a
             u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset; u.rng_step = (uint32_t)(k + 1);
             return gdx_dpm_sde_step(&u, stream);
         });
+}
+
+// unipc_sample_loop (UniPC, gdx.h): one fused unipc_step_kernel launch per step (sampler.hip) -- the corrector of the step that
+// led to a->x, then the predictor of the next input; a->base holds the corrected state, the ring is one deeper than the order
+extern "C" int gdx_unipc_loop(gdx_handle_t h, const gdx_unipc_loop_args_t* a, void* stream) {
+    return multistep_loop(
+        "gdx_unipc_loop", h, a, 1, 3, "order must be 1, 2 or 3", &gdx_unipc_loop_args_t::hist,
+        [&] { return !a->hist || !a->base || !a->coef_c ? "missing history (hist, base and coef_c are the caller's)" : nullptr; },
+        (hipStream_t)stream,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot) -> int {
+            auto u = step_args<gdx_unipc_step_args_t>(h, a, idx, x0u, sc);
+            u.corr_order = k == 0 || idx == 0 ? 0 : std::min(a->order, k);
+            u.pred_order = std::min(a->order, std::min(k + 1, idx + 1));
+            if (u.corr_order) u.x = a->base;                              // else the state itself: a->x
+            u.coef_c = a->coef_c; u.base_out = a->base;
+            for (int j = 0; j < std::max(u.corr_order, u.pred_order - 1); ++j) u.hist[j] = slot(k - 1 - j);
+            u.pred_out = slot(k);
+            return gdx_unipc_step(&u, stream);
+        },
+        false, a ? a->order + 1 : 0);
 }
 
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {

@@ -476,6 +476,60 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const DpmStepDev a) {
     store4<VEC>(a.s.out, e0, nval, r);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// One UniPC step in one pass (gdx.h gdx_unipc_step): dpm_step_kernel's m0, then the corrector of order NC over m0 (= m_new) and
+// the NC predictions before it on the base state x -- unipc_correct, weights from row idx + 1 of both tables; NC = 0: xc = x --
+// and the predictor of order NP from xc, which is dpm_multistep<NP - 1> on the row's order-NP columns.  Grid (ceil(groups / 256),
+// B): blockIdx.y is the sample, NC and NP template arguments.  Memory-bound, one pass, no LDS: per element 2 + max(NC, NP - 1)
+// reads (one more under guidance, + mask and motion under inpainting) and three writes (xc, x_p, m0).
+template <int NC>
+__device__ __forceinline__ float unipc_correct(float ab, const float* c, float x, float mn, float h0, float h1, float h2) {
+    float d = __fmul_rn(c[0], mn);
+    d = __fadd_rn(d, __fmul_rn(c[1], h0));
+    if (NC >= 2) d = __fadd_rn(d, __fmul_rn(c[2], h1));
+    if (NC >= 3) d = __fadd_rn(d, __fmul_rn(c[3], h2));
+    return __fadd_rn(__fmul_rn(ab, x), d);
+}
+
+struct UnipcStepDev {
+    StepSrc s;              // x: the corrector's base state (NC = 0: the state itself); out: x_p; pred: m0
+    const float* coef_c;
+    const float *h0, *h1, *h2;
+    float* base_out;
+};
+
+template <int NC, int NP, bool VEC>
+__global__ __launch_bounds__(256) void unipc_step_kernel(const UnipcStepDev a) {
+    constexpr int NHIST = NC > NP - 1 ? NC : NP - 1;               // history slots read
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    if (grp >= a.s.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.s.per_sample);
+    const long e0 = g.e0;
+    const int nval = g.nval;
+    const long idx = coef_row(a.s, g.b);
+    const float* c = a.s.coef + idx * 8;
+    const float* w = c + 1 + (NP - 1) * NP / 2;
+
+    const f32x4 x = load4<VEC>(a.s.x, e0, nval);
+    const f32x4 m0 = pred_xstart4<VEC>(a.s, g);
+    f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0, h2 = h0;
+    if (NHIST >= 1) h0 = load4<VEC>(a.h0, e0, nval);
+    if (NHIST >= 2) h1 = load4<VEC>(a.h1, e0, nval);
+    if (NHIST >= 3) h2 = load4<VEC>(a.h2, e0, nval);
+    f32x4 xc = x, r;
+    if (NC > 0) {
+        const float ab = a.s.coef[(idx + 1) * 8];
+        const float* cc = a.coef_c + (idx + 1) * 16 + 4 * (NC - 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xc[i] = unipc_correct<NC>(ab, cc, x[i], m0[i], h0[i], h1[i], h2[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = dpm_multistep<NP - 1>(c[0], w, xc[i], m0[i], h0[i], h1[i]);
+    if (a.s.pred) store4<VEC>(a.s.pred, e0, nval, m0);
+    store4<VEC>(a.base_out, e0, nval, xc);
+    store4<VEC>(a.s.out, e0, nval, r);
+}
+
 // De-normalisation + position / rotation split of a generated chunk (reference sample/generate.py:132-146 with
 // data_loaders/gesture/data/dataset.py:118-119): feature 6j+c is rotation component c of joint j, 6j+3+c its position.
 //   pos[b][j][c][t] = x[b][6j+3+c][t] * std[6j+3+c] + mean[6j+3+c],  rot[b][j][c][t] likewise with feature 6j+c.
@@ -856,7 +910,7 @@ static gdx::StepSrc step_src(const A* a, float* pred) {
     return s;
 }
 
-// What gdx_plms_step, gdx_dpm_step and gdx_dpm_sde_step (`who`) share in front of their launch: the refusals in their order
+// What gdx_plms_step, gdx_dpm_step, gdx_dpm_sde_step and gdx_unipc_step (`who`) share in front of their launch: the refusals in their order
 // -- null argument, the entry's own kind / order check, shape, CFG, mask, the entry's history check (both return the
 // refusal's text or nullptr) --, then the StepSrc and the (ceil(groups / 256), B) grid.  -1: refused, 1: nothing to do, 0: launch.
 template <typename A, typename Entry, typename Hist>
@@ -1048,6 +1102,59 @@ static int dpm_step_impl(const char* who, const A* a, void* stream) {
 extern "C" int gdx_dpm_step(const gdx_dpm_step_args_t* a, void* stream) { return dpm_step_impl<false>("gdx_dpm_step", a, stream); }
 extern "C" int gdx_dpm_sde_step(const gdx_dpm_sde_step_args_t* a, void* stream) {
     return dpm_step_impl<true>("gdx_dpm_sde_step", a, stream);
+}
+
+// The (corr_order, pred_order) pairs the order rule of gdx_unipc_loop reaches (gdx.h), the only instantiations
+static bool unipc_pair_ok(int nc, int np) {
+    return np == 1 ? nc <= 1 : (np == 2 ? nc >= 1 : nc >= 2);
+}
+
+template <bool VEC>
+static void launch_unipc_step(int nc, int np, dim3 grid, hipStream_t s, const gdx::UnipcStepDev& d) {
+    using namespace gdx;
+    const dim3 block(256);
+    switch (nc * 4 + np) {
+        case 0 * 4 + 1: hipLaunchKernelGGL((unipc_step_kernel<0, 1, VEC>), grid, block, 0, s, d); break;
+        case 1 * 4 + 1: hipLaunchKernelGGL((unipc_step_kernel<1, 1, VEC>), grid, block, 0, s, d); break;
+        case 1 * 4 + 2: hipLaunchKernelGGL((unipc_step_kernel<1, 2, VEC>), grid, block, 0, s, d); break;
+        case 2 * 4 + 2: hipLaunchKernelGGL((unipc_step_kernel<2, 2, VEC>), grid, block, 0, s, d); break;
+        case 3 * 4 + 2: hipLaunchKernelGGL((unipc_step_kernel<3, 2, VEC>), grid, block, 0, s, d); break;
+        case 2 * 4 + 3: hipLaunchKernelGGL((unipc_step_kernel<2, 3, VEC>), grid, block, 0, s, d); break;
+        default: hipLaunchKernelGGL((unipc_step_kernel<3, 3, VEC>), grid, block, 0, s, d); break;
+    }
+}
+
+extern "C" int gdx_unipc_step(const gdx_unipc_step_args_t* a, void* stream) {
+    using namespace gdx;
+    const char* who = "gdx_unipc_step";
+    UnipcStepDev d = {};
+    dim3 grid;
+    int nh = 0;                                                     // history slots this pair reads
+    const int rc = step_begin(
+        who, a, &gdx_unipc_step_args_t::pred_out,
+        [&]() -> const char* {
+            if (!a->base_out) return "null argument";
+            if (a->corr_order < 0 || a->corr_order > 3) return "corr_order must be 0, 1, 2 or 3";
+            if (a->pred_order < 1 || a->pred_order > 3) return "pred_order must be 1, 2 or 3";
+            if (!unipc_pair_ok(a->corr_order, a->pred_order)) return "no such (corr_order, pred_order) pair in the order rule";
+            if (a->corr_order > 0 && !a->coef_c) return "corr_order > 0 needs coef_c";
+            return a->base_out == a->out ? "base_out aliases out" : nullptr;
+        },
+        [&]() -> const char* {
+            nh = std::max(a->corr_order, a->pred_order - 1);
+            for (int i = 0; i < nh; ++i) {
+                if (!a->hist[i]) return "missing history for these orders";
+                if (a->pred_out && a->pred_out == a->hist[i]) return "pred_out aliases a history slot it reads";
+            }
+            return nullptr;
+        },
+        d.s, grid);
+    if (rc) return rc < 0 ? -1 : 0;
+    d.coef_c = a->coef_c; d.base_out = a->base_out;
+    d.h0 = nh > 0 ? a->hist[0] : nullptr; d.h1 = nh > 1 ? a->hist[1] : nullptr; d.h2 = nh > 2 ? a->hist[2] : nullptr;
+    if (vec_ok(d.s, d.h0, d.h1, d.h2, d.base_out)) launch_unipc_step<true>(a->corr_order, a->pred_order, grid, (hipStream_t)stream, d);
+    else launch_unipc_step<false>(a->corr_order, a->pred_order, grid, (hipStream_t)stream, d);
+    return launch_status("gdx_unipc_step: launch failed");
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,

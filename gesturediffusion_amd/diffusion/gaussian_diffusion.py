@@ -12,6 +12,7 @@ coefficient rows; every per-element operation runs in libgdx.so:
   * `gdx_plms_step` / `gdx_plms_loop`   plms_sample_loop (`:995-1190`): one fused multistep update per step, the loop in C++
   * `gdx_dpm_step` / `gdx_dpm_loop`     dpm_solver_sample_loop: DPM-Solver++ multistep (2M / 3M), additive, same pattern
   * `gdx_dpm_sde_step` / `gdx_dpm_sde_loop`   dpm_solver_sde_sample_loop: its stochastic twin (SDE-DPM-Solver++, orders 1 / 2)
+  * `gdx_unipc_step` / `gdx_unipc_loop`   unipc_sample_loop: UniPC, a corrector and the multistep predictor in one launch per step
   * `gdx_bpd_terms` / `gdx_bpd_loop`   the variational bound in bits/dim (`_vb_terms_bpd` :1192-1225, `_prior_bpd`
                           :1519-1535, `calc_bpd_loop` :1537-1592, and `training_losses` under LossType.KL / RESCALED_KL)
 
@@ -1208,6 +1209,121 @@ class GaussianDiffusion:
         yield from self._stepwise(self.dpm_solver_sde_sample, model, shape, noise, device, progress, skip_timesteps, init_image,
                                   rng, philox_seed, sample_offset, noise_tape, step_noise=True, clip_denoised=clip_denoised,
                                   denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, order=order, eta=eta)
+
+    # ------------------------------------------------------------------ UniPC (no counterpart in the reference)
+    def unipc_coef_rows(self):
+        """The fp64 rows behind unipc_coef_tables -> (pred [num_timesteps, 8], corr [num_timesteps, 16]): UniPC (Zhao et al.
+        2023, arXiv:2302.04867; data prediction, B(h) = expm1(-h)) collected into weights of the state and the x0 predictions.
+        pred has dpm_coef_rows' layout (a, w1_0, w2_0, w2_1, w3_0, w3_1, w3_2, 0): columns 0..3 are taken from dpm_coef_rows
+        itself (UniP-1 is DDIM, UniP-2 is 2M), columns 4..6 hold UniP-3.  corr row b, columns 4(q-1) .. 4(q-1)+3 = (cn, c0, c1,
+        c2) of UniC-q with base b: the weights of the new prediction (made at b's target) and of m_b, m_{b+1}, m_{b+2}.
+        Formulas, special rows and the order rule: include/gdx.h at gdx_unipc_step / gdx_unipc_loop."""
+        n = self.num_timesteps
+        ab, abp = self.alphas_cumprod, self.alphas_cumprod_prev
+        lam = 0.5 * np.log(ab / (1.0 - ab))
+        pred = self.dpm_coef_rows().copy()
+        pred[:, 4:7] = 0.0
+        corr = np.zeros((n, 16), dtype=np.float64)
+        for b in range(1, n):                             # row 0: abar_p = 1, h = inf -- pred (0, 1, 0, ...), corr 0
+            h = 0.5 * math.log(abp[b] / (1.0 - abp[b])) - lam[b]
+            em1 = math.expm1(-h)
+            k = -math.sqrt(abp[b]) * em1                  # -alpha_p*E: what every weight set sums to
+            hh, g, fact, beta = -h, math.expm1(-h) / -h - 1.0, 1.0, []
+            for q in (1, 2, 3):
+                beta.append(g * fact / em1)
+                fact *= q + 1
+                g = g / hh - 1.0 / fact
+            r = [(lam[b + j] - lam[b]) / h for j in (1, 2) if b + j < n]
+            if len(r) == 2:                               # UniP-3: the leading 2x2 block of R against (beta_1, beta_2)
+                rho = np.linalg.solve(np.array([[1.0, 1.0], r]), np.array(beta[:2]))
+                w = [k * rho[j] / r[j] for j in (0, 1)]
+                pred[b, 4:7] = k - w[0] - w[1], w[0], w[1]
+            for q in range(1, len(r) + 2):                # UniC-q reads m_b .. m_{b+q-1}
+                rq = r[:q - 1] + [1.0]
+                rho = np.array([0.5]) if q == 1 else np.linalg.solve(np.array([[v ** p for v in rq] for p in range(q)]),
+                                                                     np.array(beta[:q]))
+                w = [k * rho[j] / rq[j] for j in range(q)]
+                corr[b, 4 * (q - 1):4 * (q - 1) + q + 1] = [w[-1], k - sum(w)] + w[:-1]
+        return pred, corr
+
+    def unipc_coef_tables(self, device):
+        """(coef [num_timesteps, 8], coef_c [num_timesteps, 16]) fp32, consumed by gdx_unipc_step / gdx_unipc_loop:
+        unipc_coef_rows rounded once (.float(), the convention of every other table here)."""
+        key = ("unipc", str(device))
+        if key not in self._coef_cache:
+            self._coef_cache[key] = tuple(th.from_numpy(r).float().to(device) for r in self.unipc_coef_rows())
+        return self._coef_cache[key]
+
+    def unipc_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, order=2,
+                     old_out=None):
+        """One UniPC step (gdx_unipc_step).  x is the denoiser's input (on the first step x_T, afterwards the previous step's
+        "sample"); the x0 prediction comes from _pred_xstart (so EPSILON / PREVIOUS_X / denoised_fn work as elsewhere; cond_fn
+        through condition_score).  With k = the steps made so far (old_out is None: 0) the corrector of order min(order, k) --
+        none on the first step and at t = 0 -- moves old_out["base"] to the corrected state of this index, and the predictor of
+        order min(order, k + 1, t + 1) takes that to the next input.  old_out["old_pred"]: oldest first, at most `order` kept.
+        t must be the same for the whole batch.  Returns {"sample", "pred_xstart", "old_pred", "base"}."""
+        if order not in (1, 2, 3):
+            raise ValueError('order is invalid (should be int from 1-3).')
+        xc, tt, i = self._uniform_t("unipc_sample", x, t)
+        pred = self._pred_xstart(model, xc, tt, clip_denoised, denoised_fn, model_kwargs)
+        used = self._condition_score_xstart(cond_fn, xc, tt, pred, model_kwargs or {})
+        old_pred = list(old_out["old_pred"]) if old_out is not None else []
+        qc = len(old_pred) if i > 0 else 0
+        qp = min(order, len(old_pred) + 1, i + 1)
+        coef, coef_c = self.unipc_coef_tables(xc.device)
+        base = th.empty_like(xc)
+        sample = E.unipc_step(qc, qp, coef, coef_c, E.f32c(old_out["base"], "base") if qc else xc, used, th.empty_like(xc), base,
+                              hist=old_pred[::-1][:max(qc, qp - 1)], step_index=i)
+        return {"sample": sample, "pred_xstart": pred, "old_pred": (old_pred + [used])[-order:], "base": base}
+
+    def unipc_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                          model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                          randomize_class=False, cond_fn_with_grad=False, order=2, *, fused=True, rng="torch",
+                          philox_seed=0, sample_offset=0):
+        """UniPC sampling (second order by default) with dpm_solver_sample_loop's signature and routes: one forward per step,
+        whose prediction both corrects the step just made and predicts the next.  A native START_X denoiser (or its
+        ClassifierFreeSampleModel) without cond_fn / denoised_fn runs the whole loop inside libgdx (gdx_unipc_loop: one forward
+        and one fused launch per step); every other case, and fused=False, goes step by step through unipc_sample.  Both give
+        the same bits.  Like DPM-Solver++ it gains its order only on steps spaced evenly in log-SNR ("logsnrN"), and at about
+        10 steps or fewer it is no better than dpm_solver_sample_loop."""
+        if rng not in ("torch", "philox"):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        if order not in (1, 2, 3):
+            raise ValueError('order is invalid (should be int from 1-3).')
+        if cond_fn_with_grad or randomize_class:
+            raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
+        if self._runs_fused(fused, model, denoised_fn, cond_fn):
+            if model_kwargs is None:
+                model_kwargs = {}
+            device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
+                                                      philox_seed, sample_offset, None)
+            return self._fused_unipc_loop(model, img, indices, model_kwargs, int(order), progress, clip_denoised)
+        return self._final_sample(self.unipc_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, skip_timesteps=skip_timesteps, init_image=init_image,
+            order=order, rng=rng, philox_seed=philox_seed, sample_offset=sample_offset))
+
+    def _fused_unipc_loop(self, model, img, indices, model_kwargs, order, progress, clip_denoised):
+        """Whole loop inside libgdx (gdx_unipc_loop).  The ring of x0 predictions (order + 1 deep) and the corrected state live
+        in two tensors of this call; with `progress` the loop is issued in blocks of NOISE_BLOCK steps."""
+        x, eng, mode, scale, mask, motion = self._fused_setup(model, img, model_kwargs)
+        (coef, coef_c), tmap = self.unipc_coef_tables(x.device), self._timestep_map()
+        hist = th.empty((order + 1, *x.shape), device=x.device, dtype=th.float32)
+        base = th.empty_like(x)
+        self._issue_blocks(len(indices), x.device, progress, lambda k, nb: eng.unipc_loop(
+            x, mode, order, coef, coef_c, tmap, indices[k], hist, base, scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+            clip_denoised=clip_denoised, run_steps=nb, k_base=k))
+        return x
+
+    def unipc_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                      cond_fn=None, model_kwargs=None, device=None, progress=False, skip_timesteps=0,
+                                      init_image=None, randomize_class=False, cond_fn_with_grad=False, order=2, *,
+                                      rng="torch", philox_seed=0, sample_offset=0):
+        if cond_fn_with_grad or randomize_class:
+            raise NotImplementedError("cond_fn_with_grad / randomize_class are outside the sampling hot path")
+        yield from self._stepwise(self.unipc_sample, model, shape, noise, device, progress, skip_timesteps, init_image, rng,
+                                  philox_seed, sample_offset, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                  cond_fn=cond_fn, model_kwargs=model_kwargs, order=order)
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

@@ -269,6 +269,15 @@ class Engine:
                                 noise_tape=_p(noise_tape), philox_seed=philox_seed, sample_offset=sample_offset, **kw)
         self._run_loop(self.lib.gdx_dpm_sde_loop, a, x.device, tmap)
 
+    def unipc_loop(self, x, mode, order, coef, coef_c, timestep_map, first_index, hist, base, scale=None, inpaint_mask=None,
+                   inpaint_motion=None, clip_denoised=False, run_steps=0, k_base=0):
+        """gdx_unipc_loop: x (the denoiser's input) is updated in place; hist [order + 1, B, J, 1, T] and base [B, J, 1, T] are
+        the caller's and carry the x0 predictions and the corrected state from one block (run_steps / k_base) to the next."""
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base)
+        a = _lib.UnipcLoopArgs(mode=mode, order=order, first_index=first_index, x=x.data_ptr(), hist=_p(hist), base=_p(base),
+                               coef_c=coef_c.data_ptr(), **kw)
+        self._run_loop(self.lib.gdx_unipc_loop, a, x.device, tmap)
+
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
         _lib.check(self.lib.gdx_forward_flops(self.handle, mode, C.byref(f)), self.lib)
@@ -351,7 +360,7 @@ def refuse_guidance_refresh(y, guided_model, who):
     every = guidance_refresh_of(y, guided_model)
     if every > 1:
         raise ValueError(f"y['guidance_refresh'] = {every} needs the in-library loop (p_sample_loop, ddim_sample_loop, "
-                         f"plms_sample_loop, dpm_solver_sample_loop or dpm_solver_sde_sample_loop with fused=True on a native "
+                         f"plms_sample_loop, dpm_solver_sample_loop, dpm_solver_sde_sample_loop or unipc_sample_loop with fused=True on a native "
                          f"model, without cond_fn / denoised_fn): {who} cannot carry the guidance difference from one call to "
                          f"the next")
 
@@ -472,6 +481,21 @@ def dpm_sde_step(order, coef, x, x0_cond, out, hist=(), t=None, step_index=0, x0
     for i, m in enumerate(hist):
         a.hist[i] = _p(m)
     _lib.check(lib.gdx_dpm_sde_step(C.byref(a), _stream(x0_cond.device)), lib)
+    return out
+
+
+def unipc_step(corr_order, pred_order, coef, coef_c, x, x0_cond, out, base_out, hist=(), t=None, step_index=0, x0_uncond=None,
+               scale=None, inpaint_mask=None, inpaint_motion=None, clip_denoised=False, pred_out=None):
+    """gdx_unipc_step: one UniPC step in one pass (include/gdx.h) -- the corrector of order corr_order (0: none) on the base
+    state x with the x0 prediction formed here as the new one, then the predictor of order pred_order from the corrected state
+    (-> base_out) into out.  hist: older predictions, newest first; coef / coef_c = unipc_coef_tables."""
+    lib = _lib.load()
+    kw = _step_fields(x0_cond.shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised)
+    a = _lib.UnipcStepArgs(corr_order=corr_order, pred_order=pred_order, coef_c=_p(coef_c), x=x.data_ptr(),
+                           base_out=base_out.data_ptr(), out=out.data_ptr(), pred_out=_p(pred_out), **kw)
+    for i, m in enumerate(hist):
+        a.hist[i] = _p(m)
+    _lib.check(lib.gdx_unipc_step(C.byref(a), _stream(x0_cond.device)), lib)
     return out
 
 

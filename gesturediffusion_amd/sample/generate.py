@@ -50,14 +50,15 @@ def resolve_rng(rng, world):
 def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames, seed_poses, guidance_param=1.0,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
-                  guidance_refresh=1):
+                  guidance_refresh=1, unipc_order=2):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
-    of chunk outputs [b, J, 1, frames].  noise_tapes: optional list of recorded noise tapes, one per chunk (tests); the PLMS
-    and DPM-Solver++ ("dpmpp") samplers draw nothing after x_T and take entry 0 of a tape as that, the stochastic
-    DPM-Solver++ ("dpmpp_sde": order `dpm_order`, 1 or 2, noise scale `eta`) draws per step like "p" and is handed the whole
-    tape.  guidance_interval (lo, hi): guidance only on model timesteps lo <= t <= hi (y['guidance_interval']; needs
+    of chunk outputs [b, J, 1, frames].  noise_tapes: optional list of recorded noise tapes, one per chunk (tests); the PLMS,
+    DPM-Solver++ ("dpmpp") and UniPC ("unipc": order `unipc_order`) samplers draw nothing after x_T and take entry 0 of a tape
+    as that, the stochastic DPM-Solver++ ("dpmpp_sde": order `dpm_order`, 1 or 2, noise scale `eta`) draws per step like "p" and
+    is handed the whole tape.
+    guidance_interval (lo, hi): guidance only on model timesteps lo <= t <= hi (y['guidance_interval']; needs
     guidance_param != 1).  guidance_rescale phi > 0: the guidance rescale (y['guidance_rescale']; needs guidance_param != 1).
     guidance_refresh k > 1: the unconditional pass on every k-th guided denoiser call, the stored cond-uncond difference in
     between (y['guidance_refresh']; needs guidance_param != 1); each chunk is its own loop and starts with a refresh."""
@@ -71,7 +72,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
         raise ValueError("guidance_refresh needs guidance_param != 1: without guidance there is nothing to refresh")
     b, J = first_seed.shape[0], first_seed.shape[1]
     sample_fn = {"p": diffusion.p_sample_loop, "ddim": diffusion.ddim_sample_loop, "plms": diffusion.plms_sample_loop,
-                 "dpmpp": diffusion.dpm_solver_sample_loop, "dpmpp_sde": diffusion.dpm_solver_sde_sample_loop}[sampler]
+                 "dpmpp": diffusion.dpm_solver_sample_loop, "dpmpp_sde": diffusion.dpm_solver_sde_sample_loop,
+                 "unipc": diffusion.unipc_sample_loop}[sampler]
     outs, sample_out = [], None
     for chunk in range(n_chunks):
         y = {"mfcc": mfcc_of_chunk(chunk), "seed": first_seed if chunk == 0 else sample_out[..., -seed_poses:]}
@@ -94,7 +96,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             kw.update(order=dpm_order, eta=eta)
         else:
             tape = kw.pop("noise_tape")
-            kw.update(order=dpm_order if sampler == "dpmpp" else plms_order, noise=tape[0] if tape is not None else None)
+            kw.update(order={"dpmpp": dpm_order, "unipc": unipc_order, "plms": plms_order}[sampler],
+                      noise=tape[0] if tape is not None else None)
         if on_chunk is not None:
             on_chunk(chunk)
         sample_out = sample_fn(model, (b, J, 1, frames), **kw)
@@ -228,8 +231,9 @@ def main(argv=None):
                          guidance_param=args.guidance_param, sampler=args.sampler,
                          eta=args.dpm_eta if args.sampler == "dpmpp_sde" else args.eta, rng=rng,
                          philox_seed=args.seed, sample_offset=lo, progress=args.progress and rank == 0, on_chunk=on_chunk,
-                         plms_order=args.plms_order, dpm_order=args.dpm_order, guidance_interval=interval,
-                         guidance_rescale=args.guidance_rescale, guidance_refresh=args.guidance_refresh)
+                         plms_order=args.plms_order, dpm_order=args.dpm_order, unipc_order=args.unipc_order,
+                         guidance_interval=interval, guidance_rescale=args.guidance_rescale,
+                         guidance_refresh=args.guidance_refresh)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

@@ -138,15 +138,18 @@ def add_native_options(parser):
                        help="Pose channels for --synthetic when --dataset is not a GENEA set (e.g. 263).")
     group.add_argument("--arch_version", default='mdm', choices=['mdm', 'mdm_old'],
                        help="mdm = V2 (model/mdm.py), mdm_old = V1 encoder-only topology (model/mdm_old.py).")
-    group.add_argument("--sampler", default='p', choices=['p', 'ddim', 'plms', 'dpmpp', 'dpmpp_sde'],
+    group.add_argument("--sampler", default='p', choices=['p', 'ddim', 'plms', 'dpmpp', 'dpmpp_sde', 'unipc'],
                        help="p_sample_loop (reference default), ddim_sample_loop, plms_sample_loop, dpm_solver_sample_loop "
-                            "(DPM-Solver++ multistep) or dpm_solver_sde_sample_loop (its stochastic twin, orders 1 and 2); use "
-                            "the last two with --timestep_respacing logsnrN.")
+                            "(DPM-Solver++ multistep), dpm_solver_sde_sample_loop (its stochastic twin, orders 1 and 2) or "
+                            "unipc_sample_loop (UniPC: a corrector on top of the multistep predictor, same forwards per step); use "
+                            "the last three with --timestep_respacing logsnrN.")
     group.add_argument("--plms_order", default=2, type=int, choices=[2, 3, 4],
                        help="--sampler plms: order of the Adams-Bashforth multistep update.")
     group.add_argument("--dpm_order", default=2, type=int, choices=[1, 2, 3],
                        help="--sampler dpmpp: order of the multistep update (1 = DDIM at eta 0, 2 = 2M, 3 = 3M); "
                             "--sampler dpmpp_sde: 1 or 2.")
+    group.add_argument("--unipc_order", default=2, type=int, choices=[1, 2, 3],
+                       help="--sampler unipc: order of the predictor and the corrector (the corrected state is one order higher).")
     group.add_argument("--dpm_eta", default=1.0, type=float,
                        help="--sampler dpmpp_sde: scale of the injected noise (1 = the ancestral sampler's, 0 = --sampler dpmpp).")
     group.add_argument("--timestep_respacing", default='', type=str,

@@ -125,7 +125,7 @@ int gdx_set_condition(gdx_handle_t h, const float* seed, const float* mfcc, void
  *   lo <= tau <= hi : guided, exactly u + scale*(c - u)
  *   otherwise       : unguided, the x0 prediction is the conditional output c itself (not a blend at scale 1: other bits)
  *   lo > hi         : a legal empty interval, never guided
- * In the loops (gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop, gdx_bpd_loop) the host decides per step from
+ * In the loops (gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop, gdx_unipc_loop, gdx_bpd_loop) the host decides per step from
  * timestep_map[index]: an unguided step of a GDX_CFG loop runs the denoiser as GDX_COND on B samples -- the unconditional
  * pass is never computed -- and its update gets x0_uncond = scale = NULL; both forwards of gdx_plms_loop's first step take
  * the mode of their own timestep.  Inpainting, clip_denoised, the noise and the multistep history apply after the choice of
@@ -152,7 +152,7 @@ int gdx_set_guidance_interval(gdx_handle_t h, int64_t lo, int64_t hi);
  *
  * gdx_set_guidance_rescale: per-handle state like the guidance interval, 0 (off) after gdx_create; phi outside [0, 1] (NaN
  * included) or a null handle is refused before any HIP call.  With phi > 0, gdx_forward under GDX_CFG and every guided step of
- * the in-library loops (gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop, gdx_bpd_loop) run gdx_cfg_rescale between
+ * the in-library loops (gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop, gdx_unipc_loop, gdx_bpd_loop) run gdx_cfg_rescale between
  * the denoiser and the step kernel, which then gets x0_uncond = scale = NULL like an unguided step; a guided step still runs
  * 2 * batch samples.  With phi == 0 nothing is launched and every result keeps its bits.  There is no token-major variant of
  * the rescale: a gdx_sample_loop call with phi > 0 and at least one guided step takes the pose-layout path (two transposes per
@@ -199,7 +199,7 @@ int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream);
  * difference.  Block-wise issue (run_steps / k_base): the host derives the n of a call from timestep_map, the whole loop's
  * first index first_index + k_base and, for gdx_plms_loop, the second call of step 0 -- no counter lives in the handle -- so
  * issue in blocks gives the bits of one call.
- * It applies in gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop and gdx_dpm_sde_loop.  There is no token-major variant: a
+ * It applies in gdx_sample_loop, gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop and gdx_unipc_loop.  There is no token-major variant: a
  * gdx_sample_loop call with every > 1 and at least one guided step takes the pose-layout path (two transposes per step more
  * than the token-major path), and graph replay runs such a call eagerly.  gdx_forward and gdx_bpd_loop keep every guided call a
  * full one and never touch the stored difference: the step-wise forward has no memory, and the bound's steps draw independent
@@ -437,6 +437,57 @@ typedef struct {
 } gdx_dpm_sde_step_args_t;
 int gdx_dpm_sde_step(const gdx_dpm_sde_step_args_t* a, void* stream);
 
+/* One UniPC step over [B,J,1,T] in ONE pass (Zhao et al. 2023, arXiv:2302.04867, the data-prediction form with B(h) = expm1(-h),
+ * the paper's bh2; no counterpart in the reference): the x0 prediction m0 the denoiser just made is used twice -- to CORRECT the
+ * step that led to the denoiser's input (one order of accuracy more, no further forward) and to PREDICT the next input.
+ * Notation of gdx_dpm_step.  A step with base index b, target p = the target of b, h = lambda_p - lambda_b, E = expm1(-h) and the
+ * predictions m_b, m_{b+1}, ... (older = larger index):  r_j = (lambda_{b+j} - lambda_b)/h (j = 1..q-1), r_q = 1,
+ * D_j = (m_{b+j} - m_b)/r_j,  first = (sigma_p/sigma_b)*x - alpha_p*E*m_b;  with hh = -h:  g_1 = expm1(hh)/hh - 1,
+ * g_{n+1} = g_n/hh - 1/(n+1)!,  beta_n = g_n*n!/E,  R[n][j] = r_j^(n-1) (n, j = 1..q):
+ *   UniP-q (predictor, base b = i):  q = 1: x_p = first;  q = 2: rho = (1/2);  q = 3: rho solves the leading 2x2 block of R against
+ *            (beta_1, beta_2);  x_p = first - alpha_p*E*sum_{j<q} rho_j*D_j.       UniP-1 is DDIM at eta = 0, UniP-2 is 2M.
+ *   UniC-q (corrector, base b = i + 1, whose target is i; m_new = m_i, D_new = m_new - m_b):  q = 1: rho = (1/2), else rho solves
+ *            R*rho = beta (q x q);  x_c = first - alpha_p*E*(sum_{j<q} rho_j*D_j + rho_q*D_new).
+ * Both are linear in (x, m...): the host collects the weights in fp64 and rounds them once to fp32.
+ * coef: device [num_steps][8] fp32 rows (a, w1_0, w2_0, w2_1, w3_0, w3_1, w3_2, 0), the layout of gdx_dpm_step's rows; columns
+ * 0..3 ARE those rows bit for bit, columns 4..6 hold UniP-3.  coef_c: device [num_steps][16] fp32 rows; columns 4(q-1) ..
+ * 4(q-1)+3 of row b hold (cn, c0, c1, c2) of UniC-q with base b -- the weights of m_new, m_b, m_{b+1}, m_{b+2}, zero-padded --
+ * and columns 12..15 are 0.  Every non-zero weight set sums to -alpha_p*E of its row.  Row 0 of coef is (0, 1, 0, ...): the step
+ * at index 0 returns m0; row 0 of coef_c is 0 (its h is infinite).  Entries that would need an index >= num_steps are 0.  Neither
+ * kind of zero is selected by the order rule of gdx_unipc_loop.
+ * Per element, idx = t[b] if t != NULL else step_index, c = coef[idx], every product / sum rounded separately:
+ *   m0 = x0_cond -> CFG blend -> inpainting blend -> clamp, exactly as in gdx_dpm_step
+ *   corr_order q >= 1:  (cn, c0, c1, c2) = coef_c[idx + 1][4(q-1) ..],  ab = coef[idx + 1][0];
+ *       C = cn*m0;  C = C + c0*hist[0];  q >= 2: C = C + c1*hist[1];  q = 3: C = C + c2*hist[2];  xc = ab*x + C
+ *   corr_order 0:  xc = x, bits untouched (row idx + 1 of neither table is read)
+ *   pred_order p:  D = w0*m0;  p >= 2: D = D + w1*hist[0];  p = 3: D = D + w2*hist[1];  out = a*xc + D   (w = c's order-p columns)
+ * xc goes to base_out (required; may alias x), x_p to out, m0 to pred_out (optional; it must not be a history slot the step
+ * reads).  hist[j] = the prediction made j + 1 executed steps ago (index idx + 1 + j); max(corr_order, pred_order - 1) of them
+ * are read, the others never.  Only the pairs the order rule of gdx_unipc_loop reaches exist: (corr, pred) = (0,1) (1,1) (1,2)
+ * (2,2) (3,2) (2,3) (3,3); any other is refused.  128-bit accesses when J*T % 4 == 0 and every pointer is 16-byte aligned (the
+ * mask 4-byte), a scalar path otherwise.  batch <= 65535.  Refusals come before the first HIP call. */
+typedef struct {
+    int32_t corr_order;        /* 0..3 */
+    int32_t pred_order;        /* 1..3 */
+    int32_t batch, njoints, frames;
+    const float* coef;         /* [num_steps][8], rows as above */
+    const float* coef_c;       /* [num_steps][16], rows as above; required when corr_order > 0 */
+    const int64_t* t;          /* [B] or NULL */
+    int32_t step_index;        /* used when t == NULL */
+    const float* x;            /* corr_order > 0: the corrector's base state (index idx + 1, corrected); 0: the state */
+    const float* x0_cond;      /* model output (cond pass) */
+    const float* x0_uncond;    /* NULL or uncond pass */
+    const float* scale;        /* [B] when x0_uncond != NULL */
+    const uint8_t* inpaint_mask;   /* NULL or bool bytes [B,J,1,T] */
+    const float* inpaint_motion;   /* [B,J,1,T] when mask != NULL */
+    int32_t clip_denoised;
+    const float* hist[3];      /* older x0 predictions, newest first */
+    float* base_out;           /* xc; may alias x */
+    float* out;                /* x_p; may alias x, not base_out */
+    float* pred_out;           /* NULL or [B,J,1,T]: m0 */
+} gdx_unipc_step_args_t;
+int gdx_unipc_step(const gdx_unipc_step_args_t* a, void* stream);
+
 /* q_sample (gaussian_diffusion.py:233-251): out = a*x_start + b*noise, a/b per-sample from
  * coef rows (c[5], c[6]) at idx. */
 int gdx_q_sample(const float* x_start, const float* noise, const float* coef, int32_t idx,
@@ -672,6 +723,40 @@ typedef struct {
     uint64_t sample_offset;
 } gdx_dpm_sde_loop_args_t;
 int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a, void* stream);
+
+/* UniPC sampling loop (unipc_sample_loop; the update, the coefficient rows and their source are at gdx_unipc_step): the loop of
+ * gdx_dpm_loop -- same step numbering, run_steps / k_base block-wise issue, order of refusals and guided calls (guidance
+ * interval, rescale and refresh: one guided call per step) -- with ONE gdx_unipc_step launch per executed step.  x is always the
+ * denoiser's input: x_T (or the q_sample'd init) on entry, the sample (m_0) on completion.  Executed step k at index i:
+ *   1. the denoiser runs on x and gives m_i, which goes to slot k % (order + 1) of hist;
+ *   2. corrector: order qc = 0 when k == 0 or i == 0 (nothing to correct / its result would not be used), else min(order, k), with
+ *      base index i + 1, the base state in `base`, m_new = m_i and the history m_{i+1}, ...;  the corrected state (qc = 0: x
+ *      itself) is written to `base`;
+ *   3. predictor from the corrected state: order qp = min(order, k + 1, i + 1), base i, history m_i, m_{i+1}, ...;
+ *   4. its output is written to x, the next denoiser input.  The step at index 0 is first order: x = m_0.
+ * The ring of predictions holds order + 1 buffers: the corrector reads up to `order` older predictions, and the new one must not
+ * overwrite any of them.  Block-wise issue gives the bits of one call: hist and base carry the state between calls.  hist and
+ * base are the caller's; the library owns only its weights and workspace.  There is neither graph replay nor a token-major variant
+ * of this loop.  Argument checks come first, then the null handle, then readiness: every refusal precedes the first HIP call. */
+typedef struct {
+    int32_t mode;              /* GDX_COND / GDX_UNCOND / GDX_CFG */
+    int32_t order;             /* 1..3 */
+    int32_t num_steps;         /* rows of coef / coef_c / timestep_map */
+    int32_t first_index;       /* index of this call's first step (whole loop: num_steps - 1 - skip_timesteps) */
+    const float* coef;         /* device [num_steps][8], predictor rows of gdx_unipc_step */
+    const int64_t* timestep_map;   /* HOST [num_steps] */
+    float* x;                  /* in: x_T (or q_sample'd init), out: the sample */
+    const float* scale;        /* [B] for GDX_CFG */
+    const uint8_t* inpaint_mask;
+    const float* inpaint_motion;
+    int32_t clip_denoised;
+    int32_t run_steps;
+    int32_t k_base;
+    float* hist;               /* device [order + 1][B,J,1,T] */
+    float* base;               /* device [B,J,1,T]: the corrected state between steps */
+    const float* coef_c;       /* device [num_steps][16], corrector rows of gdx_unipc_step */
+} gdx_unipc_loop_args_t;
+int gdx_unipc_loop(gdx_handle_t h, const gdx_unipc_loop_args_t* a, void* stream);
 
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  A call whose

@@ -1,0 +1,293 @@
+"""Host-side checks of the UniPC sampler (unipc_coef_tables, gdx_unipc_step, gdx_unipc_loop, the CLI flags): no GPU needed.  The
+fp64 restatement lives in unipc_restatement.py; the analytic case, the schedules and the DPM-Solver++ figures it is compared with
+come from dpm_restatement.py / test_dpm_host.py."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import dpm_restatement as R
+import unipc_restatement as U
+from conftest import REPO
+from test_dpm_host import S2, analytic_x_T, diffusion
+
+# Worst relative error of the restatement's recurrence run in torch fp32 on the CPU against fp64 over the six analytic cases
+# (logsnr20 / logsnr40 x orders 1..3, x_T of shape (2, 3, 1, 4), seed 0) measured 4.574e-7 (logsnr20, order 1); the GPU test
+# allows 4x over it, the convention of test_dpm_host.FP32_LOOP_TOL.
+UNIPC_FP32_LOOP_WORST = 4.58e-7
+UNIPC_FP32_LOOP_TOL = 4 * UNIPC_FP32_LOOP_WORST
+
+GRID = [(s, r) for s in ("linear", "cosine") for r in ([1000], "ddim10", "logsnr20")]
+
+
+def restated_errors(spacings=("logsnr20", "logsnr40")):
+    """{(sampler, spacing, order): error of the fp64 restatement's final sample against the exact end point}, linear schedule;
+    sampler "dpm" = DPM-Solver++ multistep, "unipc" = UniPC."""
+    out = {}
+    x_T = analytic_x_T().numpy()
+    for sp in spacings:
+        df = diffusion("linear", sp)
+        ab, abp = df.alphas_cumprod, df.alphas_cumprod_prev
+        g = R.gaussian_gain(ab, S2)
+        den = lambda x, i: g[i] * x   # noqa: E731
+        for order in (1, 2, 3):
+            out["dpm", sp, order] = R.gaussian_error(R.dpm_loop(ab, abp, x_T, den, order), x_T, ab[-1], S2)
+            out["unipc", sp, order] = R.gaussian_error(U.unipc_loop(ab, abp, x_T, den, order), x_T, ab[-1], S2)
+    return out
+
+
+def assert_gain(err):
+    """The three inequalities of the issue (measured ratios 15.0, 3.34 and 2.50)."""
+    print({k: f"{v:.3e}" for k, v in err.items()})
+    assert err["unipc", "logsnr20", 3] <= err["dpm", "logsnr20", 3] / 8
+    assert err["unipc", "logsnr40", 2] <= err["dpm", "logsnr40", 2] / 2.5
+    assert err["unipc", "logsnr20", 3] <= err["dpm", "logsnr40", 3] / 1.5
+
+
+# ------------------------------------------------------------------------------------------------------------------ tables
+@pytest.mark.parametrize("schedule,respacing", GRID)
+def test_tables_are_the_rounded_restatement(schedule, respacing):
+    """Each fp32 entry of both tables is np.float32 of the restatement's fp64 weight, or within 1 fp32 ulp of it: the package
+    collects the weights, the restatement evaluates the D-form recurrence on unit vectors, so the fp64 values can differ in
+    their last bits and round to neighbouring fp32 numbers.  Zero entries are zero on both sides."""
+    df = diffusion(schedule, respacing)
+    got = df.unipc_coef_tables("cpu")
+    assert df.unipc_coef_tables("cpu") is got                                # cached like coef_table
+    want = U.unipc_weights(df.alphas_cumprod, df.alphas_cumprod_prev)
+    for name, g, w, width in (("pred", got[0], want[0], 8), ("corr", got[1], want[1], 16)):
+        assert g.dtype == torch.float32 and tuple(g.shape) == (df.num_timesteps, width)
+        w32 = w.astype(np.float32)
+        ulp = np.spacing(np.abs(w32)).astype(np.float64)
+        diff = np.abs(g.numpy().astype(np.float64) - w32.astype(np.float64))
+        assert (diff <= ulp).all(), (name, np.argwhere(diff > ulp)[:5])
+        assert ((g.numpy() == 0) == (w == 0)).all(), name
+        exact = float((diff == 0).mean())
+        print(f"{schedule} {respacing} {name}: {100 * exact:.2f}% of the entries are the correctly rounded restatement")
+        assert exact > 0.9
+
+
+@pytest.mark.parametrize("schedule,respacing", GRID)
+def test_table_structure(schedule, respacing):
+    """Columns 0..3 of the predictor rows are dpm_coef_rows bit for bit; the zeros and row 0 are where gdx.h puts them; every
+    non-zero weight set sums to -alpha_p*E of its row, formed here from the schedule.  The bound on the difference, relative
+    to sum |w|, is (4 + (|lambda_p| + |lambda_b|)/h) * eps: a set has at most four weights, each a handful of fp64 roundings from
+    its real value (the restatement's own sets, obtained without ever forming a sum, measured at most 1.05 eps against the
+    restatement's own -alpha_p*E), and E is a function of h = lambda_p - lambda_b, a difference that carries the rounding of both
+    logarithms -- with a libm of one's own on either side -- amplified by 1/h (h is 1e-3 and less on 1000 steps)."""
+    df = diffusion(schedule, respacing)
+    pred, corr = df.unipc_coef_rows()
+    n = df.num_timesteps
+    assert pred.dtype == corr.dtype == np.float64 and pred.shape == (n, 8) and corr.shape == (n, 16)
+    dpm = df.dpm_coef_rows()
+    assert np.array_equal(pred[:, :4], dpm[:, :4])
+    assert np.array_equal(df.unipc_coef_tables("cpu")[0][:, :4], df.dpm_coef_table("cpu")[:, :4])
+    assert pred[0].tolist() == [0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0] and (corr[0] == 0).all()
+    assert (pred[:, 7] == 0).all() and (corr[:, 12:] == 0).all()
+    assert (pred[n - 1, 2:7] == 0).all() and (pred[n - 2, 4:7] == 0).all()
+    # UniC-q at base b reads m_b .. m_{b+q-1}; its set has q + 1 weights, the rest of its four columns is padding
+    assert (corr[n - 1, 4:] == 0).all() and (corr[n - 2, 8:] == 0).all()
+    assert (corr[:, 2:4] == 0).all() and (corr[:, 7] == 0).all()
+    assert (pred[1:n - 2, 4:7] != 0).all()
+    assert (corr[1:, 0:2] != 0).all() and (corr[1:n - 1, 4:7] != 0).all() and (corr[1:n - 2, 8:12] != 0).all()
+    eps = np.finfo(np.float64).eps
+    ab, abp = df.alphas_cumprod[1:], df.alphas_cumprod_prev[1:]              # rows 1 ..: row 0 has h = inf
+    lam_b, lam_p = R.lam_of(ab), R.lam_of(abp)
+    k = np.append(1.0, -np.sqrt(abp) * np.expm1(lam_b - lam_p))              # -alpha_p*E
+    bound = np.append(0.0, (4 + (np.abs(lam_p) + np.abs(lam_b)) / (lam_p - lam_b)) * eps)
+    rest = U.unipc_weights(df.alphas_cumprod, df.alphas_cumprod_prev)
+    worst = 0.0
+    for who, (p, c) in (("package", (pred, corr)), ("restatement", rest)):
+        for rows, lo, hi, last in ((p, 4, 7, n - 2), (c, 0, 2, n), (c, 4, 7, n - 1), (c, 8, 12, n - 2)):
+            w = rows[1:last, lo:hi]
+            rel = np.abs(w.sum(axis=1) - k[1:last]) / np.abs(w).sum(axis=1)
+            worst = max(worst, float((rel / bound[1:last]).max()) if len(rel) else 0.0)
+            assert (rel <= bound[1:last]).all(), (who, lo, float((rel / bound[1:last]).max()))
+    print(f"{schedule} {respacing}: weight sums within {worst:.3f} of the bound (largest bound {bound.max() / eps:.0f} eps)")
+
+
+# ------------------------------------------------------------------------------------------------------------ convergence
+def test_restatement_gains_over_dpm_solver():
+    """fp64, analytic Gaussian case, linear schedule.  Measured: UniPC-3 at logsnr20 5.38e-4 against 3M 8.08e-3 (ratio 15.0) and
+    against 3M at logsnr40 1.35e-3 (2.50); UniPC-2 at logsnr40 1.09e-3 against 2M 3.65e-3 (3.34)."""
+    assert_gain(restated_errors())
+
+
+def test_predictor_alone_is_dpm_solver_at_orders_1_and_2():
+    x_T = analytic_x_T().numpy()
+    for sp in ("logsnr20", "logsnr40"):
+        df = diffusion("linear", sp)
+        ab, abp = df.alphas_cumprod, df.alphas_cumprod_prev
+        g = R.gaussian_gain(ab, S2)
+        den = lambda x, i: g[i] * x   # noqa: E731
+        for order in (1, 2):
+            want = R.dpm_loop(ab, abp, x_T, den, order)
+            got = U.unipc_loop(ab, abp, x_T, den, order, corrector=False)
+            assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), (sp, order)
+            assert np.abs(U.unipc_loop(ab, abp, x_T, den, order) - want).max() > 1e-6 * np.abs(want).max()   # the corrector acts
+
+
+def test_ten_steps_are_no_gain():
+    """The caveat of DESIGN.md 4j, pinned: at logsnr10 UniPC-2 (5.09e-2) is behind 2M (3.17e-2) on this case."""
+    err = restated_errors(("logsnr10",))
+    assert err["unipc", "logsnr10", 2] > err["dpm", "logsnr10", 2]
+
+
+def test_fp32_recurrence_stays_inside_the_gpu_tolerance():
+    """Where UNIPC_FP32_LOOP_TOL comes from: the restatement's recurrence in torch fp32 on the CPU against fp64, the six cases
+    of the GPU test.  The worst relative error must stay at or below the recorded figure the tolerance is 4x of."""
+    x_T = analytic_x_T()
+    worst = 0.0
+    for sp in ("logsnr20", "logsnr40"):
+        df = diffusion("linear", sp)
+        ab, abp = df.alphas_cumprod, df.alphas_cumprod_prev
+        g64 = R.gaussian_gain(ab, S2)
+        g32 = torch.from_numpy(g64).float()
+        for order in (1, 2, 3):
+            want = U.unipc_loop(ab, abp, x_T.numpy(), lambda x, i: g64[i] * x, order)
+            got = U.unipc_loop(ab, abp, x_T.float(), lambda x, i: g32[i] * x, order, xp=torch)
+            assert got.dtype == torch.float32
+            rel = float(np.abs(got.double().numpy() - want).max() / np.abs(want).max())
+            print(f"{sp} order {order}: fp32 recurrence rel err {rel:.3e}")
+            worst = max(worst, rel)
+    assert worst <= UNIPC_FP32_LOOP_WORST, worst
+
+
+def test_order_rule_reaches_exactly_the_instantiated_pairs():
+    pairs = {U.effective_orders(order, k, n - 1 - skip - k) for order in (1, 2, 3) for n in range(1, 9) for skip in range(n)
+             for k in range(n - skip)}
+    assert pairs == {(0, 1), (1, 1), (1, 2), (2, 2), (3, 2), (2, 3), (3, 3)}
+
+
+# ------------------------------------------------------------------------------------------------------------------- C ABI
+def _lib_or_skip():
+    from gesturediffusion_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libgdx.so not built (run python __graft_entry__.py)")
+    return _lib
+
+
+def test_unipc_symbols_declared_and_exported():
+    _lib = _lib_or_skip()
+    hdr = open(os.path.join(REPO, "include", "gdx.h")).read()
+    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    for name in ("gdx_unipc_step", "gdx_unipc_loop"):
+        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
+        assert name in _lib.EXPORTS and f" T {name}\n" in syms, name
+
+
+def test_unipc_ctypes_structs_match_header_sizes(tmp_path):
+    from gesturediffusion_amd import _lib
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gdx.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %zu\\n", sizeof(gdx_unipc_step_args_t), sizeof(gdx_unipc_loop_args_t), '
+                   'offsetof(gdx_unipc_step_args_t, pred_out), offsetof(gdx_unipc_loop_args_t, coef_c)); return 0; }\n')
+    exe = tmp_path / "probe"
+    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
+        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0), None)
+    assert cc, "no C compiler"
+    subprocess.run([cc, "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
+    got = tuple(int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
+    assert (C.sizeof(_lib.UnipcStepArgs), C.sizeof(_lib.UnipcLoopArgs), _lib.UnipcStepArgs.pred_out.offset,
+            _lib.UnipcLoopArgs.coef_c.offset) == got
+
+
+def _refused(lib, rc, text):
+    return rc < 0 and text in lib.gdx_last_error()
+
+
+def test_unipc_step_refusals_without_gpu():
+    """gdx_unipc_step is stateless: every refusal is decided from the argument struct (addresses are never followed)."""
+    _lib = _lib_or_skip()
+    lib = _lib.load()
+    P, Q, S = 4096, 8192, 12288                         # non-null addresses; a refused call reads nothing through them
+    assert _refused(lib, lib.gdx_unipc_step(None, None), b"null argument")
+    assert _refused(lib, lib.gdx_unipc_step(C.byref(_lib.UnipcStepArgs()), None), b"null argument")
+    ok = dict(corr_order=0, pred_order=1, batch=2, njoints=3, frames=5, coef=P, coef_c=P, x=P, x0_cond=P, out=Q, base_out=P)
+
+    def step(hist=(), **kw):
+        a = _lib.UnipcStepArgs(**{**ok, **kw})
+        for i, m in enumerate(hist):
+            a.hist[i] = m
+        return lib.gdx_unipc_step(C.byref(a), None)
+    for missing in ("coef", "x", "x0_cond", "out", "base_out"):
+        assert _refused(lib, step(**{missing: None}), b"null argument"), missing
+    for corr in (-1, 4):
+        assert _refused(lib, step(corr_order=corr), b"corr_order must be"), corr
+    for pred in (0, 4, -1):
+        assert _refused(lib, step(pred_order=pred), b"pred_order must be"), pred
+    for pair in ((2, 1), (3, 1), (0, 2), (0, 3), (1, 3)):
+        assert _refused(lib, step(corr_order=pair[0], pred_order=pair[1], hist=(S, S, S)), b"no such (corr_order, pred_order"), pair
+    assert _refused(lib, step(corr_order=1, coef_c=None, hist=(S,)), b"needs coef_c")
+    assert _refused(lib, step(out=P), b"base_out aliases out")
+    assert _refused(lib, step(batch=65536), b"bad shape") and _refused(lib, step(frames=-1), b"bad shape")
+    assert _refused(lib, step(x0_uncond=P), b"CFG needs scale")
+    assert _refused(lib, step(inpaint_mask=P), b"mask without motion")
+    assert _refused(lib, step(corr_order=1), b"missing history")                       # UniC-1 reads one older prediction
+    assert _refused(lib, step(corr_order=1, pred_order=2), b"missing history")
+    assert _refused(lib, step(corr_order=3, pred_order=3, hist=(S, S)), b"missing history")   # UniC-3 reads three
+    assert _refused(lib, step(corr_order=2, pred_order=3, hist=(S,)), b"missing history")
+    assert _refused(lib, step(corr_order=1, pred_order=2, hist=(S,), pred_out=S), b"aliases a history slot")
+    assert step(batch=0) == 0 and step(corr_order=3, pred_order=3, hist=(S, S, S), frames=0) == 0   # nothing to do is not an error
+
+
+def test_unipc_loop_refusals_without_gpu():
+    """The argument checks of gdx_unipc_loop need no handle: they come first, then the null handle, then the readiness check --
+    the order of gdx_dpm_loop."""
+    _lib = _lib_or_skip()
+    lib = _lib.load()
+    P = 4096
+    ok = dict(mode=0, order=2, num_steps=10, first_index=9, coef=P, coef_c=P, timestep_map=P, x=P, hist=P, base=P)
+    loop = lambda **kw: lib.gdx_unipc_loop(None, C.byref(_lib.UnipcLoopArgs(**{**ok, **kw})), None)   # noqa: E731
+    assert _refused(lib, lib.gdx_unipc_loop(None, None, None), b"null argument")
+    for missing in ("coef", "timestep_map", "x"):
+        assert _refused(lib, loop(**{missing: None}), b"null argument"), missing
+    assert _refused(lib, loop(mode=3), b"bad mode") and _refused(lib, loop(mode=-1), b"bad mode")
+    assert _refused(lib, loop(mode=2), b"needs scale")
+    for bad in (dict(num_steps=0), dict(first_index=10), dict(first_index=-1), dict(k_base=-1), dict(run_steps=-1),
+                dict(first_index=5, k_base=5), dict(first_index=3, run_steps=5)):
+        assert _refused(lib, loop(**bad), b"bad step range"), bad
+    for order in (0, 4, -2):
+        assert _refused(lib, loop(order=order), b"order must be"), order
+    assert _refused(lib, loop(inpaint_mask=P), b"mask without motion")
+    for missing in ("hist", "base", "coef_c"):
+        assert _refused(lib, loop(**{missing: None}), b"missing history"), missing
+    assert _refused(lib, loop(order=1, hist=None), b"missing history")   # the corrector reads a prediction at every order
+    assert _refused(lib, loop(), b"null handle")                # every argument in order: only the handle is missing
+    h = C.c_void_p()
+    cfg = _lib.Config(arch=1, njoints=16, latent_dim=128, ff_size=256, num_layers=2, num_heads=4, seed_poses=10, mfcc_dim=26,
+                      cl_head=8, window=10)
+    if lib.gdx_create(C.byref(cfg), C.byref(h)) == 0:          # where a handle can be made without a device: not prepared
+        assert _refused(lib, lib.gdx_unipc_loop(h, C.byref(_lib.UnipcLoopArgs(**ok)), None), b"gdx_prepare")
+        lib.gdx_destroy(h)
+
+
+# --------------------------------------------------------------------------------------------------------------------- CLI
+def test_parser_takes_unipc_and_its_order():
+    from gesturediffusion_amd.utils.parser_util import generate_args
+    a = generate_args(["--synthetic", "--sampler", "unipc", "--unipc_order", "3"])
+    assert a.sampler == "unipc" and a.unipc_order == 3
+    assert generate_args(["--synthetic", "--sampler", "unipc"]).unipc_order == 2
+    assert generate_args(["--synthetic"]).unipc_order == 2
+    for bad in ("0", "4"):
+        with pytest.raises(SystemExit):
+            generate_args(["--synthetic", "--sampler", "unipc", "--unipc_order", bad])
+
+
+def test_python_refusals_need_no_device():
+    df = diffusion("linear", "logsnr20")
+    for order in (0, 4):
+        with pytest.raises(ValueError, match="order is invalid"):
+            df.unipc_sample_loop(None, (2, 3, 1, 4), order=order)
+        with pytest.raises(ValueError, match="order is invalid"):
+            df.unipc_sample(None, torch.zeros(2, 3, 1, 4), torch.zeros(2, dtype=torch.long), order=order)
+    with pytest.raises(ValueError, match="rng must be"):
+        df.unipc_sample_loop(None, (2, 3, 1, 4), rng="numpy")
+    for kw in (dict(cond_fn_with_grad=True), dict(randomize_class=True)):
+        with pytest.raises(NotImplementedError):
+            df.unipc_sample_loop(None, (2, 3, 1, 4), **kw)
+        with pytest.raises(NotImplementedError):
+            next(df.unipc_sample_loop_progressive(None, (2, 3, 1, 4), **kw))

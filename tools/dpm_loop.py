@@ -2,10 +2,13 @@
 """ms/step of dpm_solver_sample_loop (orders 1 to 3) next to ddim_sample_loop and plms_sample_loop (order 2) on the same
 respacing, in one process:
     python tools/dpm_loop.py [--config genea|2|1] [--dtype fp32|fp16|bf16] [--respacing logsnr20] [--repeats 5]
-                             [--sde] [--out profiles/FILE.txt]
+                             [--sde | --unipc] [--out profiles/FILE.txt]
 --sde measures dpm_solver_sde_sample_loop (orders 1 and 2, eta = 1, in-kernel Philox noise) next to dpm_solver_sample_loop at
 order 2 and p_sample_loop (Philox) on the same respacing instead; the expectation is one Philox draw per element on top of the
 ODE step.
+--unipc measures unipc_sample_loop (orders 1 to 3) next to dpm_solver_sample_loop at the same order instead and records the
+ratio per order; the expectation is the same forward plus one launch that reads up to one history tensor more and writes the
+corrected state as well (the forward dominates; the ratio is recorded, not gated).
 Every loop runs once as a warm-up at the timed shape, then `repeats` times between two events on the stream, the loops
 alternating inside each repeat; the median is reported with the spread, per step of the respacing ("logsnrN" can keep fewer
 than N steps: the record says how many; PLMS runs one forward more than it has steps).  One JSON line per run; kernel-level
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--respacing", default="logsnr20")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sde", action="store_true", help="time the stochastic loop against the ODE loop and p_sample_loop")
+    ap.add_argument("--unipc", action="store_true", help="time unipc_sample_loop against dpm_solver_sample_loop, order by order")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -66,7 +70,13 @@ def main():
         y["scale"] = torch.full((B,), 2.5, device=dev)
         m = ClassifierFreeSampleModel(model)
     kw = dict(noise=x, clip_denoised=False, model_kwargs={"y": y})
-    if a.sde:
+    assert not (a.sde and a.unipc), "--sde and --unipc are two measurements"
+    if a.unipc:
+        loops = {}
+        for o in (1, 2, 3):                                                    # neighbours in the alternation: same order
+            loops[f"dpm_order{o}"] = lambda o=o: df.dpm_solver_sample_loop(m, (B, J, 1, T), order=o, **kw)
+            loops[f"unipc_order{o}"] = lambda o=o: df.unipc_sample_loop(m, (B, J, 1, T), order=o, **kw)
+    elif a.sde:
         loops = {f"dpm_sde_order{o}": (lambda o=o: df.dpm_solver_sde_sample_loop(m, (B, J, 1, T), order=o, eta=1.0, rng="philox",
                                                                                  philox_seed=10, **kw)) for o in (1, 2)}
         loops["dpm_order2"] = lambda: df.dpm_solver_sample_loop(m, (B, J, 1, T), order=2, **kw)
@@ -85,7 +95,9 @@ def main():
     rec = dict(tool="dpm_loop", config=a.config, label=p["label"], arch=p["arch"], B=B, T=T, J=J, d=p["d"], dtype=dtype,
                guidance=bool(p["cfg"]), respacing=a.respacing, steps=steps, repeats=a.repeats,
                device=torch.cuda.get_device_name(0))
-    if a.sde:
+    if a.unipc:
+        rec["unipc"] = True
+    elif a.sde:
         rec["sde"] = True
     else:
         ref = first["ddim"].double()
@@ -93,6 +105,10 @@ def main():
     for k, v in ms.items():
         rec[k + "_ms_per_step"] = round(statistics.median(v), 5)
         rec[k + "_ms_per_step_min_max"] = [round(min(v), 5), round(max(v), 5)]
+    if a.unipc:
+        for o in (1, 2, 3):
+            med = {w: statistics.median(ms[f"{w}_order{o}"]) for w in ("unipc", "dpm")}
+            rec[f"unipc_over_dpm_order{o}"] = round(med["unipc"] / med["dpm"], 4)
     line = json.dumps(rec)
     print(line, flush=True)
     if a.out:
