@@ -1,5 +1,5 @@
 // Device one-liners shared by the kernel files of libgdx.so (gfx950 only): vector types, the 16-bit MFMA of the build's half
-// type, the counted vector-memory wait and the XCD-contiguous workgroup id.  Included after gdx_internal.h.
+// type, the counted vector-memory wait, the wave sum and the XCD-contiguous workgroup id.  Included after gdx_internal.h.
 #pragma once
 #include "gdx_internal.h"
 
@@ -21,6 +21,13 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // s_waitcnt vmcnt(N): all but the youngest N vector-memory operations of the wave have retired
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// sum over the 64 lanes of the wave, in every lane
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 // Logical workgroup id with the workgroups of one XCD contiguous (blocks b, b + 8, b + 16, ... share an XCD and its L2; bijective
 // for any grid size G).  Work that shares operands gets consecutive logical ids and so runs on ONE XCD at about the same time:

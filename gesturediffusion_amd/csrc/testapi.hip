@@ -292,7 +292,7 @@ extern "C" int gdx_local_attention(const float* xseq, const float* cosT, const f
     return enc16 ? sc.widen(e16, enc16, n_out) : 0;
 }
 
-// ---- the boundary kernels of the denoiser step (misc.hip), each through the launcher the forwards call.  Inputs are read where
+// ---- the boundary kernels of the denoiser step (boundary.hip, boundaryh.hip), each through the launcher the forwards call.  Inputs are read where
 // the caller put them (strides and the rows behind them included); every output is staged from the caller's own values and
 // copied back whole, so elements the kernel does not store come back unchanged.  Every refusal comes before the first HIP call
 // (tests/test_host_logic.py checks them without a GPU).

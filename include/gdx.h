@@ -802,7 +802,7 @@ int gdx_linear_half(const float* A, const float* W, const float* bias, const flo
                     int32_t ldv, float* C32, float* C16, int32_t c_rows, int32_t M, int32_t N, int32_t K, int32_t T,
                     int32_t rowmap, int32_t gelu, int32_t dtype, int32_t tile_mb, int32_t tile_nbw, int32_t* launched,
                     void* stream);
-/* out = LayerNorm(x + res) over rows of d (eps 1e-5, biased variance; csrc/misc.hip) as the forwards launch it.
+/* out = LayerNorm(x + res) over rows of d (eps 1e-5, biased variance; csrc/norm.hip) as the forwards launch it.
  * half_input = 0: fp32 x / res (the fp32 kernels, with a 16-bit copy out16 in element type dtype when out16 is given);
  * half_input = 1: x / res rounded to dtype (GDX_DTYPE_F16 / _BF16) by the call, the 16-bit kernels (out16 required, out32
  * optional).  res may be NULL.  compact_S > 0: rows are [B, S] tokens and token 0 of every sample is dropped from the output.
@@ -820,7 +820,7 @@ int gdx_layernorm(const float* x, const float* res, const float* gamma, const fl
 int gdx_local_attention(const float* xseq, const float* cosT, const float* sinT, float* enc, float* enc16, int32_t enc_rows,
                         int32_t B, int32_t T, int32_t d, int32_t heads, int32_t window, int32_t dtype, int32_t* kernel,
                         void* stream);
-/* ---- the boundary kernels of the denoiser step (csrc/misc.hip; tests) -------------------- */
+/* ---- the boundary kernels of the denoiser step (csrc/boundary.hip, csrc/boundaryh.hip; tests) -------------------- */
 /* Each of the six calls below runs one launcher exactly as the forwards call it.  Inputs are fp32 device arrays read in
  * place, with the caller's strides.  Every output is an fp32 device array of a stated row capacity (at least the rows the
  * kernel stores); it is staged from the caller's own values and copied back whole, so elements the kernel does not store

@@ -1,6 +1,6 @@
 """Kernel-level tests of the 16-bit building blocks (fp16 and bf16 builds): every tile of the reduced-precision GEMM
-(csrc/gemmh.hip) under every epilogue the forwards use, the LayerNorm kernels (csrc/misc.hip) and the V2 front end
-(RoPE -> causal local attention -> RoPE at t+1, csrc/misc.hip), each through its C-ABI test entry point against a plain
+(csrc/gemmh.hip) under every epilogue the forwards use, the LayerNorm kernels (csrc/norm.hip) and the V2 front end
+(RoPE -> causal local attention -> RoPE at t+1, csrc/frontend.hip), each through its C-ABI test entry point against a plain
 float64 reference of the same operation on the same (rounded) inputs.  Need an MI355X.
 
 Every output buffer is prefilled with NaN and carries sentinel rows past its end: rows the kernel must write have to come

@@ -1,4 +1,4 @@
-"""The MFCC front end (gdx_mfcc: mfcc_frames / mfcc_power / mfcc_cepstrum kernels of csrc/misc.hip and the two fp32 GEMMs in
+"""The MFCC front end (gdx_mfcc: mfcc_frames / mfcc_power / mfcc_cepstrum kernels of csrc/mfcc.hip and the two fp32 GEMMs in
 between) stage by stage against float64, at five geometries and at the signals where such kernels go wrong.  Need an MI355X.
 
 The stages are read from the caller's workspace (MfccExtractor.workspace / stage_views); each is compared on the device's own

@@ -641,3 +641,20 @@ def test_step_entry_refusal_order_with_two_defects(entry, struct, bad, winners):
     for defects, want in zip((dict(out=None, **bad), dict(batch=65536, **bad)), winners):
         rc = getattr(lib, entry)(C.byref(getattr(_lib, struct)(**{**ok, **defects})), None)
         assert rc == -1 and lib.gdx_last_error().decode() == want, defects
+
+
+def test_half_srcs_are_exactly_the_kernel_files_that_mention_half_t():
+    """csrc/Makefile builds the files of HALF_SRCS a second time with -DGDX_BF16 (namespace gdx::b16).  A file belongs there
+    exactly when its text depends on the 16-bit type: a file of fp32-only kernels in the list would be compiled into a
+    second, never-called copy, and a file with half_t outside it would have no bf16 build."""
+    csrc = os.path.join(REPO, "gesturediffusion_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    srcs, half = (re.search(r"^%s\s*=\s*(.*)$" % var, mk, re.M).group(1).split() for var in ("SRCS", "HALF_SRCS"))
+    assert half and set(half) <= set(srcs)
+    text = {f: open(os.path.join(csrc, f)).read() for f in srcs}
+    for f in half:
+        assert "GDX_HNS_BEGIN" in text[f] and "half_t" in text[f], f
+    once = [f for f in srcs if f.endswith(".hip") and f not in half and "__global__" in text[f]]
+    assert once
+    for f in once:
+        assert "GDX_HNS_BEGIN" not in text[f] and "half_t" not in text[f], f

@@ -3,11 +3,15 @@
 
     python tools/isa_compare.py OLD_TREE NEW_TREE [-j N]
 
-Every kernel file of csrc/ is compiled to device-only assembly with the Makefile's flags (the half files also with -DGDX_BF16,
-sampler.hip with -ffp-contract=off).  Per kernel the instruction stream (comments dropped) and the .vgpr_count / .sgpr_count /
-LDS / scratch / kernarg sizes of the metadata are compared; kernels are matched by symbol (and the variant's extra flags) across the whole tree,
-so one that moved to another file compares equal and is reported as moved; the two leading template arguments that older
-trees gave gemm_kernel are removed, and so are the two trailing ones (ring depth 6, whole-line pipeline) of older trees' gemmh_kernel.  Prints one line per difference or move and a summary line; exit status 1 if any difference.
+Every kernel file of csrc/ is compiled to device-only assembly with the Makefile's flags (the files of each tree's own
+HALF_SRCS line also with -DGDX_BF16, sampler.hip with -ffp-contract=off).  Per kernel the instruction stream (comments and the
+per-file numbers of local labels dropped) and the .vgpr_count / .sgpr_count / LDS / scratch / kernarg sizes of the metadata are
+compared.  Kernels are matched by symbol (and the variant's extra flags) across the whole tree, so one that moved to another file
+compares equal and is reported as moved.  The half builds' namespaces gdx::h16:: and gdx::b16:: count as gdx:: (the -DGDX_BF16
+flag keeps the two builds apart), so a kernel that left the half build, or a template that left the namespace because its
+argument names the element type, is "moved" as well, not one removed and one added.  The two leading template arguments that
+older trees gave gemm_kernel are removed, and so are the two trailing ones (ring depth 6, whole-line pipeline) of older trees'
+gemmh_kernel.  Prints one line per difference or move and a summary line; exit status 1 if any difference.
 """
 import concurrent.futures
 import os
@@ -18,18 +22,24 @@ import tempfile
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-variable -Wno-unused-but-set-variable".split()
-HALF = ("gemmh.hip", "attentionh.hip", "misc.hip")
 META = (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".kernarg_segment_size")
 
 
+def half_srcs(csrc):
+    """the files a tree builds a second time with -DGDX_BF16: the HALF_SRCS line of its Makefile"""
+    m = re.search(r"^HALF_SRCS\s*=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
+    return m.group(1).split() if m else []
+
+
 def variants(csrc):
+    half = half_srcs(csrc)
     for f in sorted(os.listdir(csrc)):
         if not f.endswith(".hip"):
             continue
         if "__global__" not in open(os.path.join(csrc, f)).read():
             continue
         yield f, f, ["-ffp-contract=off"] if f == "sampler.hip" else []
-        if f in HALF:
+        if f in half:
             yield f + " -DGDX_BF16", f, ["-DGDX_BF16"]
 
 
@@ -39,7 +49,16 @@ def emit(csrc, src, extra, out):
     return open(out).read()
 
 
+def drop_half_ns(m):
+    """N3gdx3h16<rest> -> N3gdx<rest>: the name loses one component and with it substitution S0_, so S<k+1>_ becomes S<k>_"""
+    def shift(s):
+        k = int(s.group(1), 36)
+        return "S_" if k == 0 else "S%s_" % "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"[k - 1]   # no kernel here has more than 36
+    return "N3gdx" + re.sub(r"S([0-9A-Z])_", shift, m.group(1))
+
+
 def norm(text):
+    text = re.sub(r"N3gdx3[hb]16(\w+)", drop_half_ns, text)
     text = re.sub(r"gemm_kernelILi\dELi\dELi(\d)ELi(\d)EEE", r"gemm_kernelILi\1ELi\2EEE", text)
     return re.sub(r"gemmh_kernelILi(\d+)ELi(\d)ELi6ELb1EEE", r"gemmh_kernelILi\1ELi\2EEE", text)
 
@@ -58,7 +77,7 @@ def kernels(text):
     for n in names:
         body = text[text.index("\n%s:" % n):]
         body = body[:body.index(".Lfunc_end")]
-        lines = [re.sub(r"\s*;.*$", "", ln).strip() for ln in body.splitlines()]
+        lines = [re.sub(r"\.L([A-Za-z]+)\d+_", r".L\1_", re.sub(r"\s*;.*$", "", ln)).strip() for ln in body.splitlines()]
         out[n] = ([ln for ln in lines if ln], meta[n])
     return out
 
