@@ -1,36 +1,25 @@
-"""ctypes binding of libgdx.so (C ABI: include/gdx.h).
+"""ctypes binding of libgdx.so, derived from its C ABI, include/gdx.h, at import.
+
+The header is the one statement of the ABI: ``parse_header`` reads its constants, structs and prototypes, and this module
+builds the ``ctypes.Structure`` classes (``gdx_dpm_step_args_t`` -> ``DpmStepArgs``), the ``GDX_*`` constants, ``EXPORTS`` and
+every function's ``argtypes`` / ``restype`` from them.  The only hand-written part is the table from C type names to ctypes
+(``_CTYPES``).  The parser takes exactly the C the header uses and raises on anything else, so a header change it does not
+understand stops the import instead of producing a shorter struct.  tests/test_abi_host.py has a C compiler confirm every
+size, offset and prototype.
 
 The product path has NO fallback: if the HIP library is missing or fails to load, every
 compute entry point raises.  Build it with ``python __graft_entry__.py`` (or
 ``make -C gesturediffusion_amd/csrc``); the .so stays in-tree next to its sources.
 """
+import collections
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GDX_LIBGDX: another build of the same library (A/B measurements of one kernel on one box); there is still no fallback
 LIB_PATH = os.environ.get("GDX_LIBGDX") or os.path.join(_HERE, "csrc", "libgdx.so")
-
-GDX_ARCH_MDM_OLD, GDX_ARCH_MDM = 1, 2
-GDX_COND, GDX_UNCOND, GDX_CFG = 0, 1, 2
-GDX_SAMPLER_P, GDX_SAMPLER_DDIM = 0, 1
-GDX_ROW_PAD = 256      # include/gdx.h
-
-EXPORTS = [
-    "gdx_create", "gdx_destroy", "gdx_last_error", "gdx_set_weight", "gdx_weights_ready", "gdx_prepare",
-    "gdx_set_condition", "gdx_forward", "gdx_set_keep_taps", "gdx_get_tap", "gdx_sampler_update", "gdx_q_sample",
-    "gdx_randn", "gdx_sample_loop", "gdx_bench_ffn_gemm", "gdx_bench_gemm", "gdx_forward_flops", "gdx_profile_begin", "gdx_profile_end", "gdx_bench_attention",
-    "gdx_linear_f16", "gdx_linear_f32", "gdx_bench_gemm_f16", "gdx_attention_f16", "gdx_attention_f32", "gdx_plms_update", "gdx_postprocess", "gdx_q_sample_t", "gdx_masked_l2", "gdx_set_graph_replay", "gdx_mfcc",
-    "gdx_set_guards", "gdx_check_guards", "gdx_packed_bytes", "gdx_export_packed", "gdx_import_packed", "gdx_set_test_half_dtype",
-    "gdx_set_test_gemmh_tile", "gdx_linear_half", "gdx_layernorm", "gdx_local_attention", "gdx_attention_half",
-    "gdx_attention_f32_rows",
-    "gdx_bpd_terms", "gdx_bpd_loop", "gdx_linear_full", "gdx_plms_step", "gdx_plms_loop",
-    "gdx_dpm_step", "gdx_dpm_loop", "gdx_dpm_sde_step", "gdx_dpm_sde_loop", "gdx_unipc_step", "gdx_unipc_loop",
-    "gdx_set_guidance_interval", "gdx_forward_samples", "gdx_set_guidance_rescale", "gdx_cfg_rescale",
-    "gdx_set_guidance_refresh", "gdx_cfg_delta",
-    "gdx_transpose_in", "gdx_transpose_out", "gdx_small_linear", "gdx_gather_rows", "gdx_mfcc_project", "gdx_token0",
-]
-GDX_BPD_CHUNK = 4096   # include/gdx.h
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gdx.h")
 INT64_MIN, INT64_MAX = -2**63, 2**63 - 1   # gdx_set_guidance_interval's default: every timestep
 
 
@@ -38,151 +27,151 @@ class GdxError(RuntimeError):
     pass
 
 
-class Config(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("arch", "njoints", "latent_dim", "ff_size", "num_layers", "num_heads",
-                                         "seed_poses", "mfcc_dim", "cl_head", "window", "compute_dtype")]
+# C type name -> ctypes.  `const char*` is c_char_p, a pointer to a parsed struct is POINTER(that struct) and every other
+# pointer is c_void_p (_ctype): the header cannot tell a device address from a host out-parameter.
+_CTYPES = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "uint8_t": C.c_uint8,
+           "float": C.c_float, "double": C.c_double, "int": C.c_int, "gdx_handle_t": C.c_void_p}
+
+# constants: {name: int};  structs: {C name: [(type, field, array length or None)]};  prototypes: {name: (return type,
+# [(type, parameter)])}, all in header order.  A type is written "[const ]T[*]".
+Header = collections.namedtuple("Header", "constants structs prototypes")
+
+# The grammar, one pattern per form.  A type in front of a function's or a parameter's name is "[const] T" then '*' or a blank.
+_INT = r"([-+]?(?:0[xX][0-9a-fA-F]+|\d+))"
+_TYPE = r"(const\s+)?(\w+)(\s*\*\s*|\s+)"
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_CPLUSPLUS = re.compile(r'#ifdef __cplusplus\s+(?:extern "C" \{|\})\s+#endif\b')
+_GUARD = re.compile(r"\s*#ifndef (\w+)\s+#define \1[ \t]*\n(.*)#endif\s*", re.S)
+_DIRECTIVE = re.compile(r"^[ \t]*(#[^\n]*?)[ \t]*$", re.M)
+_DEFINE = re.compile(r"#define (\w+)\s+" + _INT)
+_DECL = re.compile(r"\s*([^;{}]*(?:\{[^{}]*\}[^;{}]*)?);")      # at most one pair of braces, never nested, ended by ';'
+_ENUM = re.compile(r"enum\s*\{(.*)\}", re.S)
+_ENUM_ENTRY = re.compile(r"\s*(\w+)\s*=\s*" + _INT + r"\s*")
+_HANDLE = re.compile(r"typedef\s+struct\s+\w+\s*\*\s*(\w+)")
+_STRUCT = re.compile(r"typedef\s+struct\s*\{(.*);\s*\}\s*(\w+)", re.S)
+_FIELD = re.compile(r"\s*(const\s+)?(\w+)\b(.*)", re.S)          # the type, then one declarator or several
+_DECLARATOR = re.compile(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*")
+_PROTO = re.compile(_TYPE + r"(\w+)\s*\((.*)\)", re.S)
+_PARAM = re.compile(r"\s*" + _TYPE + r"(\w+)\s*")
 
 
-class UpdateArgs(C.Structure):
-    _fields_ = [
-        ("kind", C.c_int32), ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32),
-        ("coef", C.c_void_p), ("t", C.c_void_p), ("step_index", C.c_int32),
-        ("x", C.c_void_p), ("x0_cond", C.c_void_p), ("x0_uncond", C.c_void_p), ("scale", C.c_void_p),
-        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("noise", C.c_void_p),
-        ("const_noise", C.c_int32), ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64),
-        ("rng_step", C.c_uint32), ("out", C.c_void_p), ("pred_xstart", C.c_void_p),
-        ("cond_grad", C.c_void_p), ("cond_coef", C.c_void_p), ("clip_denoised", C.c_int32),
-    ]
+def parse_header(text):
+    """Parse the subset of C that include/gdx.h is written in; ValueError, naming the text, on anything else.
+
+    Accepted: comments, the include guard, ``#include <stdint.h>``, the ``#ifdef __cplusplus`` / ``extern "C"`` wrapper,
+    ``#define NAME integer``, anonymous enums with explicit values, ``typedef struct tag* name;`` for a name in the type table,
+    ``typedef struct { ... } name;`` whose fields are ``[const] T name``, ``[const] T* name`` or ``[const] T* name[N]`` (several
+    declarators per line allowed), and prototypes ``[const] T[*] name(void | [const] T[*] name, ...);``."""
+    hdr = Header({}, {}, {})
+
+    def bad(what, src):
+        return ValueError(f"gdx.h: {what}: {' '.join(src.split())!r}")
+
+    def add(table, name, value, src):
+        if name in table:
+            raise bad(f"{name} declared twice", src)
+        table[name] = value
+
+    def ctype_name(const, base, star, src):
+        star = star.strip()
+        if base in hdr.structs and not star:
+            raise bad(f"struct {base} by value (a nested struct)", src)
+        if not (base in _CTYPES or base in hdr.structs or (star and base in ("void", "char"))):
+            raise bad(f"unknown type {base!r}", src)
+        return ("const " if const else "") + base + star
+
+    def directive(m):
+        define = _DEFINE.fullmatch(m.group(1))
+        if define:
+            add(hdr.constants, define.group(1), int(define.group(2), 0), m.group(1))
+        elif m.group(1) != "#include <stdint.h>":
+            raise bad("unknown directive", m.group(1))
+        return " "
+
+    text = _COMMENT.sub(" ", text)
+    if "/*" in text:
+        raise bad("unterminated comment", text[text.index("/*"):][:60])
+    text = _CPLUSPLUS.sub(" ", text)
+    guard = _GUARD.fullmatch(text)
+    text = _DIRECTIVE.sub(directive, guard.group(2) if guard else text)
+
+    decls, pos = [], 0
+    while m := _DECL.match(text, pos):
+        decls.append(m.group(1).strip())
+        pos = m.end()
+    if text[pos:].strip():
+        raise bad("nested braces or an unfinished declaration", text[pos:][:200])
+
+    for d in decls:
+        if m := _ENUM.fullmatch(d):
+            for entry in m.group(1).split(","):
+                e = _ENUM_ENTRY.fullmatch(entry)
+                if not e:
+                    raise bad("enum constant without an explicit integer value", entry)
+                add(hdr.constants, e.group(1), int(e.group(2), 0), entry)
+        elif m := _HANDLE.fullmatch(d):
+            if m.group(1) not in _CTYPES:
+                raise bad(f"unknown type {m.group(1)!r}", d)
+        elif m := _STRUCT.fullmatch(d):
+            fields = []
+            for line in m.group(1).split(";"):
+                t = _FIELD.fullmatch(line)
+                for declarator in t.group(3).split(",") if t else [""]:
+                    f = _DECLARATOR.fullmatch(declarator)
+                    if not f or (f.group(3) and not f.group(1)):        # an array of anything but pointers is not in use
+                        raise bad("not a field declaration", line)
+                    if f.group(2) in [name for _, name, _ in fields]:
+                        raise bad(f"field {f.group(2)} declared twice", line)
+                    fields.append((ctype_name(t.group(1), t.group(2), f.group(1), line), f.group(2),
+                                   int(f.group(3)) if f.group(3) else None))
+            add(hdr.structs, m.group(2), fields, d)
+        elif m := _PROTO.fullmatch(d):
+            params = []
+            for p in m.group(5).split(",") if m.group(5).strip() != "void" else []:
+                q = _PARAM.fullmatch(p)
+                if not q:
+                    raise bad("not a parameter declaration", p)
+                params.append((ctype_name(*q.group(1, 2, 3), p), q.group(4)))
+            add(hdr.prototypes, m.group(4), (ctype_name(*m.group(1, 2, 3), d), params), d)
+        else:
+            raise bad("not a declaration this binding understands", d)
+    return hdr
 
 
-class PlmsArgs(C.Structure):
-    _fields_ = [
-        ("kind", C.c_int32), ("batch", C.c_int32), ("per_sample", C.c_int64), ("coef", C.c_void_p), ("t", C.c_void_p),
-        ("step_index", C.c_int32), ("x", C.c_void_p), ("pred_xstart", C.c_void_p), ("eps", C.c_void_p * 4),
-        ("out", C.c_void_p),
-    ]
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            text = f.read()
+    except OSError as e:
+        raise GdxError(f"cannot read the C ABI {HEADER_PATH}: {e}") from e
+    return parse_header(text)
 
 
-class PlmsStepArgs(C.Structure):
-    _fields_ = [
-        ("kind", C.c_int32), ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32),
-        ("coef", C.c_void_p), ("t", C.c_void_p), ("t_eps", C.c_void_p), ("step_index", C.c_int32),
-        ("step_index_eps", C.c_int32), ("x", C.c_void_p), ("x_eps", C.c_void_p), ("x0_cond", C.c_void_p),
-        ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p),
-        ("clip_denoised", C.c_int32), ("eps_hist", C.c_void_p * 3), ("pred_prev", C.c_void_p), ("eps_out", C.c_void_p),
-        ("out", C.c_void_p), ("pred_xstart", C.c_void_p),
-    ]
+HEADER = _read_header()
+STRUCTS = {}        # C name -> ctypes.Structure class, also a module attribute under its CamelCase name
 
 
-class PlmsLoopArgs(C.Structure):
-    _fields_ = [
-        ("mode", C.c_int32), ("order", C.c_int32), ("num_steps", C.c_int32), ("first_index", C.c_int32),
-        ("coef", C.c_void_p), ("timestep_map", C.c_void_p), ("x", C.c_void_p), ("scale", C.c_void_p),
-        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32),
-        ("run_steps", C.c_int32), ("k_base", C.c_int32), ("eps_hist", C.c_void_p), ("scratch", C.c_void_p),
-    ]
+def _ctype(t):
+    if t == "const char*":
+        return C.c_char_p
+    base = t.removeprefix("const ").rstrip("*")
+    if t.endswith("*"):
+        return C.POINTER(STRUCTS[base]) if base in STRUCTS else C.c_void_p
+    return _CTYPES[base]
 
 
-class DpmStepArgs(C.Structure):
-    _fields_ = [
-        ("order", C.c_int32), ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32),
-        ("coef", C.c_void_p), ("t", C.c_void_p), ("step_index", C.c_int32), ("x", C.c_void_p), ("x0_cond", C.c_void_p),
-        ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p),
-        ("clip_denoised", C.c_int32), ("hist", C.c_void_p * 2), ("out", C.c_void_p), ("pred_out", C.c_void_p),
-    ]
+def _class_name(c_name):
+    """gdx_dpm_sde_step_args_t -> DpmSdeStepArgs"""
+    return "".join(w.capitalize() for w in c_name.removeprefix("gdx_").removesuffix("_t").split("_"))
 
 
-class DpmLoopArgs(C.Structure):
-    _fields_ = [
-        ("mode", C.c_int32), ("order", C.c_int32), ("num_steps", C.c_int32), ("first_index", C.c_int32),
-        ("coef", C.c_void_p), ("timestep_map", C.c_void_p), ("x", C.c_void_p), ("scale", C.c_void_p),
-        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32),
-        ("run_steps", C.c_int32), ("k_base", C.c_int32), ("hist", C.c_void_p),
-    ]
-
-
-class DpmSdeStepArgs(C.Structure):
-    _fields_ = [
-        ("order", C.c_int32), ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32),
-        ("coef", C.c_void_p), ("t", C.c_void_p), ("step_index", C.c_int32), ("x", C.c_void_p), ("x0_cond", C.c_void_p),
-        ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p),
-        ("clip_denoised", C.c_int32), ("hist", C.c_void_p * 1), ("out", C.c_void_p), ("pred_out", C.c_void_p),
-        ("noise", C.c_void_p), ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64), ("rng_step", C.c_uint32),
-    ]
-
-
-class DpmSdeLoopArgs(C.Structure):
-    _fields_ = [
-        ("mode", C.c_int32), ("order", C.c_int32), ("num_steps", C.c_int32), ("first_index", C.c_int32),
-        ("coef", C.c_void_p), ("timestep_map", C.c_void_p), ("x", C.c_void_p), ("scale", C.c_void_p),
-        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32),
-        ("run_steps", C.c_int32), ("k_base", C.c_int32), ("hist", C.c_void_p), ("noise_tape", C.c_void_p),
-        ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64),
-    ]
-
-
-class UnipcStepArgs(C.Structure):
-    _fields_ = [
-        ("corr_order", C.c_int32), ("pred_order", C.c_int32), ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32),
-        ("coef", C.c_void_p), ("coef_c", C.c_void_p), ("t", C.c_void_p), ("step_index", C.c_int32), ("x", C.c_void_p),
-        ("x0_cond", C.c_void_p), ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p),
-        ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32), ("hist", C.c_void_p * 3), ("base_out", C.c_void_p),
-        ("out", C.c_void_p), ("pred_out", C.c_void_p),
-    ]
-
-
-class UnipcLoopArgs(C.Structure):
-    _fields_ = [
-        ("mode", C.c_int32), ("order", C.c_int32), ("num_steps", C.c_int32), ("first_index", C.c_int32),
-        ("coef", C.c_void_p), ("timestep_map", C.c_void_p), ("x", C.c_void_p), ("scale", C.c_void_p),
-        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("clip_denoised", C.c_int32),
-        ("run_steps", C.c_int32), ("k_base", C.c_int32), ("hist", C.c_void_p), ("base", C.c_void_p), ("coef_c", C.c_void_p),
-    ]
-
-
-class LoopArgs(C.Structure):
-    _fields_ = [
-        ("kind", C.c_int32), ("mode", C.c_int32), ("num_steps", C.c_int32), ("first_index", C.c_int32),
-        ("coef", C.c_void_p), ("timestep_map", C.c_void_p), ("x", C.c_void_p), ("scale", C.c_void_p),
-        ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p), ("noise_tape", C.c_void_p),
-        ("const_noise", C.c_int32), ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64),
-        ("dump", C.c_void_p), ("dump_steps", C.c_void_p), ("n_dump", C.c_int32),
-        ("run_steps", C.c_int32), ("k_base", C.c_int32), ("clip_denoised", C.c_int32),
-    ]
-
-
-class BpdArgs(C.Structure):
-    _fields_ = [
-        ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32), ("step_index", C.c_int32),
-        ("coef", C.c_void_p), ("t", C.c_void_p), ("x_start", C.c_void_p), ("x_t", C.c_void_p), ("noise", C.c_void_p),
-        ("x0_cond", C.c_void_p), ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p),
-        ("inpaint_motion", C.c_void_p), ("model_mean", C.c_void_p), ("clip_denoised", C.c_int32), ("prior", C.c_int32),
-        ("prior_log_variance", C.c_float), ("vb", C.c_void_p), ("xstart_mse", C.c_void_p), ("mse", C.c_void_p),
-        ("ld", C.c_int32), ("col", C.c_int32), ("pred_xstart", C.c_void_p), ("workspace", C.c_void_p),
-    ]
-
-
-class BpdLoopArgs(C.Structure):
-    _fields_ = [
-        ("mode", C.c_int32), ("num_steps", C.c_int32), ("coef", C.c_void_p), ("timestep_map", C.c_void_p),
-        ("x_start", C.c_void_p), ("scale", C.c_void_p), ("inpaint_mask", C.c_void_p), ("inpaint_motion", C.c_void_p),
-        ("noise_tape", C.c_void_p), ("philox_seed", C.c_uint64), ("sample_offset", C.c_uint64),
-        ("clip_denoised", C.c_int32), ("run_steps", C.c_int32), ("k_base", C.c_int32), ("prior_log_variance", C.c_float),
-        ("vb", C.c_void_p), ("xstart_mse", C.c_void_p), ("mse", C.c_void_p), ("prior_bpd", C.c_void_p),
-    ]
-
-
-class CfgRescaleArgs(C.Structure):
-    _fields_ = [
-        ("batch", C.c_int32), ("njoints", C.c_int32), ("frames", C.c_int32), ("x0_cond", C.c_void_p),
-        ("x0_uncond", C.c_void_p), ("scale", C.c_void_p), ("phi", C.c_float), ("t", C.c_void_p), ("lo", C.c_int64),
-        ("hi", C.c_int64), ("workspace", C.c_void_p), ("factor", C.c_void_p), ("out", C.c_void_p),
-    ]
-
-
-class CfgDeltaArgs(C.Structure):
-    _fields_ = [("count", C.c_int64), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p)]
-
+for _c_name, _fields in HEADER.structs.items():
+    STRUCTS[_c_name] = type(_class_name(_c_name), (C.Structure,),
+                            {"_fields_": [(f, _ctype(t) * n if n else _ctype(t)) for t, f, n in _fields]})
+globals().update({cls.__name__: cls for cls in STRUCTS.values()})
+globals().update(HEADER.constants)      # GDX_ROW_PAD, GDX_BPD_CHUNK, GDX_ARCH_*, GDX_COND ..., GDX_DTYPE_*, GDX_SAMPLER_*
+EXPORTS = list(HEADER.prototypes)
+SIGNATURES = {name: (_ctype(ret), [_ctype(t) for t, _ in params]) for name, (ret, params) in HEADER.prototypes.items()}
 
 _lib = None
 
@@ -202,81 +191,9 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64, wrong arch ...
         raise GdxError(f"cannot load {LIB_PATH}: {e}") from e
-    vp, i32, i64, u64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_uint32
-    lib.gdx_last_error.restype = C.c_char_p
-    sigs = {
-        "gdx_create": [C.POINTER(Config), C.POINTER(vp)],
-        "gdx_destroy": [vp],
-        "gdx_set_weight": [vp, C.c_char_p, vp, C.POINTER(i64), i32, vp],
-        "gdx_weights_ready": [vp],
-        "gdx_prepare": [vp, i32, i32],
-        "gdx_set_condition": [vp, vp, vp, vp],
-        "gdx_forward": [vp, vp, vp, i32, vp, vp, vp],
-        "gdx_set_keep_taps": [vp, i32],
-        "gdx_get_tap": [vp, i32, vp, i64, vp],
-        "gdx_sampler_update": [C.POINTER(UpdateArgs), vp],
-        "gdx_q_sample": [vp, vp, vp, i32, i64, vp, vp],
-        "gdx_randn": [vp, i32, i64, u64, u64, u32, vp],
-        "gdx_sample_loop": [vp, C.POINTER(LoopArgs), vp],
-        "gdx_bench_ffn_gemm": [vp, i32, C.POINTER(C.c_float), vp],
-        "gdx_forward_flops": [vp, i32, C.POINTER(C.c_double)],
-        "gdx_bench_gemm": [i32, i32, i32, i32, i32, C.POINTER(C.c_float), vp],
-        "gdx_bench_attention": [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), vp],
-        "gdx_linear_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-        "gdx_linear_f32": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-        "gdx_linear_half": [vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                            C.POINTER(i32), vp],
-        "gdx_linear_full": [vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                            C.POINTER(i32), vp],
-        "gdx_layernorm": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-        "gdx_local_attention": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
-        "gdx_transpose_in": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-        "gdx_transpose_out": [vp, vp, i32, i32, i32, i32, i32, vp],
-        "gdx_small_linear": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-        "gdx_gather_rows": [vp, vp, vp, i32, i32, i32, i32, vp],
-        "gdx_mfcc_project": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-        "gdx_token0": [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp],
-        "gdx_set_graph_replay": [vp, i32],
-        "gdx_mfcc": [vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "gdx_q_sample_t": [vp, vp, vp, vp, i32, i64, vp, vp],
-        "gdx_masked_l2": [vp, vp, vp, vp, i32, i32, i32, vp],
-        "gdx_postprocess": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
-        "gdx_plms_update": [C.POINTER(PlmsArgs), vp],
-        "gdx_plms_step": [C.POINTER(PlmsStepArgs), vp],
-        "gdx_plms_loop": [vp, C.POINTER(PlmsLoopArgs), vp],
-        "gdx_dpm_step": [C.POINTER(DpmStepArgs), vp],
-        "gdx_dpm_loop": [vp, C.POINTER(DpmLoopArgs), vp],
-        "gdx_dpm_sde_step": [C.POINTER(DpmSdeStepArgs), vp],
-        "gdx_dpm_sde_loop": [vp, C.POINTER(DpmSdeLoopArgs), vp],
-        "gdx_unipc_step": [C.POINTER(UnipcStepArgs), vp],
-        "gdx_unipc_loop": [vp, C.POINTER(UnipcLoopArgs), vp],
-        "gdx_attention_f16": [vp, vp, i32, i32, i32, i32, vp],
-        "gdx_attention_half": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
-        "gdx_attention_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
-        "gdx_attention_f32_rows": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp],
-        "gdx_bench_gemm_f16": [i32, i32, i32, i32, i32, C.POINTER(C.c_float), vp],
-        "gdx_set_guards": [vp, i32],
-        "gdx_check_guards": [vp, C.POINTER(i64), C.POINTER(i32), vp],
-        "gdx_set_test_half_dtype": [i32],
-        "gdx_set_test_gemmh_tile": [i32, i32],
-        "gdx_packed_bytes": [vp, C.POINTER(i64)],
-        "gdx_export_packed": [vp, vp, i64, vp],
-        "gdx_import_packed": [vp, vp, i64, vp],
-        "gdx_bpd_terms": [C.POINTER(BpdArgs), vp],
-        "gdx_bpd_loop": [vp, C.POINTER(BpdLoopArgs), vp],
-        "gdx_set_guidance_interval": [vp, i64, i64],
-        "gdx_forward_samples": [vp, C.POINTER(i64)],
-        "gdx_set_guidance_rescale": [vp, C.c_float],
-        "gdx_cfg_rescale": [C.POINTER(CfgRescaleArgs), vp],
-        "gdx_set_guidance_refresh": [vp, i32],
-        "gdx_cfg_delta": [C.POINTER(CfgDeltaArgs), vp],
-        "gdx_profile_begin": [vp, i32],
-        "gdx_profile_end": [vp, C.POINTER(C.c_float), C.POINTER(i32)],
-    }
-    for name, args in sigs.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = i32
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib
 

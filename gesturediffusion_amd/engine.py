@@ -59,7 +59,7 @@ def f32c(t, what):
 
 # gdx.h GDX_DTYPE_*: "fp32" = exact fp32 MFMA everywhere (default); "fp16" / "bf16" = 16-bit GEMM / attention operands and
 # activation stream, fp32 accumulate (bf16: fp32's exponent range, 8 significant bits)
-COMPUTE_DTYPES = {"fp32": 0, "fp16": 1, "bf16": 2}
+COMPUTE_DTYPES = {"fp32": _lib.GDX_DTYPE_F32, "fp16": _lib.GDX_DTYPE_F16, "bf16": _lib.GDX_DTYPE_BF16}
 
 
 class Engine:

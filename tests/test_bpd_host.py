@@ -1,8 +1,6 @@
 """Host-side checks of the variational-bound feature (calc_bpd_loop, gdx_bpd_terms, gdx_bpd_loop): no GPU needed."""
 import ctypes as C
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -10,7 +8,7 @@ import pytest
 import torch
 
 import bpd_restatement as R
-from conftest import REPO, load_golden, weights_from
+from conftest import load_golden, weights_from
 
 TINY = dict(njoints=16, nfeats=1, latent_dim=128, ff_size=256, num_layers=2, num_heads=4, seed_poses=10)
 CASES = {  # fixture case -> (variance type, mean type, clip_denoised, cfg wrapper, inpainting)
@@ -110,30 +108,6 @@ def _lib_or_skip():
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("libgdx.so not built (run python __graft_entry__.py)")
     return _lib
-
-
-def test_bpd_symbols_declared_and_exported():
-    _lib = _lib_or_skip()
-    hdr = open(os.path.join(REPO, "include", "gdx.h")).read()
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    for name in ("gdx_bpd_terms", "gdx_bpd_loop"):
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
-        assert name in _lib.EXPORTS and f" T {name}\n" in syms, name
-    assert int(re.search(r"#define\s+GDX_BPD_CHUNK\s+(\d+)", hdr).group(1)) == _lib.GDX_BPD_CHUNK
-
-
-def test_bpd_ctypes_structs_match_header_sizes(tmp_path):
-    from gesturediffusion_amd import _lib
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include "gdx.h"\n'
-                   'int main(void) { printf("%zu %zu\\n", sizeof(gdx_bpd_args_t), sizeof(gdx_bpd_loop_args_t)); return 0; }\n')
-    exe = tmp_path / "probe"
-    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
-        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0), None)
-    assert cc, "no C compiler"
-    subprocess.run([cc, "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    a, b = (int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
-    assert (C.sizeof(_lib.BpdArgs), C.sizeof(_lib.BpdLoopArgs)) == (a, b)
 
 
 def test_bpd_entry_points_refuse_null_arguments_without_gpu():

@@ -2,8 +2,6 @@
 refusal, the ValueErrors of y['guidance_interval'], and the two C exports on a null handle."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ import torch
 
 from test_dpm_host import diffusion
 
-REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 T, F = True, False
 
 
@@ -126,15 +123,6 @@ def _lib_or_skip():
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("libgdx.so not built (run python __graft_entry__.py)")
     return _lib
-
-
-def test_symbols_declared_and_exported():
-    _lib = _lib_or_skip()
-    hdr = open(os.path.join(REPO, "include", "gdx.h")).read()
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    for name in ("gdx_set_guidance_interval", "gdx_forward_samples"):
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
-        assert name in _lib.EXPORTS and f" T {name}\n" in syms, name
 
 
 def test_null_handle_is_refused_without_a_hip_call():
