@@ -827,6 +827,40 @@ extern "C" int gdx_unipc_loop(gdx_handle_t h, const gdx_unipc_loop_args_t* a, vo
         false, a ? a->order + 1 : 0);
 }
 
+// ddim_reverse_sample_loop (DDIM inversion, gdx.h): multistep_loop's per-step pair -- denoise_guided on the pose-layout state, then
+// one fused launch (ddim_reverse_step_kernel, sampler.hip) with step_args -- over ASCENDING indices.  An ascending twin and not a
+// direction flag on multistep_loop: nothing else of that function applies here (no order, no history ring, no k_base, no second
+// call, no check_reuse), and its step range and CallSeq are both written for first_index counting down.  The
+// guidance refresh is off in the CallSeq, as in gdx_bpd_loop: the stored difference's numbering is defined for descending loops.
+extern "C" int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_steps, int32_t first_index, int32_t run_steps,
+                                     const float* coef, const int64_t* timestep_map, float* x, const float* scale,
+                                     const uint8_t* inpaint_mask, const float* inpaint_motion, int32_t clip_denoised, void* stream) {
+    const char* who = "gdx_ddim_reverse_loop";
+    const std::string w = std::string(who) + ": ";
+    if (!coef || !timestep_map || !x) return fail(w + "null argument");
+    if (check_mode(who, mode, scale)) return -1;
+    if (num_steps <= 0 || first_index < 0 || first_index >= num_steps || run_steps < 1 || run_steps > num_steps - first_index)
+        return fail(w + "bad step range");
+    if (inpaint_mask && !inpaint_motion) return fail(w + "mask without motion");
+    if (check_ready(h, who)) return -1;
+    if (h->B > 65535) return fail(w + "batch exceeds 65535");
+    if (h->guide_every > 1)
+        return fail(w + "the guidance refresh (gdx_set_guidance_refresh, every > 1) does not apply to the inversion: its numbering of "
+                        "guided calls is defined for descending loops; set every = 1");
+    hipStream_t s = (hipStream_t)stream;
+    if (build_step_tables(h, num_steps, timestep_map, s)) return -1;
+    const CallSeq q{mode, timestep_map, num_steps - 1, -1, false};
+    // the loop's operands under the names step_args reads
+    const struct { const float* coef; float* x; const uint8_t* inpaint_mask; const float* inpaint_motion; int32_t clip_denoised; }
+        a{coef, x, inpaint_mask, inpaint_motion, clip_denoised};
+    for (int idx = first_index; idx < first_index + run_steps; ++idx) {
+        const float *x0u, *sc;
+        if (denoise_guided(h, q, scale, x, idx, s, &x0u, &sc)) return -1;
+        if (gdx_ddim_reverse_step_(step_args<gdx::DdimReverseStepArgs>(h, &a, idx, x0u, sc), stream)) return -1;
+    }
+    return 0;
+}
+
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
     if (check_ready(h, "gdx_sample_loop")) return -1;
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");

@@ -215,6 +215,20 @@ struct UpdateTmDev {
     int mirror;             // an unguided step (scale == nullptr) of a guided loop: write the uncond half of xt / xt16 as well
 };
 
+// operands of gdx_ddim_reverse_step (gdx.h), under the field names every pose-layout step struct uses: what step_begin / step_src
+// (sampler.hip) and step_args (api.hip) read.  The public entry takes them as plain arguments and fills this.
+struct DdimReverseStepArgs {
+    int32_t batch, njoints, frames;
+    const float* coef;
+    const int64_t* t;
+    int32_t step_index;
+    const float *x, *x0_cond, *x0_uncond, *scale;
+    const uint8_t* inpaint_mask;
+    const float* inpaint_motion;
+    int32_t clip_denoised;
+    float *out, *pred_out, *eps_out;
+};
+
 }  // namespace gdx
 
 // the loops' (api.hip) private entries into sampler.hip; each returns 0, or -1 with the error recorded
@@ -222,6 +236,8 @@ struct UpdateTmDev {
 int gdx_sampler_update_state_(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
 // one step of the token-major fast path of gdx_sample_loop (update_tm_kernel); checks the layout arguments of `d`
 int gdx_sampler_update_tm_(const gdx::UpdateTmDev& d, void* stream);
+// gdx_ddim_reverse_step on its operands as a struct (gdx_ddim_reverse_loop builds them with step_args)
+int gdx_ddim_reverse_step_(const gdx::DdimReverseStepArgs& a, void* stream);
 // gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
 int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
                 uint32_t step, float* z_out, float* xt_out, void* stream);

@@ -530,6 +530,37 @@ __global__ __launch_bounds__(256) void unipc_step_kernel(const UnipcStepDev a) {
     store4<VEC>(a.s.out, e0, nval, r);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// One DDIM reverse-ODE (inversion) step in one pass (gdx.h gdx_ddim_reverse_step; reference :841-877): update_kernel's pred_xstart
+// (CFG blend -> inpainting -> clamp) as m0, eps_from_xstart on the row's c0 / c1 and ddim_mean on its reverse columns c2 / c3 =
+// sqrt(abar_next), sqrt(1 - abar_next).  No noise operand and no Philox draw: update_kernel with these rows and a zero tensor adds
+// 0*0 to the same mean.  Grid (ceil(groups / 256), B): blockIdx.y is the sample.  Memory-bound, one pass, no LDS, one 128-bit
+// access per stream and thread: per element 2 reads (3 under guidance, + mask and motion under inpainting) and 1..3 writes.
+struct DdimReverseDev {
+    StepSrc s;
+    float* eps_out;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ddim_reverse_step_kernel(const DdimReverseDev a) {
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    if (grp >= a.s.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.s.per_sample);
+    const float* c = a.s.coef + coef_row(a.s, g.b) * 8;
+
+    const f32x4 x = load4<VEC>(a.s.x, g.e0, g.nval);
+    const f32x4 m0 = pred_xstart4<VEC>(a.s, g);
+    f32x4 eps, r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        eps[i] = eps_from_xstart(c[0], c[1], x[i], m0[i]);
+        r[i] = ddim_mean(c[2], c[3], m0[i], eps[i]);
+    }
+    if (a.eps_out) store4<VEC>(a.eps_out, g.e0, g.nval, eps);
+    if (a.s.pred) store4<VEC>(a.s.pred, g.e0, g.nval, m0);
+    store4<VEC>(a.s.out, g.e0, g.nval, r);
+}
+
 // De-normalisation + position / rotation split of a generated chunk (reference sample/generate.py:132-146 with
 // data_loaders/gesture/data/dataset.py:118-119): feature 6j+c is rotation component c of joint j, 6j+3+c its position.
 //   pos[b][j][c][t] = x[b][6j+3+c][t] * std[6j+3+c] + mean[6j+3+c],  rot[b][j][c][t] likewise with feature 6j+c.
@@ -1155,6 +1186,36 @@ extern "C" int gdx_unipc_step(const gdx_unipc_step_args_t* a, void* stream) {
     if (vec_ok(d.s, d.h0, d.h1, d.h2, d.base_out)) launch_unipc_step<true>(a->corr_order, a->pred_order, grid, (hipStream_t)stream, d);
     else launch_unipc_step<false>(a->corr_order, a->pred_order, grid, (hipStream_t)stream, d);
     return launch_status("gdx_unipc_step: launch failed");
+}
+
+extern "C" int gdx_ddim_reverse_step(int32_t batch, int32_t njoints, int32_t frames, const float* coef, const int64_t* t,
+                                     int32_t step_index, const float* x, const float* x0_cond, const float* x0_uncond,
+                                     const float* scale, const uint8_t* inpaint_mask, const float* inpaint_motion,
+                                     int32_t clip_denoised, float* out, float* pred_out, float* eps_out, void* stream) {
+    return gdx_ddim_reverse_step_(gdx::DdimReverseStepArgs{batch, njoints, frames, coef, t, step_index, x, x0_cond, x0_uncond, scale,
+                                                           inpaint_mask, inpaint_motion, clip_denoised, out, pred_out, eps_out},
+                                  stream);
+}
+
+int gdx_ddim_reverse_step_(const gdx::DdimReverseStepArgs& args, void* stream) {
+    using namespace gdx;
+    const DdimReverseStepArgs* a = &args;
+    DdimReverseDev d = {};
+    dim3 grid;
+    const int rc = step_begin(
+        "gdx_ddim_reverse_step", a, &DdimReverseStepArgs::pred_out, [] { return (const char*)nullptr; },
+        [&]() -> const char* {
+            if ((a->pred_out && (a->pred_out == a->eps_out || a->pred_out == a->out)) || (a->eps_out && a->eps_out == a->out))
+                return "out, pred_out and eps_out must differ";
+            return nullptr;
+        },
+        d.s, grid);
+    if (rc) return rc < 0 ? -1 : 0;
+    d.eps_out = a->eps_out;
+    const dim3 block(256);
+    if (vec_ok(d.s, d.eps_out)) hipLaunchKernelGGL(ddim_reverse_step_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
+    else hipLaunchKernelGGL(ddim_reverse_step_kernel<false>, grid, block, 0, (hipStream_t)stream, d);
+    return launch_status("gdx_ddim_reverse_step: launch failed");
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,

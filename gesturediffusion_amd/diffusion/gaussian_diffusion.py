@@ -393,11 +393,82 @@ class GaussianDiffusion:
         return self._step(GDX_SAMPLER_DDIM, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta)
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
-        """Sample x_{t+1} with the DDIM reverse ODE (reference :841-877); the fused update kernel with the
-        next-alpha coefficient rows and zero noise weight."""
+        """Sample x_{t+1} with the DDIM reverse ODE (reference :841-877): one gdx_ddim_reverse_step launch on the next-alpha
+        coefficient rows, no noise operand.  A denoised_fn, or an EPSILON / PREVIOUS_X reading of the output, goes through the
+        general update kernel with those rows and a zero noise tensor (_step), which gives the same values."""
         assert eta == 0.0, "Reverse ODE only for deterministic path"
-        return self._step(GDX_SAMPLER_DDIM, model, x, t, clip_denoised, denoised_fn, None, model_kwargs, eta="reverse",
-                          noise=th.zeros_like(x))
+        if denoised_fn is not None or self.model_mean_type != ModelMeanType.START_X:
+            return self._step(GDX_SAMPLER_DDIM, model, x, t, clip_denoised, denoised_fn, None, model_kwargs, eta="reverse",
+                              noise=th.zeros_like(x))
+        if model_kwargs is None:
+            model_kwargs = {}
+        self._check_supported()
+        assert t.shape == (x.shape[0],)
+        model_output = self._call_model(model, x, t, model_kwargs)
+        y = model_kwargs["y"]                                             # KeyError like the reference (:307)
+        mask = motion = None
+        if "inpainting_mask" in y.keys() and "inpainted_motion" in y.keys():
+            mask, motion = y["inpainting_mask"], y["inpainted_motion"]
+            assert model_output.shape == mask.shape == motion.shape
+        x0 = E.f32c(model_output, "model output")
+        xc = E.f32c(x, "x")
+        assert x0.shape == x.shape
+        out, pred = th.empty_like(xc), th.empty_like(xc)
+        E.ddim_reverse_step(self.coef_table(GDX_SAMPLER_DDIM, x.device, "reverse"), xc, x0, out, t=t.to(th.int64).contiguous(),
+                            inpaint_mask=mask.contiguous() if mask is not None else None,
+                            inpaint_motion=E.f32c(motion, "inpainted_motion") if motion is not None else None,
+                            clip_denoised=clip_denoised, pred_out=pred)
+        return {"sample": out, "pred_xstart": pred}
+
+    def _inversion_steps(self, eta, until):
+        """The checks of the inversion loops -> the number of steps: indices 0 .. until - 1 are executed."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        if until is None:
+            until = self.num_timesteps - 1
+        if isinstance(until, bool) or not isinstance(until, (int, np.integer)) or not 1 <= until <= self.num_timesteps:
+            raise ValueError(f"until must be an int with 1 <= until <= num_timesteps = {self.num_timesteps}, got {until!r}")
+        return int(until)
+
+    def ddim_reverse_sample_loop(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None, device=None,
+                                 progress=False, eta=0.0, *, until=None, fused=True):
+        """DDIM inversion: x_start, read as the state at index 0 (abar_0, as ddim_reverse_sample reads it), is carried up the
+        deterministic DDIM ODE through the indices 0 .. until - 1 -> the state at index `until`.  The default until =
+        num_timesteps - 1 is the index whose state ddim_sample_loop(noise=...) takes as x_T; a state at index k is handed back
+        with ddim_sample_loop(noise=state, skip_timesteps=num_timesteps - 1 - k, init_is_state=True).  A native START_X denoiser
+        (or its ClassifierFreeSampleModel) without denoised_fn runs the whole loop inside libgdx (gdx_ddim_reverse_loop: one
+        forward and one fused launch per step); every other case, and fused=False, goes step by step through
+        ddim_reverse_sample.  Both give the same bits.  y['guidance_refresh'] > 1 is refused: the refresh is defined for the
+        sampling direction.  `device` is accepted for the sampling loops' signature; the state stays where x_start is."""
+        n = self._inversion_steps(eta, until)
+        self._refuse_refresh(model, model_kwargs, "ddim_reverse_sample_loop (the inversion runs its indices ascending; the "
+                                                  "refresh numbers guided calls of a descending loop)")
+        if not self._runs_fused(fused, model, denoised_fn, None):
+            return self._final_sample(self.ddim_reverse_sample_loop_progressive(
+                model, x_start, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs, device=device,
+                progress=progress, eta=eta, until=n))
+        x, eng, mode, scale, mask, motion = self._fused_setup(model, x_start, model_kwargs or {})
+        coef, tmap = self.coef_table(GDX_SAMPLER_DDIM, x.device, "reverse"), self._timestep_map()
+        self._issue_blocks(n, x.device, progress, lambda k, nb: eng.ddim_reverse_loop(
+            x, mode, coef, tmap, k, nb, scale=scale, inpaint_mask=mask, inpaint_motion=motion, clip_denoised=clip_denoised))
+        return x
+
+    def ddim_reverse_sample_loop_progressive(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                             device=None, progress=False, eta=0.0, *, until=None):
+        """The inversion step by step: yields ddim_reverse_sample's dict for each index 0 .. until - 1."""
+        n = self._inversion_steps(eta, until)
+        self._refuse_refresh(model, model_kwargs, "ddim_reverse_sample_loop_progressive")
+        indices = range(n)
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        img = x_start
+        for i in indices:
+            t = th.full((img.shape[0],), i, device=img.device, dtype=th.long)
+            with th.no_grad():
+                out = self.ddim_reverse_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                               model_kwargs=model_kwargs, eta=eta)
+            yield out
+            img = out["sample"]
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """Dict API of the reference (:277-388).  mean = update with zero noise; the variance
@@ -410,7 +481,9 @@ class GaussianDiffusion:
 
     # ------------------------------------------------------------------ loops
     def _prepare_loop(self, model, shape, noise, device, skip_timesteps, init_image, rng, philox_seed, sample_offset,
-                      noise_tape):
+                      noise_tape, init_is_state=False):
+        """init_is_state: `noise` is the state at the loop's first index itself (an inverted latent) and is used as it is -- no
+        q_sample, with or without skip_timesteps."""
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
@@ -422,7 +495,7 @@ class GaussianDiffusion:
             img = E.randn(tuple(shape), device, philox_seed, sample_offset, 0)
         else:
             img = th.randn(*shape, device=device)
-        if skip_timesteps and init_image is None:
+        if skip_timesteps and init_image is None and not init_is_state:
             init_image = th.zeros_like(img)
         indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
         if init_image is not None:
@@ -432,7 +505,7 @@ class GaussianDiffusion:
 
     def _loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
               eta, skip_timesteps, init_image, randomize_class, cond_fn_with_grad, const_noise, rng, philox_seed,
-              sample_offset, noise_tape, dump_steps=None, every_step=False):
+              sample_offset, noise_tape, dump_steps=None, every_step=False, init_is_state=False):
         """every_step: the caller consumes each step's dict (the *_progressive generators, or `fused=False`: the
         step-wise callable protocol model(x, t, **kw) + one gdx_sampler_update per step); otherwise only the final state
         is needed and the whole loop runs inside libgdx."""
@@ -441,7 +514,7 @@ class GaussianDiffusion:
         if rng not in ("torch", "philox"):
             raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
         device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng,
-                                                  philox_seed, sample_offset, noise_tape)
+                                                  philox_seed, sample_offset, noise_tape, init_is_state)
         fused = self._runs_fused(not every_step, model, denoised_fn, cond_fn)
         if fused:
             yield from self._fused_loop(kind, model, img, indices, model_kwargs, eta, const_noise, rng, philox_seed,
@@ -651,16 +724,23 @@ class GaussianDiffusion:
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
                          randomize_class=False, cond_fn_with_grad=False, dump_steps=None, const_noise=False,
-                         rng="torch", philox_seed=0, sample_offset=0, noise_tape=None, fused=True):
+                         rng="torch", philox_seed=0, sample_offset=0, noise_tape=None, fused=True, *, init_is_state=False):
+        """init_is_state=True: `noise` IS the state at index num_timesteps - 1 - skip_timesteps -- what
+        ddim_reverse_sample_loop(until=that index) returns -- and the loop starts from it as it is (no q_sample); init_image
+        must then be None.  False (the default): the reference's behaviour, bit for bit."""
         if dump_steps is not None:
             raise NotImplementedError()                                   # reference :903-904
         if const_noise == True:  # noqa: E712
             raise NotImplementedError()                                   # reference :905-906
+        if init_is_state and init_image is not None:
+            raise ValueError("init_is_state=True takes the start state from `noise` as it is: init_image must be None")
+        if init_is_state and noise is None:
+            raise ValueError("init_is_state=True needs the state in `noise`")
         final = None
         for sample in self._loop(GDX_SAMPLER_DDIM, model, shape, noise, clip_denoised, denoised_fn, cond_fn,
                                  model_kwargs, device, progress, eta, skip_timesteps, init_image, randomize_class,
                                  cond_fn_with_grad, False, rng, philox_seed, sample_offset, noise_tape,
-                                 every_step=not fused):
+                                 every_step=not fused, init_is_state=init_is_state):
             final = sample
         return final["sample"]
 

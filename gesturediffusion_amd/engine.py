@@ -278,6 +278,17 @@ class Engine:
                                coef_c=coef_c.data_ptr(), **kw)
         self._run_loop(self.lib.gdx_unipc_loop, a, x.device, tmap)
 
+    def ddim_reverse_loop(self, x, mode, coef, timestep_map, first_index, run_steps, scale=None, inpaint_mask=None,
+                          inpaint_motion=None, clip_denoised=False):
+        """gdx_ddim_reverse_loop: x (the state at index first_index) is updated in place to the state at first_index + run_steps;
+        the indices ascend, and nothing but x is carried from one block to the next."""
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, 0)
+        # plain arguments in gdx.h's order (this entry has no argument struct, and an ascending loop no k_base)
+        _lib.check(self.lib.gdx_ddim_reverse_loop(self.handle, mode, kw["num_steps"], first_index, kw["run_steps"], kw["coef"],
+                                                  kw["timestep_map"], x.data_ptr(), kw["scale"], kw["inpaint_mask"],
+                                                  kw["inpaint_motion"], kw["clip_denoised"], _stream(x.device)), self.lib)
+        self._keep_loop = (tmap,)
+
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
         _lib.check(self.lib.gdx_forward_flops(self.handle, mode, C.byref(f)), self.lib)
@@ -496,6 +507,19 @@ def unipc_step(corr_order, pred_order, coef, coef_c, x, x0_cond, out, base_out, 
     for i, m in enumerate(hist):
         a.hist[i] = _p(m)
     _lib.check(lib.gdx_unipc_step(C.byref(a), _stream(x0_cond.device)), lib)
+    return out
+
+
+def ddim_reverse_step(coef, x, x0_cond, out, t=None, step_index=0, x0_uncond=None, scale=None, inpaint_mask=None,
+                      inpaint_motion=None, clip_denoised=False, pred_out=None, eps_out=None):
+    """gdx_ddim_reverse_step: one DDIM reverse-ODE step x_i -> x_{i+1} in one pass (include/gdx.h); coef = the rows of
+    coef_table(GDX_SAMPLER_DDIM, device, "reverse").  out may be x; pred_out / eps_out receive the x0 prediction and eps."""
+    lib = _lib.load()
+    kw = _step_fields(x0_cond.shape, coef, t, step_index, x0_cond, x0_uncond, scale, inpaint_mask, inpaint_motion, clip_denoised)
+    # plain arguments in gdx.h's order (this entry has no argument struct)
+    _lib.check(lib.gdx_ddim_reverse_step(kw["batch"], kw["njoints"], kw["frames"], kw["coef"], kw["t"], kw["step_index"], x.data_ptr(),
+                                         kw["x0_cond"], kw["x0_uncond"], kw["scale"], kw["inpaint_mask"], kw["inpaint_motion"],
+                                         kw["clip_denoised"], out.data_ptr(), _p(pred_out), _p(eps_out), _stream(x0_cond.device)), lib)
     return out
 
 

@@ -14,6 +14,8 @@ MFCCs (computed on the GPU), text, lengths, raw audio and ground-truth motion co
 its statistics, and `results.npy` / `results.txt` / `results_len.txt` are written.  The BVH, MP4 and WAV files of
 `:218-301` are not: bvhsdk, ffmpeg and soundfile are not dependencies of this project, and what they would hold is in
 `results.npy`.  `--synthetic` needs no data: seed poses and MFCCs are N(0,1) and the tail's statistics are synthetic.
+`--invert_gt` (data directory and `--sampler ddim` only) starts every chunk's DDIM loop from the DDIM inversion of that chunk's
+ground truth instead of a drawn x_T (`sample_chunks`, `invert_of_chunk`).
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N ...`; the batch is
 sharded across ranks and gathered once at the end of every chunk (RCCL over xGMI).  Sharded runs draw their noise from
@@ -50,7 +52,7 @@ def resolve_rng(rng, world):
 def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames, seed_poses, guidance_param=1.0,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
-                  guidance_refresh=1, unipc_order=2):
+                  guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -61,7 +63,15 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     guidance_interval (lo, hi): guidance only on model timesteps lo <= t <= hi (y['guidance_interval']; needs
     guidance_param != 1).  guidance_rescale phi > 0: the guidance rescale (y['guidance_rescale']; needs guidance_param != 1).
     guidance_refresh k > 1: the unconditional pass on every k-th guided denoiser call, the stored cond-uncond difference in
-    between (y['guidance_refresh']; needs guidance_param != 1); each chunk is its own loop and starts with a refresh."""
+    between (y['guidance_refresh']; needs guidance_param != 1); each chunk is its own loop and starts with a refresh.
+    invert_of_chunk(c) -> recorded motion [b, J, 1, frames] in the sampler's normalised units ("ddim" only): chunk c's x_T is not
+    drawn but is that motion's DDIM inversion (ddim_reverse_sample_loop) under the chunk's own seed poses and MFCCs, with the
+    conditional pass alone -- no guidance, whatever guidance_param says; the (guided) DDIM loop then starts from it.  With
+    guidance_param == 1 the loop retraces the inversion, and report(text) is told each chunk's round-trip error."""
+    if invert_of_chunk is not None and sampler != "ddim":
+        raise ValueError("invert_of_chunk needs sampler='ddim': the latent is the start state of the deterministic DDIM loop")
+    if invert_of_chunk is not None and guidance_refresh > 1:
+        raise ValueError("invert_of_chunk runs no guidance refresh")
     if guidance_interval is not None and guidance_param == 1:
         raise ValueError("guidance_interval needs guidance_param != 1: without guidance there is nothing to limit")
     if guidance_rescale > 0 and guidance_param == 1:
@@ -100,7 +110,16 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
                       noise=tape[0] if tape is not None else None)
         if on_chunk is not None:
             on_chunk(chunk)
+        gt = None
+        if invert_of_chunk is not None:
+            gt = invert_of_chunk(chunk)
+            inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
+            kw["noise"] = diffusion.ddim_reverse_sample_loop(inner, gt, clip_denoised=False, progress=progress,
+                                                             model_kwargs={"y": {"mfcc": y["mfcc"], "seed": y["seed"]}})
         sample_out = sample_fn(model, (b, J, 1, frames), **kw)
+        if gt is not None and guidance_param == 1 and report is not None:
+            err = float((sample_out - gt).abs().max() / gt.abs().max())
+            report(f"### chunk {chunk + 1}: round trip max|regenerated - gt| / max|gt| = {err:.3e}")
         outs.append(sample_out)
     return outs
 
@@ -218,6 +237,14 @@ def main(argv=None):
         if rank == 0:
             print(f"### Sampling chunk {chunk + 1} of {args.chunks}")
 
+    invert_of_chunk = None
+    if args.invert_gt:
+        def invert_of_chunk(chunk):        # this rank's ground-truth chunks, normalised, as the sampler's [b, J, 1, T]
+            return gg_collate([host_item(ds, i) for i in index[chunk][lo:hi]])[0].float().to(device)
+
+    def report(text):
+        print(text if world == 1 else f"{text} (rank {rank})")
+
     interval = tuple(args.guidance_interval) if args.guidance_interval is not None else None
     if interval is not None and rank == 0:
         flags = diffusion.guided_steps(interval)
@@ -233,7 +260,7 @@ def main(argv=None):
                          philox_seed=args.seed, sample_offset=lo, progress=args.progress and rank == 0, on_chunk=on_chunk,
                          plms_order=args.plms_order, dpm_order=args.dpm_order, unipc_order=args.unipc_order,
                          guidance_interval=interval, guidance_rescale=args.guidance_rescale,
-                         guidance_refresh=args.guidance_refresh)
+                         guidance_refresh=args.guidance_refresh, invert_of_chunk=invert_of_chunk, report=report)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

@@ -56,6 +56,13 @@ def parse_and_load_from_model(parser, argv=None):
         parser.error("--guidance_refresh needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     if args.guidance_refresh is None:
         args.guidance_refresh = 1
+    if args.invert_gt:
+        if args.synthetic or args.dataset != "genea2023" or not args.data_dir:
+            parser.error("--invert_gt inverts recorded motion: it needs --dataset genea2023 --data_dir D (and no --synthetic)")
+        if args.sampler != "ddim":
+            parser.error("--invert_gt needs --sampler ddim: the latent is the start state of the deterministic DDIM loop")
+        if args.guidance_refresh > 1:
+            parser.error("--invert_gt runs no guidance refresh: the inversion is one conditional pass per step")
     return args
 
 
@@ -167,6 +174,12 @@ def add_native_options(parser):
                        help="Guidance refresh: run the unconditional pass only on every K-th guided denoiser call of a chunk's "
                             "loop and reuse the stored cond-uncond difference in between (1 = every call, the default). "
                             "Every sampler; an error with --guidance_param 1 or K < 1.")
+    group.add_argument("--invert_gt", action='store_true',
+                       help="DDIM inversion of the data: each ground-truth chunk is carried up the deterministic DDIM ODE under "
+                            "that chunk's conditioning with the conditional pass only (no guidance: the standard practice "
+                            "for inversion), and the latent replaces the drawn x_T of the (guided) DDIM loop. "
+                            "Needs --dataset genea2023 --data_dir D and --sampler ddim; with --guidance_param 1 the per-chunk "
+                            "round-trip error max|regenerated - gt| / max|gt| is printed.")
     group.add_argument("--rng", default=None, choices=['torch', 'philox'],
                        help="torch = the reference's generator and draw order (single-GPU default); philox = in-kernel "
                             "counter-based noise keyed by the global sample index (shard invariant; multi-GPU default).")

@@ -488,6 +488,36 @@ typedef struct {
 } gdx_unipc_step_args_t;
 int gdx_unipc_step(const gdx_unipc_step_args_t* a, void* stream);
 
+/* One DDIM reverse-ODE (inversion) step x_i -> x_{i+1} over [B,J,1,T] in ONE pass (ddim_reverse_sample, gaussian_diffusion.py:841-877):
+ * the deterministic DDIM step run towards MORE noise.  There is no noise operand and no random draw.  The operands are those of
+ * the step structs above under the same names; this entry and gdx_ddim_reverse_loop take theirs as plain arguments, like
+ * gdx_q_sample_t and gdx_mfcc (the set of argument structs of this header is kept as it is).
+ *   batch, njoints, frames   the shape [B,J,1,T]
+ *   coef                     device [num_steps][8] fp32 rows in the DDIM layout of gdx_sampler_update with the reverse rows of
+ *                            coef_table(GDX_SAMPLER_DDIM, "reverse"): c0 = sqrt_recip_alphas_cumprod, c1 = sqrt_recipm1_alphas_cumprod,
+ *                            c2 = sqrt(abar_next), c3 = sqrt(1 - abar_next), abar_next = alphas_cumprod_next[i] (0 behind the last
+ *                            index: the step at num_steps - 1 returns eps)
+ *   t, step_index            [B] or NULL; step_index is used when t == NULL
+ *   x                        x_i
+ *   x0_cond, x0_uncond, scale   model output (cond pass); NULL or the uncond pass; [B] when x0_uncond != NULL
+ *   inpaint_mask, inpaint_motion   NULL or bool bytes [B,J,1,T]; [B,J,1,T] when mask != NULL
+ *   clip_denoised
+ *   out                      x_{i+1}; may alias x
+ *   pred_out, eps_out        NULL or [B,J,1,T]: m0 and eps; they must differ from each other and from out
+ * Per element, row c = coef[idx], idx = t[b] if t != NULL else step_index, every product / sum / quotient rounded separately in
+ * the reference's op order:
+ *   m0  = x0_cond -> CFG blend u + scale*(c - u) -> inpainting blend -> clamp, exactly as in gdx_sampler_update
+ *   eps = (c0*x - m0) / c1
+ *   out = m0*c2 + c3*eps
+ * These are the bits of gdx_sampler_update with those rows and a zero noise tensor, up to the sign of a zero (that path adds
+ * 0*0 last).  128-bit accesses when J*T % 4 == 0 and every pointer is 16-byte aligned (the mask 4-byte), a scalar path
+ * otherwise; nothing is written past the tensor.  batch <= 65535 (the grid's second dimension is the sample).  Refusals come
+ * before the first HIP call. */
+int gdx_ddim_reverse_step(int32_t batch, int32_t njoints, int32_t frames, const float* coef, const int64_t* t, int32_t step_index,
+                          const float* x, const float* x0_cond, const float* x0_uncond, const float* scale,
+                          const uint8_t* inpaint_mask, const float* inpaint_motion, int32_t clip_denoised, float* out,
+                          float* pred_out, float* eps_out, void* stream);
+
 /* q_sample (gaussian_diffusion.py:233-251): out = a*x_start + b*noise, a/b per-sample from
  * coef rows (c[5], c[6]) at idx. */
 int gdx_q_sample(const float* x_start, const float* noise, const float* coef, int32_t idx,
@@ -757,6 +787,30 @@ typedef struct {
     const float* coef_c;       /* device [num_steps][16], corrector rows of gdx_unipc_step */
 } gdx_unipc_loop_args_t;
 int gdx_unipc_loop(gdx_handle_t h, const gdx_unipc_loop_args_t* a, void* stream);
+
+/* DDIM inversion loop (ddim_reverse_sample_loop; the update and its rows are at gdx_ddim_reverse_step) for a START_X denoiser
+ * without denoised_fn: the one loop that runs its indices ASCENDING.  It executes idx = first_index, first_index + 1, ...,
+ * first_index + run_steps - 1: per step one denoiser call on x at model timestep timestep_map[idx], through the same forward
+ * entry gdx_forward uses (so the loop has the bits of the step-wise protocol), and ONE gdx_ddim_reverse_step launch in place,
+ * all enqueued on `stream` with no host synchronisation.  x holds the state at index first_index on entry (a whole inversion:
+ * first_index = 0, the data itself, read as the state at abar_0 like the reference's method) and the state at index
+ * first_index + run_steps on return; a loop issued in blocks gives the bits of one call, and carries nothing but x between calls.
+ * The guidance interval and the guidance rescale apply per step as in every other loop (an unguided step of a GDX_CFG loop runs B
+ * samples).  The guidance refresh does not: its numbering of guided calls is defined for descending loops, so a handle with
+ * gdx_set_guidance_refresh's every > 1 is refused.  There is neither graph replay nor a token-major variant of this loop.
+ * Argument checks come first, then the null handle, then readiness: every refusal precedes the first HIP call.
+ *   mode                     GDX_COND / GDX_UNCOND / GDX_CFG
+ *   num_steps                rows of coef / timestep_map
+ *   first_index, run_steps   index of the first step this call executes (0 for a whole inversion); run_steps >= 1,
+ *                            first_index + run_steps <= num_steps
+ *   coef                     device [num_steps][8], reverse rows of gdx_ddim_reverse_step
+ *   timestep_map             HOST [num_steps]
+ *   x                        in: the state at first_index, out: the state at first_index + run_steps
+ *   scale                    [B] for GDX_CFG
+ *   inpaint_mask, inpaint_motion, clip_denoised   as in the other loops */
+int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_steps, int32_t first_index, int32_t run_steps,
+                          const float* coef, const int64_t* timestep_map, float* x, const float* scale,
+                          const uint8_t* inpaint_mask, const float* inpaint_motion, int32_t clip_denoised, void* stream);
 
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  A call whose
