@@ -56,6 +56,13 @@ extern "C" int gdx_create(const gdx_config_t* cfg, gdx_handle_t* out) {
             return fail("gdx_create: latent_dim / cl_head must be an even integer");
         if (cfg->window <= 0 || cfg->window > 16) return fail("gdx_create: window must be in 1..16");
     }
+    // use_text (model/mdm.py:36-50): 0, 0 = no text
+    if (cfg->text_dim < 0) return fail("gdx_create: text_dim must not be negative");
+    if (cfg->text_dim > 0 && cfg->arch == GDX_ARCH_MDM_OLD) return fail("gdx_create: text_dim > 0 needs GDX_ARCH_MDM (MDM_Old has no text path)");
+    if (cfg->text_dim >= cfg->latent_dim)
+        return fail("gdx_create: text_dim must be smaller than latent_dim (the seed-pose encoder gets latent_dim - text_dim rows)");
+    if (cfg->text_dim > 0 && cfg->clip_dim <= 0) return fail("gdx_create: text_dim > 0 needs clip_dim > 0");
+    if (cfg->text_dim == 0 && cfg->clip_dim != 0) return fail("gdx_create: clip_dim without text_dim (0, 0 means no text)");
     hipError_t e = gemm_init();
     if (e != hipSuccess) return fail(std::string("gemm_init: ") + hipGetErrorString(e));
     gdx_model* h = new gdx_model();
@@ -214,18 +221,9 @@ extern "C" int gdx_get_tap(gdx_handle_t h, int32_t which, float* out, int64_t co
     return 0;
 }
 
-extern "C" int gdx_set_condition(gdx_handle_t h, const float* seed, const float* mfcc, void* stream) {
-    if (!h || !seed || !mfcc) return fail("gdx_set_condition: null argument");
-    if (gdx_weights_ready(h)) return -1;
-    if (!h->B) return fail("gdx_set_condition: call gdx_prepare first");
-    hipStream_t s = (hipStream_t)stream;
+// what a conditioning does once seed_cat holds its 2B rows: the audio term, the seed half of the coarse slice, the flags
+static int finish_condition(gdx_model* h, const float* mfcc, hipStream_t s) {
     const int B = h->B, T = h->T, S = h->S, d = h->d;
-    // cond rows 0..B-1: Linear(flat seed); uncond rows B..2B-1: Linear(0) = bias   (model/mdm.py:125-127,242-250)
-    HIPCHK(launch_small_linear(seed, h->J * h->cfg.seed_poses, h->seed.w, h->seed.kpad, h->seed.bias, h->seed_cat, d, B,
-                               d, h->J * h->cfg.seed_poses, 0, s));
-    for (int b = 0; b < B; ++b)
-        HIPCHK(hipMemcpyAsync(h->seed_cat + (size_t)(B + b) * d, h->seed.bias, sizeof(float) * d,
-                              hipMemcpyDeviceToDevice, s));
     if (h->cfg.arch == GDX_ARCH_MDM_OLD) {
         // addend[b, t+1, :] = W_in[:, J:] mfcc[b,:,t] + b_in + pe[t+1]      (model/mdm_old.py:104-112)
         HIPCHK(launch_mfcc_project(mfcc, h->in_mfcc.w, h->in_mfcc.kpad, h->in_x.bias, h->pe, h->addend, 2 * B, B,
@@ -240,6 +238,40 @@ extern "C" int gdx_set_condition(gdx_handle_t h, const float* seed, const float*
     h->cond_set = true;
     h->gd_valid = false;                                          // guidance refresh: the difference of another conditioning
     return 0;
+}
+
+extern "C" int gdx_set_condition(gdx_handle_t h, const float* seed, const float* mfcc, void* stream) {
+    if (!h || !seed || !mfcc) return fail("gdx_set_condition: null argument");
+    if (h->cfg.text_dim > 0) return fail("gdx_set_condition: this handle has text_dim > 0: call gdx_set_condition_text");
+    if (gdx_weights_ready(h)) return -1;
+    if (!h->B) return fail("gdx_set_condition: call gdx_prepare first");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B, d = h->d;
+    // cond rows 0..B-1: Linear(flat seed); uncond rows B..2B-1: Linear(0) = bias   (model/mdm.py:125-127,242-250)
+    HIPCHK(launch_small_linear(seed, h->J * h->cfg.seed_poses, h->seed.w, h->seed.kpad, h->seed.bias, h->seed_cat, d, B,
+                               d, h->J * h->cfg.seed_poses, 0, s));
+    for (int b = 0; b < B; ++b)
+        HIPCHK(hipMemcpyAsync(h->seed_cat + (size_t)(B + b) * d, h->seed.bias, sizeof(float) * d,
+                              hipMemcpyDeviceToDevice, s));
+    return finish_condition(h, mfcc, s);
+}
+
+extern "C" int gdx_set_condition_text(gdx_handle_t h, const float* seed, const float* mfcc, const float* text, void* stream) {
+    if (!h || !seed || !mfcc || !text) return fail("gdx_set_condition_text: null argument");
+    if (h->cfg.text_dim <= 0) return fail("gdx_set_condition_text: this handle has no text (text_dim = 0): call gdx_set_condition");
+    if (gdx_weights_ready(h)) return -1;
+    if (!h->B) return fail("gdx_set_condition_text: call gdx_prepare first");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B, d = h->d, td = h->cfg.text_dim, cd = h->cfg.clip_dim, ks = h->J * h->cfg.seed_poses;
+    // row b = [embed_text(text_b) | seed_embed(seed_b)]: two Linears into one row of stride d   (model/mdm.py:118-127,154-155)
+    HIPCHK(launch_small_linear(text, cd, h->text.w, h->text.kpad, h->text.bias, h->seed_cat, d, B, td, cd, 0, s));
+    HIPCHK(launch_small_linear(seed, ks, h->seed.w, h->seed.kpad, h->seed.bias, h->seed_cat + td, d, B, d - td, ks, 0, s));
+    // uncond rows B..2B-1: both inputs zeroed before their Linear = [embed_text.bias | seed_embed.bias]: the same launches over
+    // no input column (K = 0)
+    float* un = h->seed_cat + (size_t)B * d;
+    HIPCHK(launch_small_linear(text, cd, h->text.w, h->text.kpad, h->text.bias, un, d, B, td, 0, 0, s));
+    HIPCHK(launch_small_linear(seed, ks, h->seed.w, h->seed.kpad, h->seed.bias, un + td, d, B, d - td, 0, 0, s));
+    return finish_condition(h, mfcc, s);
 }
 
 // ctl (test / bench entry points only): a forced file or tile, the stamp buffer and the report of what ran (gdx_internal.h)

@@ -119,6 +119,7 @@ struct gdx_model {
     std::vector<void*> allocs;        // weight allocations
     std::vector<void*> ws_allocs;     // workspace allocations
     gdx::Packed time0, time2, seed, in_x, in_mfcc, proj_pose, proj_audio, proj_coa, outp;
+    gdx::Packed text;                 // cfg.text_dim > 0: embed_text [text_dim][clip_dim]; `seed` then has d - text_dim rows
     std::vector<gdx::Layer> layers;
     float* pe = nullptr; int pe_rows = 0;
     float *rope_cos = nullptr, *rope_sin = nullptr; int rope_rows = 0;

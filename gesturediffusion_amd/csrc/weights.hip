@@ -102,8 +102,15 @@ void describe_weights(gdx_model* h) {
     const std::string te = "embed_timestep.time_embed.", in = "input_process.poseEmbedding.";
     linear(te + "0.weight", te + "0.bias", d, d, {{&h->time0, 0, d}});
     linear(te + "2.weight", te + "2.bias", d, d, {{&h->time2, 0, d}});
-    linear("seed_pose_encoder.seed_embed.weight", "seed_pose_encoder.seed_embed.bias", d, J * h->cfg.seed_poses,
+    // use_text (model/mdm.py:36-50): embed_text fills the first text_dim columns of the coarse condition, the seed encoder the rest
+    const int td = h->cfg.text_dim;
+    linear("seed_pose_encoder.seed_embed.weight", "seed_pose_encoder.seed_embed.bias", d - td, J * h->cfg.seed_poses,
            {{&h->seed, 0, J * h->cfg.seed_poses}});
+    if (td > 0) {
+        group = 2;
+        linear("embed_text.weight", "embed_text.bias", td, h->cfg.clip_dim, {{&h->text, 0, h->cfg.clip_dim}});
+        group = 0;
+    }
     if (v2) {
         linear(in + "weight", in + "bias", d, J, {{&h->in_x, 0, J}});
         group = 2;   // project_to_lat reads [pose embedding | mfcc | timestep + seed embedding]
@@ -204,7 +211,10 @@ extern "C" int gdx_weights_ready(gdx_handle_t h) {
 // bias vectors, LayerNorm vectors, the positional / rotary tables -- as ONE host blob: a header (magic, the gdx_config_t
 // it was built for, record count) and one {id, dims, byte count, bytes} record per device buffer in a fixed walk order.
 // A blob only loads into a handle created with the same configuration; its records are checked against the sizes the
-// handle computes itself, so a stale or foreign file is rejected instead of producing a wrong model.
+// handle computes itself, so a stale or foreign file is rejected instead of producing a wrong model.  The magic stays
+// "GDXPACK3" although gdx_config_t grew by text_dim / clip_dim: an image with the shorter header has its (positive) record
+// count where text_dim is read and half its checksum where clip_dim is, so the configuration compare refuses it (always for a
+// handle without text; a text handle whose two fields happened to match still fails the record and checksum checks behind).
 namespace {
 struct PackRec { int32_t id, n, k, npad, kpad, npad16, kpad16, pad; int64_t bytes; };
 struct PackHdr { char magic[8]; gdx_config_t cfg; int32_t nrec, pad; };

@@ -540,7 +540,8 @@ class GaussianDiffusion:
 
     def _native_loop_setup(self, model, x, model_kwargs):
         """What every in-library loop does once in front: input checks, the engine prepared for x's shape and conditioned on
-        y['seed'] / y['mfcc'], and the loop's operands -> (engine, mode, scale, inpainting mask, inpainted motion)."""
+        y['seed'] / y['mfcc'] (and, for a use_text model, on the text features: MDM._text_features), and the loop's operands
+        -> (engine, mode, scale, inpainting mask, inpainted motion)."""
         from ..model.cfg_sampler import ClassifierFreeSampleModel
         y = model_kwargs["y"]
         inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
@@ -555,7 +556,7 @@ class GaussianDiffusion:
         every = E.guidance_refresh_of(y, guided)
         eng = inner._get_engine(x.device)
         eng.prepare(B, T)
-        eng.set_condition(y["seed"], y["mfcc"], cache=False)
+        eng.set_condition(y["seed"], y["mfcc"], text=inner._text_features(y, B), cache=False)
         eng.set_guidance_interval(interval)          # at every loop; None resets a reused handle to "every timestep"
         eng.set_guidance_rescale(phi)                # likewise: an absent key sets 0 (off)
         eng.set_guidance_refresh(every)              # likewise: an absent key sets 1 (off); every loop starts with a refresh

@@ -62,18 +62,30 @@ def f32c(t, what):
 COMPUTE_DTYPES = {"fp32": _lib.GDX_DTYPE_F32, "fp16": _lib.GDX_DTYPE_F16, "bf16": _lib.GDX_DTYPE_BF16}
 
 
+def check_condition_entry(text_dim, have_text):
+    """The refusals of the two conditioning entries (gdx.h), made before anything touches the device: a handle with text_dim > 0
+    is conditioned by gdx_set_condition_text, one without by gdx_set_condition."""
+    if text_dim > 0 and not have_text:
+        raise GdxError("gdx_set_condition: this handle has text_dim > 0: call gdx_set_condition_text "
+                       "(Engine.set_condition(seed, mfcc, text=...))")
+    if text_dim <= 0 and have_text:
+        raise GdxError("gdx_set_condition_text: this handle has no text (text_dim = 0): call gdx_set_condition "
+                       "(Engine.set_condition(seed, mfcc))")
+
+
 class Engine:
     """One libgdx handle = one model instance on one device/stream."""
 
     def __init__(self, arch, njoints, latent_dim, ff_size, num_layers, num_heads, seed_poses, cl_head=8, window=10,
-                 compute_dtype="fp32"):
+                 compute_dtype="fp32", text_dim=0, clip_dim=0):
         self.lib = _lib.load()
         if compute_dtype not in COMPUTE_DTYPES:
             raise ValueError(f"compute_dtype must be one of {sorted(COMPUTE_DTYPES)}, got {compute_dtype!r}")
         self.compute_dtype = compute_dtype
         self.cfg = _lib.Config(arch=arch, njoints=njoints, latent_dim=latent_dim, ff_size=ff_size,
                                num_layers=num_layers, num_heads=num_heads, seed_poses=seed_poses, mfcc_dim=MFCC_DIM,
-                               cl_head=cl_head, window=window, compute_dtype=COMPUTE_DTYPES[compute_dtype])
+                               cl_head=cl_head, window=window, compute_dtype=COMPUTE_DTYPES[compute_dtype],
+                               text_dim=text_dim, clip_dim=clip_dim)
         self.handle = C.c_void_p()
         _lib.check(self.lib.gdx_create(C.byref(self.cfg), C.byref(self.handle)), self.lib)
         self.device = None
@@ -132,20 +144,32 @@ class Engine:
             self.shape = (batch, frames)
             self._cond_key = None
 
-    def set_condition(self, seed, mfcc, cache=True):
-        """seed [B,J,1,P], mfcc [B,26,1,T].  The step-wise callable protocol model(x, t, y=...) calls this on every
+    def set_condition(self, seed, mfcc, text=None, cache=True):
+        """seed [B,J,1,P], mfcc [B,26,1,T], and for a handle with text_dim > 0 text [B, clip_dim] (gdx_set_condition_text).
+        The step-wise callable protocol model(x, t, y=...) calls this on every
         step, so the step-invariant work is skipped when the SAME tensors come back: the key is (storage pointer,
-        version counter, shape, strides) and the engine keeps references to the caller's own tensors while the key is
-        live -- their storage can therefore not be freed and handed to a different tensor with an equal key (a view
+        version counter, shape, strides, dtype) of each and the engine keeps references to the caller's own tensors while the
+        key is live -- their storage can therefore not be freed and handed to a different tensor with an equal key (a view
         such as sample_out[..., -seed_poses:] shares its base's storage and version counter).  `cache=False` (the
         fused loop: one call per 1000 steps) always recomputes."""
-        key = tuple((t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype) for t in (seed, mfcc))
+        check_condition_entry(self.cfg.text_dim, text is not None)
+        given = (seed, mfcc) if text is None else (seed, mfcc, text)
+        key = tuple((t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype) for t in given)
         if cache and key == self._cond_key:
             return
         seed_c, mfcc_c = f32c(seed, "y['seed']"), f32c(mfcc, "y['mfcc']")
-        _lib.check(self.lib.gdx_set_condition(self.handle, _ptr(seed_c), _ptr(mfcc_c), _stream(seed_c.device)),
-                   self.lib)
-        self._keep = [seed, mfcc, seed_c, mfcc_c]
+        if text is None:
+            _lib.check(self.lib.gdx_set_condition(self.handle, _ptr(seed_c), _ptr(mfcc_c), _stream(seed_c.device)),
+                       self.lib)
+            self._keep = [seed, mfcc, seed_c, mfcc_c]
+        else:
+            text_c = f32c(text, "y['text_embed']")
+            if tuple(text_c.shape) != (seed_c.shape[0], self.cfg.clip_dim):
+                raise ValueError(f"y['text_embed'] must be [batch, clip_dim] = [{seed_c.shape[0]}, {self.cfg.clip_dim}], "
+                                 f"got {list(text_c.shape)}")
+            _lib.check(self.lib.gdx_set_condition_text(self.handle, _ptr(seed_c), _ptr(mfcc_c), _ptr(text_c),
+                                                       _stream(seed_c.device)), self.lib)
+            self._keep = [seed, mfcc, text, seed_c, mfcc_c, text_c]
         self._cond_key = key if cache else None
 
     def set_guidance_interval(self, interval=None):

@@ -52,7 +52,7 @@ class ClassifierFreeSampleModel(nn.Module):
         refuse_guidance_refresh(y, True, "the step-wise forward of ClassifierFreeSampleModel")
         eng = m._get_engine(x.device)
         eng.prepare(bs, nframes)
-        eng.set_condition(seed, mfcc)
+        eng.set_condition(seed, mfcc, text=m._text_features(y, bs))
         # per-sample choice in the blend kernel: guided where lo <= timesteps[b] <= hi, else the conditional output; set on
         # every call (None: every timestep), so a handle never keeps the interval of an earlier call
         eng.set_guidance_interval(interval)

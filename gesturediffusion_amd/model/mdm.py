@@ -14,7 +14,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..engine import GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_interval_of, guidance_rescale_of
+from ..engine import (GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_interval_of, guidance_rescale_of,
+                      require_device)
 from .rotation2xyz import Rotation2xyz
 
 ROPE_ROWS = 4096
@@ -153,13 +154,14 @@ class _NativeDenoiser(nn.Module):
     def _engine_tensors(self):
         named = {k: v for k, v in self.named_parameters()
                  if not k.startswith("clip_model.") and not k.startswith("wav_encoder.") and "velEmbedding" not in k
-                 and "velFinal" not in k and not k.startswith("embed_text.")}
+                 and "velFinal" not in k and (self._text_dims()[0] > 0 or not k.startswith("embed_text."))}
         named["sequence_pos_encoder.pe"] = self.sequence_pos_encoder.pe
         return named
 
     def _new_engine(self, dtype):
         eng = Engine(self._arch, self.input_feats, self.latent_dim, self.ff_size, self.num_layers, self.num_heads,
-                     self.seed_poses, cl_head=getattr(self, "cl_head", 8), window=10, compute_dtype=dtype)
+                     self.seed_poses, cl_head=getattr(self, "cl_head", 8), window=10, compute_dtype=dtype,
+                     text_dim=self._text_dims()[0], clip_dim=self._text_dims()[1])
         self.__dict__["_eng"] = eng
         self.__dict__["_eng_key"] = None
         return eng
@@ -196,6 +198,40 @@ class _NativeDenoiser(nn.Module):
 
     def _extra_engine_tensors(self, device):
         return {}
+
+    def _text_dims(self):
+        """(text_dim, clip_dim) of the engine: (0, 0) unless the model was built with use_text (MDM only)."""
+        return (self.text_dim, self.clip_dim) if getattr(self, "use_text", False) and self._arch == GDX_ARCH_MDM else (0, 0)
+
+    def set_text_encoder(self, fn):
+        """Install the caller's text tower: fn(list of B strings) -> floating device tensor [B, clip_dim], what the reference's
+        `clip_model.encode_text(clip.tokenize(texts, truncate=True)).float()` returns (model/mdm.py:252-267).  None removes it."""
+        if fn is not None and not callable(fn):
+            raise TypeError("set_text_encoder takes a callable (list of strings -> [B, clip_dim] tensor) or None")
+        self.__dict__["text_encoder"] = fn
+
+    def _text_features(self, y, bs):
+        """The text condition of a call: None for a model without text, else [bs, clip_dim] from y['text_embed'], or from
+        y['text'] through the installed text encoder.  A host tensor is refused like y['seed'] is (GdxError: no CPU fallback)."""
+        if self._text_dims()[0] <= 0:
+            return None
+        if "text_embed" in y:
+            feats = y["text_embed"]
+        elif "text" not in y:
+            raise KeyError("text")                         # the reference reads y['text'] (model/mdm.py:120)
+        elif self.__dict__.get("text_encoder") is None:
+            raise NotImplementedError("use_text: this build has no CLIP text tower; pass the features as y['text_embed'] "
+                                      "([batch, clip_dim], the output of clip_model.encode_text(...).float()) or install "
+                                      "an encoder for y['text'] with model.set_text_encoder(fn)")
+        else:
+            feats = self.text_encoder(list(y["text"]))
+        if not isinstance(feats, torch.Tensor):
+            raise TypeError("y['text_embed'] must be a torch.Tensor")
+        if not feats.is_floating_point():
+            raise ValueError(f"y['text_embed'] must be a floating tensor, got {feats.dtype}")
+        if tuple(feats.shape) != (bs, self.clip_dim):
+            raise ValueError(f"y['text_embed'] must be [batch, clip_dim] = [{bs}, {self.clip_dim}], got {list(feats.shape)}")
+        return require_device(feats, "y['text_embed']")
 
     # ---- packed-weight image (include/gdx.h, gdx_export_packed / gdx_import_packed; SURVEY 8f N2)
     def export_packed(self, device):
@@ -268,12 +304,21 @@ class MDM(_NativeDenoiser):
         self.cond_mask_prob = kargs.get("cond_mask_prob", 0.0)
         self.text_dim, self.clip_dim = text_dim, clip_dim
         if self.use_text:
-            raise NotImplementedError("use_text needs CLIP weights (network download); not available")
+            # embed_text and the narrower seed encoder are all a checkpoint holds of the text path (the reference's trainer strips
+            # clip_model.*, train/training_loop.py:269-272): no CLIP is loaded and there is no `clip_model` attribute; the
+            # features come in through y['text_embed'] or set_text_encoder
+            if not 0 < text_dim < latent_dim:
+                raise NotImplementedError(f"use_text needs 0 < text_dim < latent_dim, got text_dim {text_dim} at latent_dim "
+                                          f"{latent_dim} (the reference would build a seed encoder without outputs)")
+            if clip_dim <= 0:
+                raise ValueError("use_text needs clip_dim > 0")
+            self.embed_text = nn.Linear(clip_dim, text_dim)
+            self.clip_version = clip_version
 
         self.seed_poses = kargs.get("seed_poses", 0)
         self.compute_dtype = kargs.get("compute_dtype", None)   # additive: "fp32" (default) | "fp16" | "bf16" (engine.COMPUTE_DTYPES)
         if self.seed_poses > 0:
-            self.seed_pose_encoder = SeedPoseEncoder(njoints, self.seed_poses, latent_dim)
+            self.seed_pose_encoder = SeedPoseEncoder(njoints, self.seed_poses, latent_dim - (text_dim if self.use_text else 0))
 
         self.mfcc_input = kargs.get("mfcc_input", False)
         self.use_wav_enc = kargs.get("use_wav_enc", False)
@@ -301,12 +346,14 @@ class MDM(_NativeDenoiser):
 
     def forward(self, x, timesteps, y=None):
         """x [B, njoints, nfeats, T]; timesteps [B] int; y: dict with 'seed' [B,J,1,P], 'mfcc'
-        [B,26,1,T], optional 'uncond'.  Returns [B, njoints, nfeats, T] (contiguous)."""
+        [B,26,1,T], optional 'uncond'; a use_text model also takes 'text_embed' [B, clip_dim] (or 'text', a list of B strings,
+        once set_text_encoder installed an encoder).  Returns [B, njoints, nfeats, T] (contiguous)."""
         self._check_inputs(x, y)
         guidance_interval_of(y, False)                     # the key needs a ClassifierFreeSampleModel: ValueError here
         guidance_rescale_of(y, False)
         bs, njoints, nfeats, nframes = x.shape
         force_mask = y.get("uncond", False)
+        text = self._text_features(y, bs)                  # the reference reads y['text'] before y['seed'] (model/mdm.py:120)
         seed = y["seed"]                                   # KeyError like the reference (model/mdm.py:125)
         if self.seed_poses <= 0:
             raise AttributeError("'MDM' object has no attribute 'seed_pose_encoder'")
@@ -326,6 +373,6 @@ class MDM(_NativeDenoiser):
             raise ValueError(f"at most {ROPE_ROWS - 1} frames")
         eng = self._get_engine(x.device)
         eng.prepare(bs, nframes)
-        eng.set_condition(seed, mfcc)
+        eng.set_condition(seed, mfcc, text=text)
         out = eng.forward(x, timesteps, GDX_UNCOND if force_mask else GDX_COND)
         return out.view(bs, njoints, nfeats, nframes)

@@ -14,6 +14,8 @@ MFCCs (computed on the GPU), text, lengths, raw audio and ground-truth motion co
 its statistics, and `results.npy` / `results.txt` / `results_len.txt` are written.  The BVH, MP4 and WAV files of
 `:218-301` are not: bvhsdk, ffmpeg and soundfile are not dependencies of this project, and what they would hold is in
 `results.npy`.  `--synthetic` needs no data: seed poses and MFCCs are N(0,1) and the tail's statistics are synthetic.
+`--use_text` models are conditioned on CLIP text features, which this build does not compute: `--synthetic` draws them from the
+run's seed, a data directory needs `--text_features FILE.npz` (`--list_texts OUT.txt` writes the strings to encode and exits).
 `--invert_gt` (data directory and `--sampler ddim` only) starts every chunk's DDIM loop from the DDIM inversion of that chunk's
 ground truth instead of a drawn x_T (`sample_chunks`, `invert_of_chunk`).
 
@@ -52,7 +54,7 @@ def resolve_rng(rng, world):
 def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames, seed_poses, guidance_param=1.0,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
-                  guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None):
+                  guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None, text_of_chunk=None):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -67,7 +69,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     invert_of_chunk(c) -> recorded motion [b, J, 1, frames] in the sampler's normalised units ("ddim" only): chunk c's x_T is not
     drawn but is that motion's DDIM inversion (ddim_reverse_sample_loop) under the chunk's own seed poses and MFCCs, with the
     conditional pass alone -- no guidance, whatever guidance_param says; the (guided) DDIM loop then starts from it.  With
-    guidance_param == 1 the loop retraces the inversion, and report(text) is told each chunk's round-trip error."""
+    guidance_param == 1 the loop retraces the inversion, and report(text) is told each chunk's round-trip error.
+    text_of_chunk(c) -> text features [b, clip_dim] on the device (a use_text model): chunk c's y['text_embed']."""
     if invert_of_chunk is not None and sampler != "ddim":
         raise ValueError("invert_of_chunk needs sampler='ddim': the latent is the start state of the deterministic DDIM loop")
     if invert_of_chunk is not None and guidance_refresh > 1:
@@ -87,6 +90,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     outs, sample_out = [], None
     for chunk in range(n_chunks):
         y = {"mfcc": mfcc_of_chunk(chunk), "seed": first_seed if chunk == 0 else sample_out[..., -seed_poses:]}
+        if text_of_chunk is not None:
+            y["text_embed"] = text_of_chunk(chunk)
         if guidance_param != 1:
             y["scale"] = torch.ones(b, device=first_seed.device) * guidance_param
         if guidance_interval is not None:
@@ -115,7 +120,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             gt = invert_of_chunk(chunk)
             inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
             kw["noise"] = diffusion.ddim_reverse_sample_loop(inner, gt, clip_denoised=False, progress=progress,
-                                                             model_kwargs={"y": {"mfcc": y["mfcc"], "seed": y["seed"]}})
+                                                             model_kwargs={"y": {k: y[k] for k in ("mfcc", "seed", "text_embed")
+                                                                                 if k in y}})
         sample_out = sample_fn(model, (b, J, 1, frames), **kw)
         if gt is not None and guidance_param == 1 and report is not None:
             err = float((sample_out - gt).abs().max() / gt.abs().max())
@@ -148,6 +154,42 @@ def check_data_width(data_width, njoints):
         raise ValueError(f"the data directory's poses have {data_width} features, the model is built for {njoints}")
 
 
+def run_texts(ds, index):
+    """The text of every (take, chunk) window of a run, [n_chunks][num_samples] (`index` from chunk_items); host only."""
+    return [[ds.text_window(*ds.locate(i)) for i in row] for row in index]
+
+
+def distinct(texts):
+    """The distinct strings of run_texts' table in order of first appearance (what --list_texts writes, one per line)."""
+    return list(dict.fromkeys(t for row in texts for t in row))
+
+
+def lookup_text_features(path, texts, clip_dim):
+    """--text_features: the npz's `features` rows for run_texts' table -> float32 [n_chunks, num_samples, clip_dim] (host), each
+    string looked up by exact match in the npz's `text` array ('' is a key like any other).  ValueError, before anything is
+    sampled, for a file without the two arrays, features that are not [len(text), clip_dim], and strings the file lacks: their
+    number and the first few."""
+    with np.load(path, allow_pickle=False) as f:
+        if "text" not in f.files or "features" not in f.files:
+            raise ValueError(f"{path} must hold the arrays `text` and `features`, it holds {sorted(f.files)}")
+        keys, feats = [str(t) for t in f["text"].reshape(-1)], np.asarray(f["features"], dtype=np.float32)
+    if feats.shape != (len(keys), clip_dim):
+        raise ValueError(f"{path}: `features` must be [{len(keys)}, {clip_dim}] (one row of clip_dim per text), it is {list(feats.shape)}")
+    row = {k: i for i, k in reversed(list(enumerate(keys)))}                 # a repeated string: its first row
+    missing = [t for t in distinct(texts) if t not in row]
+    if missing:
+        raise ValueError(f"{len(missing)} of the run's {len(distinct(texts))} texts are not in {path}; the first: "
+                         f"{missing[:3]!r} (--list_texts OUT.txt writes all of them)")
+    return torch.from_numpy(np.stack([feats[[row[t] for t in chunk]] for chunk in texts]))
+
+
+def synthetic_text_features(seed, num_samples, clip_dim, n_chunks):
+    """--use_text --synthetic: N(0,1) stand-ins for the CLIP features, one [num_samples, clip_dim] per chunk, from a generator of
+    their own keyed by the run's seed (the seed-pose and MFCC draws of a run do not depend on --use_text)."""
+    g = torch.Generator().manual_seed(int(seed) * 1000003 + 512)
+    return [torch.randn(num_samples, clip_dim, generator=g) for _ in range(n_chunks)]
+
+
 def host_item(ds, idx):
     """Item `idx` of a Genea2023 without its MFCCs (zeros stand in): everything `gg_collate` needs that is host data."""
     take, sample = ds.locate(idx)
@@ -158,6 +200,15 @@ def host_item(ds, idx):
 
 def main(argv=None):
     args = generate_args(argv)
+    if args.list_texts:                # host only: the strings a user encodes with their own CLIP for --text_features
+        n = min(args.num_samples if args.num_samples else 41, args.batch_size)
+        ds = get_dataset_loader(args.dataset, n, args.num_frames, split='val', hml_mode='text_only', seed_poses=args.seed_poses,
+                                datapath=args.data_dir or None).dataset
+        lines = distinct(run_texts(ds, chunk_items(ds.samples_cumulative, n, args.chunks)))
+        with open(args.list_texts, "w") as f:
+            f.write("".join(t + "\n" for t in lines))
+        print(f"wrote {len(lines)} distinct texts to [{args.list_texts}]")
+        return 0
     fixseed(args.seed)
     rank, world, device = dist_util.init_from_env(arg_device=args.device)   # makes `device` current: nothing exists yet
     if device.type != "cuda":
@@ -179,6 +230,12 @@ def main(argv=None):
     model, diffusion = create_model_and_diffusion(args, None)
     if ds is not None:
         check_data_width(ds.mean.shape[-1], model.njoints)
+    text_dim, clip_dim = model._text_dims()
+    text_feats = None                                   # per chunk [num_samples, clip_dim] on the host, every rank the whole table
+    if text_dim and ds is not None:
+        text_feats = lookup_text_features(args.text_features, run_texts(ds, index), clip_dim)
+    elif text_dim:
+        text_feats = synthetic_text_features(args.seed, num_samples, clip_dim, args.chunks)
     if args.model_path and args.packed_cache:
         model.to(device)
         how = load_model_cached(model, args.model_path, device, args.packed_cache)
@@ -189,7 +246,7 @@ def main(argv=None):
         load_model_wo_clip(model, state_dict)
     else:
         cfg = dict(arch=args.arch_version, njoints=model.njoints, nfeats=1, latent_dim=args.latent_dim, ff_size=1024,
-                   num_layers=args.layers, num_heads=4, seed_poses=args.seed_poses)
+                   num_layers=args.layers, num_heads=4, seed_poses=args.seed_poses, text_dim=text_dim, clip_dim=clip_dim)
         model.load_state_dict(init_state_dict(cfg, seed=args.seed), strict=False)
     if args.guidance_param != 1:
         model = ClassifierFreeSampleModel(model)
@@ -233,6 +290,11 @@ def main(argv=None):
                 return torch.stack([extractor(a)[:T].t() for a in audio]).unsqueeze(2).contiguous()     # [nb, 26, 1, T]
             return torch.randn(num_samples, MFCC_DIM, 1, T, generator=g)[lo:hi].to(device)
 
+    text_of_chunk = None
+    if text_feats is not None:
+        def text_of_chunk(chunk):          # this rank's shard of the chunk's features
+            return text_feats[chunk][lo:hi].to(device)
+
     def on_chunk(chunk):
         if rank == 0:
             print(f"### Sampling chunk {chunk + 1} of {args.chunks}")
@@ -260,7 +322,8 @@ def main(argv=None):
                          philox_seed=args.seed, sample_offset=lo, progress=args.progress and rank == 0, on_chunk=on_chunk,
                          plms_order=args.plms_order, dpm_order=args.dpm_order, unipc_order=args.unipc_order,
                          guidance_interval=interval, guidance_rescale=args.guidance_rescale,
-                         guidance_refresh=args.guidance_refresh, invert_of_chunk=invert_of_chunk, report=report)
+                         guidance_refresh=args.guidance_refresh, invert_of_chunk=invert_of_chunk, report=report,
+                         text_of_chunk=text_of_chunk)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

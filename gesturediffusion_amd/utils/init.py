@@ -28,8 +28,12 @@ def param_shapes(cfg):
     s["embed_timestep.time_embed.0.bias"] = (d,)
     s["embed_timestep.time_embed.2.weight"] = (d, d)
     s["embed_timestep.time_embed.2.bias"] = (d,)
-    s["seed_pose_encoder.seed_embed.weight"] = (d, cfg["njoints"] * sp)
-    s["seed_pose_encoder.seed_embed.bias"] = (d,)
+    td = cfg.get("text_dim", 0)                      # use_text (arch 'mdm' only): embed_text + a seed encoder of d - text_dim rows
+    s["seed_pose_encoder.seed_embed.weight"] = (d - td, cfg["njoints"] * sp)
+    s["seed_pose_encoder.seed_embed.bias"] = (d - td,)
+    if td:
+        s["embed_text.weight"] = (td, cfg["clip_dim"])
+        s["embed_text.bias"] = (td,)
     if cfg.get("arch", "mdm") == "mdm":
         s["input_process.poseEmbedding.weight"] = (d, J)
         s["project_to_lat.weight"] = (d, 2 * d + MFCC_DIM)
@@ -91,10 +95,13 @@ def init_state_dict(cfg, seed=0, perturb=False):
 
 def synthetic_inputs(cfg, batch, frames, seed=10):
     """N(0,1) x_T, seed poses and MFCCs (both are z-scored in the reference's dataset:
-    data_loaders/gesture/data/dataset.py:77-78,94)."""
+    data_loaders/gesture/data/dataset.py:77-78,94).  A cfg with text_dim > 0 gets a fourth tensor, text features
+    [batch, clip_dim] drawn after the others (the first three do not depend on it)."""
     J, nf = cfg["njoints"], cfg["nfeats"]
     g = _gen(seed, "inputs")
     x = torch.randn(batch, J, nf, frames, generator=g)
     seed_poses = torch.randn(batch, J, nf, cfg["seed_poses"], generator=g)
     mfcc = torch.randn(batch, MFCC_DIM, 1, frames, generator=g)
+    if cfg.get("text_dim", 0):
+        return x, seed_poses, mfcc, torch.randn(batch, cfg["clip_dim"], generator=g)
     return x, seed_poses, mfcc

@@ -63,6 +63,11 @@ def parse_and_load_from_model(parser, argv=None):
             parser.error("--invert_gt needs --sampler ddim: the latent is the start state of the deterministic DDIM loop")
         if args.guidance_refresh > 1:
             parser.error("--invert_gt runs no guidance refresh: the inversion is one conditional pass per step")
+    if args.list_texts and args.synthetic:
+        parser.error("--list_texts lists the texts of a data directory: --synthetic has none")
+    if args.use_text and args.arch_version == "mdm" and not (args.synthetic or args.text_features or args.list_texts):
+        parser.error("--use_text on a data directory needs --text_features FILE.npz (arrays `text`: the strings, `features`: "
+                     "float32 [N, clip_dim], their CLIP text features); --list_texts OUT.txt writes the strings this run needs")
     return args
 
 
@@ -180,6 +185,13 @@ def add_native_options(parser):
                             "for inversion), and the latent replaces the drawn x_T of the (guided) DDIM loop. "
                             "Needs --dataset genea2023 --data_dir D and --sampler ddim; with --guidance_param 1 the per-chunk "
                             "round-trip error max|regenerated - gt| / max|gt| is printed.")
+    group.add_argument("--text_features", default='', type=str, metavar="FILE.npz",
+                       help="--use_text on a data directory: the CLIP text features of the run's texts, arrays `text` (strings) "
+                            "and `features` (float32 [N, clip_dim]); every (take, chunk) text is looked up by exact match before "
+                            "sampling starts.  This build has no CLIP tower: encode the strings of --list_texts with "
+                            "clip.tokenize(texts, truncate=True) and clip_model.encode_text(tokens).float().")
+    group.add_argument("--list_texts", default='', type=str, metavar="OUT.txt",
+                       help="Write the distinct texts of the run's (take, chunk) windows, one per line, and exit (no GPU needed).")
     group.add_argument("--rng", default=None, choices=['torch', 'philox'],
                        help="torch = the reference's generator and draw order (single-GPU default); philox = in-kernel "
                             "counter-based noise keyed by the global sample index (shard invariant; multi-GPU default).")

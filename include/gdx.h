@@ -6,6 +6,7 @@
  * reference's tensors:
  *     pose tensors  [B, J, 1, T]   (J = njoints * nfeats, nfeats must be 1; T fastest)
  *     seed poses    [B, J, 1, P]   mfcc [B, 26, 1, T]   timesteps int64 [B]
+ *     text features [B, clip_dim]  (use_text models only: the output of the caller's CLIP text tower, gdx_set_condition_text)
  * The library owns only its packed copy of the weights and its workspace.  One handle per
  * (device, stream); not thread-safe per handle; no hidden device synchronisation;
  * int status return (0 = ok, <0 = error, text via gdx_last_error()); no exceptions cross
@@ -67,6 +68,9 @@ typedef struct {
     int32_t window;      /* 10 (model/mdm.py:75), V2 only */
     int32_t compute_dtype;   /* GDX_DTYPE_*.  The reference samples in fp32 only (its `use_fp16` is a deprecated
                                 trainer switch, train/training_loop.py:43); fp16 is this library's additive mode */
+    int32_t text_dim;    /* use_text (model/mdm.py:36-50), V2 only: width of embed_text's output, 0 < text_dim < latent_dim; the
+                            seed-pose encoder then has latent_dim - text_dim rows.  0 = no text (with clip_dim 0) */
+    int32_t clip_dim;    /* use_text: width of the text features the caller supplies (512 for CLIP ViT-B/32); 0 without text */
 } gdx_config_t;
 
 /* ---- lifetime ------------------------------------------------------------------------- */
@@ -96,7 +100,9 @@ int gdx_weights_ready(gdx_handle_t h);
  * gdx_import_packed refuses (and leaves the handle untouched) unless the configuration, the compute dtype, every record's
  * dimensions and the checksum match what this handle computes for itself.  Once validation has passed the upload starts and
  * the handle counts as "weights not set" until it has completed: a failed allocation or copy leaves gdx_weights_ready()
- * failing, never a half-uploaded model.  After a successful import gdx_weights_ready() holds.
+ * failing, never a half-uploaded model.  After a successful import gdx_weights_ready() holds.  An image written before
+ * gdx_config_t had text_dim / clip_dim carries a shorter header: its record count lies where text_dim is read, so every handle
+ * refuses it as "built for another configuration" (utils/model_util.py load_model_cached then re-packs from the checkpoint).
  *   gdx_packed_bytes : size of the blob for this handle (all weights must be set)
  *   gdx_export_packed: fill `host` (exactly that many bytes); synchronises `stream`
  *   gdx_import_packed: upload a blob; synchronises `stream` (the caller may free `host` on return) */
@@ -117,6 +123,16 @@ int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames);
  * cond and uncond passes (model/mdm.py:125-127), the MFCC slice of the input / project_to_lat
  * linear (model/mdm.py:133-169, model/mdm_old.py:104-108).  seed [B,J,1,P], mfcc [B,26,1,T]. */
 int gdx_set_condition(gdx_handle_t h, const float* seed, const float* mfcc, void* stream);
+
+/* The same for a handle with text_dim > 0 (MDM(use_text=True), model/mdm.py:118-127,154-160).  text [B, clip_dim] holds what the
+ * reference's clip_model.encode_text(tokenize(y['text'])).float() returns: the CLIP tower and its tokenizer are the caller's (the
+ * reference's trainer strips clip_model.* from every checkpoint, train/training_loop.py:269-272, so a checkpoint holds only
+ * embed_text and the narrower seed-pose encoder).  Row b of the coarse condition becomes
+ *     cond   [ embed_text(text_b) | seed_embed(seed_b) ]      text in columns 0 .. text_dim-1, the seed in the rest
+ *     uncond [ embed_text.bias    | seed_embed.bias    ]      both inputs zeroed before their Linear (mask_cond, :242-250)
+ * and everything behind it is gdx_set_condition's.  Each of the two entries refuses a handle of the other kind, naming the entry
+ * to call; like every refusal of either (null pointer, no gdx_prepare, weights missing) that happens before any device work. */
+int gdx_set_condition_text(gdx_handle_t h, const float* seed, const float* mfcc, const float* text, void* stream);
 
 /* Guidance interval (limited-interval guidance, Kynkaanniemi et al. 2024, arXiv:2404.07724; no counterpart in the reference):
  * the MODEL timesteps -- the values the denoiser sees after the respacing map, 0..999 for the reference's schedule -- at which
