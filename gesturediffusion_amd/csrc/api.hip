@@ -121,6 +121,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     if (h->cfg.arch == GDX_ARCH_MDM && h->rope_cos && frames + 1 > h->rope_rows)
         return fail("gdx_prepare: frames exceed rotary table");
     h->gd_valid = false;                                          // guidance refresh: a stored difference never outlives a prepare
+    h->lc_valid = false;                                          // layer cache: nor does a stored change
     if (h->B == batch && h->T == frames) return 0;
     free_pool(h->ws_allocs);
     h->guard_zones.clear();
@@ -128,7 +129,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     h->temb_table = nullptr; h->temb_table_rows = 0; h->tmap_dev = nullptr; h->c2t_table = nullptr; h->c2t_valid = false;
     h->tables_valid = false;
     h->bpd_xt = h->bpd_z = h->bpd_part = nullptr;
-    h->rs_part = nullptr; h->rs_factor = nullptr; h->gd = nullptr;
+    h->rs_part = nullptr; h->rs_factor = nullptr; h->gd = nullptr; h->lc_delta = nullptr; h->lc_in = nullptr;
     // the shape is recorded only once every allocation has succeeded: after a failed hipMalloc a retry with the same
     // shape must allocate again instead of returning early on partial buffers
     h->B = 0; h->T = 0; h->S = frames + 1; h->cond_set = false;
@@ -167,7 +168,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
         act(h->xseq, NT * d, false, half && v2))
         return -1;
     if (h->keep_taps) {
-        h->taps.resize(h->L + 1);
+        h->taps.resize(h->L + 2);                                 // L + 1: the output GEMM's operand (gdx_get_tap)
         for (auto& t : h->taps)
             if (A(&t, N * d)) return -1;
     }
@@ -214,7 +215,7 @@ extern "C" int gdx_set_keep_taps(gdx_handle_t h, int32_t keep) {
 
 extern "C" int gdx_get_tap(gdx_handle_t h, int32_t which, float* out, int64_t count, void* stream) {
     if (!h || !out) return fail("gdx_get_tap: null argument");
-    if (!h->keep_taps || which < 0 || which > h->L || h->taps.empty()) return fail("gdx_get_tap: taps not kept");
+    if (!h->keep_taps || which < 0 || which > h->L + 1 || h->taps.empty()) return fail("gdx_get_tap: taps not kept");
     const int64_t maxc = 2LL * h->B * h->S * h->d;
     if (count > maxc) return fail("gdx_get_tap: count too large");
     HIPCHK(hipMemcpyAsync(out, h->taps[which], count * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -237,6 +238,7 @@ static int finish_condition(gdx_model* h, const float* mfcc, hipStream_t s) {
     }
     h->cond_set = true;
     h->gd_valid = false;                                          // guidance refresh: the difference of another conditioning
+    h->lc_valid = false;                                          // layer cache: the change under another conditioning
     return 0;
 }
 
@@ -383,11 +385,42 @@ static int add_norm(gdx_model* h, const Act& in, const Packed& W, const Act& res
 // 16-bit modes: GEMM and attention operands are 16-bit, and so is the residual stream unless stream32; every accumulation (MFMA,
 // the terms of the GEMM epilogues, LayerNorm statistics, softmax) is fp32, and so are the two boundary tensors: the pose tensor
 // read by the input transpose and the x0 prediction.
+// lc (layer cache, gdx.h gdx_set_layer_cache; the loops' layer_call decides): LC_FULL = today's forward, which also keeps the
+// stream after layer lc_keep - 1 and stores the change of the deeper layers; LC_PARTIAL = layers 0 .. lc_keep - 1 only, the output
+// GEMM's operand formed from their output plus the stored change.  LC_OFF issues exactly the launches of a handle without a cache.
+enum { LC_OFF = 0, LC_FULL = 1, LC_PARTIAL = 2 };
+
+// gdx_layer_delta on device buffers whose pairing is already one of the three: the fp32 instance, or the build of the 16-bit type
+static int layer_delta(int op, int in_dtype, int out_dtype, int B, int T, int d, const void* in, void* outc, float* delta,
+                       hipStream_t s) {
+    if (out_dtype == GDX_DTYPE_F32) HIPCHK(launch_layer_delta(op, (const float*)in, (float*)outc, delta, B, T, d, s));
+    else HIPCHK(HFN(out_dtype == GDX_DTYPE_BF16, launch_layer_delta_h, op, in_dtype == GDX_DTYPE_F32, in, (_Float16*)outc, delta, B, T, d, s));
+    return 0;
+}
+
 static int forward_core(gdx_model* h, const float* x, const float* temb, int tstride, const float* c2t, int mode,
-                        float* x0_out, hipStream_t s, const int* state = nullptr, bool tm = false) {
+                        float* x0_out, hipStream_t s, const int* state = nullptr, bool tm = false, int lc = LC_OFF) {
     const int B = h->B, T = h->T, S = h->S, d = h->d, J = h->J;
     const int Beff = mode == GDX_CFG ? 2 * B : B;
+    const int layers = lc == LC_PARTIAL ? h->lc_keep : h->L;     // encoder layers this call launches
     h->forward_samples += Beff;                                   // gdx_forward_samples (host side only)
+    h->forward_layer_samples += (int64_t)Beff * layers;           // gdx_forward_layer_samples
+    // layer cache: the residual stream is fp32 in the fp32 mode and under stream32, else the 16-bit type; the operand of the
+    // output GEMM is fp32 in the fp32 mode only
+    const bool res32 = !h->f16 || h->stream32;
+    const int lc_in_dt = res32 ? GDX_DTYPE_F32 : h->cfg.compute_dtype, lc_out_dt = h->cfg.compute_dtype;
+    const void* lc_stream = res32 ? (const void*)h->xa.f : (const void*)h->xa.h;
+    void* lc_xc = h->f16 ? (void*)h->xc.h : (void*)h->xc.f;
+    if (lc != LC_OFF) {
+        if (lc == LC_PARTIAL && (!h->lc_valid || !h->lc_delta)) return fail("forward_core: a partial call without a stored layer change");
+        if (!h->lc_delta) {
+            const size_t rows = 2 * (size_t)B * S;
+            if (ws_alloc(h, "layer cache", (void**)&h->lc_delta, sizeof(float) * 2 * B * T * d) ||
+                ws_alloc(h, "layer cache", &h->lc_in, rows * d * (res32 ? 4 : 2)))
+                return -1;
+            HIPCHK(hipStreamSynchronize(nullptr));                 // the fills are on the null stream, the first store on s
+        }
+    }
     const float* seed_emb = mode == GDX_UNCOND ? h->seed_cat + (size_t)B * d : h->seed_cat;
     const int N = Beff * S;
     // the encoder stream as the sublayers write it: in the 16-bit stream its fp32 side only for the parity taps
@@ -418,7 +451,7 @@ static int forward_core(gdx_model* h, const float* x, const float* temb, int tst
         return 0;
     };
     if (tap(0)) return -1;
-    for (int l = 0; l < h->L; ++l) {
+    for (int l = 0; l < layers; ++l) {
         const Layer& ly = h->layers[l];
         if (linear(h, h->xa, ly.qkv, {.bias = ly.qkv.bias}, h->qkv, 3 * d, N, 3 * d, s) || attend(h, Beff, s)) return -1;
         if (add_norm(h, h->ctx, ly.out, h->xa, ly.g1, ly.b1, &h->xb, nullptr, N, s)) return -1;        // x = LN1(x + out_proj(ctx))
@@ -434,6 +467,20 @@ static int forward_core(gdx_model* h, const float* x, const float* temb, int tst
         if (add_norm(h, h->ffb, ly.ff2, h->xb, ly.g2, ly.b2, !last || h->keep_taps ? &xa : nullptr, last ? &h->xc : nullptr, N, s))
             return -1;
         if (tap(l + 1)) return -1;
+        // layer cache, full call: the stream after layer lc_keep - 1 outlives the deeper layers, which overwrite xa
+        if (lc == LC_FULL && l + 1 == h->lc_keep)
+            HIPCHK(hipMemcpyAsync(h->lc_in, lc_stream, (size_t)N * d * (res32 ? 4 : 2), hipMemcpyDeviceToDevice, s));
+    }
+    if (lc == LC_FULL) {                                          // change of layers lc_keep .. L-1 on the rows the output GEMM reads
+        if (layer_delta(0, lc_in_dt, lc_out_dt, Beff, T, d, h->lc_in, lc_xc, h->lc_delta, s)) return -1;
+        h->lc_valid = true; h->lc_mode = mode;
+    }
+    // partial call: the operand from this call's own shallow layers plus the stored change (a GDX_COND call under a stored
+    // GDX_CFG reads the conditional rows, the first B)
+    if (lc == LC_PARTIAL && layer_delta(1, lc_in_dt, lc_out_dt, Beff, T, d, lc_stream, lc_xc, h->lc_delta, s)) return -1;
+    if (h->keep_taps) {                                           // tap L + 1: the output GEMM's operand, widened
+        if (h->f16) HIPCHK(HFN(h->bf16, launch_convert_f32, h->xc.h, h->taps[h->L + 1], (int64_t)Beff * T * d, s));
+        else HIPCHK(hipMemcpyAsync(h->taps[h->L + 1], h->xc.f, sizeof(float) * (size_t)Beff * T * d, hipMemcpyDeviceToDevice, s));
     }
     // OutputProcess (model/mdm.py:372-380): token-major fp32 GEMM, then the permute back to [B, J, 1, T]
     if (linear(h, h->xc, h->outp, {.bias = h->outp.bias}, Act{h->x0t, nullptr}, h->ldo, Beff * T, h->ldo, s)) return -1;
@@ -485,23 +532,56 @@ extern "C" int gdx_forward_samples(gdx_handle_t h, int64_t* samples) {
     return 0;
 }
 
+// Layer cache (gdx.h): per-handle (every, keep), every = 1 = off.  Refusals precede any HIP call.
+extern "C" int gdx_set_layer_cache(gdx_handle_t h, int32_t every, int32_t keep) {
+    if (!h) return fail("gdx_set_layer_cache: null handle");
+    if (every < 1) return fail("gdx_set_layer_cache: every must be at least 1");
+    if (every > 1 && (keep < 1 || keep > h->L - 1))
+        return fail("gdx_set_layer_cache: keep must lie in 1 .. num_layers - 1 = " + std::to_string(h->L - 1));
+    h->lc_every = every; h->lc_keep = every > 1 ? keep : 0;
+    h->lc_valid = false;
+    return 0;
+}
+
+extern "C" int gdx_forward_layer_samples(gdx_handle_t h, int64_t* n) {
+    if (!h || !n) return fail("gdx_forward_layer_samples: null argument");
+    *n = h->forward_layer_samples;
+    return 0;
+}
+
+// The stand-alone delta pass (gdx.h); every refusal precedes the first HIP call
+extern "C" int gdx_layer_delta(int32_t op, int32_t in_dtype, int32_t out_dtype, int32_t batch, int32_t frames, int32_t width,
+                               const void* in, void* outc, float* delta, void* stream) {
+    if (op != 0 && op != 1) return fail("gdx_layer_delta: op must be 0 (store) or 1 (apply)");
+    const bool pairing = (in_dtype == GDX_DTYPE_F32 && out_dtype == GDX_DTYPE_F32) || (in_dtype == GDX_DTYPE_F16 && out_dtype == GDX_DTYPE_F16) ||
+                         (in_dtype == GDX_DTYPE_F32 && out_dtype == GDX_DTYPE_BF16);
+    if (!pairing) return fail("gdx_layer_delta: the (in, out) element types must be (fp32, fp32), (fp16, fp16) or (fp32, bf16)");
+    if (batch <= 0 || frames <= 0 || width <= 0) return fail("gdx_layer_delta: batch, frames and width must be positive");
+    if (width % 32) return fail("gdx_layer_delta: width must be a multiple of 32 (there is only a 128-bit path)");
+    if (!in || !outc || !delta) return fail("gdx_layer_delta: null argument");
+    if (((uintptr_t)in | (uintptr_t)outc | (uintptr_t)delta) & 15) return fail("gdx_layer_delta: every pointer must be 16-byte aligned");
+    return layer_delta(op, in_dtype, out_dtype, batch, frames, width, in, outc, delta, (hipStream_t)stream);
+}
+
 // step_mode's internal answers under the guidance refresh (gdx.h), never a loop's own mode: a guided call that stores the
 // difference c - u, and one that runs the conditional pass alone and reuses the stored difference
 static constexpr int GDX_CFG_REFRESH = GDX_CFG + 1, GDX_CFG_REUSE = GDX_CFG + 2;
 
 // The sequence of denoiser calls a call belongs to, as far as the numbering of its guided calls needs it: the loop's mode and
 // timestep map, the WHOLE loop's first index (first_index + k_base of a block), the index of the second call of gdx_plms_loop's
-// step 0 (-1: the loop has none), and whether the loop takes part in the refresh at all (gdx_bpd_loop does not)
+// step 0 (-1: the loop has none), and whether the loop takes part in the refresh and in the layer cache at all (gdx_bpd_loop and
+// gdx_ddim_reverse_loop do not)
 struct CallSeq {
     int mode;
     const int64_t* timestep_map;
     int first, second;
     bool refresh;
+    bool cache = false;
 };
 template <typename A>
 static CallSeq call_seq(const A* a, bool two_calls) {
     const int first = a->first_index + a->k_base;
-    return CallSeq{a->mode, a->timestep_map, first, two_calls ? (first - 1 + a->num_steps) % a->num_steps : -1, true};
+    return CallSeq{a->mode, a->timestep_map, first, two_calls ? (first - 1 + a->num_steps) % a->num_steps : -1, true, true};
 }
 
 static bool guided_at(const gdx_model* h, const CallSeq& q, int idx) {
@@ -514,18 +594,65 @@ static bool guided_at(const gdx_model* h, const CallSeq& q, int idx) {
 // blend).  With gdx_set_guidance_refresh's every > 1 a guided call is numbered n = the guided calls of the loop before it, in
 // execution order q.first, q.second, q.first - 1, q.first - 2, ..., and n % every decides between GDX_CFG_REFRESH and
 // GDX_CFG_REUSE.  Every in-library loop asks here.
-static int step_mode(const gdx_model* h, const CallSeq& q, int idx, bool second = false) {
+// mode_after: the same answer from n itself, for a caller that walks the calls in order (layer_call).
+static int mode_after(const gdx_model* h, const CallSeq& q, int idx, int n) {
     if (q.mode != GDX_CFG) return q.mode;
     if (!guided_at(h, q, idx)) return GDX_COND;
     if (h->guide_every == 1 || !q.refresh) return GDX_CFG;
-    int n = 0;
-    if (second) {
-        n = guided_at(h, q, q.first);
-    } else {
-        for (int j = q.first; j > idx; --j) n += guided_at(h, q, j);
-        if (q.second >= 0 && idx < q.first) n += guided_at(h, q, q.second);
-    }
     return n % h->guide_every == 0 ? GDX_CFG_REFRESH : GDX_CFG_REUSE;
+}
+static int step_mode(const gdx_model* h, const CallSeq& q, int idx, bool second = false) {
+    int n = 0;
+    if (q.mode == GDX_CFG && h->guide_every > 1 && q.refresh && guided_at(h, q, idx)) {
+        if (second) {
+            n = guided_at(h, q, q.first);
+        } else {
+            for (int j = q.first; j > idx; --j) n += guided_at(h, q, j);
+            if (q.second >= 0 && idx < q.first) n += guided_at(h, q, q.second);
+        }
+    }
+    return mode_after(h, q, idx, n);
+}
+
+// what forward_core is run with for step_mode's answer m: a refresh is the full guided forward, a reuse the conditional pass alone
+static int forward_mode(int m) { return m == GDX_CFG_REFRESH ? GDX_CFG : m == GDX_CFG_REUSE ? GDX_COND : m; }
+
+// Layer cache (gdx.h, gdx_set_layer_cache): what ONE denoiser call of q's loop does -- lc = LC_FULL or LC_PARTIAL (LC_OFF: no
+// cache on the handle, or a loop that takes no part) -- and K, the forward mode stored by the loop's most recent full call
+// before it (-1: none).  The loop's calls are walked from its first one, in execution order q.first, q.second, q.first - 1, ...:
+// call m is full when m % every == 0 or the stored mode does not cover its own.  No counter lives in the handle, so a block of
+// a loop gets the plan of the whole loop.  Every in-library loop asks here.
+struct LayerCall { int lc, K; };
+static LayerCall layer_call(const gdx_model* h, const CallSeq& q, int idx, bool second = false) {
+    if (h->lc_every == 1 || !q.cache) return {LC_OFF, -1};
+    int K = -1, n = 0, m = 0;
+    auto visit = [&](int j) {
+        const int sm = mode_after(h, q, j, n), c = forward_mode(sm);
+        n += sm >= GDX_CFG;
+        const bool covers = K == c || (K == GDX_CFG && c == GDX_COND);
+        const LayerCall r{m % h->lc_every == 0 || !covers ? LC_FULL : LC_PARTIAL, K};
+        if (r.lc == LC_FULL) K = c;
+        ++m;
+        return r;
+    };
+    LayerCall r = visit(q.first);
+    if (!second && idx == q.first) return r;
+    if (q.second >= 0) {
+        r = visit(q.second);
+        if (second) return r;
+    }
+    for (int j = q.first - 1; j >= idx; --j) r = visit(j);
+    return r;
+}
+
+// A block that issues q's loop from first_index must not begin with a partial call whose stored change is missing or of another
+// mode than the plan's: asked before the call's first launch
+static int check_layer_cache(const gdx_model* h, const char* who, const CallSeq& q, int first_index) {
+    const LayerCall c = layer_call(h, q, first_index);
+    if (c.lc == LC_PARTIAL && !(h->lc_valid && h->lc_mode == c.K))
+        return fail(std::string(who) + ": a partial call would add the stored change of the deep layers, but none of the planned mode "
+                    "is stored: a block-wise call (run_steps / k_base) must continue the loop that stored the change");
+    return 0;
 }
 
 // A call that issues the steps first_index .. last_idx of q's loop must not begin with a reuse that has nothing to reuse: asked
@@ -656,11 +783,10 @@ static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timeste
 // The denoiser at schedule index `idx` of the loop tables build_step_tables left: x0_out (pose layout) from the state x; tm:
 // the token-major variant (x / x0_out unused); state: a captured step, which reads its row number from the device (idx = 0)
 static int denoise_step(gdx_model* h, const float* x, int idx, int mode, float* x0_out, hipStream_t s, const int* state = nullptr,
-                        bool tm = false) {
+                        bool tm = false, int lc = LC_OFF) {
     const size_t row = (size_t)idx * h->d;
-    // step_mode's refresh answers: a refresh is the full guided forward, a reuse the conditional pass alone
-    const int fm = mode == GDX_CFG_REFRESH ? GDX_CFG : mode == GDX_CFG_REUSE ? GDX_COND : mode;
-    return forward_core(h, x, h->temb_table + row, 0, h->c2t_table ? h->c2t_table + row : nullptr, fm, x0_out, s, state, tm);
+    return forward_core(h, x, h->temb_table + row, 0, h->c2t_table ? h->c2t_table + row : nullptr, forward_mode(mode), x0_out, s,
+                        state, tm, lc);
 }
 
 // Executed step k's slice of a noise tape that starts at step k_base and holds `rows` samples ([rows][per]) per step
@@ -674,7 +800,8 @@ static const float* tape_slice(const float* tape, int k, int k_base, size_t rows
 static int denoise_guided(gdx_model* h, const CallSeq& q, const float* sc_in, const float* x, int idx, hipStream_t s,
                           const float** x0_uncond, const float** scale, bool second = false) {
     const int m = step_mode(h, q, idx, second);
-    return denoise_step(h, x, idx, m, h->x0, s) || guided_operands(h, m, sc_in, s, x0_uncond, scale) ? -1 : 0;
+    const int lc = layer_call(h, q, idx, second).lc;
+    return denoise_step(h, x, idx, m, h->x0, s, nullptr, false, lc) || guided_operands(h, m, sc_in, s, x0_uncond, scale) ? -1 : 0;
 }
 
 // calc_bpd_loop (gaussian_diffusion.py:1537-1592): per step q_sample -> denoiser -> fused bound terms, through the SAME forward
@@ -769,7 +896,7 @@ static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_l
     if (h->B > 65535) return fail(w + "batch exceeds 65535");
     const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
     const CallSeq q = call_seq(a, two_calls);
-    if (check_reuse(h, who, q, a->first_index, last_idx)) return -1;
+    if (check_reuse(h, who, q, a->first_index, last_idx) || check_layer_cache(h, who, q, a->first_index)) return -1;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
     const size_t n = (size_t)h->B * h->J * h->T;
     const int depth = ring > 0 ? ring : a->order;
@@ -905,10 +1032,12 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     const int B = h->B;
     const int last_idx = a->run_steps > 0 && a->run_steps <= a->first_index ? a->first_index - a->run_steps + 1 : 0;
     // guidance refresh: the guided calls are numbered from the whole loop's first index
-    const bool refresh_on = h->guide_every > 1 && a->mode == GDX_CFG;
+    // ... and so are the calls of the layer cache
+    const bool refresh_on = (h->guide_every > 1 && a->mode == GDX_CFG) || h->lc_every > 1;
     if (refresh_on && a->first_index + a->k_base >= a->num_steps) return fail("gdx_sample_loop: bad step range");
-    const CallSeq q{a->mode, a->timestep_map, a->first_index + a->k_base, -1, true};        // first: read only when refresh_on
-    if (check_reuse(h, "gdx_sample_loop", q, a->first_index, last_idx)) return -1;
+    const CallSeq q{a->mode, a->timestep_map, a->first_index + a->k_base, -1, true, true};  // first: read only when refresh_on
+    if (check_reuse(h, "gdx_sample_loop", q, a->first_index, last_idx) || check_layer_cache(h, "gdx_sample_loop", q, a->first_index))
+        return -1;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
 
     const int64_t per = (int64_t)h->J * h->T;
@@ -983,7 +1112,7 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         int k = a->k_base;
         for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
             const int m = mode_at(idx);
-            if (denoise_step(h, nullptr, idx, m, nullptr, s, nullptr, true)) return -1;
+            if (denoise_step(h, nullptr, idx, m, nullptr, s, nullptr, true, layer_call(h, q, idx).lc)) return -1;
             u.scale = m == GDX_CFG ? a->scale : nullptr;
             u.mirror = any_guided && m != GDX_CFG && (mirror_always || (idx > last_idx && mode_at(idx - 1) == GDX_CFG));
             u.step_index = idx; u.rng_step = (uint32_t)(k + 1);
@@ -994,7 +1123,8 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         return 0;
     }
     // the graph is ONE captured step: only a call whose steps all take the same mode can replay it
-    const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8 && uniform && !refreshes;
+    const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8 && uniform && !refreshes &&
+                            h->lc_every == 1;                     // the layer cache's calls differ from one another: eager
     int idx = a->first_index, k = a->k_base;
     if (want_graph) {
         if (eager_step(idx, k)) return -1;                        // step 0 eagerly: it also sets every kernel attribute

@@ -4,6 +4,7 @@
 #include "gdx_internal.h"
 #include "gdx_device.h"
 #include "gdx_transpose.h"
+#include "gdx_layer_delta.h"
 
 namespace gdx {
 
@@ -132,6 +133,11 @@ hipError_t launch_mfcc_project(const float* mfcc, const float* W, int ldw, const
     hipLaunchKernelGGL(mfcc_project_kernel, dim3((d + 255) / 256, (unsigned)((nrows + rpb - 1) / rpb)), dim3(256), 0, s, mfcc, W,
                        ldw, bias, pe, out, B, Bsrc, C, T, d, rps, off, rpb);
     return hipGetLastError();
+}
+
+// layer cache, fp32 residual stream and fp32 operand (gdx_layer_delta.h)
+hipError_t launch_layer_delta(int op, const float* in, float* outc, float* delta, int B, int T, int d, hipStream_t s) {
+    return launch_layer_delta_t<float, float>(op, in, outc, delta, B, T, d, s);
 }
 
 }  // namespace gdx

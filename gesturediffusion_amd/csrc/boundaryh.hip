@@ -4,6 +4,7 @@
 #include "gdx_internal.h"
 #include "gdx_device.h"
 #include "gdx_transpose.h"
+#include "gdx_layer_delta.h"
 
 namespace gdx {
 GDX_HNS_BEGIN
@@ -73,6 +74,15 @@ hipError_t launch_convert_f16(const float* src, _Float16* dst_, int64_t n, hipSt
     const int64_t nth = (n + 3) / 4;
     hipLaunchKernelGGL(convert_f16_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, s, src, dst, n);
     return hipGetLastError();
+}
+
+// layer cache with a 16-bit operand (gdx_layer_delta.h): the residual stream in the build's half_t, or fp32 (in32: the bf16
+// mode's fp32 stream)
+hipError_t launch_layer_delta_h(int op, bool in32, const void* in, _Float16* outc_, float* delta, int B, int T, int d,
+                                hipStream_t s) {
+    half_t* outc = reinterpret_cast<half_t*>(outc_);
+    if (in32) return launch_layer_delta_t<float, half_t>(op, static_cast<const float*>(in), outc, delta, B, T, d, s);
+    return launch_layer_delta_t<half_t, half_t>(op, static_cast<const half_t*>(in), outc, delta, B, T, d, s);
 }
 
 GDX_HNS_END

@@ -134,7 +134,15 @@ struct gdx_model {
     int guide_every = 1;              // gdx_set_guidance_refresh: the unconditional pass runs on every guide_every-th guided call
     float* gd = nullptr;              // guidance refresh: the stored difference c - u [B, J, T], allocated on first use
     bool gd_valid = false;            // ... holds a refresh call's difference under the current conditioning
+    int lc_every = 1, lc_keep = 0;    // gdx_set_layer_cache: every lc_every-th denoiser call of a loop is full; the calls between
+                                      // run lc_keep layers and add the stored change of the deeper ones (1 = off)
+    float* lc_delta = nullptr;        // layer cache: the stored change [2B, T, d], allocated on first use
+    void* lc_in = nullptr;            // ... and the residual stream after layer lc_keep - 1 [2B, T+1, d] in the stream's element
+                                      // type, kept until the end of a full call
+    bool lc_valid = false;            // ... lc_delta holds a full call's change under the current conditioning,
+    int lc_mode = 0;                  // ... stored by a call of this forward mode (GDX_COND / GDX_UNCOND / GDX_CFG)
     int64_t forward_samples = 0;     // gdx_forward_samples: samples pushed through forward_core since gdx_create
+    int64_t forward_layer_samples = 0;   // gdx_forward_layer_samples: samples x encoder layers launched
     gdx::Act xa, xb, qkv, ctx, tmp, ffb;   // [rows_alloc] token rows: residual stream (xa, xb), sublayer operands and outputs
     gdx::Act xt, xc;                       // token-major pose in / compacted last layer, [2B*T + pad] rows
     gdx::Act emb, xseq;                    // V2 front end: InputProcess output, proj_pose output

@@ -123,6 +123,8 @@ hipError_t launch_gather_rows(const float* table, const int64_t* idx, float* out
 // out[(b*rps + t + off)*d + n] = sum_c mfcc[((b%Bsrc)*C + c)*T + t] * W[n*ldw + c] + bias[n] (+ pe[(t+1)*d + n] if pe)
 hipError_t launch_mfcc_project(const float* mfcc, const float* W, int ldw, const float* bias, const float* pe, float* out,
                                int B, int Bsrc, int C, int T, int d, int rps, int off, hipStream_t s);
+// layer cache (gdx_layer_delta.h), fp32 stream and operand: op 0 delta = outc - in rows (b, t+1), op 1 outc = in rows + delta
+hipError_t launch_layer_delta(int op, const float* in, float* outc, float* delta, int B, int T, int d, hipStream_t s);
 
 // ---- MFCC front end pieces (mfcc.hip); the two transforms in between run on the persistent GEMM (api.hip: gdx_mfcc) ----
 hipError_t launch_mfcc_frames(const float* x, long n, float* frames, int numframes, int frame_len, int frame_step, int ldf,
@@ -174,6 +176,9 @@ inline bool local_attention_mfma_supported(int d, int heads, int window) {
     hipError_t launch_token0(const float* temb, int tstride, const float* seed_emb, const float* pe0, float* enc,           \
                              _Float16* enc16, const float* c2t, const float* c2_seed, float* c2, const int* state, int B,   \
                              int Bsrc, int S, int d, hipStream_t s);                                                        \
+    /* launch_layer_delta with a half operand outc; in: the half stream, or (in32) the fp32 one */                          \
+    hipError_t launch_layer_delta_h(int op, bool in32, const void* in, _Float16* outc, float* delta, int B, int T, int d,   \
+                                    hipStream_t s);                                                                         \
     /* dst[i] = (half) src[i] and back */                                                                                   \
     hipError_t launch_convert_f16(const float* src, _Float16* dst, int64_t n, hipStream_t s);                               \
     hipError_t launch_convert_f32(const _Float16* src, float* dst, int64_t n, hipStream_t s);                               \

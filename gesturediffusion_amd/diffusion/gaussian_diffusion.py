@@ -554,12 +554,14 @@ class GaussianDiffusion:
         interval = E.guidance_interval_of(y, guided)
         phi = E.guidance_rescale_of(y, guided)
         every = E.guidance_refresh_of(y, guided)
+        layer_cache = E.layer_cache_of(y, inner.num_layers)
         eng = inner._get_engine(x.device)
         eng.prepare(B, T)
         eng.set_condition(y["seed"], y["mfcc"], text=inner._text_features(y, B), cache=False)
         eng.set_guidance_interval(interval)          # at every loop; None resets a reused handle to "every timestep"
         eng.set_guidance_rescale(phi)                # likewise: an absent key sets 0 (off)
         eng.set_guidance_refresh(every)              # likewise: an absent key sets 1 (off); every loop starts with a refresh
+        eng.set_layer_cache(*layer_cache)            # likewise: an absent key sets every = 1 (off); every loop starts with a full call
         if guided:
             mode, scale = GDX_CFG, E.f32c(y["scale"].reshape(-1), "y['scale']")
         else:
@@ -573,11 +575,14 @@ class GaussianDiffusion:
 
     @staticmethod
     def _refuse_refresh(model, model_kwargs, who):
-        """A path that calls the model step by step cannot serve y['guidance_refresh'] > 1 (engine.refuse_guidance_refresh)."""
+        """A path that calls the model step by step, or whose calls are independent of one another, can serve neither
+        y['guidance_refresh'] > 1 nor y['layer_cache'] with every > 1 (engine.refuse_guidance_refresh, engine.refuse_layer_cache)."""
         from ..model.cfg_sampler import ClassifierFreeSampleModel
         y = (model_kwargs or {}).get("y")
         if isinstance(y, dict):
             E.refuse_guidance_refresh(y, isinstance(model, ClassifierFreeSampleModel), who)
+            inner = getattr(model, "model", model) if isinstance(model, ClassifierFreeSampleModel) else model
+            E.refuse_layer_cache(y, getattr(inner, "num_layers", 2**31), who)      # a foreign model: keep cannot be judged
 
     def _runs_fused(self, fused, model, denoised_fn, cond_fn):
         """The route of every sampling loop: inside libgdx for a native START_X denoiser (or its ClassifierFreeSampleModel)
@@ -692,6 +697,30 @@ class GaussianDiffusion:
                 continue
             plan.append("refresh" if n % every == 0 else "reuse")
             n += 1
+        return plan
+
+    def layer_cache_plan(self, layer_cache, guidance_interval=None, guidance_refresh=1, guided=True, mode=None, plms=False,
+                         skip_timesteps=0):
+        """What each denoiser call of a sampling loop does under y['layer_cache'] = (every, keep), in execution order: "full"
+        (every encoder layer runs and the deep layers' change is stored) or "partial" (the first keep layers run and the
+        stored change is added).  guided: the loop of a ClassifierFreeSampleModel, whose calls take the forward modes of
+        guidance_plan (a refresh call runs as GDX_CFG; an unguided and a reuse call as GDX_COND); otherwise every call runs in
+        `mode` (GDX_COND when None).  ALL calls are numbered m = 0, 1, ...; call m is full when m % every == 0 or when the
+        mode stored by the most recent full call does not cover its own (the same mode, or GDX_CFG for a GDX_COND call): the
+        rule of gdx_set_layer_cache, on the host.  The plan does not depend on keep."""
+        every, _ = E.layer_cache_of({"layer_cache": layer_cache}, 2**31)
+        if guided:
+            calls = self.guidance_plan(guidance_interval, guidance_refresh, plms=plms, skip_timesteps=skip_timesteps)
+            modes = [GDX_CFG if c == "refresh" else GDX_COND for c in calls]
+        else:
+            n = self.num_timesteps - skip_timesteps
+            modes = [GDX_COND if mode is None else mode] * (n + (1 if plms and n > 0 else 0))
+        plan, stored = [], None
+        for m, c in enumerate(modes):
+            full = m % every == 0 or not (stored == c or (stored == GDX_CFG and c == GDX_COND))
+            if full:
+                stored = c
+            plan.append("full" if full else "partial")
         return plan
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,

@@ -187,6 +187,17 @@ class Engine:
         reuse the stored cond-uncond difference in between (gdx_set_guidance_refresh); 1 = off.  Clears the stored difference."""
         _lib.check(self.lib.gdx_set_guidance_refresh(self.handle, int(every)), self.lib)
 
+    def set_layer_cache(self, every=1, keep=0):
+        """every >= 1: the in-library sampling loops run every `every`-th denoiser call in full and, in between, recompute only
+        the first `keep` encoder layers and add the stored change of the deeper ones (gdx_set_layer_cache); 1 = off, keep is
+        then not looked at.  Clears the stored change."""
+        _lib.check(self.lib.gdx_set_layer_cache(self.handle, int(every), int(keep)), self.lib)
+
+    @staticmethod
+    def layer_delta(op, inp, outc, delta):
+        """The stand-alone gdx_layer_delta (the module's layer_delta)."""
+        return layer_delta(op, inp, outc, delta)
+
     def cfg_rescale(self, c, u, scale, phi, t=None, interval=None, out=None):
         """The stand-alone gdx_cfg_rescale on [B,J,1,T] device tensors -> (out, factor [B]); t (int64 [B]) with interval (lo, hi)
         marks the guided samples (None: all); out may be c itself.  Operands are taken as they are (no copies): tests hand it
@@ -209,6 +220,12 @@ class Engine:
         """Samples pushed through the denoiser since the handle was created (gdx_forward_samples; host-side counter)."""
         n = C.c_int64()
         _lib.check(self.lib.gdx_forward_samples(self.handle, C.byref(n)), self.lib)
+        return n.value
+
+    def forward_layer_samples(self):
+        """Samples x encoder layers launched since the handle was created (gdx_forward_layer_samples; host-side counter)."""
+        n = C.c_int64()
+        _lib.check(self.lib.gdx_forward_layer_samples(self.handle, C.byref(n)), self.lib)
         return n.value
 
     # ------------------------------------------------------------------ compute
@@ -237,6 +254,7 @@ class Engine:
         return bad.value, first.value
 
     def tap(self, which, rows, d, device):
+        """which 0 .. L: the residual stream [Beff * (T + 1), d]; L + 1: the output GEMM's operand [Beff * T, d] (gdx_get_tap)."""
         out = torch.empty(rows, d, device=device, dtype=torch.float32)
         _lib.check(self.lib.gdx_get_tap(self.handle, which, _ptr(out), out.numel(), _stream(device)), self.lib)
         return out
@@ -389,6 +407,41 @@ def guidance_refresh_of(y, guided_model):
     return int(every)
 
 
+def layer_cache_of(y, num_layers):
+    """y['layer_cache'] validated -> (every, keep), two Python ints ((1, 0) when the key is absent: off).  ValueError for anything
+    but two Python ints -- a bool and a float are refused, and a tensor because reading it would synchronise --, for every < 1,
+    and, when every > 1, for keep outside 1 .. num_layers - 1.  At every = 1 keep is not looked at.  Needs no
+    ClassifierFreeSampleModel: the cache sits inside the denoiser."""
+    if "layer_cache" not in y:
+        return 1, 0
+    lc = y["layer_cache"]
+    if isinstance(lc, torch.Tensor) or (isinstance(lc, (tuple, list)) and any(isinstance(v, torch.Tensor) for v in lc)):
+        raise ValueError("y['layer_cache'] must be two Python ints (every, keep), not a tensor: reading it would synchronise")
+    ok = (isinstance(lc, (tuple, list)) and len(lc) == 2
+          and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in lc))
+    if not ok:
+        raise ValueError(f"y['layer_cache'] must be two Python ints (every, keep), got {lc!r}")
+    every, keep = int(lc[0]), int(lc[1])
+    if not 1 <= every <= 2**31 - 1:
+        raise ValueError(f"y['layer_cache'] must satisfy 1 <= every < 2**31, got {lc!r}")
+    if every == 1:
+        return 1, 0
+    if not 1 <= keep <= num_layers - 1:
+        raise ValueError(f"y['layer_cache'] must satisfy 1 <= keep <= num_layers - 1 = {num_layers - 1}, got {lc!r}")
+    return every, keep
+
+
+def refuse_layer_cache(y, num_layers, who):
+    """The layer cache needs memory across denoiser calls, which only the in-library loops have: ValueError when
+    y['layer_cache'] with every > 1 reaches `who`, a path that makes every call on its own."""
+    every, keep = layer_cache_of(y, num_layers)
+    if every > 1:
+        raise ValueError(f"y['layer_cache'] = ({every}, {keep}) needs the in-library loop (p_sample_loop, ddim_sample_loop, "
+                         f"plms_sample_loop, dpm_solver_sample_loop, dpm_solver_sde_sample_loop or unipc_sample_loop with fused=True on a "
+                         f"native model, without cond_fn / denoised_fn): {who} cannot carry the deep layers' change from one call "
+                         f"to the next")
+
+
 def refuse_guidance_refresh(y, guided_model, who):
     """The guidance refresh needs memory across denoiser calls, which only the in-library loops have: ValueError when
     y['guidance_refresh'] > 1 reaches `who`, a path that makes every call on its own."""
@@ -410,6 +463,18 @@ def cfg_delta(a, b, out=None, count=None):
     args = _lib.CfgDeltaArgs(count=a.numel() if count is None else count, a=a.data_ptr(), b=b.data_ptr(), out=out.data_ptr())
     _lib.check(lib.gdx_cfg_delta(C.byref(args), _stream(a.device)), lib)
     return out
+
+
+def layer_delta(op, inp, outc, delta):
+    """The stand-alone gdx_layer_delta on device tensors taken as they are (no copies: tests hand it misaligned views): inp
+    [B, T + 1, d], outc [B, T, d], delta [B, T, d] fp32.  op 0 (store): delta = outc - inp[:, 1:]; op 1 (apply): outc = inp[:, 1:]
+    + delta.  The element types of (inp, outc) select the pairing; the library refuses any but its three."""
+    lib = _lib.load()
+    code = {torch.float32: _lib.GDX_DTYPE_F32, torch.float16: _lib.GDX_DTYPE_F16, torch.bfloat16: _lib.GDX_DTYPE_BF16}
+    B, T, d = outc.shape
+    _lib.check(lib.gdx_layer_delta(int(op), code[inp.dtype], code[outc.dtype], B, T, d, inp.data_ptr(), outc.data_ptr(),
+                                   delta.data_ptr(), _stream(outc.device)), lib)
+    return delta if op == 0 else outc
 
 
 def sampler_update(kind, coef, x, x0_cond, out, t=None, step_index=0, x0_uncond=None, scale=None, inpaint_mask=None,

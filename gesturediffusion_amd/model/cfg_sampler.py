@@ -10,11 +10,12 @@ kernel.  Nothing is deep-copied.
 the conditional output itself.  `y['guidance_rescale'] = phi` (additive, 0 <= phi <= 1) rescales a guided output to the
 conditional output's per-sample standard deviation and mixes it with the unscaled one by phi (include/gdx.h).
 `y['guidance_refresh'] = k` (additive, int >= 1) belongs to the in-library loops, which remember the cond-uncond difference
-between guided calls; this forward has no memory and raises ValueError for k > 1.
+between guided calls; this forward has no memory and raises ValueError for k > 1, and likewise for
+`y['layer_cache'] = (every, keep)` with every > 1 (the deep encoder layers' change reused between calls).
 """
 import torch.nn as nn
 
-from ..engine import GDX_CFG, guidance_interval_of, guidance_rescale_of, refuse_guidance_refresh
+from ..engine import GDX_CFG, guidance_interval_of, guidance_rescale_of, refuse_guidance_refresh, refuse_layer_cache
 from .mdm import _NativeDenoiser
 
 
@@ -50,6 +51,7 @@ class ClassifierFreeSampleModel(nn.Module):
         interval = guidance_interval_of(y, True)
         phi = guidance_rescale_of(y, True)
         refuse_guidance_refresh(y, True, "the step-wise forward of ClassifierFreeSampleModel")
+        refuse_layer_cache(y, m.num_layers, "the step-wise forward of ClassifierFreeSampleModel")
         eng = m._get_engine(x.device)
         eng.prepare(bs, nframes)
         eng.set_condition(seed, mfcc, text=m._text_features(y, bs))

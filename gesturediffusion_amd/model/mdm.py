@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from ..engine import (GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_interval_of, guidance_rescale_of,
-                      require_device)
+                      refuse_layer_cache, require_device)
 from .rotation2xyz import Rotation2xyz
 
 ROPE_ROWS = 4096
@@ -351,6 +351,7 @@ class MDM(_NativeDenoiser):
         self._check_inputs(x, y)
         guidance_interval_of(y, False)                     # the key needs a ClassifierFreeSampleModel: ValueError here
         guidance_rescale_of(y, False)
+        refuse_layer_cache(y, self.num_layers, "the step-wise forward of MDM")
         bs, njoints, nfeats, nframes = x.shape
         force_mask = y.get("uncond", False)
         text = self._text_features(y, bs)                  # the reference reads y['text'] before y['seed'] (model/mdm.py:120)

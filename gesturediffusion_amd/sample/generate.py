@@ -54,7 +54,8 @@ def resolve_rng(rng, world):
 def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames, seed_poses, guidance_param=1.0,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
-                  guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None, text_of_chunk=None):
+                  guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None, text_of_chunk=None,
+                  layer_cache=None):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -70,7 +71,11 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     drawn but is that motion's DDIM inversion (ddim_reverse_sample_loop) under the chunk's own seed poses and MFCCs, with the
     conditional pass alone -- no guidance, whatever guidance_param says; the (guided) DDIM loop then starts from it.  With
     guidance_param == 1 the loop retraces the inversion, and report(text) is told each chunk's round-trip error.
-    text_of_chunk(c) -> text features [b, clip_dim] on the device (a use_text model): chunk c's y['text_embed']."""
+    text_of_chunk(c) -> text features [b, clip_dim] on the device (a use_text model): chunk c's y['text_embed'].
+    layer_cache (every, keep): every every-th denoiser call in full, the first keep encoder layers plus the stored change of the
+    deeper ones in between (y['layer_cache']); each chunk is its own loop and starts with a full call."""
+    if invert_of_chunk is not None and layer_cache is not None:
+        raise ValueError("invert_of_chunk runs no layer cache")
     if invert_of_chunk is not None and sampler != "ddim":
         raise ValueError("invert_of_chunk needs sampler='ddim': the latent is the start state of the deterministic DDIM loop")
     if invert_of_chunk is not None and guidance_refresh > 1:
@@ -100,6 +105,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             y["guidance_rescale"] = float(guidance_rescale)
         if guidance_refresh > 1:
             y["guidance_refresh"] = guidance_refresh
+        if layer_cache is not None:
+            y["layer_cache"] = (int(layer_cache[0]), int(layer_cache[1]))
         kw = dict(clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=0, init_image=None, progress=progress,
                   noise=None, rng=rng, philox_seed=philox_seed + 1000 * chunk, sample_offset=sample_offset,
                   noise_tape=noise_tapes[chunk] if noise_tapes is not None else None)
@@ -316,6 +323,11 @@ def main(argv=None):
     if args.guidance_refresh > 1 and rank == 0:
         plan = diffusion.guidance_plan(interval, args.guidance_refresh, plms=args.sampler == "plms")
         print(f"### unconditional pass on {plan.count('refresh')} of {len(plan) - plan.count('off')} guided calls")
+    if args.layer_cache is not None and rank == 0:
+        plan = diffusion.layer_cache_plan(args.layer_cache, interval, args.guidance_refresh, guided=args.guidance_param != 1,
+                                          plms=args.sampler == "plms")
+        print(f"### layer cache: {plan.count('full')} full, {plan.count('partial')} partial calls; "
+              f"{args.layer_cache[1]} of {args.layers} layers on a partial call")
     outs = sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, args.chunks, T, args.seed_poses,
                          guidance_param=args.guidance_param, sampler=args.sampler,
                          eta=args.dpm_eta if args.sampler == "dpmpp_sde" else args.eta, rng=rng,
@@ -323,7 +335,7 @@ def main(argv=None):
                          plms_order=args.plms_order, dpm_order=args.dpm_order, unipc_order=args.unipc_order,
                          guidance_interval=interval, guidance_rescale=args.guidance_rescale,
                          guidance_refresh=args.guidance_refresh, invert_of_chunk=invert_of_chunk, report=report,
-                         text_of_chunk=text_of_chunk)
+                         text_of_chunk=text_of_chunk, layer_cache=args.layer_cache)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

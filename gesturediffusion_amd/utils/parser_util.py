@@ -56,7 +56,16 @@ def parse_and_load_from_model(parser, argv=None):
         parser.error("--guidance_refresh needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     if args.guidance_refresh is None:
         args.guidance_refresh = 1
+    if args.layer_cache is not None:
+        every, keep = args.layer_cache
+        if every < 1:
+            parser.error("--layer_cache EVERY must be at least 1")
+        if every > 1 and not 1 <= keep <= args.layers - 1:
+            parser.error(f"--layer_cache KEEP must lie in 1 .. layers - 1 = {args.layers - 1}")
+        args.layer_cache = (every, keep) if every > 1 else None         # EVERY = 1 is off: KEEP is not looked at
     if args.invert_gt:
+        if args.layer_cache is not None:
+            parser.error("--invert_gt runs no layer cache: the inversion makes every denoiser call in full")
         if args.synthetic or args.dataset != "genea2023" or not args.data_dir:
             parser.error("--invert_gt inverts recorded motion: it needs --dataset genea2023 --data_dir D (and no --synthetic)")
         if args.sampler != "ddim":
@@ -179,6 +188,11 @@ def add_native_options(parser):
                        help="Guidance refresh: run the unconditional pass only on every K-th guided denoiser call of a chunk's "
                             "loop and reuse the stored cond-uncond difference in between (1 = every call, the default). "
                             "Every sampler; an error with --guidance_param 1 or K < 1.")
+    group.add_argument("--layer_cache", default=None, type=int, nargs=2, metavar=("EVERY", "KEEP"),
+                       help="Layer cache: run every EVERY-th denoiser call of a chunk's loop in full and store the change its "
+                            "encoder layers KEEP .. L-1 made; the calls in between recompute only the first KEEP layers and add "
+                            "the stored change (EVERY = 1: every call in full, the default). Every sampler; an error with "
+                            "EVERY < 1, KEEP outside 1 .. layers - 1, or --invert_gt.")
     group.add_argument("--invert_gt", action='store_true',
                        help="DDIM inversion of the data: each ground-truth chunk is carried up the deterministic DDIM ODE under "
                             "that chunk's conditioning with the conditional pass only (no guidance: the standard practice "

@@ -241,6 +241,59 @@ int gdx_cfg_delta(const gdx_cfg_delta_args_t* a, void* stream);
  * that an unguided step skipped the unconditional pass instead of computing and discarding it. */
 int gdx_forward_samples(gdx_handle_t h, int64_t* samples);
 
+/* Layer cache (the deep encoder layers' change reused between denoiser calls, after DeepCache, Ma et al. 2023, arXiv:2312.00858,
+ * and the transformer block-caching samplers, arXiv:2406.01125, arXiv:2312.03209; no counterpart in the reference): every
+ * `every`-th denoiser call of a loop runs in full and stores the change its layers keep .. L-1 made to the residual stream;
+ * the calls in between recompute only layers 0 .. keep-1 and add the stored change.  every = 1 (the state after gdx_create)
+ * is the behaviour without the feature: nothing new is launched and every result keeps its bits; keep is then not looked at.
+ * One rule everywhere (L = num_layers, d = latent_dim, B = batch, Beff = the samples the call runs):
+ *   Number ALL denoiser calls of a loop m = 0, 1, 2, ... in execution order: the second call of gdx_plms_loop's first step is
+ *   counted, and so are the unguided calls of a guidance interval and the reuse calls of the guidance refresh.  The call's
+ *   forward mode c_m is what the denoiser is actually run with: GDX_COND, GDX_UNCOND or GDX_CFG (a refresh call is GDX_CFG; a
+ *   refresh-reuse call and a call outside the guidance interval are GDX_COND).  K is the mode stored by the loop's most recent
+ *   full call (none at the loop's start), and covers(K, c) = (K == c) or (K == GDX_CFG and c == GDX_COND): the conditional
+ *   rows are the first B.
+ *   full call (m % every == 0, or not covers(K, c_m)): exactly the forward of every = 1, with the same bits of x0.  In
+ *     addition delta[b,t,j] = fl32(out[b,t,j] - in[b,t+1,j]) is stored for every row (b, t), 0 <= t < T, of the Beff samples
+ *     and every column j < d, where `in` is the residual stream after encoder layer keep-1 (rows [Beff, T+1, d], token 0
+ *     skipped) and `out` the operand the output GEMM reads ([Beff, T, d]).  Both are read as fp32: the fp32 buffer where the
+ *     residual stream is fp32 (the fp32 mode, and bf16 with its fp32 stream), the widened 16-bit value otherwise (fp16 `in`;
+ *     `out` in both 16-bit modes).  It sets K = c_m.
+ *   partial call (otherwise): everything up to and including layer keep-1 runs as in a full call, with this call's own
+ *     input, timestep embedding and conditioning.  Layers keep .. L-1 are not launched: no QKV GEMM, no attention, no FFN.
+ *     The output GEMM's operand is formed as xc[b,t,j] = fl32(in'[b,t+1,j] + delta[b,t,j]), rounded once more to the 16-bit
+ *     type in the 16-bit modes; a GDX_COND call under K = GDX_CFG uses rows 0 .. B-1 of delta.  The output GEMM, the
+ *     transpose, the guidance refresh, the rescale and the step kernel follow, untouched.
+ * State: delta and the buffer that holds `in` until the end of a full call belong to the handle (first use allocates them,
+ * with guard zones under gdx_set_guards; gdx_prepare resets them).  A validity flag plus the stored mode are set by a full
+ * call and cleared by gdx_prepare, gdx_set_condition, gdx_set_condition_text and gdx_set_layer_cache.  No counter lives in the
+ * handle: for block-wise issue (run_steps / k_base) the host derives every call's m, c_m and K from the whole loop's first
+ * index first_index + k_base, as it does for the guidance refresh, so issue in blocks gives the bits of one call.  A block that
+ * would begin with a partial call without a valid delta of the planned mode is refused before its first launch.
+ * It applies in gdx_sample_loop (pose-layout AND token-major paths), gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop and
+ * gdx_unipc_loop; graph replay runs a call with every > 1 eagerly.  gdx_forward, gdx_bpd_loop and gdx_ddim_reverse_loop keep
+ * every call full and never touch delta.  The encoder part of a step falls to (1 + (every-1)*keep/L) / every of itself; how far
+ * the result moves from the uncached loop depends on the model, and nothing is claimed about motion quality on a trained
+ * checkpoint.
+ * gdx_set_layer_cache: every < 1, a null handle, or every > 1 with keep outside 1 .. num_layers - 1 is refused before any HIP
+ * call. */
+int gdx_set_layer_cache(gdx_handle_t h, int32_t every, int32_t keep);
+
+/* The stand-alone pass behind both uses, one launch on `stream`.  op 0 (store) reads in and outc and writes delta; op 1 (apply)
+ * reads in and delta and writes outc.  in [batch, frames + 1, width] of in_dtype, outc [batch, frames, width] of out_dtype,
+ * delta [batch, frames, width] fp32; row (b, t) of outc and delta pairs with row (b, t + 1) of in.  (in_dtype, out_dtype) is one
+ * of (GDX_DTYPE_F32, GDX_DTYPE_F32), (GDX_DTYPE_F16, GDX_DTYPE_F16), (GDX_DTYPE_F32, GDX_DTYPE_BF16): the three the compute
+ * modes use.  There is only a 128-bit path: width % 32 != 0 or a pointer that is not 16-byte aligned is refused, like another
+ * op or pairing, a non-positive size and a null pointer, all before the first HIP call.  Nothing outside [batch, frames, width]
+ * of the written operand is touched. */
+int gdx_layer_delta(int32_t op, int32_t in_dtype, int32_t out_dtype, int32_t batch, int32_t frames, int32_t width,
+                    const void* in, void* outc, float* delta, void* stream);
+
+/* Host-side count of samples x encoder layers launched since gdx_create: every forward adds Beff * (the encoder layers it
+ * launched), num_layers on a full call and keep on a partial one.  Issues no GPU work: a test reads off it that a partial call
+ * skipped the deep layers. */
+int gdx_forward_layer_samples(gdx_handle_t h, int64_t* n);
+
 /* ---- denoiser -------------------------------------------------------------------------- */
 /* replaces MDM.forward / MDM_Old.forward / ClassifierFreeSampleModel.forward
  * (model/mdm.py:105-224, model/mdm_old.py:84-122, model/cfg_sampler.py:23-28).
@@ -252,7 +305,10 @@ int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timesteps, int32_
 
 /* Debug/parity taps: copy an internal activation to `out` (device).  which: 0 = encoder
  * input [B,T+1,d], 1..L = output of encoder layer l [B,T+1,d] (only the most recent
- * forward's last layer buffer is live unless keep_taps was set), see gdx_set_keep_taps. */
+ * forward's last layer buffer is live unless keep_taps was set), see gdx_set_keep_taps.
+ * which = L + 1 (under keep_taps): the output GEMM's operand of the most recent forward, [Beff, T, d], as fp32 (widened in
+ * the 16-bit modes), for full and partial calls of the layer cache alike.  A partial call writes taps 0 .. keep only: taps
+ * keep+1 .. L stay stale, holding an earlier forward's values. */
 int gdx_set_keep_taps(gdx_handle_t h, int32_t keep);
 int gdx_get_tap(gdx_handle_t h, int32_t which, float* out, int64_t count, void* stream);
 
