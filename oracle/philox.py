@@ -5,7 +5,8 @@ The reference has no counter-based RNG (it draws from torch's global generator,
 diffusion/gaussian_diffusion.py:532,694,773); this generator is the build's own, used for
 throughput runs so that results do not depend on how a batch is sharded.  The oracle restates
 the published Philox4x32-10 algorithm (Salmon et al., SC'11; same constants as Random123 /
-cuRAND) and is pinned by the Random123 known-answer vectors in tests/test_philox.py.
+cuRAND) and is pinned by the Random123 known-answer vectors in tests/test_philox_host.py; tests/philox_restatement.py
+evaluates the same draw with float64 log / sqrt / cos / sin, and tests/test_gpu_philox.py holds the kernel to it.
 Keying: counter = (element_group, draw_step, sample_lo32, sample_hi32), key = (seed_lo32, seed_hi32).
 """
 import numpy as np
