@@ -1,6 +1,8 @@
-// Host side shared by api.hip (the model handle, the forwards and the loops; defines the helpers declared here), weights.hip
-// (what the handle's weights are and how they get there) and testapi.hip (the handle-free test / bench entry points).
+// Host side shared by handle.hip (the model handle and its settings), forward.hip (the per-step kernel sequence), loops.hip (the
+// in-library loops), weights.hip (what the handle's weights are and how they get there) and testapi.hip (the handle-free test /
+// bench entry points); the helpers declared here are defined in the first three.
 #pragma once
+#include "gdx_call_plan.h"
 #include "gdx_internal.h"
 
 #include <set>
@@ -10,6 +12,7 @@
 namespace gdx {
 
 int fail(const std::string& m);   // records the text of gdx_last_error (thread-local); returns -1
+void clear_error();               // ... and empties it again (a fallback that recovered)
 #define HIPCHK(expr)                                                                       \
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \
@@ -82,7 +85,7 @@ struct Layer {
 };
 
 // An activation buffer of the forward, fp32 side and 16-bit side: gdx_prepare allocates the sides the compute mode uses, the
-// helpers of the per-step sequence (api.hip: linear, attend, add_norm) pick the side they read and write
+// helpers of the per-step sequence (forward.hip: linear, attend, add_norm) pick the side they read and write
 struct Act { float* f = nullptr; _Float16* h = nullptr; };
 
 // One state-dict key of the handle's configuration: the shape it must have and the device buffers it becomes.  The handle's
@@ -178,4 +181,21 @@ struct gdx_model {
 namespace gdx {
 // weights.hip: fills h->weights, the dimensions of every Packed they name and h->required from h->cfg (gdx_create)
 void describe_weights(gdx_model* h);
+
+// handle.hip
+// A zero-filled workspace buffer of the handle, with its canary zone behind it under gdx_set_guards (`who`: the entry that asks)
+int ws_alloc(gdx_model* h, const char* who, void** p, size_t bytes);
+int check_ready(gdx_model* h, const char* who);                   // handle, gdx_prepare and a conditioning, or the refusal
+int check_mode(const char* who, int mode, const float* scale);
+
+// forward.hip
+struct ForwardOpts {
+    const int* state = nullptr;   // graph replay: the row index of temb / c2t is read from device memory
+    bool tm = false;              // token-major: the pose operand is in h->xt, the prediction stays in h->x0t
+    int lc = LC_OFF;              // the call's part in the layer cache (gdx_call_plan.h)
+};
+int forward_core(gdx_model* h, const float* x, const float* temb, int tstride, const float* c2t, int mode, float* x0_out,
+                 hipStream_t s, const ForwardOpts& o = {});
+int time_embed(gdx_model* h, const int64_t* idx, int M, float* gathered, float* hidden, float* out, hipStream_t s);
+int rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s);
 }  // namespace gdx

@@ -126,7 +126,7 @@ hipError_t launch_mfcc_project(const float* mfcc, const float* W, int ldw, const
 // layer cache (gdx_layer_delta.h), fp32 stream and operand: op 0 delta = outc - in rows (b, t+1), op 1 outc = in rows + delta
 hipError_t launch_layer_delta(int op, const float* in, float* outc, float* delta, int B, int T, int d, hipStream_t s);
 
-// ---- MFCC front end pieces (mfcc.hip); the two transforms in between run on the persistent GEMM (api.hip: gdx_mfcc) ----
+// ---- MFCC front end pieces (mfcc.hip); the two transforms in between run on the persistent GEMM (mfcc.hip: gdx_mfcc) ----
 hipError_t launch_mfcc_frames(const float* x, long n, float* frames, int numframes, int frame_len, int frame_step, int ldf,
                               float preemph, hipStream_t s);
 hipError_t launch_mfcc_power(const float* spec, int lds, int im_off, float* pw, int ldp, float* energy, int numframes,
@@ -202,7 +202,7 @@ hipError_t launch_advance_state(int* st, hipStream_t s);
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
                             float* out, int B, int64_t per_sample, hipStream_t s);
 
-// argument of update_tm_kernel (sampler.hip): one step of gdx_sample_loop's token-major fast path, filled by api.hip
+// argument of update_tm_kernel (sampler.hip): one step of gdx_sample_loop's token-major fast path, filled by loops.hip
 struct UpdateTmDev {
     int kind, B, J, T, ldx, ldo;
     const float* coef; int step_index;
@@ -221,7 +221,7 @@ struct UpdateTmDev {
 };
 
 // operands of gdx_ddim_reverse_step (gdx.h), under the field names every pose-layout step struct uses: what step_begin / step_src
-// (sampler.hip) and step_args (api.hip) read.  The public entry takes them as plain arguments and fills this.
+// (sampler.hip) and step_args (loops.hip) read.  The public entry takes them as plain arguments and fills this.
 struct DdimReverseStepArgs {
     int32_t batch, njoints, frames;
     const float* coef;
@@ -236,7 +236,7 @@ struct DdimReverseStepArgs {
 
 }  // namespace gdx
 
-// the loops' (api.hip) private entries into sampler.hip; each returns 0, or -1 with the error recorded
+// the loops' (loops.hip) private entries into sampler.hip; each returns 0, or -1 with the error recorded
 // the update of a captured step: schedule index / step number read from `state` (UpdateDev::state)
 int gdx_sampler_update_state_(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
 // one step of the token-major fast path of gdx_sample_loop (update_tm_kernel); checks the layout arguments of `d`
@@ -246,5 +246,5 @@ int gdx_ddim_reverse_step_(const gdx::DdimReverseStepArgs& a, void* stream);
 // gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
 int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
                 uint32_t step, float* z_out, float* xt_out, void* stream);
-// records the text of gdx_last_error and returns -1 (api.hip), for the files that do not include gdx_host.h
+// records the text of gdx_last_error and returns -1 (handle.hip), for the files that do not include gdx_host.h
 extern "C" int gdx_set_error_(const char* msg);

@@ -35,7 +35,7 @@
 //     BM = 80 turns M = 12 608 into 158 row tiles; with BN = 128 (N = 1024) or 64 (N = 512) that is 1 264 tiles
 //     = 4.94 per CU (98.8 % balance).  Tiles are walked lid, lid+G, ... in an XCD-aware order (the column tiles of
 //     one row panel run on one XCD and share its L2).
-// Contract with the caller (api.hip): A and C have at least ROW_PAD (gdx_internal.h) readable / writable rows beyond M
+// Contract with the caller (handle.hip: gdx_prepare; mfcc.hip: gdx_mfcc): A and C have at least ROW_PAD (gdx_internal.h) readable / writable rows beyond M
 // (workspace padding): the last row tile reads whole tiles and, in the plain / residual epilogues, stores whole tiles
 // (its surplus rows are garbage that nothing consumes; ROW_PAD >= the tallest tile is a static_assert in launch_cfg).
 // The general epilogue (boundary linears: token-row map, R, V) moves rows, so it guards every access with m < M.

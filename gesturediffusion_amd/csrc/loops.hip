@@ -1,0 +1,501 @@
+// libgdx.so host side: the in-library sampling loops (diffusion/gaussian_diffusion.py:598-730, 879-993 and the multistep solvers).
+// What each denoiser call of a loop does is planned once per entry-point call (gdx_call_plan.h); the loops index the plan by
+// position.  C ABI in include/gdx.h; the handle is in handle.hip, forward_core in forward.hip, the step kernels in sampler.hip.
+#include "gdx_host.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+using namespace gdx;
+
+static_assert(MODE_COND == GDX_COND && MODE_UNCOND == GDX_UNCOND && MODE_CFG == GDX_CFG, "gdx_call_plan.h restates gdx.h's modes");
+
+static PlanRule plan_rule(const gdx_model* h) { return {h->guide_lo, h->guide_hi, h->guide_every, h->lc_every}; }
+
+// The plan of the loop that block a (steps first_index .. last_idx) of entry `who` belongs to, and the refusals a block can meet
+// there, all before the call's first launch: a numbering that needs a first index outside the schedule; a first guided call that
+// would reuse a difference nobody stored; a first call that is partial while the stored change is missing or of another mode
+// than the plan's.
+template <typename A>
+static int plan_block(const gdx_model* h, const char* who, const A* a, int last_idx, bool two_calls, CallPlan* p) {
+    const CallSeq q{a->mode, a->timestep_map, a->num_steps, a->first_index, a->k_base, last_idx, two_calls};
+    if (!plan_loop(plan_rule(h), q, p)) return fail(std::string(who) + ": bad step range");
+    if (p->begins_with_reuse() && !h->gd_valid)
+        return fail(std::string(who) + ": a guided call would reuse the guidance difference, but none is stored: a block-wise "
+                    "call (run_steps / k_base) must continue the loop that stored the difference");
+    const PlannedCall& e = p->step(a->k_base);
+    if (e.lc == LC_PARTIAL && !(h->lc_valid && h->lc_mode == e.K))
+        return fail(std::string(who) + ": a partial call would add the stored change of the deep layers, but none of the planned mode "
+                    "is stored: a block-wise call (run_steps / k_base) must continue the loop that stored the change");
+    return 0;
+}
+
+// What the step kernel of a loop step in mode m gets as (x0_uncond, scale) after denoise_step left the prediction in h->x0.
+// Guided without rescale: the uncond half and the scales, the kernel blends.  Guided with the handle's phi > 0: the rescaled
+// guided prediction is formed here, in place on the cond half, and the kernel is called like on an unguided step (NULL, NULL).
+// Under the guidance refresh (m = MODE_CFG_REFRESH / MODE_CFG_REUSE) the difference is stored or applied first (gdx_cfg_delta on
+// the handle's buffer), and the step then continues as a guided one with (c, u or u', scale).  Every in-library loop asks here.
+static int guided_operands(gdx_model* h, int m, const float* scale, hipStream_t s, const float** x0_uncond, const float** sc) {
+    *x0_uncond = nullptr; *sc = nullptr;
+    if (m < GDX_CFG) return 0;
+    const size_t n = (size_t)h->B * h->J * h->T;
+    float* u = h->x0 + n;
+    if (m != GDX_CFG) {
+        // guidance refresh: a refresh stores d = c - u; a reuse, whose forward left only c, forms u' = c - d in u's place
+        if (!h->gd) {
+            if (ws_alloc(h, "guidance refresh", (void**)&h->gd, sizeof(float) * n)) return -1;
+            HIPCHK(hipStreamSynchronize(nullptr));                 // the fill is on the null stream, the first store on s
+        }
+        const bool store = m == MODE_CFG_REFRESH;
+        const gdx_cfg_delta_args_t g{(int64_t)n, h->x0, store ? u : h->gd, store ? h->gd : u};
+        if (gdx_cfg_delta(&g, (void*)s)) return -1;
+        if (store) h->gd_valid = true;
+    }
+    if (h->guide_phi > 0.0f) return rescale_x0(h, h->x0, u, scale, nullptr, h->x0, s);
+    *x0_uncond = u; *sc = scale;
+    return 0;
+}
+
+// timestep-embedding table (and, V2, its W_coa image) for every kept step of a loop, shared by gdx_sample_loop and gdx_bpd_loop
+static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timestep_map, hipStream_t s) {
+    const int d = h->d;
+    // timestep-embedding table for every kept step, once per loop (same t for the whole batch:
+    // gaussian_diffusion.py:712), through the respacing map (respace.py:124-129)
+    if (h->temb_table_rows < num_steps) {
+        float* t3 = nullptr;
+        // + GDX_ROW_PAD rows behind the last of the three tables: the table linears run on the persistent GEMM, which
+        // reads / stores whole tiles
+        if (dev_alloc(h->ws_allocs, (void**)&t3, sizeof(float) * (3 * (size_t)num_steps + GDX_ROW_PAD) * d)) return -1;
+        HIPCHK(hipMemsetAsync(t3, 0, sizeof(float) * (3 * (size_t)num_steps + GDX_ROW_PAD) * d, s));
+        if (h->cfg.arch == GDX_ARCH_MDM && dev_alloc(h->ws_allocs, (void**)&h->c2t_table, sizeof(float) * ((size_t)num_steps + GDX_ROW_PAD) * d))
+            return -1;
+        if (dev_alloc(h->ws_allocs, (void**)&h->tmap_dev, sizeof(int64_t) * num_steps)) return -1;
+        h->temb_table = t3;
+        h->temb_table_rows = num_steps;
+        h->tables_valid = false; h->c2t_valid = false;
+    }
+    float* table = h->temb_table;
+    // the tables depend on the weights and the timestep map only: a loop run in blocks (run_steps) builds them once
+    const bool tables_live = h->tables_valid && (int)h->tmap_host.size() == num_steps &&
+                             !memcmp(h->tmap_host.data(), timestep_map, sizeof(int64_t) * num_steps) &&
+                             (h->cfg.arch != GDX_ARCH_MDM || h->c2t_valid);
+    if (tables_live) return 0;
+    h->tmap_host.assign(timestep_map, timestep_map + num_steps);
+    HIPCHK(hipMemcpyAsync(h->tmap_dev, h->tmap_host.data(), sizeof(int64_t) * num_steps, hipMemcpyHostToDevice, s));
+    float* scratch0 = table + (size_t)h->temb_table_rows * d;
+    float* scratch1 = scratch0 + (size_t)h->temb_table_rows * d;
+    if (time_embed(h, h->tmap_dev, num_steps, scratch0, scratch1, table, s)) return -1;
+    if (h->cfg.arch == GDX_ARCH_MDM) {
+        // timestep half of the coarse slice of project_to_lat for every kept step, once per loop (same kernel as
+        // gdx_forward's per-sample rows)
+        HIPCHK(launch_small_linear(table, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2t_table, d, num_steps, d, d, 0, s));
+        h->c2t_valid = true;
+    }
+    h->tables_valid = true;
+    return 0;
+}
+
+// The planned call e of a loop, at its schedule index of the tables build_step_tables left: x0_out (pose layout) from the state x;
+// tm: the token-major variant (x / x0_out unused); state: a captured step, which reads its row number from the device (e.idx = 0)
+static int denoise_step(gdx_model* h, const float* x, const PlannedCall& e, float* x0_out, hipStream_t s, const int* state = nullptr,
+                        bool tm = false) {
+    const size_t row = (size_t)e.idx * h->d;
+    return forward_core(h, x, h->temb_table + row, 0, h->c2t_table ? h->c2t_table + row : nullptr, forward_mode(e.mode), x0_out, s,
+                        {.state = state, .tm = tm, .lc = e.lc});
+}
+
+// Executed step k's slice of a noise tape that starts at step k_base and holds `rows` samples ([rows][per]) per step
+static const float* tape_slice(const float* tape, int k, int k_base, size_t rows, size_t per) {
+    return tape ? tape + (ptrdiff_t)(k - k_base) * (ptrdiff_t)(rows * per) : nullptr;
+}
+
+// One forward of a loop on the state x as its plan has it (e), and the step kernel's view of its output in h->x0:
+// (x0_uncond, scale).  Every in-library loop's eager step asks here; sc_in: the loop's scales.
+static int denoise_guided(gdx_model* h, const PlannedCall& e, const float* sc_in, const float* x, hipStream_t s,
+                          const float** x0_uncond, const float** scale) {
+    return denoise_step(h, x, e, h->x0, s) || guided_operands(h, e.mode, sc_in, s, x0_uncond, scale) ? -1 : 0;
+}
+
+// calc_bpd_loop (gaussian_diffusion.py:1537-1592): per step q_sample -> denoiser -> fused bound terms, through the SAME forward
+// entry (pose-layout x_t, forward_core) the step-wise protocol reaches via gdx_forward, so both give the same bits.
+extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* stream) {
+    if (!h) return fail("gdx_bpd_loop: null handle");
+    if (!a) return fail("gdx_bpd_loop: null argument");
+    if (check_ready(h, "gdx_bpd_loop")) return -1;
+    if (!a->coef || !a->timestep_map || !a->x_start || !a->vb || !a->xstart_mse || !a->mse)
+        return fail("gdx_bpd_loop: null argument");
+    if (check_mode("gdx_bpd_loop", a->mode, a->scale)) return -1;
+    if (a->num_steps <= 0 || a->k_base < 0 || a->k_base >= a->num_steps || a->run_steps < 0 || a->k_base + a->run_steps > a->num_steps)
+        return fail("gdx_bpd_loop: bad step range");
+    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_bpd_loop: mask without motion");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B;
+    const size_t per = (size_t)h->J * h->T;
+    const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
+    if (!h->bpd_xt && dev_alloc(h->ws_allocs, (void**)&h->bpd_xt, sizeof(float) * B * per)) return -1;
+    if (!h->bpd_part && dev_alloc(h->ws_allocs, (void**)&h->bpd_part, sizeof(float) * 4 * B * chunks)) return -1;
+    if (!a->noise_tape && !h->bpd_z && dev_alloc(h->ws_allocs, (void**)&h->bpd_z, sizeof(float) * B * per)) return -1;
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    gdx_bpd_args_t u;
+    memset(&u, 0, sizeof(u));
+    u.batch = B; u.njoints = h->J; u.frames = h->T;
+    u.coef = a->coef; u.x_start = a->x_start; u.x_t = h->bpd_xt;
+    u.x0_cond = h->x0;
+    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
+    u.clip_denoised = a->clip_denoised;
+    u.vb = a->vb; u.xstart_mse = a->xstart_mse; u.mse = a->mse; u.ld = a->num_steps;
+    u.workspace = h->bpd_part;
+    const int k_end = a->run_steps > 0 ? a->k_base + a->run_steps : a->num_steps;
+    // no guidance refresh here: the steps draw independent x_t, so every guided call is a full one
+    const CallPlan plan = plan_unnumbered(plan_rule(h), a->mode, a->timestep_map, a->num_steps - 1 - a->k_base, k_end - a->k_base, -1);
+    for (int k = a->k_base; k < k_end; ++k) {
+        const int idx = a->num_steps - 1 - k;
+        if (a->noise_tape) {
+            u.noise = tape_slice(a->noise_tape, k, a->k_base, B, per);
+            if (gdx_q_sample(a->x_start, u.noise, a->coef, idx, (int64_t)(B * per), h->bpd_xt, stream)) return -1;
+        } else {
+            u.noise = h->bpd_z;
+            if (gdx_bpd_xt_(a->x_start, a->coef, idx, B, (long)per, a->philox_seed, a->sample_offset, (uint32_t)k, h->bpd_z, h->bpd_xt,
+                            stream))
+                return -1;
+        }
+        if (denoise_guided(h, plan.calls[k - a->k_base], a->scale, h->bpd_xt, s, &u.x0_uncond, &u.scale)) return -1;
+        u.step_index = idx; u.col = k;
+        if (gdx_bpd_terms(&u, stream)) return -1;
+    }
+    if (a->prior_bpd) {
+        u.prior = 1; u.prior_log_variance = a->prior_log_variance; u.step_index = a->num_steps - 1;
+        u.vb = a->prior_bpd; u.ld = 1; u.col = 0;
+        if (gdx_bpd_terms(&u, stream)) return -1;
+    }
+    return 0;
+}
+
+// The arguments U of a loop's step kernel at index idx, as far as every pose-layout step struct names them alike: the handle's
+// shape, the loop's coefficients / state (updated in place) / inpainting / clip, and the denoiser's output as denoise_guided left it
+template <typename U, typename A>
+static U step_args(const gdx_model* h, const A* a, int idx, const float* x0_uncond, const float* scale) {
+    U u;
+    memset(&u, 0, sizeof(u));
+    u.batch = h->B; u.njoints = h->J; u.frames = h->T;
+    u.coef = a->coef; u.step_index = idx; u.x = a->x; u.out = a->x;
+    u.x0_cond = h->x0; u.x0_uncond = x0_uncond; u.scale = scale;
+    u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion; u.clip_denoised = a->clip_denoised;
+    return u;
+}
+
+// The scaffold of the multistep loops gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop and gdx_unipc_loop (`who`), whose argument
+// structs A name the fields mode .. k_base alike: per step the denoiser through forward_core on the pose-layout state (the entry
+// gdx_forward uses: same bits as the step-wise protocol), then step(idx, k, x0_uncond, scale, slot, plan), the entry's own fused
+// launch; slot(k) = executed step k's place in the caller's ring of `ring` buffers (0: a->order of them) at a->*hist; two_calls: step 0
+// makes a second denoiser call (plan.second_call(); the entry's step issues it).  No graph replay and no token-major variant:
+// these solvers run 10-50 steps.  The argument checks need no handle and come first (then null handle, then not prepared), so
+// every refusal precedes the first HIP call; missing() gives the entry's history refusal or nullptr.  A new multistep sampler
+// is one more caller of this function ("Where a new in-library loop goes").
+template <typename A, typename Missing, typename Step>
+static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_lo, int order_hi, const char* order_msg,
+                          float* A::*hist, Missing missing, hipStream_t s, Step step, bool two_calls = false, int ring = 0) {
+    const std::string w = std::string(who) + ": ";
+    if (!a || !a->coef || !a->timestep_map || !a->x) return fail(w + "null argument");
+    if (check_mode(who, a->mode, a->scale)) return -1;
+    if (a->num_steps <= 0 || a->first_index < 0 || a->k_base < 0 || a->run_steps < 0 || a->first_index + a->k_base >= a->num_steps ||
+        a->run_steps > a->first_index + 1)
+        return fail(w + "bad step range");
+    if (a->order < order_lo || a->order > order_hi) return fail(w + order_msg);
+    if (a->inpaint_mask && !a->inpaint_motion) return fail(w + "mask without motion");
+    if (const char* m = missing()) return fail(w + m);
+    if (check_ready(h, who)) return -1;
+    if (h->B > 65535) return fail(w + "batch exceeds 65535");
+    const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
+    CallPlan plan;
+    if (plan_block(h, who, a, last_idx, two_calls, &plan)) return -1;
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    const size_t n = (size_t)h->B * h->J * h->T;
+    const int depth = ring > 0 ? ring : a->order;
+    auto slot = [&](int k) { return a->*hist + (size_t)(k % depth) * n; };
+    int k = a->k_base;
+    for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
+        const float *x0u, *sc;
+        if (denoise_guided(h, plan.step(k), a->scale, a->x, s, &x0u, &sc) || step(idx, k, x0u, sc, slot, plan)) return -1;
+    }
+    return 0;
+}
+
+// plms_sample_loop (gaussian_diffusion.py:995-1190): one fused plms_step_kernel launch per step (sampler.hip); the first step
+// needs the state in the reference layout twice.
+extern "C" int gdx_plms_loop(gdx_handle_t h, const gdx_plms_loop_args_t* a, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    return multistep_loop(
+        "gdx_plms_loop", h, a, 2, 4, "order must be 2, 3 or 4", &gdx_plms_loop_args_t::eps_hist,
+        [&] { return !a->eps_hist || !a->scratch ? "missing history (eps_hist and scratch are the caller's)" : nullptr; }, s,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot, const CallPlan& plan) -> int {
+            auto u = step_args<gdx_plms_step_args_t>(h, a, idx, x0u, sc);
+            if (k == 0) {                               // pseudo improved Euler (:1043-1052): predictor, second forward, corrector
+                u.kind = 6; u.eps_out = slot(0); u.out = a->scratch; u.pred_xstart = slot(1);
+                if (gdx_plms_step(&u, stream)) return -1;
+                const int idx2 = (idx - 1 + a->num_steps) % a->num_steps;
+                if (denoise_guided(h, plan.second_call(), a->scale, a->scratch, s, &u.x0_uncond, &u.scale)) return -1;
+                u.kind = 5; u.step_index_eps = idx2; u.x_eps = a->scratch; u.eps_hist[0] = slot(0); u.pred_prev = slot(1);
+                u.eps_out = nullptr; u.out = a->x; u.pred_xstart = nullptr;
+                return gdx_plms_step(&u, stream);
+            }
+            u.kind = k + 1 < a->order ? k + 1 : a->order;
+            u.eps_out = slot(k);
+            for (int j = 0; j < u.kind - 1; ++j) u.eps_hist[j] = slot(k - 1 - j);
+            return gdx_plms_step(&u, stream);
+        },
+        true);
+}
+
+// dpm_solver_sample_loop (DPM-Solver++ multistep, gdx.h): one fused dpm_step_kernel launch per step (sampler.hip)
+extern "C" int gdx_dpm_loop(gdx_handle_t h, const gdx_dpm_loop_args_t* a, void* stream) {
+    return multistep_loop(
+        "gdx_dpm_loop", h, a, 1, 3, "order must be 1, 2 or 3", &gdx_dpm_loop_args_t::hist,
+        [&] { return a->order > 1 && !a->hist ? "missing history (hist is the caller's)" : nullptr; }, (hipStream_t)stream,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot, const CallPlan& plan) -> int {
+            auto u = step_args<gdx_dpm_step_args_t>(h, a, idx, x0u, sc);
+            u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, lower order at the end
+            for (int j = 0; j < u.order - 1; ++j) u.hist[j] = slot(k - 1 - j);
+            u.pred_out = a->order > 1 ? slot(k) : nullptr;
+            return gdx_dpm_step(&u, stream);
+        });
+}
+
+// dpm_solver_sde_sample_loop (SDE-DPM-Solver++ multistep, gdx.h): gdx_dpm_loop with the noisy instantiation of dpm_step_kernel,
+// whose noise is slice k - k_base of the tape or Philox draw k + 1
+extern "C" int gdx_dpm_sde_loop(gdx_handle_t h, const gdx_dpm_sde_loop_args_t* a, void* stream) {
+    return multistep_loop(
+        "gdx_dpm_sde_loop", h, a, 1, 2, "order must be 1 or 2", &gdx_dpm_sde_loop_args_t::hist,
+        [&] { return a->order > 1 && !a->hist ? "missing history (hist is the caller's)" : nullptr; }, (hipStream_t)stream,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot, const CallPlan& plan) -> int {
+            auto u = step_args<gdx_dpm_sde_step_args_t>(h, a, idx, x0u, sc);
+            u.order = std::min(a->order, std::min(k + 1, idx + 1));      // warm-up at the start, first order on the step to sigma = 0
+            u.hist[0] = u.order > 1 ? slot(k - 1) : nullptr;
+            u.pred_out = a->order > 1 ? slot(k) : nullptr;
+            u.noise = tape_slice(a->noise_tape, k, a->k_base, h->B, (size_t)h->J * h->T);
+            u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset; u.rng_step = (uint32_t)(k + 1);
+            return gdx_dpm_sde_step(&u, stream);
+        });
+}
+
+// unipc_sample_loop (UniPC, gdx.h): one fused unipc_step_kernel launch per step (sampler.hip) -- the corrector of the step that
+// led to a->x, then the predictor of the next input; a->base holds the corrected state, the ring is one deeper than the order
+extern "C" int gdx_unipc_loop(gdx_handle_t h, const gdx_unipc_loop_args_t* a, void* stream) {
+    return multistep_loop(
+        "gdx_unipc_loop", h, a, 1, 3, "order must be 1, 2 or 3", &gdx_unipc_loop_args_t::hist,
+        [&] { return !a->hist || !a->base || !a->coef_c ? "missing history (hist, base and coef_c are the caller's)" : nullptr; },
+        (hipStream_t)stream,
+        [&](int idx, int k, const float* x0u, const float* sc, auto slot, const CallPlan& plan) -> int {
+            auto u = step_args<gdx_unipc_step_args_t>(h, a, idx, x0u, sc);
+            u.corr_order = k == 0 || idx == 0 ? 0 : std::min(a->order, k);
+            u.pred_order = std::min(a->order, std::min(k + 1, idx + 1));
+            if (u.corr_order) u.x = a->base;                              // else the state itself: a->x
+            u.coef_c = a->coef_c; u.base_out = a->base;
+            for (int j = 0; j < std::max(u.corr_order, u.pred_order - 1); ++j) u.hist[j] = slot(k - 1 - j);
+            u.pred_out = slot(k);
+            return gdx_unipc_step(&u, stream);
+        },
+        false, a ? a->order + 1 : 0);
+}
+
+// ddim_reverse_sample_loop (DDIM inversion, gdx.h): multistep_loop's per-step pair -- denoise_guided on the pose-layout state, then
+// one fused launch (ddim_reverse_step_kernel, sampler.hip) with step_args -- over ASCENDING indices.  An ascending twin and not a
+// direction flag on multistep_loop: nothing else of that function applies here (no order, no history ring, no k_base, no second
+// call, no refusal of plan_block), and its step range and CallSeq are both written for first_index counting down.  The
+// plan is the unnumbered one, as in gdx_bpd_loop: the stored difference's numbering is defined for descending loops.
+extern "C" int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_steps, int32_t first_index, int32_t run_steps,
+                                     const float* coef, const int64_t* timestep_map, float* x, const float* scale,
+                                     const uint8_t* inpaint_mask, const float* inpaint_motion, int32_t clip_denoised, void* stream) {
+    const char* who = "gdx_ddim_reverse_loop";
+    const std::string w = std::string(who) + ": ";
+    if (!coef || !timestep_map || !x) return fail(w + "null argument");
+    if (check_mode(who, mode, scale)) return -1;
+    if (num_steps <= 0 || first_index < 0 || first_index >= num_steps || run_steps < 1 || run_steps > num_steps - first_index)
+        return fail(w + "bad step range");
+    if (inpaint_mask && !inpaint_motion) return fail(w + "mask without motion");
+    if (check_ready(h, who)) return -1;
+    if (h->B > 65535) return fail(w + "batch exceeds 65535");
+    if (h->guide_every > 1)
+        return fail(w + "the guidance refresh (gdx_set_guidance_refresh, every > 1) does not apply to the inversion: its numbering of "
+                        "guided calls is defined for descending loops; set every = 1");
+    hipStream_t s = (hipStream_t)stream;
+    if (build_step_tables(h, num_steps, timestep_map, s)) return -1;
+    const CallPlan plan = plan_unnumbered(plan_rule(h), mode, timestep_map, first_index, run_steps, +1);
+    // the loop's operands under the names step_args reads
+    const struct { const float* coef; float* x; const uint8_t* inpaint_mask; const float* inpaint_motion; int32_t clip_denoised; }
+        a{coef, x, inpaint_mask, inpaint_motion, clip_denoised};
+    for (int idx = first_index; idx < first_index + run_steps; ++idx) {
+        const float *x0u, *sc;
+        if (denoise_guided(h, plan.calls[idx - first_index], scale, x, s, &x0u, &sc)) return -1;
+        if (gdx_ddim_reverse_step_(step_args<gdx::DdimReverseStepArgs>(h, &a, idx, x0u, sc), stream)) return -1;
+    }
+    return 0;
+}
+
+extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
+    if (check_ready(h, "gdx_sample_loop")) return -1;
+    if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");
+    if (check_mode("gdx_sample_loop", a->mode, a->scale)) return -1;
+    if (a->num_steps <= 0 || a->first_index >= a->num_steps || a->first_index < 0 || a->run_steps < 0 || a->k_base < 0)
+        return fail("gdx_sample_loop: bad step range");
+    if (a->kind == GDX_SAMPLER_DDIM && (a->const_noise || a->n_dump))
+        return fail("gdx_sample_loop: ddim_sample_loop supports neither const_noise nor dump_steps");  // :903-906
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B;
+    const int last_idx = a->run_steps > 0 && a->run_steps <= a->first_index ? a->first_index - a->run_steps + 1 : 0;
+    CallPlan plan;
+    if (plan_block(h, "gdx_sample_loop", a, last_idx, false, &plan)) return -1;
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+
+    const int64_t per = (int64_t)h->J * h->T;
+    const size_t tape_rows = a->const_noise ? 1 : B;             // samples per step of the noise tape
+    int dump_i = 0;
+    while (dump_i < a->n_dump && a->dump_steps[dump_i] < a->k_base) ++dump_i;     // entries of earlier blocks
+    // (x0_uncond, scale): guided_operands' answer for the step
+    auto fill_update = [&](gdx_update_args_t& u, int idx, int k, const float* x0_uncond, const float* scale) {
+        u = step_args<gdx_update_args_t>(h, a, idx, x0_uncond, scale);
+        u.kind = a->kind;
+        u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
+        u.const_noise = a->const_noise;
+        u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset; u.rng_step = (uint32_t)(k + 1);
+    };
+    auto eager_step = [&](int idx, int k) -> int {
+        const float *x0u, *sc;
+        if (denoise_guided(h, plan.step(k), a->scale, a->x, s, &x0u, &sc)) return -1;
+        gdx_update_args_t u;
+        fill_update(u, idx, k, x0u, sc);
+        if (gdx_sampler_update(&u, stream)) return -1;
+        while (a->dump && dump_i < a->n_dump && a->dump_steps[dump_i] <= k) {      // duplicates / stale entries never stall
+            if (a->dump_steps[dump_i] == k)
+                HIPCHK(hipMemcpyAsync(a->dump + (size_t)dump_i * B * per, a->x, sizeof(float) * B * per,
+                                      hipMemcpyDeviceToDevice, s));
+            ++dump_i;
+        }
+        return 0;
+    };
+
+    // Optional hipGraph replay of the step (gdx_set_graph_replay): ONE step is captured and replayed; everything that
+    // changes from step to step (timestep-embedding row, coefficient row, Philox draw number, noise-tape slice) is read
+    // from a two-int device state that a one-thread kernel advances at the end of the step.  Measured on MI355X /
+    // ROCm 7.2 (tools/small_loop.py, 1000 steps, B=4 T=60 d=512 fp16): eager 0.307 ms/step, graph replay 0.337 -- the
+    // ~65 small kernels of a step are bound by their GPU-side dispatch + ramp, not by host launch time, and a graph
+    // node costs slightly more than a stream launch; so it is OFF by default and kept as a switch.
+    // guidance interval: the modes this call's steps take (all the loop's own mode unless it is GDX_CFG)
+    const int mode0 = plan.step(a->k_base).mode;
+    bool uniform = true, any_guided = false;
+    for (int k = plan.k_base; k < plan.k_end; ++k) {
+        const int m = plan.step(k).mode;
+        uniform = uniform && m == mode0;
+        any_guided = any_guided || m >= GDX_CFG;
+    }
+    // Token-major fast path (sampler.hip, update_tm_kernel): with nothing but the noise tape living in the reference layout
+    // (no inpainting, no dumps; the tape is read in place), the state stays in the input GEMM's operand layout for the whole
+    // call -- one transpose in front, none per step (2 launches and ~40 MB per step less), the last update also writes the
+    // sample in the reference layout.  Bit-identical to the general path (tests: fused Philox loop == step-wise Philox loop).
+    // the guidance rescale has no token-major variant: a call that rescales a step takes the general path; nor has the guidance
+    // refresh, whose calls also run eagerly under graph replay (the stored difference is host-tracked state)
+    const bool rescales = h->guide_phi > 0.0f && any_guided;
+    const bool refreshes = h->guide_every > 1 && any_guided;
+    if (!((uintptr_t)a->noise_tape & 15) && !a->inpaint_mask && !a->n_dump && !h->graph_replay && !h->keep_taps && h->T % 4 == 0 &&
+        !rescales && !refreshes) {
+        // guided loop: the state holds both halves (the same x feeds both passes).  An unguided step reads and writes the cond
+        // half and mirrors into the uncond half only when the NEXT step of this call is guided (every call transposes the
+        // state in afresh); a call without a guided step keeps one half, like a loop that is not guided at all.
+        // GDX_TM_MIRROR=always mirrors on every unguided step of such a call (the A/B of DESIGN 4f).
+        static const bool mirror_always = [] { const char* e = getenv("GDX_TM_MIRROR"); return e && !strcmp(e, "always"); }();
+        const int Beff = any_guided ? 2 * B : B;
+        // half modes: the fp32 state keeps the half operand's row stride, and the update kernel also writes that operand
+        const int ldx = h->f16 ? h->in_x.kpad16 : h->in_x.kpad;
+        HIPCHK(launch_transpose_in(a->x, h->xt.f, Beff, B, h->J, h->T, ldx, s));
+        if (h->f16) HIPCHK(HFN(h->bf16, launch_transpose_in_f16, a->x, h->xt.h, Beff, B, h->J, h->T, ldx, s));
+        gdx::UpdateTmDev u;
+        memset(&u, 0, sizeof(u));
+        u.kind = a->kind; u.B = B; u.J = h->J; u.T = h->T; u.ldx = ldx; u.ldo = h->ldo;
+        u.coef = a->coef; u.xt = h->xt.f; u.x0t = h->x0t;
+        u.const_noise = a->const_noise; u.seed = a->philox_seed; u.sample_offset = a->sample_offset;
+        u.clip = a->clip_denoised;
+        u.xt16 = h->xt.h; u.half_dtype = h->cfg.compute_dtype;
+        int k = a->k_base;
+        for (int idx = a->first_index; idx >= last_idx; --idx, ++k) {
+            const int m = plan.step(k).mode;
+            if (denoise_step(h, nullptr, plan.step(k), nullptr, s, nullptr, true)) return -1;
+            u.scale = m == GDX_CFG ? a->scale : nullptr;
+            u.mirror = any_guided && m != GDX_CFG && (mirror_always || (idx > last_idx && plan.step(k + 1).mode == GDX_CFG));
+            u.step_index = idx; u.rng_step = (uint32_t)(k + 1);
+            u.out_pose = idx == last_idx ? a->x : nullptr;
+            u.noise = tape_slice(a->noise_tape, k, a->k_base, tape_rows, per);
+            if (gdx_sampler_update_tm_(u, stream)) return -1;
+        }
+        return 0;
+    }
+    // the graph is ONE captured step: only a call whose steps all take the same mode can replay it
+    const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8 && uniform && !refreshes &&
+                            h->lc_every == 1;                     // the layer cache's calls differ from one another: eager
+    int idx = a->first_index, k = a->k_base;
+    if (want_graph) {
+        if (eager_step(idx, k)) return -1;                        // step 0 eagerly: it also sets every kernel attribute
+        --idx; ++k;
+        bool ok = true;
+        if (!h->gstream) {
+            ok = hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking) == hipSuccess &&
+                 hipEventCreateWithFlags(&h->gev_in, hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&h->gev_out, hipEventDisableTiming) == hipSuccess &&
+                 hipMalloc((void**)&h->gstate, 64) == hipSuccess;
+            if (!ok) { (void)hipGetLastError(); }
+        }
+        if (ok && h->gexec) {                                     // the previous loop's graph: its launches must have drained
+            (void)hipStreamSynchronize(h->gstream);
+            (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr;
+            (void)hipGraphDestroy(h->ggraph); h->ggraph = nullptr;
+        }
+        if (ok) {
+            ok = launch_set_state(h->gstate, idx, k, s) == hipSuccess && hipEventRecord(h->gev_in, s) == hipSuccess &&
+                 hipStreamWaitEvent(h->gstream, h->gev_in, 0) == hipSuccess;
+        }
+        if (ok && hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const int64_t counted = h->forward_samples;          // the capture enqueues no forward: the replays are counted
+            int rc = denoise_step(h, a->x, PlannedCall{0, mode0}, h->x0, h->gstream, h->gstate);
+            h->forward_samples = counted;
+            const float *x0u = nullptr, *sc = nullptr;           // the rescale's launches depend on no per-step state: captured as they are
+            if (!rc) rc = guided_operands(h, mode0, a->scale, h->gstream, &x0u, &sc);
+            if (!rc) {
+                gdx_update_args_t u;
+                fill_update(u, 0, 0, x0u, sc);                    // noise: step 0's slice; the kernel adds state[1] * stride
+                rc = gdx_sampler_update_state_(&u, h->gstate, (long)(tape_rows * per), (void*)h->gstream);
+            }
+            if (!rc && launch_advance_state(h->gstate, h->gstream) != hipSuccess) rc = -1;
+            hipGraph_t g = nullptr;
+            const hipError_t ee = hipStreamEndCapture(h->gstream, &g);
+            if (rc || ee != hipSuccess || !g) {
+                if (g) (void)hipGraphDestroy(g);
+                (void)hipGetLastError();
+                ok = false;
+            } else if (hipGraphInstantiate(&h->gexec, g, nullptr, nullptr, 0) != hipSuccess) {
+                (void)hipGraphDestroy(g);
+                (void)hipGetLastError();
+                h->gexec = nullptr;
+                ok = false;
+            } else {
+                h->ggraph = g;
+            }
+        } else {
+            ok = false;
+            (void)hipGetLastError();
+        }
+        if (ok) {
+            for (; idx >= last_idx; --idx, ++k) {
+                HIPCHK(hipGraphLaunch(h->gexec, h->gstream));
+                h->forward_samples += mode0 == GDX_CFG ? 2 * B : B;
+            }
+            HIPCHK(hipEventRecord(h->gev_out, h->gstream));
+            HIPCHK(hipStreamWaitEvent(s, h->gev_out, 0));
+            return 0;
+        }
+        clear_error();                                          // capture unavailable: finish the loop eagerly
+    }
+    for (; idx >= last_idx; --idx, ++k)
+        if (eager_step(idx, k)) return -1;
+    return 0;
+}

@@ -1,7 +1,7 @@
 // MFCC front end of y['mfcc'] (reference data_loaders/gesture/data/dataset.py:81-95 -> python_speech_features.mfcc):
-// pre-emphasis + framing, power spectrum (the DFT itself is a GEMM against a cos / -sin table, api.hip), log mel
+// pre-emphasis + framing, power spectrum (the DFT itself is a GEMM against a cos / -sin table, gdx_mfcc below), log mel
 // energies (GEMM against the filterbank), DCT-II + lifter + log-energy + z-score.  fp32 only.
-#include "gdx_internal.h"
+#include "gdx_host.h"
 
 namespace gdx {
 
@@ -91,3 +91,38 @@ hipError_t launch_mfcc_cepstrum(const float* mel, int ldm, const float* energy, 
 }
 
 }  // namespace gdx
+
+using namespace gdx;
+
+// MFCC front end (reference data_loaders/gesture/data/dataset.py:81-95).  The caller supplies the tables (built once on the
+// host in fp64, stored fp32) and the workspace; layouts:
+//   dft  [2*nbp][Lp]   rows k < nbins: cos(2 pi k i / nfft), rows nbp + k: -sin(...), zero elsewhere; Lp = frame_len up to 32,
+//                      nbp = nbins up to 64
+//   mel  [64][nbp]     rows j < nfilt: triangular filter j over the nbins power bins, zero elsewhere
+//   work               (numframes + GDX_ROW_PAD) * (Lp + 2*nbp + nbp + 64) + numframes floats
+extern "C" int gdx_mfcc(const float* signal, int64_t n, int32_t frame_len, int32_t frame_step, int32_t numframes,
+                        int32_t nfft, int32_t nfilt, int32_t numcep, float preemph, const float* dft, const float* mel,
+                        const float* dct, const float* lifter, const float* mean, const float* stdv, float* work,
+                        float* out, void* stream) {
+    if (!signal || !dft || !mel || !dct || !lifter || !work || !out) return fail("gdx_mfcc: null argument");
+    if (n <= 0 || frame_len <= 0 || frame_step <= 0 || numframes <= 0 || nfft < frame_len || nfilt <= 0 || nfilt > 64 ||
+        numcep <= 0 || numcep > nfilt)
+        return fail("gdx_mfcc: bad geometry");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = gemm_init();
+    if (e != hipSuccess) return fail(std::string("gemm_init: ") + hipGetErrorString(e));
+    const int nbins = nfft / 2 + 1, Lp = round_up(frame_len, 32), nbp = round_up(nbins, 64), rows = numframes + GDX_ROW_PAD;
+    float* frames = work;
+    float* spec = frames + (size_t)rows * Lp;
+    float* pw = spec + (size_t)rows * 2 * nbp;
+    float* melv = pw + (size_t)rows * nbp;
+    float* energy = melv + (size_t)rows * 64;
+    HIPCHK(launch_mfcc_frames(signal, (long)n, frames, numframes, frame_len, frame_step, Lp, preemph, s));
+    GemmParams p{frames, Lp, dft, Lp, nullptr, nullptr, 0, nullptr, 0, spec, 2 * nbp, numframes, 2 * nbp, Lp, 1};
+    if (gemm(OUT_ROWS, EPI_BIAS, p, s)) return -1;                       // DFT: [F, L] x [2*nbins, L]^T
+    HIPCHK(launch_mfcc_power(spec, 2 * nbp, nbp, pw, nbp, energy, numframes, nbins, nfft, s));
+    GemmParams q{pw, nbp, mel, nbp, nullptr, nullptr, 0, nullptr, 0, melv, 64, numframes, 64, nbp, 1};
+    if (gemm(OUT_ROWS, EPI_BIAS, q, s)) return -1;                       // mel energies
+    HIPCHK(launch_mfcc_cepstrum(melv, 64, energy, dct, lifter, mean, stdv, out, numframes, nfilt, numcep, s));
+    return 0;
+}

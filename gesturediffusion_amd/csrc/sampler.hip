@@ -960,7 +960,7 @@ static int step_begin(const char* who, const A* a, float* A::*pred, Entry entry_
 
 static int sampler_update_impl(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
 
-// internal (api.hip, gdx_sample_loop): one step of the token-major fast path (update_tm_kernel)
+// internal (loops.hip, gdx_sample_loop): one step of the token-major fast path (update_tm_kernel)
 int gdx_sampler_update_tm_(const gdx::UpdateTmDev& d, void* stream) {
     using namespace gdx;
     const int jpad = (d.J + 3) / 4 * 4;
@@ -1320,7 +1320,7 @@ extern "C" int gdx_cfg_delta(const gdx_cfg_delta_args_t* a, void* stream) {
     return launch_status("gdx_cfg_delta: launch failed");
 }
 
-// internal (api.hip, gdx_bpd_loop): x_t and the stored Philox noise of one step (bpd_xt_kernel)
+// internal (loops.hip, gdx_bpd_loop): x_t and the stored Philox noise of one step (bpd_xt_kernel)
 int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
                 uint32_t step, float* z_out, float* xt_out, void* stream) {
     using namespace gdx;

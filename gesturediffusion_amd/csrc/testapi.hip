@@ -485,7 +485,7 @@ extern "C" int gdx_attention_f32_rows(const float* qkv, int32_t qkv_rows, float*
     if (!head_dim_supported(d / H)) return fail("gdx_attention_f32_rows: head_dim must be " GDX_HEAD_DIMS);
     if (kernel != 0 && kernel != 1 && kernel != 3 && kernel != 5)
         return fail("gdx_attention_f32_rows: unknown kernel (0 = dispatch, 1 = attention.hip, 3 = attention3.hip, 5 = its persistent form)");
-    const bool a3 = kernel == 3 || kernel == 5 || (kernel == 0 && attention3_supported(S, H, d));   // the rule of attend() (api.hip)
+    const bool a3 = kernel == 3 || kernel == 5 || (kernel == 0 && attention3_supported(S, H, d));   // the rule of attend() (forward.hip)
     if (kernel && a3 && !attention3_supported(S, H, d))
         return fail("gdx_attention_f32_rows: shape not supported by attention3.hip (head_dim 64 / 128, at most 256 tokens)");
     if (grid < 0 || (grid > 0 && kernel != 5) || (grid == 0 && kernel == 5))

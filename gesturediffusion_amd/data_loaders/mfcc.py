@@ -77,7 +77,7 @@ class MfccExtractor:
         return 1 if n <= self.frame_len else 1 + int(math.ceil((1.0 * n - self.frame_len) / self.frame_step))
 
     def _stage_widths(self):
-        """Row widths of the workspace's four row-major stages (csrc/api.hip, above gdx_mfcc): frames | spec | pw | mel."""
+        """Row widths of the workspace's four row-major stages (csrc/mfcc.hip, above gdx_mfcc): frames | spec | pw | mel."""
         return self.Lp, 2 * self.nbp, self.nbp, 64
 
     def workspace_size(self, F):

@@ -620,7 +620,7 @@ int gdx_postprocess(const float* x, const double* mean, const double* std, float
  * (python_speech_features.mfcc(signal, winlen=0.06, winstep=1/fps, samplerate=sr, numcep=27, nfft=5000) and the z-score):
  * pre-emphasis + rectangular framing, power spectrum by a DFT-as-GEMM on the fp32 MFMA kernel, mel filterbank (GEMM),
  * log, DCT-II (ortho), sinusoidal lifter, log frame energy in coefficient 0, (m - mean) / std.
- * signal [n] fp32 (device); tables and workspace ((numframes + GDX_ROW_PAD) rows per stage) as laid out at the definition (csrc/api.hip); mean / std [numcep] or
+ * signal [n] fp32 (device); tables and workspace ((numframes + GDX_ROW_PAD) rows per stage) as laid out at the definition (csrc/mfcc.hip); mean / std [numcep] or
  * NULL; out [numframes][numcep] fp32.  The package is absent from this image: parity with it is UNPINNED
  * (oracle/mfcc.py restates its published algorithm). */
 int gdx_mfcc(const float* signal, int64_t n, int32_t frame_len, int32_t frame_step, int32_t numframes,
@@ -888,7 +888,7 @@ int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_steps, int32
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  A call whose
  * steps do not all take the same mode (a guidance interval that begins or ends inside it) runs eagerly.  Off by
  * default: on ROCm 7.2 the replay measured ~10 % slower than eager launches even for launch-dominated small batches
- * (csrc/api.hip, gdx_sample_loop).  Ignored while taps, dump_steps or in-situ profiling are active. */
+ * (csrc/loops.hip, gdx_sample_loop).  Ignored while taps, dump_steps or in-situ profiling are active. */
 int gdx_set_graph_replay(gdx_handle_t h, int32_t on);
 
 /* ---- measurement helpers (bench.py only) ------------------------------------------------ */

@@ -1,4 +1,4 @@
-"""The MFCC front end (gdx_mfcc, csrc/api.hip + csrc/mfcc.hip) restated stage by stage in float64, with the input builders,
+"""The MFCC front end (gdx_mfcc and its kernels, csrc/mfcc.hip) restated stage by stage in float64, with the input builders,
 the error bounds and the comparison functions that tests/test_gpu_mfcc.py (GPU) and tests/test_mfcc_host.py (CPU, mutation
 check) share.  No GPU code here.
 

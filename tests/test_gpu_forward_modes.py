@@ -1,4 +1,4 @@
-"""The branches of the per-step kernel sequence that depend on the compute mode and on keep_taps (csrc/api.hip: forward_core and
+"""The branches of the per-step kernel sequence that depend on the compute mode and on keep_taps (csrc/forward.hip: forward_core and
 its helpers linear / attend / add_norm), at the smallest models that take them.  Need an MI355X.
 
 fp32 runs every sublayer in fp32; fp16 keeps a 16-bit residual stream, whose fp32 copies exist only while taps are kept; bf16 keeps

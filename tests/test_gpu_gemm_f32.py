@@ -1,6 +1,6 @@
 """Kernel-level tests of the fp32 GEMMs: every tile shape of the persistent kernel (csrc/gemm2.hip gemm4_kernel, its
 residual-prefetch variant RESP included) and the 128 x 128 fallback (csrc/gemm.hip), under each of the five launches of the
-fp32 forwards (csrc/api.hip forward_core), through the test entry point gdx_linear_full and the forwards' own dispatcher,
+fp32 forwards (csrc/forward.hip forward_core), through the test entry point gdx_linear_full and the forwards' own dispatcher,
 against float64 torch on the same fp32 inputs.  Need an MI355X.
 
 What each call checks:

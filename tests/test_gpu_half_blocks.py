@@ -85,7 +85,7 @@ GEMM_SHAPES = [(1, 256, 256, 1), (50, 256, 320, 7), (333, 512, 256, 37), (3000, 
 # test_fp16_gemm_vs_torch
 GEMM_TOL32, GEMM_TOL32_GELU = 2e-6, 3e-5
 
-# name: (bias, gelu, R, V, rowmap, C32, C16) -- the forwards' launches (csrc/api.hip forward_core)
+# name: (bias, gelu, R, V, rowmap, C32, C16) -- the forwards' launches (csrc/forward.hip forward_core)
 EPILOGUES = {
     "bias": (1, 0, 0, 0, 0, 1, 1),              # QKV, out-proj / FFN-2 of the 16-bit stream, output linear
     "bias_gelu": (1, 1, 0, 0, 0, 1, 1),         # FFN-1

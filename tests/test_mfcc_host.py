@@ -1,5 +1,5 @@
 """CPU-only tests of the MFCC front end's host side (gesturediffusion_amd/data_loaders/mfcc.py): the extractor's tables against
-oracle/mfcc.py and numpy's FFT, frame counts, the workspace layout against the formula at gdx_mfcc (csrc/api.hip), what
+oracle/mfcc.py and numpy's FFT, frame counts, the workspace layout against the formula at gdx_mfcc (csrc/mfcc.hip), what
 gdx_mfcc refuses before it touches the device, and a mutation check of the bounds the GPU test asserts
 (tests/mfcc_restatement.py): each of eight plausible kernel mistakes, applied to the float64 restatement of the pipeline, must
 be rejected by the GPU test's own comparison functions on at least one of its inputs, and the unmutated restatement accepted
