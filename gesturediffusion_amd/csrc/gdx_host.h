@@ -3,6 +3,7 @@
 // bench entry points); the helpers declared here are defined in the first three.
 #pragma once
 #include "gdx_call_plan.h"
+#include "gdx_window_stride.h"
 #include "gdx_internal.h"
 
 #include <set>
@@ -161,6 +162,12 @@ struct gdx_model {
     bool tables_valid = false;        // temb_table (and c2t_table) hold the rows of tmap_host under the current weights
     std::vector<int64_t> tmap_host;
     float *bpd_xt = nullptr, *bpd_z = nullptr, *bpd_part = nullptr;   // gdx_bpd_loop: x_t, Philox noise [B, J, T], chunk sums
+    // gdx_parallel_loop (B = window x samples): the window's predictions [B, J, T], the sweep's errors [B] and chunk sums, the scales
+    // repeated per slot [B], and the model timestep of every slot the loop can reach, [steps + window][samples] (what pl_ts_host holds)
+    float *pl_x0 = nullptr, *pl_scale = nullptr;
+    double *pl_err = nullptr, *pl_part = nullptr;
+    int64_t* pl_ts = nullptr; size_t pl_ts_cap = 0;
+    std::vector<int64_t> pl_ts_host;
     // graph replay of launch-bound loops (gdx_sample_loop)
     bool graph_replay = false;        // gdx_set_graph_replay
     int* gstate = nullptr;            // device {schedule index, executed-step number}

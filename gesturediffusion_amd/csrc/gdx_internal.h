@@ -246,5 +246,7 @@ int gdx_ddim_reverse_step_(const gdx::DdimReverseStepArgs& a, void* stream);
 // gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
 int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
                 uint32_t step, float* z_out, float* xt_out, void* stream);
+// gdx_parallel_loop: the window's planes [W + 1][plane] slid down by `stride` planes, the tail filled with P_W (window_slide_kernel)
+int gdx_window_slide_(float* planes, long plane, int W, int stride, void* stream);
 // records the text of gdx_last_error and returns -1 (handle.hip), for the files that do not include gdx_host.h
 extern "C" int gdx_set_error_(const char* msg);

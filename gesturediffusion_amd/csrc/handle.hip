@@ -126,6 +126,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     h->temb_table = nullptr; h->temb_table_rows = 0; h->tmap_dev = nullptr; h->c2t_table = nullptr; h->c2t_valid = false;
     h->tables_valid = false;
     h->bpd_xt = h->bpd_z = h->bpd_part = nullptr;
+    h->pl_x0 = h->pl_scale = nullptr; h->pl_err = h->pl_part = nullptr; h->pl_ts = nullptr; h->pl_ts_cap = 0; h->pl_ts_host.clear();
     h->rs_part = nullptr; h->rs_factor = nullptr; h->gd = nullptr; h->lc_delta = nullptr; h->lc_in = nullptr;
     // the shape is recorded only once every allocation has succeeded: after a failed hipMalloc a retry with the same
     // shape must allocate again instead of returning early on partial buffers

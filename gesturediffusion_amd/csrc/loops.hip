@@ -334,6 +334,91 @@ extern "C" int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_s
     return 0;
 }
 
+// parallel_sample_loop (parallel-in-time sampling, gdx.h): per iteration ONE denoiser call on the window's W planes as a batch of
+// W x B samples -- gdx_forward itself: per-sample timestep rows, the blend that selects per sample by the guidance interval, the
+// rescale --, ONE gdx_window_sweep launch, the stride from the sweep's errors (gdx_window_stride.h), the slide.  The one loop
+// that synchronises its stream, once per iteration: the stride depends on the data.  Nothing of multistep_loop applies (no plan:
+// every call is a full one at per-sample timesteps; no history; the step count of a call is not known in advance).
+extern "C" int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int32_t num_steps, int32_t first_index, const float* coef,
+                                 const int64_t* timestep_map, const double* threshold, int32_t window, float* planes,
+                                 const float* scale, const uint8_t* inpaint_mask, const float* inpaint_motion, int32_t clip_denoised,
+                                 const float* noise_tape, uint64_t philox_seed, uint64_t sample_offset, int32_t* anchor,
+                                 int32_t max_iterations, int32_t* strides_out, int32_t strides_capacity, int32_t* iterations_out,
+                                 void* stream) {
+    const char* who = "gdx_parallel_loop";
+    const std::string w = std::string(who) + ": ";
+    if (!coef || !timestep_map || !threshold || !planes || !anchor || !iterations_out) return fail(w + "null argument");
+    if (kind != GDX_SAMPLER_P && kind != GDX_SAMPLER_DDIM) return fail(w + "kind must be GDX_SAMPLER_P or GDX_SAMPLER_DDIM");
+    if (check_mode(who, mode, scale)) return -1;
+    if (num_steps <= 0 || first_index < 0 || first_index >= num_steps) return fail(w + "bad step range");
+    const int K = first_index + 1;
+    if (*anchor < 0 || *anchor > K) return fail(w + "anchor must lie in 0 .. first_index + 1");
+    if (window < 1 || window > 64) return fail(w + "window must lie in 1 .. 64");
+    if (max_iterations < 0 || strides_capacity < 0 || (strides_capacity > 0 && !strides_out))
+        return fail(w + "bad max_iterations / strides_out");
+    if (inpaint_mask && !inpaint_motion) return fail(w + "mask without motion");
+    if (!h) return fail(w + "null handle");
+    if (h->guide_every > 1)
+        return fail(w + "the guidance refresh (gdx_set_guidance_refresh, every > 1) needs memory across sequential denoiser calls; "
+                        "the window's calls are not sequential: set every = 1");
+    if (h->lc_every > 1)
+        return fail(w + "the layer cache (gdx_set_layer_cache, every > 1) needs memory across sequential denoiser calls; the "
+                        "window's calls are not sequential: set every = 1");
+    if (check_ready(h, who)) return -1;
+    if (h->B % window)
+        return fail(w + "the handle is prepared for " + std::to_string(h->B) + " samples, which window = " + std::to_string(window) +
+                    " does not divide (prepare it for window x batch)");
+    if ((long)h->B * (mode == GDX_CFG ? 2 : 1) > 65535) return fail(w + "window x batch (x 2 under guidance) exceeds 65535");
+    hipStream_t s = (hipStream_t)stream;
+    const int WB = h->B, B = WB / window;
+    const size_t per = (size_t)h->J * h->T, plane = (size_t)B * per;
+    const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
+    *iterations_out = 0;
+    if (!h->pl_x0) {
+        if (ws_alloc(h, who, (void**)&h->pl_x0, sizeof(float) * WB * per) || ws_alloc(h, who, (void**)&h->pl_scale, sizeof(float) * WB) ||
+            ws_alloc(h, who, (void**)&h->pl_err, sizeof(double) * WB) || ws_alloc(h, who, (void**)&h->pl_part, sizeof(double) * WB * chunks))
+            return -1;
+        HIPCHK(hipStreamSynchronize(nullptr));                     // the fills are on the null stream, the first store on s
+    }
+    // the model timestep of executed step k for every k a slot can name, one row of B per step: the window at anchor a reads rows
+    // a .. a + W - 1 as its W x B timesteps; rows behind the last step (ignored tail slots) run at index 0
+    std::vector<int64_t> ts((size_t)(K + window) * B);
+    for (int k = 0; k < K + window; ++k)
+        std::fill_n(ts.begin() + (size_t)k * B, B, timestep_map[k < K ? first_index - k : 0]);
+    if (h->pl_ts_cap < ts.size()) {
+        if (dev_alloc(h->ws_allocs, (void**)&h->pl_ts, sizeof(int64_t) * ts.size())) return -1;
+        h->pl_ts_cap = ts.size();
+        h->pl_ts_host.clear();
+    }
+    if (h->pl_ts_host != ts) {
+        HIPCHK(hipStreamSynchronize(s));                           // an earlier call's forwards may still read the rows
+        HIPCHK(hipMemcpy(h->pl_ts, ts.data(), sizeof(int64_t) * ts.size(), hipMemcpyHostToDevice));
+        h->pl_ts_host.swap(ts);
+    }
+    if (mode == GDX_CFG)
+        for (int j = 0; j < window; ++j)
+            HIPCHK(hipMemcpyAsync(h->pl_scale + (size_t)j * B, scale, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
+    std::vector<double> err((size_t)window * B);
+    int a = *anchor, it = 0;
+    while (a < K && (max_iterations == 0 || it < max_iterations)) {
+        const int n = std::min(window, K - a);
+        if (gdx_forward(h, planes, h->pl_ts + (size_t)a * B, mode, mode == GDX_CFG ? h->pl_scale : nullptr, h->pl_x0, stream)) return -1;
+        if (gdx_window_sweep(kind, B, h->J, h->T, n, coef, first_index - a, planes, h->pl_x0, inpaint_mask, inpaint_motion, clip_denoised,
+                             noise_tape ? noise_tape + (size_t)a * plane : nullptr, philox_seed, sample_offset, (uint32_t)(a + 1),
+                             h->pl_err, h->pl_part, stream))
+            return -1;
+        HIPCHK(hipMemcpyAsync(err.data(), h->pl_err, sizeof(double) * n * B, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const int stride = window_stride(err.data(), B, n, threshold, first_index - a);
+        if (gdx_window_slide_(planes, (long)plane, window, stride, stream)) return -1;
+        a += stride;
+        *anchor = a;
+        if (it < strides_capacity) strides_out[it] = stride;
+        *iterations_out = ++it;
+    }
+    return 0;
+}
+
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
     if (check_ready(h, "gdx_sample_loop")) return -1;
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");

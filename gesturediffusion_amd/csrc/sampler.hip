@@ -890,6 +890,95 @@ __global__ __launch_bounds__(256) void cfg_delta_kernel(const float* a, const fl
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Parallel-in-time sampling (gdx.h gdx_window_sweep): the sequential update chain over a window of planes P_0 .. P_n with the
+// denoiser's predictions M_0 .. M_{n-1} held fixed, in ONE launch.  A thread owns one group of four elements and walks the slots
+// with the running state v in registers: v' = step(v, M_j) through pred_xstart4 / update_value / philox_normal4 -- the statements
+// update_kernel runs, hence n successive gdx_sampler_update launches bit for bit --, the squared change of P_{j+1} in fp64, the
+// store, v = v'.  Streaming: 2n planes read (M_j, old P_{j+1}; + tape noise, + mask and motion), n written.  The slot's squared
+// differences are reduced across the wave inside the slot loop (one double per thread live at a time, not n) and meet in LDS
+// once, behind the loop; the order is fixed, no atomics: thread -> wave -> block (= one chunk of GDX_BPD_CHUNK elements: 1024
+// threads, one group each) -> part[(slot*B + b)*chunks + chunk], and window_err_kernel adds a (slot, sample)'s chunks in chunk
+// order and divides by J*T.  Grid (chunks, B).
+struct WindowSweepDev {
+    StepSrc s;              // coef, step_index (slot 0's), mask / motion / clip, the geometry; x, x0c, out, pred are not read
+    int kind, batch, n_slots, chunks;
+    float* planes;          // [n_slots + 1][B][per_sample]
+    const float* x0;        // [n_slots][B][per_sample]
+    const float* noise;     // nullptr (Philox) or [n_slots][B][per_sample]
+    long plane;             // B * per_sample
+    uint64_t seed, sample_offset;
+    uint32_t rng_step;      // slot 0's Philox draw
+    double* part;
+};
+constexpr int WINDOW_MAX_SLOTS = 64;
+static_assert(BPD_GROUPS == 1024, "window_sweep_kernel: one block of 1024 threads is one chunk");
+
+template <bool VEC>
+__global__ __launch_bounds__(1024) void window_sweep_kernel(const WindowSweepDev a) {
+    __shared__ double red[BPD_GROUPS / 64][WINDOW_MAX_SLOTS];
+    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    const long grp = (long)chunk * BPD_GROUPS + tid;
+    const bool live = grp < a.s.groups;                            // a dead thread still takes part in the wave's reduction
+    const Group g = group_at<VEC>(b, live ? grp : 0, a.s.per_sample);
+    StepSrc s = a.s;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (live) v = load4<VEC>(a.planes, g.e0, g.nval);
+    for (int j = 0; j < a.n_slots; ++j) {
+        double d2 = 0.0;
+        if (live) {
+            const float* c = a.s.coef + (long)(a.s.step_index - j) * 8;
+            s.x0c = a.x0 + (long)j * a.plane;
+            const f32x4 x0 = pred_xstart4<VEC>(s, g);
+            const f32x4 z = a.noise ? load4<VEC>(a.noise + (long)j * a.plane, g.e0, g.nval)
+                                    : philox_normal4(a.seed, a.sample_offset + (uint64_t)b, a.rng_step + (uint32_t)j, g.grp);
+            float* next = a.planes + (long)(j + 1) * a.plane;
+            const f32x4 old = load4<VEC>(next, g.e0, g.nval);
+            f32x4 r;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r[i] = update_value(a.kind, c, v[i], x0[i], z[i]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i < g.nval) {
+                    const double d = __dsub_rn((double)r[i], (double)old[i]);
+                    d2 = __dadd_rn(d2, __dmul_rn(d, d));
+                }
+            }
+            store4<VEC>(next, g.e0, g.nval, r);
+            v = r;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) d2 = __dadd_rn(d2, __shfl_down(d2, off, 64));
+        if ((tid & 63) == 0) red[tid >> 6][j] = d2;
+    }
+    __syncthreads();
+    if (tid < a.n_slots) {
+        double t = red[0][tid];
+#pragma unroll
+        for (int w = 1; w < BPD_GROUPS / 64; ++w) t = __dadd_rn(t, red[w][tid]);
+        a.part[((long)tid * a.batch + b) * a.chunks + chunk] = t;
+    }
+}
+
+// err[i] = (the chunk sums of (slot, sample) pair i, in chunk order) / (J*T); one thread per pair
+__global__ void window_err_kernel(const double* __restrict__ part, int chunks, long per_sample, int count, double* __restrict__ err) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    double t = 0.0;
+    for (int ch = 0; ch < chunks; ++ch) t = __dadd_rn(t, part[(long)i * chunks + ch]);
+    err[i] = __ddiv_rn(t, (double)per_sample);
+}
+
+// The window's slide by `stride` planes (gdx_parallel_loop): P_j <- P_{min(j + stride, W)} for j = 0 .. W-1 in ascending order, so
+// the planes that fall off the end become copies of P_W.  A thread owns one element (V = f32x4: four) of every plane: what it
+// reads at j + stride it has not yet written.  `count`: elements of type V per plane.
+template <typename V>
+__global__ __launch_bounds__(256) void window_slide_kernel(V* planes, long count, int W, int stride) {
+    const long step = (long)gridDim.x * 256;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < count; e += step)
+        for (int j = 0; j < W; ++j) planes[(long)j * count + e] = planes[(long)min(j + stride, W) * count + e];
+}
+
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
                             float* out, int B, int64_t per_sample, hipStream_t s) {
     const long total = (long)B * per_sample;
@@ -1216,6 +1305,56 @@ int gdx_ddim_reverse_step_(const gdx::DdimReverseStepArgs& args, void* stream) {
     if (vec_ok(d.s, d.eps_out)) hipLaunchKernelGGL(ddim_reverse_step_kernel<true>, grid, block, 0, (hipStream_t)stream, d);
     else hipLaunchKernelGGL(ddim_reverse_step_kernel<false>, grid, block, 0, (hipStream_t)stream, d);
     return launch_status("gdx_ddim_reverse_step: launch failed");
+}
+
+extern "C" int gdx_window_sweep(int32_t kind, int32_t batch, int32_t njoints, int32_t frames, int32_t n_slots, const float* coef,
+                                int32_t first_index, float* planes, const float* x0, const uint8_t* inpaint_mask,
+                                const float* inpaint_motion, int32_t clip_denoised, const float* noise, uint64_t philox_seed,
+                                uint64_t sample_offset, uint32_t rng_step, double* err, double* workspace, void* stream) {
+    using namespace gdx;
+    const char* who = "gdx_window_sweep";
+    if (!coef || !planes || !x0 || !err || !workspace) return refuse(who, "null argument");
+    if (kind != GDX_SAMPLER_P && kind != GDX_SAMPLER_DDIM) return refuse(who, "kind must be GDX_SAMPLER_P or GDX_SAMPLER_DDIM");
+    if (batch < 0 || njoints < 0 || frames < 0 || batch > 65535) return refuse(who, "bad shape");
+    if (n_slots < 1 || n_slots > WINDOW_MAX_SLOTS) return refuse(who, "n_slots must lie in 1 .. 64");
+    if (first_index < n_slots - 1) return refuse(who, "the window runs below index 0 (first_index < n_slots - 1)");
+    if (inpaint_mask && !inpaint_motion) return refuse(who, "mask without motion");
+    if (((uintptr_t)err | (uintptr_t)workspace) & 7) return refuse(who, "err and workspace must be 8-byte aligned");
+    WindowSweepDev d = {};
+    StepSrc& s = d.s;
+    s.per_sample = (long)njoints * frames;
+    s.groups = (s.per_sample + 3) / 4;
+    if (batch == 0 || s.per_sample == 0) return 0;
+    s.coef = coef; s.step_index = first_index;
+    s.mask = inpaint_mask; s.motion = inpaint_motion; s.clip = clip_denoised;
+    d.kind = kind; d.batch = batch; d.n_slots = n_slots;
+    d.chunks = (int)((s.per_sample + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK);
+    d.planes = planes; d.x0 = x0; d.noise = noise; d.plane = (long)batch * s.per_sample;
+    d.seed = philox_seed; d.sample_offset = sample_offset; d.rng_step = rng_step;
+    d.part = workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(d.chunks, batch), block(BPD_GROUPS);
+    // per_sample % 4 == 0 keeps every plane / slot / tape slice as aligned as its base
+    if (vec_ok(s.per_sample, (const float*)planes, x0, noise, inpaint_mask, inpaint_motion))
+        hipLaunchKernelGGL(window_sweep_kernel<true>, grid, block, 0, st, d);
+    else
+        hipLaunchKernelGGL(window_sweep_kernel<false>, grid, block, 0, st, d);
+    if (launch_status("gdx_window_sweep: launch failed")) return -1;
+    const int pairs = n_slots * batch;
+    hipLaunchKernelGGL(window_err_kernel, dim3((pairs + 63) / 64), dim3(64), 0, st, d.part, d.chunks, s.per_sample, pairs, err);
+    return launch_status("gdx_window_sweep: launch failed");
+}
+
+// internal (loops.hip, gdx_parallel_loop): planes [W + 1][plane] slid down by `stride` planes (window_slide_kernel)
+int gdx_window_slide_(float* planes, long plane, int W, int stride, void* stream) {
+    using namespace gdx;
+    if (plane == 0 || stride <= 0) return 0;
+    const bool vec = plane % 4 == 0 && group_aligned(planes);
+    const long count = vec ? plane / 4 : plane;
+    const dim3 grid((unsigned)std::min(2048L, (count + 255) / 256)), block(256);
+    if (vec) hipLaunchKernelGGL(window_slide_kernel<f32x4>, grid, block, 0, (hipStream_t)stream, (f32x4*)planes, count, W, stride);
+    else hipLaunchKernelGGL(window_slide_kernel<float>, grid, block, 0, (hipStream_t)stream, planes, count, W, stride);
+    return launch_status("gdx_parallel_loop: slide launch failed");
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,

@@ -13,6 +13,7 @@ coefficient rows; every per-element operation runs in libgdx.so:
   * `gdx_dpm_step` / `gdx_dpm_loop`     dpm_solver_sample_loop: DPM-Solver++ multistep (2M / 3M), additive, same pattern
   * `gdx_dpm_sde_step` / `gdx_dpm_sde_loop`   dpm_solver_sde_sample_loop: its stochastic twin (SDE-DPM-Solver++, orders 1 / 2)
   * `gdx_unipc_step` / `gdx_unipc_loop`   unipc_sample_loop: UniPC, a corrector and the multistep predictor in one launch per step
+  * `gdx_window_sweep` / `gdx_parallel_loop`   parallel_sample_loop: parallel-in-time sampling, a window of states per denoiser call
   * `gdx_bpd_terms` / `gdx_bpd_loop`   the variational bound in bits/dim (`_vb_terms_bpd` :1192-1225, `_prior_bpd`
                           :1519-1535, `calc_bpd_loop` :1537-1592, and `training_losses` under LossType.KL / RESCALED_KL)
 
@@ -538,10 +539,11 @@ class GaussianDiffusion:
             yield out
             img = out["sample"]
 
-    def _native_loop_setup(self, model, x, model_kwargs):
+    def _native_loop_setup(self, model, x, model_kwargs, window=None):
         """What every in-library loop does once in front: input checks, the engine prepared for x's shape and conditioned on
         y['seed'] / y['mfcc'] (and, for a use_text model, on the text features: MDM._text_features), and the loop's operands
-        -> (engine, mode, scale, inpainting mask, inpainted motion)."""
+        -> (engine, mode, scale, inpainting mask, inpainted motion).  window (parallel_sample_loop): the engine is prepared for
+        window x batch samples and the conditioning repeated window-major (Engine.prepare_window)."""
         from ..model.cfg_sampler import ClassifierFreeSampleModel
         y = model_kwargs["y"]
         inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
@@ -556,8 +558,11 @@ class GaussianDiffusion:
         every = E.guidance_refresh_of(y, guided)
         layer_cache = E.layer_cache_of(y, inner.num_layers)
         eng = inner._get_engine(x.device)
-        eng.prepare(B, T)
-        eng.set_condition(y["seed"], y["mfcc"], text=inner._text_features(y, B), cache=False)
+        if window is None:
+            eng.prepare(B, T)
+            eng.set_condition(y["seed"], y["mfcc"], text=inner._text_features(y, B), cache=False)
+        else:
+            eng.prepare_window(B, T, window, y["seed"], y["mfcc"], text=inner._text_features(y, B))
         eng.set_guidance_interval(interval)          # at every loop; None resets a reused handle to "every timestep"
         eng.set_guidance_rescale(phi)                # likewise: an absent key sets 0 (off)
         eng.set_guidance_refresh(every)              # likewise: an absent key sets 1 (off); every loop starts with a refresh
@@ -781,6 +786,70 @@ class GaussianDiffusion:
         yield from self._loop(GDX_SAMPLER_DDIM, model, shape, noise, clip_denoised, denoised_fn, cond_fn,
                               model_kwargs, device, progress, eta, skip_timesteps, init_image, randomize_class,
                               cond_fn_with_grad, False, "torch", 0, 0, None, every_step=True)
+
+    # ------------------------------------------------------------------ parallel-in-time sampling
+    def parallel_threshold(self, tolerance):
+        """threshold[i] = tolerance^2 * exp(posterior_log_variance_clipped[i]) in float64: the mean squared change a window
+        plane may show at index i and still count as converged (ParaDiGMS's scaling; used for the DDIM kind as well)."""
+        return float(tolerance) ** 2 * np.exp(np.asarray(self.posterior_log_variance_clipped, dtype=np.float64))
+
+    def parallel_sample_loop(self, model, shape, noise=None, clip_denoised=True, model_kwargs=None, device=None, progress=False,
+                             skip_timesteps=0, init_image=None, *, sampler="p", eta=0.0, window=16, tolerance=0.1,
+                             philox_seed=0, sample_offset=0, noise_tape=None, report=None):
+        """Parallel-in-time sampling (ParaDiGMS, Shih et al. 2023) of p_sample_loop (sampler="p") or ddim_sample_loop ("ddim",
+        eta) inside libgdx (gdx_parallel_loop; the rule is in include/gdx.h): a window of `window` consecutive states goes through
+        the denoiser as ONE batch of window x B samples, the update chain is re-run over the window with those predictions held
+        fixed (gdx_window_sweep), and the window advances past every state whose mean squared change stayed within
+        parallel_threshold(tolerance).  Fewer, fatter denoiser calls one after the other, for more denoiser work in total.
+        x_T is `noise`, else entry 0 of `noise_tape`, else Philox draw 0, as p_sample_loop(rng="philox") forms it; the step noise is
+        the tape's or Philox draw k + 1; init_image / skip_timesteps go through q_sample as in p_sample_loop.  tolerance = 0: the
+        fp32 result has the bits of the sequential loop under the same noise.  window = 1 is the sequential loop.  tolerance > 0:
+        the stride is decided by the batch's worst sample, so a sample's result depends on the batch it runs in (and on the shard
+        under multi-GPU); at tolerance 0 it does not.  report (a dict) receives iterations, strides and forward_samples.
+        ValueError for a non-native model, y['guidance_refresh'] > 1, y['layer_cache'] with every > 1 (both need memory across
+        sequential calls), a window outside 1 .. 64, a negative or NaN tolerance and another sampler."""
+        kinds = {"p": GDX_SAMPLER_P, "ddim": GDX_SAMPLER_DDIM}
+        if sampler not in kinds:
+            raise ValueError(f"parallel_sample_loop runs sampler 'p' or 'ddim', got {sampler!r}")
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= 64:
+            raise ValueError(f"window must be an int with 1 <= window <= 64, got {window!r}")
+        if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.floating, np.integer)) or not tolerance >= 0:
+            raise ValueError(f"tolerance must be a number >= 0 (not NaN), got {tolerance!r}")
+        if not _is_native(model) or self.model_mean_type != ModelMeanType.START_X:
+            raise ValueError("parallel_sample_loop runs inside libgdx: it needs a native START_X denoiser (MDM / MDM_Old or its "
+                             "ClassifierFreeSampleModel)")
+        self._refuse_refresh(model, model_kwargs, "parallel_sample_loop (its window evaluates steps side by side)")
+        if self.rescale_timesteps:
+            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
+        self._check_supported()
+        window = int(window)
+        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, "philox",
+                                                  philox_seed, sample_offset, noise_tape)
+        x = E.f32c(img, "x_T")
+        n = len(indices)
+        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs, window=window)
+        planes = x.unsqueeze(0).repeat(window + 1, 1, 1, 1, 1)
+        tape = E.f32c(noise_tape[1:1 + n], "noise_tape") if noise_tape is not None else None
+        coef, tmap, thr = self.coef_table(kinds[sampler], x.device, eta), self._timestep_map(), self.parallel_threshold(tolerance)
+        before = eng.forward_samples()
+        bar = None
+        if progress:
+            from tqdm.auto import tqdm
+            bar = tqdm(total=n)
+        anchor, strides = 0, []
+        while anchor < n:
+            new, s = eng.parallel_loop(planes, kinds[sampler], mode, coef, tmap, thr, indices[0], anchor=anchor, scale=scale,
+                                       inpaint_mask=mask, inpaint_motion=motion, clip_denoised=clip_denoised, noise_tape=tape,
+                                       philox_seed=philox_seed, sample_offset=sample_offset, max_iterations=1 if progress else 0)
+            strides += s
+            if bar is not None:
+                bar.update(new - anchor)
+            anchor = new
+        if bar is not None:
+            bar.close()
+        if report is not None:
+            report.update(iterations=len(strides), strides=strides, forward_samples=eng.forward_samples() - before)
+        return planes[0].clone()
 
     # ------------------------------------------------------------------ explicitly out of scope
     def masked_l2(self, a, b, mask):

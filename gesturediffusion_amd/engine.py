@@ -331,6 +331,35 @@ class Engine:
                                                   kw["inpaint_motion"], kw["clip_denoised"], _stream(x.device)), self.lib)
         self._keep_loop = (tmap,)
 
+    def prepare_window(self, batch, frames, window, seed, mfcc, text=None):
+        """The handle of gdx_parallel_loop: prepared for window x batch samples and conditioned on seed / mfcc (and text)
+        repeated window-major, row j * batch + b = sample b."""
+        rep = lambda t: t.repeat(window, *([1] * (t.dim() - 1))) if t is not None else None   # noqa: E731
+        self.prepare(window * batch, frames)
+        self.set_condition(rep(seed), rep(mfcc), text=rep(text), cache=False)
+
+    def parallel_loop(self, planes, kind, mode, coef, timestep_map, threshold, first_index, anchor=0, scale=None,
+                      inpaint_mask=None, inpaint_motion=None, clip_denoised=False, noise_tape=None, philox_seed=0,
+                      sample_offset=0, max_iterations=0):
+        """gdx_parallel_loop on planes [window + 1, B, J, 1, T] (updated in place; planes[0] is the sample once the anchor has
+        reached first_index + 1) -> (anchor, this call's strides).  threshold: float64 [num_steps] on the host.  The call
+        synchronises the stream once per iteration (gdx.h); max_iterations > 0 issues a block and carries nothing but the planes
+        and the anchor to the next."""
+        kw, tmap = _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, 0, 0)
+        thr = np.ascontiguousarray(np.asarray(threshold, dtype=np.float64))
+        if thr.shape != (len(tmap),):
+            raise ValueError(f"threshold must hold one float64 per step ({len(tmap)}), got shape {thr.shape}")
+        window = planes.shape[0] - 1
+        cap = first_index + 1
+        a, its, strides = C.c_int32(anchor), C.c_int32(0), (C.c_int32 * cap)()
+        # plain arguments in gdx.h's order (this entry has no argument struct)
+        _lib.check(self.lib.gdx_parallel_loop(self.handle, kind, mode, kw["num_steps"], first_index, kw["coef"], kw["timestep_map"],
+                                              thr.ctypes.data, window, planes.data_ptr(), kw["scale"], kw["inpaint_mask"],
+                                              kw["inpaint_motion"], kw["clip_denoised"], _p(noise_tape), philox_seed, sample_offset,
+                                              C.byref(a), max_iterations, strides, cap, C.byref(its), _stream(planes.device)),
+                   self.lib)
+        return a.value, list(strides[:its.value])
+
     def forward_flops(self, mode=GDX_COND):
         f = C.c_double()
         _lib.check(self.lib.gdx_forward_flops(self.handle, mode, C.byref(f)), self.lib)
@@ -610,6 +639,25 @@ def ddim_reverse_step(coef, x, x0_cond, out, t=None, step_index=0, x0_uncond=Non
                                          kw["x0_cond"], kw["x0_uncond"], kw["scale"], kw["inpaint_mask"], kw["inpaint_motion"],
                                          kw["clip_denoised"], out.data_ptr(), _p(pred_out), _p(eps_out), _stream(x0_cond.device)), lib)
     return out
+
+
+def window_sweep(kind, coef, first_index, planes, x0, n_slots=None, inpaint_mask=None, inpaint_motion=None, clip_denoised=False,
+                 noise=None, philox_seed=0, sample_offset=0, rng_step=1):
+    """gdx_window_sweep: the update chain over planes [>= n + 1, B, J, 1, T] (in place; plane 0 is only read) with the predictions
+    x0 [>= n, B, J, 1, T] held fixed, slot j at index first_index - j with noise[j] or Philox draw rng_step + j (include/gdx.h)
+    -> err, float64 [n, B]: each slot's mean squared change per sample.  n_slots: n (default: every slot of x0).  Operands are taken
+    as they are (no copies: tests hand it misaligned views)."""
+    lib = _lib.load()
+    n = x0.shape[0] if n_slots is None else n_slots
+    _, B, J, F, T = planes.shape
+    chunks = (J * F * T + _lib.GDX_BPD_CHUNK - 1) // _lib.GDX_BPD_CHUNK
+    err = torch.empty(max(n, 1), B, device=planes.device, dtype=torch.float64)
+    ws = torch.empty(max(n, 1) * B * chunks, device=planes.device, dtype=torch.float64)
+    # plain arguments in gdx.h's order (this entry has no argument struct)
+    _lib.check(lib.gdx_window_sweep(kind, B, J * F, T, n, coef.data_ptr(), first_index, planes.data_ptr(), x0.data_ptr(),
+                                    _p(inpaint_mask), _p(inpaint_motion), int(bool(clip_denoised)), _p(noise), philox_seed,
+                                    sample_offset, rng_step, err.data_ptr(), ws.data_ptr(), _stream(planes.device)), lib)
+    return err
 
 
 def postprocess(sample, mean, std):

@@ -18,6 +18,8 @@ its statistics, and `results.npy` / `results.txt` / `results_len.txt` are writte
 run's seed, a data directory needs `--text_features FILE.npz` (`--list_texts OUT.txt` writes the strings to encode and exits).
 `--invert_gt` (data directory and `--sampler ddim` only) starts every chunk's DDIM loop from the DDIM inversion of that chunk's
 ground truth instead of a drawn x_T (`sample_chunks`, `invert_of_chunk`).
+`--parallel_window W --parallel_tolerance TAU` (`--sampler p` / `ddim`) runs every chunk's loop parallel in time
+(`parallel_sample_loop`) and prints each chunk's iteration count.
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N ...`; the batch is
 sharded across ranks and gathered once at the end of every chunk (RCCL over xGMI).  Sharded runs draw their noise from
@@ -55,7 +57,7 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
                   guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None, text_of_chunk=None,
-                  layer_cache=None):
+                  layer_cache=None, parallel=None):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -73,7 +75,17 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     guidance_param == 1 the loop retraces the inversion, and report(text) is told each chunk's round-trip error.
     text_of_chunk(c) -> text features [b, clip_dim] on the device (a use_text model): chunk c's y['text_embed'].
     layer_cache (every, keep): every every-th denoiser call in full, the first keep encoder layers plus the stored change of the
-    deeper ones in between (y['layer_cache']); each chunk is its own loop and starts with a full call."""
+    deeper ones in between (y['layer_cache']); each chunk is its own loop and starts with a full call.
+    parallel (window, tolerance): every chunk's loop runs parallel in time (parallel_sample_loop; samplers "p" and "ddim", Philox
+    noise or a tape; neither guidance_refresh > 1, layer_cache nor invert_of_chunk) and report(text) is told each chunk's iterations."""
+    if parallel is not None:
+        if sampler not in ("p", "ddim"):
+            raise ValueError("parallel needs sampler='p' or 'ddim'")
+        if guidance_refresh != 1 or layer_cache is not None or invert_of_chunk is not None:
+            raise ValueError("parallel runs neither guidance_refresh > 1, layer_cache nor invert_of_chunk: its window evaluates steps "
+                             "side by side")
+        if rng != "philox" and noise_tapes is None:
+            raise ValueError("parallel draws its noise from the counter-based generator: rng must be 'philox' (or pass noise_tapes)")
     if invert_of_chunk is not None and layer_cache is not None:
         raise ValueError("invert_of_chunk runs no layer cache")
     if invert_of_chunk is not None and sampler != "ddim":
@@ -129,6 +141,16 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             kw["noise"] = diffusion.ddim_reverse_sample_loop(inner, gt, clip_denoised=False, progress=progress,
                                                              model_kwargs={"y": {k: y[k] for k in ("mfcc", "seed", "text_embed")
                                                                                  if k in y}})
+        if parallel is not None:
+            stats = {}
+            sample_out = diffusion.parallel_sample_loop(
+                model, (b, J, 1, frames), clip_denoised=False, model_kwargs={"y": y}, progress=progress, sampler=sampler, eta=eta,
+                window=parallel[0], tolerance=parallel[1], philox_seed=kw["philox_seed"], sample_offset=sample_offset,
+                noise_tape=kw["noise_tape"], report=stats)
+            if report is not None:
+                report(f"### chunk {chunk + 1}: parallel: {stats['iterations']} iterations for {sum(stats['strides'])} steps")
+            outs.append(sample_out)
+            continue
         sample_out = sample_fn(model, (b, J, 1, frames), **kw)
         if gt is not None and guidance_param == 1 and report is not None:
             err = float((sample_out - gt).abs().max() / gt.abs().max())
@@ -335,7 +357,8 @@ def main(argv=None):
                          plms_order=args.plms_order, dpm_order=args.dpm_order, unipc_order=args.unipc_order,
                          guidance_interval=interval, guidance_rescale=args.guidance_rescale,
                          guidance_refresh=args.guidance_refresh, invert_of_chunk=invert_of_chunk, report=report,
-                         text_of_chunk=text_of_chunk, layer_cache=args.layer_cache)
+                         text_of_chunk=text_of_chunk, layer_cache=args.layer_cache,
+                         parallel=(args.parallel_window, args.parallel_tolerance) if args.parallel_window else None)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

@@ -72,6 +72,22 @@ def parse_and_load_from_model(parser, argv=None):
             parser.error("--invert_gt needs --sampler ddim: the latent is the start state of the deterministic DDIM loop")
         if args.guidance_refresh > 1:
             parser.error("--invert_gt runs no guidance refresh: the inversion is one conditional pass per step")
+    if args.parallel_window < 0 or args.parallel_window > 64:
+        parser.error("--parallel_window must lie in 0 .. 64 (0 = off)")
+    if not args.parallel_tolerance >= 0:
+        parser.error("--parallel_tolerance must be >= 0")
+    if args.parallel_window:
+        if args.sampler not in ("p", "ddim"):
+            parser.error("--parallel_window runs --sampler p or ddim only: the window re-runs their one-step update chain")
+        if args.guidance_refresh > 1:
+            parser.error("--parallel_window runs no guidance refresh: the stored difference needs sequential denoiser calls")
+        if args.layer_cache is not None:
+            parser.error("--parallel_window runs no layer cache: the stored change needs sequential denoiser calls")
+        if args.invert_gt:
+            parser.error("--parallel_window does not combine with --invert_gt")
+        if args.rng == "torch":
+            parser.error("--parallel_window draws its noise from the counter-based generator: use --rng philox (its default)")
+        args.rng = "philox"
     if args.list_texts and args.synthetic:
         parser.error("--list_texts lists the texts of a data directory: --synthetic has none")
     if args.use_text and args.arch_version == "mdm" and not (args.synthetic or args.text_features or args.list_texts):
@@ -199,6 +215,14 @@ def add_native_options(parser):
                             "for inversion), and the latent replaces the drawn x_T of the (guided) DDIM loop. "
                             "Needs --dataset genea2023 --data_dir D and --sampler ddim; with --guidance_param 1 the per-chunk "
                             "round-trip error max|regenerated - gt| / max|gt| is printed.")
+    group.add_argument("--parallel_window", default=0, type=int, metavar="W",
+                       help="Parallel-in-time sampling (ParaDiGMS): evaluate W consecutive states of a chunk's loop in one batched "
+                            "denoiser call and advance past every state that has stopped changing (0 = off, at most 64). "
+                            "--sampler p and ddim only; an error with --guidance_refresh > 1, --layer_cache and --invert_gt. "
+                            "Implies --rng philox.")
+    group.add_argument("--parallel_tolerance", default=0.1, type=float, metavar="TAU",
+                       help="--parallel_window: a state counts as converged when its mean squared change is at most TAU^2 times "
+                            "the step's posterior variance; 0 reproduces the sequential loop bit for bit in fp32.")
     group.add_argument("--text_features", default='', type=str, metavar="FILE.npz",
                        help="--use_text on a data directory: the CLIP text features of the run's texts, arrays `text` (strings) "
                             "and `features` (float32 [N, clip_dim]); every (take, chunk) text is looked up by exact match before "

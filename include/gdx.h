@@ -884,6 +884,87 @@ int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_steps, int32
                           const float* coef, const int64_t* timestep_map, float* x, const float* scale,
                           const uint8_t* inpaint_mask, const float* inpaint_motion, int32_t clip_denoised, void* stream);
 
+/* ---- parallel-in-time sampling ----------------------------------------------------------- */
+/* ParaDiGMS (Shih et al. 2023, arXiv:2305.16317) over the ancestral and the DDIM step: a window of W consecutive states is
+ * evaluated by ONE batched denoiser call, the known update chain is re-run over the window with those W predictions held fixed,
+ * and the window advances past every state that has stopped changing.  It shortens the chain of denoiser calls that must run
+ * one after the other at the price of more total denoiser work.
+ *
+ * The rule.  A loop executes steps k = 0 .. K-1 (K = first_index + 1) at indices i_k = first_index - k; s_k is the state after
+ * k steps, s_0 the start state.  The sequential step is s_{k+1} = step_k(s_k, m_k): m_k = the denoiser's x0 prediction on s_k at
+ * timestep_map[i_k]; step_k = gdx_sampler_update's formula at row i_k (x0 -> inpainting -> clamp, then the P or DDIM update);
+ * its noise z_k = Philox draw k + 1 keyed by (philox_seed; sample_offset + b; element) or slice k of a tape: gdx_sample_loop's
+ * convention.  The window state is an anchor a (steps finished) and planes P_0 .. P_W, each [B,J,1,T]: P_0 = s_a, P_j the current
+ * guess of s_{a+j}; initially a = 0 and every plane is a copy of the start state.  One iteration, n = min(W, K - a):
+ *   1. one denoiser call on P_0 .. P_{W-1} as a batch of W*B samples (2*W*B under GDX_CFG), row j*B + b, slot j at
+ *      timestep_map[i_{a+j}] (slots j >= n run at index 0 and are never read), through gdx_forward: blended predictions M_0 .. M_{n-1};
+ *   2. one gdx_window_sweep: per element v = P_0; for j = 0 .. n-1: v' = step_{a+j}(v, M_j), the error sum of (j, b) takes
+ *      ((double)v' - (double)P_{j+1})^2, P_{j+1} = v', v = v'; err[j][b] = that sum / (J*T) in fp64;
+ *   3. the stride: E_j = max_b err[j][b] (a NaN never passes); s = 1 + the number of LEADING j = 0, 1, ... with
+ *      E_j <= threshold[i_{a+j}], capped at n.  Plane 1 is always final; plane j + 1 is accepted when planes 1 .. j did not move
+ *      by more than their thresholds;
+ *   4. the slide: a += s, P_j <- P_{j+s}, the planes that fall off the end become copies of the old P_W.  Done when a = K; the
+ *      sample is P_0.
+ * threshold[i] = tau^2 * exp(posterior_log_variance_clipped[i]) is the caller's (fp64).  What follows: tau = 0 accepts a plane only
+ * when it did not change, so the fp32 result has the bits of the sequential loop under the same noise; W = 1 is the sequential
+ * loop for any tau; tau -> infinity strides n every time, ceil(K / W) iterations; every iteration strides at least 1, so the loop
+ * ends after at most K iterations, NaNs included; and for tau > 0 the maximum over b couples the samples: a sample's result
+ * depends on the batch it runs in (on the shard under multi-GPU), at tau = 0 it does not.
+ *
+ * gdx_window_sweep: step 2 alone, stateless, plain arguments like gdx_ddim_reverse_step.
+ *   kind                     GDX_SAMPLER_P / GDX_SAMPLER_DDIM
+ *   batch, njoints, frames   the shape [B,J,1,T] of one plane
+ *   n_slots                  n, 1 .. 64
+ *   coef                     device [num_steps][8], rows of gdx_sampler_update
+ *   first_index              the schedule index of slot 0; slot j runs at first_index - j (>= 0)
+ *   planes                   [n_slots + 1][B,J,1,T], updated in place; plane 0 is only read
+ *   x0                       [n_slots][B,J,1,T]: M_j
+ *   inpaint_mask, inpaint_motion   NULL or [B,J,1,T], indexed by b, not by slot
+ *   clip_denoised
+ *   noise                    NULL -> Philox; else [n_slots][B,J,1,T], slice 0 is slot 0's
+ *   philox_seed, sample_offset, rng_step   rng_step = the Philox draw of slot 0; slot j draws rng_step + j
+ *   err                      device double [n_slots][B]
+ *   workspace                device double [n_slots * B * ceil(J*T / GDX_BPD_CHUNK)]
+ * The planes have the bits of n successive gdx_sampler_update launches on the same operands (one definition of each formula).
+ * A thread owns one 4-element group and walks the slots with the state in registers; 128-bit accesses when J*T % 4 == 0 and
+ * every pointer is 16-byte aligned (the mask 4-byte), a scalar path otherwise; nothing is written in front of plane 1 or behind
+ * plane n.  The error sums are accumulated in a fixed order without atomics: per-chunk partials of GDX_BPD_CHUNK elements (one
+ * block each) in `workspace`, added in chunk order by a second, tiny launch.  Streaming: 2n planes read, n written.  batch <= 65535.
+ * Refusals come before the first HIP call. */
+int gdx_window_sweep(int32_t kind, int32_t batch, int32_t njoints, int32_t frames, int32_t n_slots, const float* coef,
+                     int32_t first_index, float* planes, const float* x0, const uint8_t* inpaint_mask, const float* inpaint_motion,
+                     int32_t clip_denoised, const float* noise, uint64_t philox_seed, uint64_t sample_offset, uint32_t rng_step,
+                     double* err, double* workspace, void* stream);
+
+/* The loop of the rule above.  The handle is prepared for window * B samples and conditioned on seed / mfcc (and text) repeated
+ * window-major (row j*B + b = sample b); B = the prepared batch / window.  THE ONE LOOP THAT SYNCHRONISES `stream`: once per
+ * iteration, to read the n error rows the stride depends on.  Issued in blocks (max_iterations) it carries nothing between calls
+ * but the planes and *anchor and gives the bits of one call.  The guidance interval and the guidance rescale apply per sample as in
+ * gdx_forward (a partly guided window keeps the double batch).  Refused, before the first launch: a handle whose guidance refresh
+ * or layer cache has every > 1 (both need memory across SEQUENTIAL calls); window outside 1 .. 64; a prepared batch the window
+ * does not divide; window * B * (2 under GDX_CFG) > 65535.  Neither graph replay nor the token-major path applies.
+ * gdx_forward_samples advances by window * B * (1 or 2) per iteration, ignored tail slots included.
+ *   kind, mode               GDX_SAMPLER_P / _DDIM; GDX_COND / GDX_UNCOND / GDX_CFG
+ *   num_steps, first_index   rows of coef / timestep_map / threshold; the loop's first index (K = first_index + 1 steps)
+ *   coef                     device [num_steps][8]
+ *   timestep_map             HOST [num_steps]
+ *   threshold                HOST double [num_steps]
+ *   window                   W
+ *   planes                   device [window + 1][B,J,1,T]; in: every plane the start state (or a block's planes), out: P_0 = the sample
+ *   scale                    [B] for GDX_CFG
+ *   inpaint_mask, inpaint_motion, clip_denoised   as in the other loops, [B,J,1,T]
+ *   noise_tape               device [K][B,J,1,T] (slice k = executed step k of the WHOLE loop) or NULL -> Philox draw k + 1
+ *   philox_seed, sample_offset
+ *   anchor                   HOST, in / out: steps finished (0 at the start, K at the end)
+ *   max_iterations           0 = run to the end
+ *   strides_out, strides_capacity   HOST array or NULL: this call's strides, the first strides_capacity of them
+ *   iterations_out           HOST: this call's iterations */
+int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int32_t num_steps, int32_t first_index, const float* coef,
+                      const int64_t* timestep_map, const double* threshold, int32_t window, float* planes, const float* scale,
+                      const uint8_t* inpaint_mask, const float* inpaint_motion, int32_t clip_denoised, const float* noise_tape,
+                      uint64_t philox_seed, uint64_t sample_offset, int32_t* anchor, int32_t max_iterations, int32_t* strides_out,
+                      int32_t strides_capacity, int32_t* iterations_out, void* stream);
+
 /* Replay ONE captured step as a hipGraph inside gdx_sample_loop (device-resident step state; the graph runs on an
  * internal stream ordered after / before `stream` by events).  Results are bit-identical to the eager loop.  A call whose
  * steps do not all take the same mode (a guidance interval that begins or ends inside it) runs eagerly.  Off by
