@@ -170,6 +170,9 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
         for (auto& t : h->taps)
             if (A(&t, N * d)) return -1;
     }
+    // the fills are on the null stream and hipMemset returns before they have run when that stream is busy; the first stores
+    // (gdx_set_condition) are on the caller's stream, which nothing orders behind the null stream when it is non-blocking
+    HIPCHK(hipStreamSynchronize(nullptr));
     h->B = batch; h->T = frames;
     return 0;
 }

@@ -12,6 +12,16 @@
  * int status return (0 = ok, <0 = error, text via gdx_last_error()); no exceptions cross
  * the ABI.  `stream` is a hipStream_t passed as void*.
  *
+ * The stream contract.  Every launch, copy and fill of a call goes to the `stream` it was given: any stream is accepted, the
+ * null stream, a blocking or a non-blocking one (PyTorch's side streams are non-blocking), and the result has the same bits on
+ * each.  The calls on ONE handle must be ordered by the caller -- one stream, or the caller's own events between streams: the
+ * handle's workspace is shared by all of them.  Two handles may run on two streams at once.  gdx_prepare (which takes no
+ * stream) and the first use of a feature that needs further workspace (the guidance refresh, the layer cache, the guidance
+ * rescale, gdx_bpd_loop, gdx_parallel_loop) may allocate and synchronise: gdx_prepare, the guidance refresh, the layer cache and
+ * gdx_parallel_loop zero what they allocate on the null stream and wait for that stream before their first store on `stream`.
+ * The entries that say "synchronises" wait for `stream`.  Nothing else waits.
+ * tests/test_gpu_streams.py runs every entry with a `stream` on a non-default stream against its default-stream bits.
+ *
  * The reference has no plugin ABI for this path: it is pure Python.  Each
  * entry point below names the reference Python interface it replaces; INTEGRATION.md shows
  * the ctypes stub a reference maintainer would add.
