@@ -20,6 +20,13 @@
 //     MFMA, issue their share of the DMA, and store their accumulators straight from registers; the bias vector
 //     is copied to LDS once per launch so the tile loop contains NO ordinary global load (one would make hipcc
 //     drain the DMA pipeline with vmcnt(0));
+//   * the K loop (profiles/gemm_kloop_attribution.txt, _ab.txt, _isa.txt): a fragment read costs the consumer wave 4-7 cycles
+//     of matrix time (QKV 6.7, FFN-1 5.2, residual 3.9-4.3; 2.4-3.7 % of a launch), and it is issue cost: waiting for the reads
+//     one group later gains nothing, so neither a longer read-ahead nor fewer reads per group can return much.  What did pay:
+//     a fixed MFMA order (no accumulator is reused by the next MFMA; hipcc's own order stalled 8 cycles per such pair, 4-34
+//     pairs per step in 11 of the 33 instantiations), two address instructions per K step instead of four to six, and in the
+//     two-stage rings the last MB * NBW MFMAs of a step behind the barrier, under the first read of the slab that just landed.
+//     Accumulators in a[] registers lost: hipcc puts their read-back into every K step (+5-9 % on the hot shapes);
 //   * the residual add of the out-proj / FFN-2 GEMMs: first moved into the LayerNorm kernel that follows (one extra
 //     operand stream in an HBM-bound kernel instead of 40 scattered 4-byte loads per lane in the MFMA-bound one); with
 //     the swapped accumulator layout it is 5-10 float4 loads per lane per tile, and the RESP variant of the kernel
@@ -81,17 +88,6 @@ __device__ __forceinline__ f32x2 gelu_fast2(f32x2 x) {
     const f32x2 r = 1.0f - pl * t * ex;
     const f32x2 er = f32x2{copysignf(r.x, z.x), copysignf(r.y, z.y)};
     return x * 0.5f * (1.0f + er);
-}
-
-template <int R, int NRD, int NMM>
-__device__ __forceinline__ void g4_sched_interleave() {
-    if constexpr (R < NRD) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);        // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);        // DS read
-        g4_sched_interleave<R + 1, NRD, NMM>();
-    } else if constexpr (NMM > NRD) {
-        __builtin_amdgcn_sched_group_barrier(0x008, NMM - NRD, 0);
-    }
 }
 
 // RESP: the residual variant (out-proj / FFN-2: C = A W^T + bias + R, R [M][ldr] row-aligned with C).  The R block of a
@@ -203,24 +199,51 @@ __global__ __launch_bounds__(512, 1) void gemm4_kernel(const GemmParams p, const
     for (int i = 0; i < MB; ++i)
 #pragma unroll
         for (int j = 0; j < NBW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int a_off = l15 * ST + 4 * lq;                                        // floats
-    const int b_off = A_BYTES / 4 + (wave * WN + l15) * ST + 4 * lq;
-    f32x4 fa0[MB], fb0[NBW], fa1[MB], fb1[NBW];
-    auto rd = [&](f32x4 (&fa)[MB], f32x4 (&fb)[NBW], int stage, int kk) {
-        const float* S = reinterpret_cast<const float*>(smem + stage * STAGE_BYTES);
-#pragma unroll
-        for (int i = 0; i < MB; ++i) fa[i] = *reinterpret_cast<const f32x4*>(&S[a_off + i * 16 * ST + kk * 16]);
-#pragma unroll
-        for (int j = 0; j < NBW; ++j) fb[j] = *reinterpret_cast<const f32x4*>(&S[b_off + j * 16 * ST + kk * 16]);
+    // Fragment addresses.  a_lane / b_lane: this lane's row and 16-byte column inside stage 0; a_ad / b_ad: the same inside the
+    // stage the next reads come from, stepped ONCE per K step (two VALU adds of an SGPR).  The lane parts pass through an empty
+    // asm, which the compiler cannot see through, so they stay two registers: computed from the float index of each read, the
+    // lane part and the bases of the current and the next stage were rebuilt inside every step of the three- and four-stage
+    // shapes (four to six VALU instructions per step, and in this kernel every VALU instruction is lost matrix time).
+    typedef const __attribute__((address_space(3))) char* lds_cptr;
+    typedef const __attribute__((address_space(3))) f32x4* lds_f4ptr;
+    lds_cptr a_lane = (lds_cptr)(lds_ptr_t)smem + (l15 * ST + 4 * lq) * 4;
+    lds_cptr b_lane = (lds_cptr)(lds_ptr_t)smem + A_BYTES + ((wave * WN + l15) * ST + 4 * lq) * 4;
+    asm volatile("" : "+v"(a_lane), "+v"(b_lane));
+    lds_cptr a_ad = a_lane, b_ad = b_lane;
+    auto to_stage = [&](int stage) {
+        a_ad = a_lane + stage * STAGE_BYTES;
+        b_ad = b_lane + stage * STAGE_BYTES;
     };
-    auto mm = [&](const f32x4 (&fa)[MB], const f32x4 (&fb)[NBW]) {
+    f32x4 fa0[MB], fb0[NBW], fa1[MB], fb1[NBW];
+    // read r of a fragment group: the MB activation fragments, then the NBW weight fragments
+    auto rd1 = [&](f32x4 (&fa)[MB], f32x4 (&fb)[NBW], int kk, int r) {
+        if (r < MB) fa[r] = *(lds_f4ptr)(a_ad + r * 16 * ROWB + kk * 64);
+        else fb[r - MB] = *(lds_f4ptr)(b_ad + (r - MB) * 16 * ROWB + kk * 64);
+    };
+    auto rd = [&](f32x4 (&fa)[MB], f32x4 (&fb)[NBW], int kk) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
+        for (int r = 0; r < MB + NBW; ++r) rd1(fa, fb, kk, r);
+    };
+    // One 16-deep fragment group: 4 * MB * NBW MFMAs in a FIXED order -- k index outermost, so an accumulator comes round again
+    // only after the MB * NBW - 1 others (the result of v_mfma_f32_16x16x4_f32 is ready after 40 cycles, the issue interval is
+    // 32: an accumulator used by two MFMAs in a row stalls the SIMD's only consumer wave) -- with the reads of the NEXT group
+    // (kk_next >= 0), one behind each of the first MB + NBW MFMAs.  sched_barrier(0) after every MFMA: nothing may cross it,
+    // so the scheduler cannot re-pair the MFMAs (it used to run e = 1, 2 of the first accumulator back to back right behind
+    // the reads: tools/mfma_reuse.py counts such pairs) or sink the reads to the end of the group, where the next group
+    // would wait out the LDS latency.  Per element the k order is unchanged: e = 0 .. 3 inside a group, groups in order.
+    auto group = [&](const f32x4 (&fa)[MB], const f32x4 (&fb)[NBW], f32x4 (&na)[MB], f32x4 (&nb)[NBW], int kk_next, int e0 = 0,
+                     int e1 = 4) {
+#pragma unroll
+        for (int e = e0; e < e1; ++e)
 #pragma unroll
             for (int i = 0; i < MB; ++i)
 #pragma unroll
-                for (int j = 0; j < NBW; ++j)
+                for (int j = 0; j < NBW; ++j) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][e], fa[i][e], acc[i][j], 0, 0, 0);   // swapped: D = W A^T
+                    const int n = (e * MB + i) * NBW + j;
+                    if (kk_next >= 0 && n < MB + NBW) rd1(na, nb, kk_next, n);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
     };
 
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // slabs 0 and 1 landed (loaders waited)
@@ -228,11 +251,7 @@ __global__ __launch_bounds__(512, 1) void gemm4_kernel(const GemmParams p, const
     if (dbg) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
 
     int ks = 0, stage = 0, tile_i = 0;
-    rd(fa0, fb0, 0, 0);
-    // scheduling recipe for one fragment group: its MB + NBW reads (of the NEXT group) go out one per MFMA right at the
-    // start of this group's 4 * MB * NBW MFMAs; left to itself the compiler sinks them to the end of the MFMA block and
-    // the next group then waits out the LDS latency (~120 cycles per group); A/B in one session: 0-4 % faster
-    auto interleave = [&]() { g4_sched_interleave<0, MB + NBW, 4 * MB * NBW>(); };
+    rd(fa0, fb0, 0);
     f32x4 radd[RESP ? MB : 1][RESP ? NBW : 1];
     auto load_res = [&](int tile) {
         if constexpr (RESP) {
@@ -250,20 +269,36 @@ __global__ __launch_bounds__(512, 1) void gemm4_kernel(const GemmParams p, const
     load_res(lid);
     for (int g = 0; g < total; ++g) {
         const int nstage = stage == NST - 1 ? 0 : stage + 1;
-        rd(fa1, fb1, stage, 1);
-        mm(fa0, fb0);
-        interleave();
-        if (KK == 4) {
-            rd(fa0, fb0, stage, 2);
-            mm(fa1, fb1);
-            interleave();
-            rd(fa1, fb1, stage, 3);
-            mm(fa0, fb0);
-            interleave();
+        lds_cptr a_nx = a_ad, b_nx = b_ad;
+        if constexpr (NST == 2) {
+            // the next stage's addresses, computed while the wave waits for the reads it issued behind the barrier (free there;
+            // between the barrier and those reads they delayed every step), and pinned in front of the first MFMA's wait
+            a_nx = a_lane + nstage * STAGE_BYTES;
+            b_nx = b_lane + nstage * STAGE_BYTES;
+            asm volatile("" : "+v"(a_nx), "+v"(b_nx));
+            __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (NST >= 3) rd(fa0, fb0, nstage, 0);      // next slab's first group: landed before the last barrier
-        mm(fa1, fb1);                                         // (past the last slab: a stale stage, never used)
-        if constexpr (NST >= 3) interleave();
+        group(fa0, fb0, fa1, fb1, 1);
+        if (KK == 4) {
+            group(fa1, fb1, fa0, fb0, 2);
+            group(fa0, fb0, fa1, fb1, 3);
+        }
+        if constexpr (NST >= 3) {
+            // the next slab's first group: landed before the last barrier (past the last slab: a stale stage, never used)
+            to_stage(nstage);
+            group(fa1, fb1, fa0, fb0, 0);
+        } else {
+            // two stages: slab g+1 lands DURING step g, so its first group can only be read behind the step's barrier.  The
+            // step's last MB * NBW MFMAs (k index 3 of the last group) need registers only: they run behind the barrier and the
+            // reads, where the wave used to sit out the LDS latency.  The stage is free for the loaders as before: every read
+            // of it has returned (lgkmcnt(0)) when the barrier is reached.
+            group(fa1, fb1, fa0, fb0, -1, 0, 3);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            a_ad = a_nx; b_ad = b_nx;
+            rd(fa0, fb0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            group(fa1, fb1, fa0, fb0, -1, 3, 4);
+        }
         if (++ks == nk) {
             ks = 0;
             // ---- epilogue straight from the accumulators.  The MFMA runs swapped (weight fragment = A operand), so a
@@ -354,9 +389,8 @@ __global__ __launch_bounds__(512, 1) void gemm4_kernel(const GemmParams p, const
             }
         }
         // the loaders have waited for slab g+2 before this barrier; step g+1 prefetches from it
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if constexpr (NST >= 3) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         stage = nstage;
-        if constexpr (NST == 2) rd(fa0, fb0, stage, 0);       // the slab that landed during the step
     }
     if (dbg && blockIdx.x == 0 && tid == 0) {                 // diagnostic stamps (gdx_bench_gemm + GDX_GEMM_DEBUG)
         dbg[0] = __builtin_amdgcn_s_memtime() - t0;
