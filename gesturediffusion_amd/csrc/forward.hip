@@ -144,14 +144,11 @@ int gdx::forward_core(gdx_model* h, const float* x, const float* temb, int tstri
     const void* lc_stream = res32 ? (const void*)h->xa.f : (const void*)h->xa.h;
     void* lc_xc = h->f16 ? (void*)h->xc.h : (void*)h->xc.f;
     if (lc != LC_OFF) {
-        if (lc == LC_PARTIAL && (!h->lc_valid || !h->lc_delta)) return fail("forward_core: a partial call without a stored layer change");
-        if (!h->lc_delta) {
-            const size_t rows = 2 * (size_t)B * S;
-            if (ws_alloc(h, "layer cache", (void**)&h->lc_delta, sizeof(float) * 2 * B * T * d) ||
-                ws_alloc(h, "layer cache", &h->lc_in, rows * d * (res32 ? 4 : 2)))
-                return -1;
-            HIPCHK(hipStreamSynchronize(nullptr));                 // the fills are on the null stream, the first store on s
-        }
+        if (lc == LC_PARTIAL && (!h->late.lc_valid || !h->late.lc_delta))
+            return fail("forward_core: a partial call without a stored layer change");
+        if (ws_need(h, &h->late.lc_delta, sizeof(float) * 2 * B * T * d, s) ||
+            ws_need(h, &h->late.lc_in, 2 * (size_t)B * S * d * (res32 ? 4 : 2), s))
+            return -1;
     }
     const float* seed_emb = mode == GDX_UNCOND ? h->seed_cat + (size_t)B * d : h->seed_cat;
     const int N = Beff * S;
@@ -201,15 +198,15 @@ int gdx::forward_core(gdx_model* h, const float* x, const float* temb, int tstri
         if (tap(l + 1)) return -1;
         // layer cache, full call: the stream after layer lc_keep - 1 outlives the deeper layers, which overwrite xa
         if (lc == LC_FULL && l + 1 == h->lc_keep)
-            HIPCHK(hipMemcpyAsync(h->lc_in, lc_stream, (size_t)N * d * (res32 ? 4 : 2), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(h->late.lc_in, lc_stream, (size_t)N * d * (res32 ? 4 : 2), hipMemcpyDeviceToDevice, s));
     }
     if (lc == LC_FULL) {                                          // change of layers lc_keep .. L-1 on the rows the output GEMM reads
-        if (layer_delta(0, lc_in_dt, lc_out_dt, Beff, T, d, h->lc_in, lc_xc, h->lc_delta, s)) return -1;
-        h->lc_valid = true; h->lc_mode = mode;
+        if (layer_delta(0, lc_in_dt, lc_out_dt, Beff, T, d, h->late.lc_in, lc_xc, h->late.lc_delta, s)) return -1;
+        h->late.lc_valid = true; h->late.lc_mode = mode;
     }
     // partial call: the operand from this call's own shallow layers plus the stored change (a GDX_COND call under a stored
     // GDX_CFG reads the conditional rows, the first B)
-    if (lc == LC_PARTIAL && layer_delta(1, lc_in_dt, lc_out_dt, Beff, T, d, lc_stream, lc_xc, h->lc_delta, s)) return -1;
+    if (lc == LC_PARTIAL && layer_delta(1, lc_in_dt, lc_out_dt, Beff, T, d, lc_stream, lc_xc, h->late.lc_delta, s)) return -1;
     if (h->keep_taps) {                                           // tap L + 1: the output GEMM's operand, widened
         if (h->f16) HIPCHK(HFN(h->bf16, launch_convert_f32, h->xc.h, h->taps[h->L + 1], (int64_t)Beff * T * d, s));
         else HIPCHK(hipMemcpyAsync(h->taps[h->L + 1], h->xc.f, sizeof(float) * (size_t)Beff * T * d, hipMemcpyDeviceToDevice, s));
@@ -238,14 +235,14 @@ extern "C" int gdx_layer_delta(int32_t op, int32_t in_dtype, int32_t out_dtype, 
 // lo <= t[b] <= hi.  The chunk sums and factors belong to the handle (first use allocates, gdx_prepare resets).
 int gdx::rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s) {
     const size_t per = (size_t)h->J * h->T, chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
-    if (!h->rs_part && dev_alloc(h->ws_allocs, (void**)&h->rs_part, sizeof(double) * 4 * h->B * chunks)) return -1;
-    if (!h->rs_factor && dev_alloc(h->ws_allocs, (void**)&h->rs_factor, sizeof(float) * h->B)) return -1;
+    if (ws_need(h, &h->late.rs_part, sizeof(double) * 4 * h->B * chunks, s) || ws_need(h, &h->late.rs_factor, sizeof(float) * h->B, s))
+        return -1;
     gdx_cfg_rescale_args_t r;
     memset(&r, 0, sizeof(r));
     r.batch = h->B; r.njoints = h->J; r.frames = h->T;
     r.x0_cond = c; r.x0_uncond = u; r.scale = scale; r.phi = h->guide_phi;
     r.t = t; r.lo = h->guide_lo; r.hi = h->guide_hi;
-    r.workspace = h->rs_part; r.factor = h->rs_factor; r.out = out;
+    r.workspace = h->late.rs_part; r.factor = h->late.rs_factor; r.out = out;
     return gdx_cfg_rescale(&r, (void*)s);
 }
 

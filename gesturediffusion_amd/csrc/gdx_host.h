@@ -108,6 +108,29 @@ struct WeightSpec {
     int group = 0;                     // place in the "missing weights" report (the table itself is in packed-image order)
 };
 
+// Workspace the handle acquires after gdx_prepare, each buffer on first use (ws_need) by the call that needs it, with the host-side
+// facts about that memory.  gdx_prepare frees the pool and resets all of this with ONE assignment: a new field needs no reset line.
+struct LateWorkspace {
+    float* temb_table = nullptr; int temb_table_rows = 0;   // step tables (loops.hip: build_step_tables), regrown for a longer loop
+    float* c2t_table = nullptr; bool c2t_valid = false;     // V2: W_coa * temb_table rows (valid while c2t_valid)
+    bool tables_valid = false;        // temb_table (and c2t_table) hold the rows of tmap_host under the current weights
+    int64_t* tmap_dev = nullptr; std::vector<int64_t> tmap_host;
+    float *bpd_xt = nullptr, *bpd_z = nullptr, *bpd_part = nullptr;   // gdx_bpd_loop: x_t, Philox noise [B, J, T], chunk sums
+    // gdx_parallel_loop (B = window x samples): the window's predictions [B, J, T], the sweep's errors [B] and chunk sums, the scales
+    // repeated per slot [B], and the model timestep of every slot the loop can reach, [steps + window][samples] (what pl_ts_host holds)
+    float *pl_x0 = nullptr, *pl_scale = nullptr; double *pl_err = nullptr, *pl_part = nullptr;
+    int64_t* pl_ts = nullptr; size_t pl_ts_cap = 0;
+    std::vector<int64_t> pl_ts_host;
+    double* rs_part = nullptr; float* rs_factor = nullptr;   // guidance rescale: chunk sums [B][chunks][4] and factors [B]
+    float* gd = nullptr;              // guidance refresh: the stored difference c - u [B, J, T]
+    bool gd_valid = false;            // ... holds a refresh call's difference under the current conditioning
+    float* lc_delta = nullptr;        // layer cache: the stored change [2B, T, d]
+    void* lc_in = nullptr;            // ... and the residual stream after layer lc_keep - 1 [2B, T+1, d] in the stream's element
+                                      // type, kept until the end of a full call
+    bool lc_valid = false;            // ... lc_delta holds a full call's change under the current conditioning,
+    int lc_mode = 0;                  // ... stored by a call of this forward mode (GDX_COND / GDX_UNCOND / GDX_CFG)
+};
+
 }  // namespace gdx
 
 struct gdx_model {
@@ -133,18 +156,9 @@ struct gdx_model {
     bool cond_set = false;
     int64_t guide_lo = INT64_MIN, guide_hi = INT64_MAX;   // gdx_set_guidance_interval: model timesteps that get guidance
     float guide_phi = 0.f;            // gdx_set_guidance_rescale: 0 = off
-    double* rs_part = nullptr;        // guidance rescale: chunk sums [B][chunks][4] and factors [B], allocated on first use
-    float* rs_factor = nullptr;
     int guide_every = 1;              // gdx_set_guidance_refresh: the unconditional pass runs on every guide_every-th guided call
-    float* gd = nullptr;              // guidance refresh: the stored difference c - u [B, J, T], allocated on first use
-    bool gd_valid = false;            // ... holds a refresh call's difference under the current conditioning
     int lc_every = 1, lc_keep = 0;    // gdx_set_layer_cache: every lc_every-th denoiser call of a loop is full; the calls between
                                       // run lc_keep layers and add the stored change of the deeper ones (1 = off)
-    float* lc_delta = nullptr;        // layer cache: the stored change [2B, T, d], allocated on first use
-    void* lc_in = nullptr;            // ... and the residual stream after layer lc_keep - 1 [2B, T+1, d] in the stream's element
-                                      // type, kept until the end of a full call
-    bool lc_valid = false;            // ... lc_delta holds a full call's change under the current conditioning,
-    int lc_mode = 0;                  // ... stored by a call of this forward mode (GDX_COND / GDX_UNCOND / GDX_CFG)
     int64_t forward_samples = 0;     // gdx_forward_samples: samples pushed through forward_core since gdx_create
     int64_t forward_layer_samples = 0;   // gdx_forward_layer_samples: samples x encoder layers launched
     gdx::Act xa, xb, qkv, ctx, tmp, ffb;   // [rows_alloc] token rows: residual stream (xa, xb), sublayer operands and outputs
@@ -155,19 +169,7 @@ struct gdx_model {
     float* x0 = nullptr;              // [2B, J, T]
     float* x0t = nullptr;             // token-major x0
     int ldo = 0;                      // row stride of x0t = J rounded up to 64
-    float* temb_table = nullptr; int temb_table_rows = 0;
-    float* c2t_table = nullptr;       // V2: W_coa * temb_table rows (valid while c2t_valid)
     float* c2_seed = nullptr;         // V2: W_coa * seed_cat rows [2B, d]
-    bool c2t_valid = false;
-    bool tables_valid = false;        // temb_table (and c2t_table) hold the rows of tmap_host under the current weights
-    std::vector<int64_t> tmap_host;
-    float *bpd_xt = nullptr, *bpd_z = nullptr, *bpd_part = nullptr;   // gdx_bpd_loop: x_t, Philox noise [B, J, T], chunk sums
-    // gdx_parallel_loop (B = window x samples): the window's predictions [B, J, T], the sweep's errors [B] and chunk sums, the scales
-    // repeated per slot [B], and the model timestep of every slot the loop can reach, [steps + window][samples] (what pl_ts_host holds)
-    float *pl_x0 = nullptr, *pl_scale = nullptr;
-    double *pl_err = nullptr, *pl_part = nullptr;
-    int64_t* pl_ts = nullptr; size_t pl_ts_cap = 0;
-    std::vector<int64_t> pl_ts_host;
     // graph replay of launch-bound loops (gdx_sample_loop)
     bool graph_replay = false;        // gdx_set_graph_replay
     int* gstate = nullptr;            // device {schedule index, executed-step number}
@@ -175,7 +177,6 @@ struct gdx_model {
     hipEvent_t gev_in = nullptr, gev_out = nullptr;
     hipGraph_t ggraph = nullptr;
     hipGraphExec_t gexec = nullptr;
-    int64_t* tmap_dev = nullptr;
     bool prof = false;                // in-situ FFN-1 GEMM timing (gdx_profile_begin / gdx_profile_end)
     std::vector<hipEvent_t> prof_ev;  // pairs, recorded around each FFN-1 launch while prof is on
     size_t prof_used = 0;
@@ -183,6 +184,7 @@ struct gdx_model {
     std::vector<float*> taps;         // [L+1] x [2B*S*d] when keep_taps
     bool guards = false;              // gdx_set_guards: every workspace allocation carries a canary zone behind it
     std::vector<std::pair<unsigned char*, size_t>> guard_zones;
+    gdx::LateWorkspace late;
 };
 
 namespace gdx {
@@ -190,8 +192,13 @@ namespace gdx {
 void describe_weights(gdx_model* h);
 
 // handle.hip
-// A zero-filled workspace buffer of the handle, with its canary zone behind it under gdx_set_guards (`who`: the entry that asks)
-int ws_alloc(gdx_model* h, const char* who, void** p, size_t bytes);
+// A workspace buffer of the handle, zero-filled on s, the stream of the call that asks, which orders the fill ahead of that call's
+// first store; under gdx_set_guards with its canary zone behind it.  The only function that adds to h->ws_allocs.
+int ws_alloc(gdx_model* h, void** p, size_t bytes, hipStream_t s);
+// ... on first use: nothing to do once *p is set (the fields of h->late)
+template <class T> int ws_need(gdx_model* h, T** p, size_t bytes, hipStream_t s) {
+    return *p ? 0 : ws_alloc(h, (void**)p, bytes, s);
+}
 int check_ready(gdx_model* h, const char* who);                   // handle, gdx_prepare and a conditioning, or the refusal
 int check_mode(const char* who, int mode, const float* scale);
 

@@ -98,15 +98,19 @@ extern "C" int gdx_destroy(gdx_handle_t h) {
     return 0;
 }
 
-int gdx::ws_alloc(gdx_model* h, const char* who, void** p, size_t bytes) {
+int gdx::ws_alloc(gdx_model* h, void** p, size_t bytes, hipStream_t s) {
     if (dev_alloc(h->ws_allocs, p, bytes + (h->guards ? GUARD_BYTES : 0))) return -1;
-    if (hipMemset(*p, 0, bytes) != hipSuccess) return fail(std::string(who) + ": hipMemset failed");
-    if (h->guards) {
-        unsigned char* g = (unsigned char*)*p + bytes;
-        if (hipMemset(g, GUARD_BYTE, GUARD_BYTES) != hipSuccess) return fail(std::string(who) + ": hipMemset failed");
-        h->guard_zones.emplace_back(g, bytes);
-    }
+    unsigned char* g = (unsigned char*)*p + bytes;
+    if (h->guards) h->guard_zones.emplace_back(g, bytes);
+    if (hipMemsetAsync(*p, 0, bytes, s) != hipSuccess || (h->guards && hipMemsetAsync(g, GUARD_BYTE, GUARD_BYTES, s) != hipSuccess))
+        return fail("workspace: hipMemsetAsync failed");
     return 0;
+}
+
+// Results stored under another conditioning, shape or setting are not reused: the refresh's difference, the layer cache's change
+static void forget_stored(gdx_model* h, bool difference = true, bool change = true) {
+    if (difference) h->late.gd_valid = false;
+    if (change) h->late.lc_valid = false;
 }
 
 extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
@@ -117,17 +121,11 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     if (h->pe && frames + 1 > h->pe_rows) return fail("gdx_prepare: frames exceed positional table");
     if (h->cfg.arch == GDX_ARCH_MDM && h->rope_cos && frames + 1 > h->rope_rows)
         return fail("gdx_prepare: frames exceed rotary table");
-    h->gd_valid = false;                                          // guidance refresh: a stored difference never outlives a prepare
-    h->lc_valid = false;                                          // layer cache: nor does a stored change
+    forget_stored(h);                                             // also by a prepare that keeps the shape (and the step tables)
     if (h->B == batch && h->T == frames) return 0;
     free_pool(h->ws_allocs);
-    h->guard_zones.clear();
-    h->taps.clear();
-    h->temb_table = nullptr; h->temb_table_rows = 0; h->tmap_dev = nullptr; h->c2t_table = nullptr; h->c2t_valid = false;
-    h->tables_valid = false;
-    h->bpd_xt = h->bpd_z = h->bpd_part = nullptr;
-    h->pl_x0 = h->pl_scale = nullptr; h->pl_err = h->pl_part = nullptr; h->pl_ts = nullptr; h->pl_ts_cap = 0; h->pl_ts_host.clear();
-    h->rs_part = nullptr; h->rs_factor = nullptr; h->gd = nullptr; h->lc_delta = nullptr; h->lc_in = nullptr;
+    h->late = {};                                                 // everything that pointed into the pool
+    h->guard_zones.clear(); h->taps.clear();
     // the shape is recorded only once every allocation has succeeded: after a failed hipMalloc a retry with the same
     // shape must allocate again instead of returning early on partial buffers
     h->B = 0; h->T = 0; h->S = frames + 1; h->cond_set = false;
@@ -136,7 +134,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     const size_t B2 = 2 * (size_t)batch, N = B2 * h->S + GDX_ROW_PAD, d = h->d;
     h->rows_alloc = (long)N;
     // zero-filled: the padding rows are read by whole-tile GEMMs / K-V tiles and must stay finite
-    auto raw = [&](void** p, size_t bytes) { return ws_alloc(h, "gdx_prepare", p, bytes); };
+    auto raw = [&](void** p, size_t bytes) { return ws_alloc(h, p, bytes, nullptr); };
     auto A = [&](float** p, size_t n) { return raw((void**)p, n * sizeof(float)); };
     // the sides of an activation pair this mode uses; every fp32 side is allocated before the first 16-bit one, in the order below
     // (the order of the guard zones gdx_check_guards reports)
@@ -170,8 +168,8 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
         for (auto& t : h->taps)
             if (A(&t, N * d)) return -1;
     }
-    // the fills are on the null stream and hipMemset returns before they have run when that stream is busy; the first stores
-    // (gdx_set_condition) are on the caller's stream, which nothing orders behind the null stream when it is non-blocking
+    // gdx_prepare takes no stream: its fills are on the null stream, and nothing orders the first stores (gdx_set_condition, on the
+    // caller's stream) behind that stream when the caller's is non-blocking
     HIPCHK(hipStreamSynchronize(nullptr));
     h->B = batch; h->T = frames;
     return 0;
@@ -195,6 +193,9 @@ extern "C" int gdx_set_guards(gdx_handle_t h, int32_t on) {
 extern "C" int gdx_check_guards(gdx_handle_t h, int64_t* bad_bytes, int32_t* first_bad_zone, void* stream) {
     if (!h || !bad_bytes) return fail("gdx_check_guards: null argument");
     if (!h->guards) return fail("gdx_check_guards: guards are off (gdx_set_guards)");
+    if (h->guard_zones.size() != h->ws_allocs.size())            // ws_alloc alone adds to either
+        return fail("gdx_check_guards: " + std::to_string(h->ws_allocs.size()) + " workspace allocations but " +
+                    std::to_string(h->guard_zones.size()) + " guard zones: an allocation did not go through ws_alloc");
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     std::vector<unsigned char> host(GUARD_BYTES);
     int64_t bad = 0;
@@ -238,8 +239,7 @@ static int finish_condition(gdx_model* h, const float* mfcc, hipStream_t s) {
         HIPCHK(launch_small_linear(h->seed_cat, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2_seed, d, 2 * B, d, d, 0, s));
     }
     h->cond_set = true;
-    h->gd_valid = false;                                          // guidance refresh: the difference of another conditioning
-    h->lc_valid = false;                                          // layer cache: the change under another conditioning
+    forget_stored(h);
     return 0;
 }
 
@@ -311,7 +311,7 @@ extern "C" int gdx_set_guidance_refresh(gdx_handle_t h, int32_t every) {
     if (!h) return fail("gdx_set_guidance_refresh: null handle");
     if (every < 1) return fail("gdx_set_guidance_refresh: every must be at least 1");
     h->guide_every = every;
-    h->gd_valid = false;
+    forget_stored(h, true, false);
     return 0;
 }
 
@@ -328,7 +328,7 @@ extern "C" int gdx_set_layer_cache(gdx_handle_t h, int32_t every, int32_t keep) 
     if (every > 1 && (keep < 1 || keep > h->L - 1))
         return fail("gdx_set_layer_cache: keep must lie in 1 .. num_layers - 1 = " + std::to_string(h->L - 1));
     h->lc_every = every; h->lc_keep = every > 1 ? keep : 0;
-    h->lc_valid = false;
+    forget_stored(h, false, true);
     return 0;
 }
 

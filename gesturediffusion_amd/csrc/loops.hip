@@ -22,11 +22,11 @@ template <typename A>
 static int plan_block(const gdx_model* h, const char* who, const A* a, int last_idx, bool two_calls, CallPlan* p) {
     const CallSeq q{a->mode, a->timestep_map, a->num_steps, a->first_index, a->k_base, last_idx, two_calls};
     if (!plan_loop(plan_rule(h), q, p)) return fail(std::string(who) + ": bad step range");
-    if (p->begins_with_reuse() && !h->gd_valid)
+    if (p->begins_with_reuse() && !h->late.gd_valid)
         return fail(std::string(who) + ": a guided call would reuse the guidance difference, but none is stored: a block-wise "
                     "call (run_steps / k_base) must continue the loop that stored the difference");
     const PlannedCall& e = p->step(a->k_base);
-    if (e.lc == LC_PARTIAL && !(h->lc_valid && h->lc_mode == e.K))
+    if (e.lc == LC_PARTIAL && !(h->late.lc_valid && h->late.lc_mode == e.K))
         return fail(std::string(who) + ": a partial call would add the stored change of the deep layers, but none of the planned mode "
                     "is stored: a block-wise call (run_steps / k_base) must continue the loop that stored the change");
     return 0;
@@ -44,14 +44,11 @@ static int guided_operands(gdx_model* h, int m, const float* scale, hipStream_t 
     float* u = h->x0 + n;
     if (m != GDX_CFG) {
         // guidance refresh: a refresh stores d = c - u; a reuse, whose forward left only c, forms u' = c - d in u's place
-        if (!h->gd) {
-            if (ws_alloc(h, "guidance refresh", (void**)&h->gd, sizeof(float) * n)) return -1;
-            HIPCHK(hipStreamSynchronize(nullptr));                 // the fill is on the null stream, the first store on s
-        }
+        if (ws_need(h, &h->late.gd, sizeof(float) * n, s)) return -1;
         const bool store = m == MODE_CFG_REFRESH;
-        const gdx_cfg_delta_args_t g{(int64_t)n, h->x0, store ? u : h->gd, store ? h->gd : u};
+        const gdx_cfg_delta_args_t g{(int64_t)n, h->x0, store ? u : h->late.gd, store ? h->late.gd : u};
         if (gdx_cfg_delta(&g, (void*)s)) return -1;
-        if (store) h->gd_valid = true;
+        if (store) h->late.gd_valid = true;
     }
     if (h->guide_phi > 0.0f) return rescale_x0(h, h->x0, u, scale, nullptr, h->x0, s);
     *x0_uncond = u; *sc = scale;
@@ -61,39 +58,37 @@ static int guided_operands(gdx_model* h, int m, const float* scale, hipStream_t 
 // timestep-embedding table (and, V2, its W_coa image) for every kept step of a loop, shared by gdx_sample_loop and gdx_bpd_loop
 static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timestep_map, hipStream_t s) {
     const int d = h->d;
+    const bool v2 = h->cfg.arch == GDX_ARCH_MDM;
+    LateWorkspace& lw = h->late;
     // timestep-embedding table for every kept step, once per loop (same t for the whole batch:
     // gaussian_diffusion.py:712), through the respacing map (respace.py:124-129)
-    if (h->temb_table_rows < num_steps) {
-        float* t3 = nullptr;
-        // + GDX_ROW_PAD rows behind the last of the three tables: the table linears run on the persistent GEMM, which
-        // reads / stores whole tiles
-        if (dev_alloc(h->ws_allocs, (void**)&t3, sizeof(float) * (3 * (size_t)num_steps + GDX_ROW_PAD) * d)) return -1;
-        HIPCHK(hipMemsetAsync(t3, 0, sizeof(float) * (3 * (size_t)num_steps + GDX_ROW_PAD) * d, s));
-        if (h->cfg.arch == GDX_ARCH_MDM && dev_alloc(h->ws_allocs, (void**)&h->c2t_table, sizeof(float) * ((size_t)num_steps + GDX_ROW_PAD) * d))
+    if (lw.temb_table_rows < num_steps) {
+        // regrown: the outgrown tables stay in the pool until the next gdx_prepare.  + GDX_ROW_PAD rows behind the last of the
+        // three tables: the table linears run on the persistent GEMM, which reads / stores whole tiles
+        lw.temb_table_rows = 0; lw.tables_valid = lw.c2t_valid = false;          // until all three stand
+        if (ws_alloc(h, (void**)&lw.temb_table, sizeof(float) * (3 * (size_t)num_steps + GDX_ROW_PAD) * d, s) ||
+            (v2 && ws_alloc(h, (void**)&lw.c2t_table, sizeof(float) * ((size_t)num_steps + GDX_ROW_PAD) * d, s)) ||
+            ws_alloc(h, (void**)&lw.tmap_dev, sizeof(int64_t) * num_steps, s))
             return -1;
-        if (dev_alloc(h->ws_allocs, (void**)&h->tmap_dev, sizeof(int64_t) * num_steps)) return -1;
-        h->temb_table = t3;
-        h->temb_table_rows = num_steps;
-        h->tables_valid = false; h->c2t_valid = false;
+        lw.temb_table_rows = num_steps;
     }
-    float* table = h->temb_table;
+    float* table = lw.temb_table;
     // the tables depend on the weights and the timestep map only: a loop run in blocks (run_steps) builds them once
-    const bool tables_live = h->tables_valid && (int)h->tmap_host.size() == num_steps &&
-                             !memcmp(h->tmap_host.data(), timestep_map, sizeof(int64_t) * num_steps) &&
-                             (h->cfg.arch != GDX_ARCH_MDM || h->c2t_valid);
+    const bool tables_live = lw.tables_valid && (int)lw.tmap_host.size() == num_steps &&
+                             !memcmp(lw.tmap_host.data(), timestep_map, sizeof(int64_t) * num_steps) && (!v2 || lw.c2t_valid);
     if (tables_live) return 0;
-    h->tmap_host.assign(timestep_map, timestep_map + num_steps);
-    HIPCHK(hipMemcpyAsync(h->tmap_dev, h->tmap_host.data(), sizeof(int64_t) * num_steps, hipMemcpyHostToDevice, s));
-    float* scratch0 = table + (size_t)h->temb_table_rows * d;
-    float* scratch1 = scratch0 + (size_t)h->temb_table_rows * d;
-    if (time_embed(h, h->tmap_dev, num_steps, scratch0, scratch1, table, s)) return -1;
-    if (h->cfg.arch == GDX_ARCH_MDM) {
+    lw.tmap_host.assign(timestep_map, timestep_map + num_steps);
+    HIPCHK(hipMemcpyAsync(lw.tmap_dev, lw.tmap_host.data(), sizeof(int64_t) * num_steps, hipMemcpyHostToDevice, s));
+    float* scratch0 = table + (size_t)lw.temb_table_rows * d;
+    float* scratch1 = scratch0 + (size_t)lw.temb_table_rows * d;
+    if (time_embed(h, lw.tmap_dev, num_steps, scratch0, scratch1, table, s)) return -1;
+    if (v2) {
         // timestep half of the coarse slice of project_to_lat for every kept step, once per loop (same kernel as
         // gdx_forward's per-sample rows)
-        HIPCHK(launch_small_linear(table, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2t_table, d, num_steps, d, d, 0, s));
-        h->c2t_valid = true;
+        HIPCHK(launch_small_linear(table, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, lw.c2t_table, d, num_steps, d, d, 0, s));
+        lw.c2t_valid = true;
     }
-    h->tables_valid = true;
+    lw.tables_valid = true;
     return 0;
 }
 
@@ -102,7 +97,8 @@ static int build_step_tables(gdx_model* h, int num_steps, const int64_t* timeste
 static int denoise_step(gdx_model* h, const float* x, const PlannedCall& e, float* x0_out, hipStream_t s, const int* state = nullptr,
                         bool tm = false) {
     const size_t row = (size_t)e.idx * h->d;
-    return forward_core(h, x, h->temb_table + row, 0, h->c2t_table ? h->c2t_table + row : nullptr, forward_mode(e.mode), x0_out, s,
+    const LateWorkspace& lw = h->late;
+    return forward_core(h, x, lw.temb_table + row, 0, lw.c2t_table ? lw.c2t_table + row : nullptr, forward_mode(e.mode), x0_out, s,
                         {.state = state, .tm = tm, .lc = e.lc});
 }
 
@@ -132,21 +128,22 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_bpd_loop: mask without motion");
     hipStream_t s = (hipStream_t)stream;
     const int B = h->B;
+    LateWorkspace& lw = h->late;
     const size_t per = (size_t)h->J * h->T;
     const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
-    if (!h->bpd_xt && dev_alloc(h->ws_allocs, (void**)&h->bpd_xt, sizeof(float) * B * per)) return -1;
-    if (!h->bpd_part && dev_alloc(h->ws_allocs, (void**)&h->bpd_part, sizeof(float) * 4 * B * chunks)) return -1;
-    if (!a->noise_tape && !h->bpd_z && dev_alloc(h->ws_allocs, (void**)&h->bpd_z, sizeof(float) * B * per)) return -1;
+    if (ws_need(h, &lw.bpd_xt, sizeof(float) * B * per, s) || ws_need(h, &lw.bpd_part, sizeof(float) * 4 * B * chunks, s) ||
+        (!a->noise_tape && ws_need(h, &lw.bpd_z, sizeof(float) * B * per, s)))
+        return -1;
     if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
     gdx_bpd_args_t u;
     memset(&u, 0, sizeof(u));
     u.batch = B; u.njoints = h->J; u.frames = h->T;
-    u.coef = a->coef; u.x_start = a->x_start; u.x_t = h->bpd_xt;
+    u.coef = a->coef; u.x_start = a->x_start; u.x_t = lw.bpd_xt;
     u.x0_cond = h->x0;
     u.inpaint_mask = a->inpaint_mask; u.inpaint_motion = a->inpaint_motion;
     u.clip_denoised = a->clip_denoised;
     u.vb = a->vb; u.xstart_mse = a->xstart_mse; u.mse = a->mse; u.ld = a->num_steps;
-    u.workspace = h->bpd_part;
+    u.workspace = lw.bpd_part;
     const int k_end = a->run_steps > 0 ? a->k_base + a->run_steps : a->num_steps;
     // no guidance refresh here: the steps draw independent x_t, so every guided call is a full one
     const CallPlan plan = plan_unnumbered(plan_rule(h), a->mode, a->timestep_map, a->num_steps - 1 - a->k_base, k_end - a->k_base, -1);
@@ -154,14 +151,13 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
         const int idx = a->num_steps - 1 - k;
         if (a->noise_tape) {
             u.noise = tape_slice(a->noise_tape, k, a->k_base, B, per);
-            if (gdx_q_sample(a->x_start, u.noise, a->coef, idx, (int64_t)(B * per), h->bpd_xt, stream)) return -1;
+            if (gdx_q_sample(a->x_start, u.noise, a->coef, idx, (int64_t)(B * per), lw.bpd_xt, stream)) return -1;
         } else {
-            u.noise = h->bpd_z;
-            if (gdx_bpd_xt_(a->x_start, a->coef, idx, B, (long)per, a->philox_seed, a->sample_offset, (uint32_t)k, h->bpd_z, h->bpd_xt,
-                            stream))
+            u.noise = lw.bpd_z;
+            if (gdx_bpd_xt_(a->x_start, a->coef, idx, B, (long)per, a->philox_seed, a->sample_offset, (uint32_t)k, lw.bpd_z, lw.bpd_xt, stream))
                 return -1;
         }
-        if (denoise_guided(h, plan.calls[k - a->k_base], a->scale, h->bpd_xt, s, &u.x0_uncond, &u.scale)) return -1;
+        if (denoise_guided(h, plan.calls[k - a->k_base], a->scale, lw.bpd_xt, s, &u.x0_uncond, &u.scale)) return -1;
         u.step_index = idx; u.col = k;
         if (gdx_bpd_terms(&u, stream)) return -1;
     }
@@ -374,40 +370,37 @@ extern "C" int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int
     const size_t per = (size_t)h->J * h->T, plane = (size_t)B * per;
     const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
     *iterations_out = 0;
-    if (!h->pl_x0) {
-        if (ws_alloc(h, who, (void**)&h->pl_x0, sizeof(float) * WB * per) || ws_alloc(h, who, (void**)&h->pl_scale, sizeof(float) * WB) ||
-            ws_alloc(h, who, (void**)&h->pl_err, sizeof(double) * WB) || ws_alloc(h, who, (void**)&h->pl_part, sizeof(double) * WB * chunks))
-            return -1;
-        HIPCHK(hipStreamSynchronize(nullptr));                     // the fills are on the null stream, the first store on s
-    }
+    LateWorkspace& lw = h->late;
+    if (ws_need(h, &lw.pl_x0, sizeof(float) * WB * per, s) || ws_need(h, &lw.pl_scale, sizeof(float) * WB, s) ||
+        ws_need(h, &lw.pl_err, sizeof(double) * WB, s) || ws_need(h, &lw.pl_part, sizeof(double) * WB * chunks, s))
+        return -1;
     // the model timestep of executed step k for every k a slot can name, one row of B per step: the window at anchor a reads rows
     // a .. a + W - 1 as its W x B timesteps; rows behind the last step (ignored tail slots) run at index 0
     std::vector<int64_t> ts((size_t)(K + window) * B);
     for (int k = 0; k < K + window; ++k)
         std::fill_n(ts.begin() + (size_t)k * B, B, timestep_map[k < K ? first_index - k : 0]);
-    if (h->pl_ts_cap < ts.size()) {
-        if (dev_alloc(h->ws_allocs, (void**)&h->pl_ts, sizeof(int64_t) * ts.size())) return -1;
-        h->pl_ts_cap = ts.size();
-        h->pl_ts_host.clear();
+    if (lw.pl_ts_cap < ts.size()) {                                // regrown, like the step tables
+        if (ws_alloc(h, (void**)&lw.pl_ts, sizeof(int64_t) * ts.size(), s)) return -1;
+        lw.pl_ts_cap = ts.size(); lw.pl_ts_host.clear();
     }
-    if (h->pl_ts_host != ts) {
-        HIPCHK(hipStreamSynchronize(s));                           // an earlier call's forwards may still read the rows
-        HIPCHK(hipMemcpy(h->pl_ts, ts.data(), sizeof(int64_t) * ts.size(), hipMemcpyHostToDevice));
-        h->pl_ts_host.swap(ts);
+    if (lw.pl_ts_host != ts) {
+        HIPCHK(hipStreamSynchronize(s));                           // an earlier call may still read the rows, or this one's fill run
+        HIPCHK(hipMemcpy(lw.pl_ts, ts.data(), sizeof(int64_t) * ts.size(), hipMemcpyHostToDevice));
+        lw.pl_ts_host.swap(ts);
     }
     if (mode == GDX_CFG)
         for (int j = 0; j < window; ++j)
-            HIPCHK(hipMemcpyAsync(h->pl_scale + (size_t)j * B, scale, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(lw.pl_scale + (size_t)j * B, scale, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
     std::vector<double> err((size_t)window * B);
     int a = *anchor, it = 0;
     while (a < K && (max_iterations == 0 || it < max_iterations)) {
         const int n = std::min(window, K - a);
-        if (gdx_forward(h, planes, h->pl_ts + (size_t)a * B, mode, mode == GDX_CFG ? h->pl_scale : nullptr, h->pl_x0, stream)) return -1;
-        if (gdx_window_sweep(kind, B, h->J, h->T, n, coef, first_index - a, planes, h->pl_x0, inpaint_mask, inpaint_motion, clip_denoised,
+        if (gdx_forward(h, planes, lw.pl_ts + (size_t)a * B, mode, mode == GDX_CFG ? lw.pl_scale : nullptr, lw.pl_x0, stream)) return -1;
+        if (gdx_window_sweep(kind, B, h->J, h->T, n, coef, first_index - a, planes, lw.pl_x0, inpaint_mask, inpaint_motion, clip_denoised,
                              noise_tape ? noise_tape + (size_t)a * plane : nullptr, philox_seed, sample_offset, (uint32_t)(a + 1),
-                             h->pl_err, h->pl_part, stream))
+                             lw.pl_err, lw.pl_part, stream))
             return -1;
-        HIPCHK(hipMemcpyAsync(err.data(), h->pl_err, sizeof(double) * n * B, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(err.data(), lw.pl_err, sizeof(double) * n * B, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         const int stride = window_stride(err.data(), B, n, threshold, first_index - a);
         if (gdx_window_slide_(planes, (long)plane, window, stride, stream)) return -1;
@@ -520,7 +513,8 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
                             h->lc_every == 1;                     // the layer cache's calls differ from one another: eager
     int idx = a->first_index, k = a->k_base;
     if (want_graph) {
-        if (eager_step(idx, k)) return -1;                        // step 0 eagerly: it also sets every kernel attribute
+        // step 0 eagerly: it sets every kernel attribute and acquires the late workspace, so the captured step never allocates
+        if (eager_step(idx, k)) return -1;
         --idx; ++k;
         bool ok = true;
         if (!h->gstream) {

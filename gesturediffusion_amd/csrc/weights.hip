@@ -149,8 +149,8 @@ void describe_weights(gdx_model* h) {
 // whatever depends on the weights (the conditioning terms, the loops' timestep tables) has to be rebuilt
 static void weights_changed(gdx_model* h) {
     h->cond_set = false;
-    h->c2t_valid = false;
-    h->tables_valid = false;
+    h->late.c2t_valid = false;
+    h->late.tables_valid = false;
 }
 
 }  // namespace gdx

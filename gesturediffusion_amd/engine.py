@@ -245,8 +245,7 @@ class Engine:
     def set_guards(self, on=True):
         """Test aid: canary zones behind every workspace buffer (gdx_set_guards)."""
         _lib.check(self.lib.gdx_set_guards(self.handle, int(bool(on))), self.lib)
-        self.shape = self.shape          # the workspace was re-allocated: conditioning must be set again
-        self._cond_key = None
+        self._cond_key = None            # the workspace was re-allocated: conditioning must be set again
 
     def check_guards(self, device):
         bad, first = C.c_int64(), C.c_int32()

@@ -16,9 +16,8 @@
  * null stream, a blocking or a non-blocking one (PyTorch's side streams are non-blocking), and the result has the same bits on
  * each.  The calls on ONE handle must be ordered by the caller -- one stream, or the caller's own events between streams: the
  * handle's workspace is shared by all of them.  Two handles may run on two streams at once.  gdx_prepare (which takes no
- * stream) and the first use of a feature that needs further workspace (the guidance refresh, the layer cache, the guidance
- * rescale, gdx_bpd_loop, gdx_parallel_loop) may allocate and synchronise: gdx_prepare, the guidance refresh, the layer cache and
- * gdx_parallel_loop zero what they allocate on the null stream and wait for that stream before their first store on `stream`.
+ * stream) zeroes what it allocates on the null stream and waits for that stream.  Workspace that a later call needs (its first
+ * use of a feature, a loop with more steps than before) is allocated by that call and zeroed on that call's `stream`.
  * The entries that say "synchronises" wait for `stream`.  Nothing else waits.
  * tests/test_gpu_streams.py runs every entry with a `stream` on a non-default stream against its default-stream bits.
  *
@@ -322,9 +321,9 @@ int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timesteps, int32_
 int gdx_set_keep_taps(gdx_handle_t h, int32_t keep);
 int gdx_get_tap(gdx_handle_t h, int32_t which, float* out, int64_t count, void* stream);
 
-/* Test aid: with guards on, every workspace buffer gdx_prepare allocates is followed by a 64 KiB canary zone;
- * gdx_check_guards synchronises `stream` and counts canary bytes that were overwritten (0 = no kernel stored past
- * a buffer).  first_bad_zone (optional) = allocation order index of the first damaged zone, -1 if none. */
+/* Test aid: with guards on, every workspace buffer, whenever it is allocated, is followed by a 64 KiB canary
+ * zone; gdx_check_guards synchronises `stream` and counts canary bytes that were overwritten (0 = no kernel stored past
+ * a buffer); it fails when a workspace allocation has no zone.  first_bad_zone (optional) = allocation order index of the first damaged zone, -1 if none. */
 int gdx_set_guards(gdx_handle_t h, int32_t on);
 int gdx_check_guards(gdx_handle_t h, int64_t* bad_bytes, int32_t* first_bad_zone, void* stream);
 

@@ -271,6 +271,33 @@ def test_training_losses_kl_vs_reference_fixture(arch, loss):
     assert list(terms) == ["loss"] and bool((err <= allow).all())
 
 
+@pytest.mark.parametrize("arch,T", [("mdm", 20), ("mdm_old", 12)])
+def test_guided_bpd_loop_leaves_the_workspace_guards_intact(arch, T):
+    """gdx_bpd_loop under gdx_set_guards, guided (so that the loops' guided_operands runs), B = 2, ten steps: once on a noise tape
+    (x_t and the chunk sums are allocated) and once with rng="philox" (the noise buffer too), each buffer with its canary zone.
+    No canary byte changes, no workspace allocation is without a zone (gdx_check_guards refuses that), and vb / xstart_mse / mse
+    have the bits of the unguarded runs."""
+    from test_gpu_guidance_interval import _cfg, _df, _inputs, _model, _ys
+    m, d = _model(arch, "fp32"), dev()
+    eng = m._get_engine(d)
+    df, i = _df("p"), _inputs(T)[1]
+    noise = {"tape": dict(noise_tape=i["tape"][:10].contiguous()), "philox": dict(rng="philox", philox_seed=11)}
+
+    def run(kw):
+        return df.calc_bpd_loop(_cfg(m), i["x_start"], clip_denoised=True, model_kwargs={"y": _ys(T)[0]}, **kw)
+    plain = {k: run(kw) for k, kw in noise.items()}
+    eng.set_guards(True)
+    try:
+        for k, kw in noise.items():
+            r = run(kw)
+            bad, zone = eng.check_guards(d)
+            assert bad == 0, f"{k}: {bad} canary bytes overwritten, first in workspace allocation #{zone}"
+            for name in ("vb", "xstart_mse", "mse"):
+                assert torch.isfinite(r[name]).all() and torch.equal(r[name], plain[k][name]), (k, name)
+    finally:
+        eng.set_guards(False)
+
+
 def test_bpd_loop_refusals():
     """The refusals of gdx_bpd_loop that need a handle: call before gdx_prepare, bad step range, CFG without scale."""
     import ctypes as C

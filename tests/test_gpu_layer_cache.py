@@ -1,7 +1,7 @@
 """Layer cache on the GPU (y['layer_cache'], gdx_set_layer_cache, gdx_layer_delta, gdx_forward_layer_samples, tap L + 1;
 include/gdx.h): the stand-alone pass against torch, no key / every = 1 against today's loops, full and partial calls through the
-taps bit for bit, the encoder layers actually skipped, the same bits along every route, the CPU restatement, workspace guards
-and the CLI.
+taps bit for bit, the encoder layers actually skipped, the same bits along every route, the CPU restatement, workspace guards,
+every feature with late workspace on a handle prepared for another shape and back, and the CLI.
 
 Loops: the TINY model (L = 2, so keep = 1; golden weights), inputs, samplers and schedules of test_gpu_guidance_interval.py
 (B = 2, scales (2.5, -1.0), 10 steps), plus UniPC on the DPM schedule, and a 4-layer variant of TINY (keep in {1, 2, 3})
@@ -499,6 +499,55 @@ def test_cached_loops_leave_the_workspace_guards_intact(arch, T, dtype):
                     assert torch.equal(r, plain[sampler, j]), (sampler, j)
         finally:
             eng.set_guards(False)
+
+
+# ---------------------------------------------------------------------- 7b. a handle prepared for another shape and back again
+def _bpd(model, y, T):
+    r = _df("p").calc_bpd_loop(model, _inputs(T)[1]["x_start"], clip_denoised=True, model_kwargs={"y": y}, rng="philox", philox_seed=SEED)
+    return torch.stack([r[k] for k in ("vb", "xstart_mse", "mse")])
+
+
+def _parallel(model, y, T):
+    tape = _inputs(T)[1]["tape"]
+    return _df("p").parallel_sample_loop(model, tuple(tape.shape[1:]), clip_denoised=False, model_kwargs={"y": y}, window=4,
+                                         tolerance=0.0, noise_tape=tape)
+
+
+# the features whose workspace the handle acquires after gdx_prepare: (the run, its keys in y)
+LATE = {"step_tables": (functools.partial(_run, "ddim"), {}),
+        "bpd_loop": (_bpd, {}),
+        "parallel_loop": (_parallel, {}),
+        "guidance_rescale": (functools.partial(_run, "ddim"), dict(guidance_rescale=0.7)),
+        "guidance_refresh": (functools.partial(_run, "ddim"), dict(guidance_refresh=2)),
+        "layer_cache": (functools.partial(_run, "ddim"), dict(layer_cache=(2, 1)))}
+
+
+@pytest.mark.parametrize("feature", list(LATE))
+def test_a_handle_prepared_for_another_shape_and_back_repeats_its_result(feature):
+    """Each feature that owns late workspace (the step tables of a plain gdx_sample_loop, gdx_bpd_loop with Philox noise,
+    gdx_parallel_loop at tolerance 0, the guidance rescale, the guidance refresh, the layer cache), guided, on a handle of its own:
+    run it, prepare the handle for another (B, T) -- which frees the workspace and with it every late buffer --, run it again (the
+    loop prepares the handle back and conditions it again): the bits of the first run, and those of a fresh handle."""
+    run, keys = LATE[feature]
+    arch, T = "mdm", 20
+    y = dict(_ys(T)[0], **keys)
+
+    def fresh():
+        m = build_model(arch, TINY, weights_from(load_golden(f"loops_{arch}_tiny.npz")))
+        m.compute_dtype = "fp32"
+        return m
+    m = fresh()
+    first = run(_cfg(m), y, T)
+    eng = m._get_engine(dev())
+    shape = eng.shape
+    eng.prepare(3, 30)
+    assert shape in ((B, T), (4 * B, T)) and eng.shape == (3, 30)
+    again = run(_cfg(m), y, T)
+    assert eng.shape == shape
+    other = run(_cfg(fresh()), y, T)
+    assert torch.isfinite(first).all()
+    assert torch.equal(again, first), feature
+    assert torch.equal(other, first), feature
 
 
 # --------------------------------------------------------------------------------------------------------------------- 8. CLI

@@ -879,9 +879,10 @@ def test_first_prepare_behind_a_busy_default_stream():
 
 @pytest.mark.parametrize("cid", ["loop/sample/layer_cache/mdm/fp32", "loop/parallel/tol0/mdm/fp32", "loop/bpd/cfg/mdm/fp32"])
 def test_late_allocation_behind_a_busy_default_stream(cid):
-    """The first layer-cache call, the first gdx_parallel_loop and the first gdx_bpd_loop of a handle allocate and fill on the null
-    stream, then wait for it (hipStreamSynchronize(nullptr)) because their first store is on the caller's stream.  With the default
-    stream busy and the call on a side stream, a fill that landed late would wipe what the loop had stored."""
+    """The first layer-cache call, the first gdx_parallel_loop and the first gdx_bpd_loop of a handle allocate their workspace and
+    zero it on the caller's stream (ws_alloc: hipMemsetAsync on the stream of the call that asks), so the stream itself orders the
+    fill ahead of the call's first store and nothing waits.  With the default stream busy and the call on a side stream, a fill
+    left on the null stream would land late and wipe what the loop had stored."""
     case = build(cid)
     X, ref, _ = reference(case)
     state = case.setup()
