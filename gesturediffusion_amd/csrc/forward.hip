@@ -133,7 +133,7 @@ int gdx::forward_core(gdx_model* h, const float* x, const float* temb, int tstri
                       hipStream_t s, const ForwardOpts& o) {
     const auto [state, tm, lc] = o;
     const int B = h->B, T = h->T, S = h->S, d = h->d, J = h->J;
-    const int Beff = mode == GDX_CFG ? 2 * B : B;
+    const int Beff = mode == GDX_CFG ? h->groups() * B : B;      // guided: row groups F, U -- or F, M, U (gdx_set_guidance_compose)
     const int layers = lc == LC_PARTIAL ? h->lc_keep : h->L;     // encoder layers this call launches
     h->forward_samples += Beff;                                   // gdx_forward_samples (host side only)
     h->forward_layer_samples += (int64_t)Beff * layers;           // gdx_forward_layer_samples
@@ -150,7 +150,8 @@ int gdx::forward_core(gdx_model* h, const float* x, const float* temb, int tstri
             ws_need(h, &h->late.lc_in, 2 * (size_t)B * S * d * (res32 ? 4 : 2), s))
             return -1;
     }
-    const float* seed_emb = mode == GDX_UNCOND ? h->seed_cat + (size_t)B * d : h->seed_cat;
+    const size_t uncond_rows = (size_t)h->u_group() * B * d;     // GDX_UNCOND: the all-dropped rows U, wherever the mode keeps them
+    const float* seed_emb = mode == GDX_UNCOND ? h->seed_cat + uncond_rows : h->seed_cat;
     const int N = Beff * S;
     // the encoder stream as the sublayers write it: in the 16-bit stream its fp32 side only for the parity taps
     const Act xa{!h->f16 || h->stream32 || h->keep_taps ? h->xa.f : nullptr, h->xa.h};
@@ -164,7 +165,7 @@ int gdx::forward_core(gdx_model* h, const float* x, const float* temb, int tstri
     } else {
         // coarse slice of project_to_lat = W_coa temb (c2t, from the caller) + W_coa seed_emb (c2_seed, per conditioning)
         if (!c2t) return fail("forward_core: V2 needs the W_coa * temb rows");
-        const float* c2s = mode == GDX_UNCOND ? h->c2_seed + (size_t)B * d : h->c2_seed;
+        const float* c2s = mode == GDX_UNCOND ? h->c2_seed + uncond_rows : h->c2_seed;
         HIPCHK(HFN(h->bf16, launch_token0, temb, tstride, seed_emb, nullptr, h->xa.f, h->xa.h, c2t, c2s, h->c2, state, Beff, B, S, d, s));
         if (linear(h, h->xt, h->in_x, {.bias = h->in_x.bias}, h->emb, d, Beff * T, d, s)) return -1;
         // proj_pose writes the operand the front end's kernel reads: 16-bit xseq.h, or fp32 xseq.f for the fp32 kernels
@@ -233,7 +234,8 @@ extern "C" int gdx_layer_delta(int32_t op, int32_t in_dtype, int32_t out_dtype, 
 
 // gdx_cfg_rescale on the handle's buffers: c, u -> out for the B samples of the workspace, guided where t == nullptr or
 // lo <= t[b] <= hi.  The chunk sums and factors belong to the handle (first use allocates, gdx_prepare resets).
-int gdx::rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s) {
+int gdx::rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s,
+                    const float* g) {
     const size_t per = (size_t)h->J * h->T, chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
     if (ws_need(h, &h->late.rs_part, sizeof(double) * 4 * h->B * chunks, s) || ws_need(h, &h->late.rs_factor, sizeof(float) * h->B, s))
         return -1;
@@ -243,7 +245,17 @@ int gdx::rescale_x0(gdx_model* h, const float* c, const float* u, const float* s
     r.x0_cond = c; r.x0_uncond = u; r.scale = scale; r.phi = h->guide_phi;
     r.t = t; r.lo = h->guide_lo; r.hi = h->guide_hi;
     r.workspace = h->late.rs_part; r.factor = h->late.rs_factor; r.out = out;
-    return gdx_cfg_rescale(&r, (void*)s);
+    return gdx_cfg_rescale_(&r, g, (void*)s);
+}
+
+// With phi > 0 the composed prediction is formed in the M third, which nothing reads afterwards, and the rescale reads c = F beside it
+int gdx::compose_x0(gdx_model* h, const float* scale, const int64_t* t, float* out, hipStream_t s) {
+    const int64_t per = (int64_t)h->J * h->T;
+    const size_t n = (size_t)h->B * per;
+    float *F = h->x0, *M = F + n, *U = M + n;
+    const bool rescale = h->guide_phi > 0.0f;
+    HIPCHK(launch_cfg_compose(F, M, U, scale, scale + h->B, t, h->guide_lo, h->guide_hi, rescale ? M : out, h->B, per, s));
+    return rescale ? rescale_x0(h, F, nullptr, nullptr, t, out, s, M) : 0;
 }
 
 // timestep embedding rows for idx[M] (model/mdm.py:296-310): pe gather -> Linear -> SiLU -> Linear.  The same
@@ -262,6 +274,8 @@ extern "C" int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timest
     if (check_ready(h, "gdx_forward")) return -1;
     if (!x || !timesteps || !out) return fail("gdx_forward: null argument");
     if (check_mode("gdx_forward", mode, scale)) return -1;
+    const bool three = mode == GDX_CFG && h->three_pass();
+    if (three && h->B > 65535) return fail("gdx_forward: batch exceeds 65535 (3-pass guidance)");
     hipStream_t s = (hipStream_t)stream;
     if (time_embed(h, timesteps, h->B, h->temb_in, h->temb_h, h->temb, s)) return -1;
     const float* c2t = nullptr;
@@ -271,6 +285,7 @@ extern "C" int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timest
     }
     if (mode != GDX_CFG) return forward_core(h, x, h->temb, h->d, c2t, mode, out, s);
     if (forward_core(h, x, h->temb, h->d, c2t, mode, h->x0, s)) return -1;
+    if (three) return compose_x0(h, scale, timesteps, out, s);
     const int64_t per = (int64_t)h->J * h->T;
     // the timesteps are on the device: the double batch stays, the blend selects per sample (guided: blend, else c)
     if (h->guide_phi > 0.0f) return rescale_x0(h, h->x0, h->x0 + (size_t)h->B * per, scale, timesteps, out, s);

@@ -150,12 +150,14 @@ struct gdx_model {
     std::vector<gdx::Layer> layers;
     float* pe = nullptr; int pe_rows = 0;
     float *rope_cos = nullptr, *rope_sin = nullptr; int rope_rows = 0;
-    // workspace (sized for 2*B samples so that CFG runs as one double batch)
+    // workspace (sized for G*B samples so that CFG runs as one batch of G row groups: 2, or 3 in a 3-pass compose mode)
     int B = 0, T = 0, S = 0;
-    long rows_alloc = 0;              // rows of the [2B*S + pad] token buffers
+    int G = 2;                        // row groups the workspace is prepared for (groups())
+    long rows_alloc = 0;              // rows of the [G*B*S + pad] token buffers
     bool cond_set = false;
     int64_t guide_lo = INT64_MIN, guide_hi = INT64_MAX;   // gdx_set_guidance_interval: model timesteps that get guidance
     float guide_phi = 0.f;            // gdx_set_guidance_rescale: 0 = off
+    int guide_compose = GDX_GUIDE_JOINT;   // gdx_set_guidance_compose: which passes a guided call contrasts (gdx.h)
     int guide_every = 1;              // gdx_set_guidance_refresh: the unconditional pass runs on every guide_every-th guided call
     int lc_every = 1, lc_keep = 0;    // gdx_set_layer_cache: every lc_every-th denoiser call of a loop is full; the calls between
                                       // run lc_keep layers and add the stored change of the deeper ones (1 = off)
@@ -166,10 +168,15 @@ struct gdx_model {
     gdx::Act emb, xseq;                    // V2 front end: InputProcess output, proj_pose output
     float* addend = nullptr;
     float *seed_cat = nullptr, *temb_in = nullptr, *temb_h = nullptr, *temb = nullptr, *coa = nullptr, *c2 = nullptr;
-    float* x0 = nullptr;              // [2B, J, T]
+    float* x0 = nullptr;              // [G*B, J, T]
     float* x0t = nullptr;             // token-major x0
     int ldo = 0;                      // row stride of x0t = J rounded up to 64
-    float* c2_seed = nullptr;         // V2: W_coa * seed_cat rows [2B, d]
+    float* c2_seed = nullptr;         // V2: W_coa * seed_cat rows [3B, d]
+    // guidance compose: the passes of a guided call are row groups F, then M (a 3-pass mode's middle pass, or the contrast of modes
+    // 1 and 2), then U; JOINT has no M and keeps U in group 1
+    bool three_pass() const { return guide_compose >= GDX_GUIDE_SEED_TEXT; }
+    int groups() const { return three_pass() ? 3 : 2; }
+    int u_group() const { return guide_compose == GDX_GUIDE_JOINT ? 1 : 2; }   // where GDX_UNCOND finds the all-dropped rows
     // graph replay of launch-bound loops (gdx_sample_loop)
     bool graph_replay = false;        // gdx_set_graph_replay
     int* gstate = nullptr;            // device {schedule index, executed-step number}
@@ -211,5 +218,10 @@ struct ForwardOpts {
 int forward_core(gdx_model* h, const float* x, const float* temb, int tstride, const float* c2t, int mode, float* x0_out,
                  hipStream_t s, const ForwardOpts& o = {});
 int time_embed(gdx_model* h, const int64_t* idx, int M, float* gathered, float* hidden, float* out, hipStream_t s);
-int rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s);
+// g != nullptr: the guided prediction is already formed (compose_x0) and u / scale are not read
+int rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s,
+               const float* g = nullptr);
+// a guided 3-pass call's prediction from the three thirds (F, M, U) of h->x0 and scale [2][B] (gdx.h gdx_set_guidance_compose),
+// rescaled under the handle's phi > 0; guided where t == nullptr or lo <= t[b] <= hi, else F.  out may be the F third.
+int compose_x0(gdx_model* h, const float* scale, const int64_t* t, float* out, hipStream_t s);
 }  // namespace gdx

@@ -202,6 +202,11 @@ hipError_t launch_advance_state(int* st, hipStream_t s);
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
                             float* out, int B, int64_t per_sample, hipStream_t s);
 
+// out = g1 + s1[b]*(f - m) with g1 = u + s0[b]*(m - u) where t == nullptr or lo <= t[b] <= hi, else f (gdx_set_guidance_compose's
+// 3-pass rule); grid.y = sample, so B <= 65535; out may alias f, m or u
+hipError_t launch_cfg_compose(const float* f, const float* m, const float* u, const float* s0, const float* s1, const int64_t* t,
+                              int64_t lo, int64_t hi, float* out, int B, int64_t per_sample, hipStream_t s);
+
 // argument of update_tm_kernel (sampler.hip): one step of gdx_sample_loop's token-major fast path, filled by loops.hip
 struct UpdateTmDev {
     int kind, B, J, T, ldx, ldo;
@@ -248,5 +253,7 @@ int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per
                 uint32_t step, float* z_out, float* xt_out, void* stream);
 // gdx_parallel_loop: the window's planes [W + 1][plane] slid down by `stride` planes, the tail filled with P_W (window_slide_kernel)
 int gdx_window_slide_(float* planes, long plane, int W, int stride, void* stream);
+// gdx_cfg_rescale with the guided prediction g given instead of blended from (x0_uncond, scale), which may then be NULL
+int gdx_cfg_rescale_(const gdx_cfg_rescale_args_t* a, const float* g, void* stream);
 // records the text of gdx_last_error and returns -1 (handle.hip), for the files that do not include gdx_host.h
 extern "C" int gdx_set_error_(const char* msg);

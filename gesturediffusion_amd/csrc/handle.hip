@@ -122,7 +122,7 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     if (h->cfg.arch == GDX_ARCH_MDM && h->rope_cos && frames + 1 > h->rope_rows)
         return fail("gdx_prepare: frames exceed rotary table");
     forget_stored(h);                                             // also by a prepare that keeps the shape (and the step tables)
-    if (h->B == batch && h->T == frames) return 0;
+    if (h->B == batch && h->T == frames && h->G == h->groups()) return 0;
     free_pool(h->ws_allocs);
     h->late = {};                                                 // everything that pointed into the pool
     h->guard_zones.clear(); h->taps.clear();
@@ -131,7 +131,9 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     h->B = 0; h->T = 0; h->S = frames + 1; h->cond_set = false;
     // + GDX_ROW_PAD rows: the persistent GEMM reads / stores whole tiles past the last logical row (gemm2.hip; its
     // tallest tile is checked against the pad at compile time)
-    const size_t B2 = 2 * (size_t)batch, N = B2 * h->S + GDX_ROW_PAD, d = h->d;
+    // B2: the samples of the largest forward, G row groups (2; 3 in a 3-pass compose mode).  The conditioning rows always have
+    // room for three groups: modes 1 and 2 run two but keep the all-dropped rows in a third for GDX_UNCOND
+    const size_t B2 = (size_t)h->groups() * batch, B3 = 3 * (size_t)batch, N = B2 * h->S + GDX_ROW_PAD, d = h->d;
     h->rows_alloc = (long)N;
     // zero-filled: the padding rows are read by whole-tile GEMMs / K-V tiles and must stay finite
     auto raw = [&](void** p, size_t bytes) { return ws_alloc(h, p, bytes, nullptr); };
@@ -143,9 +145,9 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     };
     const bool half = h->f16, f32 = !half, v2 = h->cfg.arch == GDX_ARCH_MDM;
     const bool res32 = f32 || h->stream32;                         // the residual stream is fp32 (add_norm)
-    if (act(h->xa, N * d, true, false) || A(&h->addend, N * d) || A(&h->seed_cat, B2 * d) || A(&h->temb_in, B2 * d) ||
+    if (act(h->xa, N * d, true, false) || A(&h->addend, N * d) || A(&h->seed_cat, B3 * d) || A(&h->temb_in, B2 * d) ||
         A(&h->temb_h, B2 * d) || A(&h->temb, B2 * d) || A(&h->coa, B2 * d) || A(&h->c2, (B2 + 1) * d) ||
-        A(&h->c2_seed, B2 * d) ||
+        A(&h->c2_seed, B3 * d) ||
         A(&h->x0, B2 * h->J * (size_t)frames))
         return -1;
     if (act(h->xb, N * d, res32, false) || act(h->qkv, N * 3 * d, f32, false) || act(h->ctx, N * d, f32, false) ||
@@ -171,18 +173,23 @@ extern "C" int gdx_prepare(gdx_handle_t h, int32_t batch, int32_t frames) {
     // gdx_prepare takes no stream: its fills are on the null stream, and nothing orders the first stores (gdx_set_condition, on the
     // caller's stream) behind that stream when the caller's is non-blocking
     HIPCHK(hipStreamSynchronize(nullptr));
-    h->B = batch; h->T = frames;
+    h->B = batch; h->T = frames; h->G = h->groups();
     return 0;
+}
+
+// the workspace again at the current shape, after a setting that shapes it has changed
+static int reprepare(gdx_model* h) {
+    const int B = h->B, T = h->T;
+    if (!B) return 0;
+    h->B = 0;
+    return gdx_prepare(h, B, T);
 }
 
 // gdx_set_guards / gdx_set_keep_taps: the flag shapes the workspace, so a change re-prepares it at the current shape
 static int set_workspace_flag(gdx_model* h, bool& flag, bool on) {
     if (flag == on) return 0;
     flag = on;
-    const int B = h->B, T = h->T;
-    if (!B) return 0;
-    h->B = 0;
-    return gdx_prepare(h, B, T);
+    return reprepare(h);
 }
 
 extern "C" int gdx_set_guards(gdx_handle_t h, int32_t on) {
@@ -218,25 +225,27 @@ extern "C" int gdx_set_keep_taps(gdx_handle_t h, int32_t keep) {
 extern "C" int gdx_get_tap(gdx_handle_t h, int32_t which, float* out, int64_t count, void* stream) {
     if (!h || !out) return fail("gdx_get_tap: null argument");
     if (!h->keep_taps || which < 0 || which > h->L + 1 || h->taps.empty()) return fail("gdx_get_tap: taps not kept");
-    const int64_t maxc = 2LL * h->B * h->S * h->d;
+    const int64_t maxc = (int64_t)h->G * h->B * h->S * h->d;
     if (count > maxc) return fail("gdx_get_tap: count too large");
     HIPCHK(hipMemcpyAsync(out, h->taps[which], count * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
-// what a conditioning does once seed_cat holds its 2B rows: the audio term, the seed half of the coarse slice, the flags
+// what a conditioning does once seed_cat holds its rows (2B under JOINT, else the 3B of F, M, U): the audio term of every row group
+// of a forward (audio is never dropped), the seed half of the coarse slice, the flags
 static int finish_condition(gdx_model* h, const float* mfcc, hipStream_t s) {
     const int B = h->B, T = h->T, S = h->S, d = h->d;
+    const int GB = h->G * B, rows = (h->u_group() + 1) * B;
     if (h->cfg.arch == GDX_ARCH_MDM_OLD) {
         // addend[b, t+1, :] = W_in[:, J:] mfcc[b,:,t] + b_in + pe[t+1]      (model/mdm_old.py:104-112)
-        HIPCHK(launch_mfcc_project(mfcc, h->in_mfcc.w, h->in_mfcc.kpad, h->in_x.bias, h->pe, h->addend, 2 * B, B,
+        HIPCHK(launch_mfcc_project(mfcc, h->in_mfcc.w, h->in_mfcc.kpad, h->in_x.bias, h->pe, h->addend, GB, B,
                                    h->cfg.mfcc_dim, T, d, S, 1, s));
     } else {
         // audio_term[b*T+t, :] = W_proj[:, d:d+26] mfcc[b,:,t] + b_proj     (model/mdm.py:151-169)
         HIPCHK(launch_mfcc_project(mfcc, h->proj_audio.w, h->proj_audio.kpad, h->proj_pose.bias, nullptr, h->addend,
-                                   2 * B, B, h->cfg.mfcc_dim, T, d, T, 0, s));
-        // seed half of the coarse slice of project_to_lat (model/mdm.py:154-169), cond and uncond rows
-        HIPCHK(launch_small_linear(h->seed_cat, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2_seed, d, 2 * B, d, d, 0, s));
+                                   GB, B, h->cfg.mfcc_dim, T, d, T, 0, s));
+        // seed half of the coarse slice of project_to_lat (model/mdm.py:154-169), the rows of every group
+        HIPCHK(launch_small_linear(h->seed_cat, d, h->proj_coa.w, h->proj_coa.kpad, nullptr, h->c2_seed, d, rows, d, d, 0, s));
     }
     h->cond_set = true;
     forget_stored(h);
@@ -269,11 +278,19 @@ extern "C" int gdx_set_condition_text(gdx_handle_t h, const float* seed, const f
     // row b = [embed_text(text_b) | seed_embed(seed_b)]: two Linears into one row of stride d   (model/mdm.py:118-127,154-155)
     HIPCHK(launch_small_linear(text, cd, h->text.w, h->text.kpad, h->text.bias, h->seed_cat, d, B, td, cd, 0, s));
     HIPCHK(launch_small_linear(seed, ks, h->seed.w, h->seed.kpad, h->seed.bias, h->seed_cat + td, d, B, d - td, ks, 0, s));
-    // uncond rows B..2B-1: both inputs zeroed before their Linear = [embed_text.bias | seed_embed.bias]: the same launches over
-    // no input column (K = 0)
-    float* un = h->seed_cat + (size_t)B * d;
+    // uncond rows (group 1 under JOINT, else group 2): both inputs zeroed before their Linear = [embed_text.bias | seed_embed.bias]:
+    // the same launches over no input column (K = 0)
+    float* un = h->seed_cat + (size_t)h->u_group() * B * d;
     HIPCHK(launch_small_linear(text, cd, h->text.w, h->text.kpad, h->text.bias, un, d, B, td, 0, 0, s));
     HIPCHK(launch_small_linear(seed, ks, h->seed.w, h->seed.kpad, h->seed.bias, un + td, d, B, d - td, 0, 0, s));
+    if (h->guide_compose != GDX_GUIDE_JOINT) {
+        // group 1 = M, one input dropped (gdx_set_guidance_compose): S = [embed_text.bias | seed_embed(seed)] where the text is the
+        // steered condition (TEXT, SEED_TEXT), X = [embed_text(text) | seed_embed.bias] where the seed is (SEED, TEXT_SEED)
+        const bool drop_text = h->guide_compose == GDX_GUIDE_TEXT || h->guide_compose == GDX_GUIDE_SEED_TEXT;
+        float* mid = h->seed_cat + (size_t)B * d;
+        HIPCHK(launch_small_linear(text, cd, h->text.w, h->text.kpad, h->text.bias, mid, d, B, td, drop_text ? 0 : cd, 0, s));
+        HIPCHK(launch_small_linear(seed, ks, h->seed.w, h->seed.kpad, h->seed.bias, mid + td, d, B, d - td, drop_text ? ks : 0, 0, s));
+    }
     return finish_condition(h, mfcc, s);
 }
 
@@ -296,6 +313,19 @@ extern "C" int gdx_set_guidance_interval(gdx_handle_t h, int64_t lo, int64_t hi)
     if (!h) return fail("gdx_set_guidance_interval: null handle");
     h->guide_lo = lo; h->guide_hi = hi;
     return 0;
+}
+
+// Per-condition guidance (gdx.h): which passes a guided call contrasts.  Refusals precede any HIP call; the conditioning rows
+// depend on the mode, so the caller conditions again, and the number of row groups shapes the workspace
+extern "C" int gdx_set_guidance_compose(gdx_handle_t h, int32_t mode) {
+    if (!h) return fail("gdx_set_guidance_compose: null handle");
+    if (mode < GDX_GUIDE_JOINT || mode > GDX_GUIDE_TEXT_SEED) return fail("gdx_set_guidance_compose: unknown mode");
+    if (mode != GDX_GUIDE_JOINT && h->cfg.text_dim == 0)
+        return fail("gdx_set_guidance_compose: this handle has no text (text_dim = 0): one droppable condition, nothing to compose");
+    h->guide_compose = mode;
+    h->cond_set = false;
+    forget_stored(h);
+    return h->G == h->groups() ? 0 : reprepare(h);
 }
 
 // Guidance rescale (gdx.h): per-handle phi, 0 = off.  Refusals precede any HIP call.
@@ -375,7 +405,7 @@ extern "C" int gdx_forward_flops(gdx_handle_t h, int32_t mode, double* flops) {
     if (!h || !flops) return fail("gdx_forward_flops: null argument");
     if (!h->B) return fail("gdx_forward_flops: call gdx_prepare first");
     // SURVEY.md section 8d
-    const double B = (mode == GDX_CFG ? 2.0 : 1.0) * h->B, T = h->T, S = h->S, d = h->d, J = h->J, ff = h->ff;
+    const double B = (mode == GDX_CFG ? (double)h->groups() : 1.0) * h->B, T = h->T, S = h->S, d = h->d, J = h->J, ff = h->ff;
     const double N = B * S, Sp = h->cfg.seed_poses, mf = h->cfg.mfcc_dim;
     double f = 2 * B * d * d * 2 + 2 * B * J * Sp * d;
     if (h->cfg.arch == GDX_ARCH_MDM)

@@ -14,12 +14,26 @@ static_assert(MODE_COND == GDX_COND && MODE_UNCOND == GDX_UNCOND && MODE_CFG == 
 
 static PlanRule plan_rule(const gdx_model* h) { return {h->guide_lo, h->guide_hi, h->guide_every, h->lc_every}; }
 
+// A guided loop of entry `who` on a handle in a 3-pass compose mode (gdx.h gdx_set_guidance_compose): the refresh's stored
+// difference and the layer cache's stored change are written for two row groups, so either is refused, before the first launch
+static int compose_conflict(const gdx_model* h, const char* who, int mode) {
+    if (mode != GDX_CFG || !h->three_pass()) return 0;
+    if (h->guide_every > 1)
+        return fail(std::string(who) + ": the guidance refresh (gdx_set_guidance_refresh, every > 1) stores one cond-uncond difference; a "
+                    "3-pass guidance compose mode (gdx_set_guidance_compose) has two: set every = 1");
+    if (h->lc_every > 1)
+        return fail(std::string(who) + ": the layer cache (gdx_set_layer_cache, every > 1) holds two row groups; a 3-pass guidance compose "
+                    "mode (gdx_set_guidance_compose) runs three: set every = 1");
+    return 0;
+}
+
 // The plan of the loop that block a (steps first_index .. last_idx) of entry `who` belongs to, and the refusals a block can meet
 // there, all before the call's first launch: a numbering that needs a first index outside the schedule; a first guided call that
 // would reuse a difference nobody stored; a first call that is partial while the stored change is missing or of another mode
 // than the plan's.
 template <typename A>
 static int plan_block(const gdx_model* h, const char* who, const A* a, int last_idx, bool two_calls, CallPlan* p) {
+    if (compose_conflict(h, who, a->mode)) return -1;
     const CallSeq q{a->mode, a->timestep_map, a->num_steps, a->first_index, a->k_base, last_idx, two_calls};
     if (!plan_loop(plan_rule(h), q, p)) return fail(std::string(who) + ": bad step range");
     if (p->begins_with_reuse() && !h->late.gd_valid)
@@ -40,6 +54,8 @@ static int plan_block(const gdx_model* h, const char* who, const A* a, int last_
 static int guided_operands(gdx_model* h, int m, const float* scale, hipStream_t s, const float** x0_uncond, const float** sc) {
     *x0_uncond = nullptr; *sc = nullptr;
     if (m < GDX_CFG) return 0;
+    // 3-pass compose mode (never under the refresh: compose_conflict): composed, and rescaled under phi > 0, in place on the cond third
+    if (h->three_pass()) return compose_x0(h, scale, nullptr, h->x0, s);
     const size_t n = (size_t)h->B * h->J * h->T;
     float* u = h->x0 + n;
     if (m != GDX_CFG) {
@@ -360,6 +376,9 @@ extern "C" int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int
     if (h->lc_every > 1)
         return fail(w + "the layer cache (gdx_set_layer_cache, every > 1) needs memory across sequential denoiser calls; the "
                         "window's calls are not sequential: set every = 1");
+    if (mode == GDX_CFG && h->three_pass())
+        return fail(w + "a 3-pass guidance compose mode (gdx_set_guidance_compose) is not supported by the parallel loop, whose "
+                        "window repeats one scale per slot: use GDX_GUIDE_JOINT, _TEXT or _SEED");
     if (check_ready(h, who)) return -1;
     if (h->B % window)
         return fail(w + "the handle is prepared for " + std::to_string(h->B) + " samples, which window = " + std::to_string(window) +
@@ -476,8 +495,9 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     // refresh, whose calls also run eagerly under graph replay (the stored difference is host-tracked state)
     const bool rescales = h->guide_phi > 0.0f && any_guided;
     const bool refreshes = h->guide_every > 1 && any_guided;
+    const bool composes = h->three_pass() && any_guided;          // nor has the 3-pass compose, whose calls also run eagerly
     if (!((uintptr_t)a->noise_tape & 15) && !a->inpaint_mask && !a->n_dump && !h->graph_replay && !h->keep_taps && h->T % 4 == 0 &&
-        !rescales && !refreshes) {
+        !rescales && !refreshes && !composes) {
         // guided loop: the state holds both halves (the same x feeds both passes).  An unguided step reads and writes the cond
         // half and mirrors into the uncond half only when the NEXT step of this call is guided (every call transposes the
         // state in afresh); a call without a guided step keeps one half, like a loop that is not guided at all.
@@ -510,7 +530,7 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
     }
     // the graph is ONE captured step: only a call whose steps all take the same mode can replay it
     const bool want_graph = h->graph_replay && !h->prof && !h->keep_taps && !a->n_dump && a->first_index - last_idx >= 8 && uniform && !refreshes &&
-                            h->lc_every == 1;                     // the layer cache's calls differ from one another: eager
+                            !composes && h->lc_every == 1;                     // the layer cache's calls differ from one another: eager
     int idx = a->first_index, k = a->k_base;
     if (want_graph) {
         // step 0 eagerly: it sets every kernel attribute and acquires the late workspace, so the captured step never allocates

@@ -630,6 +630,40 @@ __global__ void cfg_blend_kernel(const float* __restrict__ c, const float* __res
     out[i] = lo <= tb && tb <= hi ? cfg_blend(c[i], u[i], scale[b]) : c[i];
 }
 
+// Per-condition guidance, 3-pass rule (gdx.h gdx_set_guidance_compose): g = g1 + s1*(f - m) with g1 = u + s0*(m - u), every
+// difference, product and sum rounded on its own.  A sample is composed when t == NULL or lo <= t[b] <= hi (cfg_blend_kernel's
+// rule), else it is f.  Grid (ceil(groups / 256), B) like cfg_rescale_apply_kernel; out may alias f, m or u (no __restrict__: a
+// thread reads its group of every operand before it writes it, and no other thread touches that group).
+struct CfgComposeDev {
+    long per_sample, groups;
+    const float *f, *m, *u, *s0, *s1;
+    const int64_t* t;
+    int64_t lo, hi;
+    float* out;
+};
+__device__ __forceinline__ float cfg_compose(float f, float m, float u, float s0, float s1) {
+    return __fadd_rn(cfg_blend(m, u, s0), __fmul_rn(s1, __fsub_rn(f, m)));
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_compose_kernel(const CfgComposeDev a) {
+    const long grp = (long)blockIdx.x * 256 + threadIdx.x;
+    if (grp >= a.groups) return;
+    const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
+    f32x4 x0 = load4<VEC>(a.f, g.e0, g.nval);
+    bool guided = true;
+    if (a.t) {
+        const int64_t tb = a.t[g.b];
+        guided = a.lo <= tb && tb <= a.hi;
+    }
+    if (guided) {
+        const f32x4 m = load4<VEC>(a.m, g.e0, g.nval), u = load4<VEC>(a.u, g.e0, g.nval);
+        const float s0 = a.s0[g.b], s1 = a.s1[g.b];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x0[i] = cfg_compose(x0[i], m[i], u[i], s0, s1);
+    }
+    store4<VEC>(a.out, g.e0, g.nval, x0);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Variational bound (reference gaussian_diffusion.py:1192-1225, 1519-1592, diffusion/losses.py:12-77; gdx.h gdx_bpd_terms).
 // bpd_xt_kernel forms x_t = sa*x0 + s1m*z with in-kernel Philox noise and STORES z next to it: the terms kernel reads the
@@ -779,6 +813,7 @@ struct CfgRescaleDev {
     long per_sample, groups;
     int chunks, batch;
     const float *c, *u, *scale;
+    const float* g;                  // the guided prediction already formed (gdx_cfg_rescale_), or nullptr: cfg_blend(c, u, scale)
     const int64_t* t;
     int64_t lo, hi;
     double phi;
@@ -790,6 +825,17 @@ __device__ __forceinline__ bool rescale_guided(const CfgRescaleDev& a, int b) {
     const int64_t tb = a.t[b];
     return a.lo <= tb && tb <= a.hi;
 }
+// the guided prediction of a guided sample's group whose conditional output is c
+template <bool VEC>
+__device__ __forceinline__ f32x4 rescale_g4(const CfgRescaleDev& a, const f32x4 c, int b, long e0, int nval) {
+    if (a.g) return load4<VEC>(a.g, e0, nval);
+    const f32x4 u = load4<VEC>(a.u, e0, nval);
+    const float sc = a.scale[b];
+    f32x4 g;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g[i] = cfg_blend(c[i], u[i], sc);
+    return g;
+}
 
 // bpd_terms_kernel's decomposition and summation order (grid (chunks, B), thread -> wave -> block -> one ordinary store of the
 // block's four sums to part[(b*chunks + chunk)*4 ..]): a function of J*T alone, no atomics.
@@ -798,7 +844,6 @@ __global__ __launch_bounds__(256) void cfg_rescale_stats_kernel(const CfgRescale
     __shared__ double red[4][4];
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
     if (!rescale_guided(a, b)) return;                             // block-uniform
-    const float sc = a.scale[b];
     const long base = (long)b * a.per_sample;
     double s[4] = {0.0, 0.0, 0.0, 0.0};                            // sum c, sum c^2, sum g, sum g^2
     for (int it = 0; it < BPD_GROUPS / 256; ++it) {
@@ -807,11 +852,11 @@ __global__ __launch_bounds__(256) void cfg_rescale_stats_kernel(const CfgRescale
         const long e0 = base + 4L * grp;
         const int nval = VEC ? 4 : (int)min(4L, a.per_sample - 4L * grp);
         const f32x4 c = load4<VEC>(a.c, e0, nval);
-        const f32x4 u = load4<VEC>(a.u, e0, nval);
+        const f32x4 g = rescale_g4<VEC>(a, c, b, e0, nval);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (i < nval) {
-                const double dc = (double)c[i], dg = (double)cfg_blend(c[i], u[i], sc);
+                const double dc = (double)c[i], dg = (double)g[i];
                 s[0] = __dadd_rn(s[0], dc);
                 s[1] = __dadd_rn(s[1], __dmul_rn(dc, dc));
                 s[2] = __dadd_rn(s[2], dg);
@@ -863,10 +908,10 @@ __global__ __launch_bounds__(256) void cfg_rescale_apply_kernel(const CfgRescale
     const Group g = group_at<VEC>(blockIdx.y, grp, a.per_sample);
     f32x4 x0 = load4<VEC>(a.c, g.e0, g.nval);
     if (rescale_guided(a, g.b)) {
-        const f32x4 u = load4<VEC>(a.u, g.e0, g.nval);
-        const float sc = a.scale[g.b], f = a.factor[g.b];
+        const f32x4 gp = rescale_g4<VEC>(a, x0, g.b, g.e0, g.nval);
+        const float f = a.factor[g.b];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) x0[i] = __fmul_rn(cfg_blend(x0[i], u[i], sc), f);
+        for (int i = 0; i < 4; ++i) x0[i] = __fmul_rn(gp[i], f);
     }
     store4<VEC>(a.out, g.e0, g.nval, x0);
 }
@@ -1013,6 +1058,16 @@ static bool vec_ok(long per_sample, const P*... p) { return per_sample % 4 == 0 
 template <typename... P>
 static bool vec_ok(const gdx::StepSrc& s, const P*... more) {
     return vec_ok(s.per_sample, s.x, s.x0c, s.x0u, s.mask, s.motion, s.out, s.pred, more...);
+}
+
+hipError_t gdx::launch_cfg_compose(const float* f, const float* m, const float* u, const float* s0, const float* s1, const int64_t* t,
+                                   int64_t lo, int64_t hi, float* out, int B, int64_t per_sample, hipStream_t s) {
+    CfgComposeDev d{(long)per_sample, (long)(per_sample + 3) / 4, f, m, u, s0, s1, t, lo, hi, out};
+    if (B <= 0 || per_sample <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)B), block(256);
+    if (vec_ok(d.per_sample, f, m, u, out)) hipLaunchKernelGGL(cfg_compose_kernel<true>, grid, block, 0, s, d);
+    else hipLaunchKernelGGL(cfg_compose_kernel<false>, grid, block, 0, s, d);
+    return hipGetLastError();
 }
 
 static int refuse(const char* who, const char* what) { return gdx_set_error_((std::string(who) + ": " + what).c_str()); }
@@ -1416,10 +1471,12 @@ extern "C" int gdx_bpd_terms(const gdx_bpd_args_t* a, void* stream) {
     return launch_status("gdx_bpd_terms: launch failed");
 }
 
-extern "C" int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream) {
+extern "C" int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream) { return gdx_cfg_rescale_(a, nullptr, stream); }
+
+int gdx_cfg_rescale_(const gdx_cfg_rescale_args_t* a, const float* g, void* stream) {
     using namespace gdx;
     if (!a) return gdx_set_error_("gdx_cfg_rescale: null argument");
-    if (!a->x0_cond || !a->x0_uncond || !a->scale || !a->workspace || !a->factor || !a->out)
+    if (!a->x0_cond || (!g && (!a->x0_uncond || !a->scale)) || !a->workspace || !a->factor || !a->out)
         return gdx_set_error_("gdx_cfg_rescale: null argument");
     if (a->batch <= 0 || a->njoints <= 0 || a->frames <= 0 || a->batch > 65535) return gdx_set_error_("gdx_cfg_rescale: bad shape");
     if (!(a->phi >= 0.0f && a->phi <= 1.0f)) return gdx_set_error_("gdx_cfg_rescale: phi must lie in [0, 1]");
@@ -1429,19 +1486,19 @@ extern "C" int gdx_cfg_rescale(const gdx_cfg_rescale_args_t* a, void* stream) {
     d.groups = (d.per_sample + 3) / 4;
     d.chunks = (int)((d.per_sample + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK);
     d.batch = a->batch;
-    d.c = a->x0_cond; d.u = a->x0_uncond; d.scale = a->scale;
+    d.c = a->x0_cond; d.u = a->x0_uncond; d.scale = a->scale; d.g = g;
     d.t = a->t; d.lo = a->lo; d.hi = a->hi;
     d.phi = (double)a->phi;
     d.part = a->workspace; d.factor = a->factor; d.out = a->out;
     hipStream_t s = (hipStream_t)stream;
     const dim3 block(256);
-    if (vec_ok(d.per_sample, d.c, d.u)) hipLaunchKernelGGL(cfg_rescale_stats_kernel<true>, dim3(d.chunks, a->batch), block, 0, s, d);
+    if (vec_ok(d.per_sample, d.c, d.u, d.g)) hipLaunchKernelGGL(cfg_rescale_stats_kernel<true>, dim3(d.chunks, a->batch), block, 0, s, d);
     else hipLaunchKernelGGL(cfg_rescale_stats_kernel<false>, dim3(d.chunks, a->batch), block, 0, s, d);
     if (launch_status("gdx_cfg_rescale: launch failed")) return -1;
     hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3((a->batch + 63) / 64), dim3(64), 0, s, d);
     if (launch_status("gdx_cfg_rescale: launch failed")) return -1;
     const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)a->batch);
-    if (vec_ok(d.per_sample, d.c, d.u, d.out)) hipLaunchKernelGGL(cfg_rescale_apply_kernel<true>, grid, block, 0, s, d);
+    if (vec_ok(d.per_sample, d.c, d.u, d.g, d.out)) hipLaunchKernelGGL(cfg_rescale_apply_kernel<true>, grid, block, 0, s, d);
     else hipLaunchKernelGGL(cfg_rescale_apply_kernel<false>, grid, block, 0, s, d);
     return launch_status("gdx_cfg_rescale: launch failed");
 }

@@ -557,7 +557,10 @@ class GaussianDiffusion:
         phi = E.guidance_rescale_of(y, guided)
         every = E.guidance_refresh_of(y, guided)
         layer_cache = E.layer_cache_of(y, inner.num_layers)
+        compose, text_scale = E.guidance_compose_of(y, guided, getattr(inner, "use_text", False))
+        E.refuse_compose_conflicts(y, compose, inner.num_layers, parallel=window is not None)
         eng = inner._get_engine(x.device)
+        eng.set_guidance_compose(compose)            # in front of the conditioning, whose rows depend on it; absent keys set JOINT
         if window is None:
             eng.prepare(B, T)
             eng.set_condition(y["seed"], y["mfcc"], text=inner._text_features(y, B), cache=False)
@@ -568,7 +571,7 @@ class GaussianDiffusion:
         eng.set_guidance_refresh(every)              # likewise: an absent key sets 1 (off); every loop starts with a refresh
         eng.set_layer_cache(*layer_cache)            # likewise: an absent key sets every = 1 (off); every loop starts with a full call
         if guided:
-            mode, scale = GDX_CFG, E.f32c(y["scale"].reshape(-1), "y['scale']")
+            mode, scale = GDX_CFG, E.f32c(E.pack_scales(compose, y["scale"], text_scale), "y['scale']")
         else:
             mode, scale = (GDX_UNCOND if y.get("uncond", False) else GDX_COND), None
         mask = motion = None

@@ -92,6 +92,7 @@ class Engine:
         self.shape = None          # (B, T) the workspace is sized for
         self._cond_key = None
         self._weights_key = None
+        self._compose = _lib.GDX_GUIDE_JOINT   # the handle's gdx_set_guidance_compose mode
         self._keep = []            # tensors that must outlive enqueued work
 
     def __del__(self):
@@ -176,6 +177,16 @@ class Engine:
         """(lo, hi): GDX_CFG guides only model timesteps lo <= t <= hi (gdx_set_guidance_interval); None = every timestep."""
         lo, hi = interval if interval is not None else (_lib.INT64_MIN, _lib.INT64_MAX)
         _lib.check(self.lib.gdx_set_guidance_interval(self.handle, lo, hi), self.lib)
+
+    def set_guidance_compose(self, mode=_lib.GDX_GUIDE_JOINT):
+        """Which passes a guided call contrasts (gdx_set_guidance_compose; GDX_GUIDE_*, JOINT = today's cond / uncond pair).  Set
+        in front of prepare / set_condition on every call, so a handle never keeps an earlier call's mode; a change clears the
+        conditioning (the rows depend on the mode), the same mode again is no call at all."""
+        if mode == self._compose:
+            return
+        _lib.check(self.lib.gdx_set_guidance_compose(self.handle, int(mode)), self.lib)
+        self._compose = mode
+        self._cond_key = None
 
     def set_guidance_rescale(self, phi=0.0):
         """phi in [0, 1]: guided x0 predictions are rescaled to the conditional output's per-sample standard deviation and mixed
@@ -397,6 +408,76 @@ def guidance_interval_of(y, guided_model):
     if not (_lib.INT64_MIN <= lo <= _lib.INT64_MAX and _lib.INT64_MIN <= hi <= _lib.INT64_MAX):
         raise ValueError(f"y['guidance_interval'] bounds must fit 64 bits, got {iv!r}")
     return lo, hi
+
+
+GUIDANCE_DROPS = {"both": _lib.GDX_GUIDE_JOINT, "text": _lib.GDX_GUIDE_TEXT, "seed": _lib.GDX_GUIDE_SEED}
+GUIDANCE_ORDERS = {"seed_text": _lib.GDX_GUIDE_SEED_TEXT, "text_seed": _lib.GDX_GUIDE_TEXT_SEED}
+COMPOSE_KEYS = ("guidance_drop", "text_scale", "guidance_order")
+
+
+def guidance_compose_of(y, guided_model, use_text=True):
+    """y['guidance_drop'] / y['text_scale'] / y['guidance_order'] validated -> (mode, text_scale): the GDX_GUIDE_* mode of
+    gdx_set_guidance_compose and the text scales, a floating device tensor [B], or None outside the 3-pass modes.  Without any
+    of the keys: (GDX_GUIDE_JOINT, None).  guidance_drop names what the contrast pass drops, "both" (JOINT), "text" or "seed",
+    under the one scale y['scale'].  text_scale selects a 3-pass mode, in which y['scale'] is the seed scale and guidance_order
+    says which condition is stepped to first: "seed_text" (default) or "text_seed".  ValueError for a key on a model that is not a
+    ClassifierFreeSampleModel (`guided_model` False) or has no use_text, for text_scale together with guidance_drop, for
+    guidance_order without text_scale, and for a wrong type or shape (text_scale must match y['scale'] entry for entry)."""
+    present = [k for k in COMPOSE_KEYS if k in y]
+    if not present:
+        return _lib.GDX_GUIDE_JOINT, None
+    if not guided_model:
+        raise ValueError(f"y['{present[0]}'] needs a ClassifierFreeSampleModel: this model runs no guidance to compose")
+    if not use_text:
+        raise ValueError(f"y['{present[0]}'] needs a use_text model: without text the seed poses are the one condition that "
+                         f"can be dropped, and there is nothing to compose")
+    if "text_scale" not in y:
+        if "guidance_order" in y:
+            raise ValueError("y['guidance_order'] needs y['text_scale']: with one scale there is one stage and no order")
+        drop = y["guidance_drop"]
+        if not isinstance(drop, str) or drop not in GUIDANCE_DROPS:
+            raise ValueError(f"y['guidance_drop'] must be one of {sorted(GUIDANCE_DROPS)}, got {drop!r}")
+        return GUIDANCE_DROPS[drop], None
+    if "guidance_drop" in y:
+        raise ValueError("y['text_scale'] and y['guidance_drop'] exclude each other: text_scale runs both contrast passes, "
+                         "guidance_drop chooses the one that runs")
+    order = y.get("guidance_order", "seed_text")
+    if not isinstance(order, str) or order not in GUIDANCE_ORDERS:
+        raise ValueError(f"y['guidance_order'] must be one of {sorted(GUIDANCE_ORDERS)}, got {order!r}")
+    ts = y["text_scale"]
+    if not isinstance(ts, torch.Tensor) or not ts.is_floating_point():
+        raise ValueError(f"y['text_scale'] must be a floating tensor [batch], got {type(ts).__name__ if not isinstance(ts, torch.Tensor) else ts.dtype}")
+    scale = y.get("scale")
+    if ts.dim() != 1 or (isinstance(scale, torch.Tensor) and ts.numel() != scale.numel()):
+        raise ValueError(f"y['text_scale'] must be [batch] like y['scale'], got {list(ts.shape)}")
+    return GUIDANCE_ORDERS[order], require_device(ts, "y['text_scale']")
+
+
+def pack_scales(mode, scale, text_scale):
+    """The `scale` operand of a guided call: y['scale'] flattened [B], or in a 3-pass mode [2, B] in stage order -- row 0 the
+    scale of the condition stepped to first, row 1 the other's (gdx_set_guidance_compose)."""
+    scale = scale.reshape(-1).float()
+    if text_scale is None:
+        return scale.contiguous()
+    text_scale = text_scale.reshape(-1).float()
+    first, second = (scale, text_scale) if mode == _lib.GDX_GUIDE_SEED_TEXT else (text_scale, scale)
+    return torch.stack([first, second]).contiguous()
+
+
+def refuse_compose_conflicts(y, mode, num_layers, parallel=False):
+    """A 3-pass mode runs three row groups; the guidance refresh and the layer cache are written for two, and the window of
+    parallel_sample_loop (`parallel`) repeats one scale per slot (gdx.h)."""
+    if mode < _lib.GDX_GUIDE_SEED_TEXT:
+        return
+    if parallel:
+        raise ValueError("y['text_scale'] (3-pass guidance) is not supported by parallel_sample_loop, whose window repeats one "
+                         "scale per slot: use y['guidance_drop']")
+    if guidance_refresh_of(y, True) > 1:
+        raise ValueError("y['text_scale'] (3-pass guidance) and y['guidance_refresh'] > 1 exclude each other: the refresh stores "
+                         "one cond-uncond difference")
+    if layer_cache_of(y, num_layers)[0] > 1:
+        raise ValueError("y['text_scale'] (3-pass guidance) and y['layer_cache'] with every > 1 exclude each other: the cache "
+                         "holds two row groups")
 
 
 def guidance_rescale_of(y, guided_model):

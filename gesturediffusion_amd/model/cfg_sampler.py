@@ -12,10 +12,13 @@ conditional output's per-sample standard deviation and mixes it with the unscale
 `y['guidance_refresh'] = k` (additive, int >= 1) belongs to the in-library loops, which remember the cond-uncond difference
 between guided calls; this forward has no memory and raises ValueError for k > 1, and likewise for
 `y['layer_cache'] = (every, keep)` with every > 1 (the deep encoder layers' change reused between calls).
+For a use_text model `y['guidance_drop']` ("both" | "text" | "seed") names what the contrast pass drops, and `y['text_scale']`
+([B], with `y['guidance_order']`) steers the two conditions on their own in three passes (engine.guidance_compose_of).
 """
 import torch.nn as nn
 
-from ..engine import GDX_CFG, guidance_interval_of, guidance_rescale_of, refuse_guidance_refresh, refuse_layer_cache
+from ..engine import (GDX_CFG, guidance_compose_of, guidance_interval_of, guidance_rescale_of, pack_scales, refuse_guidance_refresh,
+                      refuse_layer_cache)
 from .mdm import _NativeDenoiser
 
 
@@ -50,14 +53,16 @@ class ClassifierFreeSampleModel(nn.Module):
             raise NotImplementedError
         interval = guidance_interval_of(y, True)
         phi = guidance_rescale_of(y, True)
+        compose, text_scale = guidance_compose_of(y, True, getattr(m, "use_text", False))
         refuse_guidance_refresh(y, True, "the step-wise forward of ClassifierFreeSampleModel")
         refuse_layer_cache(y, m.num_layers, "the step-wise forward of ClassifierFreeSampleModel")
         eng = m._get_engine(x.device)
+        eng.set_guidance_compose(compose)          # in front of the conditioning, whose rows depend on it; absent keys set JOINT
         eng.prepare(bs, nframes)
         eng.set_condition(seed, mfcc, text=m._text_features(y, bs))
         # per-sample choice in the blend kernel: guided where lo <= timesteps[b] <= hi, else the conditional output; set on
         # every call (None: every timestep), so a handle never keeps the interval of an earlier call
         eng.set_guidance_interval(interval)
         eng.set_guidance_rescale(phi)              # likewise: an absent key sets 0
-        out = eng.forward(x, timesteps, GDX_CFG, scale.reshape(-1))
+        out = eng.forward(x, timesteps, GDX_CFG, pack_scales(compose, scale, text_scale))
         return out.view(bs, njoints, nfeats, nframes)

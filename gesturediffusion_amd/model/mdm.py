@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..engine import (GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_interval_of, guidance_rescale_of,
+from ..engine import (GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_compose_of, guidance_interval_of, guidance_rescale_of,
                       refuse_layer_cache, require_device)
 from .rotation2xyz import Rotation2xyz
 
@@ -351,6 +351,7 @@ class MDM(_NativeDenoiser):
         self._check_inputs(x, y)
         guidance_interval_of(y, False)                     # the key needs a ClassifierFreeSampleModel: ValueError here
         guidance_rescale_of(y, False)
+        guidance_compose_of(y, False)
         refuse_layer_cache(y, self.num_layers, "the step-wise forward of MDM")
         bs, njoints, nfeats, nframes = x.shape
         force_mask = y.get("uncond", False)
@@ -373,6 +374,7 @@ class MDM(_NativeDenoiser):
         if nframes + 1 > ROPE_ROWS:
             raise ValueError(f"at most {ROPE_ROWS - 1} frames")
         eng = self._get_engine(x.device)
+        eng.set_guidance_compose()                         # JOINT: a handle never keeps an earlier guided call's mode
         eng.prepare(bs, nframes)
         eng.set_condition(seed, mfcc, text=text)
         out = eng.forward(x, timesteps, GDX_UNCOND if force_mask else GDX_COND)

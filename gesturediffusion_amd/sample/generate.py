@@ -57,7 +57,7 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
                   guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None, text_of_chunk=None,
-                  layer_cache=None, parallel=None):
+                  layer_cache=None, parallel=None, text_guidance_param=None, guidance_order=None, guidance_drop=None):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -77,7 +77,13 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     layer_cache (every, keep): every every-th denoiser call in full, the first keep encoder layers plus the stored change of the
     deeper ones in between (y['layer_cache']); each chunk is its own loop and starts with a full call.
     parallel (window, tolerance): every chunk's loop runs parallel in time (parallel_sample_loop; samplers "p" and "ddim", Philox
-    noise or a tape; neither guidance_refresh > 1, layer_cache nor invert_of_chunk) and report(text) is told each chunk's iterations."""
+    noise or a tape; neither guidance_refresh > 1, layer_cache nor invert_of_chunk) and report(text) is told each chunk's iterations.
+    Per-condition guidance of a use_text model (needs guidance_param != 1; the loops validate the rest): guidance_drop "both" |
+    "text" | "seed" names what the contrast pass drops (y['guidance_drop']); text_guidance_param S runs three passes with the text
+    stage at S and the seed stage at guidance_param (y['text_scale']), guidance_order saying which comes first (y['guidance_order'])."""
+    if guidance_param == 1 and (text_guidance_param is not None or guidance_order is not None or guidance_drop is not None):
+        raise ValueError("text_guidance_param / guidance_order / guidance_drop need guidance_param != 1: without guidance there is "
+                         "nothing to compose")
     if parallel is not None:
         if sampler not in ("p", "ddim"):
             raise ValueError("parallel needs sampler='p' or 'ddim'")
@@ -117,6 +123,12 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             y["guidance_rescale"] = float(guidance_rescale)
         if guidance_refresh > 1:
             y["guidance_refresh"] = guidance_refresh
+        if text_guidance_param is not None:
+            y["text_scale"] = torch.ones(b, device=first_seed.device) * text_guidance_param
+        if guidance_order is not None:
+            y["guidance_order"] = guidance_order
+        if guidance_drop is not None:
+            y["guidance_drop"] = guidance_drop
         if layer_cache is not None:
             y["layer_cache"] = (int(layer_cache[0]), int(layer_cache[1]))
         kw = dict(clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=0, init_image=None, progress=progress,
@@ -342,6 +354,11 @@ def main(argv=None):
         print(f"### guidance on {sum(flags)} of {len(flags)} steps (model timesteps {interval[0]}..{interval[1]})")
     if args.guidance_rescale > 0 and rank == 0:
         print(f"### guidance rescale {args.guidance_rescale:.2f}")
+    if args.text_guidance_param is not None and rank == 0:
+        print(f"### per-condition guidance ({args.guidance_order or 'seed_text'}): seed scale {args.guidance_param:g}, text scale "
+              f"{args.text_guidance_param:g}, three passes per guided step")
+    if args.guidance_drop is not None and rank == 0:
+        print(f"### guidance contrast pass drops: {args.guidance_drop}")
     if args.guidance_refresh > 1 and rank == 0:
         plan = diffusion.guidance_plan(interval, args.guidance_refresh, plms=args.sampler == "plms")
         print(f"### unconditional pass on {plan.count('refresh')} of {len(plan) - plan.count('off')} guided calls")
@@ -357,7 +374,8 @@ def main(argv=None):
                          plms_order=args.plms_order, dpm_order=args.dpm_order, unipc_order=args.unipc_order,
                          guidance_interval=interval, guidance_rescale=args.guidance_rescale,
                          guidance_refresh=args.guidance_refresh, invert_of_chunk=invert_of_chunk, report=report,
-                         text_of_chunk=text_of_chunk, layer_cache=args.layer_cache,
+                         text_of_chunk=text_of_chunk, layer_cache=args.layer_cache, text_guidance_param=args.text_guidance_param,
+                         guidance_order=args.guidance_order, guidance_drop=args.guidance_drop,
                          parallel=(args.parallel_window, args.parallel_tolerance) if args.parallel_window else None)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:

@@ -56,6 +56,26 @@ def parse_and_load_from_model(parser, argv=None):
         parser.error("--guidance_refresh needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     if args.guidance_refresh is None:
         args.guidance_refresh = 1
+    composes = [f for f, on in (("--text_guidance_param", args.text_guidance_param is not None),
+                                ("--guidance_order", args.guidance_order is not None),
+                                ("--guidance_drop", args.guidance_drop is not None)) if on]
+    if composes:
+        if not args.use_text:
+            parser.error(f"{composes[0]} needs --use_text: without text the seed poses are the one condition that can be dropped")
+        if args.guidance_param == 1:
+            parser.error(f"{composes[0]} needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
+        if args.text_guidance_param is not None and args.guidance_drop is not None:
+            parser.error("--text_guidance_param and --guidance_drop exclude each other: the first runs both contrast passes, "
+                         "the second chooses the one that runs")
+        if args.guidance_order is not None and args.text_guidance_param is None:
+            parser.error("--guidance_order needs --text_guidance_param: with one scale there is one stage and no order")
+    if args.text_guidance_param is not None:
+        if args.guidance_refresh > 1:
+            parser.error("--text_guidance_param runs no guidance refresh: the refresh stores one cond-uncond difference")
+        if args.layer_cache is not None and args.layer_cache[0] > 1:
+            parser.error("--text_guidance_param runs no layer cache: the cache holds two row groups, this guidance runs three")
+        if args.parallel_window:
+            parser.error("--text_guidance_param does not combine with --parallel_window, whose window repeats one scale per slot")
     if args.layer_cache is not None:
         every, keep = args.layer_cache
         if every < 1:
@@ -200,6 +220,18 @@ def add_native_options(parser):
                        help="Guidance rescale (Lin et al. 2023): scale each guided x0 prediction to the conditional one's "
                             "per-sample standard deviation and mix it with the unscaled one by PHI in [0, 1]; 0 = off. "
                             "Every sampler; an error with --guidance_param 1.")
+    group.add_argument("--text_guidance_param", default=None, type=float, metavar="S",
+                       help="--use_text: steer the text on its own in three passes per guided step (text+seed, one condition "
+                            "dropped, neither): S scales the text stage, --guidance_param the seed-pose stage. An error without "
+                            "--use_text, with --guidance_param 1, --guidance_drop, --guidance_refresh > 1, --layer_cache or "
+                            "--parallel_window.")
+    group.add_argument("--guidance_order", default=None, choices=["seed_text", "text_seed"],
+                       help="--text_guidance_param: the condition stepped to first from the unconditional prediction "
+                            "(default seed_text).")
+    group.add_argument("--guidance_drop", default=None, choices=["both", "text", "seed"],
+                       help="--use_text: what the contrast pass of classifier-free guidance drops (default both, the "
+                            "unconditional pass); text keeps the seed poses out of the extrapolation, seed the text. Two passes "
+                            "per guided step under the one scale --guidance_param.")
     group.add_argument("--guidance_refresh", default=None, type=int, metavar="K",
                        help="Guidance refresh: run the unconditional pass only on every K-th guided denoiser call of a chunk's "
                             "loop and reuse the stored cond-uncond difference in between (1 = every call, the default). "

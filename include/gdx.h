@@ -143,6 +143,41 @@ int gdx_set_condition(gdx_handle_t h, const float* seed, const float* mfcc, void
  * to call; like every refusal of either (null pointer, no gdx_prepare, weights missing) that happens before any device work. */
 int gdx_set_condition_text(gdx_handle_t h, const float* seed, const float* mfcc, const float* text, void* stream);
 
+/* Per-condition guidance for a handle with text_dim > 0 (compositional classifier-free guidance, Liu et al. 2022,
+ * arXiv:2206.01714; the two-scale form of Brooks et al. 2023, arXiv:2211.09800, section 3.2).  The reference's trainer drops the
+ * text features and the seed poses independently (mask_cond is called once on each, model/mdm.py:121,127,242-250), so a use_text
+ * checkpoint has seen four conditioning states.  Per sample, with the MFCC term unchanged in all four (audio is never dropped):
+ *     F  text + seed   [ embed_text(text) | seed_embed(seed) ]     the conditional pass
+ *     S  seed only     [ embed_text.bias  | seed_embed(seed) ]     the text features zeroed in front of embed_text
+ *     X  text only     [ embed_text(text) | seed_embed.bias  ]     the flat seed poses zeroed in front of seed_embed
+ *     U  neither       [ embed_text.bias  | seed_embed.bias  ]     the unconditional pass
+ * The mode says which of them a guided call (GDX_CFG inside the guidance interval) runs, as row groups of ONE batch in the order
+ * given, and how it combines them; every difference, product and sum is a separate fp32 operation in the order written:
+ *     GDX_GUIDE_JOINT      (F, U)     g = U + s*(F - U)                       the state after gdx_create
+ *     GDX_GUIDE_TEXT       (F, S)     g = S + s*(F - S)                       the text steered, the seed kept out of the contrast
+ *     GDX_GUIDE_SEED       (F, X)     g = X + s*(F - X)
+ *     GDX_GUIDE_SEED_TEXT  (F, S, U)  g = (U + s0*(S - U)) + s1*(F - S)       3 passes: first to the seed, then to the text
+ *     GDX_GUIDE_TEXT_SEED  (F, X, U)  g = (U + s0*(X - U)) + s1*(F - X)       3 passes
+ * Modes 1 and 2 are the two-group guided call of JOINT with other rows in the second group: every path of a guided call applies
+ * unchanged (token-major, graph replay, refresh, layer cache, rescale) and `scale` stays [B].  GDX_UNCOND gives U in every mode.
+ * In the 3-pass modes every entry that takes `scale` -- gdx_forward and the scale field of every loop argument struct -- reads
+ * it as [2][B] contiguous under GDX_CFG: row 0 is s0 (it multiplies M - U, M the middle pass), row 1 is s1 (F - M).  No struct
+ * layout changes.  A guided 3-pass call runs 3 * batch samples (gdx_forward_samples, the 2 GiB operand check); a call outside the
+ * guidance interval runs GDX_COND on batch samples and computes neither contrast pass; gdx_forward, whose timesteps are on the
+ * device, keeps the triple batch and selects per sample like the blend does.  The loops compose in place on the conditional third
+ * of the prediction and call the unchanged step kernel with x0_uncond = scale = NULL, as the guidance rescale does; gdx_sample_loop
+ * takes the pose-layout path and graph replay runs such a call eagerly.  The guidance rescale applies in every mode under its rule
+ * with c = F and g = the composed prediction.
+ * Refused in a 3-pass mode under GDX_CFG, before the first launch: the guidance refresh (every > 1) and the layer cache
+ * (every > 1) in every loop that takes part in them -- their buffers and the covers() rule are written for two row groups -- and
+ * gdx_parallel_loop.
+ * gdx_set_guidance_compose: a null handle, an unknown mode, or a mode other than GDX_GUIDE_JOINT on a handle with text_dim == 0
+ * (one droppable condition, nothing to compose) is refused before any HIP call.  The conditioning rows depend on the mode: the
+ * call clears the conditioning (condition again before the next forward) and the stored guidance difference and layer change.
+ * When the number of row groups changes (2 <-> 3) the workspace is prepared again at the current shape (allocates). */
+enum { GDX_GUIDE_JOINT = 0, GDX_GUIDE_TEXT = 1, GDX_GUIDE_SEED = 2, GDX_GUIDE_SEED_TEXT = 3, GDX_GUIDE_TEXT_SEED = 4 };
+int gdx_set_guidance_compose(gdx_handle_t h, int32_t mode);
+
 /* Guidance interval (limited-interval guidance, Kynkaanniemi et al. 2024, arXiv:2404.07724; no counterpart in the reference):
  * the MODEL timesteps -- the values the denoiser sees after the respacing map, 0..999 for the reference's schedule -- at which
  * GDX_CFG means guidance, bounds inclusive.  Per-handle state like the conditioning; after gdx_create it is every timestep
@@ -308,7 +343,8 @@ int gdx_forward_layer_samples(gdx_handle_t h, int64_t* n);
  * (model/mdm.py:105-224, model/mdm_old.py:84-122, model/cfg_sampler.py:23-28).
  * x [B,J,1,T]; timesteps int64 [B] (already mapped through timestep_map); mode GDX_COND /
  * GDX_UNCOND / GDX_CFG; scale [B] (GDX_CFG only, y['scale']); out [B,J,1,T] contiguous.  Under GDX_CFG sample b is blended
- * when timesteps[b] lies in the handle's guidance interval and is the conditional output otherwise. */
+ * when timesteps[b] lies in the handle's guidance interval and is the conditional output otherwise.  In a 3-pass mode of
+ * gdx_set_guidance_compose scale is [2][B] and the blend is that mode's composition. */
 int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timesteps, int32_t mode,
                 const float* scale, float* out, void* stream);
 
