@@ -1,4 +1,5 @@
-"""Oracle: MDM denoiser forward, CPU fp32 restatement (test infrastructure only).
+"""Oracle: MDM denoiser forward, CPU restatement (test infrastructure only); fp32 as the reference runs it, and the same
+functions in float64 / float16 / bfloat16 when the parameter dict and the inputs have that dtype.
 
 Functional re-statement, over a plain ``{name: tensor}`` parameter dict that uses
 the reference's state-dict names, of
@@ -25,19 +26,31 @@ import torch.nn.functional as F
 
 
 # ----------------------------------------------------------------------------- tables
-def sinusoidal_pe(d_model, max_len=5000):
-    """reference model/mdm.py:277-289 (PositionalEncoding.__init__) -> [max_len, d]."""
-    pe = torch.zeros(max_len, d_model)
-    position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
-    div_term = torch.exp(torch.arange(0, d_model, 2).float() * (-math.log(10000.0) / d_model))
+def _table_dtype(dtype):
+    """The tables follow the parameters' dtype: built in float64 for float64 parameters, in float32 otherwise (a 16-bit
+    run rounds the finished table entries, not the positions and angles they are made from)."""
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def param_dtype(p):
+    return p["input_process.poseEmbedding.weight"].dtype
+
+
+def sinusoidal_pe(d_model, max_len=5000, dtype=torch.float32):
+    """reference model/mdm.py:277-289 (PositionalEncoding.__init__) -> [max_len, d] in `dtype`."""
+    ct = _table_dtype(dtype)
+    pe = torch.zeros(max_len, d_model, dtype=ct)
+    position = torch.arange(0, max_len, dtype=ct).unsqueeze(1)
+    div_term = torch.exp(torch.arange(0, d_model, 2).to(ct) * (-math.log(10000.0) / d_model))
     pe[:, 0::2] = torch.sin(position * div_term)
     pe[:, 1::2] = torch.cos(position * div_term)
-    return pe
+    return pe.to(dtype)
 
 
-def rotary_freqs(n, dim):
-    """reference model/local_attention.py:43-53 -> freqs [n, dim] (two copies of dim/2)."""
-    inv_freq = 1.0 / (10000 ** (torch.arange(0, dim, 2).float() / dim))
+def rotary_freqs(n, dim, dtype=torch.float32):
+    """reference model/local_attention.py:43-53 -> freqs [n, dim] (two copies of dim/2): angles in float32, or in float64
+    for float64 parameters (apply_rotary rounds their cos / sin to the dtype of what it rotates)."""
+    inv_freq = 1.0 / (10000 ** (torch.arange(0, dim, 2).to(_table_dtype(dtype)) / dim))
     t = torch.arange(n).type_as(inv_freq)
     freqs = torch.einsum("i,j->ij", t, inv_freq)
     return torch.cat((freqs, freqs), dim=-1)
@@ -51,7 +64,7 @@ def rotate_half(x):
 
 def apply_rotary(x, freqs):
     """reference model/local_attention.py:60-62."""
-    return (x * freqs.cos()) + (rotate_half(x) * freqs.sin())
+    return (x * freqs.cos().to(x.dtype)) + (rotate_half(x) * freqs.sin().to(x.dtype))
 
 
 # ----------------------------------------------------------------------------- blocks
@@ -114,11 +127,12 @@ def encoder_layer(p, prefix, x, nhead, taps=None):
     ctx = ctx.transpose(0, 1).reshape(S, B, d)
     sa = F.linear(ctx, p[prefix + "self_attn.out_proj.weight"], p[prefix + "self_attn.out_proj.bias"])
     x = F.layer_norm(x + sa, (d,), p[prefix + "norm1.weight"], p[prefix + "norm1.bias"], 1e-5)
-    ff = F.linear(x, p[prefix + "linear1.weight"], p[prefix + "linear1.bias"])
-    ff = F.gelu(ff)                                                 # exact erf form
+    ff1 = F.linear(x, p[prefix + "linear1.weight"], p[prefix + "linear1.bias"])
+    ff = F.gelu(ff1)                                                # exact erf form
     ff = F.linear(ff, p[prefix + "linear2.weight"], p[prefix + "linear2.bias"])
     x = F.layer_norm(x + ff, (d,), p[prefix + "norm2.weight"], p[prefix + "norm2.bias"], 1e-5)
     if taps is not None:
+        taps[prefix + "ffn1"] = ff1                                 # GELU's argument
         taps[prefix + "ctx"] = ctx
         taps[prefix + "out"] = x
     return x
@@ -147,7 +161,8 @@ def mdm_forward(p, cfg, x, timesteps, y, taps=None):
     """V2: reference model/mdm.py:105-224.  x [B,J,1,T] -> [B,J,1,T]."""
     bs, njoints, nfeats, nframes = x.shape
     d, heads, cl = cfg["latent_dim"], cfg["num_heads"], cfg.get("cl_head", 8)
-    pe = sinusoidal_pe(d)
+    dt = param_dtype(p)
+    pe = sinusoidal_pe(d, dtype=dt)
     uncond = bool(y.get("uncond", False))
     if "seed" not in y:
         raise KeyError("seed")
@@ -167,7 +182,7 @@ def mdm_forward(p, cfg, x, timesteps, y, taps=None):
         taps["project_to_lat"] = xseq
     # rotary + causal local attention on cl heads of d/cl dims (mdm.py:176-194)
     xs = _heads_split(xseq, bs, nframes, cl)
-    xs = apply_rotary(xs, rotary_freqs(nframes, d // cl))
+    xs = apply_rotary(xs, rotary_freqs(nframes, d // cl, dt))
     if taps is not None:
         taps["rope1"] = xs
     xs = local_attention(xs, window=10)
@@ -177,7 +192,7 @@ def mdm_forward(p, cfg, x, timesteps, y, taps=None):
     # conditioning token + second rotary over T+1 positions (mdm.py:197-213)
     xseq = torch.cat((coa, xseq), dim=0)
     xs = _heads_split(xseq, bs, nframes + 1, cl)
-    xs = apply_rotary(xs, rotary_freqs(nframes + 1, d // cl))
+    xs = apply_rotary(xs, rotary_freqs(nframes + 1, d // cl, dt))
     xseq = _heads_merge(xs, bs, nframes + 1, cl)
     if taps is not None:
         taps["enc_in"] = xseq
@@ -190,7 +205,7 @@ def mdm_old_forward(p, cfg, x, timesteps, y, taps=None):
     """V1: reference model/mdm_old.py:84-122."""
     bs, njoints, nfeats, nframes = x.shape
     d, heads = cfg["latent_dim"], cfg["num_heads"]
-    pe = sinusoidal_pe(d)
+    pe = sinusoidal_pe(d, dtype=param_dtype(p))
     uncond = bool(y.get("uncond", False))
     emb = timestep_embed(p, timesteps, pe) + seed_embed(p, y["seed"], uncond)     # [B, d]
     xc = torch.cat((x, y["mfcc"]), dim=1)                           # [B, J+26, 1, T]
