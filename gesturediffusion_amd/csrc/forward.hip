@@ -236,7 +236,7 @@ extern "C" int gdx_layer_delta(int32_t op, int32_t in_dtype, int32_t out_dtype, 
 // lo <= t[b] <= hi.  The chunk sums and factors belong to the handle (first use allocates, gdx_prepare resets).
 int gdx::rescale_x0(gdx_model* h, const float* c, const float* u, const float* scale, const int64_t* t, float* out, hipStream_t s,
                     const float* g) {
-    const size_t per = (size_t)h->J * h->T, chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
+    const size_t chunks = bpd_chunks((long)h->J * h->T);
     if (ws_need(h, &h->late.rs_part, sizeof(double) * 4 * h->B * chunks, s) || ws_need(h, &h->late.rs_factor, sizeof(float) * h->B, s))
         return -1;
     gdx_cfg_rescale_args_t r;

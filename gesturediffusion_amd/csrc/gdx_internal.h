@@ -194,11 +194,15 @@ inline bool local_attention_mfma_supported(int d, int heads, int window) {
 inline namespace h16 { GDX_HALF_API }
 namespace b16 { GDX_HALF_API }
 
-// ---- sampler.hip (fp32 only) --------------------------------------------------------------
-// graph replay of the sampling loop: device-resident {schedule index, executed-step number}
+// ---- the pose-layout files (fp32 only, contraction off: gdx_pose_device.h) -----------------
+// chunks of GDX_BPD_CHUNK elements per sample: the blocks per sample of every chunked sum (gdx_bpd_terms, gdx_cfg_rescale,
+// gdx_window_sweep) and the unit their workspaces are sized in
+inline long bpd_chunks(long per_sample) { return (per_sample + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK; }
+
+// sampler.hip.  Graph replay of the sampling loop: device-resident {schedule index, executed-step number}
 hipError_t launch_set_state(int* st, int idx, int k, hipStream_t s);
 hipError_t launch_advance_state(int* st, hipStream_t s);
-// out = u + scale[b]*(c - u) where lo <= t[b] <= hi (the handle's guidance interval), else c
+// guidance.hip.  out = u + scale[b]*(c - u) where lo <= t[b] <= hi (the handle's guidance interval), else c
 hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, const int64_t* t, int64_t lo, int64_t hi,
                             float* out, int B, int64_t per_sample, hipStream_t s);
 
@@ -226,7 +230,7 @@ struct UpdateTmDev {
 };
 
 // operands of gdx_ddim_reverse_step (gdx.h), under the field names every pose-layout step struct uses: what step_begin / step_src
-// (sampler.hip) and step_args (loops.hip) read.  The public entry takes them as plain arguments and fills this.
+// (gdx_pose_host.h) and step_args (loops.hip) read.  The public entry takes them as plain arguments and fills this.
 struct DdimReverseStepArgs {
     int32_t batch, njoints, frames;
     const float* coef;
@@ -241,19 +245,19 @@ struct DdimReverseStepArgs {
 
 }  // namespace gdx
 
-// the loops' (loops.hip) private entries into sampler.hip; each returns 0, or -1 with the error recorded
-// the update of a captured step: schedule index / step number read from `state` (UpdateDev::state)
+// the loops' (loops.hip) private entries into the pose-layout files; each returns 0, or -1 with the error recorded
+// sampler.hip.  The update of a captured step: schedule index / step number read from `state` (UpdateDev::state)
 int gdx_sampler_update_state_(const gdx_update_args_t* a, const int* state, long noise_stride, void* stream);
 // one step of the token-major fast path of gdx_sample_loop (update_tm_kernel); checks the layout arguments of `d`
 int gdx_sampler_update_tm_(const gdx::UpdateTmDev& d, void* stream);
 // gdx_ddim_reverse_step on its operands as a struct (gdx_ddim_reverse_loop builds them with step_args)
 int gdx_ddim_reverse_step_(const gdx::DdimReverseStepArgs& a, void* stream);
-// gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
-int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
-                uint32_t step, float* z_out, float* xt_out, void* stream);
 // gdx_parallel_loop: the window's planes [W + 1][plane] slid down by `stride` planes, the tail filled with P_W (window_slide_kernel)
 int gdx_window_slide_(float* planes, long plane, int W, int stride, void* stream);
-// gdx_cfg_rescale with the guided prediction g given instead of blended from (x0_uncond, scale), which may then be NULL
+// bound.hip.  gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
+int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
+                uint32_t step, float* z_out, float* xt_out, void* stream);
+// guidance.hip.  gdx_cfg_rescale with the guided prediction g given instead of blended from (x0_uncond, scale), which may then be NULL
 int gdx_cfg_rescale_(const gdx_cfg_rescale_args_t* a, const float* g, void* stream);
 // records the text of gdx_last_error and returns -1 (handle.hip), for the files that do not include gdx_host.h
 extern "C" int gdx_set_error_(const char* msg);

@@ -1,6 +1,7 @@
 // libgdx.so host side: the in-library sampling loops (diffusion/gaussian_diffusion.py:598-730, 879-993 and the multistep solvers).
 // What each denoiser call of a loop does is planned once per entry-point call (gdx_call_plan.h); the loops index the plan by
-// position.  C ABI in include/gdx.h; the handle is in handle.hip, forward_core in forward.hip, the step kernels in sampler.hip.
+// position.  C ABI in include/gdx.h; the handle is in handle.hip, forward_core in forward.hip, the step kernels in sampler.hip,
+// the guidance arithmetic in guidance.hip, the bound's kernels in bound.hip.
 #include "gdx_host.h"
 
 #include <algorithm>
@@ -146,7 +147,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     const int B = h->B;
     LateWorkspace& lw = h->late;
     const size_t per = (size_t)h->J * h->T;
-    const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
+    const size_t chunks = bpd_chunks(per);
     if (ws_need(h, &lw.bpd_xt, sizeof(float) * B * per, s) || ws_need(h, &lw.bpd_part, sizeof(float) * 4 * B * chunks, s) ||
         (!a->noise_tape && ws_need(h, &lw.bpd_z, sizeof(float) * B * per, s)))
         return -1;
@@ -387,7 +388,7 @@ extern "C" int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int
     hipStream_t s = (hipStream_t)stream;
     const int WB = h->B, B = WB / window;
     const size_t per = (size_t)h->J * h->T, plane = (size_t)B * per;
-    const size_t chunks = (per + GDX_BPD_CHUNK - 1) / GDX_BPD_CHUNK;
+    const size_t chunks = bpd_chunks(per);
     *iterations_out = 0;
     LateWorkspace& lw = h->late;
     if (ws_need(h, &lw.pl_x0, sizeof(float) * WB * per, s) || ws_need(h, &lw.pl_scale, sizeof(float) * WB, s) ||

@@ -24,6 +24,11 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
+def _bpd_chunks(per_sample):
+    """Chunks of GDX_BPD_CHUNK elements per sample: the unit the chunked sums' workspaces are sized in (include/gdx.h)."""
+    return (per_sample + _lib.GDX_BPD_CHUNK - 1) // _lib.GDX_BPD_CHUNK
+
+
 def _loop_fields(coef, timestep_map, scale, inpaint_mask, inpaint_motion, clip_denoised, run_steps, k_base):
     """The fields every in-library loop's argument struct shares, as keywords, and the host timestep map they point into
     (the caller keeps it alive while the loop is enqueued)."""
@@ -218,8 +223,7 @@ class Engine:
         if out is None:
             out = torch.empty_like(c)
         factor = torch.empty(B, device=dev, dtype=torch.float32)
-        chunks = (J * F * T + _lib.GDX_BPD_CHUNK - 1) // _lib.GDX_BPD_CHUNK
-        ws = torch.empty(4 * B * chunks, device=dev, dtype=torch.float64)
+        ws = torch.empty(4 * B * _bpd_chunks(J * F * T), device=dev, dtype=torch.float64)
         lo, hi = interval if interval is not None else (_lib.INT64_MIN, _lib.INT64_MAX)
         a = _lib.CfgRescaleArgs(batch=B, njoints=J * F, frames=T, x0_cond=c.data_ptr(), x0_uncond=u.data_ptr(),
                                 scale=scale.data_ptr(), phi=float(phi), t=t.data_ptr() if t is not None else None, lo=lo, hi=hi,
@@ -600,8 +604,7 @@ def sampler_update(kind, coef, x, x0_cond, out, t=None, step_index=0, x0_uncond=
 
 def bpd_workspace(batch, per_sample, device):
     """Chunk-sum scratch of gdx_bpd_terms (include/gdx.h): 4 floats per (sample, GDX_BPD_CHUNK-element chunk)."""
-    chunks = (per_sample + _lib.GDX_BPD_CHUNK - 1) // _lib.GDX_BPD_CHUNK
-    return torch.empty(max(1, 4 * batch * chunks), device=device, dtype=torch.float32)
+    return torch.empty(max(1, 4 * batch * _bpd_chunks(per_sample)), device=device, dtype=torch.float32)
 
 
 def bpd_terms(coef, x_start, x_t, x0_cond, noise=None, t=None, step_index=0, x0_uncond=None, scale=None, inpaint_mask=None,
@@ -730,9 +733,8 @@ def window_sweep(kind, coef, first_index, planes, x0, n_slots=None, inpaint_mask
     lib = _lib.load()
     n = x0.shape[0] if n_slots is None else n_slots
     _, B, J, F, T = planes.shape
-    chunks = (J * F * T + _lib.GDX_BPD_CHUNK - 1) // _lib.GDX_BPD_CHUNK
     err = torch.empty(max(n, 1), B, device=planes.device, dtype=torch.float64)
-    ws = torch.empty(max(n, 1) * B * chunks, device=planes.device, dtype=torch.float64)
+    ws = torch.empty(max(n, 1) * B * _bpd_chunks(J * F * T), device=planes.device, dtype=torch.float64)
     # plain arguments in gdx.h's order (this entry has no argument struct)
     _lib.check(lib.gdx_window_sweep(kind, B, J * F, T, n, coef.data_ptr(), first_index, planes.data_ptr(), x0.data_ptr(),
                                     _p(inpaint_mask), _p(inpaint_motion), int(bool(clip_denoised)), _p(noise), philox_seed,

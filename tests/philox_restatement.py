@@ -1,4 +1,4 @@
-"""The in-kernel noise generator (philox_normal4, csrc/sampler.hip) restated next to oracle/philox.py: the counter words with
+"""The in-kernel noise generator (philox_normal4, csrc/gdx_pose_device.h) restated next to oracle/philox.py: the counter words with
 the oracle's keying, Box-Muller with log / sqrt / cos / sin in float64, the per-element bound, the statistics and the key
 sets that tests/test_philox_host.py (CPU) and tests/test_gpu_philox.py (GPU) share, and the mutants of the negative
 controls.  No GPU code here.

@@ -1,5 +1,5 @@
 """Kernel-level tests of the boundary kernels of the denoiser step (csrc/boundary.hip and csrc/boundaryh.hip: the two pose <-> token-major transposes,
-small_linear, gather_rows, mfcc_project, token0) and of masked_l2 (csrc/sampler.hip), each through its C-ABI entry point against
+small_linear, gather_rows, mfcc_project, token0) and of masked_l2 (csrc/bound.hip), each through its C-ABI entry point against
 a plain reference of the same operation: torch indexing / torch fp32 in the reference's order where the kernel must be
 bit-exact, float64 elsewhere.  Need an MI355X.
 

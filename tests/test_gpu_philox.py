@@ -1,4 +1,4 @@
-"""philox_normal4 (csrc/sampler.hip) on the GPU, held to tests/philox_restatement.py: gdx_randn per element against the float64
+"""philox_normal4 (csrc/gdx_pose_device.h) on the GPU, held to tests/philox_restatement.py: gdx_randn per element against the float64
 restatement at keys that set every counter and key word, the Box-Muller edge rows, the statistics of the key sets fixed on the
 CPU (tests/test_philox_host.py), and every kernel that draws in-kernel noise against the same call fed gdx_randn's tape, bit for
 bit, at a seed >= 2^32 and a batch that crosses sample 2^32.  The bound, its unit and K: philox_restatement.py."""

@@ -1,4 +1,4 @@
-"""The pose-layout sampler kernels behind their float4 dispatch (sampler.hip: vec_ok, pred_xstart4, update_value): every
+"""The pose-layout sampler kernels behind their float4 dispatch (sampler.hip; gdx_pose_host.h: vec_ok; gdx_pose_device.h: pred_xstart4, update_value): every
 CFG / inpainting / clip_denoised combination of gdx_sampler_update against the torch-CPU expressions of oracle/sampler.py,
 and gdx_bpd_terms on operands off 16-byte alignment against itself on aligned ones -- all by torch.equal."""
 import itertools

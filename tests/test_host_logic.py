@@ -643,3 +643,30 @@ def test_half_srcs_are_exactly_the_kernel_files_that_mention_half_t():
     assert once
     for f in once:
         assert "GDX_HNS_BEGIN" not in text[f] and "half_t" not in text[f], f
+
+
+def test_exact_srcs_are_exactly_the_files_that_include_the_pose_device_header():
+    """The bit-pinned formulas of gdx_pose_device.h need every mul and add rounded on its own.  One rule keeps contraction off
+    for them: the header opens with the pragma, the files that include it are the Makefile's EXACT_SRCS, and exactly the
+    objects of EXACT_SRCS are compiled with -ffp-contract=off (read off `make -n`; the compiler is not run)."""
+    csrc = os.path.join(REPO, "gesturediffusion_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    srcs, half, exact = (re.search(r"^%s\s*=\s*(.*)$" % var, mk, re.M).group(1).split() for var in ("SRCS", "HALF_SRCS", "EXACT_SRCS"))
+    assert exact and set(exact) <= set(srcs)
+    hips = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert set(hips) == set(srcs)
+    including = [f for f in hips if re.search(r'^#include "gdx_pose_device\.h"', open(os.path.join(csrc, f)).read(), re.M)]
+    assert sorted(exact) == including
+    header = open(os.path.join(csrc, "gdx_pose_device.h")).read()
+    code = [ln for ln in header.splitlines() if ln.strip() and not ln.startswith("//")]
+    assert code[:2] == ["#pragma once", "#pragma clang fp contract(off)"], code[:2]
+
+    out = subprocess.run(["make", "-n", "-B", "-C", csrc], check=True, capture_output=True, text=True).stdout
+    flagged = {}
+    for ln in out.splitlines():
+        m = re.search(r" -c (\S+)\.hip -o (\S+\.o)\s*$", ln)
+        if m:
+            flagged[m.group(2)] = "-ffp-contract=off" in ln.split()
+    objs = {f[:-4] + ".o" for f in srcs} | {f[:-4] + ".bf16.o" for f in half}
+    assert set(flagged) == objs
+    assert {o for o, on in flagged.items() if on} == {f[:-4] + ".o" for f in exact}

@@ -4,7 +4,8 @@
     python tools/isa_compare.py OLD_TREE NEW_TREE [-j N]
 
 Every kernel file of csrc/ is compiled to device-only assembly with the Makefile's flags (the files of each tree's own
-HALF_SRCS line also with -DGDX_BF16, sampler.hip with -ffp-contract=off).  Per kernel the instruction stream (comments and the
+HALF_SRCS line also with -DGDX_BF16, the files of its own EXACT_SRCS line with -ffp-contract=off; a tree from before that line
+existed has the flag on sampler.hip, as it was built).  Per kernel the instruction stream (comments and the
 per-file numbers of local labels dropped) and the .vgpr_count / .sgpr_count / LDS / scratch / kernarg sizes of the metadata are
 compared.  Kernels are matched by symbol (and the variant's extra flags) across the whole tree, so one that moved to another file
 compares equal and is reported as moved.  The half builds' namespaces gdx::h16:: and gdx::b16:: count as gdx:: (the -DGDX_BF16
@@ -25,20 +26,21 @@ FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-variable -
 META = (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".kernarg_segment_size")
 
 
-def half_srcs(csrc):
-    """the files a tree builds a second time with -DGDX_BF16: the HALF_SRCS line of its Makefile"""
-    m = re.search(r"^HALF_SRCS\s*=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
-    return m.group(1).split() if m else []
+def makefile_list(csrc, var, default):
+    """the files of the line `var = ...` of a tree's Makefile; `default` for a tree whose Makefile has no such line"""
+    m = re.search(r"^%s\s*=\s*(.*)$" % var, open(os.path.join(csrc, "Makefile")).read(), re.M)
+    return m.group(1).split() if m else default
 
 
 def variants(csrc):
-    half = half_srcs(csrc)
+    half = makefile_list(csrc, "HALF_SRCS", [])                 # built a second time with -DGDX_BF16
+    exact = makefile_list(csrc, "EXACT_SRCS", ["sampler.hip"])  # built with -ffp-contract=off; older trees: the one file
     for f in sorted(os.listdir(csrc)):
         if not f.endswith(".hip"):
             continue
         if "__global__" not in open(os.path.join(csrc, f)).read():
             continue
-        yield f, f, ["-ffp-contract=off"] if f == "sampler.hip" else []
+        yield f, f, ["-ffp-contract=off"] if f in exact else []
         if f in half:
             yield f + " -DGDX_BF16", f, ["-DGDX_BF16"]
 
