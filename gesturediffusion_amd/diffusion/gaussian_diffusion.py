@@ -38,6 +38,7 @@ import numpy as np
 import torch as th
 
 from .. import engine as E
+from .. import sampling_options
 from ..engine import GDX_CFG, GDX_COND, GDX_UNCOND
 from .._lib import GDX_SAMPLER_DDIM, GDX_SAMPLER_P
 
@@ -553,25 +554,18 @@ class GaussianDiffusion:
             from ..model.mdm import _window_error
             raise _window_error(T, 10)
         guided = isinstance(model, ClassifierFreeSampleModel)
-        interval = E.guidance_interval_of(y, guided)
-        phi = E.guidance_rescale_of(y, guided)
-        every = E.guidance_refresh_of(y, guided)
-        layer_cache = E.layer_cache_of(y, inner.num_layers)
-        compose, text_scale = E.guidance_compose_of(y, guided, getattr(inner, "use_text", False))
-        E.refuse_compose_conflicts(y, compose, inner.num_layers, parallel=window is not None)
+        options = sampling_options.read(y, guided=guided, num_layers=inner.num_layers, use_text=getattr(inner, "use_text", False))
+        options.refuse_conflicts(parallel=window is not None)
         eng = inner._get_engine(x.device)
-        eng.set_guidance_compose(compose)            # in front of the conditioning, whose rows depend on it; absent keys set JOINT
+        options.apply_before_condition(eng)
         if window is None:
             eng.prepare(B, T)
             eng.set_condition(y["seed"], y["mfcc"], text=inner._text_features(y, B), cache=False)
         else:
             eng.prepare_window(B, T, window, y["seed"], y["mfcc"], text=inner._text_features(y, B))
-        eng.set_guidance_interval(interval)          # at every loop; None resets a reused handle to "every timestep"
-        eng.set_guidance_rescale(phi)                # likewise: an absent key sets 0 (off)
-        eng.set_guidance_refresh(every)              # likewise: an absent key sets 1 (off); every loop starts with a refresh
-        eng.set_layer_cache(*layer_cache)            # likewise: an absent key sets every = 1 (off); every loop starts with a full call
+        options.apply_after_condition(eng)           # at every loop: every loop starts with a refresh and a full call
         if guided:
-            mode, scale = GDX_CFG, E.f32c(E.pack_scales(compose, y["scale"], text_scale), "y['scale']")
+            mode, scale = GDX_CFG, E.f32c(options.scale_operand(y["scale"]), "y['scale']")
         else:
             mode, scale = (GDX_UNCOND if y.get("uncond", False) else GDX_COND), None
         mask = motion = None
@@ -584,13 +578,15 @@ class GaussianDiffusion:
     @staticmethod
     def _refuse_refresh(model, model_kwargs, who):
         """A path that calls the model step by step, or whose calls are independent of one another, can serve neither
-        y['guidance_refresh'] > 1 nor y['layer_cache'] with every > 1 (engine.refuse_guidance_refresh, engine.refuse_layer_cache)."""
+        y['guidance_refresh'] > 1 nor y['layer_cache'] with every > 1 (sampling_options.MEMORY)."""
         from ..model.cfg_sampler import ClassifierFreeSampleModel
         y = (model_kwargs or {}).get("y")
         if isinstance(y, dict):
-            E.refuse_guidance_refresh(y, isinstance(model, ClassifierFreeSampleModel), who)
-            inner = getattr(model, "model", model) if isinstance(model, ClassifierFreeSampleModel) else model
-            E.refuse_layer_cache(y, getattr(inner, "num_layers", 2**31), who)      # a foreign model: keep cannot be judged
+            guided = isinstance(model, ClassifierFreeSampleModel)
+            inner = getattr(model, "model", model) if guided else model
+            layers = getattr(inner, "num_layers", 2**31)                           # a foreign model: keep cannot be judged
+            sampling_options.read(y, guided=guided, num_layers=layers, use_text=False,
+                                  options=sampling_options.MEMORY).refuse_memory(who)
 
     def _runs_fused(self, fused, model, denoised_fn, cond_fn):
         """The route of every sampling loop: inside libgdx for a native START_X denoiser (or its ClassifierFreeSampleModel)
@@ -692,7 +688,7 @@ class GaussianDiffusion:
         diffusion's indices num_timesteps - 1 - skip_timesteps .. 0; plms: step 0 makes a second call at the index below the
         first (modulo num_timesteps), as plms_sample_loop does.  The guided calls are numbered n = 0, 1, ... in this order and
         call n refreshes when n % guidance_refresh == 0: the rule of gdx_set_guidance_refresh, on the host."""
-        every = E.guidance_refresh_of({"guidance_refresh": guidance_refresh}, True)
+        every = E.guidance_refresh_value(guidance_refresh)
         flags = self.guided_steps(guidance_interval)
         n_t = self.num_timesteps
         calls = list(range(n_t - skip_timesteps))[::-1]
@@ -716,7 +712,7 @@ class GaussianDiffusion:
         `mode` (GDX_COND when None).  ALL calls are numbered m = 0, 1, ...; call m is full when m % every == 0 or when the
         mode stored by the most recent full call does not cover its own (the same mode, or GDX_CFG for a GDX_COND call): the
         rule of gdx_set_layer_cache, on the host.  The plan does not depend on keep."""
-        every, _ = E.layer_cache_of({"layer_cache": layer_cache}, 2**31)
+        every, _ = E.layer_cache_value(layer_cache, 2**31)
         if guided:
             calls = self.guidance_plan(guidance_interval, guidance_refresh, plms=plms, skip_timesteps=skip_timesteps)
             modes = [GDX_CFG if c == "refresh" else GDX_COND for c in calls]

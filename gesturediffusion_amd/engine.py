@@ -457,33 +457,6 @@ def guidance_compose_of(y, guided_model, use_text=True):
     return GUIDANCE_ORDERS[order], require_device(ts, "y['text_scale']")
 
 
-def pack_scales(mode, scale, text_scale):
-    """The `scale` operand of a guided call: y['scale'] flattened [B], or in a 3-pass mode [2, B] in stage order -- row 0 the
-    scale of the condition stepped to first, row 1 the other's (gdx_set_guidance_compose)."""
-    scale = scale.reshape(-1).float()
-    if text_scale is None:
-        return scale.contiguous()
-    text_scale = text_scale.reshape(-1).float()
-    first, second = (scale, text_scale) if mode == _lib.GDX_GUIDE_SEED_TEXT else (text_scale, scale)
-    return torch.stack([first, second]).contiguous()
-
-
-def refuse_compose_conflicts(y, mode, num_layers, parallel=False):
-    """A 3-pass mode runs three row groups; the guidance refresh and the layer cache are written for two, and the window of
-    parallel_sample_loop (`parallel`) repeats one scale per slot (gdx.h)."""
-    if mode < _lib.GDX_GUIDE_SEED_TEXT:
-        return
-    if parallel:
-        raise ValueError("y['text_scale'] (3-pass guidance) is not supported by parallel_sample_loop, whose window repeats one "
-                         "scale per slot: use y['guidance_drop']")
-    if guidance_refresh_of(y, True) > 1:
-        raise ValueError("y['text_scale'] (3-pass guidance) and y['guidance_refresh'] > 1 exclude each other: the refresh stores "
-                         "one cond-uncond difference")
-    if layer_cache_of(y, num_layers)[0] > 1:
-        raise ValueError("y['text_scale'] (3-pass guidance) and y['layer_cache'] with every > 1 exclude each other: the cache "
-                         "holds two row groups")
-
-
 def guidance_rescale_of(y, guided_model):
     """y['guidance_rescale'] validated -> phi, a Python float with 0 <= phi <= 1 (0.0 when the key is absent: off).  ValueError
     for anything but a finite Python float or int in that range -- a bool is refused, and a tensor because reading it would
@@ -508,9 +481,13 @@ def guidance_refresh_of(y, guided_model):
     a model that is not a ClassifierFreeSampleModel (`guided_model` False)."""
     if "guidance_refresh" not in y:
         return 1
-    every = y["guidance_refresh"]
     if not guided_model:
         raise ValueError("y['guidance_refresh'] needs a ClassifierFreeSampleModel: this model runs no guidance to refresh")
+    return guidance_refresh_value(y["guidance_refresh"])
+
+
+def guidance_refresh_value(every):
+    """guidance_refresh_of's rule for the value itself (GaussianDiffusion.guidance_plan takes it as an argument)."""
     if isinstance(every, torch.Tensor):
         raise ValueError("y['guidance_refresh'] must be a Python int, not a tensor: reading it would synchronise")
     if isinstance(every, bool) or not isinstance(every, (int, np.integer)):
@@ -525,9 +502,11 @@ def layer_cache_of(y, num_layers):
     but two Python ints -- a bool and a float are refused, and a tensor because reading it would synchronise --, for every < 1,
     and, when every > 1, for keep outside 1 .. num_layers - 1.  At every = 1 keep is not looked at.  Needs no
     ClassifierFreeSampleModel: the cache sits inside the denoiser."""
-    if "layer_cache" not in y:
-        return 1, 0
-    lc = y["layer_cache"]
+    return layer_cache_value(y["layer_cache"], num_layers) if "layer_cache" in y else (1, 0)
+
+
+def layer_cache_value(lc, num_layers):
+    """layer_cache_of's rule for the value itself (GaussianDiffusion.layer_cache_plan takes it as an argument)."""
     if isinstance(lc, torch.Tensor) or (isinstance(lc, (tuple, list)) and any(isinstance(v, torch.Tensor) for v in lc)):
         raise ValueError("y['layer_cache'] must be two Python ints (every, keep), not a tensor: reading it would synchronise")
     ok = (isinstance(lc, (tuple, list)) and len(lc) == 2
@@ -542,28 +521,6 @@ def layer_cache_of(y, num_layers):
     if not 1 <= keep <= num_layers - 1:
         raise ValueError(f"y['layer_cache'] must satisfy 1 <= keep <= num_layers - 1 = {num_layers - 1}, got {lc!r}")
     return every, keep
-
-
-def refuse_layer_cache(y, num_layers, who):
-    """The layer cache needs memory across denoiser calls, which only the in-library loops have: ValueError when
-    y['layer_cache'] with every > 1 reaches `who`, a path that makes every call on its own."""
-    every, keep = layer_cache_of(y, num_layers)
-    if every > 1:
-        raise ValueError(f"y['layer_cache'] = ({every}, {keep}) needs the in-library loop (p_sample_loop, ddim_sample_loop, "
-                         f"plms_sample_loop, dpm_solver_sample_loop, dpm_solver_sde_sample_loop or unipc_sample_loop with fused=True on a "
-                         f"native model, without cond_fn / denoised_fn): {who} cannot carry the deep layers' change from one call "
-                         f"to the next")
-
-
-def refuse_guidance_refresh(y, guided_model, who):
-    """The guidance refresh needs memory across denoiser calls, which only the in-library loops have: ValueError when
-    y['guidance_refresh'] > 1 reaches `who`, a path that makes every call on its own."""
-    every = guidance_refresh_of(y, guided_model)
-    if every > 1:
-        raise ValueError(f"y['guidance_refresh'] = {every} needs the in-library loop (p_sample_loop, ddim_sample_loop, "
-                         f"plms_sample_loop, dpm_solver_sample_loop, dpm_solver_sde_sample_loop or unipc_sample_loop with fused=True on a native "
-                         f"model, without cond_fn / denoised_fn): {who} cannot carry the guidance difference from one call to "
-                         f"the next")
 
 
 # ---------------------------------------------------------------------- standalone kernels

@@ -14,11 +14,12 @@ between guided calls; this forward has no memory and raises ValueError for k > 1
 `y['layer_cache'] = (every, keep)` with every > 1 (the deep encoder layers' change reused between calls).
 For a use_text model `y['guidance_drop']` ("both" | "text" | "seed") names what the contrast pass drops, and `y['text_scale']`
 ([B], with `y['guidance_order']`) steers the two conditions on their own in three passes (engine.guidance_compose_of).
+Every key is one entry of sampling_options.OPTIONS, the table through which this forward and the loops read them.
 """
 import torch.nn as nn
 
-from ..engine import (GDX_CFG, guidance_compose_of, guidance_interval_of, guidance_rescale_of, pack_scales, refuse_guidance_refresh,
-                      refuse_layer_cache)
+from .. import sampling_options
+from ..engine import GDX_CFG
 from .mdm import _NativeDenoiser
 
 
@@ -51,18 +52,13 @@ class ClassifierFreeSampleModel(nn.Module):
             raise _window_error(nframes, 10)
         if m.data_rep != "genea_vec":
             raise NotImplementedError
-        interval = guidance_interval_of(y, True)
-        phi = guidance_rescale_of(y, True)
-        compose, text_scale = guidance_compose_of(y, True, getattr(m, "use_text", False))
-        refuse_guidance_refresh(y, True, "the step-wise forward of ClassifierFreeSampleModel")
-        refuse_layer_cache(y, m.num_layers, "the step-wise forward of ClassifierFreeSampleModel")
+        options = sampling_options.read(y, guided=True, num_layers=m.num_layers, use_text=getattr(m, "use_text", False))
+        options.refuse_memory("the step-wise forward of ClassifierFreeSampleModel")
         eng = m._get_engine(x.device)
-        eng.set_guidance_compose(compose)          # in front of the conditioning, whose rows depend on it; absent keys set JOINT
+        options.apply_before_condition(eng)
         eng.prepare(bs, nframes)
         eng.set_condition(seed, mfcc, text=m._text_features(y, bs))
-        # per-sample choice in the blend kernel: guided where lo <= timesteps[b] <= hi, else the conditional output; set on
-        # every call (None: every timestep), so a handle never keeps the interval of an earlier call
-        eng.set_guidance_interval(interval)
-        eng.set_guidance_rescale(phi)              # likewise: an absent key sets 0
-        out = eng.forward(x, timesteps, GDX_CFG, pack_scales(compose, scale, text_scale))
+        # the interval is a per-sample choice in the blend kernel: guided where lo <= timesteps[b] <= hi, else the conditional output
+        options.apply_after_condition(eng)
+        out = eng.forward(x, timesteps, GDX_CFG, options.scale_operand(scale))
         return out.view(bs, njoints, nfeats, nframes)

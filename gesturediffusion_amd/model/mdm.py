@@ -14,8 +14,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..engine import (GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, guidance_compose_of, guidance_interval_of, guidance_rescale_of,
-                      refuse_layer_cache, require_device)
+from .. import sampling_options
+from ..engine import GDX_ARCH_MDM, GDX_COND, GDX_UNCOND, Engine, GdxError, require_device
 from .rotation2xyz import Rotation2xyz
 
 ROPE_ROWS = 4096
@@ -267,6 +267,12 @@ class _NativeDenoiser(nn.Module):
         if self.training and self.cond_mask_prob > 0.0:
             raise NotImplementedError("only the sampling path (model.eval()) is implemented natively")
 
+    def _refuse_options(self, y, name):
+        """The sampling options of y at a plain step-wise forward: ValueError for a key that needs a ClassifierFreeSampleModel and
+        for one that needs memory across calls.  y['guidance_refresh'] is not looked at (sampling_options.PLAIN_FORWARD)."""
+        sampling_options.read(y, guided=False, num_layers=self.num_layers, use_text=False,
+                              options=sampling_options.PLAIN_FORWARD).refuse_memory(f"the step-wise forward of {name}")
+
     def parameters_wo_clip(self):
         return [p for name, p in self.named_parameters() if not name.startswith("clip_model.")]
 
@@ -349,10 +355,7 @@ class MDM(_NativeDenoiser):
         [B,26,1,T], optional 'uncond'; a use_text model also takes 'text_embed' [B, clip_dim] (or 'text', a list of B strings,
         once set_text_encoder installed an encoder).  Returns [B, njoints, nfeats, T] (contiguous)."""
         self._check_inputs(x, y)
-        guidance_interval_of(y, False)                     # the key needs a ClassifierFreeSampleModel: ValueError here
-        guidance_rescale_of(y, False)
-        guidance_compose_of(y, False)
-        refuse_layer_cache(y, self.num_layers, "the step-wise forward of MDM")
+        self._refuse_options(y, "MDM")
         bs, njoints, nfeats, nframes = x.shape
         force_mask = y.get("uncond", False)
         text = self._text_features(y, bs)                  # the reference reads y['text'] before y['seed'] (model/mdm.py:120)

@@ -7,8 +7,7 @@ All arithmetic runs in libgdx.so; the modules only hold parameters.
 """
 import torch.nn as nn
 
-from ..engine import (GDX_ARCH_MDM_OLD, GDX_COND, GDX_UNCOND, guidance_compose_of, guidance_interval_of, guidance_rescale_of,
-                      refuse_layer_cache)
+from ..engine import GDX_ARCH_MDM_OLD, GDX_COND, GDX_UNCOND
 from .mdm import (EncoderParams, InputProcess, OutputProcess, PositionalEncoding, SeedPoseEncoder, TimestepEmbedder,
                   _NativeDenoiser)
 from .rotation2xyz import Rotation2xyz
@@ -49,10 +48,7 @@ class MDM_Old(_NativeDenoiser):
 
     def forward(self, x, timesteps, y=None):
         self._check_inputs(x, y)
-        guidance_interval_of(y, False)                     # the key needs a ClassifierFreeSampleModel: ValueError here
-        guidance_rescale_of(y, False)
-        guidance_compose_of(y, False)
-        refuse_layer_cache(y, self.num_layers, "the step-wise forward of MDM_Old")
+        self._refuse_options(y, "MDM_Old")
         bs, njoints, nfeats, nframes = x.shape
         force_mask = y.get("uncond", False)
         seed = y["seed"]

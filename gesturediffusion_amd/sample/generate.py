@@ -32,6 +32,7 @@ import torch
 
 from .. import engine as E
 from ..model.cfg_sampler import ClassifierFreeSampleModel
+from ..sampling_options import y_of_kwargs
 from ..utils import dist_util
 from ..utils.fixseed import fixseed
 from ..data_loaders.get_data import get_dataset_loader
@@ -110,6 +111,9 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     sample_fn = {"p": diffusion.p_sample_loop, "ddim": diffusion.ddim_sample_loop, "plms": diffusion.plms_sample_loop,
                  "dpmpp": diffusion.dpm_solver_sample_loop, "dpmpp_sde": diffusion.dpm_solver_sde_sample_loop,
                  "unipc": diffusion.unipc_sample_loop}[sampler]
+    options = dict(guidance_interval=guidance_interval, guidance_rescale=guidance_rescale, guidance_refresh=guidance_refresh,
+                   text_guidance_param=text_guidance_param, guidance_order=guidance_order, guidance_drop=guidance_drop,
+                   layer_cache=layer_cache)
     outs, sample_out = [], None
     for chunk in range(n_chunks):
         y = {"mfcc": mfcc_of_chunk(chunk), "seed": first_seed if chunk == 0 else sample_out[..., -seed_poses:]}
@@ -117,20 +121,7 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
             y["text_embed"] = text_of_chunk(chunk)
         if guidance_param != 1:
             y["scale"] = torch.ones(b, device=first_seed.device) * guidance_param
-        if guidance_interval is not None:
-            y["guidance_interval"] = (int(guidance_interval[0]), int(guidance_interval[1]))
-        if guidance_rescale > 0:
-            y["guidance_rescale"] = float(guidance_rescale)
-        if guidance_refresh > 1:
-            y["guidance_refresh"] = guidance_refresh
-        if text_guidance_param is not None:
-            y["text_scale"] = torch.ones(b, device=first_seed.device) * text_guidance_param
-        if guidance_order is not None:
-            y["guidance_order"] = guidance_order
-        if guidance_drop is not None:
-            y["guidance_drop"] = guidance_drop
-        if layer_cache is not None:
-            y["layer_cache"] = (int(layer_cache[0]), int(layer_cache[1]))
+        y.update(y_of_kwargs(options, b, first_seed.device))
         kw = dict(clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=0, init_image=None, progress=progress,
                   noise=None, rng=rng, philox_seed=philox_seed + 1000 * chunk, sample_offset=sample_offset,
                   noise_tape=noise_tapes[chunk] if noise_tapes is not None else None)

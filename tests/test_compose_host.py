@@ -10,6 +10,7 @@ import compose_restatement as cr
 from conftest import load_golden, rel_err
 from gesturediffusion_amd import _lib
 from gesturediffusion_amd import engine as E
+from gesturediffusion_amd import sampling_options
 from oracle import sampler as osamp
 from oracle import schedule as osch
 
@@ -71,14 +72,16 @@ def test_equal_scales_give_the_joint_blend_in_fp64(g):
 
 # ------------------------------------------------------------------------------------------------------------ the [2][B] packing
 def test_scales_are_packed_in_stage_order():
+    def operand(mode, scale, text_scale):
+        return sampling_options.Record({"compose": (mode, text_scale)}).scale_operand(scale)
     seed, text = torch.tensor([1.0, 2.0, 3.0]), torch.tensor([10.0, 20.0, 30.0])
-    a = E.pack_scales(_lib.GDX_GUIDE_SEED_TEXT, seed.view(3, 1), text)
-    b = E.pack_scales(_lib.GDX_GUIDE_TEXT_SEED, seed, text.double())
+    a = operand(_lib.GDX_GUIDE_SEED_TEXT, seed.view(3, 1), text)
+    b = operand(_lib.GDX_GUIDE_TEXT_SEED, seed, text.double())
     assert a.shape == b.shape == (2, 3) and a.is_contiguous() and b.is_contiguous() and b.dtype == torch.float32
     assert torch.equal(a, torch.stack([seed, text])) and torch.equal(b, torch.stack([text, seed]))
     assert torch.equal(a, cr.packed(cr.SEED_TEXT, seed, text)) and torch.equal(b, cr.packed(cr.TEXT_SEED, seed, text))
     for mode in (_lib.GDX_GUIDE_JOINT, _lib.GDX_GUIDE_TEXT, _lib.GDX_GUIDE_SEED):
-        assert torch.equal(E.pack_scales(mode, seed.view(3, 1, 1, 1), None), seed)
+        assert torch.equal(operand(mode, seed.view(3, 1, 1, 1), None), seed)
     assert [_lib.GDX_GUIDE_JOINT, _lib.GDX_GUIDE_TEXT, _lib.GDX_GUIDE_SEED, _lib.GDX_GUIDE_SEED_TEXT, _lib.GDX_GUIDE_TEXT_SEED] == [
         cr.JOINT, cr.TEXT, cr.SEED, cr.SEED_TEXT, cr.TEXT_SEED] == list(range(5))
 
@@ -146,16 +149,20 @@ def test_plain_models_refuse_the_new_keys():
 def test_three_pass_conflicts():
     y = {"text_scale": torch.ones(2)}
     three, two = _lib.GDX_GUIDE_SEED_TEXT, _lib.GDX_GUIDE_TEXT
-    E.refuse_compose_conflicts(y, three, 8)
-    E.refuse_compose_conflicts(dict(y, guidance_refresh=1, layer_cache=(1, 0)), _lib.GDX_GUIDE_TEXT_SEED, 8)
+
+    def conflicts(y, mode, num_layers, parallel=False):         # the mode as given: y['text_scale'] is on the host
+        sampling_options.Record({"compose": (mode, y.get("text_scale")), "refresh": E.guidance_refresh_of(y, True),
+                                 "layer_cache": E.layer_cache_of(y, num_layers)}).refuse_conflicts(parallel=parallel)
+    conflicts(y, three, 8)
+    conflicts(dict(y, guidance_refresh=1, layer_cache=(1, 0)), _lib.GDX_GUIDE_TEXT_SEED, 8)
     with pytest.raises(ValueError, match=r"guidance_refresh'\] > 1 exclude each other"):
-        E.refuse_compose_conflicts(dict(y, guidance_refresh=2), three, 8)
+        conflicts(dict(y, guidance_refresh=2), three, 8)
     with pytest.raises(ValueError, match=r"layer_cache'\] with every > 1 exclude each other"):
-        E.refuse_compose_conflicts(dict(y, layer_cache=(2, 1)), three, 8)
+        conflicts(dict(y, layer_cache=(2, 1)), three, 8)
     with pytest.raises(ValueError, match="not supported by parallel_sample_loop"):
-        E.refuse_compose_conflicts(y, three, 8, parallel=True)
+        conflicts(y, three, 8, parallel=True)
     # the two-pass modes keep every feature
-    E.refuse_compose_conflicts({"guidance_drop": "text", "guidance_refresh": 2, "layer_cache": (2, 1)}, two, 8, parallel=True)
+    conflicts({"guidance_drop": "text", "guidance_refresh": 2, "layer_cache": (2, 1)}, two, 8, parallel=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the C ABI

@@ -36,19 +36,22 @@ def test_key_validation():
 def test_paths_without_memory_refuse_the_key():
     """every > 1 outside the in-library loops is a ValueError that names the in-library loop; every = 1 and no key pass."""
     from gesturediffusion_amd.diffusion.gaussian_diffusion import GaussianDiffusion
-    from gesturediffusion_amd.engine import refuse_guidance_refresh
     from gesturediffusion_amd.model.cfg_sampler import ClassifierFreeSampleModel
+    from gesturediffusion_amd.sampling_options import MEMORY, read
+
+    def refuse(y, guided_model, who):
+        read(y, guided=guided_model, num_layers=8, use_text=False, options=MEMORY).refuse_memory(who)
     for k in (2, 3, 100):
         with pytest.raises(ValueError, match="in-library loop") as e:
-            refuse_guidance_refresh({"guidance_refresh": k}, True, "the step-wise forward")
+            refuse({"guidance_refresh": k}, True, "the step-wise forward")
         assert "the step-wise forward" in str(e.value) and f"= {k}" in str(e.value)
-    refuse_guidance_refresh({"guidance_refresh": 1}, True, "x")
-    refuse_guidance_refresh({}, True, "x")
-    refuse_guidance_refresh({}, False, "x")
+    refuse({"guidance_refresh": 1}, True, "x")
+    refuse({}, True, "x")
+    refuse({}, False, "x")
     with pytest.raises(ValueError, match="ClassifierFreeSampleModel"):
-        refuse_guidance_refresh({"guidance_refresh": 2}, False, "x")
+        refuse({"guidance_refresh": 2}, False, "x")
     with pytest.raises(ValueError, match="guidance_refresh"):
-        refuse_guidance_refresh({"guidance_refresh": 0}, True, "x")
+        refuse({"guidance_refresh": 0}, True, "x")
     guided = object.__new__(ClassifierFreeSampleModel)       # only its type is looked at
     with pytest.raises(ValueError, match="in-library loop"):
         GaussianDiffusion._refuse_refresh(guided, {"y": {"guidance_refresh": 2}}, "calc_bpd_loop")

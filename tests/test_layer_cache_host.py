@@ -47,16 +47,19 @@ def test_paths_without_memory_refuse_the_key():
     """every > 1 outside the in-library loops is a ValueError that names the in-library loop; every = 1 and no key pass; the
     key needs no guided model."""
     from gesturediffusion_amd.diffusion.gaussian_diffusion import GaussianDiffusion
-    from gesturediffusion_amd.engine import refuse_layer_cache
     from gesturediffusion_amd.model.cfg_sampler import ClassifierFreeSampleModel
+    from gesturediffusion_amd.sampling_options import MEMORY, read
+
+    def refuse(y, num_layers, who):
+        read(y, guided=False, num_layers=num_layers, use_text=False, options=MEMORY).refuse_memory(who)
     for lc in ((2, 1), (3, 2), (100, 7)):
         with pytest.raises(ValueError, match="in-library loop") as e:
-            refuse_layer_cache({"layer_cache": lc}, 8, "the step-wise forward")
+            refuse({"layer_cache": lc}, 8, "the step-wise forward")
         assert "the step-wise forward" in str(e.value) and f"= ({lc[0]}, {lc[1]})" in str(e.value)
-    refuse_layer_cache({"layer_cache": (1, 0)}, 8, "x")
-    refuse_layer_cache({}, 8, "x")
+    refuse({"layer_cache": (1, 0)}, 8, "x")
+    refuse({}, 8, "x")
     with pytest.raises(ValueError, match="two Python ints"):
-        refuse_layer_cache({"layer_cache": 2}, 8, "x")
+        refuse({"layer_cache": 2}, 8, "x")
     guided = object.__new__(ClassifierFreeSampleModel)       # only its type is looked at
     for model in (guided, lambda x, t, **kw: x):
         with pytest.raises(ValueError, match="in-library loop"):
