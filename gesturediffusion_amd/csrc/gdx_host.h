@@ -3,6 +3,7 @@
 // bench entry points); the helpers declared here are defined in the first three.
 #pragma once
 #include "gdx_call_plan.h"
+#include "gdx_resample_plan.h"
 #include "gdx_window_stride.h"
 #include "gdx_internal.h"
 
@@ -129,6 +130,8 @@ struct LateWorkspace {
                                       // type, kept until the end of a full call
     bool lc_valid = false;            // ... lc_delta holds a full call's change under the current conditioning,
     int lc_mode = 0;                  // ... stored by a call of this forward mode (GDX_COND / GDX_UNCOND / GDX_CFG)
+    float* rp_tab = nullptr; int rp_tab_rows = 0;   // resampling: the device image of the handle's rp_rows, regrown for a longer schedule
+    bool rp_tab_valid = false;        // ... holds the rows of the most recent gdx_set_resample
 };
 
 }  // namespace gdx
@@ -161,6 +164,8 @@ struct gdx_model {
     int guide_every = 1;              // gdx_set_guidance_refresh: the unconditional pass runs on every guide_every-th guided call
     int lc_every = 1, lc_keep = 0;    // gdx_set_layer_cache: every lc_every-th denoiser call of a loop is full; the calls between
                                       // run lc_keep layers and add the stored change of the deeper ones (1 = off)
+    int rp_jump = 1, rp_repeats = 1, rp_steps = 0;   // gdx_set_resample: repeats = 1 is off; rp_steps = the schedule's length
+    std::vector<float> rp_rows;       // ... host [rp_steps][2]: row l = (a, b) of the forward hop from level l to level l + rp_jump
     int64_t forward_samples = 0;     // gdx_forward_samples: samples pushed through forward_core since gdx_create
     int64_t forward_layer_samples = 0;   // gdx_forward_layer_samples: samples x encoder layers launched
     gdx::Act xa, xb, qkv, ctx, tmp, ffb;   // [rows_alloc] token rows: residual stream (xa, xb), sublayer operands and outputs
@@ -208,6 +213,8 @@ template <class T> int ws_need(gdx_model* h, T** p, size_t bytes, hipStream_t s)
 }
 int check_ready(gdx_model* h, const char* who);                   // handle, gdx_prepare and a conditioning, or the refusal
 int check_mode(const char* who, int mode, const float* scale);
+// the refusal of a loop `who` whose history does not survive a forward hop, while resampling is on (gdx_set_resample)
+int refuse_resampling(const gdx_model* h, const char* who);
 
 // forward.hip
 struct ForwardOpts {

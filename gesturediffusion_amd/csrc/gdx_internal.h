@@ -254,6 +254,10 @@ int gdx_sampler_update_tm_(const gdx::UpdateTmDev& d, void* stream);
 int gdx_ddim_reverse_step_(const gdx::DdimReverseStepArgs& a, void* stream);
 // gdx_parallel_loop: the window's planes [W + 1][plane] slid down by `stride` planes, the tail filled with P_W (window_slide_kernel)
 int gdx_window_slide_(float* planes, long plane, int W, int stride, void* stream);
+// gdx_sample_loop under gdx_set_resample: one forward hop x <- a*x + b*z in place, (a, b) = row `row` of tab [rows][2], z = noise
+// [batch][per_sample] or the Philox draw rng_step (renoise_kernel)
+int gdx_renoise_(float* x, const float* tab, int row, int batch, long per_sample, const float* noise, uint64_t seed,
+                 uint64_t sample_offset, uint32_t rng_step, void* stream);
 // bound.hip.  gdx_bpd_loop: x_t and the stored Philox noise of one step (bpd_xt_kernel)
 int gdx_bpd_xt_(const float* x0, const float* coef, int idx, int batch, long per_sample, uint64_t seed, uint64_t sample_offset,
                 uint32_t step, float* z_out, float* xt_out, void* stream);

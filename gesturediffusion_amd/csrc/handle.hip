@@ -362,6 +362,33 @@ extern "C" int gdx_set_layer_cache(gdx_handle_t h, int32_t every, int32_t keep) 
     return 0;
 }
 
+// Resampling (gdx.h): per-handle (jump, repeats), repeats = 1 = off, and the fp32 (a, b) row of every forward hop the schedule
+// admits.  Refusals precede any HIP call, and the setter makes none: gdx_sample_loop uploads the rows on its own stream.
+extern "C" int gdx_set_resample(gdx_handle_t h, int32_t jump, int32_t repeats, const double* alpha_bar, int32_t num_steps) {
+    if (!h) return fail("gdx_set_resample: null handle");
+    if (jump < 1) return fail("gdx_set_resample: jump must be at least 1");
+    if (repeats < 1) return fail("gdx_set_resample: repeats must be at least 1");
+    std::vector<float> rows;
+    if (repeats > 1) {
+        if (!alpha_bar || num_steps <= 0) return fail("gdx_set_resample: repeats > 1 needs alpha_bar [num_steps]");
+        for (int i = 0; i < num_steps; ++i)
+            if (!(alpha_bar[i] > 0.0 && alpha_bar[i] <= 1.0 && (i == 0 || alpha_bar[i] <= alpha_bar[i - 1])))
+                return fail("gdx_set_resample: alpha_bar must lie in (0, 1] and must not increase");
+        rows.assign(2 * (size_t)num_steps, 0.0f);
+        for (int l = 0; l + jump <= num_steps; ++l) resample_coef(alpha_bar, l, l + jump, &rows[2 * l], &rows[2 * l + 1]);
+    }
+    h->rp_jump = jump; h->rp_repeats = repeats; h->rp_steps = repeats > 1 ? num_steps : 0;
+    h->rp_rows.swap(rows);
+    h->late.rp_tab_valid = false;
+    return 0;
+}
+
+int gdx::refuse_resampling(const gdx_model* h, const char* who) {
+    if (h->rp_repeats == 1) return 0;
+    return fail(std::string(who) + ": resampling is on (gdx_set_resample, repeats > 1), and this loop's history does not survive a "
+                                   "forward hop: gdx_sample_loop resamples; set repeats = 1");
+}
+
 extern "C" int gdx_forward_layer_samples(gdx_handle_t h, int64_t* n) {
     if (!h || !n) return fail("gdx_forward_layer_samples: null argument");
     *n = h->forward_layer_samples;

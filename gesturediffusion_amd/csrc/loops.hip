@@ -136,7 +136,7 @@ static int denoise_guided(gdx_model* h, const PlannedCall& e, const float* sc_in
 extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* stream) {
     if (!h) return fail("gdx_bpd_loop: null handle");
     if (!a) return fail("gdx_bpd_loop: null argument");
-    if (check_ready(h, "gdx_bpd_loop")) return -1;
+    if (check_ready(h, "gdx_bpd_loop") || refuse_resampling(h, "gdx_bpd_loop")) return -1;
     if (!a->coef || !a->timestep_map || !a->x_start || !a->vb || !a->xstart_mse || !a->mse)
         return fail("gdx_bpd_loop: null argument");
     if (check_mode("gdx_bpd_loop", a->mode, a->scale)) return -1;
@@ -219,7 +219,7 @@ static int multistep_loop(const char* who, gdx_model* h, const A* a, int order_l
     if (a->order < order_lo || a->order > order_hi) return fail(w + order_msg);
     if (a->inpaint_mask && !a->inpaint_motion) return fail(w + "mask without motion");
     if (const char* m = missing()) return fail(w + m);
-    if (check_ready(h, who)) return -1;
+    if (check_ready(h, who) || refuse_resampling(h, who)) return -1;
     if (h->B > 65535) return fail(w + "batch exceeds 65535");
     const int last_idx = a->run_steps > 0 ? a->first_index - a->run_steps + 1 : 0;
     CallPlan plan;
@@ -328,7 +328,7 @@ extern "C" int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_s
     if (num_steps <= 0 || first_index < 0 || first_index >= num_steps || run_steps < 1 || run_steps > num_steps - first_index)
         return fail(w + "bad step range");
     if (inpaint_mask && !inpaint_motion) return fail(w + "mask without motion");
-    if (check_ready(h, who)) return -1;
+    if (check_ready(h, who) || refuse_resampling(h, who)) return -1;
     if (h->B > 65535) return fail(w + "batch exceeds 65535");
     if (h->guide_every > 1)
         return fail(w + "the guidance refresh (gdx_set_guidance_refresh, every > 1) does not apply to the inversion: its numbering of "
@@ -371,6 +371,7 @@ extern "C" int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int
         return fail(w + "bad max_iterations / strides_out");
     if (inpaint_mask && !inpaint_motion) return fail(w + "mask without motion");
     if (!h) return fail(w + "null handle");
+    if (refuse_resampling(h, who)) return -1;
     if (h->guide_every > 1)
         return fail(w + "the guidance refresh (gdx_set_guidance_refresh, every > 1) needs memory across sequential denoiser calls; "
                         "the window's calls are not sequential: set every = 1");
@@ -432,6 +433,60 @@ extern "C" int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int
     return 0;
 }
 
+// gdx_sample_loop while resampling is on (gdx_set_resample, repeats > 1): the hops [k_base, k_base + run_steps) of the walk of
+// gdx_resample_plan.h over the WHOLE loop, levels first_index + 1 .. 0.  A reverse hop is the eager step of the plain loop --
+// denoise_guided on the pose-layout state, then gdx_sampler_update --, a forward hop one renoise_kernel launch; hop k of either kind
+// takes tape slice k - k_base or Philox draw k + 1.  The plan is the unnumbered one: every reverse hop takes the mode of its own
+// model timestep, and nothing is carried from one denoiser call to the next.  No token-major path, no graph capture.
+static int resample_loop(gdx_model* h, const gdx_loop_args_t* a, hipStream_t s) {
+    const std::string w = "gdx_sample_loop: resampling (gdx_set_resample, repeats > 1) ";
+    if (a->kind != GDX_SAMPLER_P && a->kind != GDX_SAMPLER_DDIM) return fail(w + "runs GDX_SAMPLER_P or GDX_SAMPLER_DDIM");
+    if (a->n_dump) return fail(w + "does not support dump_steps: an executed-step number names no single state of the walk");
+    if (a->const_noise) return fail(w + "does not support const_noise");
+    if (h->guide_every > 1)
+        return fail(w + "and the guidance refresh (gdx_set_guidance_refresh, every > 1) exclude each other: a forward hop invalidates "
+                        "the stored difference; set every = 1");
+    if (h->lc_every > 1)
+        return fail(w + "and the layer cache (gdx_set_layer_cache, every > 1) exclude each other: a forward hop invalidates the "
+                        "stored change; set every = 1");
+    if (a->num_steps != h->rp_steps)
+        return fail(w + "was set for a schedule of " + std::to_string(h->rp_steps) + " steps, the loop has " + std::to_string(a->num_steps));
+    if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_sample_loop: mask without motion");
+    const std::vector<Hop> hops = resample_walk(a->first_index + 1, h->rp_jump, h->rp_repeats);
+    const long n_hops = (long)hops.size();
+    if (a->k_base >= n_hops || (long)a->k_base + a->run_steps > n_hops) return fail("gdx_sample_loop: bad step range");
+    const long k_end = a->run_steps > 0 ? (long)a->k_base + a->run_steps : n_hops;
+    if (build_step_tables(h, a->num_steps, a->timestep_map, s)) return -1;
+    LateWorkspace& lw = h->late;
+    if (lw.rp_tab_rows < h->rp_steps) {                            // regrown, like the step tables
+        lw.rp_tab_rows = 0; lw.rp_tab_valid = false;
+        if (ws_alloc(h, (void**)&lw.rp_tab, sizeof(float) * 2 * (size_t)h->rp_steps, s)) return -1;
+        lw.rp_tab_rows = h->rp_steps;
+    }
+    if (!lw.rp_tab_valid) {
+        HIPCHK(hipMemcpyAsync(lw.rp_tab, h->rp_rows.data(), sizeof(float) * h->rp_rows.size(), hipMemcpyHostToDevice, s));
+        lw.rp_tab_valid = true;
+    }
+    const size_t per = (size_t)h->J * h->T;
+    PlanWalk walk{plan_rule(h), a->mode, a->timestep_map, false};
+    for (long k = a->k_base; k < k_end; ++k) {
+        const Hop& hop = hops[k];
+        const float* z = tape_slice(a->noise_tape, (int)k, a->k_base, h->B, per);
+        if (hop.forward) {
+            if (gdx_renoise_(a->x, lw.rp_tab, hop.from, h->B, (long)per, z, a->philox_seed, a->sample_offset, (uint32_t)(k + 1), (void*)s))
+                return -1;
+            continue;
+        }
+        const float *x0u, *sc;
+        if (denoise_guided(h, walk.visit(hop.to), a->scale, a->x, s, &x0u, &sc)) return -1;
+        gdx_update_args_t u = step_args<gdx_update_args_t>(h, a, hop.to, x0u, sc);
+        u.kind = a->kind; u.noise = z;
+        u.philox_seed = a->philox_seed; u.sample_offset = a->sample_offset; u.rng_step = (uint32_t)(k + 1);
+        if (gdx_sampler_update(&u, (void*)s)) return -1;
+    }
+    return 0;
+}
+
 extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream) {
     if (check_ready(h, "gdx_sample_loop")) return -1;
     if (!a || !a->coef || !a->timestep_map || !a->x) return fail("gdx_sample_loop: null argument");
@@ -440,6 +495,7 @@ extern "C" int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* s
         return fail("gdx_sample_loop: bad step range");
     if (a->kind == GDX_SAMPLER_DDIM && (a->const_noise || a->n_dump))
         return fail("gdx_sample_loop: ddim_sample_loop supports neither const_noise nor dump_steps");  // :903-906
+    if (h->rp_repeats > 1) return resample_loop(h, a, (hipStream_t)stream);
     hipStream_t s = (hipStream_t)stream;
     const int B = h->B;
     const int last_idx = a->run_steps > 0 && a->run_steps <= a->first_index ? a->first_index - a->run_steps + 1 : 0;

@@ -427,6 +427,36 @@ __global__ void randn_kernel(float* __restrict__ out, int batch, long per_sample
     store4<false>(out, g.e0, g.nval, philox_normal4(seed, sample_offset + (uint64_t)g.b, step, g.grp));
 }
 
+// The forward hop of a resampled loop (gdx.h gdx_set_resample; gdx_sample_loop) in ONE pass, in place: x <- a*x + b*z with (a, b)
+// row `row` of the handle's table and z this hop's tape slice or philox_normal4 keyed like update_kernel (sample_offset + b,
+// rng_step, group), through q_sample_value: the bits of gdx_randn followed by gdx_q_sample on a row holding (c[5], c[6]) = (a, b).
+// The whole tensor, an inpainted region included.  Memory-bound: per element one read and one write (+ one read under a tape).
+// Not fused into the update in front of it: one forward hop comes per `jump` denoiser calls.
+struct RenoiseDev {
+    float* x;
+    const float* tab;       // [rows][2]
+    int row, batch;
+    long per_sample, groups;
+    const float* noise;     // nullptr (Philox) or [B][per_sample]
+    uint64_t seed, sample_offset;
+    uint32_t rng_step;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void renoise_kernel(const RenoiseDev a) {
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= a.groups * a.batch) return;
+    const Group g = group_of<VEC>(gid, a.groups, a.per_sample);
+    const float ca = a.tab[2L * a.row], cb = a.tab[2L * a.row + 1];
+    const f32x4 x = load4<VEC>(a.x, g.e0, g.nval);
+    const f32x4 z = a.noise ? load4<VEC>(a.noise, g.e0, g.nval)
+                            : philox_normal4(a.seed, a.sample_offset + (uint64_t)g.b, a.rng_step, g.grp);
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = q_sample_value(ca, cb, x[i], z[i]);
+    store4<VEC>(a.x, g.e0, g.nval, r);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Parallel-in-time sampling (gdx.h gdx_window_sweep): the sequential update chain over a window of planes P_0 .. P_n with the
 // denoiser's predictions M_0 .. M_{n-1} held fixed, in ONE launch.  A thread owns one group of four elements and walks the slots
@@ -820,6 +850,21 @@ int gdx_window_slide_(float* planes, long plane, int W, int stride, void* stream
     if (vec) hipLaunchKernelGGL(window_slide_kernel<f32x4>, grid, block, 0, (hipStream_t)stream, (f32x4*)planes, count, W, stride);
     else hipLaunchKernelGGL(window_slide_kernel<float>, grid, block, 0, (hipStream_t)stream, planes, count, W, stride);
     return launch_status("gdx_parallel_loop: slide launch failed");
+}
+
+// internal (loops.hip, gdx_sample_loop under gdx_set_resample): one forward hop on the state x [batch][per_sample], in place
+int gdx_renoise_(float* x, const float* tab, int row, int batch, long per_sample, const float* noise, uint64_t seed,
+                 uint64_t sample_offset, uint32_t rng_step, void* stream) {
+    using namespace gdx;
+    RenoiseDev d;
+    d.x = x; d.tab = tab; d.row = row; d.batch = batch;
+    d.per_sample = per_sample; d.groups = (per_sample + 3) / 4;
+    d.noise = noise; d.seed = seed; d.sample_offset = sample_offset; d.rng_step = rng_step;
+    const long total = d.groups * batch;
+    if (total == 0) return 0;
+    launch_vec(vec_ok(per_sample, (const float*)x, noise), renoise_kernel<true>, renoise_kernel<false>, dim3((total + 255) / 256),
+               dim3(256), (hipStream_t)stream, d);
+    return launch_status("gdx_sample_loop: forward hop launch failed");
 }
 
 extern "C" int gdx_postprocess(const float* x, const double* mean, const double* stdv, float* pos, float* rot,

@@ -850,6 +850,152 @@ class GaussianDiffusion:
             report.update(iterations=len(strides), strides=strides, forward_samples=eng.forward_samples() - before)
         return planes[0].clone()
 
+    # ------------------------------------------------------------------ resampling (RePaint)
+    @staticmethod
+    def _resample_args(jump, repeats):
+        for name, v in (("jump", jump), ("repeats", repeats)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 2**31 - 1:
+                raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+        return int(jump), int(repeats)
+
+    def resample_plan(self, jump, repeats, skip_timesteps=0):
+        """The hops of a resampled loop in execution order: ("r", index) is the reverse step at this diffusion's index, ("f", l,
+        l + jump) a forward hop between levels, where level L is the input of the reverse step at index L - 1 and level 0 the
+        sample.  The loop starts at level N = num_timesteps - skip_timesteps; the jump levels are 0, jump, 2 jump, ... with
+        l + jump < N, each with repeats - 1 jumps left; on arriving at one with jumps left the walk uses one up, hops forward and
+        descends again.  Denoiser calls: N + n_levels * (repeats - 1) * jump.  The rule of gdx_set_resample
+        (csrc/gdx_resample_plan.h), on the host."""
+        jump, repeats = self._resample_args(jump, repeats)
+        n = self.num_timesteps - skip_timesteps
+        left = {l: repeats - 1 for l in range(0, max(n - jump, 0), jump)}
+        plan, level = [], n
+        while level > 0:
+            level -= 1
+            plan.append(("r", level))
+            if left.get(level, 0) > 0:
+                left[level] -= 1
+                plan.append(("f", level, level + jump))
+                level += jump
+        return plan
+
+    def resample_coef(self, plan):
+        """The fp32 rows (a, b) of the plan's forward hops, one per hop in execution order, [n_forward, 2]: a = sqrt(r), b =
+        sqrt(1 - r) with r = abar[to] / abar[from] and abar = [1, alphas_cumprod ...] by level, computed in float64 and rounded
+        once: x <- a x + b z is `to - from` steps of the forward process in one."""
+        abar = np.append(1.0, np.asarray(self.alphas_cumprod, dtype=np.float64))
+        r = np.array([abar[h[2]] / abar[h[1]] for h in plan if h[0] == "f"], dtype=np.float64)
+        return np.stack([np.sqrt(r), np.sqrt(1.0 - r)], axis=1).astype(np.float32).reshape(-1, 2)
+
+    def repaint_sample_loop(self, model, shape, noise=None, clip_denoised=True, model_kwargs=None, device=None, progress=False,
+                            skip_timesteps=0, init_image=None, *, sampler="p", eta=0.0, jump=10, repeats=10, rng="torch",
+                            philox_seed=0, sample_offset=0, noise_tape=None, fused=True):
+        """p_sample_loop (sampler="p") or ddim_sample_loop ("ddim", eta) with RePaint's resampling (Lugmayr et al. 2022,
+        arXiv:2201.09865, section 4.2): after the chain has come down `jump` steps it is diffused forward `jump` steps again and
+        comes down again, `repeats` times in all (resample_plan), so that the part generated beside y['inpainting_mask'] /
+        y['inpainted_motion'] catches up with the known part.  The known part itself is handled as in every loop here -- it
+        replaces the x0 prediction of each step --, not noised and pasted into the state as RePaint does.  Without a mask the
+        loop still runs, as a plain stochastic resampler of the unconstrained chain.
+        Executed hops of both kinds are numbered k = 0, 1, ...: hop k takes entry 1 + k of noise_tape (entry 0 is x_T, so a tape
+        holds 1 + len(resample_plan(...)) entries), Philox draw k + 1 (rng="philox"), or one draw from torch's generator in
+        execution order.  fused=True on a native START_X denoiser runs inside libgdx (gdx_sample_loop under gdx_set_resample) in
+        blocks of at most NOISE_BLOCK hops, the progress bar advancing per block; fused=False, and any other model, runs hop by
+        hop -- the model call and gdx_sampler_update, or the noise and gdx_q_sample -- with the same bits.  repeats = 1 is
+        p_sample_loop / ddim_sample_loop itself.
+        ValueError for jump / repeats that are not ints >= 1, another sampler, y['guidance_refresh'] > 1 or y['layer_cache'] with
+        every > 1 (a forward hop invalidates what they carry), a tape of another length than 1 + hops and a tape whose entries do
+        not have `shape` (no const_noise-style broadcast)."""
+        kinds = {"p": GDX_SAMPLER_P, "ddim": GDX_SAMPLER_DDIM}
+        if sampler not in kinds:
+            raise ValueError(f"repaint_sample_loop runs sampler 'p' or 'ddim', got {sampler!r}")
+        jump, repeats = self._resample_args(jump, repeats)
+        if rng not in ("torch", "philox"):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        if model_kwargs is None:
+            model_kwargs = {}
+        self._refuse_memory_under_resampling(model, model_kwargs)
+        plan =self.resample_plan(jump, repeats, skip_timesteps)
+        hops = len(plan)
+        if noise_tape is not None:
+            if len(noise_tape) != 1 + hops:
+                raise ValueError(f"noise_tape must hold x_T and one entry per hop, 1 + {hops}, got {len(noise_tape)}")
+            if tuple(noise_tape.shape[1:]) != tuple(shape):
+                raise ValueError(f"every noise_tape entry must have the sample's shape {tuple(shape)} (no const_noise-style "
+                                 f"broadcast), got {tuple(noise_tape.shape[1:])}")
+        kind = kinds[sampler]
+        if self.rescale_timesteps:
+            raise NotImplementedError("rescale_timesteps=True is not used by the reference's sampler configuration")
+        self._check_supported()
+        device, img, indices = self._prepare_loop(model, shape, noise, device, skip_timesteps, init_image, rng, philox_seed,
+                                                  sample_offset, noise_tape)
+        if self._runs_fused(fused, model, None, None):
+            return self._fused_repaint_loop(kind, model, img, indices, plan, model_kwargs, eta, jump, repeats, rng, philox_seed,
+                                            sample_offset, noise_tape, progress, clip_denoised)
+        rows = self.resample_coef(plan)
+        ftab = th.zeros(max(len(rows), 1), 8, dtype=th.float32)
+        ftab[:len(rows), 5:7] = th.from_numpy(rows)
+        ftab = ftab.to(device)
+        if progress:
+            from tqdm.auto import tqdm
+            plan = tqdm(plan)
+        n_forward = 0
+        for k, hop in enumerate(plan):
+            z = None
+            if noise_tape is not None:
+                z = noise_tape[1 + k]
+            elif rng == "philox":
+                z = E.randn(tuple(shape), device, philox_seed, sample_offset, k + 1)
+            if hop[0] == "r":
+                t = th.full((shape[0],), hop[1], device=device, dtype=th.long)
+                with th.no_grad():
+                    img = self._step(kind, model, img, t, clip_denoised, None, None, model_kwargs, eta=eta, noise=z)["sample"]
+            else:
+                if z is None:
+                    z = th.randn_like(img)
+                img = E.q_sample(E.f32c(img, "x"), E.f32c(z, "noise"), ftab, n_forward)
+                n_forward += 1
+        return img
+
+    @staticmethod
+    def _refuse_memory_under_resampling(model, model_kwargs):
+        """y['guidance_refresh'] > 1 and y['layer_cache'] with every > 1 (sampling_options.MEMORY) carry a result from one denoiser
+        call to the next; a forward hop in between invalidates it, so neither route of repaint_sample_loop serves them."""
+        from ..model.cfg_sampler import ClassifierFreeSampleModel
+        y = (model_kwargs or {}).get("y")
+        if not isinstance(y, dict):
+            return
+        guided = isinstance(model, ClassifierFreeSampleModel)
+        inner = getattr(model, "model", model) if guided else model
+        values = sampling_options.read(y, guided=guided, num_layers=getattr(inner, "num_layers", 2**31), use_text=False,
+                                       options=sampling_options.MEMORY).values
+        for o in sampling_options.MEMORY:
+            if o.name in values and o.memory[0](values[o.name]) > 1:
+                raise ValueError(f"y['{o.keys[0]}'] = {values[o.name]} does not combine with repaint_sample_loop: a forward hop "
+                                 f"invalidates {o.memory[1]}")
+
+    def _fused_repaint_loop(self, kind, model, img, indices, plan, model_kwargs, eta, jump, repeats, rng, philox_seed,
+                            sample_offset, noise_tape, progress, clip_denoised):
+        """The resampled loop inside libgdx: gdx_sample_loop under gdx_set_resample, issued in blocks of at most NOISE_BLOCK hops
+        (_issue_blocks; k_base / run_steps count hops, first_index is the whole loop's); the setter is switched off again whatever
+        happens.  repeats = 1: the plain fused loop."""
+        if repeats == 1:
+            return next(self._fused_loop(kind, model, img, indices, model_kwargs, eta, False, rng, philox_seed, sample_offset,
+                                         noise_tape, None, progress, clip_denoised))["sample"]
+        x = E.f32c(img, "x_T").clone()
+        eng, mode, scale, mask, motion = self._native_loop_setup(model, x, model_kwargs)
+        hops = len(plan)
+        tape = E.f32c(noise_tape[1:1 + hops], "noise_tape") if noise_tape is not None else None
+        block, tape_of = self._step_noise(tape, rng, hops, x)
+        coef, tmap = self.coef_table(kind, x.device, eta), self._timestep_map()
+        eng.set_resample(jump, repeats, self.alphas_cumprod)
+        try:
+            self._issue_blocks(hops, x.device, progress, lambda k, nb: eng.sample_loop(
+                x, kind, mode, coef, tmap, indices[0], scale=scale, inpaint_mask=mask, inpaint_motion=motion,
+                noise_tape=tape_of(k, nb), philox_seed=philox_seed, sample_offset=sample_offset, run_steps=nb, k_base=k,
+                clip_denoised=clip_denoised), min(hops, NOISE_BLOCK, block or hops))
+        finally:
+            eng.set_resample(1, 1)
+        return x
+
     # ------------------------------------------------------------------ explicitly out of scope
     def masked_l2(self, a, b, mask):
         """reference :201-213; a, b [B,J,1,T], mask bool [B,1,1,T] -> [B]."""

@@ -209,6 +209,14 @@ class Engine:
         then not looked at.  Clears the stored change."""
         _lib.check(self.lib.gdx_set_layer_cache(self.handle, int(every), int(keep)), self.lib)
 
+    def set_resample(self, jump=1, repeats=1, alpha_bar=None):
+        """repeats > 1: sample_loop executes the resampling walk (gdx_set_resample; the rule is in include/gdx.h) with forward hops
+        of `jump` levels built from alpha_bar, the float64 alphas_cumprod of the loop's own schedule; 1 = off, alpha_bar is then
+        not looked at.  The other loops refuse while it is on."""
+        ab = np.ascontiguousarray(np.asarray(alpha_bar, dtype=np.float64)) if repeats > 1 and alpha_bar is not None else None
+        _lib.check(self.lib.gdx_set_resample(self.handle, int(jump), int(repeats), ab.ctypes.data if ab is not None else None,
+                                             len(ab) if ab is not None else 0), self.lib)
+
     @staticmethod
     def layer_delta(op, inp, outc, delta):
         """The stand-alone gdx_layer_delta (the module's layer_delta)."""

@@ -18,6 +18,9 @@ its statistics, and `results.npy` / `results.txt` / `results_len.txt` are writte
 run's seed, a data directory needs `--text_features FILE.npz` (`--list_texts OUT.txt` writes the strings to encode and exits).
 `--invert_gt` (data directory and `--sampler ddim` only) starts every chunk's DDIM loop from the DDIM inversion of that chunk's
 ground truth instead of a drawn x_T (`sample_chunks`, `invert_of_chunk`).
+`--edit_mode in_between [--prefix_end 0.25 --suffix_start 0.75]` keeps every chunk's ground-truth frames outside the gap and
+generates the gap (the reference's `sample/edit.py:76-83`); `--resample JUMP REPEATS` (`--sampler p` / `ddim`) adds RePaint's
+resampling (`repaint_sample_loop`), with or without `--edit_mode`, and prints the hop and denoiser-call counts per chunk.
 `--parallel_window W --parallel_tolerance TAU` (`--sampler p` / `ddim`) runs every chunk's loop parallel in time
 (`parallel_sample_loop`) and prints each chunk's iteration count.
 
@@ -58,7 +61,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
                   sampler="p", eta=0.0, rng="torch", philox_seed=0, sample_offset=0, noise_tapes=None, progress=False,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
                   guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None, text_of_chunk=None,
-                  layer_cache=None, parallel=None, text_guidance_param=None, guidance_order=None, guidance_drop=None):
+                  layer_cache=None, parallel=None, text_guidance_param=None, guidance_order=None, guidance_drop=None,
+                  inpaint_of_chunk=None, resample=None):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -81,7 +85,15 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     noise or a tape; neither guidance_refresh > 1, layer_cache nor invert_of_chunk) and report(text) is told each chunk's iterations.
     Per-condition guidance of a use_text model (needs guidance_param != 1; the loops validate the rest): guidance_drop "both" |
     "text" | "seed" names what the contrast pass drops (y['guidance_drop']); text_guidance_param S runs three passes with the text
-    stage at S and the seed stage at guidance_param (y['text_scale']), guidance_order saying which comes first (y['guidance_order'])."""
+    stage at S and the seed stage at guidance_param (y['text_scale']), guidance_order saying which comes first (y['guidance_order']).
+    inpaint_of_chunk(c) -> (mask bool, motion) [b, J, 1, frames] on the device: chunk c's y['inpainting_mask'] / y['inpainted_motion'];
+    the seed hand-off is unchanged.  resample (jump, repeats): every chunk's loop resamples (repaint_sample_loop; samplers "p" and
+    "ddim"; neither guidance_refresh > 1, layer_cache, parallel nor invert_of_chunk); a recorded tape then holds one entry per hop."""
+    if resample is not None:
+        if sampler not in ("p", "ddim"):
+            raise ValueError("resample needs sampler='p' or 'ddim': a multistep sampler's history does not survive a jump")
+        if guidance_refresh != 1 or layer_cache is not None or parallel is not None or invert_of_chunk is not None:
+            raise ValueError("resample runs neither guidance_refresh > 1, layer_cache, parallel nor invert_of_chunk")
     if guidance_param == 1 and (text_guidance_param is not None or guidance_order is not None or guidance_drop is not None):
         raise ValueError("text_guidance_param / guidance_order / guidance_drop need guidance_param != 1: without guidance there is "
                          "nothing to compose")
@@ -122,6 +134,8 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
         if guidance_param != 1:
             y["scale"] = torch.ones(b, device=first_seed.device) * guidance_param
         y.update(y_of_kwargs(options, b, first_seed.device))
+        if inpaint_of_chunk is not None:
+            y["inpainting_mask"], y["inpainted_motion"] = inpaint_of_chunk(chunk)
         kw = dict(clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=0, init_image=None, progress=progress,
                   noise=None, rng=rng, philox_seed=philox_seed + 1000 * chunk, sample_offset=sample_offset,
                   noise_tape=noise_tapes[chunk] if noise_tapes is not None else None)
@@ -152,6 +166,13 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
                 noise_tape=kw["noise_tape"], report=stats)
             if report is not None:
                 report(f"### chunk {chunk + 1}: parallel: {stats['iterations']} iterations for {sum(stats['strides'])} steps")
+            outs.append(sample_out)
+            continue
+        if resample is not None:
+            sample_out = diffusion.repaint_sample_loop(
+                model, (b, J, 1, frames), clip_denoised=False, model_kwargs={"y": y}, progress=progress, sampler=sampler, eta=eta,
+                jump=resample[0], repeats=resample[1], rng=rng, philox_seed=kw["philox_seed"], sample_offset=sample_offset,
+                noise_tape=kw["noise_tape"])
             outs.append(sample_out)
             continue
         sample_out = sample_fn(model, (b, J, 1, frames), **kw)
@@ -220,6 +241,27 @@ def synthetic_text_features(seed, num_samples, clip_dim, n_chunks):
     their own keyed by the run's seed (the seed-pose and MFCC draws of a run do not depend on --use_text)."""
     g = torch.Generator().manual_seed(int(seed) * 1000003 + 512)
     return [torch.randn(num_samples, clip_dim, generator=g) for _ in range(n_chunks)]
+
+
+def edit_mask(edit_mode, prefix_end, suffix_start, shape, device):
+    """--edit_mode: the y['inpainting_mask'] of a chunk of `shape` [b, J, 1, T], True where the ground truth is kept (reference
+    sample/edit.py:76-83 at full length): in_between keeps the frames outside [int(prefix_end * T), int(suffix_start * T))."""
+    if edit_mode == "upper_body":
+        raise NotImplementedError("--edit_mode upper_body: the reference's mask is HumanML's joint table (HML_LOWER_BODY_MASK), "
+                                  "which says nothing about a GENEA skeleton")
+    if edit_mode != "in_between":
+        raise ValueError(f"edit_mode must be 'in_between' or 'upper_body', got {edit_mode!r}")
+    T = shape[-1]
+    mask = torch.ones(shape, dtype=torch.bool, device=device)
+    mask[..., int(prefix_end * T):int(suffix_start * T)] = False
+    return mask
+
+
+def synthetic_ground_truth(seed, num_samples, njoints, frames, n_chunks):
+    """--edit_mode --synthetic: N(0,1) stand-ins for the recorded chunks, one [num_samples, njoints, 1, frames] per chunk, from a
+    generator of their own keyed by the run's seed (the seed-pose and MFCC draws of a run do not depend on --edit_mode)."""
+    g = torch.Generator().manual_seed(int(seed) * 1000003 + 1024)
+    return [torch.randn(num_samples, njoints, 1, frames, generator=g) for _ in range(n_chunks)]
 
 
 def host_item(ds, idx):
@@ -336,6 +378,23 @@ def main(argv=None):
         def invert_of_chunk(chunk):        # this rank's ground-truth chunks, normalised, as the sampler's [b, J, 1, T]
             return gg_collate([host_item(ds, i) for i in index[chunk][lo:hi]])[0].float().to(device)
 
+    inpaint_of_chunk = None
+    if args.edit_mode is not None:
+        mask = edit_mask(args.edit_mode, args.prefix_end, args.suffix_start, (hi - lo, J, 1, T), device)
+        synthetic_gt = synthetic_ground_truth(args.seed, num_samples, J, T, args.chunks) if ds is None else None
+
+        def inpaint_of_chunk(chunk):       # this rank's ground-truth chunks, normalised, and the frames that are kept of them
+            if ds is None:
+                return mask, synthetic_gt[chunk][lo:hi].to(device)
+            return mask, gg_collate([host_item(ds, i) for i in index[chunk][lo:hi]])[0].float().to(device)
+        if rank == 0:
+            print(f"### in-betweening: frames {int(args.prefix_end * T)}..{int(args.suffix_start * T) - 1} of {T} are generated, the "
+                  f"rest is kept")
+    if args.resample is not None and rank == 0:
+        plan = diffusion.resample_plan(*args.resample)
+        print(f"### resampling (jump {args.resample[0]}, repeats {args.resample[1]}): {len(plan)} hops, "
+              f"{sum(h[0] == 'r' for h in plan)} denoiser calls per chunk")
+
     def report(text):
         print(text if world == 1 else f"{text} (rank {rank})")
 
@@ -367,7 +426,8 @@ def main(argv=None):
                          guidance_refresh=args.guidance_refresh, invert_of_chunk=invert_of_chunk, report=report,
                          text_of_chunk=text_of_chunk, layer_cache=args.layer_cache, text_guidance_param=args.text_guidance_param,
                          guidance_order=args.guidance_order, guidance_drop=args.guidance_drop,
-                         parallel=(args.parallel_window, args.parallel_tolerance) if args.parallel_window else None)
+                         parallel=(args.parallel_window, args.parallel_tolerance) if args.parallel_window else None,
+                         inpaint_of_chunk=inpaint_of_chunk, resample=args.resample)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

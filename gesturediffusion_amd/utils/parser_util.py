@@ -108,6 +108,23 @@ def parse_and_load_from_model(parser, argv=None):
         if args.rng == "torch":
             parser.error("--parallel_window draws its noise from the counter-based generator: use --rng philox (its default)")
         args.rng = "philox"
+    if not 0 <= args.prefix_end <= args.suffix_start <= 1:
+        parser.error("--prefix_end and --suffix_start must satisfy 0 <= prefix_end <= suffix_start <= 1")
+    if args.resample is not None:
+        jump, repeats = args.resample
+        if jump < 1 or repeats < 1:
+            parser.error("--resample JUMP REPEATS must both be at least 1")
+        if args.sampler not in ("p", "ddim"):
+            parser.error("--resample runs --sampler p or ddim only: a multistep sampler's history does not survive a jump")
+        if args.guidance_refresh > 1:
+            parser.error("--resample runs no guidance refresh: a forward hop invalidates the stored difference")
+        if args.layer_cache is not None:
+            parser.error("--resample runs no layer cache: a forward hop invalidates the stored change")
+        if args.parallel_window:
+            parser.error("--resample does not combine with --parallel_window")
+        if args.invert_gt:
+            parser.error("--resample does not combine with --invert_gt: the resampled chain is stochastic")
+        args.resample = (jump, repeats)
     if args.list_texts and args.synthetic:
         parser.error("--list_texts lists the texts of a data directory: --synthetic has none")
     if args.use_text and args.arch_version == "mdm" and not (args.synthetic or args.text_features or args.list_texts):
@@ -252,6 +269,18 @@ def add_native_options(parser):
                             "denoiser call and advance past every state that has stopped changing (0 = off, at most 64). "
                             "--sampler p and ddim only; an error with --guidance_refresh > 1, --layer_cache and --invert_gt. "
                             "Implies --rng philox.")
+    group.add_argument("--edit_mode", default=None, choices=['in_between', 'upper_body'], type=str,
+                       help="Inpainting, with the reference's sample/edit.py flag names: in_between keeps each chunk's ground-truth "
+                            "frames outside [prefix_end * T, suffix_start * T) and generates the gap (y['inpainting_mask'] / "
+                            "y['inpainted_motion']); the ground truth is the data directory's, or under --synthetic drawn from the "
+                            "run's seed. upper_body is not implemented (the reference's mask is HumanML's joint table).")
+    group.add_argument("--prefix_end", default=0.25, type=float, help="--edit_mode in_between: end of the known prefix, a fraction of the chunk.")
+    group.add_argument("--suffix_start", default=0.75, type=float, help="--edit_mode in_between: start of the known suffix, a fraction of the chunk.")
+    group.add_argument("--resample", default=None, type=int, nargs=2, metavar=("JUMP", "REPEATS"),
+                       help="RePaint resampling (Lugmayr et al. 2022): after every JUMP steps down, diffuse JUMP steps forward again "
+                            "and come down again, REPEATS times in all, so that the generated frames catch up with the known ones "
+                            "(REPEATS = 1: off). --sampler p and ddim only; allowed without --edit_mode; an error with "
+                            "--guidance_refresh > 1, --layer_cache, --parallel_window and --invert_gt.")
     group.add_argument("--parallel_tolerance", default=0.1, type=float, metavar="TAU",
                        help="--parallel_window: a state counts as converged when its mean squared change is at most TAU^2 times "
                             "the step's posterior variance; 0 reproduces the sequential loop bit for bit in fp32.")

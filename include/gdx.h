@@ -708,6 +708,40 @@ typedef struct {
 } gdx_loop_args_t;
 int gdx_sample_loop(gdx_handle_t h, const gdx_loop_args_t* a, void* stream);
 
+/* Resampling (RePaint, Lugmayr et al. 2022, arXiv:2201.09865, section 4.2; no counterpart in the reference): after the chain has
+ * come down `jump` steps it is diffused forward `jump` steps again and comes down again, `repeats` times in all, so that the
+ * generated part of an inpainted sample catches up with the known part.  repeats = 1 (the state after gdx_create) is the
+ * behaviour without the feature: nothing new is launched and every result keeps its bits; alpha_bar may then be NULL.  One
+ * rule everywhere (csrc/gdx_resample_plan.h; GaussianDiffusion.resample_plan / resample_coef restate it):
+ *   Levels.  Level L is the input of the reverse step at schedule index L - 1, level 0 is the sample; a loop starts at level
+ *     N = first_index + 1.
+ *   Jump levels.  l in {0, jump, 2 jump, ...} with l + jump < N (RePaint's range(0, t_T - jump, jump), level 0 included); each has
+ *     repeats - 1 jumps left.
+ *   Walk.  A reverse hop takes level l + 1 -> l.  On arriving at a jump level with jumps left: use one up, take a forward hop
+ *     l -> l + jump, go on descending.  N = 6, jump = 2, repeats = 2: r5 r4 r3 r2 f(2->4) r3 r2 r1 r0 f(0->2) r1 r0.
+ *     Denoiser calls = N + n_levels * (repeats - 1) * jump; hops = calls + n_levels * (repeats - 1).
+ *   Forward hop from -> to.  x <- a x + b z with a = sqrt(r), b = sqrt(1 - r), r = abar[to] / abar[from], abar = [1, alpha_bar ...] by
+ *     level; a and b are computed in fp64 and rounded to fp32 once; product and sum are rounded separately; the whole tensor,
+ *     an inpainted region included.  One hop of `jump` levels in place of RePaint's `jump` single steps: the same distribution,
+ *     one launch, one draw.  Its bits are those of gdx_randn followed by gdx_q_sample on a row with (c[5], c[6]) = (a, b).
+ *   Draws.  Executed hops of both kinds are numbered k = 0, 1, ... in one sequence: hop k takes Philox draw k + 1 (x_T is draw
+ *     0), or slice k of a noise tape.
+ * gdx_set_resample builds the (a, b) row of every forward hop from alpha_bar (HOST, [num_steps], the loop's own -- respaced --
+ * schedule: in (0, 1], not increasing); the library owns the device table and uploads it on the stream of the next loop.
+ * With repeats > 1, gdx_sample_loop (GDX_SAMPLER_P and GDX_SAMPLER_DDIM) executes the walk: a reverse hop is the denoiser call and
+ * the gdx_sampler_update of the plain loop, unchanged; a forward hop is one launch.  first_index is then the WHOLE loop's first
+ * index in every block, k_base / run_steps count executed hops of both kinds, and noise_tape starts at the block's first hop,
+ * one [B,J,1,T] slice per hop.  The loop takes the pose-layout eager path: there is no token-major variant and no graph
+ * capture.  Every reverse hop takes the mode of its own model timestep, so the guidance interval, the rescale and the 3-pass
+ * compose apply as they are.  Refused, before the first launch: dump_steps, const_noise, gdx_set_guidance_refresh and
+ * gdx_set_layer_cache with every > 1 (a forward hop invalidates what they carry), and a num_steps other than the setter's.
+ * gdx_plms_loop, gdx_dpm_loop, gdx_dpm_sde_loop, gdx_unipc_loop, gdx_ddim_reverse_loop, gdx_parallel_loop and gdx_bpd_loop refuse
+ * while repeats > 1: their history does not survive a jump.  Nothing is claimed about motion quality on a trained checkpoint
+ * (DESIGN.md 4p holds the analytic case).
+ * gdx_set_resample makes no HIP call; a null handle, jump < 1, repeats < 1 and, with repeats > 1, a NULL or ill-formed alpha_bar
+ * are refused. */
+int gdx_set_resample(gdx_handle_t h, int32_t jump, int32_t repeats, const double* alpha_bar, int32_t num_steps);
+
 /* ---- variational bound (evaluation) ----------------------------------------------------- */
 /* One term of the variational bound in bits/dim plus the two per-step error curves, fused over [B,J,1,T]: replaces
  * _vb_terms_bpd (gaussian_diffusion.py:1192-1225) with its helpers normal_kl / discretized_gaussian_log_likelihood
