@@ -28,6 +28,8 @@
 // loader's idx -> (row, column) map divides by the constant HD/4.  Registers: 96 fits two workgroups per CU (48 Q + 48 O + 2 x 16
 // scores + 24 in-flight tile registers: 186 allocated); 192 needs 96 + 96 + 32 + 48 and runs one workgroup per CU, like 256
 // (256 VGPRs + 244 accumulation registers with its two score chains, no scratch).
+#include <algorithm>
+
 #include "gdx_internal.h"
 #include "gdx_device.h"
 
@@ -227,4 +229,43 @@ hipError_t launch_attention(const float* qkv, float* ctx, int B, int S, int H, i
     }
 }
 
+// Identity attention (perturbed-attention guidance, gdx.h gdx_set_attention_guidance): with the attention map replaced by the
+// identity every token attends to itself alone, so ctx[r][:] is the V third of qkv[r][:].  A bit copy in 16-byte units, one
+// instance per element size EB (fp16 and bf16 share the 2-byte one: a copy needs no half-typed build); a row of d elements is
+// d * EB / 16 whole units for every supported d.  Grid-stride over the rows * d * EB / 16 units of ctx: nothing else is written.
+// Traffic: rows * d * EB bytes read and as many written.
+template <int EB>
+__global__ __launch_bounds__(256) void attn_identity_kernel(const uint4* __restrict__ qkv, uint4* __restrict__ ctx, long units, int d) {
+    const int row_units = d * EB / 16;
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < units; i += stride) {
+        const long r = i / row_units;
+        const int c = (int)(i - r * row_units);
+        ctx[i] = qkv[(3 * r + 2) * row_units + c];
+    }
+}
+
+hipError_t launch_attention_identity(int elem_bytes, const void* qkv, void* ctx, long rows, int d, hipStream_t s) {
+    if ((elem_bytes != 2 && elem_bytes != 4) || rows <= 0 || d <= 0 || (d * elem_bytes) % 16) return hipErrorInvalidValue;
+    const long units = rows * (d * elem_bytes / 16);
+    // memory-bound: at most 2048 blocks, the rest grid-strided
+    const dim3 grid((unsigned)std::min(2048L, (units + 255) / 256)), block(256);
+    if (elem_bytes == 4) hipLaunchKernelGGL(attn_identity_kernel<4>, grid, block, 0, s, (const uint4*)qkv, (uint4*)ctx, units, d);
+    else hipLaunchKernelGGL(attn_identity_kernel<2>, grid, block, 0, s, (const uint4*)qkv, (uint4*)ctx, units, d);
+    return hipGetLastError();
+}
+
 }  // namespace gdx
+
+// The stand-alone identity-attention pass (gdx.h), synchronous with the device; every refusal precedes the first HIP call
+extern "C" int gdx_attention_identity(int32_t elem_bytes, int64_t rows, int32_t d, const void* qkv, void* ctx) {
+    if (elem_bytes != 2 && elem_bytes != 4) return gdx_set_error_("gdx_attention_identity: elem_bytes must be 2 (fp16 / bf16) or 4 (fp32)");
+    if (!qkv || !ctx) return gdx_set_error_("gdx_attention_identity: null argument");
+    if (rows <= 0 || d <= 0) return gdx_set_error_("gdx_attention_identity: rows and d must be positive");
+    if (((int64_t)d * elem_bytes) % 16) return gdx_set_error_("gdx_attention_identity: a row of d elements must be a multiple of 16 bytes (there is only a 128-bit path)");
+    if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return gdx_set_error_("gdx_attention_identity: every pointer must be 16-byte aligned");
+    if (hipDeviceSynchronize() != hipSuccess || gdx::launch_attention_identity(elem_bytes, qkv, ctx, (long)rows, d, nullptr) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess)
+        return gdx_set_error_("gdx_attention_identity: launch failed");
+    return 0;
+}

@@ -74,14 +74,27 @@ static int linear(gdx_model* h, const Act& in, const Packed& W, const Terms& t, 
     return 0;
 }
 
-// Self-attention of Beff samples: qkv -> ctx
-static int attend(gdx_model* h, int Beff, hipStream_t s) {
+// Self-attention of samples b0 .. b0 + nb - 1 of the batch: qkv -> ctx on their rows.  Every attention kernel takes
+// qkv [rows][3d] -> ctx [rows][d], so a sub-batch is a launch on offset pointers; the rows readable behind it shrink with the offset
+static int attend(gdx_model* h, int b0, int nb, hipStream_t s) {
+    const size_t r0 = (size_t)b0 * h->S, d = h->d;
     if (h->f16)
-        HIPCHK(HFN(h->bf16, launch_attentionh, h->qkv.h, h->ctx.h, Beff, h->S, h->H, h->d, h->rows_alloc, s));
+        HIPCHK(HFN(h->bf16, launch_attentionh, h->qkv.h + r0 * 3 * d, h->ctx.h + r0 * d, nb, h->S, h->H, h->d, h->rows_alloc - (long)r0, s));
     else if (attention3_supported(h->S, h->H, h->d))
-        HIPCHK(launch_attention3(h->qkv.f, h->ctx.f, Beff, h->S, h->H, h->d, s));
+        HIPCHK(launch_attention3(h->qkv.f + r0 * 3 * d, h->ctx.f + r0 * d, nb, h->S, h->H, h->d, s));
     else                                              // other head dims / more than 256 tokens: the general 32 x 32-block kernel
-        HIPCHK(launch_attention(h->qkv.f, h->ctx.f, Beff, h->S, h->H, h->d, s));
+        HIPCHK(launch_attention(h->qkv.f + r0 * 3 * d, h->ctx.f + r0 * d, nb, h->S, h->H, h->d, s));
+    return 0;
+}
+
+// Self-attention of a guided call's layer under perturbed-attention guidance (gdx.h gdx_set_attention_guidance), groups (F, P) or
+// (F, P, U) of B samples: attention on the contiguous runs of unperturbed groups, the identity (ctx = V, a copy) on the rows of P
+static int attend_perturbed(gdx_model* h, int Beff, hipStream_t s) {
+    const int B = h->B;
+    const size_t r0 = (size_t)B * h->S, d = h->d;
+    if (attend(h, 0, B, s) || (Beff > 2 * B && attend(h, 2 * B, Beff - 2 * B, s))) return -1;
+    if (h->f16) HIPCHK(launch_attention_identity(2, h->qkv.h + r0 * 3 * d, h->ctx.h + r0 * d, (long)r0, h->d, s));
+    else HIPCHK(launch_attention_identity(4, h->qkv.f + r0 * 3 * d, h->ctx.f + r0 * d, (long)r0, h->d, s));
     return 0;
 }
 
@@ -135,6 +148,7 @@ int gdx::forward_core(gdx_model* h, const float* x, const float* temb, int tstri
     const int B = h->B, T = h->T, S = h->S, d = h->d, J = h->J;
     const int Beff = mode == GDX_CFG ? h->groups() * B : B;      // guided: row groups F, U -- or F, M, U (gdx_set_guidance_compose)
     const int layers = lc == LC_PARTIAL ? h->lc_keep : h->L;     // encoder layers this call launches
+    const uint64_t perturbed = mode == GDX_CFG && h->pag() ? h->pag_mask : 0;   // layers whose group P gets identity attention
     h->forward_samples += Beff;                                   // gdx_forward_samples (host side only)
     h->forward_layer_samples += (int64_t)Beff * layers;           // gdx_forward_layer_samples
     // layer cache: the residual stream is fp32 in the fp32 mode and under stream32, else the 16-bit type; the operand of the
@@ -183,7 +197,8 @@ int gdx::forward_core(gdx_model* h, const float* x, const float* temb, int tstri
     if (tap(0)) return -1;
     for (int l = 0; l < layers; ++l) {
         const Layer& ly = h->layers[l];
-        if (linear(h, h->xa, ly.qkv, {.bias = ly.qkv.bias}, h->qkv, 3 * d, N, 3 * d, s) || attend(h, Beff, s)) return -1;
+        if (linear(h, h->xa, ly.qkv, {.bias = ly.qkv.bias}, h->qkv, 3 * d, N, 3 * d, s)) return -1;
+        if (perturbed >> l & 1 ? attend_perturbed(h, Beff, s) : attend(h, 0, Beff, s)) return -1;
         if (add_norm(h, h->ctx, ly.out, h->xa, ly.g1, ly.b1, &h->xb, nullptr, N, s)) return -1;        // x = LN1(x + out_proj(ctx))
         const bool stamp = h->prof && h->prof_used + 2 <= h->prof_ev.size();
         if (stamp) HIPCHK(hipEventRecord(h->prof_ev[h->prof_used], s));
@@ -254,7 +269,8 @@ int gdx::compose_x0(gdx_model* h, const float* scale, const int64_t* t, float* o
     const size_t n = (size_t)h->B * per;
     float *F = h->x0, *M = F + n, *U = M + n;
     const bool rescale = h->guide_phi > 0.0f;
-    HIPCHK(launch_cfg_compose(F, M, U, scale, scale + h->B, t, h->guide_lo, h->guide_hi, rescale ? M : out, h->B, per, s));
+    HIPCHK(launch_cfg_compose(F, M, U, scale, scale + h->B, t, h->guide_lo, h->guide_hi, rescale ? M : out, h->B, per, s,
+                              h->pag() ? COMPOSE_PAG : COMPOSE_CHAIN));
     return rescale ? rescale_x0(h, F, nullptr, nullptr, t, out, s, M) : 0;
 }
 
@@ -273,7 +289,7 @@ extern "C" int gdx_forward(gdx_handle_t h, const float* x, const int64_t* timest
                            float* out, void* stream) {
     if (check_ready(h, "gdx_forward")) return -1;
     if (!x || !timesteps || !out) return fail("gdx_forward: null argument");
-    if (check_mode("gdx_forward", mode, scale)) return -1;
+    if (check_mode("gdx_forward", mode, scale) || pag_conflict(h, "gdx_forward", mode)) return -1;
     const bool three = mode == GDX_CFG && h->three_pass();
     if (three && h->B > 65535) return fail("gdx_forward: batch exceeds 65535 (3-pass guidance)");
     hipStream_t s = (hipStream_t)stream;

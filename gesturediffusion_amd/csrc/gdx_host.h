@@ -134,6 +134,18 @@ struct LateWorkspace {
     bool rp_tab_valid = false;        // ... holds the rows of the most recent gdx_set_resample
 };
 
+// What a guided call runs, by (compose mode, PAG kind): its row groups, whether it composes three passes, and the group that
+// holds the all-dropped rows U.  The one table behind gdx_model::groups / three_pass / u_group.
+struct GuideLayout { int groups; bool three; int u_group; };
+constexpr GuideLayout GUIDE_LAYOUT[5][3] = {
+    //  GDX_PAG_OFF      GDX_PAG_ONLY     GDX_PAG_CFG
+    {{2, false, 1}, {2, false, 2}, {3, true, 2}},    // GDX_GUIDE_JOINT      (F, U)   | (F, P) + U | (F, P, U)
+    {{2, false, 2}, {2, false, 2}, {2, false, 2}},   // GDX_GUIDE_TEXT       (F, S) + U
+    {{2, false, 2}, {2, false, 2}, {2, false, 2}},   // GDX_GUIDE_SEED       (F, X) + U
+    {{3, true, 2}, {3, true, 2}, {3, true, 2}},      // GDX_GUIDE_SEED_TEXT  (F, S, U)
+    {{3, true, 2}, {3, true, 2}, {3, true, 2}},      // GDX_GUIDE_TEXT_SEED  (F, X, U)
+};
+
 }  // namespace gdx
 
 struct gdx_model {
@@ -179,9 +191,15 @@ struct gdx_model {
     float* c2_seed = nullptr;         // V2: W_coa * seed_cat rows [3B, d]
     // guidance compose: the passes of a guided call are row groups F, then M (a 3-pass mode's middle pass, or the contrast of modes
     // 1 and 2), then U; JOINT has no M and keeps U in group 1
-    bool three_pass() const { return guide_compose >= GDX_GUIDE_SEED_TEXT; }
-    int groups() const { return three_pass() ? 3 : 2; }
-    int u_group() const { return guide_compose == GDX_GUIDE_JOINT ? 1 : 2; }   // where GDX_UNCOND finds the all-dropped rows
+    // perturbed-attention guidance (gdx_set_attention_guidance) takes the place of M under JOINT: (F, P) with U kept in group 2 for
+    // GDX_UNCOND, or (F, P, U); under another compose mode a guided call is refused (pag_conflict), and the mode's own layout stands
+    int pag_kind = GDX_PAG_OFF;       // gdx_set_attention_guidance
+    uint64_t pag_mask = 0;            // ... bit l: encoder layer l gives the rows of group P identity attention
+    bool pag() const { return pag_kind != GDX_PAG_OFF && guide_compose == GDX_GUIDE_JOINT; }
+    const gdx::GuideLayout& layout() const { return gdx::GUIDE_LAYOUT[guide_compose][pag_kind]; }
+    bool three_pass() const { return layout().three; }
+    int groups() const { return layout().groups; }
+    int u_group() const { return layout().u_group; }   // where GDX_UNCOND finds the all-dropped rows
     // graph replay of launch-bound loops (gdx_sample_loop)
     bool graph_replay = false;        // gdx_set_graph_replay
     int* gstate = nullptr;            // device {schedule index, executed-step number}
@@ -213,6 +231,8 @@ template <class T> int ws_need(gdx_model* h, T** p, size_t bytes, hipStream_t s)
 }
 int check_ready(gdx_model* h, const char* who);                   // handle, gdx_prepare and a conditioning, or the refusal
 int check_mode(const char* who, int mode, const float* scale);
+// the refusal of a guided call of `who` under perturbed-attention guidance on a handle whose compose mode is not GDX_GUIDE_JOINT
+int pag_conflict(const gdx_model* h, const char* who, int mode);
 // the refusal of a loop `who` whose history does not survive a forward hop, while resampling is on (gdx_set_resample)
 int refuse_resampling(const gdx_model* h, const char* who);
 

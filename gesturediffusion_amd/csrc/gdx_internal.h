@@ -103,6 +103,9 @@ hipError_t launch_attention(const float* qkv, float* ctx, int B, int S, int H, i
 // the encoder head widths with a self-attention kernel in every compute mode (attention.hip, attentionh.hip)
 inline bool head_dim_supported(int hd) { return hd == 32 || hd == 64 || hd == 96 || hd == 128 || hd == 192 || hd == 256; }
 #define GDX_HEAD_DIMS "32, 64, 96, 128, 192 or 256"
+// identity attention (perturbed-attention guidance): ctx [rows][d] = the V third of qkv [rows][3d], a bit copy of elem_bytes (2 or
+// 4) wide elements in 16-byte units; d * elem_bytes % 16 == 0 and both pointers 16-byte aligned
+hipError_t launch_attention_identity(int elem_bytes, const void* qkv, void* ctx, long rows, int d, hipStream_t s);
 
 // eight-wave single-pass variant with the last query block shared out over four waves (attention3.hip); needs 64
 // readable rows past the last sample
@@ -207,9 +210,11 @@ hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, 
                             float* out, int B, int64_t per_sample, hipStream_t s);
 
 // out = g1 + s1[b]*(f - m) with g1 = u + s0[b]*(m - u) where t == nullptr or lo <= t[b] <= hi, else f (gdx_set_guidance_compose's
-// 3-pass rule); grid.y = sample, so B <= 65535; out may alias f, m or u
+// 3-pass rule); rule = COMPOSE_PAG: g1 = u + s0[b]*(f - u) instead (gdx_set_attention_guidance's GDX_PAG_CFG, m = the perturbed
+// pass); grid.y = sample, so B <= 65535; out may alias f, m or u
+enum ComposeRule { COMPOSE_CHAIN = 0, COMPOSE_PAG = 1 };
 hipError_t launch_cfg_compose(const float* f, const float* m, const float* u, const float* s0, const float* s1, const int64_t* t,
-                              int64_t lo, int64_t hi, float* out, int B, int64_t per_sample, hipStream_t s);
+                              int64_t lo, int64_t hi, float* out, int B, int64_t per_sample, hipStream_t s, int rule = COMPOSE_CHAIN);
 
 // argument of update_tm_kernel (sampler.hip): one step of gdx_sample_loop's token-major fast path, filled by loops.hip
 struct UpdateTmDev {

@@ -34,7 +34,12 @@ struct CfgComposeDev {
 __device__ __forceinline__ float cfg_compose(float f, float m, float u, float s0, float s1) {
     return __fadd_rn(cfg_blend(m, u, s0), __fmul_rn(s1, __fsub_rn(f, m)));
 }
-template <bool VEC>
+// Perturbed-attention guidance stacked on classifier-free guidance (gdx.h gdx_set_attention_guidance, GDX_PAG_CFG), m = the
+// perturbed pass P: g = (u + s0*(f - u)) + s1*(f - m), rounded like the rule above
+__device__ __forceinline__ float cfg_compose_pag(float f, float m, float u, float s0, float s1) {
+    return __fadd_rn(cfg_blend(f, u, s0), __fmul_rn(s1, __fsub_rn(f, m)));
+}
+template <bool VEC, int RULE>
 __global__ __launch_bounds__(256) void cfg_compose_kernel(const CfgComposeDev a) {
     const long grp = (long)blockIdx.x * 256 + threadIdx.x;
     if (grp >= a.groups) return;
@@ -49,7 +54,8 @@ __global__ __launch_bounds__(256) void cfg_compose_kernel(const CfgComposeDev a)
         const f32x4 m = load4<VEC>(a.m, g.e0, g.nval), u = load4<VEC>(a.u, g.e0, g.nval);
         const float s0 = a.s0[g.b], s1 = a.s1[g.b];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) x0[i] = cfg_compose(x0[i], m[i], u[i], s0, s1);
+        for (int i = 0; i < 4; ++i)
+            x0[i] = RULE == COMPOSE_PAG ? cfg_compose_pag(x0[i], m[i], u[i], s0, s1) : cfg_compose(x0[i], m[i], u[i], s0, s1);
     }
     store4<VEC>(a.out, g.e0, g.nval, x0);
 }
@@ -194,11 +200,15 @@ hipError_t launch_cfg_blend(const float* c, const float* u, const float* scale, 
 }
 
 hipError_t launch_cfg_compose(const float* f, const float* m, const float* u, const float* s0, const float* s1, const int64_t* t,
-                              int64_t lo, int64_t hi, float* out, int B, int64_t per_sample, hipStream_t s) {
+                              int64_t lo, int64_t hi, float* out, int B, int64_t per_sample, hipStream_t s, int rule) {
     CfgComposeDev d{(long)per_sample, (long)(per_sample + 3) / 4, f, m, u, s0, s1, t, lo, hi, out};
     if (B <= 0 || per_sample <= 0) return hipSuccess;
     const dim3 grid((unsigned)((d.groups + 255) / 256), (unsigned)B);
-    launch_vec(vec_ok(d.per_sample, f, m, u, out), cfg_compose_kernel<true>, cfg_compose_kernel<false>, grid, dim3(256), s, d);
+    const bool vec = vec_ok(d.per_sample, f, m, u, out);
+    if (rule == COMPOSE_PAG)
+        launch_vec(vec, cfg_compose_kernel<true, COMPOSE_PAG>, cfg_compose_kernel<false, COMPOSE_PAG>, grid, dim3(256), s, d);
+    else
+        launch_vec(vec, cfg_compose_kernel<true, COMPOSE_CHAIN>, cfg_compose_kernel<false, COMPOSE_CHAIN>, grid, dim3(256), s, d);
     return hipGetLastError();
 }
 }  // namespace gdx

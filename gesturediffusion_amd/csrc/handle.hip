@@ -236,6 +236,8 @@ extern "C" int gdx_get_tap(gdx_handle_t h, int32_t which, float* out, int64_t co
 static int finish_condition(gdx_model* h, const float* mfcc, hipStream_t s) {
     const int B = h->B, T = h->T, S = h->S, d = h->d;
     const int GB = h->G * B, rows = (h->u_group() + 1) * B;
+    // perturbed-attention guidance: group 1 = P has the conditioning rows of F (gdx_set_attention_guidance)
+    if (h->pag()) HIPCHK(hipMemcpyAsync(h->seed_cat + (size_t)B * d, h->seed_cat, sizeof(float) * B * d, hipMemcpyDeviceToDevice, s));
     if (h->cfg.arch == GDX_ARCH_MDM_OLD) {
         // addend[b, t+1, :] = W_in[:, J:] mfcc[b,:,t] + b_in + pe[t+1]      (model/mdm_old.py:104-112)
         HIPCHK(launch_mfcc_project(mfcc, h->in_mfcc.w, h->in_mfcc.kpad, h->in_x.bias, h->pe, h->addend, GB, B,
@@ -259,11 +261,11 @@ extern "C" int gdx_set_condition(gdx_handle_t h, const float* seed, const float*
     if (!h->B) return fail("gdx_set_condition: call gdx_prepare first");
     hipStream_t s = (hipStream_t)stream;
     const int B = h->B, d = h->d;
-    // cond rows 0..B-1: Linear(flat seed); uncond rows B..2B-1: Linear(0) = bias   (model/mdm.py:125-127,242-250)
+    // cond rows 0..B-1: Linear(flat seed); uncond rows (group u_group()): Linear(0) = bias   (model/mdm.py:125-127,242-250)
     HIPCHK(launch_small_linear(seed, h->J * h->cfg.seed_poses, h->seed.w, h->seed.kpad, h->seed.bias, h->seed_cat, d, B,
                                d, h->J * h->cfg.seed_poses, 0, s));
     for (int b = 0; b < B; ++b)
-        HIPCHK(hipMemcpyAsync(h->seed_cat + (size_t)(B + b) * d, h->seed.bias, sizeof(float) * d,
+        HIPCHK(hipMemcpyAsync(h->seed_cat + (size_t)(h->u_group() * B + b) * d, h->seed.bias, sizeof(float) * d,
                               hipMemcpyDeviceToDevice, s));
     return finish_condition(h, mfcc, s);
 }
@@ -326,6 +328,27 @@ extern "C" int gdx_set_guidance_compose(gdx_handle_t h, int32_t mode) {
     h->cond_set = false;
     forget_stored(h);
     return h->G == h->groups() ? 0 : reprepare(h);
+}
+
+// Perturbed-attention guidance (gdx.h): what a guided call contrasts F with, and the layers whose attention map P replaces by the
+// identity.  Refusals precede any HIP call and leave the handle as it was
+extern "C" int gdx_set_attention_guidance(gdx_handle_t h, int32_t kind, uint64_t layer_mask) {
+    if (!h) return fail("gdx_set_attention_guidance: null handle");
+    if (kind < GDX_PAG_OFF || kind > GDX_PAG_CFG) return fail("gdx_set_attention_guidance: unknown kind");
+    if (kind != GDX_PAG_OFF && h->L > 64) return fail("gdx_set_attention_guidance: layer_mask names 64 layers, this handle has more");
+    if (h->L < 64 && (layer_mask >> h->L))
+        return fail("gdx_set_attention_guidance: layer_mask names a layer beyond num_layers = " + std::to_string(h->L));
+    const int u_before = h->u_group();
+    h->pag_kind = kind; h->pag_mask = layer_mask;
+    if (h->u_group() != u_before) h->cond_set = false;            // the rows of U, and of P, change place
+    forget_stored(h);
+    return h->G == h->groups() ? 0 : reprepare(h);
+}
+
+int gdx::pag_conflict(const gdx_model* h, const char* who, int mode) {
+    if (mode != GDX_CFG || h->pag_kind == GDX_PAG_OFF || h->guide_compose == GDX_GUIDE_JOINT) return 0;
+    return fail(std::string(who) + ": perturbed-attention guidance (gdx_set_attention_guidance) adds a row group to a guided call, and "
+                                   "four are not supported: set the compose mode to GDX_GUIDE_JOINT (gdx_set_guidance_compose)");
 }
 
 // Guidance rescale (gdx.h): per-handle phi, 0 = off.  Refusals precede any HIP call.
@@ -441,6 +464,8 @@ extern "C" int gdx_forward_flops(gdx_handle_t h, int32_t mode, double* flops) {
         f += 2 * B * T * (J + mf) * d;
     f += h->L * (2 * N * d * 3 * d + 4 * B * S * S * d + 2 * N * d * d + 4 * N * d * ff);
     f += 2 * B * T * d * J;
+    // perturbed-attention guidance: group P's rows skip QK^T, the softmax and PV in the masked layers
+    if (mode == GDX_CFG && h->pag()) f -= __builtin_popcountll(h->pag_mask) * (4.0 * h->B * S * S * d);
     *flops = f;
     return 0;
 }

@@ -18,6 +18,7 @@ static PlanRule plan_rule(const gdx_model* h) { return {h->guide_lo, h->guide_hi
 // A guided loop of entry `who` on a handle in a 3-pass compose mode (gdx.h gdx_set_guidance_compose): the refresh's stored
 // difference and the layer cache's stored change are written for two row groups, so either is refused, before the first launch
 static int compose_conflict(const gdx_model* h, const char* who, int mode) {
+    if (pag_conflict(h, who, mode)) return -1;
     if (mode != GDX_CFG || !h->three_pass()) return 0;
     if (h->guide_every > 1)
         return fail(std::string(who) + ": the guidance refresh (gdx_set_guidance_refresh, every > 1) stores one cond-uncond difference; a "
@@ -139,7 +140,7 @@ extern "C" int gdx_bpd_loop(gdx_handle_t h, const gdx_bpd_loop_args_t* a, void* 
     if (check_ready(h, "gdx_bpd_loop") || refuse_resampling(h, "gdx_bpd_loop")) return -1;
     if (!a->coef || !a->timestep_map || !a->x_start || !a->vb || !a->xstart_mse || !a->mse)
         return fail("gdx_bpd_loop: null argument");
-    if (check_mode("gdx_bpd_loop", a->mode, a->scale)) return -1;
+    if (check_mode("gdx_bpd_loop", a->mode, a->scale) || pag_conflict(h, "gdx_bpd_loop", a->mode)) return -1;
     if (a->num_steps <= 0 || a->k_base < 0 || a->k_base >= a->num_steps || a->run_steps < 0 || a->k_base + a->run_steps > a->num_steps)
         return fail("gdx_bpd_loop: bad step range");
     if (a->inpaint_mask && !a->inpaint_motion) return fail("gdx_bpd_loop: mask without motion");
@@ -328,7 +329,7 @@ extern "C" int gdx_ddim_reverse_loop(gdx_handle_t h, int32_t mode, int32_t num_s
     if (num_steps <= 0 || first_index < 0 || first_index >= num_steps || run_steps < 1 || run_steps > num_steps - first_index)
         return fail(w + "bad step range");
     if (inpaint_mask && !inpaint_motion) return fail(w + "mask without motion");
-    if (check_ready(h, who) || refuse_resampling(h, who)) return -1;
+    if (check_ready(h, who) || refuse_resampling(h, who) || pag_conflict(h, who, mode)) return -1;
     if (h->B > 65535) return fail(w + "batch exceeds 65535");
     if (h->guide_every > 1)
         return fail(w + "the guidance refresh (gdx_set_guidance_refresh, every > 1) does not apply to the inversion: its numbering of "
@@ -378,6 +379,7 @@ extern "C" int gdx_parallel_loop(gdx_handle_t h, int32_t kind, int32_t mode, int
     if (h->lc_every > 1)
         return fail(w + "the layer cache (gdx_set_layer_cache, every > 1) needs memory across sequential denoiser calls; the "
                         "window's calls are not sequential: set every = 1");
+    if (pag_conflict(h, who, mode)) return -1;
     if (mode == GDX_CFG && h->three_pass())
         return fail(w + "a 3-pass guidance compose mode (gdx_set_guidance_compose) is not supported by the parallel loop, whose "
                         "window repeats one scale per slot: use GDX_GUIDE_JOINT, _TEXT or _SEED");

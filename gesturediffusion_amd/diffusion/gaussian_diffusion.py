@@ -554,7 +554,8 @@ class GaussianDiffusion:
             from ..model.mdm import _window_error
             raise _window_error(T, 10)
         guided = isinstance(model, ClassifierFreeSampleModel)
-        options = sampling_options.read(y, guided=guided, num_layers=inner.num_layers, use_text=getattr(inner, "use_text", False))
+        options = sampling_options.read(y, guided=guided, num_layers=inner.num_layers, use_text=getattr(inner, "use_text", False),
+                                        pag_only=getattr(model, "pag_only", False))
         options.refuse_conflicts(parallel=window is not None)
         eng = inner._get_engine(x.device)
         options.apply_before_condition(eng)
@@ -565,7 +566,7 @@ class GaussianDiffusion:
             eng.prepare_window(B, T, window, y["seed"], y["mfcc"], text=inner._text_features(y, B))
         options.apply_after_condition(eng)           # at every loop: every loop starts with a refresh and a full call
         if guided:
-            mode, scale = GDX_CFG, E.f32c(options.scale_operand(y["scale"]), "y['scale']")
+            mode, scale = GDX_CFG, E.f32c(options.scale_operand(y.get("scale") if model.pag_only else y["scale"]), "y['scale']")
         else:
             mode, scale = (GDX_UNCOND if y.get("uncond", False) else GDX_COND), None
         mask = motion = None

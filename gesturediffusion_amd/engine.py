@@ -98,6 +98,7 @@ class Engine:
         self._cond_key = None
         self._weights_key = None
         self._compose = _lib.GDX_GUIDE_JOINT   # the handle's gdx_set_guidance_compose mode
+        self._attention = (_lib.GDX_PAG_OFF, 0)   # ... and its gdx_set_attention_guidance (kind, layer mask)
         self._keep = []            # tensors that must outlive enqueued work
 
     def __del__(self):
@@ -183,14 +184,27 @@ class Engine:
         lo, hi = interval if interval is not None else (_lib.INT64_MIN, _lib.INT64_MAX)
         _lib.check(self.lib.gdx_set_guidance_interval(self.handle, lo, hi), self.lib)
 
-    def set_guidance_compose(self, mode=_lib.GDX_GUIDE_JOINT):
-        """Which passes a guided call contrasts (gdx_set_guidance_compose; GDX_GUIDE_*, JOINT = today's cond / uncond pair).  Set
-        in front of prepare / set_condition on every call, so a handle never keeps an earlier call's mode; a change clears the
-        conditioning (the rows depend on the mode), the same mode again is no call at all."""
+    def set_guidance_compose(self, mode=_lib.GDX_GUIDE_JOINT, attention=(_lib.GDX_PAG_OFF, 0)):
+        """Which passes a guided call contrasts (gdx_set_guidance_compose; GDX_GUIDE_*, JOINT = today's cond / uncond pair), and
+        `attention` = (kind, layer mask), whether one of them is the perturbed-attention pass (set_attention_guidance).  Set
+        in front of prepare / set_condition on every call, so a handle never keeps an earlier call's mode or kind; a change clears
+        the conditioning (the rows depend on both), the same mode again is no call at all."""
+        self.set_attention_guidance(*attention)
         if mode == self._compose:
             return
         _lib.check(self.lib.gdx_set_guidance_compose(self.handle, int(mode)), self.lib)
         self._compose = mode
+        self._cond_key = None
+
+    def set_attention_guidance(self, kind=_lib.GDX_PAG_OFF, layer_mask=0):
+        """Perturbed-attention guidance (gdx_set_attention_guidance): GDX_PAG_ONLY contrasts the conditional pass with one whose
+        self-attention map is the identity in the encoder layers of layer_mask (bit l = layer l), GDX_PAG_CFG adds that pass to
+        the cond / uncond pair as a third; GDX_PAG_OFF = neither.  A change clears the conditioning; the same setting again is no
+        call at all.  A refused call leaves handle and engine as they were."""
+        if (kind, layer_mask) == self._attention:
+            return
+        _lib.check(self.lib.gdx_set_attention_guidance(self.handle, int(kind), int(layer_mask)), self.lib)
+        self._attention = (kind, layer_mask)
         self._cond_key = None
 
     def set_guidance_rescale(self, phi=0.0):
@@ -465,6 +479,60 @@ def guidance_compose_of(y, guided_model, use_text=True):
     return GUIDANCE_ORDERS[order], require_device(ts, "y['text_scale']")
 
 
+PAG_KEYS = ("pag_scale", "pag_layers")
+PAG_OFF = (_lib.GDX_PAG_OFF, 0, None)
+
+
+def attention_guidance_of(y, guided_model, num_layers, pag_only=False):
+    """y['pag_scale'] / y['pag_layers'] validated -> (kind, layer_mask, pag_scale): the arguments of gdx_set_attention_guidance and
+    the PAG scales w, a floating device tensor [B].  Without either key: PAG_OFF.  pag_scale turns perturbed-attention guidance on;
+    pag_layers, a tuple or list of distinct Python ints in 0 .. num_layers - 1, names the encoder layers whose attention map the
+    contrast pass replaces by the identity (default: the middle layer, num_layers // 2).  Under a ClassifierFreeSampleModel
+    (`guided_model` True) the kind is GDX_PAG_CFG, three passes; under a PerturbedAttentionSampleModel (`pag_only`) it is
+    GDX_PAG_ONLY, pag_scale is required and the keys of classifier-free guidance are refused.  ValueError for a key on a plain
+    MDM / MDM_Old, for pag_layers without pag_scale, for pag_scale together with guidance_drop other than "both" or with text_scale,
+    and for a wrong type, shape or layer."""
+    present = [k for k in PAG_KEYS if k in y]
+    if not present:
+        if pag_only:
+            raise ValueError("PerturbedAttentionSampleModel needs y['pag_scale'], a floating tensor [batch]: it runs no other guidance")
+        return PAG_OFF
+    if not guided_model:
+        raise ValueError(f"y['{present[0]}'] needs a PerturbedAttentionSampleModel or a ClassifierFreeSampleModel: this model runs no "
+                         f"guidance")
+    if "pag_scale" not in y:
+        raise ValueError("y['pag_layers'] needs y['pag_scale']: the layers say where the pass is perturbed, the scale turns it on")
+    if pag_only:
+        for key in ("scale", "guidance_drop", "text_scale", "guidance_order"):
+            if key in y:
+                raise ValueError(f"y['{key}'] belongs to classifier-free guidance, which a PerturbedAttentionSampleModel does not run: "
+                                 f"wrap the model in ClassifierFreeSampleModel to stack both (y['scale'] and y['pag_scale'])")
+    else:
+        if y.get("guidance_drop", "both") != "both":
+            raise ValueError("y['pag_scale'] and y['guidance_drop'] other than 'both' exclude each other: the perturbed pass takes the "
+                             "place of the pass with one condition dropped")
+        if "text_scale" in y:
+            raise ValueError("y['pag_scale'] and y['text_scale'] exclude each other: each adds a third pass, and four are not supported")
+    ps = y["pag_scale"]
+    if not isinstance(ps, torch.Tensor) or not ps.is_floating_point():
+        raise ValueError(f"y['pag_scale'] must be a floating tensor [batch], got {type(ps).__name__ if not isinstance(ps, torch.Tensor) else ps.dtype}")
+    like = y.get("seed") if pag_only else y.get("scale")
+    batch = (like.shape[0] if pag_only else like.numel()) if isinstance(like, torch.Tensor) else None
+    if ps.dim() != 1 or (batch is not None and ps.numel() != batch):
+        raise ValueError(f"y['pag_scale'] must be [batch], got {list(ps.shape)}")
+    layers = y.get("pag_layers", (num_layers // 2,))
+    if isinstance(layers, torch.Tensor):
+        raise ValueError("y['pag_layers'] must be a tuple or list of Python ints, not a tensor: reading it would synchronise")
+    ok = (isinstance(layers, (tuple, list)) and len(layers) > 0
+          and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in layers))
+    if not ok:
+        raise ValueError(f"y['pag_layers'] must be a non-empty tuple or list of Python ints, got {layers!r}")
+    if len(set(int(v) for v in layers)) != len(layers) or not all(0 <= v < min(num_layers, 64) for v in layers):
+        raise ValueError(f"y['pag_layers'] must name distinct encoder layers in 0 .. num_layers - 1 = {num_layers - 1}, got {layers!r}")
+    mask = sum(1 << int(v) for v in layers)
+    return (_lib.GDX_PAG_ONLY if pag_only else _lib.GDX_PAG_CFG), mask, require_device(ps, "y['pag_scale']")
+
+
 def guidance_rescale_of(y, guided_model):
     """y['guidance_rescale'] validated -> phi, a Python float with 0 <= phi <= 1 (0.0 when the key is absent: off).  ValueError
     for anything but a finite Python float or int in that range -- a bool is refused, and a tensor because reading it would
@@ -541,6 +609,15 @@ def cfg_delta(a, b, out=None, count=None):
     args = _lib.CfgDeltaArgs(count=a.numel() if count is None else count, a=a.data_ptr(), b=b.data_ptr(), out=out.data_ptr())
     _lib.check(lib.gdx_cfg_delta(C.byref(args), _stream(a.device)), lib)
     return out
+
+
+def attention_identity(qkv, ctx):
+    """The stand-alone gdx_attention_identity on device tensors taken as they are (no copies: tests hand it misaligned views):
+    qkv [rows, 3 * d] -> ctx [rows, d] = the V third, a bit copy in the tensors' element size.  Synchronous with the device."""
+    lib = _lib.load()
+    rows, d = ctx.shape
+    _lib.check(lib.gdx_attention_identity(ctx.element_size(), rows, d, qkv.data_ptr(), ctx.data_ptr()), lib)
+    return ctx
 
 
 def layer_delta(op, inp, outc, delta):

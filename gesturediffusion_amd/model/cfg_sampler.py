@@ -15,6 +15,8 @@ between guided calls; this forward has no memory and raises ValueError for k > 1
 For a use_text model `y['guidance_drop']` ("both" | "text" | "seed") names what the contrast pass drops, and `y['text_scale']`
 ([B], with `y['guidance_order']`) steers the two conditions on their own in three passes (engine.guidance_compose_of).
 Every key is one entry of sampling_options.OPTIONS, the table through which this forward and the loops read them.
+Perturbed-attention guidance (pag_scale, pag_layers: engine.attention_guidance_of) is read beside the table: with it this
+wrapper runs three passes, model/pag_sampler.py's subclass the conditional and the perturbed pass alone.
 """
 import torch.nn as nn
 
@@ -24,10 +26,12 @@ from .mdm import _NativeDenoiser
 
 
 class ClassifierFreeSampleModel(nn.Module):
+    pag_only = False               # model/pag_sampler.py: the subclass whose one contrast pass is the perturbed-attention pass
+
     def __init__(self, model):
         super().__init__()
         self.model = model
-        assert self.model.cond_mask_prob > 0, \
+        assert self.pag_only or self.model.cond_mask_prob > 0, \
             'Cannot run a guided diffusion on a model that has not been trained with no conditions'
         if not isinstance(model, _NativeDenoiser):
             raise TypeError("ClassifierFreeSampleModel wraps gesturediffusion_amd MDM / MDM_Old instances")
@@ -40,7 +44,7 @@ class ClassifierFreeSampleModel(nn.Module):
         m = self.model
         m._check_inputs(x, y)
         bs, njoints, nfeats, nframes = x.shape
-        scale = y["scale"]
+        scale = y.get("scale") if self.pag_only else y["scale"]     # the subclass reads y['pag_scale'] instead (scale_operand)
         y_c = dict(y)
         y_c.pop("uncond", None)
         # argument validation identical to a plain forward (raises the same errors)
@@ -52,7 +56,8 @@ class ClassifierFreeSampleModel(nn.Module):
             raise _window_error(nframes, 10)
         if m.data_rep != "genea_vec":
             raise NotImplementedError
-        options = sampling_options.read(y, guided=True, num_layers=m.num_layers, use_text=getattr(m, "use_text", False))
+        options = sampling_options.read(y, guided=True, num_layers=m.num_layers, use_text=getattr(m, "use_text", False),
+                                        pag_only=self.pag_only)
         options.refuse_memory("the step-wise forward of ClassifierFreeSampleModel")
         eng = m._get_engine(x.device)
         options.apply_before_condition(eng)

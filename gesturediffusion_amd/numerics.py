@@ -28,6 +28,17 @@ def guidance_factor(scale):
     return abs(s) + abs(1.0 - s)
 
 
+def pag_factor(pag_scale, scale=None):
+    """The triangle factor of the perturbed-attention rules (include/gdx.h gdx_set_attention_guidance) over their forwards, whose
+    rounding errors are independent.  GDX_PAG_ONLY (scale None), g = P + (1 + w)(F - P) = (1 + w) F - w P: |1 + w| + |w|.
+    GDX_PAG_CFG, g = U + s (F - U) + w (F - P) = (1 - s) U + (s + w) F - w P: |1 - s| + |s + w| + |w|."""
+    w = float(pag_scale)
+    if scale is None:
+        return abs(1.0 + w) + abs(w)
+    s = float(scale)
+    return abs(1.0 - s) + abs(s + w) + abs(w)
+
+
 def stated_tolerance(compute_dtype, guidance_scale=None, loop=True):
     """The tolerance the mode states for a forward (loop=False) or a whole sampling loop, relative to max|reference|.
     guidance_scale: the largest classifier-free guidance scale of the batch (None: no ClassifierFreeSampleModel)."""

@@ -35,6 +35,7 @@ import torch
 
 from .. import engine as E
 from ..model.cfg_sampler import ClassifierFreeSampleModel
+from ..model.pag_sampler import PerturbedAttentionSampleModel
 from ..sampling_options import y_of_kwargs
 from ..utils import dist_util
 from ..utils.fixseed import fixseed
@@ -62,7 +63,7 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
                   on_chunk=None, plms_order=2, dpm_order=2, guidance_interval=None, guidance_rescale=0.0,
                   guidance_refresh=1, unipc_order=2, invert_of_chunk=None, report=None, text_of_chunk=None,
                   layer_cache=None, parallel=None, text_guidance_param=None, guidance_order=None, guidance_drop=None,
-                  inpaint_of_chunk=None, resample=None):
+                  inpaint_of_chunk=None, resample=None, pag_scale=None, pag_layers=None):
     """The chunked autoregressive driver of reference `sample/generate.py:91-130`: chunk c is one complete sampling loop
     conditioned on its MFCCs and on seed poses that are `first_seed` for c = 0 and afterwards the LAST `seed_poses` frames
     of chunk c-1 -- a view of the previous output that stays on the device (`:104-107`).  Yields nothing; returns the list
@@ -88,7 +89,13 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
     stage at S and the seed stage at guidance_param (y['text_scale']), guidance_order saying which comes first (y['guidance_order']).
     inpaint_of_chunk(c) -> (mask bool, motion) [b, J, 1, frames] on the device: chunk c's y['inpainting_mask'] / y['inpainted_motion'];
     the seed hand-off is unchanged.  resample (jump, repeats): every chunk's loop resamples (repaint_sample_loop; samplers "p" and
-    "ddim"; neither guidance_refresh > 1, layer_cache, parallel nor invert_of_chunk); a recorded tape then holds one entry per hop."""
+    "ddim"; neither guidance_refresh > 1, layer_cache, parallel nor invert_of_chunk); a recorded tape then holds one entry per hop.
+    pag_scale W: perturbed-attention guidance (y['pag_scale'], with pag_layers as y['pag_layers']; the loops validate both): with
+    guidance_param == 1 the model is a PerturbedAttentionSampleModel and this is the run's guidance -- interval, rescale and
+    refresh then apply to it --, otherwise it is the third pass of a ClassifierFreeSampleModel."""
+    guided = guidance_param != 1 or pag_scale is not None
+    if pag_layers is not None and pag_scale is None:
+        raise ValueError("pag_layers needs pag_scale")
     if resample is not None:
         if sampler not in ("p", "ddim"):
             raise ValueError("resample needs sampler='p' or 'ddim': a multistep sampler's history does not survive a jump")
@@ -111,13 +118,13 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
         raise ValueError("invert_of_chunk needs sampler='ddim': the latent is the start state of the deterministic DDIM loop")
     if invert_of_chunk is not None and guidance_refresh > 1:
         raise ValueError("invert_of_chunk runs no guidance refresh")
-    if guidance_interval is not None and guidance_param == 1:
+    if guidance_interval is not None and not guided:
         raise ValueError("guidance_interval needs guidance_param != 1: without guidance there is nothing to limit")
-    if guidance_rescale > 0 and guidance_param == 1:
+    if guidance_rescale > 0 and not guided:
         raise ValueError("guidance_rescale needs guidance_param != 1: without guidance there is nothing to rescale")
     if isinstance(guidance_refresh, bool) or not isinstance(guidance_refresh, int) or guidance_refresh < 1:
         raise ValueError(f"guidance_refresh must be an int >= 1, got {guidance_refresh!r}")
-    if guidance_refresh > 1 and guidance_param == 1:
+    if guidance_refresh > 1 and not guided:
         raise ValueError("guidance_refresh needs guidance_param != 1: without guidance there is nothing to refresh")
     b, J = first_seed.shape[0], first_seed.shape[1]
     sample_fn = {"p": diffusion.p_sample_loop, "ddim": diffusion.ddim_sample_loop, "plms": diffusion.plms_sample_loop,
@@ -134,6 +141,10 @@ def sample_chunks(model, diffusion, first_seed, mfcc_of_chunk, n_chunks, frames,
         if guidance_param != 1:
             y["scale"] = torch.ones(b, device=first_seed.device) * guidance_param
         y.update(y_of_kwargs(options, b, first_seed.device))
+        if pag_scale is not None:
+            y["pag_scale"] = torch.ones(b, device=first_seed.device) * pag_scale
+            if pag_layers is not None:
+                y["pag_layers"] = tuple(int(l) for l in pag_layers)
         if inpaint_of_chunk is not None:
             y["inpainting_mask"], y["inpainted_motion"] = inpaint_of_chunk(chunk)
         kw = dict(clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=0, init_image=None, progress=progress,
@@ -324,6 +335,8 @@ def main(argv=None):
         model.load_state_dict(init_state_dict(cfg, seed=args.seed), strict=False)
     if args.guidance_param != 1:
         model = ClassifierFreeSampleModel(model)
+    elif args.pag_scale is not None:
+        model = PerturbedAttentionSampleModel(model)
     model.to(device)
     model.eval()
 
@@ -407,13 +420,15 @@ def main(argv=None):
     if args.text_guidance_param is not None and rank == 0:
         print(f"### per-condition guidance ({args.guidance_order or 'seed_text'}): seed scale {args.guidance_param:g}, text scale "
               f"{args.text_guidance_param:g}, three passes per guided step")
+    if args.pag_scale is not None and rank == 0:
+        print(f"### perturbed-attention guidance: scale {args.pag_scale:g} on layers {list(args.pag_layers)}")
     if args.guidance_drop is not None and rank == 0:
         print(f"### guidance contrast pass drops: {args.guidance_drop}")
     if args.guidance_refresh > 1 and rank == 0:
         plan = diffusion.guidance_plan(interval, args.guidance_refresh, plms=args.sampler == "plms")
         print(f"### unconditional pass on {plan.count('refresh')} of {len(plan) - plan.count('off')} guided calls")
     if args.layer_cache is not None and rank == 0:
-        plan = diffusion.layer_cache_plan(args.layer_cache, interval, args.guidance_refresh, guided=args.guidance_param != 1,
+        plan = diffusion.layer_cache_plan(args.layer_cache, interval, args.guidance_refresh, guided=args.guidance_param != 1 or args.pag_scale is not None,
                                           plms=args.sampler == "plms")
         print(f"### layer cache: {plan.count('full')} full, {plan.count('partial')} partial calls; "
               f"{args.layer_cache[1]} of {args.layers} layers on a partial call")
@@ -427,7 +442,8 @@ def main(argv=None):
                          text_of_chunk=text_of_chunk, layer_cache=args.layer_cache, text_guidance_param=args.text_guidance_param,
                          guidance_order=args.guidance_order, guidance_drop=args.guidance_drop,
                          parallel=(args.parallel_window, args.parallel_tolerance) if args.parallel_window else None,
-                         inpaint_of_chunk=inpaint_of_chunk, resample=args.resample)
+                         inpaint_of_chunk=inpaint_of_chunk, resample=args.resample, pag_scale=args.pag_scale,
+                         pag_layers=args.pag_layers)
     out_chunks, rot_chunks = [], []
     for sample_out in outs:
         full = dist_util.gather_samples(sample_out, num_samples)

@@ -22,7 +22,8 @@ OPTIONS = (
     Option("rescale", ("guidance_rescale",), lambda y, guided, L, text: E.guidance_rescale_of(y, guided), 0.0, True, None,
            lambda eng, v: eng.set_guidance_rescale(v), False),
     Option("compose", E.COMPOSE_KEYS, lambda y, guided, L, text: E.guidance_compose_of(y, guided, text),
-           (_lib.GDX_GUIDE_JOINT, None), True, None, lambda eng, v: eng.set_guidance_compose(v[0]), True),
+           (_lib.GDX_GUIDE_JOINT, None), True, None,
+           lambda eng, v, attention=E.PAG_OFF[:2]: eng.set_guidance_compose(v[0], attention=attention), True),
     Option("refresh", ("guidance_refresh",), lambda y, guided, L, text: E.guidance_refresh_of(y, guided), 1, True,
            (lambda v: v, "the guidance difference"), lambda eng, v: eng.set_guidance_refresh(v), False),
     Option("layer_cache", ("layer_cache",), lambda y, guided, L, text: E.layer_cache_of(y, L), (1, 0), False,
@@ -36,11 +37,24 @@ AFTER_WITHOUT_MEMORY = tuple(o for o in AFTER if not o.memory)
 PLAIN_FORWARD = tuple(o for o in OPTIONS if o.name != "refresh")    # MDM / MDM_Old.forward never looked at y['guidance_refresh']
 
 
-def read(y, *, guided, num_layers, use_text, options=OPTIONS):
+# Perturbed-attention guidance, y['pag_scale'] / y['pag_layers'], is read beside the table: what the keys mean depends on the
+# wrapper (ClassifierFreeSampleModel: a third pass; PerturbedAttentionSampleModel: the only contrast, `pag_only`), which the
+# table's validators are not told, and its setting travels with the compose mode's setter call (Engine.set_guidance_compose), the
+# other half of "which passes a guided call runs".  A reader of a part of the table (`options`) reads it too unless the part is
+# MEMORY: the plain forwards refuse the keys like every other key of a guided model.
+ATTENTION_KEYS = frozenset(E.PAG_KEYS)
+
+
+def read(y, *, guided, num_layers, use_text, options=OPTIONS, pag_only=False):
     """`options` of y validated, in the table's order -> Record.  guided: the model is a ClassifierFreeSampleModel; num_layers,
-    use_text: its denoiser's.  ValueError as the validators raise it; nothing is read from the device.  A y without any of the
-    keys, the usual one of a step-wise loop's thousand calls, is every option "off" without a validator call."""
-    return Record(OFF if KEYS.isdisjoint(y) else {o.name: o.validate(y, guided, num_layers, use_text) for o in options})
+    use_text: its denoiser's; pag_only: it is a PerturbedAttentionSampleModel.  ValueError as the validators raise it; nothing is
+    read from the device.  A y without any of the keys, the usual one of a step-wise loop's thousand calls, is every option "off"
+    without a validator call."""
+    values = OFF if KEYS.isdisjoint(y) else {o.name: o.validate(y, guided, num_layers, use_text) for o in options}
+    attention = E.PAG_OFF
+    if options is not MEMORY and (pag_only or not ATTENTION_KEYS.isdisjoint(y)):
+        attention = E.attention_guidance_of(y, guided, num_layers, pag_only)
+    return Record(values, attention)
 
 
 class Record:
@@ -48,8 +62,9 @@ class Record:
     every, layer_cache (every, keep)) of the options that were read; never written to."""
     after = AFTER                                  # the options apply_after_condition sets
 
-    def __init__(self, values):
+    def __init__(self, values, attention=E.PAG_OFF):
         self.values = values
+        self.attention = attention                 # (kind, layer mask, pag_scale) of engine.attention_guidance_of
 
     def refuse_memory(self, who):
         """For `who`, a path that makes every denoiser call on its own: ValueError for an option that needs memory across calls.
@@ -65,6 +80,16 @@ class Record:
     def refuse_conflicts(self, parallel=False):
         """A 3-pass mode runs three row groups; the guidance refresh and the layer cache are written for two, and the window of
         parallel_sample_loop (`parallel`) repeats one scale per slot (gdx.h)."""
+        if self.attention[0] == _lib.GDX_PAG_CFG:
+            if parallel:
+                raise ValueError("y['pag_scale'] with y['scale'] (3-pass guidance) is not supported by parallel_sample_loop, whose "
+                                 "window repeats one scale per slot: use a PerturbedAttentionSampleModel")
+            if self.values["refresh"] > 1:
+                raise ValueError("y['pag_scale'] with y['scale'] (3-pass guidance) and y['guidance_refresh'] > 1 exclude each other: "
+                                 "the refresh stores one cond-uncond difference")
+            if self.values["layer_cache"][0] > 1:
+                raise ValueError("y['pag_scale'] with y['scale'] (3-pass guidance) and y['layer_cache'] with every > 1 exclude each "
+                                 "other: the cache holds two row groups")
         if self.values["compose"][0] < _lib.GDX_GUIDE_SEED_TEXT:
             return
         if parallel:
@@ -78,9 +103,9 @@ class Record:
                              "holds two row groups")
 
     def apply_before_condition(self, eng):
-        """In front of prepare / set_condition, for a record of all OPTIONS; absent keys set JOINT."""
+        """In front of prepare / set_condition, for a record of all OPTIONS; absent keys set JOINT and no perturbed pass."""
         for o in BEFORE:
-            o.setter(eng, self.values[o.name])
+            o.setter(eng, self.values[o.name], attention=self.attention[:2])
 
     def apply_after_condition(self, eng):
         """Behind set_condition; absent keys set "off" (every timestep, phi 0, every 1), so a reused handle is reset."""
@@ -89,9 +114,15 @@ class Record:
 
     def scale_operand(self, scale):
         """The `scale` operand of a guided call: y['scale'] flattened [B], or in a 3-pass mode [2, B] in stage order -- row 0 the
-        scale of the condition stepped to first, row 1 the other's (gdx_set_guidance_compose)."""
+        scale of the condition stepped to first, row 1 the other's (gdx_set_guidance_compose).  Under perturbed-attention guidance
+        (gdx_set_attention_guidance): 1 + y['pag_scale'] alone (`scale` is not read), or [y['scale'], y['pag_scale']] stacked."""
+        kind, _, pag_scale = self.attention
+        if kind == _lib.GDX_PAG_ONLY:                       # g = P + (1 + w)(F - P) = F + w(F - P); fl32(1 + w), computed once
+            return (1.0 + pag_scale.reshape(-1).float()).contiguous()
         mode, text_scale = self.values["compose"]
         scale = scale.reshape(-1).float()
+        if kind == _lib.GDX_PAG_CFG:                        # [2, B]: row 0 the CFG scale s0, row 1 the PAG scale s1
+            return torch.stack([scale, pag_scale.reshape(-1).float()]).contiguous()
         if text_scale is None:
             return scale.contiguous()
         text_scale = text_scale.reshape(-1).float()

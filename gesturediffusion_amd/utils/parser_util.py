@@ -44,15 +44,41 @@ def parse_and_load_from_model(parser, argv=None):
         args.data_dir = asked_data_dir
     if args.cond_mask_prob == 0:
         args.guidance_param = 1
-    if args.guidance_interval is not None and args.guidance_param == 1:
+    if args.pag_layers is not None and args.pag_scale is None:
+        parser.error("--pag_layers needs --pag_scale: the layers say where the pass is perturbed, the scale turns it on")
+    if args.pag_scale is not None:
+        layers = args.pag_layers if args.pag_layers is not None else [args.layers // 2]
+        if len(set(layers)) != len(layers) or not all(0 <= l < args.layers for l in layers):
+            parser.error(f"--pag_layers must name distinct encoder layers in 0 .. layers - 1 = {args.layers - 1}")
+        args.pag_layers = tuple(layers)
+        if args.text_guidance_param is not None:
+            parser.error("--pag_scale and --text_guidance_param exclude each other: each adds a third pass, and four are not supported")
+        if args.guidance_drop in ("text", "seed"):
+            parser.error("--pag_scale and --guidance_drop text|seed exclude each other: the perturbed pass takes the place of the "
+                         "pass with one condition dropped")
+        if args.invert_gt:
+            parser.error("--pag_scale does not combine with --invert_gt: the inversion is one conditional pass per step")
+        if args.guidance_param != 1:                             # three passes: the conflicts of --text_guidance_param
+            if args.guidance_refresh is not None and args.guidance_refresh > 1:
+                parser.error("--pag_scale with --guidance_param != 1 runs no guidance refresh: the refresh stores one cond-uncond "
+                             "difference (use --guidance_param 1)")
+            if args.layer_cache is not None and args.layer_cache[0] > 1:
+                parser.error("--pag_scale with --guidance_param != 1 runs no layer cache: the cache holds two row groups, this "
+                             "guidance runs three (use --guidance_param 1)")
+            if args.parallel_window:
+                parser.error("--pag_scale with --guidance_param != 1 does not combine with --parallel_window, whose window repeats "
+                             "one scale per slot (use --guidance_param 1)")
+    # perturbed-attention guidance guides without the unconditional pass: the options of a guided loop apply to it
+    unguided = args.guidance_param == 1 and args.pag_scale is None
+    if args.guidance_interval is not None and unguided:
         parser.error("--guidance_interval needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     if not 0 <= args.guidance_rescale <= 1:
         parser.error("--guidance_rescale must lie in [0, 1]")
-    if args.guidance_rescale > 0 and args.guidance_param == 1:
+    if args.guidance_rescale > 0 and unguided:
         parser.error("--guidance_rescale needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     if args.guidance_refresh is not None and args.guidance_refresh < 1:
         parser.error("--guidance_refresh must be at least 1")
-    if args.guidance_refresh is not None and args.guidance_param == 1:
+    if args.guidance_refresh is not None and unguided:
         parser.error("--guidance_refresh needs guidance: --guidance_param is 1 (no classifier-free guidance runs at all)")
     if args.guidance_refresh is None:
         args.guidance_refresh = 1
@@ -249,6 +275,15 @@ def add_native_options(parser):
                        help="--use_text: what the contrast pass of classifier-free guidance drops (default both, the "
                             "unconditional pass); text keeps the seed poses out of the extrapolation, seed the text. Two passes "
                             "per guided step under the one scale --guidance_param.")
+    group.add_argument("--pag_scale", default=None, type=float, metavar="W",
+                       help="Perturbed-attention guidance (Ahn et al. 2024): contrast the conditional pass with one whose "
+                            "self-attention map is the identity in the encoder layers --pag_layers, x0 = F + W (F - P). Needs no "
+                            "condition dropout: with --guidance_param 1 it is the only guidance (two passes per guided step), "
+                            "otherwise it is added to classifier-free guidance as a third pass. An error with "
+                            "--text_guidance_param, --guidance_drop text|seed and --invert_gt; in the 3-pass case also with "
+                            "--guidance_refresh > 1, --layer_cache and --parallel_window.")
+    group.add_argument("--pag_layers", default=None, type=int, nargs="+", metavar="L",
+                       help="--pag_scale: the perturbed encoder layers, distinct, 0 .. layers - 1 (default: the middle layer).")
     group.add_argument("--guidance_refresh", default=None, type=int, metavar="K",
                        help="Guidance refresh: run the unconditional pass only on every K-th guided denoiser call of a chunk's "
                             "loop and reuse the stored cond-uncond difference in between (1 = every call, the default). "

@@ -178,6 +178,39 @@ int gdx_set_condition_text(gdx_handle_t h, const float* seed, const float* mfcc,
 enum { GDX_GUIDE_JOINT = 0, GDX_GUIDE_TEXT = 1, GDX_GUIDE_SEED = 2, GDX_GUIDE_SEED_TEXT = 3, GDX_GUIDE_TEXT_SEED = 4 };
 int gdx_set_guidance_compose(gdx_handle_t h, int32_t mode);
 
+/* Perturbed-attention guidance (PAG; Ahn et al. 2024, arXiv:2403.17377; no counterpart in the reference).  The contrast pass P is
+ * the conditional forward F -- the same conditioning rows -- in which the self-attention map of chosen encoder layers is replaced
+ * by the identity: every token attends to itself alone, so ctx = V.  It needs no condition dropout at training time.  `kind`
+ * says what a guided call (GDX_CFG inside the guidance interval) runs, as row groups of ONE batch in the order given; every
+ * difference, product and sum is a separate fp32 operation in the order written:
+ *     GDX_PAG_OFF   the state after gdx_create: nothing new is launched, every result keeps its bits
+ *     GDX_PAG_ONLY  (F, P)     g = P + s*(F - P)                       scale [B]; s = 1 + w gives the paper's F + w*(F - P)
+ *     GDX_PAG_CFG   (F, P, U)  g = (U + s0*(F - U)) + s1*(F - P)       scale [2][B]: row 0 = s0 (CFG), row 1 = s1 (PAG)
+ * GDX_PAG_ONLY is the two-group guided call with P where U stood: the step kernels, the token-major path, graph replay, the
+ * refresh, the rescale and the layer cache apply unchanged with u := P.  GDX_PAG_CFG composes in place on the conditional third
+ * like the 3-pass modes of gdx_set_guidance_compose, runs 3 * batch samples, applies the guidance rescale with c = F, and has
+ * their conflicts: the refresh (every > 1), the layer cache (every > 1) and gdx_parallel_loop are refused before the first launch.
+ * Bit l of layer_mask: in encoder layer l the rows of group P get the identity (gdx_attention_identity) instead of
+ * self-attention; the attention kernels run on the other groups' rows only, and all other layers and rows run as without PAG.
+ * GDX_COND and GDX_UNCOND calls are never perturbed, nor is V2's local-attention front end; GDX_UNCOND reads U in every kind
+ * (the all-dropped rows are kept in group 2).  gdx_forward_flops leaves out the attention core of the perturbed (layer, group)
+ * pairs.  A guided call with kind != GDX_PAG_OFF on a handle whose compose mode is not GDX_GUIDE_JOINT is refused before its
+ * first launch (four row groups are not supported).
+ * gdx_set_attention_guidance: a null handle, an unknown kind, a mask bit >= num_layers, or num_layers > 64 with kind !=
+ * GDX_PAG_OFF is refused before any HIP call, and the handle stays as it was.  The call clears the stored guidance difference and
+ * layer change; when the place of the U rows changes (kind 0 <-> not 0) it clears the conditioning (condition again before the
+ * next forward), and when the number of row groups changes the workspace is prepared again at the current shape (allocates). */
+enum { GDX_PAG_OFF = 0, GDX_PAG_ONLY = 1, GDX_PAG_CFG = 2 };
+int gdx_set_attention_guidance(gdx_handle_t h, int32_t kind, uint64_t layer_mask);
+
+/* ctx[r][c] = qkv[r][2*d + c] for r < rows, c < d: what self-attention gives when its map is the identity, as a bit copy of
+ * elem_bytes-wide elements (4 = fp32, 2 = fp16 or bf16) in 128-bit accesses.  qkv is [rows][3*d], ctx [rows][d]; nothing outside
+ * rows * d elements of ctx is written.  A test entry of the kernel the forwards launch on their own stream: it takes none, waits
+ * for the device's pending work (the operands, on whatever stream they were written), runs on the null stream and returns when
+ * the copy is done.  Refused before the first HIP call: elem_bytes not 2 or 4, a null pointer, a non-positive size, d * elem_bytes
+ * not a multiple of 16, a pointer that is not 16-byte aligned. */
+int gdx_attention_identity(int32_t elem_bytes, int64_t rows, int32_t d, const void* qkv, void* ctx);
+
 /* Guidance interval (limited-interval guidance, Kynkaanniemi et al. 2024, arXiv:2404.07724; no counterpart in the reference):
  * the MODEL timesteps -- the values the denoiser sees after the respacing map, 0..999 for the reference's schedule -- at which
  * GDX_CFG means guidance, bounds inclusive.  Per-handle state like the conditioning; after gdx_create it is every timestep
